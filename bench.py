@@ -32,7 +32,15 @@ and prints the first rung's line that succeeds (`launcher.ladder` says what happ
 rung failed, a JSON line with "error" and exit code 2.  It never exits without a line.  Fewer than N devices
 visible: a line with "error", exit code 2, never a smaller job under an `n_gpus: N` label.
 
-Secondary objects in the same JSON line (N = 1 measures all of them):
+**Plain run and --full (N = 1).**  `python bench.py --gpus 1 --steps K --warmup W` does only what the headline needs: it builds
+the matrix, warms up, times K steps and prints the line (`metric`, `value`, `unit`, `ms_per_step`, `roofline` from the same steps'
+hipEvents, `compute`, `tuning`).  `--full` adds everything below: the secondary legs, the CPU baselines, the bitwise check of the
+last timed step against the oracle (`checked_vs_oracle`) and the counter passes; the `--no-*` switches leave single parts out of it.
+`--dump-outputs DIR` writes, after the timed steps, what the last one computed: DIR/jaccard_ut_sample.npy (float32, the condensed
+upper triangle at a fixed seeded sample of at most DUMP_VALUES positions; the inputs are seeded too, so two builds compare value
+for value).
+
+Secondary objects in the same JSON line (N = 1 with --full measures all of them):
   compute.matrices  the pair kernel on three matrices: unrelated sketches (1 id plane), the stated one,
                     and an adversarial one where every value occurs exactly twice per column
   sketch            K1 bases/s on BASELINE config 2's shape (1 000 x 5 Mbp, k=31, S=1024): synthetic
@@ -61,6 +69,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 VALU_PEAK_LANEOPS = 256 * 4 * 32 * 2.4e9   # 256 CU x 4 SIMD-32 x 2.4 GHz = 7.86e13 lane-ops/s
 PMC_FILE = os.path.join(ROOT, "profiles", "r06_pmc.json")   # tools/pmc_round.sh -> tools/pmc_summary.py: the fallback when rocprofv3 cannot run here
+DUMP_VALUES = 1 << 23          # --dump-outputs: at most 8 Mi float32 values (32 MiB) of the output
+DUMP_SEED = 20261016
 
 
 def parse_args():
@@ -74,6 +84,11 @@ def parse_args():
     ap.add_argument("--scaling", default=None, choices=["strong", "weak"],
                     help="N > 1: strong (default) = BASELINE config 4, fixed 50000 sketches; weak = 10000*sqrt(N) sketches")
     ap.add_argument("--sketchsize", type=int, default=1024)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline, also run the secondary legs, the CPU baselines, the oracle check of the timed step's "
+                         "output and the counter passes (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write the last timed step's output (a fixed seeded sample of it) to DIR/jaccard_ut_sample.npy")
     ap.add_argument("--no-config4", action="store_true", help="N = 1: skip the secondary config-4 (50000 sketches) run")
     ap.add_argument("--no-matrices", action="store_true", help="N = 1: skip the plane-count sensitivity runs")
     ap.add_argument("--no-sketch", action="store_true", help="skip the secondary K1 measurement")
@@ -1279,6 +1294,16 @@ def run_single(args):
         return dt
 
     dt = timed_run(step)
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the float32 condensed upper triangle of the last timed step, at the same seeded
+        # sorted positions in every run (all of them when the triangle has at most DUMP_VALUES pairs)
+        got = out[:pairs_total]
+        if pairs_total > DUMP_VALUES:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, pairs_total, DUMP_VALUES))
+            got = got[torch.from_numpy(idx).to(dev)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "jaccard_ut_sample.npy"), got.cpu().numpy())
+        del got
     nk2, k2_ms, _ = ctx.kernel_ms("k2")
     _, prep_ms, _ = ctx.kernel_ms("k2prep")
     max_distinct, nbits, mean_nbits = cs.planes(stream)
@@ -1844,7 +1869,13 @@ def main():
     if args.worker:                      # a measuring child of the supervisor (tests also run one directly at world size 1)
         return run_multi(args)
     if args.gpus > 1:
+        if args.dump_outputs:
+            print(json.dumps(error_line(args, "--dump-outputs is implemented for --gpus 1 only")), flush=True)
+            raise SystemExit(2)
         raise SystemExit(supervise(args))
+    if not args.full:
+        # a plain run times the headline and nothing else: every part that --full adds is left out
+        args.no_matrices = args.no_config4 = args.no_sketch = args.no_multiset = args.no_cpu_baseline = args.no_traffic = True
     run_single(args)
 
 

@@ -1015,3 +1015,26 @@ def test_k2_timed_sequence_at_config3_vs_oracle(gpu_ctx, d2g, oracle):
         for i in rows:
             np.testing.assert_array_equal(host[off[i]:off[i + 1]], want[i], err_msg=f"prepare {rep} row {i}")
     cs.close()
+
+
+def test_bench_plain_run_dumps_the_timed_steps_output(d2g, oracle, tmp_path):
+    """a plain `bench.py --gpus 1` run prints the headline line without any --full part, and --dump-outputs writes what its last timed step
+    computed: at N = 3000 (below DUMP_VALUES pairs) the whole float32 triangle, bit for bit the oracle's all-pairs of the same seeded matrix"""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    N, S = 3000, 1024
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--sketches", str(N), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 3 and line["config"]["pairs"] == N * (N - 1) // 2
+    assert all(line[k] is None for k in ("cpu_baseline", "checked_vs_oracle", "config4_1gpu", "sketch", "multiset_sketch"))
+    assert "matrices" not in line["compute"] and line["roofline"]["traffic"] is None
+    got = np.load(tmp_path / "jaccard_ut_sample.npy")
+    regs = synth.synthetic_registers(N, S, nclusters=max(8, N // 150), seed=20260928)
+    sig, cards = d2g.oph_finalize(regs, S, nthreads=8)
+    want = oracle.allpairs_ut(sig, cards, measure=oracle.SIMILARITY, k=31, nthreads=4)
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
