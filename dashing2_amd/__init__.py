@@ -12,7 +12,7 @@ from .capi import (  # noqa: F401
     SIMILARITY, CONTAINMENT, SYMMETRIC_CONTAINMENT, POISSON_LLR, INTERSECTION, UNION_SIZE,
     CMP_AUTO, CMP_DIRECT, CMP_BITSLICE, BITSLICE_OPS_PER_GROUP_EXTRA, TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0, PinnedArray,
     wang_hash, seed_mask, oph_xor_const, oph_m, oph_finalize, densify, epilogue_lut,
-    epilogue_gtlt, epilogue_neq, host_epilogue_ut, operand_layout, ut_count, ut_partition,
+    epilogue_gtlt, epilogue_neq, host_epilogue_ut, operand_layout, sparse_bin_geometry, ut_count, ut_partition,
 )
 
 __all__ = [
@@ -21,5 +21,5 @@ __all__ = [
     "SIMILARITY", "CONTAINMENT", "SYMMETRIC_CONTAINMENT", "POISSON_LLR", "INTERSECTION", "UNION_SIZE",
     "CMP_AUTO", "CMP_DIRECT", "CMP_BITSLICE", "BITSLICE_OPS_PER_GROUP_EXTRA", "TIME_K1", "TIME_K2", "TIME_K2PREP", "TIME_K3", "TIME_K0", "PinnedArray",
     "wang_hash", "seed_mask", "oph_xor_const", "oph_m", "oph_finalize", "densify", "epilogue_lut",
-    "epilogue_gtlt", "epilogue_neq", "host_epilogue_ut", "operand_layout", "ut_count", "ut_partition",
+    "epilogue_gtlt", "epilogue_neq", "host_epilogue_ut", "operand_layout", "sparse_bin_geometry", "ut_count", "ut_partition",
 ]

@@ -117,6 +117,8 @@ SIGNATURES = {
     "d2g_cmp_set_status": (_int, [_vp, _vp, _vp]),
     "d2g_cmp_set_sparse_info": (_int, [_vp, _vp, _vp, _vp]),
     "d2g_cmp_set_debug_pairs": (_int, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    "d2g_cmp_set_sparse_detail": (_int, [_vp, _vp, _vp, _vp]),
+    "d2g_sparse_bin_geometry": (_int, [_sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_int)]),
     "d2g_warmup": (_int, [_vp, _int]),
     "d2g_device_name": (_int, [_int, C.c_char_p, _sz]),
     "d2g_comm_unique_id": (_int, [_vp]),
@@ -273,6 +275,15 @@ def operand_layout(N, S):
     if rc:
         raise D2GError(rc)
     return int(gw.value), int(ng.value)
+
+
+def sparse_bin_geometry(N):
+    """-> dict(cshift, nch, nbins, binned_ok): the output bins of the sparse path's pair list for a set of N sketches (no GPU needed)"""
+    cs, nch, nb, ok = C.c_uint32(), C.c_uint32(), C.c_uint32(), _int()
+    rc = lib().d2g_sparse_bin_geometry(N, C.byref(cs), C.byref(nch), C.byref(nb), C.byref(ok))
+    if rc:
+        raise D2GError(rc)
+    return {"cshift": cs.value, "nch": nch.value, "nbins": nb.value, "binned_ok": bool(ok.value)}
 
 
 def ut_count(N, r0=0, r1=None):
@@ -748,6 +759,13 @@ class CmpSet:
         a = np.zeros(4, np.uint32)
         self.ctx._check(lib().d2g_cmp_set_sparse_info(self.ctx._h, self._h, stream, a.ctypes.data))
         return sparse_info_dict(a)
+
+    def sparse_detail(self, stream=None):
+        """-> dict of the last prepare's first look (its decision and raw sums) and list form (synchronises; zeros without a sparse path)"""
+        a = np.zeros(8, np.uint64)
+        self.ctx._check(lib().d2g_cmp_set_sparse_detail(self.ctx._h, self._h, stream, a.ctypes.data))
+        return {"looked": bool(a[0]), "looked_dense": bool(a[1]), "entries": int(a[2]), "family_pairs": int(a[3]), "shared_values": int(a[4]),
+                "planes": int(a[5]), "binned": bool(a[6]), "bin_cshift": int(a[7])}
 
     def debug_pairs(self, cap=1 << 24, stream=None):
         """-> (pairs [n][2] uint32: the pair list of the last prepare (i < j), roots [N] uint32: the family root of every sketch)"""

@@ -76,6 +76,7 @@ struct d2g_cmp_set {
     uint32_t *d_samp = nullptr;       // [16][Npad] + 2: the first look at a matrix (sp_sample): registers shared with sixteen sampled sketches
     bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)
     bool sp_big = true;               // this prepare enqueued the binned form of the pair list (sp_expect_long_list)
+    bool looked = false, looked_dense = false; uint32_t samp_sums[4] = {0, 0, 0, 0};   // the last prepare's first look: taken, its decision, its raw sums E, F, shared values, planes
     uint32_t *prefilled = nullptr;        // output the engine filled at the start of its step (d2g_bitslice_prefill): the next sparse launch into it skips its fill
     size_t prefilled_cnt = 0;             // ... and how many outputs that fill covered
     size_t prefilled_pieces = 0;          // ... and how many 32 KB pieces of it are written (all of them after an early fill; what rode on the prepare's kernels otherwise)
@@ -96,6 +97,7 @@ struct d2g_cmp_set {
     uint32_t *d_cw_ents = nullptr; unsigned long long *d_cw_vals = nullptr; size_t cw_ecap = 0, cw_vcap = 0;   // sp_emit_kernel -> sp_pairs_kernel: the holders of the mixed values, one record per value
     uint32_t *d_hoff = nullptr;                       // [bin_nwg][nbins] where the entries a counting workgroup met go inside their bin (sp_hist_body -> sp_bin_kernel)
     uint32_t nbins = 0, bin_nch = 0, bin_cshift = 10, bin_nwg = 1;
+    bool bin_ok = true;                               // the bins fit (sp_bin_geometry): otherwise the list is applied entry by entry only
     size_t tilebm_words = 0, tiles_cap = 0;
 };
 constexpr int BS_CC_STRIDE = 8;
@@ -120,6 +122,7 @@ int  d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream
 int  d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set);
 int  d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s);
 int  d2g_bitslice_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint32_t *out4);
+int  d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out8);
 int  d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out);
 int  d2g_bitslice_status(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s);   // synchronises; D2G_ERR_INTERNAL on overflow
 // exporter set over an N x S_local column slice (no operand of its own); d2g_bitslice_prepare_slice transposes + prepares it

@@ -348,6 +348,15 @@ int d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, 
     return d2g_bitslice_debug_read(ctx, set, as_stream(stream), pairs_out, cap, npairs, root_out);
 }
 
+int d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out8) {
+    if (!ctx || !out8) return D2G_ERR_INVALID;
+    D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_sparse_detail: set belongs to another context");
+    D2G_HIP(ctx, hipSetDevice(ctx->device));
+    for (int x = 0; x < 8; ++x) out8[x] = 0;
+    if (set->algo != D2G_CMP_BITSLICE) { D2G_HIP(ctx, hipStreamSynchronize(as_stream(stream))); return D2G_OK; }
+    return d2g_bitslice_sparse_detail(ctx, set, as_stream(stream), out8);
+}
+
 int d2g_cmp_set_status(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream) {
     if (!ctx) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_status: set belongs to another context");

@@ -1230,6 +1230,28 @@ int d2g_bitslice_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s
     return D2G_OK;
 }
 
+// diagnostics of the last prepare's first look and list form (synchronises `s`): see d2g.h
+int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out8) {
+    uint32_t binned = 0;
+    if (set->d_plctl) D2G_HIP(ctx, hipMemcpyAsync(&binned, set->d_plctl + SP_PL_BINNED, 4, hipMemcpyDeviceToHost, s));   // (raised by sp_bin_kernel when the binned form ran)
+    D2G_HIP(ctx, hipStreamSynchronize(s));
+    if (!set->sparse_ok) return D2G_OK;
+    out8[0] = set->looked ? 1 : 0; out8[1] = set->looked_dense ? 1 : 0;
+    if (set->looked) for (int x = 0; x < 4; ++x) out8[2 + x] = set->samp_sums[x];   // (a prepare that did not look reports no sums: those of an earlier look are not its own)
+    out8[6] = binned ? 1 : 0; out8[7] = set->bin_cshift;
+    return D2G_OK;
+}
+
+int d2g_sparse_bin_geometry(size_t N, uint32_t *cshift, uint32_t *nch, uint32_t *nbins, int *binned_ok) {
+    if (!N) return D2G_ERR_INVALID;
+    const SpBinGeom g = sp_bin_geometry(N);
+    if (cshift) *cshift = g.cshift;
+    if (nch) *nch = g.nch;
+    if (nbins) *nbins = g.nbins;
+    if (binned_ok) *binned_ok = g.ok ? 1 : 0;
+    return D2G_OK;
+}
+
 // diagnostics: the pair list and the sorted order of the last prepare, copied to the host (synchronises `s`)
 int d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out /* [N] or null */) {
     *npairs = 0;

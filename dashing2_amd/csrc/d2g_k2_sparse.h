@@ -354,7 +354,8 @@ __global__ __launch_bounds__(1024) void sp_scan_kernel(uint32_t *__restrict__ cn
         est = min(est, 0x0FFFFFFFu);
         if ((size_t)big * 2 > N) s_big = 1;
         uint32_t total;
-        uint32_t run = sp_block_scan(sum, wave_tot, &total) + s_run;
+        const uint32_t run0 = s_run;                                   // (read once: thread 0 advances s_run below while others still write this block's segment ends)
+        uint32_t run = sp_block_scan(sum, wave_tot, &total) + run0;
         {
             uint32_t o[8];
 #pragma unroll
@@ -365,7 +366,7 @@ __global__ __launch_bounds__(1024) void sp_scan_kernel(uint32_t *__restrict__ cn
         __syncthreads();
         for (uint32_t x = tid; x < n; x += 1024) {                     // cnt becomes the placing cursor, start and segend stay (a segment ends where the next one starts)
             cnt[base + x] = tile[x]; start[base + x] = tile[x];
-            segend[base + x] = x + 1 < n ? tile[x + 1] : s_run + total;
+            segend[base + x] = x + 1 < n ? tile[x + 1] : run0 + total;
         }
         if (tid == 0) s_run += total;
         __syncthreads();
@@ -421,6 +422,10 @@ struct SpColWork { uint32_t *ents; uint4 *vals; uint32_t ecap, vcap; };
 // the entry stream's and the value records' cursors as ONE aligned 64-bit word among plctl[8..10] (entries | records << 32): a step of sp_emit_kernel
 // reserves both with one atomic
 __device__ __forceinline__ unsigned long long *sp_pl_streams(uint32_t *plctl) { return reinterpret_cast<unsigned long long *>(plctl + 8 + (((uintptr_t)(plctl + 8) >> 2) & 1u)); }
+// the early projection's (columns so far | pairs so far << 17) as ONE aligned 64-bit word among plctl[1..3]: with two atomics the pairs of the
+// columns between a workgroup's two adds ran ahead of the column count (at 65 535 columns of one pair each: 1 000 columns' pairs over 32 columns,
+// a list projected 30 times too long -- the ordering gave up now and then on a matrix whose list fits)
+__device__ __forceinline__ unsigned long long *sp_pl_proj(uint32_t *plctl) { return reinterpret_cast<unsigned long long *>(plctl + 1 + (((uintptr_t)(plctl + 1) >> 2) & 1u)); }
 
 // (b): every shared value of every column; the pairs of its holders that lie in different segments go to the pair list.  One workgroup
 // per column; the column's shared values are walked in ranges of at most vcap ranks (1536; 768 from N = 65 536 on, where the two
@@ -438,7 +443,7 @@ __device__ __forceinline__ unsigned long long *sp_pl_streams(uint32_t *plctl) { 
 //           segment -- are written by that kernel, flat over all columns (round 5 let every outsider write its own run from inside this kernel's
 //           per-column latency chain: 64 eight-byte stores to 64 different lines per wave instruction, 50 ps per entry).
 // A list that is full raises order[0] (dense walk): the list is then longer than an eighth of all pairs -- not a sparse matrix.
-// A list that will not fit is noticed EARLY: every workgroup adds its column's pair count to plctl[2] and bumps plctl[3]; once 32
+// A list that will not fit is noticed EARLY: every workgroup adds its column's pair count and one column to one word (sp_pl_proj); once 32
 // columns are in, (pairs so far / columns so far) x columns > 1.5 x capacity raises order[0] and everybody stops at its next range.
 #ifndef D2G_SP_EMIT_T
 #define D2G_SP_EMIT_T 512
@@ -639,9 +644,10 @@ __global__ __launch_bounds__(SP_EMIT_T) __attribute__((amdgpu_waves_per_eu(8, 8)
             }
         }
     }
-    if (tid == 0 && colpairs) {
-        const uint32_t tot = atomicAdd(&plctl[2], colpairs) + colpairs, done = atomicAdd(&plctl[3], 1u) + 1u;
-        if (done >= 32 && (size_t)tot / done * ncols > (size_t)plcap + plcap / 4 * 2) { order[0] = 1; *gaveup = 1; }
+    if (tid == 0 && colpairs) {                                       // (columns < 2^17: the sparse path takes S < 65 536)
+        const unsigned long long add = 1ull | ((unsigned long long)colpairs << 17), o = atomicAdd(sp_pl_proj(plctl), add) + add;
+        const unsigned long long done = o & 0x1FFFFu, tot = o >> 17;
+        if (done >= 32 && tot / done * ncols > (unsigned long long)plcap + plcap / 4 * 2) { order[0] = 1; *gaveup = 1; }
     }
 }
 
@@ -1018,6 +1024,19 @@ __global__ __launch_bounds__(SP_FILL_THREADS) void sp_fill_kernel(uint32_t *__re
 // for the compose kernel; then it moves the slice its counting twin (sp_hist_body, same index) counted: the place of an entry is the bin's start
 // + what the twin's atomic returned + an LDS cursor.  One pass, no global atomics.
 constexpr uint32_t SP_BIN_MAX = 39 * 1024;    // bins a set may have: their cursors live in the LDS of one workgroup (156 KB); 50 000 sketches: 1563 bands x 25 chunks of 2048 columns
+// the bins of a set of N sketches: bands of 32 rows x chunks of 2^cshift columns -- 1024 columns, wider while there would be more than SP_BIN_MAX
+// bins.  Beyond 1 277 952 sketches (SP_BIN_MAX bands) the bands alone are too many: no binned form (ok = false, nbins = 0; sp_expect_long_list),
+// cshift then covers N with one chunk.  Host arithmetic: sp_alloc and d2g_sparse_bin_geometry.
+struct SpBinGeom { uint32_t cshift, nch, nbins; bool ok; };
+inline SpBinGeom sp_bin_geometry(size_t N) {
+    const size_t bands = div_up<size_t>(N, 32);
+    SpBinGeom g{10u, 0u, 0u, bands <= SP_BIN_MAX};
+    if (g.ok) { while (bands * div_up<size_t>(N, (size_t)1 << g.cshift) > SP_BIN_MAX) ++g.cshift; }   // (ends by cshift 21: one chunk)
+    else { while (((size_t)1 << g.cshift) < N) ++g.cshift; }
+    g.nch = (uint32_t)div_up<size_t>(N, (size_t)1 << g.cshift);
+    g.nbins = g.ok ? (uint32_t)(bands * g.nch) : 0u;
+    return g;
+}
 __global__ __launch_bounds__(1024) void sp_bin_kernel(const unsigned long long *__restrict__ plist, unsigned long long *__restrict__ plist2, uint32_t *__restrict__ plctl,
                                                       uint32_t plcap, SpBins bn, const uint32_t *__restrict__ hoff, const uint32_t *__restrict__ order) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lc[];     // [nbins] cursors
@@ -1399,11 +1418,9 @@ int sp_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     // holders of mixed values: h holders make h - 1 pairs at least -- and a column has N holders at most; a record per mixed value: a pair at least each, N / 2 values per column at most
     set->cw_ecap = std::min<size_t>(std::min<size_t>(2 * set->plist_cap, set->ncols * set->N), 0xFFFFFFF0u);
     set->cw_vcap = std::min<size_t>(set->plist_cap, set->ncols * (set->N / 2 + 1));
-    // output bins of the pair list: bands of 32 rows x chunks of 2^cshift columns (1024, wider while there would be more than SP_BIN_MAX bins)
-    set->bin_cshift = 10;
-    while (div_up<size_t>(set->N, 32) * div_up<size_t>(set->N, (size_t)1 << set->bin_cshift) > SP_BIN_MAX) ++set->bin_cshift;
-    set->bin_nch = (uint32_t)div_up<size_t>(set->N, (size_t)1 << set->bin_cshift);
-    set->nbins = (uint32_t)(div_up<size_t>(set->N, 32) * set->bin_nch);
+    // output bins of the pair list (sp_bin_geometry)
+    const SpBinGeom bg = sp_bin_geometry(set->N);
+    set->bin_cshift = bg.cshift; set->bin_nch = bg.nch; set->nbins = bg.nbins; set->bin_ok = bg.ok;
     // one zero-initialised block per prepare: [counters Npad + 1 | 8 global control words + tile bitmap | order 8 | list control 8 | control words of a whole-triangle launch 16 | entries per bin | bin cursors]
     set->spz_words = (Npad + 1) + (8 + set->tilebm_words) + 8 + 12 + SP_CTL_WORDS + (size_t)set->nbins;
     // the workgroups that count (and then move) the list's entries: one per ~16 384 entries of a full list, at most two per CU
@@ -1431,7 +1448,7 @@ int sp_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
         (e = hipMemset(set->d_samp, 0, (SP_SAMPLE_ROWS * Npad + 8) * 4)) != hipSuccess ||
         (e = hipMalloc((void **)&set->d_cw_ents, set->cw_ecap * 4)) != hipSuccess ||
         (e = hipMalloc((void **)&set->d_cw_vals, set->cw_vcap * 16)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_hoff, (size_t)set->bin_nwg * set->nbins * 4)) != hipSuccess) {
+        (e = hipMalloc((void **)&set->d_hoff, std::max<size_t>((size_t)set->bin_nwg * set->nbins, 1) * 4)) != hipSuccess) {
         ctx->last_error = std::string("bitslice sparse alloc: ") + hipGetErrorString(e);
         return e == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
     }
@@ -1503,7 +1520,12 @@ __global__ void sp_giveup_kernel(uint32_t *__restrict__ order, uint32_t *__restr
 // synchronisation, on the set's first prepare (and whenever a remembered give-up is due for its retry) instead of after link / sort / emit
 // (0.05-0.3 ms).  Later prepares of the set go by what is remembered.  A heuristic: whatever it says, the results are exact.
 struct SpSampleRows { uint32_t r[SP_SAMPLE_ROWS]; };
+// a (sample, sketch) count is the sum over the 32-column groups of min(equal registers in the group, SP_SAMPLE_FAM): below 256 up to 63 groups
+// (S <= 2016), a byte per sample, four samples per word; more groups take 16-bit fields, two per word (2048 groups x 4 = 8192 at S = 65535)
+inline uint32_t sp_sample_field_bits(size_t ncols) { return div_up<size_t>(ncols, SP_SAMPLE_COLS) * SP_SAMPLE_FAM < 256 ? 8u : 16u; }
+template <uint32_t FB>
 __global__ __launch_bounds__(256) void sp_sample_kernel(const uint32_t *__restrict__ ids, size_t N, size_t Npad, uint32_t ncols, SpSampleRows rows, uint32_t *__restrict__ cntm) {
+    constexpr uint32_t PW = 32 / FB;                                  // samples per count word
     __shared__ __attribute__((aligned(16))) uint32_t sm[SP_SAMPLE_COLS][SP_SAMPLE_ROWS];   // the sampled sketches' ids in this workgroup's columns
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t t0 = blockIdx.y * SP_SAMPLE_COLS, t1 = min(ncols, t0 + SP_SAMPLE_COLS);
@@ -1526,17 +1548,21 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(const uint32_t *__restri
             acc[4 * q] += wx == s4.x; acc[4 * q + 1] += wx == s4.y; acc[4 * q + 2] += wx == s4.z; acc[4 * q + 3] += wx == s4.w;
         }
     }
-    // four sampled sketches per word, a byte each, a column group's share capped at SP_SAMPLE_FAM (what counts is "fewer than that in all, or not":
-    // 32 groups x 4 stay below 256) -- a noisy matrix has a count for every (sample, sketch, group): a quarter of the atomics
+    // PW sampled sketches per word, a column group's share capped at SP_SAMPLE_FAM (what counts is "fewer than that in all, or not"; the field
+    // holds the sum over all groups: sp_sample_field_bits) -- a noisy matrix has a count for every (sample, sketch, group): a fraction of the atomics
 #pragma unroll
-    for (uint32_t q = 0; q < SP_SAMPLE_ROWS / 4; ++q) {
-        const uint32_t w = min(acc[4 * q], SP_SAMPLE_FAM) | (min(acc[4 * q + 1], SP_SAMPLE_FAM) << 8) | (min(acc[4 * q + 2], SP_SAMPLE_FAM) << 16) | (min(acc[4 * q + 3], SP_SAMPLE_FAM) << 24);
+    for (uint32_t q = 0; q < SP_SAMPLE_ROWS / PW; ++q) {
+        uint32_t w = 0;
+#pragma unroll
+        for (uint32_t y = 0; y < PW; ++y) w |= min(acc[PW * q + y], SP_SAMPLE_FAM) << (FB * y);
         if (w) atomicAdd(&cntm[(size_t)q * Npad + j], w);
     }
 }
 // the counts -> (E, F) in mapped host memory; the kernel cleans up behind itself (counters, its sums, the ticket)
+template <uint32_t FB>
 __global__ __launch_bounds__(256) void sp_sample_fin_kernel(uint32_t *__restrict__ cntm, size_t N, size_t Npad, SpSampleRows rows, uint32_t *__restrict__ acc3, uint32_t *__restrict__ host_out,
                                                             const uint32_t *__restrict__ colcnt, uint32_t ncols, int nsplit, uint32_t ticket) {
+    constexpr uint32_t PW = 32 / FB, MASK = (1u << FB) - 1u;
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     uint32_t e = 0, f = 0;
     // (the same grid also sums what the rank kernel left: the shared values of every column, and the id planes a column of that many needs -- the
@@ -1548,14 +1574,14 @@ __global__ __launch_bounds__(256) void sp_sample_fin_kernel(uint32_t *__restrict
     }
     if (j < N) {
 #pragma unroll
-        for (uint32_t q = 0; q < SP_SAMPLE_ROWS / 4; ++q) {
+        for (uint32_t q = 0; q < SP_SAMPLE_ROWS / PW; ++q) {
             const uint32_t w = cntm[(size_t)q * Npad + j];
             if (!w) continue;
             cntm[(size_t)q * Npad + j] = 0;
 #pragma unroll
-            for (uint32_t y = 0; y < 4; ++y) {
-                const uint32_t c = (w >> (8 * y)) & 0xFFu;
-                if (c && j != rows.r[4 * q + y]) { if (c >= SP_SAMPLE_FAM) ++f; else e += c; }
+            for (uint32_t y = 0; y < PW; ++y) {
+                const uint32_t c = (w >> (FB * y)) & MASK;
+                if (c && j != rows.r[PW * q + y]) { if (c >= SP_SAMPLE_FAM) ++f; else e += c; }
             }
         }
     }
@@ -1604,6 +1630,7 @@ SpPairs sp_pairs_of(const d2g_cmp_set *set, const SpColWork &cw, const uint32_t 
 // remembered give-up: a prepare still in flight has not written yet and the one before it decides.  Both forms are exact for any list.
 bool sp_expect_long_list(const d2g_ctx *ctx, const d2g_cmp_set *set) {
     const SpTuning t = sp_tuning(ctx);
+    if (!set->bin_ok) return false;                                    // (more than SP_BIN_MAX bands: no bins)
     if (t.list_form == 1) return false;
     if (t.list_form == 2) return true;
     if (set->pred_valid) return set->pred_entries >= (double)t.long_list;
@@ -1650,8 +1677,10 @@ int sp_sample_enqueue(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         s = (hipStream_t)set->samp_stream;
     }
 #endif
-    hipLaunchKernelGGL(sp_sample_kernel, dim3((unsigned)div_up<size_t>(N, 256), (unsigned)div_up<size_t>(set->ncols, SP_SAMPLE_COLS)), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)set->ncols, rows, set->d_samp);
-    hipLaunchKernelGGL(sp_sample_fin_kernel, dim3((unsigned)div_up<size_t>(std::max(N, set->ncols), 256)), dim3(256), 0, s, set->d_samp, N, Npad, rows, acc3, set->d_gaveup + 2,
+    const bool wide = sp_sample_field_bits(set->ncols) == 16;           // (d_samp holds SP_SAMPLE_ROWS words per sketch: 16-bit fields fill all of them)
+    const dim3 sgrid((unsigned)div_up<size_t>(N, 256), (unsigned)div_up<size_t>(set->ncols, SP_SAMPLE_COLS)), fgrid((unsigned)div_up<size_t>(std::max(N, set->ncols), 256));
+    hipLaunchKernelGGL(wide ? sp_sample_kernel<16> : sp_sample_kernel<8>, sgrid, dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)set->ncols, rows, set->d_samp);
+    hipLaunchKernelGGL(wide ? sp_sample_fin_kernel<16> : sp_sample_fin_kernel<8>, fgrid, dim3(256), 0, s, set->d_samp, N, Npad, rows, acc3, set->d_gaveup + 2,
                        set->d_colcnt, (uint32_t)set->ncols, set->nsplit, ++set->sample_ticket);
     D2G_HIP(ctx, hipGetLastError());
     set->sample_pending = true;
@@ -1677,6 +1706,7 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     }
     const double scale = (double)N / (2.0 * SP_SAMPLE_ROWS), pairs = (double)N * (double)(N - 1) / 2.0;
     set->pred_valid = true;
+    for (int x = 0; x < 4; ++x) set->samp_sums[x] = h[2 + x];            // (diagnostics: d2g_cmp_set_sparse_detail)
     set->pred_entries = (double)h[2] * scale;
     set->pred_family_pairs = (double)h[3] * scale;
     const double values = (double)h[4], planes = set->ncols ? (double)h[5] / (double)set->ncols : 1.0;
@@ -1707,6 +1737,7 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
     const bool skip = set->pred_valid ? set->pred_dense : (remembered && set->ride_total == 0);
     set->sp_big = sp_expect_long_list(ctx, set);
     ++set->sp_prepares;
+    set->looked = set->pred_valid; set->looked_dense = set->pred_valid && set->pred_dense;   // (diagnostics: d2g_cmp_set_sparse_detail)
     set->pred_valid = false;                                           // (a prediction serves the prepare that made it)
     if (skip) {
         hipLaunchKernelGGL(sp_giveup_kernel, dim3(1), dim3(64), 0, s, set->d_order, set->d_fullctl, (uint32_t)std::min<size_t>(sp_full_candidates(Npad), 0xFFFFFFFFu));

@@ -350,6 +350,14 @@ int  d2g_cmp_set_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream,
 /* diagnostics of the last prepare (synchronises `stream`): up to `cap` entries of the pair list (i | j << 32, i < j) and, if root_out is not null, the family
  * root of every sketch (sketches with equal roots sit in one segment).  Nothing in the product reads these back; tools/plist_stats.py does. */
 int  d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out);
+/* diagnostics of the last prepare's sparse path (synchronises `stream`; all 0 for a set without one): [0] 1 = the prepare took the first look at its
+ * matrix (sixteen sampled sketches against all), [1] 1 = the first look decided for the dense walk, [2..5] that look's raw sums (0 without one): register
+ * counts below 4 (E), pairs at 4 or more (F), shared values over all columns, id planes over all columns; [6] 1 = the pair list went through
+ * the binned + composed form, [7] the set's bin width (log2 of the columns of a chunk).  Nothing in the product reads these back. */
+int  d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out8);
+/* the output bins of the pair list of a set of N sketches (bands of 32 rows x chunks of 2^cshift columns): what a set's allocation computes.
+ * binned_ok = 0: more bands than bins fit, the list is applied entry by entry (nbins = 0).  Host arithmetic, no context. */
+int  d2g_sparse_bin_geometry(size_t N, uint32_t *cshift, uint32_t *nch, uint32_t *nbins, int *binned_ok);
 /* ---- sharded prepare (multi-GPU).  The bit-sliced operand is an array of independent
  * 32-register groups of `group_words` u32 each (+ one u32 of meta per group) whose geometry depends
  * on N only, so ranks can each build the groups of their own column slice and all-gather them:
