@@ -818,6 +818,9 @@ class CmpSet:
     def eqcount_rect_dev(self, out_dev_ptr, a0, a1, b0, b1, stream=None):
         self.ctx._check(lib().d2g_cmp_eqcount_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, out_dev_ptr, stream))
 
+    def gtlt_rect_dev(self, gt_dev_ptr, lt_dev_ptr, a0, a1, b0, b1, stream=None):
+        self.ctx._check(lib().d2g_cmp_gtlt_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, gt_dev_ptr, lt_dev_ptr, stream))
+
     # host-returning helpers built on the raw device-memory calls
     def eqcount_ut(self, r0=0, r1=None):
         r1 = self.N if r1 is None else r1
@@ -853,7 +856,7 @@ class CmpSet:
             return gt, lt
         dg, dl = self.ctx.malloc(gt.nbytes), self.ctx.malloc(lt.nbytes)
         try:
-            self.ctx._check(lib().d2g_cmp_gtlt_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, dg, dl, None))
+            self.gtlt_rect_dev(dg, dl, a0, a1, b0, b1)
             self.ctx.d2h(gt, dg)
             self.ctx.d2h(lt, dl)
         finally:

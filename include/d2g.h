@@ -407,7 +407,9 @@ int  d2g_cmp_ut_announce_dev(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r
  * prepare of a new set does */
 int  d2g_cmp_set_forget(d2g_ctx *ctx, d2g_cmp_set *set);
 /* (#a>b, #a<b) counts per pair: needs a set created with D2G_CMP_DIRECT (the raw patterns);
- * required when S is not a power of two in set space */
+ * required when S is not a power of two in set space.  The order is that of the 64-bit patterns as
+ * unsigned integers, which is the order of the doubles for non-negative, non-NaN registers (every
+ * register the product writes) */
 int  d2g_cmp_gtlt_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1,
                          uint32_t *gt_out_dev, uint32_t *lt_out_dev, void *stream);
 /* rectangular block: rows [a0,a1) x cols [b0,b1) of the full N x N equality-count matrix,
@@ -415,7 +417,8 @@ int  d2g_cmp_gtlt_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t
 int  d2g_cmp_eqcount_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, size_t a1,
                               size_t b0, size_t b1, uint32_t *neq_out_dev, void *stream);
 
-/* (#a>b, #a<b) for a rectangular block, a = row sketch, b = column sketch (compare(i,j) order) */
+/* (#a>b, #a<b) for a rectangular block, a = row sketch, b = column sketch (compare(i,j) order);
+ * the same unsigned 64-bit pattern order as d2g_cmp_gtlt_ut_dev */
 int  d2g_cmp_gtlt_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, size_t a1, size_t b0, size_t b1,
                            uint32_t *gt_out_dev, uint32_t *lt_out_dev, void *stream);
 

@@ -436,6 +436,28 @@ void d2o_count_gtlt(const double *a, const double *b, size_t n, uint64_t *gt, ui
     for (size_t i = 0; i < n; ++i) { g += a[i] > b[i]; l += a[i] < b[i]; }
     *gt = g; *lt = l;
 }
+/* (gt, lt) of the block rows [a0,a1) x columns [b0,b1) of the N x N pair matrix, row-major: gt[p] = #(sigs[i] > sigs[j]),
+ * lt[p] = #(sigs[i] < sigs[j]) with the double comparisons of d2o_count_gtlt (i = row sketch: the compare(i, j) order).
+ * Test infrastructure: the batched form of d2o_count_gtlt, OpenMP over rows. */
+void d2o_gtlt_block(const double *sigs, size_t N, size_t S, size_t a0, size_t a1, size_t b0, size_t b1,
+                    uint32_t *gt, uint32_t *lt, int nthreads) {
+    (void)N;
+    if (a1 <= a0 || b1 <= b0) return;
+    const size_t w = b1 - b0;
+    if (nthreads < 1) nthreads = 1;
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(dynamic) num_threads(nthreads)
+#endif
+    for (size_t i = a0; i < a1; ++i) {
+        const double *a = sigs + S * i;
+        for (size_t j = b0; j < b1; ++j) {
+            uint64_t g, l;
+            d2o_count_gtlt(a, sigs + S * j, S, &g, &l);
+            gt[(i - a0) * w + (j - b0)] = (uint32_t)g;
+            lt[(i - a0) * w + (j - b0)] = (uint32_t)l;
+        }
+    }
+}
 uint64_t d2o_count_eq(const double *a, const double *b, size_t n) {
     uint64_t e = 0;
     for (size_t i = 0; i < n; ++i) e += a[i] == b[i];

@@ -103,6 +103,9 @@ size_t d2o_densify(double *sig, size_t S);
 /* sketch::eq::count_gtlt (ABSENT): gt = #(a>b), lt = #(a<b); cmp_core.cpp:461 */
 void d2o_count_gtlt(const double *a, const double *b, size_t n, uint64_t *gt, uint64_t *lt);
 uint64_t d2o_count_eq(const double *a, const double *b, size_t n);
+/* batched d2o_count_gtlt over rows [a0,a1) x columns [b0,b1) of sigs [N][S]; gt/lt row-major [a1-a0][b1-b0], OpenMP over rows */
+void d2o_gtlt_block(const double *sigs, size_t N, size_t S, size_t a0, size_t a1, size_t b0, size_t b1,
+                    uint32_t *gt, uint32_t *lt, int nthreads);
 
 enum d2o_measure {           /* cmp_main.h:8-17 order */
     D2O_SIMILARITY = 0, D2O_CONTAINMENT = 1, D2O_SYMMETRIC_CONTAINMENT = 2,

@@ -59,6 +59,7 @@ def load(path=None):
         "d2o_densify": (sz, [pdbl, sz]),
         "d2o_count_gtlt": (None, [pdbl, pdbl, sz, pu64, pu64]),
         "d2o_count_eq": (u64, [pdbl, pdbl, sz]),
+        "d2o_gtlt_block": (None, [pdbl, sz, sz, sz, sz, sz, sz, pu32, pu32, i32]),
         "d2o_compare_from_gtlt": (C.c_float, [u64, u64, sz, dbl, dbl, i32, i32]),
         "d2o_compare_from_neq": (C.c_float, [u64, sz, dbl, dbl, i32, i32]),
         "d2o_compare": (C.c_float, [pdbl, pdbl, sz, sz, sz, i32, i32]),
@@ -170,6 +171,20 @@ def count_gtlt(a, b):
     gt, lt = C.c_uint64(), C.c_uint64()
     load().d2o_count_gtlt(_p(a, C.c_double), _p(b, C.c_double), a.size, C.byref(gt), C.byref(lt))
     return gt.value, lt.value
+
+
+def gtlt_rect(sigs, a0, a1, b0, b1, nthreads=None):
+    """(gt, lt) uint32 [a1-a0][b1-b0]: gt = #(sigs[i] > sigs[j]), lt = #(sigs[i] < sigs[j]) for rows i in [a0,a1), columns j in
+    [b0,b1) -- d2o_count_gtlt's double comparisons, batched (OpenMP over rows; nthreads defaults to OMP_NUM_THREADS or 16)"""
+    sigs = np.ascontiguousarray(sigs, np.float64)
+    N, S = sigs.shape
+    assert 0 <= a0 <= a1 <= N and 0 <= b0 <= b1 <= N
+    if nthreads is None:
+        nthreads = int(os.environ.get("OMP_NUM_THREADS") or 0) or min(16, os.cpu_count() or 1)
+    gt = np.zeros((a1 - a0, b1 - b0), np.uint32)
+    lt = np.zeros((a1 - a0, b1 - b0), np.uint32)
+    load().d2o_gtlt_block(_p(sigs, C.c_double), N, S, a0, a1, b0, b1, _p(gt, C.c_uint32), _p(lt, C.c_uint32), nthreads)
+    return gt, lt
 
 
 def compare_from_gtlt(gt, lt, S, lhc, rhc, measure=SIMILARITY, k=31):

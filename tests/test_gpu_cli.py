@@ -124,6 +124,89 @@ def test_cli_nonpow2_sketchsize_and_nocanon(oracle, genomes, tmp_path):
     np.testing.assert_array_equal(np.fromfile(b, np.float32).view(np.uint32), exp.view(np.uint32))
 
 
+def _nonpow2_genomes(d):
+    """fourteen unrelated genomes (every pair shares no register; lengths shuffled so both orientations of the split occur in the
+    triangle), three related ones and a tiny one that densify fills: refs, queries of a panel split after the ninth"""
+    ln = np.random.default_rng(2).permutation(14)
+    un = []
+    for i in range(14):
+        p = d / f"u{i:02d}.fa"
+        synth.write_fasta(p, f"u{i:02d}", synth.random_genome(300 + i, 20000 + 1500 * int(ln[i])))
+        un.append(str(p))
+    base = synth.random_genome(350, 40000)
+    rel = []
+    for i, rate in enumerate([0.0, 0.002, 0.03]):
+        p = d / f"r{i}.fa"
+        synth.write_fasta(p, f"r{i}", synth.mutate(base, rate, seed=50 + i) if rate else base)
+        rel.append(str(p))
+    p = d / "tiny.fa"
+    synth.write_fasta(p, "tiny", synth.random_genome(9, 400))
+    return un[0::2] + [rel[0], str(p)], un[1::2] + rel[1:]
+
+
+def _union_sensitive(oracle, dens, cards, pairs):
+    """pairs (i, j) whose union size changes under (lt, gt), and under (S - eq, 0): where a swapped (gt, lt) or the equality-count path shows"""
+    S = dens.shape[1]
+    u = lambda g, l, i, j: np.float32(oracle.compare_from_gtlt(g, l, S, cards[i], cards[j], oracle.UNION_SIZE, 21)).view(np.uint32)
+    nswap = neqp = 0
+    for i, j in pairs:
+        g, l = oracle.count_gtlt(dens[i], dens[j])
+        nswap += u(g, l, i, j) != u(l, g, i, j)
+        neqp += u(g, l, i, j) != u(g + l, 0, i, j)
+    return nswap, neqp
+
+
+def test_cli_nonpow2_dense_shapes_gtlt(oracle, tmp_path):
+    """S = 1000 in set space: the (gt, lt) path through the CLI's three dense shapes -- symmetric triangle, --square, -F/-Q panel --
+    for union size, containment and similarity, bit for bit against compare(i, j) of the oracle (rows = references, columns = queries).
+    Union size on pairs that share no register is what tells (gt, lt) from (lt, gt) or from the equality-count path; every shape first
+    shows that its pairs hold such cases.  Tiny row batches (D2G_CMP_SLOT_VALUES: batches start past row 0, the lt array cycles through
+    the slots) may not change a byte."""
+    from oracle import textfmt
+    import ctypes as C
+    k, S = 21, 1000
+    d = tmp_path / "fa"
+    d.mkdir()
+    refs, qs = _nonpow2_genomes(d)
+    paths = refs + qs
+    N, nf = len(paths), len(refs)
+    esigs, ecards = _oracle_result(oracle, paths, k, S)
+    dens = _densified(oracle, esigs)
+    assert not np.array_equal(dens[nf - 1], esigs[nf - 1])                         # the tiny genome was densified
+    lib = oracle.load()
+
+    def compare(i, j, meas):
+        return lib.d2o_compare(dens.ctypes.data_as(C.POINTER(C.c_double)), ecards.ctypes.data_as(C.POINTER(C.c_double)), S, i, j, meas, k)
+
+    ut_pairs = [(i, j) for i in range(N) for j in range(i + 1, N)]
+    shapes = {"symmetric": ut_pairs, "square": [(i, j) for i in range(N) for j in range(N)],
+              "panel": [(i, nf + j) for i in range(nf) for j in range(N - nf)]}
+    for name, pairs in shapes.items():
+        nswap, neqp = _union_sensitive(oracle, dens, ecards, pairs)
+        assert nswap >= 5 and neqp >= 5, f"{name}: the genomes cannot show the bugs this test is for ({nswap}, {neqp})"
+    st = tmp_path / "s.bin"
+    _run(["sketch", "-k", str(k), "-S", str(S), "-o", str(st)] + paths)
+    ff, qf = tmp_path / "refs.txt", tmp_path / "qs.txt"
+    ff.write_text("\n".join(refs) + "\n")
+    qf.write_text("\n".join(qs) + "\n")
+    cmd = {"symmetric": ["cmp", "--presketched", "-k", str(k), str(st)],
+           "square": ["cmp", "--presketched", "-k", str(k), "--square", str(st)],
+           "panel": ["sketch", "-k", str(k), "-S", str(S), "-F", str(ff), "-Q", str(qf)]}
+    for flags, meas in [(["--union-size"], oracle.UNION_SIZE), (["--containment"], oracle.CONTAINMENT), ([], oracle.SIMILARITY)]:
+        for name, pairs in shapes.items():
+            exp = np.array([compare(i, j, meas) for i, j in pairs], np.float32)
+            outs = []
+            for env in ({}, {"D2G_CMP_SLOT_VALUES": "40"}):
+                b = tmp_path / "o.bin"
+                _run(cmd[name] + ["--binary-output", "--cmpout", str(b)] + flags, env=dict(os.environ, **env))
+                outs.append(b.read_bytes())
+            np.testing.assert_array_equal(np.frombuffer(outs[0], np.uint32), exp.view(np.uint32), err_msg=f"{name} {flags}")
+            assert outs[1] == outs[0], f"{name} {flags}: row batches changed the output"
+    r = _run(["cmp", "--presketched", "-k", str(k), "--union-size", str(st)])
+    exp = np.array([compare(i, j, oracle.UNION_SIZE) for i, j in ut_pairs], np.float32)
+    assert r.stdout.decode() == textfmt.render_symmetric(paths, exp, phylip=False, options_string=OPTSTR.format(k=k, S=S))
+
+
 def test_cli_cache_and_panel(oracle, genomes, tmp_path):
     k, S = 31, 256
     pref = tmp_path / "cache"

@@ -117,6 +117,44 @@ def test_epilogue_lut(d2g, oracle):
         assert lut[e] == np.float32(oracle.compare_from_neq(e, 1000, 1., 1., oracle.SIMILARITY, 31))
 
 
+def _union_bits(oracle, gt, lt, S, lhc, rhc):
+    return np.float32(oracle.compare_from_gtlt(int(gt), int(lt), S, lhc, rhc, oracle.UNION_SIZE, 31)).view(np.uint32)
+
+
+@pytest.mark.parametrize("S", [100, 1000, 1023])
+def test_host_epilogue_ut_with_lt_counts(d2g, oracle, S):
+    """d2g_epilogue_ut(ca = gt, cb = lt, ...): the set-space epilogue of a sketch size that is not a power of two, where the value
+    depends on the split of S - eq into gt and lt (cmp_core.cpp:461-476).  Every measure, row ranges that start past row 0, one and four
+    threads, bit for bit against the oracle's compare_from_gtlt pair by pair."""
+    rng = np.random.default_rng(S + 11)
+    N = 61
+    iu, ju = np.triu_indices(N, 1)
+    cnt = iu.size
+    gt = rng.integers(0, S + 1, cnt)
+    lt = (rng.random(cnt) * (S - gt + 1)).astype(np.int64)             # gt + lt <= S
+    disjoint = rng.random(cnt) < 0.5                                    # pairs that share no register: gt + lt = S
+    lt[disjoint] = S - gt[disjoint]
+    gt[:4], lt[:4] = [0, S, 0, S // 3], [0, 0, S, S - S // 3]
+    assert gt.max() <= S and (gt + lt).max() <= S and ((gt + lt) == S).sum() > cnt // 3
+    cards = rng.uniform(1e2, 1e7, N)
+    cards[1], cards[2] = 1234.5, 6789.25
+    # without pairs whose union size changes under (lt, gt) and under (S - eq, 0), this test could not see either mistake
+    nswap = sum(_union_bits(oracle, gt[p], lt[p], S, cards[iu[p]], cards[ju[p]]) !=
+                _union_bits(oracle, lt[p], gt[p], S, cards[iu[p]], cards[ju[p]]) for p in range(cnt))
+    neqp = sum(_union_bits(oracle, gt[p], lt[p], S, cards[iu[p]], cards[ju[p]]) !=
+               _union_bits(oracle, gt[p] + lt[p], 0, S, cards[iu[p]], cards[ju[p]]) for p in range(cnt))
+    assert nswap >= 20 and neqp >= 20, (nswap, neqp)
+    ca, cb = gt.astype(np.uint32), lt.astype(np.uint32)
+    for meas in range(6):
+        exp = np.array([oracle.compare_from_gtlt(int(gt[p]), int(lt[p]), S, cards[iu[p]], cards[ju[p]], meas, 31) for p in range(cnt)],
+                       np.float32)
+        for r0, r1 in [(0, N), (1, 2), (3, 17), (17, N), (29, 31), (N - 2, N), (N - 1, N)]:
+            o0, o1 = d2g.ut_count(N, 0, r0), d2g.ut_count(N, 0, r1)
+            for nt in (1, 4):
+                got = d2g.host_epilogue_ut(ca[o0:o1], cb[o0:o1], cards, N, S, r0, r1, meas, 31, nthreads=nt)
+                np.testing.assert_array_equal(got.view(np.uint32), exp[o0:o1].view(np.uint32), err_msg=f"measure {meas} rows {r0}:{r1} nt {nt}")
+
+
 def test_ut_count_and_partition(d2g):
     for N in [0, 1, 2, 5, 100, 1001]:
         assert d2g.ut_count(N) == N * (N - 1) // 2

@@ -170,6 +170,22 @@ def test_allpairs_matches_pairwise(oracle):
         np.testing.assert_array_equal(part, full[off:off + part.size])
 
 
+def test_gtlt_rect_matches_pairwise(oracle):
+    """the batched (gt, lt) of a block equals count_gtlt(row, column) pair by pair, at any block offset and thread count"""
+    rng = np.random.default_rng(12)
+    N, S = 41, 33
+    sigs = rng.random((3, S))[rng.integers(0, 3, (N, S)), np.arange(S)[None, :]]
+    sigs[5] = sigs[9]
+    sigs[7] = np.inf
+    sigs[8] = 0.0
+    for a0, a1, b0, b1, nt in [(0, N, 0, N, 4), (3, 30, 17, 40, 1), (40, 41, 0, N, 2), (0, N, 6, 7, 3), (4, 4, 0, N, 2)]:
+        gt, lt = oracle.gtlt_rect(sigs, a0, a1, b0, b1, nthreads=nt)
+        assert gt.shape == lt.shape == (a1 - a0, b1 - b0)
+        for i in range(a0, a1):
+            for j in range(b0, b1):
+                assert (gt[i - a0, j - b0], lt[i - a0, j - b0]) == oracle.count_gtlt(sigs[i], sigs[j]), (i, j)
+
+
 def test_text_formatter_vs_fmt_golden():
     """tests/golden/fmt_float.tsv was produced by fmt 12.1.0 `fmt::format("{}", float)` (exp_upper = 7);
     fmt10_float.tsv is the fmt < 11 layout (exp_upper = 16, the oracle's and the CLI's default)."""
