@@ -3,13 +3,64 @@
 #include "../../include/d2g.h"
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <utility>
 
 #include <vector>
+struct d2g_ctx;
+int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what);   // (below) sets last_error to what + ": " + HIP's text; out of memory -> D2G_ERR_NOMEM
+
+// ---- ownership.  The library's structs own GPU resources through the four move-only types below and through nothing else: the
+// destructor gives the resource back, so a struct that owns buffers needs no free list.  A plain pointer (or hipStream_t / hipEvent_t)
+// field is a VIEW of something another object owns.  Kernels, kernel-argument structs and launches take raw pointers (get() / conversion).
+template <class T, bool Pinned> class d2g_owned {
+    T *p_ = nullptr; size_t cap_ = 0;
+public:
+    d2g_owned() = default;
+    d2g_owned(d2g_owned &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+    d2g_owned &operator=(d2g_owned &&o) noexcept { if (this != &o) { reset(); p_ = o.p_; cap_ = o.cap_; o.p_ = nullptr; o.cap_ = 0; } return *this; }
+    ~d2g_owned() { reset(); }
+    void reset() { if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_)); p_ = nullptr; cap_ = 0; }
+    // n ELEMENTS in one allocation; `flags` (hipHostMallocDefault, hipHostMallocMapped) applies to pinned memory only
+    int alloc(d2g_ctx *ctx, size_t n, const char *what, unsigned flags = hipHostMallocDefault) {
+        reset();
+        const hipError_t e = Pinned ? hipHostMalloc((void **)&p_, n * sizeof(T), flags) : hipMalloc((void **)&p_, n * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr; else cap_ = n;
+        return d2g_hip_status(ctx, e, what);
+    }
+    // grow-only work buffer: the old block is released FIRST (its contents are not kept), then need + need/4 + slack elements are allocated
+    int grow(d2g_ctx *ctx, size_t need, size_t slack, const char *what = "work buffer", unsigned flags = hipHostMallocDefault) {
+        return need <= cap_ ? D2G_OK : alloc(ctx, need + need / 4 + slack, what, flags);
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t cap() const { return cap_; }   // elements
+};
+template <class T> using d2g_dev = d2g_owned<T, false>;      // one hipMalloc
+template <class T> using d2g_pinned = d2g_owned<T, true>;    // one hipHostMalloc
+
+template <class H, hipError_t (*Destroy)(H)> class d2g_handle {
+protected:
+    H h_ = nullptr;
+public:
+    d2g_handle() = default;
+    d2g_handle(d2g_handle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    d2g_handle &operator=(d2g_handle &&o) noexcept { if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; } return *this; }
+    ~d2g_handle() { reset(); }
+    void reset() { if (h_) (void)Destroy(h_); h_ = nullptr; }
+    operator H() const { return h_; }
+};
+struct d2g_stream : d2g_handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create(unsigned flags = hipStreamDefault) { reset(); return hipStreamCreateWithFlags(&h_, flags); }
+};
+struct d2g_event : d2g_handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDefault) { reset(); return hipEventCreateWithFlags(&h_, flags); }
+};
+
 // every timed launch appends a (start, stop) pair; nothing synchronises until the caller asks
 struct d2g_evlog {
-    std::vector<hipEvent_t> a, b;
+    std::vector<d2g_event> a, b;
 };
 
 // Every D2G_* switch that selects a kernel, a threshold or a test hook inside the library is read from the environment ONCE per context
@@ -36,6 +87,11 @@ struct d2g_ctx {
     struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3_bmh.hip)
 };
 void d2g_k3_state_destroy(struct d2g_k3_state *st);
+inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
+    if (e == hipSuccess) return D2G_OK;
+    ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
+}
 
 #define D2G_HIP(ctx, call)                                                            \
     do {                                                                              \
@@ -62,10 +118,10 @@ struct d2g_timer {
         const int bit = e == &c->ev_k1 ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : D2G_TIME_K3;
         on = (c->timing & bit) != 0;
         if (on) {
-            hipEvent_t x = nullptr, y = nullptr;
-            if (hipEventCreate(&x) != hipSuccess || hipEventCreate(&y) != hipSuccess) { on = false; return; }
-            ev->a.push_back(x); ev->b.push_back(y);
+            d2g_event x, y;
+            if (x.create() != hipSuccess || y.create() != hipSuccess) { on = false; return; }
             (void)hipEventRecord(x, s);
+            ev->a.push_back(std::move(x)); ev->b.push_back(std::move(y));
         }
     }
     void stop() { if (on) (void)hipEventRecord(ev->b.back(), s); }

@@ -329,12 +329,12 @@ __global__ __launch_bounds__(K0_THREADS) void k0_emit_kernel(const uint8_t *__re
 
 // ------------------------------------------------------------------------------------------------ host side
 struct d2g_k0_state {
-    uint8_t *d_raw = nullptr; size_t cap_raw = 0;
-    K0File *d_files = nullptr; size_t cap_files = 0;
-    uint32_t *d_tile_nl = nullptr, *d_tile_nbase = nullptr, *d_tile_cls = nullptr; size_t cap_tiles = 0;
-    uint64_t *d_file_total = nullptr, *d_file_base = nullptr; size_t cap_ftot = 0;
-    uint64_t *d_run_list = nullptr; size_t cap_runs = 0;
-    uint32_t *d_ctl = nullptr;                      // [0] run count, [1] status
+    d2g_dev<uint8_t> d_raw;                         // grow-only, like every buffer here
+    d2g_dev<K0File> d_files;
+    d2g_dev<uint32_t> d_tile_nl, d_tile_nbase, d_tile_cls;
+    d2g_dev<uint64_t> d_file_total, d_file_base;
+    d2g_dev<uint64_t> d_run_list;
+    d2g_dev<uint32_t> d_ctl;                        // [0] run count, [1] status
     // the run table of the stream ingested last (host)
     std::vector<uint64_t> run_start, genome_run_off, genome_nkmers;
     std::vector<uint32_t> run_len;
@@ -343,13 +343,7 @@ struct d2g_k0_state {
     int k = 0;
 };
 
-void d2g_k0_state_destroy(d2g_k0_state *st) {
-    if (!st) return;
-    (void)hipFree(st->d_raw); (void)hipFree(st->d_files); (void)hipFree(st->d_tile_nl); (void)hipFree(st->d_tile_nbase);
-    (void)hipFree(st->d_tile_cls); (void)hipFree(st->d_file_total); (void)hipFree(st->d_file_base); (void)hipFree(st->d_run_list);
-    (void)hipFree(st->d_ctl);
-    delete st;
-}
+void d2g_k0_state_destroy(d2g_k0_state *st) { delete st; }
 
 bool d2g_k0_ingested(const d2g_sketcher *sk, uint64_t *nbases) {
     if (!sk->k0 || !sk->k0->valid) return false;
@@ -384,28 +378,19 @@ int d2g_sketcher_ingest_fasta(d2g_sketcher *sk, const uint8_t *raw, size_t raw_b
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = sk->stream;
     const size_t out_bytes = raw_bytes / 4 + 128;                        // every byte a base at worst; + the 64-byte pad K1 reads
-    if (int rc = d2g_grow(ctx, &st->d_raw, &st->cap_raw, raw_bytes + 64)) return rc;
-    if (int rc = d2g_grow(ctx, &sk->d_packed, &sk->cap_packed, out_bytes + 64)) return rc;
-    if (int rc = d2g_grow(ctx, &st->d_files, &st->cap_files, nfiles + 1)) return rc;
-    if (ntiles > st->cap_tiles) {
-        (void)hipFree(st->d_tile_nl); (void)hipFree(st->d_tile_nbase); (void)hipFree(st->d_tile_cls);
-        st->d_tile_nl = st->d_tile_nbase = st->d_tile_cls = nullptr; st->cap_tiles = 0;
-        const size_t ncap = ntiles + ntiles / 4 + 1024;
-        D2G_HIP(ctx, hipMalloc((void **)&st->d_tile_nl, ncap * 4));
-        D2G_HIP(ctx, hipMalloc((void **)&st->d_tile_nbase, ncap * 4));
-        D2G_HIP(ctx, hipMalloc((void **)&st->d_tile_cls, ncap * 4));
-        st->cap_tiles = ncap;
-    }
-    if (nfiles + 1 > st->cap_ftot) {
-        (void)hipFree(st->d_file_total); (void)hipFree(st->d_file_base);
-        st->d_file_total = st->d_file_base = nullptr; st->cap_ftot = 0;
+    const char *what = "ingest alloc";
+    if (int rc = st->d_raw.grow(ctx, raw_bytes + 64, 4096, what)) return rc;
+    if (int rc = sk->d_packed.grow(ctx, out_bytes + 64, 4096, what)) return rc;
+    if (int rc = st->d_files.grow(ctx, nfiles + 1, 4096, what)) return rc;
+    for (auto *b : {&st->d_tile_nl, &st->d_tile_nbase, &st->d_tile_cls})
+        if (int rc = b->grow(ctx, ntiles, 1024, what)) return rc;
+    if (nfiles + 1 > st->d_file_base.cap()) {                            // (the second of the pair: both are in place or this runs again)
         const size_t ncap = nfiles + 1 + nfiles / 4 + 64;
-        D2G_HIP(ctx, hipMalloc((void **)&st->d_file_total, ncap * 8));
-        D2G_HIP(ctx, hipMalloc((void **)&st->d_file_base, ncap * 8));
-        st->cap_ftot = ncap;
+        if (int rc = st->d_file_total.alloc(ctx, ncap, what)) return rc;
+        if (int rc = st->d_file_base.alloc(ctx, ncap, what)) return rc;
     }
-    if (!st->d_ctl) D2G_HIP(ctx, hipMalloc((void **)&st->d_ctl, 16));
-    if (!st->cap_runs) { D2G_HIP(ctx, hipMalloc((void **)&st->d_run_list, (size_t(1) << 20) * 8)); st->cap_runs = size_t(1) << 20; }
+    if (!st->d_ctl) if (int rc = st->d_ctl.alloc(ctx, 4, what)) return rc;
+    if (!st->d_run_list) if (int rc = st->d_run_list.alloc(ctx, size_t(1) << 20, what)) return rc;
     st->nbases = 0; st->k = k;
     st->run_start.clear(); st->run_len.clear();
     st->genome_run_off.assign(n + 1, 0); st->genome_nkmers.assign(n, 0);
@@ -427,8 +412,8 @@ int d2g_sketcher_ingest_fasta(d2g_sketcher *sk, const uint8_t *raw, size_t raw_b
         hipLaunchKernelGGL(k0_file_prefix_kernel, dim3(1), dim3(1024), 0, s, st->d_file_total, (uint32_t)nfiles, st->d_file_base);
         for (int attempt = 0;; ++attempt) {
             hipLaunchKernelGGL(k0_emit_kernel, dim3((unsigned)ntiles), dim3(K0_THREADS), 0, s, st->d_raw, st->d_files, (uint32_t)nfiles, st->d_tile_nl,
-                               st->d_tile_nbase, st->d_tile_cls, st->d_file_base, reinterpret_cast<uint32_t *>(sk->d_packed), st->d_run_list,
-                               (uint32_t)std::min<size_t>(st->cap_runs, 0xFFFFFFFFu), st->d_ctl, st->d_ctl + 1);
+                               st->d_tile_nbase, st->d_tile_cls, st->d_file_base, reinterpret_cast<uint32_t *>(sk->d_packed.get()), st->d_run_list,
+                               (uint32_t)std::min<size_t>(st->d_run_list.cap(), 0xFFFFFFFFu), st->d_ctl, st->d_ctl + 1);
             tm.stop();
             D2G_HIP(ctx, hipGetLastError());
             uint32_t ctl[2] = {0, 0};
@@ -438,10 +423,7 @@ int d2g_sketcher_ingest_fasta(d2g_sketcher *sk, const uint8_t *raw, size_t raw_b
             if (ctl[1] & K0_ST_PLUS) { ctx->last_error = "ingest: a line starts with '+' (FASTQ quality section): host parser"; return D2G_ERR_UNSUPPORTED; }
             if (ctl[1] & K0_ST_RUNLIST) {                                // more run starts than the list holds: grow it and emit again (idempotent)
                 if (attempt) { ctx->last_error = "ingest: run list overflow"; return D2G_ERR_INTERNAL; }
-                (void)hipFree(st->d_run_list); st->d_run_list = nullptr; st->cap_runs = 0;
-                const size_t ncap = (size_t)ctl[0] + 1024;
-                D2G_HIP(ctx, hipMalloc((void **)&st->d_run_list, ncap * 8));
-                st->cap_runs = ncap;
+                if (int rc = st->d_run_list.alloc(ctx, (size_t)ctl[0] + 1024, "ingest run list")) return rc;
                 D2G_HIP(ctx, hipMemsetAsync(st->d_ctl, 0, 16, s));
                 continue;
             }

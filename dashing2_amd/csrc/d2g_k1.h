@@ -20,14 +20,14 @@ struct d2g_oph_plan {
     uint64_t nkmers = 0, nbases = 0;
     std::vector<uint32_t> h_run_len;           // host copies kept for K3's bucket layout
     std::vector<uint64_t> h_genome_run_off;
-    uint64_t *d_run_start = nullptr;
-    uint32_t *d_run_len = nullptr;
-    uint64_t *d_run_chunk_off = nullptr;
-    uint32_t *d_blk_genome = nullptr;
-    uint64_t *d_blk_chunk0 = nullptr;
-    uint32_t *d_blk_nchunks = nullptr;
-    uint32_t *d_blk_run_lo = nullptr;
-    uint32_t *d_blk_run_hi = nullptr;
+    d2g_dev<uint64_t> d_run_start;
+    d2g_dev<uint32_t> d_run_len;
+    d2g_dev<uint64_t> d_run_chunk_off;
+    d2g_dev<uint32_t> d_blk_genome;
+    d2g_dev<uint64_t> d_blk_chunk0;
+    d2g_dev<uint32_t> d_blk_nchunks;
+    d2g_dev<uint32_t> d_blk_run_lo;
+    d2g_dev<uint32_t> d_blk_run_hi;
 };
 
 
@@ -41,15 +41,6 @@ inline KmerArgs d2g_plan_args(const d2g_oph_plan *plan, const uint8_t *packed_de
     return a;
 }
 
-template <class T> inline int d2g_grow(d2g_ctx *ctx, T **p, size_t *cap, size_t need) {
-    if (need <= *cap) return D2G_OK;
-    (void)hipFree(*p); *p = nullptr; *cap = 0;
-    const size_t ncap = need + need / 4 + 4096;
-    D2G_HIP(ctx, hipMalloc((void **)p, ncap * sizeof(T)));
-    *cap = ncap;
-    return D2G_OK;
-}
-
 // Host ingest feeds K1 in groups of inputs; re-allocating device buffers and uploading eight
 // small tables per group costs ~20 ms, the kernel ~0.1 ms.  The sketcher keeps grow-only device
 // buffers and ships all launch tables in ONE copy from a pinned arena.
@@ -57,11 +48,11 @@ struct d2g_k3_state;
 struct d2g_k0_state;
 struct d2g_sketcher {
     d2g_ctx *ctx = nullptr;
-    hipStream_t stream = nullptr;
-    uint8_t *d_packed = nullptr; size_t cap_packed = 0;
-    uint64_t *d_regs = nullptr;  size_t cap_regs = 0;      // in u64
-    uint8_t *d_arena = nullptr, *h_arena = nullptr; size_t cap_arena = 0;
-    uint8_t *h_stage = nullptr; size_t cap_stage = 0;      // pinned staging of the packed stream
+    d2g_stream stream;
+    d2g_dev<uint8_t> d_packed;                             // grow-only, like the buffers below
+    d2g_dev<uint64_t> d_regs;
+    d2g_dev<uint8_t> d_arena; d2g_pinned<uint8_t> h_arena; // the launch tables: device copy and its pinned source
+    d2g_pinned<uint8_t> h_stage;                           // pinned staging of the packed stream
     d2g_k3_state *k3 = nullptr;                            // --multiset work buffers (d2g_k3_bmh.hip)
     d2g_k0_state *k0 = nullptr;                            // device FASTA ingest (d2g_k0.hip): raw bytes, tile tables, the last run table
 };

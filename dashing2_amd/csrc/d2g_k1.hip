@@ -66,9 +66,9 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
 }
 
 template <class T>
-static int upload(d2g_ctx *ctx, const std::vector<T> &h, T **d) {
-    D2G_HIP(ctx, hipMalloc((void **)d, std::max<size_t>(h.size(), 1) * sizeof(T)));
-    if (!h.empty()) D2G_HIP(ctx, hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+static int upload(d2g_ctx *ctx, const std::vector<T> &h, d2g_dev<T> &d) {
+    if (int rc = d.alloc(ctx, std::max<size_t>(h.size(), 1), "oph plan alloc")) return rc;
+    if (!h.empty()) D2G_HIP(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return D2G_OK;
 }
 
@@ -79,9 +79,6 @@ extern "C" {
 void d2g_oph_plan_destroy(d2g_oph_plan *p) {
     if (!p) return;
     (void)hipSetDevice(p->ctx->device);
-    (void)hipFree(p->d_run_start); (void)hipFree(p->d_run_len); (void)hipFree(p->d_run_chunk_off);
-    (void)hipFree(p->d_blk_genome); (void)hipFree(p->d_blk_chunk0); (void)hipFree(p->d_blk_nchunks);
-    (void)hipFree(p->d_blk_run_lo); (void)hipFree(p->d_blk_run_hi);
     delete p;
 }
 
@@ -158,10 +155,10 @@ int d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t 
     std::vector<uint64_t> rs(run_start, run_start + nrun);
     std::vector<uint32_t> rl(run_len, run_len + nrun);
     int rc;
-    if ((rc = upload(ctx, rs, &p->d_run_start)) || (rc = upload(ctx, rl, &p->d_run_len)) ||
-        (rc = upload(ctx, ph.chunk_off, &p->d_run_chunk_off)) || (rc = upload(ctx, ph.bg, &p->d_blk_genome)) ||
-        (rc = upload(ctx, ph.bc0, &p->d_blk_chunk0)) || (rc = upload(ctx, ph.bn, &p->d_blk_nchunks)) ||
-        (rc = upload(ctx, ph.blo, &p->d_blk_run_lo)) || (rc = upload(ctx, ph.bhi, &p->d_blk_run_hi))) {
+    if ((rc = upload(ctx, rs, p->d_run_start)) || (rc = upload(ctx, rl, p->d_run_len)) ||
+        (rc = upload(ctx, ph.chunk_off, p->d_run_chunk_off)) || (rc = upload(ctx, ph.bg, p->d_blk_genome)) ||
+        (rc = upload(ctx, ph.bc0, p->d_blk_chunk0)) || (rc = upload(ctx, ph.bn, p->d_blk_nchunks)) ||
+        (rc = upload(ctx, ph.blo, p->d_blk_run_lo)) || (rc = upload(ctx, ph.bhi, p->d_blk_run_hi))) {
         d2g_oph_plan_destroy(p);
         return rc;
     }
@@ -198,46 +195,38 @@ int d2g_oph_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, con
     d2g_oph_plan *plan = nullptr;
     int rc = d2g_oph_plan_create(ctx, run_start, run_len, nrun, genome_run_off, n, k, &plan);
     if (rc) return rc;
+    const std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> plan_owner(plan, d2g_oph_plan_destroy);
     // the kernel reads up to 20 bytes past a chunk's first word: require the documented pad
     if (nrun) {
         uint64_t maxend = 0;
         for (size_t r = 0; r < nrun; ++r) maxend = std::max<uint64_t>(maxend, run_start[r] + run_len[r]);
         if (packed_bytes < (maxend + 3) / 4 + 64) {
-            d2g_oph_plan_destroy(plan);
             ctx->last_error = "packed stream lacks the 64-byte tail pad";
             return D2G_ERR_INVALID;
         }
     }
     const size_t m = d2g_oph_m(sketchsize);
-    uint8_t *d_packed = nullptr;
-    uint64_t *d_regs = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_packed); (void)hipFree(d_regs); d2g_oph_plan_destroy(plan); };
+    d2g_dev<uint8_t> d_packed;
+    d2g_dev<uint64_t> d_regs;
+    if ((rc = d_packed.alloc(ctx, std::max<size_t>(packed_bytes, 4), "oph sketch alloc")) ||
+        (rc = d_regs.alloc(ctx, std::max<size_t>(n * m, 1), "oph sketch alloc"))) return rc;
     hipError_t e;
-    if ((e = hipMalloc((void **)&d_packed, std::max<size_t>(packed_bytes, 4))) != hipSuccess ||
-        (e = hipMalloc((void **)&d_regs, std::max<size_t>(n * m, 1) * sizeof(uint64_t))) != hipSuccess) {
-        ctx->last_error = hipGetErrorString(e); cleanup(); return D2G_ERR_NOMEM;
-    }
     if (packed_bytes && (e = hipMemcpy(d_packed, packed, packed_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-        ctx->last_error = hipGetErrorString(e); cleanup(); return D2G_ERR_HIP;
+        ctx->last_error = hipGetErrorString(e); return D2G_ERR_HIP;
     }
     rc = d2g_oph_sketch_dev(ctx, plan, d_packed, canon, xormask, sketchsize, d_regs, nullptr);
     if (rc == D2G_OK && n) {
         e = hipMemcpy(regs_out, d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost);
         if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = D2G_ERR_HIP; }
     }
-    cleanup();
     return rc;
 }
 
 void d2g_sketcher_destroy(d2g_sketcher *sk) {
     if (!sk) return;
     (void)hipSetDevice(sk->ctx->device);
-    (void)hipFree(sk->d_packed); (void)hipFree(sk->d_regs); (void)hipFree(sk->d_arena);
-    if (sk->h_arena) (void)hipHostFree(sk->h_arena);
-    if (sk->h_stage) (void)hipHostFree(sk->h_stage);
     if (sk->k3) d2g_k3_state_destroy(sk->k3);
     if (sk->k0) d2g_k0_state_destroy(sk->k0);
-    if (sk->stream) (void)hipStreamDestroy(sk->stream);
     delete sk;
 }
 
@@ -248,7 +237,7 @@ int d2g_sketcher_create(d2g_ctx *ctx, d2g_sketcher **out) {
     d2g_sketcher *sk = new (std::nothrow) d2g_sketcher();
     if (!sk) return D2G_ERR_NOMEM;
     sk->ctx = ctx;
-    hipError_t e = hipStreamCreateWithFlags(&sk->stream, hipStreamNonBlocking);
+    hipError_t e = sk->stream.create(hipStreamNonBlocking);
     if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); delete sk; return D2G_ERR_HIP; }
     *out = sk;
     return D2G_OK;
@@ -266,7 +255,7 @@ int d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_byte
     if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon,
                                     &a.km, &nblk, nullptr)) return rc;
     const size_t m = d2g_oph_m(sketchsize);
-    if (int rc = d2g_grow(ctx, &sk->d_regs, &sk->cap_regs, std::max<size_t>(n * m, 1))) return rc;
+    if (int rc = sk->d_regs.grow(ctx, std::max<size_t>(n * m, 1), 4096)) return rc;
     hipStream_t s = sk->stream;
     D2G_HIP(ctx, hipMemsetAsync(sk->d_regs, 0xFF, std::max<size_t>(n * m, 1) * sizeof(uint64_t), s));   // registers_ = T(-1): oph.h:147,233
     if (nblk) {
@@ -301,7 +290,7 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_by
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nblk = ph.bg.size();
     if (!use_ingested)
-        if (int rc = d2g_grow(ctx, &sk->d_packed, &sk->cap_packed, std::max<size_t>(packed_bytes, 4))) return rc;
+        if (int rc = sk->d_packed.grow(ctx, std::max<size_t>(packed_bytes, 4), 4096)) return rc;
     // arena layout (256-byte aligned pieces)
     auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
     size_t off = 0;
@@ -313,15 +302,8 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_by
     const size_t o_bn = off;  off = al(off + nblk * 4);
     const size_t o_lo = off;  off = al(off + nblk * 4);
     const size_t o_hi = off;  off = al(off + nblk * 4);
-    if (off > sk->cap_arena) {
-        (void)hipFree(sk->d_arena);
-        if (sk->h_arena) (void)hipHostFree(sk->h_arena);
-        sk->d_arena = sk->h_arena = nullptr; sk->cap_arena = 0;
-        const size_t ncap = off + off / 4 + 65536;
-        D2G_HIP(ctx, hipMalloc((void **)&sk->d_arena, ncap));
-        D2G_HIP(ctx, hipHostMalloc((void **)&sk->h_arena, ncap, hipHostMallocDefault));
-        sk->cap_arena = ncap;
-    }
+    if (int rc = sk->d_arena.grow(ctx, off, 65536)) return rc;
+    if (int rc = sk->h_arena.grow(ctx, off, 65536)) return rc;
     uint8_t *h = sk->h_arena;
     if (nrun) { std::memcpy(h + o_rs, run_start, nrun * 8); std::memcpy(h + o_rl, run_len, nrun * 4); }
     std::memcpy(h + o_co, ph.chunk_off.data(), (nrun + 1) * 8);
@@ -335,17 +317,11 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_by
     if (packed_bytes && !use_ingested) {
         // pageable source: stage through our own pinned buffer (the runtime would otherwise pin the
         // caller's pages on the fly, which contends with parser threads on the process' mm locks)
-        if (packed_bytes > sk->cap_stage) {
-            if (sk->h_stage) (void)hipHostFree(sk->h_stage);
-            sk->h_stage = nullptr; sk->cap_stage = 0;
-            const size_t ncap = packed_bytes + packed_bytes / 4 + 65536;
-            D2G_HIP(ctx, hipHostMalloc((void **)&sk->h_stage, ncap, hipHostMallocDefault));
-            sk->cap_stage = ncap;
-        }
+        if (int rc = sk->h_stage.grow(ctx, packed_bytes, 65536)) return rc;
         std::memcpy(sk->h_stage, packed, packed_bytes);
         D2G_HIP(ctx, hipMemcpyAsync(sk->d_packed, sk->h_stage, packed_bytes, hipMemcpyHostToDevice, s));
     }
-    out->packed = reinterpret_cast<const uint32_t *>(sk->d_packed);
+    out->packed = reinterpret_cast<const uint32_t *>(sk->d_packed.get());
     out->run_start = reinterpret_cast<const uint64_t *>(sk->d_arena + o_rs);
     out->run_len = reinterpret_cast<const uint32_t *>(sk->d_arena + o_rl);
     out->run_chunk_off = reinterpret_cast<const uint64_t *>(sk->d_arena + o_co);

@@ -7,26 +7,27 @@ struct d2g_cmp_set {
     size_t N = 0, S = 0;
     size_t Npad = 0;              // N rounded up to the column tile (256)
     int algo = D2G_CMP_DIRECT;    // algorithm actually prepared
-    uint64_t *d_rows = nullptr;   // [N][S]     row-major 64-bit patterns
-    uint64_t *d_cols = nullptr;   // [S][Npad]  register-major (transposed), zero padded
+    d2g_dev<uint64_t> d_rows;     // [N][S]     row-major 64-bit patterns
+    d2g_dev<uint64_t> d_cols;     // [S][Npad]  register-major (transposed), zero padded
     // bit-sliced operand (algo == D2G_CMP_BITSLICE); all buffers are allocated once per set
+    d2g_dev<uint32_t> own_planes, own_meta;   // what d_planes / d_meta point at when the set allocated them itself; empty in a set over the caller's operand
     uint32_t *d_planes = nullptr; // exchanged form [ntb][nbits_cap+1][Nstride]: bit x of word = bit b of id[32*tb+x][j], unique values
                                   // coded 0; last slot = the "unique" plane (fixed geometry: groups are independent)
-    uint32_t *d_stream = nullptr; // what the pair kernel walks: [live planes of all groups][2][Nstride] -- row-coded words, then the
+    d2g_dev<uint32_t> d_stream;   // what the pair kernel walks: [live planes of all groups][2][Nstride] -- row-coded words, then the
                                   // same plane with unique values coded all-ones (column coding); + one block of slack
     size_t Nstride = 0;           // Npad + 64 (row tiles may read past Npad)
     int nbits_cap = 0;            // id-plane slots per 32-register group: smallest c with 2^c >= N/2 + 2
     int ntb = 0;                  // ceil(S/32)
     uint32_t *d_meta = nullptr;   // [tb] = max over the group's columns of (#values occurring >= 2 times) + 1 (device side; the kernels
                                   //       derive the live plane count from it, no host round trip)
-    uint32_t *d_ids = nullptr;    // workspace: [S][Npad] dense ids
+    d2g_dev<uint32_t> d_ids;      // workspace: [S][Npad] dense ids (engine-managed gathered operands: allocated with d_colcnt for the sparse path, ids re-derived from the planes)
     uint32_t T = 0; int logT = 0; // hash space of the rank kernel (power of two >= 1.5 N)
-    bool borrowed = false;        // planes/meta belong to the caller (d2g_cmp_set_from_planes_dev)
+    bool borrowed = false;        // planes/meta are the caller's (d2g_cmp_set_from_planes_dev): never re-prepared, status from status_words
     bool want_exchange = false;   // d_planes is kept up to date by every prepare (set by the first export)
     // column plan (bs_colplan_kernel): the 32-register groups are formed from the columns SORTED by their live-plane class, so
     // that meta[tb] is the maximum over 32 similar columns (equality counts are a sum over columns: any permutation is exact)
-    uint32_t *d_colcnt = nullptr; // [S][BS_CC_STRIDE]: per column, slots 0..3 = rank offset of each split of the rank kernel, slot 4 = #shared values
-    uint32_t *d_perm = nullptr;   // [ntb*32]: the column that sits in each register slot of the operand, ~0 = padding
+    d2g_dev<uint32_t> d_colcnt;   // [S][BS_CC_STRIDE]: per column, slots 0..3 = rank offset of each split of the rank kernel, slot 4 = #shared values
+    d2g_dev<uint32_t> d_perm;     // [ntb*32]: the column that sits in each register slot of the operand, ~0 = padding
     int nsplit = 1;               // workgroups per column in the multi-partition rank kernel (narrow slices of large N: fills the CUs)
     // exporter sets (the multi-GPU engine's per-rank column slices): the prepare writes the exchange form, the group meta and its
     // status word straight into the caller's gathered operand; no plane stream, no private d_planes
@@ -43,37 +44,36 @@ struct d2g_cmp_set {
     bool sparse_ok = false;       // eligible and enabled (D2G_BS_SPARSE, D2G_BS_SPARSE_MIN_N)
     unsigned sp_launch = 0;       // sparse launches so far: the control words are double-buffered (a launch zeroes the next one's)
     size_t ncols = 0;             // register columns the sparse path walks: S, or all ntb * 32 register slots of an engine-managed gathered operand
-    bool ids_owned = false;       // engine-managed gathered operands: d_ids / d_colcnt were allocated for the sparse path (ids re-derived from the planes)
     bool srt_valid = false;       // d_stream_s / d_sperm describe the operand last prepared
     bool nat_valid = false;       // d_stream (caller's order; rectangular launches, dense launches) is up to date
-    uint32_t *d_stream_s = nullptr;   // plane stream in sorted order
-    uint32_t *d_sperm = nullptr;      // [Nstride] sketch at sorted position p (0xFFFFFFFF = padding)
-    uint32_t *d_sinv = nullptr;       // [Npad]    sorted position of sketch j
-    uint32_t *d_label = nullptr;      // [2][Npad] union-find labels (-> segment starts after the sort) | root of every sketch
-    uint32_t *d_owner = nullptr;      // [S][owner_stride] one holder of every shared value (rank r -> owner[r - 1]); single-partition owning sets only
+    d2g_dev<uint32_t> d_stream_s;   // plane stream in sorted order
+    d2g_dev<uint32_t> d_sperm;      // [Nstride] sketch at sorted position p (0xFFFFFFFF = padding)
+    d2g_dev<uint32_t> d_sinv;       // [Npad]    sorted position of sketch j
+    d2g_dev<uint32_t> d_label;      // [2][Npad] union-find labels (-> segment starts after the sort) | root of every sketch
+    d2g_dev<uint32_t> d_owner;      // [S][owner_stride] one holder of every shared value (rank r -> owner[r - 1]); single-partition owning sets only
     size_t owner_stride = 0;
-    uint32_t *d_segend = nullptr;     // [Npad]    end of the segment of root r (the sort's scan)
-    uint32_t *d_posseg = nullptr;     // [Npad][2] (start, end) of the segment sorted position p lies in (sp_place_kernel; the sub-tile test of the pair kernel and the pair list)
-    uint32_t *d_hint = nullptr;       // [2][Npad] per sketch the smallest holder of a value it shares (even / odd column pairs), 0xFFFFFFFF = none
-    uint32_t *d_spz = nullptr;        // ONE block the prepare clears: the arrays below
+    d2g_dev<uint32_t> d_segend;     // [Npad]    end of the segment of root r (the sort's scan)
+    d2g_dev<uint32_t> d_posseg;     // [Npad][2] (start, end) of the segment sorted position p lies in (sp_place_kernel; the sub-tile test of the pair kernel and the pair list)
+    d2g_dev<uint32_t> d_hint;       // [2][Npad] per sketch the smallest holder of a value it shares (even / odd column pairs), 0xFFFFFFFF = none
+    d2g_dev<uint32_t> d_spz;        // ONE block the prepare clears: the arrays below
     size_t spz_words = 0;
-    uint32_t *d_lcnt = nullptr;       // [Npad+1]  counting sort: sketches per root, then the placing cursors (= segment ends)
+    uint32_t *d_lcnt = nullptr;       // (this and d_gbm, d_order, d_plctl, d_fullctl, d_binc: inside d_spz) [Npad+1]  counting sort: sketches per root, then the placing cursors (= segment ends)
     uint32_t *d_gbm = nullptr;        // 8 control words + the tile bitmap over ALL sorted row blocks (the segments' tiles); partial launches derive theirs from it
     uint32_t *d_order = nullptr;      // [8] [0] 1 = the launches walk every tile of the caller's-order operand (dense), [2] deep label chains
     uint32_t *d_plctl = nullptr;      // [12] [0] entries emitted into the pair list
-    uint32_t *d_rowpos = nullptr;     // [Nstride] launch rows: sorted position of launch row k
-    uint32_t *d_rowk = nullptr;       // [Npad]    launch row of sketch j (0xFFFFFFFF = not a row of this launch)
-    uint32_t *d_rowstream = nullptr;  // [planes][Nstride] row-coded words of the launch rows, gathered (partial launches)
-    uint32_t *d_tilebm = nullptr, *d_tiles = nullptr, *d_spctl = nullptr;   // a partial launch's tile bitmap, work list, 2 x 8 control words {tiles listed, flags, -, candidates}
-    uint32_t *d_tiles_full = nullptr, *d_fullctl = nullptr;   // work lists + control words of a whole-triangle launch, left by the prepare (sp_permute_kernel)
+    d2g_dev<uint32_t> d_rowpos;     // [Nstride] launch rows: sorted position of launch row k
+    d2g_dev<uint32_t> d_rowk;       // [Npad]    launch row of sketch j (0xFFFFFFFF = not a row of this launch)
+    d2g_dev<uint32_t> d_rowstream;  // [planes][Nstride] row-coded words of the launch rows, gathered (partial launches)
+    d2g_dev<uint32_t> d_tiles, d_spctl; uint32_t *d_tilebm = nullptr;   // a partial launch's work list, 2 x 8 control words {tiles listed, flags, -, candidates} + its tile bitmap (inside d_spctl)
+    d2g_dev<uint32_t> d_tiles_full; uint32_t *d_fullctl = nullptr;   // work lists + control words (inside d_spz) of a whole-triangle launch, left by the prepare (sp_permute_kernel)
     bool full_list_valid = false;
-    uint32_t *h_gaveup = nullptr, *d_gaveup = nullptr;   // a word of mapped host memory: 1 = the last ordering raised order[0] (the next prepare skips the ordering)
+    d2g_pinned<uint32_t> h_gaveup; uint32_t *d_gaveup = nullptr;   // a word of mapped host memory and its device address: 1 = the last ordering raised order[0] (the next prepare skips the ordering); no mapped memory: d_gaveup is a spare word of d_order
     unsigned sp_prepares = 0; bool sp_skipped = false;
-    void *fill_stream = nullptr, *fill_fork = nullptr, *fill_join = nullptr;   // (hipStream_t / hipEvent_t) a LARGE announced output is filled beside the rank kernel (d2g_bitslice_prepare)
-    void *samp_stream = nullptr, *samp_event = nullptr;   // (hipStream_t / hipEvent_t) the first look runs beside the column plan and the planes kernel
+    d2g_stream fill_stream; d2g_event fill_fork, fill_join;   // a LARGE announced output is filled beside the rank kernel (d2g_bitslice_prepare)
+    d2g_stream samp_stream; d2g_event samp_event;   // the first look runs beside the column plan and the planes kernel
     bool sample_pending = false; uint32_t sample_ticket = 0;   // the first look's kernels are enqueued; the word (h_gaveup[6]) their last workgroup writes when the sums are in
     int skip_cached = -1;             // this prepare's reading of the remembered give-up (-1: not read yet)
-    uint32_t *d_samp = nullptr;       // [16][Npad] + 2: the first look at a matrix (sp_sample): registers shared with sixteen sampled sketches
+    d2g_dev<uint32_t> d_samp;       // [16][Npad] + 2: the first look at a matrix (sp_sample): registers shared with sixteen sampled sketches
     bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)
     bool sp_big = true;               // this prepare enqueued the binned form of the pair list (sp_expect_long_list)
     bool looked = false, looked_dense = false; uint32_t samp_sums[4] = {0, 0, 0, 0};   // the last prepare's first look: taken, its decision, its raw sums E, F, shared values, planes
@@ -88,14 +88,14 @@ struct d2g_cmp_set {
     uint32_t *ride_out = nullptr; size_t ride_cnt = 0; const uint32_t *ride_vsrc = nullptr; uint32_t ride_vimm = 0;
     uint32_t ride_next = 0, ride_total = 0;   // pieces of 32 KB handed out so far / in all (0: nothing rides in this prepare)
     const uint32_t *last_ctl = nullptr;   // control words of the last sparse launch (d2g_cmp_set_sparse_info)
-    unsigned long long *d_plist = nullptr;   // pair list: (i | j << 32), i < j caller's indices, one entry per (pair in different segments, shared value)
+    d2g_dev<unsigned long long> d_plist;   // pair list: (i | j << 32), i < j caller's indices, one entry per (pair in different segments, shared value)
     size_t plist_cap = 0;
     // the list BINNED by output region (band of 32 rows x chunk of 2^bin_cshift columns): what sp_compose_kernel reads
-    unsigned long long *d_plist2 = nullptr;
+    d2g_dev<unsigned long long> d_plist2;
     uint32_t *d_binc = nullptr;                       // [nbins] entries per bin (inside the block the prepare clears)
-    uint32_t *d_bstart = nullptr;                     // [nbins + 1] first entry of every bin in d_plist2
-    uint32_t *d_cw_ents = nullptr; unsigned long long *d_cw_vals = nullptr; size_t cw_ecap = 0, cw_vcap = 0;   // sp_emit_kernel -> sp_pairs_kernel: the holders of the mixed values, one record per value
-    uint32_t *d_hoff = nullptr;                       // [bin_nwg][nbins] where the entries a counting workgroup met go inside their bin (sp_hist_body -> sp_bin_kernel)
+    d2g_dev<uint32_t> d_bstart;                     // [nbins + 1] first entry of every bin in d_plist2
+    d2g_dev<uint32_t> d_cw_ents; d2g_dev<unsigned long long> d_cw_vals; size_t cw_ecap = 0, cw_vcap = 0;   // sp_emit_kernel -> sp_pairs_kernel: the holders of the mixed values, one record per value
+    d2g_dev<uint32_t> d_hoff;                       // [bin_nwg][nbins] where the entries a counting workgroup met go inside their bin (sp_hist_body -> sp_bin_kernel)
     uint32_t nbins = 0, bin_nch = 0, bin_cshift = 10, bin_nwg = 1;
     bool bin_ok = true;                               // the bins fit (sp_bin_geometry): otherwise the list is applied entry by entry only
     size_t tilebm_words = 0, tiles_cap = 0;
@@ -114,7 +114,6 @@ void d2g_bitslice_geometry(d2g_cmp_set *set);
 int  d2g_bitslice_alloc(d2g_ctx *ctx, d2g_cmp_set *set);
 int  d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s);
 int  d2g_bitslice_export(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s);
-void d2g_bitslice_free(d2g_cmp_set *set);
 int  d2g_bitslice_alloc_stream(d2g_ctx *ctx, d2g_cmp_set *set);
 int  d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s);   // caller's-order stream of a sparse set, on demand
 // engine-managed gathered operands (d2g_mgpu.hip): buffers for the sparse-tile path, and the call that says "every group has arrived and

@@ -198,9 +198,6 @@ extern "C" {
 void d2g_cmp_set_destroy(d2g_cmp_set *set) {
     if (!set) return;
     (void)hipSetDevice(set->ctx->device);
-    (void)hipFree(set->d_rows);
-    (void)hipFree(set->d_cols);
-    d2g_bitslice_free(set);
     delete set;
 }
 
@@ -250,12 +247,7 @@ int d2g_cmp_set_create_dev(d2g_ctx *ctx, const uint64_t *sig_bits_dev, size_t N,
     if (!set) return D2G_ERR_NOMEM;
     set->ctx = ctx; set->N = N; set->S = S;
     set->Npad = div_up<size_t>(N, K2_CB) * K2_CB;
-    hipError_t e;
-    if ((e = hipMalloc((void **)&set->d_cols, set->Npad * S * sizeof(uint64_t))) != hipSuccess) {
-        ctx->last_error = hipGetErrorString(e);
-        d2g_cmp_set_destroy(set);
-        return D2G_ERR_NOMEM;
-    }
+    if (int rc = set->d_cols.alloc(ctx, set->Npad * S, "cmp_set alloc")) { d2g_cmp_set_destroy(set); return rc; }
     set->algo = D2G_CMP_DIRECT;
     if (algo != D2G_CMP_DIRECT) {
         int rc = d2g_bitslice_alloc(ctx, set);
@@ -263,11 +255,7 @@ int d2g_cmp_set_create_dev(d2g_ctx *ctx, const uint64_t *sig_bits_dev, size_t N,
         else if (!(rc == D2G_ERR_UNSUPPORTED && algo == D2G_CMP_AUTO)) { d2g_cmp_set_destroy(set); return rc; }
     }
     if (set->algo == D2G_CMP_DIRECT) {
-        if ((e = hipMalloc((void **)&set->d_rows, (N + K2_RB) * S * sizeof(uint64_t))) != hipSuccess) {
-            ctx->last_error = hipGetErrorString(e);
-            d2g_cmp_set_destroy(set);
-            return D2G_ERR_NOMEM;
-        }
+        if (int rc = set->d_rows.alloc(ctx, (N + K2_RB) * S, "cmp_set alloc")) { d2g_cmp_set_destroy(set); return rc; }
         // slack rows past N are read (never stored) by a partial last row tile
         (void)hipMemsetAsync(set->d_rows + N * S, 0, (size_t)K2_RB * S * sizeof(uint64_t), s);
     }
@@ -315,10 +303,10 @@ int d2g_cmp_set_create(d2g_ctx *ctx, const uint64_t *sig_bits_host, size_t N, si
     if (!ctx || !out) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, sig_bits_host != nullptr && N >= 1 && S >= 1, "cmp_set: bad host matrix");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    uint64_t *tmp = nullptr;
-    D2G_HIP(ctx, hipMalloc((void **)&tmp, N * S * sizeof(uint64_t)));
+    d2g_dev<uint64_t> tmp;
+    if (int rc = tmp.alloc(ctx, N * S, "cmp_set staging alloc")) return rc;
     hipError_t e = hipMemcpy(tmp, sig_bits_host, N * S * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(tmp); ctx->last_error = hipGetErrorString(e); return D2G_ERR_HIP; }
+    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return D2G_ERR_HIP; }
     int rc = d2g_cmp_set_create_dev(ctx, tmp, N, S, algo, nullptr, out);
     (void)hipStreamSynchronize(nullptr);
     if (rc == D2G_OK && (*out)->algo == D2G_CMP_BITSLICE && d2g_bitslice_status(ctx, *out, nullptr) != D2G_OK) {
@@ -329,7 +317,6 @@ int d2g_cmp_set_create(d2g_ctx *ctx, const uint64_t *sig_bits_host, size_t N, si
         rc = algo == D2G_CMP_AUTO ? d2g_cmp_set_create_dev(ctx, tmp, N, S, D2G_CMP_DIRECT, nullptr, out) : (int)D2G_ERR_INTERNAL;
         (void)hipStreamSynchronize(nullptr);
     }
-    (void)hipFree(tmp);
     return rc;
 }
 
@@ -531,19 +518,15 @@ int d2g_cmp_eqcount_ut(d2g_ctx *ctx, const uint64_t *sig_bits, size_t N, size_t 
     d2g_cmp_set *set = nullptr;
     int rc = d2g_cmp_set_create(ctx, sig_bits, N, S, algo, &set);
     if (rc) return rc;
+    const std::unique_ptr<d2g_cmp_set, void (*)(d2g_cmp_set *)> set_owner(set, d2g_cmp_set_destroy);
     const size_t cnt = d2g_ut_count(N, r0, r1);
-    uint32_t *d_out = nullptr;
-    if (cnt) {
-        hipError_t e = hipMalloc((void **)&d_out, cnt * sizeof(uint32_t));
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); d2g_cmp_set_destroy(set); return D2G_ERR_NOMEM; }
-    }
+    d2g_dev<uint32_t> d_out;
+    if (cnt && (rc = d_out.alloc(ctx, cnt, "cmp output alloc"))) return rc;
     rc = d2g_cmp_eqcount_ut_dev(ctx, set, r0, r1, d_out, nullptr);
     if (rc == D2G_OK && cnt) {
         hipError_t e = hipMemcpy(neq_out, d_out, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost);
         if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = D2G_ERR_HIP; }
     }
-    (void)hipFree(d_out);
-    d2g_cmp_set_destroy(set);
     return rc;
 }
 
@@ -563,35 +546,34 @@ int d2g_cmp_dist_ut(d2g_ctx *ctx, const uint64_t *sig_bits, const double *cards,
     const bool need_gtlt = !multiset_space && (S & (S - 1)) != 0;
     int rc = d2g_cmp_set_create(ctx, sig_bits, N, S, need_gtlt ? (int)D2G_CMP_DIRECT : algo, &set);
     if (rc) return rc;
-    void *d_a = nullptr, *d_b = nullptr, *d_lut = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_a); (void)hipFree(d_b); (void)hipFree(d_lut); d2g_cmp_set_destroy(set); };
-#define D2G_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { ctx->last_error = hipGetErrorString(e__); cleanup(); return D2G_ERR_HIP; } } while (0)
-    D2G_TRY(hipMalloc(&d_a, cnt * 4));
+    const std::unique_ptr<d2g_cmp_set, void (*)(d2g_cmp_set *)> set_owner(set, d2g_cmp_set_destroy);
+    d2g_dev<uint32_t> d_a, d_b;
+    d2g_dev<float> d_lut;
+#define D2G_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { ctx->last_error = hipGetErrorString(e__); return D2G_ERR_HIP; } } while (0)
+    if ((rc = d_a.alloc(ctx, cnt, "cmp output alloc"))) return rc;
     if (have_lut) {
         // card-independent measure, value = f(neq): fused table epilogue on the device
-        D2G_TRY(hipMalloc(&d_lut, (S + 1) * sizeof(float)));
+        if ((rc = d_lut.alloc(ctx, S + 1, "cmp table alloc"))) return rc;
         D2G_TRY(hipMemcpy(d_lut, lut.data(), (S + 1) * sizeof(float), hipMemcpyHostToDevice));
-        rc = d2g_cmp_lut_ut_dev(ctx, set, r0, r1, (const float *)d_lut, (float *)d_a, nullptr);
+        rc = d2g_cmp_lut_ut_dev(ctx, set, r0, r1, d_lut, reinterpret_cast<float *>(d_a.get()), nullptr);
         if (rc == D2G_OK) D2G_TRY(hipMemcpy(out, d_a, cnt * 4, hipMemcpyDeviceToHost));
-        cleanup();
         return rc;
     }
     // integer counts from the device, x87 epilogue on the host (bit-exact with cmp_core.cpp:458-517)
     std::vector<uint32_t> ca(cnt), cb;
     if (need_gtlt) {
-        D2G_TRY(hipMalloc(&d_b, cnt * 4));
-        rc = d2g_cmp_gtlt_ut_dev(ctx, set, r0, r1, (uint32_t *)d_a, (uint32_t *)d_b, nullptr);
+        if ((rc = d_b.alloc(ctx, cnt, "cmp output alloc"))) return rc;
+        rc = d2g_cmp_gtlt_ut_dev(ctx, set, r0, r1, d_a, d_b, nullptr);
         if (rc == D2G_OK) {
             cb.resize(cnt);
             D2G_TRY(hipMemcpy(ca.data(), d_a, cnt * 4, hipMemcpyDeviceToHost));
             D2G_TRY(hipMemcpy(cb.data(), d_b, cnt * 4, hipMemcpyDeviceToHost));
         }
     } else {
-        rc = d2g_cmp_eqcount_ut_dev(ctx, set, r0, r1, (uint32_t *)d_a, nullptr);
+        rc = d2g_cmp_eqcount_ut_dev(ctx, set, r0, r1, d_a, nullptr);
         if (rc == D2G_OK) D2G_TRY(hipMemcpy(ca.data(), d_a, cnt * 4, hipMemcpyDeviceToHost));
     }
 #undef D2G_TRY
-    cleanup();
     if (rc) return rc;
     d2g_epilogue_ut(ca.data(), need_gtlt ? cb.data() : nullptr, cards, N, S, r0, r1, measure, k,
                          multiset_space, nthreads, out);

@@ -874,18 +874,6 @@ int launch_bitslice(d2g_ctx *ctx, const d2g_cmp_set *set, PairShape sh, Store st
 
 }  // namespace
 
-void d2g_bitslice_free(d2g_cmp_set *set) {
-    if (!set) return;
-    if (!set->borrowed) { (void)hipFree(set->d_planes); (void)hipFree(set->d_meta); }
-    (void)hipFree(set->d_stream);
-    (void)hipFree(set->d_ids);
-    (void)hipFree(set->d_colcnt);
-    (void)hipFree(set->d_perm);
-    (void)hipFree(set->d_owner); set->d_owner = nullptr;
-    set->d_planes = set->d_stream = set->d_meta = set->d_ids = set->d_colcnt = set->d_perm = nullptr;
-    sp_free(set);
-}
-
 // geometry of the bit-sliced operand: a function of N (and S) only, identical on every rank.
 // A column holds at most floor(N/2) values that occur twice; ranks 1..D2 plus the two codes of "unique"
 // (0 and 2^nbits - 1) need 2^nbits >= D2 + 2.
@@ -899,12 +887,7 @@ void d2g_bitslice_geometry(d2g_cmp_set *set) {
 // the plane stream: at most nbits_cap live planes per group, two codings each, + one block of slack (the
 // kernel's prefetch runs one plane past the end)
 int d2g_bitslice_alloc_stream(d2g_ctx *ctx, d2g_cmp_set *set) {
-    hipError_t e = hipMalloc((void **)&set->d_stream, ((size_t)set->ntb * set->nbits_cap + 1) * 2 * set->Nstride * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        ctx->last_error = std::string("bitslice alloc: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
-    }
-    return D2G_OK;
+    return set->d_stream.alloc(ctx, ((size_t)set->ntb * set->nbits_cap + 1) * 2 * set->Nstride, "bitslice alloc");
 }
 
 namespace {
@@ -928,17 +911,15 @@ int alloc_prepare_workspace(d2g_ctx *ctx, d2g_cmp_set *set) {
         }
         set->nsplit = want;
     }
-    hipError_t e;
-    if ((e = hipMalloc((void **)&set->d_ids, S * Npad * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemset(set->d_ids, 0, S * Npad * sizeof(uint32_t))) != hipSuccess ||     // split rank passes rely on "no stale pending word"
-        (e = hipMalloc((void **)&set->d_colcnt, S * BS_CC_STRIDE * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_perm, (size_t)set->ntb * 32 * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_meta, (size_t)(set->ntb + 4) * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemset(set->d_meta, 0, (size_t)(set->ntb + 4) * sizeof(uint32_t))) != hipSuccess) {
-        ctx->last_error = std::string("bitslice alloc: ") + hipGetErrorString(e);
-        d2g_bitslice_free(set);
-        return e == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
-    }
+    const char *what = "bitslice alloc";
+    int rc;
+    if ((rc = set->d_ids.alloc(ctx, S * Npad, what)) ||
+        (rc = d2g_hip_status(ctx, hipMemset(set->d_ids, 0, S * Npad * sizeof(uint32_t)), what)) ||     // split rank passes rely on "no stale pending word"
+        (rc = set->d_colcnt.alloc(ctx, S * BS_CC_STRIDE, what)) ||
+        (rc = set->d_perm.alloc(ctx, (size_t)set->ntb * 32, what)) ||
+        (rc = set->own_meta.alloc(ctx, (size_t)(set->ntb + 4), what)) ||
+        (rc = d2g_hip_status(ctx, hipMemset(set->own_meta, 0, (size_t)(set->ntb + 4) * sizeof(uint32_t)), what))) return rc;
+    set->d_meta = set->own_meta;
     return D2G_OK;
 }
 bool sort_columns(const d2g_ctx *ctx) {
@@ -950,19 +931,15 @@ bool sort_columns(const d2g_ctx *ctx) {
 // one-time allocation of the bit-sliced operand and its workspace
 int d2g_bitslice_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     if (int rc = alloc_prepare_workspace(ctx, set)) return rc;
-    hipError_t e;
-    if ((e = hipMalloc((void **)&set->d_planes, (size_t)set->ntb * (set->nbits_cap + 1) * set->Nstride * sizeof(uint32_t))) != hipSuccess) {
-        ctx->last_error = std::string("bitslice alloc: ") + hipGetErrorString(e);
-        d2g_bitslice_free(set);
-        return e == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
-    }
-    if (int rc = d2g_bitslice_alloc_stream(ctx, set)) { d2g_bitslice_free(set); return rc; }
+    if (int rc = set->own_planes.alloc(ctx, (size_t)set->ntb * (set->nbits_cap + 1) * set->Nstride, "bitslice alloc")) return rc;
+    set->d_planes = set->own_planes;
+    if (int rc = d2g_bitslice_alloc_stream(ctx, set)) return rc;
     set->ncols = set->S;
     set->sparse_ok = sparse_enabled(ctx, set->N) && set->S < 65536;          // (the sparse kernel packs two mismatch counts into one LDS word)
     if (set->sparse_ok && sp_alloc(ctx, set) != D2G_OK) { sp_free(set); (void)hipGetLastError(); set->sparse_ok = false; }
     if (set->sparse_ok && set->nsplit == 1) {                            // one holder per shared value, left by the rank kernel (sp_olink_kernel)
         set->owner_stride = set->N / 2 + 8;
-        if (hipMalloc((void **)&set->d_owner, set->S * set->owner_stride * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); set->d_owner = nullptr; }
+        if (set->d_owner.alloc(ctx, set->S * set->owner_stride, "bitslice owner alloc") != D2G_OK) (void)hipGetLastError();
     }   // no memory for the sparse path's buffers: the dense walk works without them
     return D2G_OK;
 }
@@ -985,20 +962,18 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     bool side_fill = false;
     if (set->ride_total >= SP_SIDE_FILL_PIECES) {
         if (!set->fill_stream) {
-            hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&e0, hipEventDisableTiming) == hipSuccess &&
-                hipEventCreateWithFlags(&e1, hipEventDisableTiming) == hipSuccess) { set->fill_stream = st; set->fill_fork = e0; set->fill_join = e1; }
-            else { (void)hipGetLastError(); if (st) (void)hipStreamDestroy(st); if (e0) (void)hipEventDestroy(e0); }
+            if (set->fill_stream.create(hipStreamNonBlocking) != hipSuccess || set->fill_fork.create(hipEventDisableTiming) != hipSuccess ||
+                set->fill_join.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); set->fill_stream.reset(); set->fill_fork.reset(); set->fill_join.reset(); }
         }
         if (set->fill_stream) {
             // behind everything already on `s` (the transpose of this update; whoever read the output last), beside everything this prepare enqueues
-            hipStream_t fs = (hipStream_t)set->fill_stream;
-            D2G_HIP(ctx, hipEventRecord((hipEvent_t)set->fill_fork, s));
-            D2G_HIP(ctx, hipStreamWaitEvent(fs, (hipEvent_t)set->fill_fork, 0));
+            hipStream_t fs = set->fill_stream;
+            D2G_HIP(ctx, hipEventRecord(set->fill_fork, s));
+            D2G_HIP(ctx, hipStreamWaitEvent(fs, set->fill_fork, 0));
             const SpRider all{set->ride_out, set->ride_cnt, set->ride_vsrc, set->ride_vimm, 0u, 0u};
             const unsigned fgrid = sp_side_fill_grid(ctx, set->ride_total, set->ride_cnt, N, S);
             hipLaunchKernelGGL(sp_side_fill_kernel, dim3(fgrid), dim3(256), 0, fs, all, set->ride_total);
-            D2G_HIP(ctx, hipEventRecord((hipEvent_t)set->fill_join, fs));
+            D2G_HIP(ctx, hipEventRecord(set->fill_join, fs));
             set->ride_next = set->ride_total;                            // nothing left for the riders
             side_fill = true;
         }
@@ -1044,7 +1019,7 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         if (int rc = sp_sample_collect(ctx, set, s)) return rc;         // (the first look, enqueued behind the rank kernel: the host waits for its word here)
         if (int rc = sp_prepare_order(ctx, set, split, s)) return rc;
         if (int rc = sp_permute(ctx, set, s)) return rc;
-        if (side_fill) D2G_HIP(ctx, hipStreamWaitEvent(s, (hipEvent_t)set->fill_join, 0));     // the launch writes into the filled output
+        if (side_fill) D2G_HIP(ctx, hipStreamWaitEvent(s, set->fill_join, 0));     // the launch writes into the filled output
         set->srt_valid = true; set->nat_valid = true;
         if (set->ride_total) { set->prefilled = set->ride_out; set->prefilled_cnt = set->ride_cnt; set->prefilled_pieces = set->ride_next; set->prefilled_src = set->ride_vsrc; set->prefilled_by_riders = true; }   // (the launch fills what is left)
         else if (set->prefilled_by_riders) set->prefilled = nullptr;        // what an EARLIER prepare's riders wrote is void once another prepare has run (the caller may have used the buffer in between)
@@ -1096,9 +1071,8 @@ int d2g_bitslice_exporter_create(d2g_ctx *ctx, size_t N, size_t S_local, d2g_cmp
     set->Npad = div_up<size_t>(N, BS_CB) * BS_CB;
     set->algo = D2G_CMP_BITSLICE;
     set->export_only = true;
-    hipError_t e = hipMalloc((void **)&set->d_cols, set->Npad * S_local * sizeof(uint64_t));
-    if (e != hipSuccess) { ctx->last_error = std::string("bitslice exporter alloc: ") + hipGetErrorString(e); delete set; return D2G_ERR_NOMEM; }
-    if (int rc = alloc_prepare_workspace(ctx, set)) { (void)hipFree(set->d_cols); delete set; return rc; }
+    if (int rc = set->d_cols.alloc(ctx, set->Npad * S_local, "bitslice exporter alloc")) { delete set; return rc; }
+    if (int rc = alloc_prepare_workspace(ctx, set)) { delete set; return rc; }
     *out = set;
     return D2G_OK;
 }
@@ -1180,16 +1154,15 @@ int d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     if (!set->borrowed || set->sparse_ok) return D2G_OK;
     set->ncols = (size_t)set->ntb * 32;
     if (!(sparse_enabled(ctx, set->N) && set->S < 65536)) return D2G_OK;
-    hipError_t e;
-    if ((e = hipMalloc((void **)&set->d_ids, set->ncols * set->Npad * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_colcnt, set->ncols * BS_CC_STRIDE * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMemset(set->d_colcnt, 0, set->ncols * BS_CC_STRIDE * sizeof(uint32_t))) != hipSuccess) {
+    const char *what = "bitslice sparse alloc";
+    if (set->d_ids.alloc(ctx, set->ncols * set->Npad, what) != D2G_OK ||
+        set->d_colcnt.alloc(ctx, set->ncols * BS_CC_STRIDE, what) != D2G_OK ||
+        hipMemset(set->d_colcnt, 0, set->ncols * BS_CC_STRIDE * sizeof(uint32_t)) != hipSuccess) {
         // not enough memory for the sparse path's buffers: the dense walk works without them
-        (void)hipFree(set->d_ids); (void)hipFree(set->d_colcnt); set->d_ids = set->d_colcnt = nullptr;
+        set->d_ids.reset(); set->d_colcnt.reset();
         (void)hipGetLastError();
         return D2G_OK;
     }
-    set->ids_owned = true;
     if (sp_alloc(ctx, set) != D2G_OK) { sp_free(set); (void)hipGetLastError(); return D2G_OK; }
     set->sparse_ok = true;
     return D2G_OK;

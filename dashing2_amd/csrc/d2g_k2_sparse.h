@@ -1426,32 +1426,30 @@ int sp_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     // the workgroups that count (and then move) the list's entries: one per ~16 384 entries of a full list, at most two per CU
     set->bin_nwg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)std::max(ctx->num_cus / 2, 1), div_up<size_t>(set->plist_cap, 16384)));   // (128 of them measured best at config 3: 64 / 128 / 512 / 1024 -> counting + moving 90 / 65 / 70 / 84 us)
     const size_t planes_words = (size_t)set->ntb * set->nbits_cap + 1;
-    hipError_t e;
-    if ((e = hipMalloc((void **)&set->d_stream_s, planes_words * 2 * Nstride * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_rowstream, planes_words * Nstride * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_sperm, Nstride * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_sinv, Npad * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_label, 2 * Npad * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_hint, 2 * Npad * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_segend, Npad * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_posseg, Npad * 8)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_spz, set->spz_words * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_rowpos, Nstride * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_rowk, Npad * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_spctl, (2 * SP_CTL_WORDS + set->tilebm_words) * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_tiles, 8 * std::max<size_t>(set->tiles_cap, 1) * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_tiles_full, 8 * std::max<size_t>(set->tiles_cap, 1) * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_plist, set->plist_cap * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_plist2, set->plist_cap * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_bstart, ((size_t)set->nbins + 1) * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_samp, (SP_SAMPLE_ROWS * Npad + 8) * 4)) != hipSuccess ||
-        (e = hipMemset(set->d_samp, 0, (SP_SAMPLE_ROWS * Npad + 8) * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_cw_ents, set->cw_ecap * 4)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_cw_vals, set->cw_vcap * 16)) != hipSuccess ||
-        (e = hipMalloc((void **)&set->d_hoff, std::max<size_t>((size_t)set->bin_nwg * set->nbins, 1) * 4)) != hipSuccess) {
-        ctx->last_error = std::string("bitslice sparse alloc: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
-    }
+    const char *what = "bitslice sparse alloc";
+    int rc;
+    if ((rc = set->d_stream_s.alloc(ctx, planes_words * 2 * Nstride, what)) ||
+        (rc = set->d_rowstream.alloc(ctx, planes_words * Nstride, what)) ||
+        (rc = set->d_sperm.alloc(ctx, Nstride, what)) ||
+        (rc = set->d_sinv.alloc(ctx, Npad, what)) ||
+        (rc = set->d_label.alloc(ctx, 2 * Npad, what)) ||
+        (rc = set->d_hint.alloc(ctx, 2 * Npad, what)) ||
+        (rc = set->d_segend.alloc(ctx, Npad, what)) ||
+        (rc = set->d_posseg.alloc(ctx, Npad * 2, what)) ||
+        (rc = set->d_spz.alloc(ctx, set->spz_words, what)) ||
+        (rc = set->d_rowpos.alloc(ctx, Nstride, what)) ||
+        (rc = set->d_rowk.alloc(ctx, Npad, what)) ||
+        (rc = set->d_spctl.alloc(ctx, 2 * SP_CTL_WORDS + set->tilebm_words, what)) ||
+        (rc = set->d_tiles.alloc(ctx, 8 * std::max<size_t>(set->tiles_cap, 1), what)) ||
+        (rc = set->d_tiles_full.alloc(ctx, 8 * std::max<size_t>(set->tiles_cap, 1), what)) ||
+        (rc = set->d_plist.alloc(ctx, set->plist_cap, what)) ||
+        (rc = set->d_plist2.alloc(ctx, set->plist_cap, what)) ||
+        (rc = set->d_bstart.alloc(ctx, (size_t)set->nbins + 1, what)) ||
+        (rc = set->d_samp.alloc(ctx, SP_SAMPLE_ROWS * Npad + 8, what)) ||
+        (rc = d2g_hip_status(ctx, hipMemset(set->d_samp, 0, (SP_SAMPLE_ROWS * Npad + 8) * 4), what)) ||
+        (rc = set->d_cw_ents.alloc(ctx, set->cw_ecap, what)) ||
+        (rc = set->d_cw_vals.alloc(ctx, set->cw_vcap * 2, what)) ||                      // (a record per value: 16 bytes)
+        (rc = set->d_hoff.alloc(ctx, std::max<size_t>((size_t)set->bin_nwg * set->nbins, 1), what))) return rc;
     set->d_lcnt = set->d_spz;
     set->d_gbm = set->d_lcnt + (Npad + 1);
     set->d_order = set->d_gbm + 8 + set->tilebm_words;
@@ -1459,33 +1457,21 @@ int sp_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     set->d_fullctl = set->d_plctl + 12;
     set->d_binc = set->d_fullctl + SP_CTL_WORDS;
     set->d_tilebm = set->d_spctl + 2 * SP_CTL_WORDS;
-    if ((e = hipMemset(set->d_spctl, 0, 2 * SP_CTL_WORDS * 4)) != hipSuccess) { ctx->last_error = std::string("bitslice sparse alloc: ") + hipGetErrorString(e); return D2G_ERR_HIP; }
+    if ((rc = d2g_hip_status(ctx, hipMemset(set->d_spctl, 0, 2 * SP_CTL_WORDS * 4), what))) return rc;
     // one word of host memory the device can write: the remembered give-up (sp_prepare_order)
-    if (hipHostMalloc((void **)&set->h_gaveup, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void **)&set->d_gaveup, set->h_gaveup, 0) == hipSuccess) std::memset(set->h_gaveup, 0, 64);   // (all 16 words: the first look's ticket word must not hold what an earlier owner of the page left)
-    else { (void)hipGetLastError(); if (set->h_gaveup) (void)hipHostFree(set->h_gaveup); set->h_gaveup = nullptr; set->d_gaveup = set->d_order + 7; }   // (no mapped host memory: a spare device word, never read by the host)
+    if (set->h_gaveup.alloc(ctx, 16, what, hipHostMallocMapped) == D2G_OK && hipHostGetDevicePointer((void **)&set->d_gaveup, set->h_gaveup, 0) == hipSuccess) std::memset(set->h_gaveup, 0, 64);   // (all 16 words: the first look's ticket word must not hold what an earlier owner of the page left)
+    else { (void)hipGetLastError(); set->h_gaveup.reset(); set->d_gaveup = set->d_order + 7; }   // (no mapped host memory: a spare device word, never read by the host)
     set->sp_launch = 0;
     return D2G_OK;
 }
 
+// sp_alloc failed half-way: the set goes on with the dense walk, and the sparse path's buffers go back now (not when the set is destroyed)
 void sp_free(d2g_cmp_set *set) {
-    for (uint32_t **p : {&set->d_stream_s, &set->d_sperm, &set->d_sinv, &set->d_label, &set->d_hint, &set->d_segend, &set->d_posseg, &set->d_spz, &set->d_rowpos, &set->d_rowk,
-                         &set->d_rowstream, &set->d_tiles, &set->d_tiles_full, &set->d_spctl}) { (void)hipFree(*p); *p = nullptr; }
-    (void)hipFree(set->d_plist); set->d_plist = nullptr;
-    (void)hipFree(set->d_plist2); set->d_plist2 = nullptr;
-    (void)hipFree(set->d_bstart); set->d_bstart = nullptr;
-    (void)hipFree(set->d_hoff); set->d_hoff = nullptr;
-    (void)hipFree(set->d_samp); set->d_samp = nullptr;
-    if (set->fill_stream) { (void)hipStreamDestroy((hipStream_t)set->fill_stream); set->fill_stream = nullptr; }
-    if (set->fill_fork) { (void)hipEventDestroy((hipEvent_t)set->fill_fork); set->fill_fork = nullptr; }
-    if (set->fill_join) { (void)hipEventDestroy((hipEvent_t)set->fill_join); set->fill_join = nullptr; }
-    if (set->samp_stream) { (void)hipStreamDestroy((hipStream_t)set->samp_stream); set->samp_stream = nullptr; }
-    if (set->samp_event) { (void)hipEventDestroy((hipEvent_t)set->samp_event); set->samp_event = nullptr; }
-    (void)hipFree(set->d_cw_ents); set->d_cw_ents = nullptr;
-    (void)hipFree(set->d_cw_vals); set->d_cw_vals = nullptr;
-    set->d_binc = nullptr;
-    if (set->h_gaveup) { (void)hipHostFree(set->h_gaveup); set->h_gaveup = nullptr; }
-    set->d_gaveup = nullptr;
-    set->d_tilebm = set->d_lcnt = set->d_gbm = set->d_order = set->d_plctl = set->d_fullctl = nullptr;
+    for (d2g_dev<uint32_t> *p : {&set->d_stream_s, &set->d_sperm, &set->d_sinv, &set->d_label, &set->d_hint, &set->d_segend, &set->d_posseg, &set->d_spz, &set->d_rowpos, &set->d_rowk,
+                                 &set->d_rowstream, &set->d_tiles, &set->d_tiles_full, &set->d_spctl, &set->d_bstart, &set->d_hoff, &set->d_samp, &set->d_cw_ents}) p->reset();
+    set->d_plist.reset(); set->d_plist2.reset(); set->d_cw_vals.reset(); set->h_gaveup.reset();
+    set->fill_stream.reset(); set->fill_fork.reset(); set->fill_join.reset(); set->samp_stream.reset(); set->samp_event.reset();
+    set->d_gaveup = set->d_binc = set->d_tilebm = set->d_lcnt = set->d_gbm = set->d_order = set->d_plctl = set->d_fullctl = nullptr;
 }
 
 // what the kernel in front of sp_prepare_order initialises for it: label[j] = j, the hints, and the zero block (counters,
@@ -1619,7 +1605,7 @@ SpRider sp_take_rider(d2g_cmp_set *set, unsigned own, unsigned weight, bool last
     return r;
 }
 SpColWork sp_colwork_of(const d2g_cmp_set *set) {
-    return SpColWork{set->d_cw_ents, reinterpret_cast<uint4 *>(set->d_cw_vals), (uint32_t)std::min<size_t>(set->cw_ecap, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(set->cw_vcap, 0xFFFFFFFFu)};
+    return SpColWork{set->d_cw_ents, reinterpret_cast<uint4 *>(set->d_cw_vals.get()), (uint32_t)std::min<size_t>(set->cw_ecap, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(set->cw_vcap, 0xFFFFFFFFu)};
 }
 SpPairs sp_pairs_of(const d2g_cmp_set *set, const SpColWork &cw, const uint32_t *seg) {
     return SpPairs{cw, seg, set->d_plctl, set->d_plist, (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu), set->d_order, set->d_gaveup, set->d_fullctl};
@@ -1667,14 +1653,12 @@ int sp_sample_enqueue(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     // on a stream of their own, behind the rank kernel: the column plan (ONE workgroup) and the planes kernel run beside them.  No join: the host
     // waits for the sample's word before it enqueues anything else, and nothing the two kernels read is written before the set's next prepare.
     if (!set->samp_stream) {
-        hipStream_t st = nullptr; hipEvent_t ev = nullptr;
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) { set->samp_stream = st; set->samp_event = ev; }
-        else { (void)hipGetLastError(); if (st) (void)hipStreamDestroy(st); }
+        if (set->samp_stream.create(hipStreamNonBlocking) != hipSuccess || set->samp_event.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); set->samp_stream.reset(); set->samp_event.reset(); }
     }
     if (set->samp_stream) {
-        D2G_HIP(ctx, hipEventRecord((hipEvent_t)set->samp_event, s));
-        D2G_HIP(ctx, hipStreamWaitEvent((hipStream_t)set->samp_stream, (hipEvent_t)set->samp_event, 0));
-        s = (hipStream_t)set->samp_stream;
+        D2G_HIP(ctx, hipEventRecord(set->samp_event, s));
+        D2G_HIP(ctx, hipStreamWaitEvent(set->samp_stream, set->samp_event, 0));
+        s = set->samp_stream;
     }
 #endif
     const bool wide = sp_sample_field_bits(set->ncols) == 16;           // (d_samp holds SP_SAMPLE_ROWS words per sketch: 16-bit fields fill all of them)
@@ -1701,7 +1685,7 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         uint32_t spins = 0;
         while (__atomic_load_n(&set->h_gaveup[6], __ATOMIC_ACQUIRE) != set->sample_ticket) {
             __builtin_ia32_pause();
-            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(250)) { D2G_HIP(ctx, hipStreamSynchronize(set->samp_stream ? (hipStream_t)set->samp_stream : s)); break; }
+            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(250)) { D2G_HIP(ctx, hipStreamSynchronize(set->samp_stream ? set->samp_stream : s)); break; }
         }
     }
     const double scale = (double)N / (2.0 * SP_SAMPLE_ROWS), pairs = (double)N * (double)(N - 1) / 2.0;
@@ -1781,7 +1765,7 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
       hipLaunchKernelGGL(sp_scan_kernel, dim3(g), dim3(1024), 0, s, set->d_lcnt, N, set->d_order, la, set->d_segend, seg_limit, set->d_gaveup, rd); }    // la (labels) is dead after the count kernel: it keeps the segment starts
     { unsigned g; const SpRider rd = sp_take_rider(set, (unsigned)div_up<size_t>(set->Nstride, 256), 0, true, &g, 32);
       hipLaunchKernelGGL(sp_place_kernel, dim3(g), dim3(256), 0, s, lb, N, set->Nstride, set->d_lcnt, set->d_sperm, set->d_sinv, set->d_order,
-                         la, set->d_segend, CW, set->d_gbm + 8, reinterpret_cast<uint2 *>(set->d_posseg), rd); }
+                         la, set->d_segend, CW, set->d_gbm + 8, reinterpret_cast<uint2 *>(set->d_posseg.get()), rd); }
     // (a certificate pass in front -- one thread per (column, sketch) comparing the sketch's segment with that of its value's owner, so that
     // columns where nothing crosses a segment need no workgroup here -- was measured: 17 us for the pass, and the 17 stragglers a clean
     // collection of 10 000 leaves still put a mixed value into a hundred columns, whose workgroups take as long as before: 0.338 vs 0.329 ms)
@@ -1810,7 +1794,7 @@ int sp_permute(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     const uint32_t part = (uint32_t)(div_up<size_t>(div_up<size_t>(set->Nstride, H), 4) * 4);
     SpFullList fl{set->d_gbm + 8, (uint32_t)nrb, (uint32_t)ncb, (uint32_t)((ncb + 31) / 32), set->d_tiles_full, (uint32_t)set->tiles_cap, set->d_fullctl,
                   (uint32_t)std::min<size_t>(sp_full_candidates(set->Npad), 0xFFFFFFFFu), (uint32_t)div_up<size_t>(ntile, 1024), (uint32_t)set->N,
-                  reinterpret_cast<const uint2 *>(set->d_posseg)};
+                  reinterpret_cast<const uint2 *>(set->d_posseg.get())};
     const size_t nperm = (size_t)set->ntb * set->nbits_cap * (both ? 1 : 2) * H;
     const uint32_t plcap = (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu);
     // behind the list builders: the workgroups that count a LONG list per output bin, or those that make the pairs of a short one
@@ -1916,9 +1900,9 @@ int launch_sparse(d2g_ctx *ctx, const d2g_cmp_set *cset, PairShape sh, Store sto
     if (own_list)
         hipLaunchKernelGGL(sp_list_kernel, dim3((unsigned)div_up<size_t>(ntile, 1024)), dim3(1024), 0, s, bm, nrb, ncb, CW, full ? 1 : 0,
                            tiles, (uint32_t)set->tiles_cap, ctl, cand32, set->d_order, ctl_next, (uint32_t)N, full ? (const uint32_t *)nullptr : set->d_rowpos,
-                           reinterpret_cast<const uint2 *>(set->d_posseg));
+                           reinterpret_cast<const uint2 *>(set->d_posseg.get()));
     SpArgs a{set->d_stream_s, set->Nstride, full ? (const uint32_t *)nullptr : set->d_rowstream, set->Nstride, set->d_meta, set->ntb, (uint32_t)set->S, (uint32_t)N,
-             set->d_sperm, set->d_rowpos, tiles, ctl, ncb, cand32, (uint32_t)set->tiles_cap, reinterpret_cast<const uint2 *>(set->d_posseg)};
+             set->d_sperm, set->d_rowpos, tiles, ctl, ncb, cand32, (uint32_t)set->tiles_cap, reinterpret_cast<const uint2 *>(set->d_posseg.get())};
     // contiguous 32 KB per workgroup, workgroups in dispatch order: a streaming write (6.1 TB/s at N = 50 000: 825 us; the grid-stride loop over 16
     // workgroups per CU it replaces, whose iterations lie 16 MB apart, reached 4.6: 1105 us).  One store per thread is faster still (722-760 us) but when
     // the launch turns out dense all of its 19 M waves start only to return: 254 us instead of 34
@@ -1947,7 +1931,7 @@ int launch_sparse(d2g_ctx *ctx, const d2g_cmp_set *cset, PairShape sh, Store sto
         hipLaunchKernelGGL((sp_compose_kernel<Store>), dim3((unsigned)nwg), dim3(SP_CMP_T), 0, s, ca, sh, store);
     }
     // (a short list is applied entry by entry: the pair kernel's tail adds, the gated launch behind it turns the sums into table values)
-    SpPatchArgs pa{set->d_plist, set->d_plctl, (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu), ctl, cand32, set->d_sinv, set->d_rowk, set->d_rowpos, reinterpret_cast<const uint2 *>(set->d_posseg), (uint32_t)N, bm, CW, (uint32_t)r0, (uint32_t)r1, full ? 1 : 0, std::min<uint32_t>(grid, (uint32_t)ctx->num_cus * 8u)};
+    SpPatchArgs pa{set->d_plist, set->d_plctl, (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu), ctl, cand32, set->d_sinv, set->d_rowk, set->d_rowpos, reinterpret_cast<const uint2 *>(set->d_posseg.get()), (uint32_t)N, bm, CW, (uint32_t)r0, (uint32_t)r1, full ? 1 : 0, std::min<uint32_t>(grid, (uint32_t)ctx->num_cus * 8u)};
     hipLaunchKernelGGL((k2_bitslice_sparse_kernel<SP_JR, Store>), dim3(grid), dim3(64 * D2G_SP_KS), 0, s, a, sh, store, pa);
     // behind the gate: every tile of the caller's-order operand in dense mode; otherwise the second step of a short pair list (table epilogue)
     if (dsh.nvalid_total)

@@ -1185,50 +1185,40 @@ uint32_t ceil_log2(uint64_t x) { uint32_t b = 0; while ((1ull << b) < x) ++b; re
 // grow-only work buffers of the --multiset path (owned by a sketcher or by a one-shot call)
 struct d2g_k3_state {
     d2g_ctx *ctx = nullptr;
-    uint32_t *d_gtab = nullptr; size_t cap_gtab = 0;        // g_bbits [n] + g_boff [n+1]
-    uint64_t *d_koff = nullptr; size_t cap_koff = 0;        // [n+1]
-    uint32_t *d_bucket_cnt = nullptr; size_t cap_bcnt = 0;
-    uint64_t *d_bucket_off = nullptr; size_t cap_boff = 0;
-    uint64_t *d_cursor = nullptr; size_t cap_cursor = 0;
-    uint32_t *d_l2 = nullptr; size_t cap_l2 = 0;     // two-level split: coarse bucket table
-    uint32_t *d_blk_coarse = nullptr; size_t cap_blk_coarse = 0;
-    uint64_t *d_gq = nullptr; size_t cap_gq = 0;     // survivors of the light first pass (QEntry)
-    uint64_t *d_gq_off = nullptr; size_t cap_gq_off = 0;   // [grid+1] region offsets, then [grid] u32 counts
+    d2g_dev<uint32_t> d_gtab;        // g_bbits [n] + g_boff [n+1]
+    d2g_dev<uint64_t> d_koff;        // [n+1]
+    d2g_dev<uint32_t> d_bucket_cnt;
+    d2g_dev<uint64_t> d_bucket_off;
+    d2g_dev<uint64_t> d_cursor;
+    d2g_dev<uint32_t> d_l2;     // two-level split: coarse bucket table
+    d2g_dev<uint32_t> d_blk_coarse;
+    d2g_dev<uint64_t> d_gq;     // survivors of the light first pass (QEntry)
+    d2g_dev<uint64_t> d_gq_off;   // [grid+1] region offsets, then [grid] u32 counts
     int light_overflows = 0;
-    hipStream_t xs = nullptr;                        // second stream of the sub-batch pipeline
-    hipEvent_t ev_a[8] = {}, ev_b = nullptr;
+    d2g_stream xs;                                   // second stream of the sub-batch pipeline
+    d2g_event ev_a[8], ev_b;
     int pipelined_calls = 0;
-    uint64_t *d_keys = nullptr; size_t cap_keys = 0;
-    uint64_t *d_skeys = nullptr; size_t cap_skeys = 0;      // big inputs: keys regrouped by sub-range
-    uint32_t *d_gblk = nullptr; size_t cap_gblk = 0;        // compact path: first launch-plan block of each genome
-    uint16_t *d_tile_cnt = nullptr; size_t cap_tile_cnt = 0;
-    uint32_t *d_tile_off = nullptr; size_t cap_tile_off = 0;
-    uint64_t *d_sub_off = nullptr; size_t cap_sub_off = 0;
-    uint32_t *d_gsplit = nullptr; size_t cap_gsplit = 0;
-    uint64_t *d_gsub = nullptr; size_t cap_gsub = 0;
-    uint64_t *d_h = nullptr; size_t cap_h = 0;
-    double *d_tw = nullptr; size_t cap_tw = 0;
-    int *d_status = nullptr;               // [0] status, [1] nredo
-    uint64_t *d_guess = nullptr; size_t cap_guess = 0;
-    double *d_tw_bucket = nullptr; size_t cap_twb = 0;
+    d2g_dev<uint64_t> d_keys;
+    d2g_dev<uint64_t> d_skeys;      // big inputs: keys regrouped by sub-range
+    d2g_dev<uint32_t> d_gblk;        // compact path: first launch-plan block of each genome
+    d2g_dev<uint16_t> d_tile_cnt;
+    d2g_dev<uint32_t> d_tile_off;
+    d2g_dev<uint64_t> d_sub_off;
+    d2g_dev<uint32_t> d_gsplit;
+    d2g_dev<uint64_t> d_gsub;
+    d2g_dev<uint64_t> d_h;
+    d2g_dev<double> d_tw;
+    d2g_dev<int> d_status;                 // [0] status, [1] nredo
+    d2g_dev<uint64_t> d_guess;
+    d2g_dev<double> d_tw_bucket;
     int last_nredo = 0;
-    uint32_t *d_redo = nullptr; size_t cap_redo = 0;
-    uint32_t *d_out_counts = nullptr; size_t cap_oc = 0;
-    uint32_t *d_bucket_nd = nullptr; size_t cap_nd = 0;
-    uint64_t *d_out_keys = nullptr; size_t cap_ok = 0;
+    d2g_dev<uint32_t> d_redo;
+    d2g_dev<uint32_t> d_out_counts;
+    d2g_dev<uint32_t> d_bucket_nd;
+    d2g_dev<uint64_t> d_out_keys;
 };
 
-void d2g_k3_state_destroy(d2g_k3_state *st) {
-    if (!st) return;
-    (void)hipFree(st->d_gtab); (void)hipFree(st->d_koff); (void)hipFree(st->d_bucket_cnt); (void)hipFree(st->d_bucket_off); (void)hipFree(st->d_cursor); (void)hipFree(st->d_l2); (void)hipFree(st->d_blk_coarse); (void)hipFree(st->d_gq); (void)hipFree(st->d_gq_off);
-    for (auto &e : st->ev_a) if (e) (void)hipEventDestroy(e);
-    if (st->ev_b) (void)hipEventDestroy(st->ev_b);
-    if (st->xs) (void)hipStreamDestroy(st->xs);
-    (void)hipFree(st->d_keys); (void)hipFree(st->d_skeys); (void)hipFree(st->d_sub_off); (void)hipFree(st->d_gsplit); (void)hipFree(st->d_gsub); (void)hipFree(st->d_h); (void)hipFree(st->d_tw);
-    (void)hipFree(st->d_status); (void)hipFree(st->d_guess); (void)hipFree(st->d_tw_bucket); (void)hipFree(st->d_redo); (void)hipFree(st->d_out_counts); (void)hipFree(st->d_bucket_nd);
-    (void)hipFree(st->d_out_keys); (void)hipFree(st->d_gblk); (void)hipFree(st->d_tile_cnt); (void)hipFree(st->d_tile_off);
-    delete st;
-}
+void d2g_k3_state_destroy(d2g_k3_state *st) { delete st; }
 
 namespace {
 
@@ -1319,15 +1309,15 @@ int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_
 int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, size_t nblk, const K3Host &kh, size_t n,
            uint64_t xormask, size_t m, double thr, bool count_only, bool distinct_only = false) {
     const uint32_t TB = kh.TB;
-    if (int rc = d2g_grow(ctx, &st->d_gtab, &st->cap_gtab, 2 * n + 1)) return rc;
-    if (int rc = d2g_grow(ctx, &st->d_bucket_cnt, &st->cap_bcnt, (size_t)TB + 1)) return rc;
-    if (int rc = d2g_grow(ctx, &st->d_bucket_off, &st->cap_boff, (size_t)TB + 1)) return rc;
-    if (int rc = d2g_grow(ctx, &st->d_cursor, &st->cap_cursor, (size_t)TB + 1)) return rc;
+    if (int rc = st->d_gtab.grow(ctx, 2 * n + 1, 4096)) return rc;
+    if (int rc = st->d_bucket_cnt.grow(ctx, (size_t)TB + 1, 4096)) return rc;
+    if (int rc = st->d_bucket_off.grow(ctx, (size_t)TB + 1, 4096)) return rc;
+    if (int rc = st->d_cursor.grow(ctx, (size_t)TB + 1, 4096)) return rc;
     // 8 bytes of masked key per k-mer on the generic path, 4 bytes of stored word on the compact one
     const uint64_t key_words = kh.compact ? (kh.total + 1) / 2 : kh.total;
-    if (int rc = d2g_grow(ctx, &st->d_keys, &st->cap_keys, std::max<uint64_t>(key_words, 1))) return rc;
-    if (!st->d_status) D2G_HIP(ctx, hipMalloc((void **)&st->d_status, 2 * sizeof(int)));
-    if (int rc = d2g_grow(ctx, &st->d_koff, &st->cap_koff, n + 1)) return rc;
+    if (int rc = st->d_keys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
+    if (!st->d_status) if (int rc = st->d_status.alloc(ctx, 2, "k3 status alloc")) return rc;
+    if (int rc = st->d_koff.grow(ctx, n + 1, 4096)) return rc;
     D2G_HIP(ctx, hipMemcpyAsync(st->d_gtab, kh.gtab.data(), (2 * n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     D2G_HIP(ctx, hipMemcpyAsync(st->d_koff, kh.koff.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     D2G_HIP(ctx, hipMemsetAsync(st->d_bucket_cnt, 0, ((size_t)TB + 1) * sizeof(uint32_t), s));
@@ -1373,14 +1363,14 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
         // 4-byte stored words, tile-sorted split: histogram per tile -> per-tile write offsets -> coalesced flush
         D2G_CHECK(ctx, kh.gblk[n] == nblk, "internal: K3 block layout disagrees with the launch plan");
         const size_t ntiles = nblk * K1_CPT;
-        if (int rc = d2g_grow(ctx, &st->d_gblk, &st->cap_gblk, n + 1)) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_tile_cnt, &st->cap_tile_cnt, std::max<size_t>(ntiles, 1) * K3C_MAXB)) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_tile_off, &st->cap_tile_off, std::max<size_t>(ntiles, 1) * K3C_MAXB)) return rc;
+        if (int rc = st->d_gblk.grow(ctx, n + 1, 4096)) return rc;
+        if (int rc = st->d_tile_cnt.grow(ctx, std::max<size_t>(ntiles, 1) * K3C_MAXB, 4096)) return rc;
+        if (int rc = st->d_tile_off.grow(ctx, std::max<size_t>(ntiles, 1) * K3C_MAXB, 4096)) return rc;
         D2G_HIP(ctx, hipMemcpyAsync(st->d_gblk, kh.gblk.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         K3cArgs c;
         c.km = km; c.g_bbits = st->d_gtab; c.g_boff = st->d_gtab + n; c.g_koff = st->d_koff; c.g_blk = st->d_gblk;
         c.tile_cnt = st->d_tile_cnt; c.tile_off = st->d_tile_off; c.bucket_cnt = st->d_bucket_cnt; c.bucket_off = st->d_bucket_off;
-        c.keys32 = reinterpret_cast<uint32_t *>(st->d_keys); c.hb = kh.hb; c.TB = TB;
+        c.keys32 = reinterpret_cast<uint32_t *>(st->d_keys.get()); c.hb = kh.hb; c.TB = TB;
         if (nblk) hipLaunchKernelGGL(k3c_hist_kernel, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, c);
         hipLaunchKernelGGL(k3c_scan_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, c);
         if (nblk) {
@@ -1397,13 +1387,13 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
         const size_t nl2 = kh.l2_tb0.size();
         if (nl2) {
             // the coarse keys borrow the sub-range buffer: k3_split_kernel (big inputs) runs after the refinement
-            if (int rc = d2g_grow(ctx, &st->d_skeys, &st->cap_skeys, std::max<uint64_t>(key_words, 1))) return rc;
-            if (int rc = d2g_grow(ctx, &st->d_l2, &st->cap_l2, 2 * nl2)) return rc;
+            if (int rc = st->d_skeys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
+            if (int rc = st->d_l2.grow(ctx, 2 * nl2, 4096)) return rc;
             D2G_HIP(ctx, hipMemcpyAsync(st->d_l2, kh.l2_tb0.data(), nl2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
             D2G_HIP(ctx, hipMemcpyAsync(st->d_l2 + nl2, kh.l2_bits.data(), nl2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
             a.coarse = st->d_skeys; a.l2_tb0 = st->d_l2; a.l2_bits = st->d_l2 + nl2;
         }
-        if (int rc = d2g_grow(ctx, &st->d_blk_coarse, &st->cap_blk_coarse, std::max<size_t>(nblk, 1) << kh.l1bits)) return rc;
+        if (int rc = st->d_blk_coarse.grow(ctx, std::max<size_t>(nblk, 1) << kh.l1bits, 4096)) return rc;
         a.blk_coarse = st->d_blk_coarse;
         a.g0 = 0; a.n_genomes = (uint32_t)n;
         ka = a;
@@ -1411,19 +1401,19 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
     }
     BmhArgs b;
     std::memset(&b, 0, sizeof(b));
-    b.keys = st->d_keys; b.keys32 = reinterpret_cast<const uint32_t *>(st->d_keys); b.g_bbits = st->d_gtab; b.hb = kh.hb; b.xormask = xormask;
+    b.keys = st->d_keys; b.keys32 = reinterpret_cast<const uint32_t *>(st->d_keys.get()); b.g_bbits = st->d_gtab; b.hb = kh.hb; b.xormask = xormask;
     b.bucket_off = st->d_bucket_off; b.g_boff = st->d_gtab + n;
     b.n = (uint32_t)n; b.TB = TB; b.m = (uint32_t)m; b.thr = thr; b.status = st->d_status;
     if (kh.any_split) {
         const uint64_t nsub = kh.gsub[n];
-        if (int rc = d2g_grow(ctx, &st->d_skeys, &st->cap_skeys, std::max<uint64_t>(key_words, 1))) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_sub_off, &st->cap_sub_off, nsub + 1)) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_gsplit, &st->cap_gsplit, n)) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_gsub, &st->cap_gsub, n + 1)) return rc;
+        if (int rc = st->d_skeys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
+        if (int rc = st->d_sub_off.grow(ctx, nsub + 1, 4096)) return rc;
+        if (int rc = st->d_gsplit.grow(ctx, n, 4096)) return rc;
+        if (int rc = st->d_gsub.grow(ctx, n + 1, 4096)) return rc;
         D2G_HIP(ctx, hipMemcpyAsync(st->d_gsplit, kh.gsplit.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
         D2G_HIP(ctx, hipMemcpyAsync(st->d_gsub, kh.gsub.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
         b.g_split = st->d_gsplit; b.g_sub = st->d_gsub; b.sub_off = st->d_sub_off; b.skeys = st->d_skeys;
-        b.skeys32 = reinterpret_cast<uint32_t *>(st->d_skeys);
+        b.skeys32 = reinterpret_cast<uint32_t *>(st->d_skeys.get());
         const unsigned gs = (unsigned)std::min<size_t>(TB, (size_t)ctx->num_cus * 8);
         hipLaunchKernelGGL(kh.compact ? k3_split_kernel<true> : k3_split_kernel<false>, dim3(gs), dim3(K3_THREADS), 0, s, b);
     }
@@ -1431,19 +1421,19 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
     if (const char *e = ctx->tune.get("D2G_K3_ROUND_KEYS")) { const int v = std::atoi(e); if (v >= 1 && v <= K3_ROUND_KEYS) b.round_keys = (uint32_t)v; }
     if (count_only) {
         if (!distinct_only) {
-            if (int rc = d2g_grow(ctx, &st->d_out_keys, &st->cap_ok, std::max<uint64_t>(kh.total, 1))) return rc;
-            if (int rc = d2g_grow(ctx, &st->d_out_counts, &st->cap_oc, std::max<uint64_t>(kh.total, 1))) return rc;
+            if (int rc = st->d_out_keys.grow(ctx, std::max<uint64_t>(kh.total, 1), 4096)) return rc;
+            if (int rc = st->d_out_counts.grow(ctx, std::max<uint64_t>(kh.total, 1), 4096)) return rc;
             b.out_keys = st->d_out_keys; b.out_counts = st->d_out_counts;
         }
-        if (int rc = d2g_grow(ctx, &st->d_bucket_nd, &st->cap_nd, (size_t)TB + 1)) return rc;
+        if (int rc = st->d_bucket_nd.grow(ctx, (size_t)TB + 1, 4096)) return rc;
         b.bucket_nd = st->d_bucket_nd;
         if (TB) hipLaunchKernelGGL(kh.compact ? k3_count_kernel<true> : k3_count_kernel<false>, dim3(TB), dim3(K3_THREADS), 0, s, b);
     } else {
-        if (int rc = d2g_grow(ctx, &st->d_h, &st->cap_h, std::max<size_t>(n * m, 1))) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_tw, &st->cap_tw, std::max<size_t>(n, 1))) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_guess, &st->cap_guess, std::max<size_t>(n, 1))) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_redo, &st->cap_redo, std::max<size_t>(n, 1))) return rc;
-        if (int rc = d2g_grow(ctx, &st->d_tw_bucket, &st->cap_twb, (size_t)TB + 1)) return rc;
+        if (int rc = st->d_h.grow(ctx, std::max<size_t>(n * m, 1), 4096)) return rc;
+        if (int rc = st->d_tw.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
+        if (int rc = st->d_guess.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
+        if (int rc = st->d_redo.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
+        if (int rc = st->d_tw_bucket.grow(ctx, (size_t)TB + 1, 4096)) return rc;
         D2G_HIP(ctx, hipMemsetAsync(st->d_tw_bucket, 0, ((size_t)TB + 1) * sizeof(double), s));
         // first guess: with no count threshold the total weight IS the k-mer count; with one it is an
         // upper bound (a too small guess only costs a second pass, which then knows the exact weight)
@@ -1456,7 +1446,7 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
             std::memcpy(&guess[g], &gv, 8);
         }
         D2G_HIP(ctx, hipMemcpyAsync(st->d_guess, guess.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        b.h = st->d_h; b.tw = st->d_tw; b.tw_acc = reinterpret_cast<uint64_t *>(st->d_tw_bucket); b.guess = st->d_guess; b.redo = st->d_redo;
+        b.h = st->d_h; b.tw = st->d_tw; b.tw_acc = reinterpret_cast<uint64_t *>(st->d_tw_bucket.get()); b.guess = st->d_guess; b.redo = st->d_redo;
         b.nredo = reinterpret_cast<uint32_t *>(st->d_status + 1);
         const size_t ninit = std::max<size_t>(n * m, n);
         hipLaunchKernelGGL(k3_bmh_init_kernel, dim3((unsigned)div_up<size_t>(ninit, K3_THREADS)), dim3(K3_THREADS), 0, s,
@@ -1525,17 +1515,17 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
                 entries += off.back(); n_words += L.grid;
                 ll.push_back(L);
             }
-            if (int rc = d2g_grow(ctx, &st->d_gq, &st->cap_gq, (size_t)entries * (sizeof(QEntry) / 8) + 8)) return rc;
-            if (int rc = d2g_grow(ctx, &st->d_gq_off, &st->cap_gq_off, all_off.size() + (n_words + 1) / 2 + 1)) return rc;
+            if (int rc = st->d_gq.grow(ctx, (size_t)entries * (sizeof(QEntry) / 8) + 8, 4096)) return rc;
+            if (int rc = st->d_gq_off.grow(ctx, all_off.size() + (n_words + 1) / 2 + 1, 4096)) return rc;
             D2G_HIP(ctx, hipMemcpyAsync(st->d_gq_off, all_off.data(), all_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
             for (auto &L : ll) L.n_at += 2 * all_off.size();                 // u32 index into the same buffer, behind the offsets
         }
         auto light_args = [&](const LightLaunch &L) {
             BmhArgs x = b;
             x.tb0 = L.t0; x.tb1 = L.t1; x.g0 = L.g0; x.redo_mode = 0;
-            x.gq = reinterpret_cast<QEntry *>(st->d_gq) + L.entry0;
+            x.gq = reinterpret_cast<QEntry *>(st->d_gq.get()) + L.entry0;
             x.gq_off = st->d_gq_off + L.off_at;
-            x.gq_n = reinterpret_cast<uint32_t *>(st->d_gq_off) + L.n_at;
+            x.gq_n = reinterpret_cast<uint32_t *>(st->d_gq_off.get()) + L.n_at;
             return x;
         };
         void (*light_k)(BmhArgs) = k3_bmh_main_kernel<false, true>, (*heavy_k)(BmhArgs) = k3_bmh_main_kernel<false, false>;
@@ -1546,9 +1536,9 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
             const bool run = TB && D2G_K3_EXP != 1 && D2G_K3_EXP != 2 && D2G_K3_EXP != 6 && D2G_K3_EXP != 7;
             if (lt && pipeline) {
                 if (!st->xs) {
-                    D2G_HIP(ctx, hipStreamCreateWithFlags(&st->xs, hipStreamNonBlocking));
-                    for (auto &e : st->ev_a) D2G_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    D2G_HIP(ctx, hipEventCreateWithFlags(&st->ev_b, hipEventDisableTiming));
+                    D2G_HIP(ctx, st->xs.create(hipStreamNonBlocking));
+                    for (auto &e : st->ev_a) D2G_HIP(ctx, e.create(hipEventDisableTiming));
+                    D2G_HIP(ctx, st->ev_b.create(hipEventDisableTiming));
                 }
                 for (size_t j = 0; j < ll.size(); ++j) {
                     stage_a(ll[j].g0, ll[j].g1);
@@ -1821,27 +1811,23 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
     }
     D2G_CHECK(ctx, bset.size() < (1ull << 31), "too many workgroups");
     const size_t nb = bset.size();
-    uint64_t *d_ids = nullptr, *d_blo = nullptr, *d_h = nullptr, *d_guess = nullptr, *d_arg = nullptr, *d_setlo = nullptr;
-    double *d_w = nullptr, *d_tw = nullptr;
-    uint32_t *d_bset = nullptr, *d_bcnt = nullptr, *d_redo = nullptr;
-    int *d_status = nullptr;
+    d2g_dev<uint64_t> d_ids, d_blo, d_h, d_guess, d_arg, d_setlo;
+    d2g_dev<double> d_w, d_tw;
+    d2g_dev<uint32_t> d_bset, d_bcnt, d_redo;
+    d2g_dev<int> d_status;
     int rc = D2G_OK;
-    auto cleanup = [&]() {
-        (void)hipFree(d_ids); (void)hipFree(d_blo); (void)hipFree(d_h); (void)hipFree(d_guess); (void)hipFree(d_redo);
-        (void)hipFree(d_w); (void)hipFree(d_tw); (void)hipFree(d_bset); (void)hipFree(d_bcnt); (void)hipFree(d_status);
-        (void)hipFree(d_arg); (void)hipFree(d_setlo);
-    };
-#define K3_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ctx->last_error = hipGetErrorString(e_); cleanup(); return D2G_ERR_HIP; } } while (0)
-    K3_TRY(hipMalloc((void **)&d_ids, std::max<uint64_t>(total, 1) * 8));
-    K3_TRY(hipMalloc((void **)&d_blo, std::max<size_t>(nb, 1) * 8));
-    K3_TRY(hipMalloc((void **)&d_bset, std::max<size_t>(nb, 1) * 4));
-    K3_TRY(hipMalloc((void **)&d_bcnt, std::max<size_t>(nb, 1) * 4));
-    K3_TRY(hipMalloc((void **)&d_h, nsets * m * 8));
-    K3_TRY(hipMalloc((void **)&d_guess, nsets * 8));
-    K3_TRY(hipMalloc((void **)&d_redo, nsets * 4));
-    K3_TRY(hipMalloc((void **)&d_tw, nsets * 8));
-    K3_TRY(hipMalloc((void **)&d_status, 2 * sizeof(int)));
-    if (weights) { K3_TRY(hipMalloc((void **)&d_w, std::max<uint64_t>(total, 1) * 8)); K3_TRY(hipMemcpy(d_w, weights, total * 8, hipMemcpyHostToDevice)); }
+    const char *what = "weighted sets alloc";
+#define K3_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ctx->last_error = hipGetErrorString(e_); return D2G_ERR_HIP; } } while (0)
+    if ((rc = d_ids.alloc(ctx, std::max<uint64_t>(total, 1), what)) ||
+        (rc = d_blo.alloc(ctx, std::max<size_t>(nb, 1), what)) ||
+        (rc = d_bset.alloc(ctx, std::max<size_t>(nb, 1), what)) ||
+        (rc = d_bcnt.alloc(ctx, std::max<size_t>(nb, 1), what)) ||
+        (rc = d_h.alloc(ctx, nsets * m, what)) ||
+        (rc = d_guess.alloc(ctx, nsets, what)) ||
+        (rc = d_redo.alloc(ctx, nsets, what)) ||
+        (rc = d_tw.alloc(ctx, nsets, what)) ||
+        (rc = d_status.alloc(ctx, 2, what))) return rc;
+    if (weights) { if ((rc = d_w.alloc(ctx, std::max<uint64_t>(total, 1), what))) return rc; K3_TRY(hipMemcpy(d_w, weights, total * 8, hipMemcpyHostToDevice)); }
     if (total) K3_TRY(hipMemcpy(d_ids, ids, total * 8, hipMemcpyHostToDevice));
     K3_TRY(hipMemcpy(d_guess, guess.data(), nsets * 8, hipMemcpyHostToDevice));
     if (nb) {
@@ -1868,12 +1854,11 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
             int st2[2] = {0, 0};
             K3_TRY(hipMemcpy(st2, d_status, sizeof(st2), hipMemcpyDeviceToHost));
             if (st2[0] || !st2[1]) break;
-            if (pass >= 40) { ctx->last_error = "internal: BagMinHash bound did not converge"; cleanup(); return D2G_ERR_INTERNAL; }
+            if (pass >= 40) { ctx->last_error = "internal: BagMinHash bound did not converge"; return D2G_ERR_INTERNAL; }
             K3_TRY(hipMemset(d_status + 1, 0, sizeof(int)));
         }
         if (owner_out) {
-            K3_TRY(hipMalloc((void **)&d_arg, nsets * m * 8));
-            K3_TRY(hipMalloc((void **)&d_setlo, nsets * 8));
+            if ((rc = d_arg.alloc(ctx, nsets * m, what)) || (rc = d_setlo.alloc(ctx, nsets, what))) return rc;
             K3_TRY(hipMemset(d_arg, 0xFF, nsets * m * 8));
             K3_TRY(hipMemcpy(d_setlo, set_off, nsets * 8, hipMemcpyHostToDevice));
             a.arg = d_arg; a.set_lo = d_setlo;
@@ -1888,7 +1873,6 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
     if (owner_out) K3_TRY(hipMemcpy(owner_out, d_arg, nsets * m * 8, hipMemcpyDeviceToHost));
     std::memcpy(total_weight_out, tw.data(), nsets * sizeof(double));
 #undef K3_TRY
-    cleanup();
     if (status == 2) { ctx->last_error = "BagMinHash weight outside (0, 2^53]"; rc = D2G_ERR_INVALID; }
     if (status == 3) { ctx->last_error = "internal: BagMinHash process stack overflow"; rc = D2G_ERR_INTERNAL; }
     return rc;

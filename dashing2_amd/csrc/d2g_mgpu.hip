@@ -150,19 +150,17 @@ int local_flush(d2g_comm *c) {
         D2G_CHECK(c->ctx, j < ops.size() && ops[j].bytes == ops[i].bytes, "loopback transport: unmatched send/recv");
         used[j] = 1;
         d2g_ctx *sc = g.members[ops[i].from]->ctx, *rc = g.members[ops[i].to]->ctx;
-        hipEvent_t ready = nullptr, done = nullptr;
+        d2g_event ready, done;
         D2G_HIP(c->ctx, hipSetDevice(sc->device));
-        D2G_HIP(c->ctx, hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+        D2G_HIP(c->ctx, ready.create(hipEventDisableTiming));
         D2G_HIP(c->ctx, hipEventRecord(ready, ops[i].s));                   // sender's data is complete
         D2G_HIP(c->ctx, hipSetDevice(rc->device));
         D2G_HIP(c->ctx, hipStreamWaitEvent(ops[j].s, ready, 0));
         D2G_HIP(c->ctx, hipMemcpyAsync(ops[j].dst, ops[i].src, ops[i].bytes, hipMemcpyDeviceToDevice, ops[j].s));
-        D2G_HIP(c->ctx, hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        D2G_HIP(c->ctx, done.create(hipEventDisableTiming));
         D2G_HIP(c->ctx, hipEventRecord(done, ops[j].s));
         D2G_HIP(c->ctx, hipSetDevice(sc->device));
         D2G_HIP(c->ctx, hipStreamWaitEvent(ops[i].s, done, 0));             // the sender may reuse its buffer afterwards
-        (void)hipEventDestroy(ready);
-        (void)hipEventDestroy(done);
     }
     for (size_t j = 0; j < ops.size(); ++j)
         D2G_CHECK(c->ctx, ops[j].is_send || used[j], "loopback transport: recv without a matching send");
@@ -221,17 +219,17 @@ struct d2g_allpairs {
     std::vector<size_t> chunk_g0;        // [C+1] gathered groups of chunk c = [chunk_g0[c], chunk_g0[c+1])
     size_t r0 = 0, r1 = 0;               // rows of the triangle this rank computes
     size_t gw = 0, ng = 0;               // words per exchanged group, number of groups
-    uint32_t *d_colstart = nullptr;
-    uint16_t *d_colblk = nullptr;
-    uint64_t *d_send = nullptr, *d_recv = nullptr;
+    d2g_dev<uint32_t> d_colstart;
+    d2g_dev<uint16_t> d_colblk;
+    d2g_dev<uint64_t> d_send, d_recv;
     d2g_cmp_set *local[MG_MAX_CHUNKS] = {nullptr, nullptr, nullptr, nullptr};   // my column slice, chunk by chunk (exporter sets)
     // two operand buffers: the pipelined form prepares buffer i+1 while the pair kernel reads buffer i
-    uint32_t *d_planes[2] = {nullptr, nullptr}, *d_meta[2] = {nullptr, nullptr};   // meta: [ng] groups + [W*C] status words
+    d2g_dev<uint32_t> d_planes[2], d_meta[2];   // meta: [ng] groups + [W*C] status words; full[b] is a set over them (destroyed before them)
     d2g_cmp_set *full[2] = {nullptr, nullptr};
-    hipStream_t xs = nullptr;            // exchange stream
-    hipStream_t ps = nullptr;            // compute stream of the pipelined form's prepare
-    hipEvent_t ev_pack = nullptr, ev_x1[MG_MAX_CHUNKS] = {}, ev_prep[MG_MAX_CHUNKS] = {}, ev_x2[MG_MAX_CHUNKS] = {};
-    hipEvent_t x_done[2] = {nullptr, nullptr}, p_done[2] = {nullptr, nullptr}, in_ready = nullptr, plain_done = nullptr;
+    d2g_stream xs;                       // exchange stream
+    d2g_stream ps;                       // compute stream of the pipelined form's prepare
+    d2g_event ev_pack, ev_x1[MG_MAX_CHUNKS], ev_prep[MG_MAX_CHUNKS], ev_x2[MG_MAX_CHUNKS];
+    d2g_event x_done[2], p_done[2], in_ready, plain_done;
     bool p_valid[2] = {false, false}, plain_valid = false;
     unsigned long long nsteps = 0;
     int last = 0;                        // buffer of the most recent prepare
@@ -239,9 +237,9 @@ struct d2g_allpairs {
     void *pre_out = nullptr; const float *pre_lut = nullptr;
     // per-phase timing of ONE step (d2g_allpairs_set_phase_timing): timing-enabled event pairs around every phase, on the
     // stream the phase is enqueued on; nothing synchronises until d2g_allpairs_phase_times
-    struct PhaseEv { hipEvent_t a, b; int kind, chunk; };
+    struct PhaseEv { d2g_event a, b; int kind, chunk; };
     bool phase_timing = false;
-    hipEvent_t ev_step0 = nullptr;
+    d2g_event ev_step0;
     std::vector<PhaseEv> pev;
     int blk(int q, int c) const { return q * C + c; }
     size_t n_me() const { return row_lo[rank + 1] - row_lo[rank]; }
@@ -257,8 +255,8 @@ int eng_alloc_buffer(d2g_allpairs *e, int b) {
     d2g_ctx *ctx = e->ctx;
     if (e->full[b]) return D2G_OK;
     const size_t nstat = (size_t)e->W * e->C;
-    D2G_HIP(ctx, hipMalloc((void **)&e->d_planes[b], std::max<size_t>(e->ng * e->gw, 1) * 4));
-    D2G_HIP(ctx, hipMalloc((void **)&e->d_meta[b], (e->ng + nstat + 4) * 4));
+    if (int rc = e->d_planes[b].alloc(ctx, std::max<size_t>(e->ng * e->gw, 1), "allpairs operand alloc")) return rc;
+    if (int rc = e->d_meta[b].alloc(ctx, e->ng + nstat + 4, "allpairs operand alloc")) return rc;
     D2G_HIP(ctx, hipMemset(e->d_meta[b], 0, (e->ng + nstat + 4) * 4));      // blocks without groups never write their status word
     if (int rc = d2g_cmp_set_from_planes_dev(ctx, e->N, e->S, e->d_planes[b], e->d_meta[b], &e->full[b])) return rc;
     e->full[b]->managed = true;                                             // the engine derives the plane stream, chunk by chunk
@@ -269,26 +267,25 @@ int eng_alloc_buffer(d2g_allpairs *e, int b) {
 
 // phase timing: begin/end bracket a phase's enqueue on stream s (no-ops unless enabled)
 void pt_clear(d2g_allpairs *e) {
-    for (auto &p : e->pev) { if (p.a) (void)hipEventDestroy(p.a); if (p.b) (void)hipEventDestroy(p.b); }
     e->pev.clear();
-    if (e->ev_step0) { (void)hipEventDestroy(e->ev_step0); e->ev_step0 = nullptr; }
+    e->ev_step0.reset();
 }
 int pt_step_begin(d2g_allpairs *e, hipStream_t s) {
     if (!e->phase_timing) return D2G_OK;
     D2G_HIP(e->ctx, hipSetDevice(e->ctx->device));
     pt_clear(e);
-    D2G_HIP(e->ctx, hipEventCreate(&e->ev_step0));
+    D2G_HIP(e->ctx, e->ev_step0.create());
     D2G_HIP(e->ctx, hipEventRecord(e->ev_step0, s));
     return D2G_OK;
 }
 int pt_begin(d2g_allpairs *e, int kind, int chunk, hipStream_t s) {
     if (!e->phase_timing) return D2G_OK;
     D2G_HIP(e->ctx, hipSetDevice(e->ctx->device));
-    d2g_allpairs::PhaseEv p{nullptr, nullptr, kind, chunk};
-    D2G_HIP(e->ctx, hipEventCreate(&p.a));
-    D2G_HIP(e->ctx, hipEventCreate(&p.b));
-    e->pev.push_back(p);
+    d2g_allpairs::PhaseEv p{{}, {}, kind, chunk};
+    D2G_HIP(e->ctx, p.a.create());
+    D2G_HIP(e->ctx, p.b.create());
     D2G_HIP(e->ctx, hipEventRecord(p.a, s));
+    e->pev.push_back(std::move(p));
     return D2G_OK;
 }
 int pt_end(d2g_allpairs *e, int kind, int chunk, hipStream_t s) {
@@ -435,15 +432,14 @@ int verify_shape_across_ranks(d2g_allpairs *e) {
     if (!c->ranked || !c->nccl || e->W < 2) return D2G_OK;
     d2g_ctx *ctx = e->ctx;
     const int W = e->W;
-    uint64_t *d_v = nullptr;
+    d2g_dev<uint64_t> d_v;
     std::vector<uint64_t> all((size_t)W * 4, 0);
     // [3]: chunks in the low word, a hash of the K2 switches (D2G_BS_* / D2G_SP_*: which kernels a rank runs) in the high one
     const uint64_t mine[4] = {(uint64_t)e->N, (uint64_t)e->S, (uint64_t)e->W, (uint64_t)e->C | (d2g_k2_tuning_hash(e->ctx) << 32)};
-    D2G_HIP(ctx, hipMalloc((void **)&d_v, (size_t)W * 32));
-    int rc = D2G_OK;
-    auto fail = [&](int r) { (void)hipFree(d_v); return r; };
-    if (hipMemcpy(d_v + (size_t)e->rank * 4, mine, 32, hipMemcpyHostToDevice) != hipSuccess) return fail(D2G_ERR_HIP);
-    if ((rc = comm_group_begin(c))) return fail(rc);
+    int rc = d_v.alloc(ctx, (size_t)W * 4, "allpairs shape exchange alloc");
+    if (rc) return rc;
+    if (hipMemcpy(d_v + (size_t)e->rank * 4, mine, 32, hipMemcpyHostToDevice) != hipSuccess) return D2G_ERR_HIP;
+    if ((rc = comm_group_begin(c))) return rc;
     for (int q = 0; q < W && rc == D2G_OK; ++q) {
         if (q == e->rank) continue;
         rc = comm_send(c, q, d_v + (size_t)e->rank * 4, 32, e->xs);
@@ -451,9 +447,8 @@ int verify_shape_across_ranks(d2g_allpairs *e) {
     }
     const int rc2 = comm_group_end(c);
     if (rc == D2G_OK) rc = rc2;
-    if (rc != D2G_OK) return fail(rc);
-    if (hipStreamSynchronize(e->xs) != hipSuccess || hipMemcpy(all.data(), d_v, (size_t)W * 32, hipMemcpyDeviceToHost) != hipSuccess) return fail(D2G_ERR_HIP);
-    (void)hipFree(d_v);
+    if (rc != D2G_OK) return rc;
+    if (hipStreamSynchronize(e->xs) != hipSuccess || hipMemcpy(all.data(), d_v, (size_t)W * 32, hipMemcpyDeviceToHost) != hipSuccess) return D2G_ERR_HIP;
     for (int q = 0; q < W; ++q)
         if (std::memcmp(&all[(size_t)q * 4], mine, 32) != 0) {
             char buf[256];
@@ -572,8 +567,7 @@ static int bcast_sigs_impl(d2g_ctx **ctxs, d2g_comm **comms, int nctx, const uin
     d2g_ctx *c0 = ctxs[0];
     for (int i = 0; i < nctx; ++i) {
         D2G_CHECK(c0, ctxs[i] && comms[i] && comms[i]->ctx == ctxs[i] && comms[i]->world == nctx && comms[i]->rank == i, "bcast_sigs: comm/ctx mismatch");
-        D2G_HIP(ctxs[i], hipSetDevice(ctxs[i]->device));
-        D2G_HIP(ctxs[i], hipMalloc((void **)&sig_dev_out[i], bytes));
+        if (int rc = d2g_malloc(ctxs[i], bytes, (void **)&sig_dev_out[i])) return rc;      // (the caller's from here on: d2g_free)
     }
     D2G_HIP(c0, hipSetDevice(c0->device));
     D2G_HIP(c0, hipMemcpyAsync(sig_dev_out[0], host_sig, bytes, hipMemcpyHostToDevice, nullptr));
@@ -610,7 +604,7 @@ int d2g_bcast_sigs(d2g_ctx **ctxs, d2g_comm **comms, int nctx, const uint64_t *h
     const int rc = bcast_sigs_impl(ctxs, comms, nctx, host_sig, N * S * 8, sig_dev_out);
     if (rc != D2G_OK)
         for (int i = 0; i < nctx; ++i)
-            if (sig_dev_out[i] && ctxs[i]) { (void)hipSetDevice(ctxs[i]->device); (void)hipDeviceSynchronize(); (void)hipFree(sig_dev_out[i]); sig_dev_out[i] = nullptr; }
+            if (sig_dev_out[i] && ctxs[i]) { (void)hipSetDevice(ctxs[i]->device); (void)hipDeviceSynchronize(); (void)d2g_free(ctxs[i], sig_dev_out[i]); sig_dev_out[i] = nullptr; }
     return rc;
 }
 
@@ -653,32 +647,25 @@ int d2g_allpairs_create(d2g_ctx *ctx, d2g_comm *comm, size_t N, size_t S, d2g_al
     std::vector<size_t> ob(e->W + 1);
     d2g_ut_partition(N, e->W, ob.data());
     e->r0 = ob[e->rank]; e->r1 = ob[e->rank + 1];
-    hipError_t he;
-    if ((he = hipMalloc((void **)&e->d_colstart, (nb + 1) * 4)) != hipSuccess ||
-        (he = hipMemcpy(e->d_colstart, e->colstart.data(), (nb + 1) * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-        (he = hipMalloc((void **)&e->d_colblk, S * 2)) != hipSuccess ||
-        (he = hipMemcpy(e->d_colblk, colblk.data(), S * 2, hipMemcpyHostToDevice)) != hipSuccess ||
-        (he = hipMalloc((void **)&e->d_send, std::max<size_t>(e->n_me() * S, 1) * 8)) != hipSuccess ||
-        (he = hipMalloc((void **)&e->d_recv, std::max<size_t>(N * e->s_me(), 1) * 8)) != hipSuccess ||
-        (he = hipStreamCreateWithFlags(&e->xs, hipStreamNonBlocking)) != hipSuccess ||
-        (he = hipEventCreateWithFlags(&e->ev_pack, hipEventDisableTiming)) != hipSuccess ||
-        (he = hipEventCreateWithFlags(&e->plain_done, hipEventDisableTiming)) != hipSuccess) {
-        ctx->last_error = std::string("allpairs alloc: ") + hipGetErrorString(he);
-        d2g_allpairs_destroy(e);
-        return he == hipErrorOutOfMemory ? D2G_ERR_NOMEM : D2G_ERR_HIP;
-    }
+    const char *what = "allpairs alloc";
+    int rc;
+    if ((rc = e->d_colstart.alloc(ctx, nb + 1, what)) ||
+        (rc = d2g_hip_status(ctx, hipMemcpy(e->d_colstart, e->colstart.data(), (nb + 1) * 4, hipMemcpyHostToDevice), what)) ||
+        (rc = e->d_colblk.alloc(ctx, S, what)) ||
+        (rc = d2g_hip_status(ctx, hipMemcpy(e->d_colblk, colblk.data(), S * 2, hipMemcpyHostToDevice), what)) ||
+        (rc = e->d_send.alloc(ctx, std::max<size_t>(e->n_me() * S, 1), what)) ||
+        (rc = e->d_recv.alloc(ctx, std::max<size_t>(N * e->s_me(), 1), what)) ||
+        (rc = d2g_hip_status(ctx, e->xs.create(hipStreamNonBlocking), what)) ||
+        (rc = d2g_hip_status(ctx, e->ev_pack.create(hipEventDisableTiming), what)) ||
+        (rc = d2g_hip_status(ctx, e->plain_done.create(hipEventDisableTiming), what))) { d2g_allpairs_destroy(e); return rc; }
     for (int c = 0; c < e->C; ++c)
-        if ((he = hipEventCreateWithFlags(&e->ev_x1[c], hipEventDisableTiming)) != hipSuccess ||
-            (he = hipEventCreateWithFlags(&e->ev_prep[c], hipEventDisableTiming)) != hipSuccess ||
-            (he = hipEventCreateWithFlags(&e->ev_x2[c], hipEventDisableTiming)) != hipSuccess) {
-            ctx->last_error = std::string("allpairs alloc: ") + hipGetErrorString(he);
-            d2g_allpairs_destroy(e);
-            return D2G_ERR_HIP;
-        }
+        if ((rc = d2g_hip_status(ctx, e->ev_x1[c].create(hipEventDisableTiming), what)) ||
+            (rc = d2g_hip_status(ctx, e->ev_prep[c].create(hipEventDisableTiming), what)) ||
+            (rc = d2g_hip_status(ctx, e->ev_x2[c].create(hipEventDisableTiming), what))) { d2g_allpairs_destroy(e); return rc; }
     // the exchange of (N, S, world, chunks, switches) comes BEFORE the large allocations: a rank that then runs out of memory returns
     // without leaving its peers blocked in this (collective) call
-    if (int rc = verify_shape_across_ranks(e)) { d2g_allpairs_destroy(e); return rc; }
-    if (int rc = eng_alloc_buffer(e, 0)) { d2g_allpairs_destroy(e); return rc; }
+    if ((rc = verify_shape_across_ranks(e))) { d2g_allpairs_destroy(e); return rc; }
+    if ((rc = eng_alloc_buffer(e, 0))) { d2g_allpairs_destroy(e); return rc; }
     *out = e;
     return D2G_OK;
 }
@@ -687,25 +674,8 @@ void d2g_allpairs_destroy(d2g_allpairs *e) {
     if (!e) return;
     (void)hipSetDevice(e->ctx->device);
     (void)hipDeviceSynchronize();
-    for (int b = 0; b < 2; ++b) {
-        d2g_cmp_set_destroy(e->full[b]);
-        (void)hipFree(e->d_planes[b]); (void)hipFree(e->d_meta[b]);
-        if (e->x_done[b]) (void)hipEventDestroy(e->x_done[b]);
-        if (e->p_done[b]) (void)hipEventDestroy(e->p_done[b]);
-    }
-    for (int c = 0; c < MG_MAX_CHUNKS; ++c) {
-        d2g_cmp_set_destroy(e->local[c]);
-        if (e->ev_x1[c]) (void)hipEventDestroy(e->ev_x1[c]);
-        if (e->ev_prep[c]) (void)hipEventDestroy(e->ev_prep[c]);
-        if (e->ev_x2[c]) (void)hipEventDestroy(e->ev_x2[c]);
-    }
-    pt_clear(e);
-    if (e->ev_pack) (void)hipEventDestroy(e->ev_pack);
-    if (e->in_ready) (void)hipEventDestroy(e->in_ready);
-    if (e->plain_done) (void)hipEventDestroy(e->plain_done);
-    (void)hipFree(e->d_colstart); (void)hipFree(e->d_colblk); (void)hipFree(e->d_send); (void)hipFree(e->d_recv);
-    if (e->xs) (void)hipStreamDestroy(e->xs);
-    if (e->ps) (void)hipStreamDestroy(e->ps);
+    for (int b = 0; b < 2; ++b) d2g_cmp_set_destroy(e->full[b]);             // the sets first: they look at the engine's d_planes / d_meta
+    for (int c = 0; c < MG_MAX_CHUNKS; ++c) d2g_cmp_set_destroy(e->local[c]);
     delete e;
 }
 
@@ -839,12 +809,12 @@ int d2g_allpairs_enqueue_lut_dev(d2g_allpairs *e, const uint64_t *my_rows_dev, c
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t main = as_stream(stream);
     if (!e->ps) {
-        D2G_HIP(ctx, hipStreamCreateWithFlags(&e->ps, hipStreamNonBlocking));
+        D2G_HIP(ctx, e->ps.create(hipStreamNonBlocking));
         for (int b = 0; b < 2; ++b) {
-            D2G_HIP(ctx, hipEventCreateWithFlags(&e->x_done[b], hipEventDisableTiming));
-            D2G_HIP(ctx, hipEventCreateWithFlags(&e->p_done[b], hipEventDisableTiming));
+            D2G_HIP(ctx, e->x_done[b].create(hipEventDisableTiming));
+            D2G_HIP(ctx, e->p_done[b].create(hipEventDisableTiming));
         }
-        D2G_HIP(ctx, hipEventCreateWithFlags(&e->in_ready, hipEventDisableTiming));
+        D2G_HIP(ctx, e->in_ready.create(hipEventDisableTiming));
     }
     const int b = (int)(e->nsteps & 1);
     if (!input_ready) {

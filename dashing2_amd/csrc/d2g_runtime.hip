@@ -73,10 +73,6 @@ int d2g_ctx_create(int device, d2g_ctx **out) {
 void d2g_ctx_destroy(d2g_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (d2g_evlog *e : {&c->ev_k1, &c->ev_k2, &c->ev_k2prep, &c->ev_k3, &c->ev_k0}) {
-        for (hipEvent_t x : e->a) (void)hipEventDestroy(x);
-        for (hipEvent_t x : e->b) (void)hipEventDestroy(x);
-    }
     if (c->k3) d2g_k3_state_destroy(c->k3);
     delete c;
 }
@@ -151,11 +147,10 @@ int d2g_warmup(d2g_ctx *c, int what) {
         // the first host<->device copy of a process sets up the runtime's copy machinery (~30 ms on MI355X / ROCm 7: measured with any
         // size and with pinned or pageable memory alike; a 4 KB copy leaves part of it to the first large one, 1 MB does not)
         std::vector<char> src((size_t)1 << 20);                 // per call: two helper threads may warm two contexts at once
-        void *d = nullptr;
-        D2G_HIP(c, hipMalloc(&d, src.size()));
+        d2g_dev<char> d;
+        if (int rc = d.alloc(c, src.size(), "warmup alloc")) return rc;
         hipError_t e = hipMemcpy(d, src.data(), src.size(), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(src.data(), d, 4096, hipMemcpyDeviceToHost);
-        (void)hipFree(d);
         D2G_HIP(c, e);
     }
     if (what & D2G_WARM_K0) d2g_warm_k0();
@@ -199,11 +194,7 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     if (count) *count = n;
     if (avg_ms) *avg_ms = n ? (float)(sum / n) : 0.f;
     if (last_ms) *last_ms = last;
-    if (reset) {
-        for (hipEvent_t x : e->a) (void)hipEventDestroy(x);
-        for (hipEvent_t x : e->b) (void)hipEventDestroy(x);
-        e->a.clear(); e->b.clear();
-    }
+    if (reset) { e->a.clear(); e->b.clear(); }
     return D2G_OK;
 }
 
