@@ -10,16 +10,18 @@ from .capi import (  # noqa: F401
     D2GError, Context, CmpSet, SeqPack, Comm, AllPairs, lib, build, LIB_PATH,
     comm_unique_id, allpairs_step_all, allpairs_prepare_all, bcast_sigs,
     SIMILARITY, CONTAINMENT, SYMMETRIC_CONTAINMENT, POISSON_LLR, INTERSECTION, UNION_SIZE,
-    CMP_AUTO, CMP_DIRECT, CMP_BITSLICE, BITSLICE_OPS_PER_GROUP_EXTRA, TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0, PinnedArray,
+    CMP_AUTO, CMP_DIRECT, CMP_BITSLICE, CMP_PLANES, BITSLICE_OPS_PER_GROUP_EXTRA, TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0, PinnedArray,
     wang_hash, seed_mask, oph_xor_const, oph_m, oph_finalize, densify, epilogue_lut,
     epilogue_gtlt, epilogue_neq, host_epilogue_ut, operand_layout, sparse_bin_geometry, ut_count, ut_partition,
+    regs_truncate, epilogue_trunc_neq, epilogue_trunc_gtlt, host_epilogue_trunc_ut, host_epilogue_trunc_rect,
 )
 
 __all__ = [
     "D2GError", "Context", "CmpSet", "SeqPack", "Comm", "AllPairs", "lib", "build", "LIB_PATH",
     "comm_unique_id", "allpairs_step_all", "allpairs_prepare_all", "bcast_sigs",
     "SIMILARITY", "CONTAINMENT", "SYMMETRIC_CONTAINMENT", "POISSON_LLR", "INTERSECTION", "UNION_SIZE",
-    "CMP_AUTO", "CMP_DIRECT", "CMP_BITSLICE", "BITSLICE_OPS_PER_GROUP_EXTRA", "TIME_K1", "TIME_K2", "TIME_K2PREP", "TIME_K3", "TIME_K0", "PinnedArray",
+    "CMP_AUTO", "CMP_DIRECT", "CMP_BITSLICE", "CMP_PLANES", "BITSLICE_OPS_PER_GROUP_EXTRA", "TIME_K1", "TIME_K2", "TIME_K2PREP", "TIME_K3", "TIME_K0", "PinnedArray",
     "wang_hash", "seed_mask", "oph_xor_const", "oph_m", "oph_finalize", "densify", "epilogue_lut",
     "epilogue_gtlt", "epilogue_neq", "host_epilogue_ut", "operand_layout", "sparse_bin_geometry", "ut_count", "ut_partition",
+    "regs_truncate", "epilogue_trunc_neq", "epilogue_trunc_gtlt", "host_epilogue_trunc_ut", "host_epilogue_trunc_rect",
 ]

@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("D2G_LIB") or os.path.join(_HERE, "libd2g.so")
 _lib = None
 
 SIMILARITY, CONTAINMENT, SYMMETRIC_CONTAINMENT, POISSON_LLR, INTERSECTION, UNION_SIZE = range(6)
-CMP_AUTO, CMP_DIRECT, CMP_BITSLICE = 0, 1, 2
+CMP_AUTO, CMP_DIRECT, CMP_BITSLICE, CMP_PLANES = 0, 1, 2, 3
 # bit-sliced pair kernel: VALU operations per pair and 32-register group = (id planes of the group) + this (one v_bcnt)
 BITSLICE_OPS_PER_GROUP_EXTRA = 1
 
@@ -72,6 +72,11 @@ SIGNATURES = {
     "d2g_epilogue_neq": (_f32, [_u64, _sz, _dbl, _dbl, _int, _int]),
     "d2g_epilogue_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _vp]),
     "d2g_epilogue_lut": (_int, [_sz, _int, _int, _int, _pf32]),
+    "d2g_regs_truncate": (_int, [_vp, _sz, _sz, _int, _int, _vp, _vp, _vp, _int, C.c_char_p, _sz]),
+    "d2g_epilogue_trunc_neq": (_f32, [_u64, _sz, _int, _dbl, _dbl, _int, _int]),
+    "d2g_epilogue_trunc_gtlt": (_f32, [_u64, _u64, _sz, _vp, _dbl, _dbl, _int, _int]),
+    "d2g_epilogue_trunc_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _vp, _int, _vp]),
+    "d2g_epilogue_trunc_rect": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _int, _int, _int, _vp, _int, _vp]),
     "d2g_seqpack_create": (_int, [_int, C.POINTER(_vp)]),
     "d2g_seqpack_destroy": (None, [_vp]),
     "d2g_seqpack_clear": (None, [_vp]),
@@ -162,6 +167,10 @@ SIGNATURES = {
     "d2g_cmp_eqcount_ut": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _int, _vp]),
     "d2g_cmp_dist_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _int, _vp]),
     "d2g_ut_partition": (_int, [_sz, _int, C.POINTER(_sz)]),
+    "d2g_cmp_set_create_codes_dev": (_int, [_vp, _vp, _sz, _sz, _int, _vp, C.POINTER(_vp)]),
+    "d2g_cmp_set_create_codes": (_int, [_vp, _vp, _sz, _sz, _int, C.POINTER(_vp)]),
+    "d2g_cmp_set_operand_bytes": (_sz, [_vp]),
+    "d2g_cmp_dist_trunc_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _int, _vp]),
 }
 
 
@@ -266,6 +275,71 @@ def epilogue_gtlt(gt, lt, S, lhc, rhc, measure=SIMILARITY, k=31):
 
 def epilogue_neq(neq, S, lhc, rhc, measure=SIMILARITY, k=31):
     return float(lib().d2g_epilogue_neq(neq, S, lhc, rhc, measure, k))
+
+
+# ---- truncated registers (--fastcmp <4|2|1>, --bbit-sigs)
+_CODE_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.uint32}
+
+
+def _longdouble_ptr(b):
+    """one x87 long double as a pointer (ctypes would round it to a double on the way in)"""
+    assert np.finfo(np.longdouble).nmant == 63, "np.longdouble is not the x87 80-bit format here"
+    a = np.array([b], np.longdouble)
+    return a, a.ctypes.data
+
+
+def regs_truncate(sigs, regbytes, bbit=False, nthreads=1, with_minmax=False):
+    """double signatures [n][S] -> (codes [n][S] of regbytes, a, b) with a, b np.longdouble (0, 0 for b-bit codes);
+    with_minmax: also (minreg, maxreg) of the setsketch method"""
+    sigs = np.ascontiguousarray(sigs, np.float64)
+    assert sigs.ndim == 2
+    n, S = sigs.shape
+    codes = np.zeros((n, S), _CODE_DTYPES.get(regbytes, np.uint32))
+    assert np.finfo(np.longdouble).nmant == 63, "np.longdouble is not the x87 80-bit format here"
+    ab = np.zeros(2, np.longdouble)
+    mm = np.zeros(2, np.float64)
+    err = C.create_string_buffer(256)
+    rc = lib().d2g_regs_truncate(_np_ptr(sigs), n, S, regbytes, int(bool(bbit)), _np_ptr(codes), _np_ptr(ab), _np_ptr(mm), nthreads, err, 256)
+    if rc:
+        raise D2GError(rc, err.value.decode())
+    return (codes, ab[0], ab[1], float(mm[0]), float(mm[1])) if with_minmax else (codes, ab[0], ab[1])
+
+
+def epilogue_trunc_neq(neq, S, regbytes, lhc, rhc, measure=SIMILARITY, k=31):
+    return float(lib().d2g_epilogue_trunc_neq(neq, S, regbytes, lhc, rhc, measure, k))
+
+
+def epilogue_trunc_gtlt(gt, lt, S, b, lhc, rhc, measure=SIMILARITY, k=31):
+    keep, pb = _longdouble_ptr(b)
+    return float(lib().d2g_epilogue_trunc_gtlt(gt, lt, S, pb, lhc, rhc, measure, k))
+
+
+def host_epilogue_trunc_ut(ca, cb, cards, N, S, r0, r1, measure=SIMILARITY, k=31, regbytes=1, b=None, nthreads=0):
+    """counts of rows [r0,r1) of truncated codes -> float32: b None = ca is neq of b-bit codes, else (ca, cb) = (gt, lt)"""
+    ca = np.ascontiguousarray(ca, np.uint32)
+    cb = None if cb is None else np.ascontiguousarray(cb, np.uint32)
+    cards = np.ascontiguousarray(cards, np.float64)
+    out = np.empty(ca.size, np.float32)
+    keep, pb = (None, None) if b is None else _longdouble_ptr(b)
+    rc = lib().d2g_epilogue_trunc_ut(_np_ptr(ca), _np_ptr(cb), _np_ptr(cards), N, S, r0, r1, measure, k, regbytes, pb,
+                                     nthreads or (os.cpu_count() or 1), _np_ptr(out))
+    if rc:
+        raise D2GError(rc)
+    return out
+
+
+def host_epilogue_trunc_rect(ca, cb, cards, N, S, a0, a1, b0, b1, measure=SIMILARITY, k=31, regbytes=1, b=None, nthreads=0):
+    """the same over the row-major block rows [a0,a1) x columns [b0,b1)"""
+    ca = np.ascontiguousarray(ca, np.uint32)
+    cb = None if cb is None else np.ascontiguousarray(cb, np.uint32)
+    cards = np.ascontiguousarray(cards, np.float64)
+    out = np.empty((a1 - a0, b1 - b0), np.float32)
+    keep, pb = (None, None) if b is None else _longdouble_ptr(b)
+    rc = lib().d2g_epilogue_trunc_rect(_np_ptr(ca), _np_ptr(cb), _np_ptr(cards), N, S, a0, a1, b0, b1, measure, k, regbytes, pb,
+                                       nthreads or (os.cpu_count() or 1), _np_ptr(out))
+    if rc:
+        raise D2GError(rc)
+    return out
 
 
 def operand_layout(N, S):
@@ -545,6 +619,31 @@ class Context:
         self._check(lib().d2g_cmp_set_create_dev(self._h, dev_ptr, N, S, algo, stream, C.byref(h)))
         return CmpSet(self, h, N, S)
 
+    def cmp_set_codes(self, codes_host):
+        """set of truncated codes (uint8 / uint16 / uint32 [N][S]): (gt, lt) and equality counts only"""
+        a = np.ascontiguousarray(codes_host)
+        assert a.ndim == 2 and a.dtype in (np.uint8, np.uint16, np.uint32)
+        h = _vp()
+        self._check(lib().d2g_cmp_set_create_codes(self._h, _np_ptr(a), a.shape[0], a.shape[1], a.dtype.itemsize, C.byref(h)))
+        return CmpSet(self, h, a.shape[0], a.shape[1])
+
+    def cmp_set_codes_dev(self, dev_ptr, N, S, regbytes, stream=None):
+        h = _vp()
+        self._check(lib().d2g_cmp_set_create_codes_dev(self._h, dev_ptr, N, S, regbytes, stream, C.byref(h)))
+        return CmpSet(self, h, N, S)
+
+    def cmp_dist_trunc_ut(self, sigs, cards, measure=SIMILARITY, k=31, regbytes=1, bbit=False, r0=0, r1=None, nthreads=1):
+        """truncate + upload + count + epilogue: float32 values of rows [r0,r1) from (densified) double signatures"""
+        a = np.ascontiguousarray(sigs, np.float64)
+        assert a.ndim == 2
+        cards = np.ascontiguousarray(cards, np.float64)
+        N, S = a.shape
+        r1 = N if r1 is None else r1
+        out = np.empty(ut_count(N, r0, r1), np.float32)
+        self._check(lib().d2g_cmp_dist_trunc_ut(self._h, _np_ptr(a), _np_ptr(cards), N, S, r0, r1, measure, k, regbytes,
+                                                int(bool(bbit)), nthreads, _np_ptr(out)))
+        return out
+
     def cmp_set_from_planes(self, N, S, planes_dev_ptr, meta_dev_ptr):
         h = _vp()
         self._check(lib().d2g_cmp_set_from_planes_dev(self._h, N, S, planes_dev_ptr, meta_dev_ptr, C.byref(h)))
@@ -735,6 +834,10 @@ class CmpSet:
     @property
     def algo(self):
         return int(lib().d2g_cmp_set_algo(self._h))
+
+    @property
+    def operand_bytes(self):
+        return int(lib().d2g_cmp_set_operand_bytes(self._h))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -246,6 +246,175 @@ int d2g_epilogue_ut(const uint32_t *ca, const uint32_t *cb, const double *cards,
     return D2G_OK;
 }
 
+// ---- truncated registers (--fastcmp <4|2|1>, --bbit-sigs): make_compressed, cmp_core.cpp:209-322
+static void trunc_fail(char *err, size_t cap, const char *msg) { if (err && cap) std::snprintf(err, cap, "%s", msg); }
+
+int d2g_regs_truncate(const double *sigs, size_t n, size_t S, int regbytes, int bbit, void *codes_out, long double *ab_out,
+                      double *minmax_out, int nthreads, char *err, size_t errcap) {
+    if (err && errcap) err[0] = 0;
+    if (regbytes != 1 && regbytes != 2 && regbytes != 4) { trunc_fail(err, errcap, "regs_truncate: register size must be 1, 2 or 4 bytes"); return D2G_ERR_INVALID; }
+    if (!sigs || !codes_out || !n || !S) { trunc_fail(err, errcap, "regs_truncate: null or empty matrix"); return D2G_ERR_INVALID; }
+    if (nthreads < 1) nthreads = 1;
+    const size_t nsigs = n * S;
+    uint8_t *c8 = static_cast<uint8_t *>(codes_out);
+    uint16_t *c16 = static_cast<uint16_t *>(codes_out);
+    uint32_t *c32 = static_cast<uint32_t *>(codes_out);
+    auto put = [&](size_t i, uint64_t v) {
+        if (regbytes == 4) c32[i] = (uint32_t)v; else if (regbytes == 2) c16[i] = (uint16_t)v; else c8[i] = (uint8_t)v;
+    };
+    if (bbit) {                                                   // :294-320, reg2sig :19-30
+        const int shift = regbytes == 1 ? 58 : regbytes == 2 ? 48 : 32;
+        if (ab_out) ab_out[0] = ab_out[1] = 0.L;
+#ifdef _OPENMP
+        #pragma omp parallel for schedule(static) num_threads(nthreads)
+#endif
+        for (size_t i = 0; i < nsigs; ++i) {
+            uint64_t v;
+            std::memcpy(&v, &sigs[i], sizeof(v));
+            put(i, d2g_wang_hash(v ^ 0xa3407fb23cd20efull) >> shift);
+        }
+        return D2G_OK;
+    }
+    // :246-292
+    const long double q = regbytes == 1 ? 254.3 : regbytes == 2 ? 65534 : 4294967294;     // 254.3 is a double constant there, too
+    double minreg = std::numeric_limits<double>::max(), maxreg = -std::numeric_limits<double>::max();
+    bool has_inf = false;
+    for (size_t i = 0; i < nsigs; ++i) {
+        const double v = sigs[i];
+        if (v <= 0 || v == std::numeric_limits<double>::max()) continue;
+        if (std::isinf(v)) has_inf = true;
+        minreg = std::min(minreg, v);
+        maxreg = std::max(maxreg, v);
+    }
+    if (has_inf) { trunc_fail(err, errcap, "regs_truncate: a register is +inf"); return D2G_ERR_INVALID; }
+    if (maxreg < minreg) { trunc_fail(err, errcap, "regs_truncate: the matrix holds no finite positive register"); return D2G_ERR_INVALID; }
+    // CSetSketch::optimal_parameters (setsketch.h:563-566, called with (min, max): swapped) -> setsketch.cpp:7-10
+    const long double hi = maxreg, lo = minreg;
+    const long double b = std::exp(std::log(hi / lo) / q);
+    const long double a = hi / b;
+    if (minmax_out) { minmax_out[0] = minreg; minmax_out[1] = maxreg; }
+    if (!(a > 0.L) || !(b > 0.L) || std::isinf(a) || std::isinf(b)) {
+        trunc_fail(err, errcap, "regs_truncate: setsketch parameters a, b are not finite and positive");
+        return D2G_ERR_INVALID;
+    }
+    if (ab_out) { ab_out[0] = a; ab_out[1] = b; }
+    const long double logbinv = 1.L / std::log1p(b - 1.L);
+    const int64_t top = int64_t(q + 1);
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(static) num_threads(nthreads)
+#endif
+    for (size_t i = 0; i < nsigs; ++i) {
+        const long double sub = 1.L - std::log(static_cast<long double>(sigs[i]) / a) * logbinv;
+        // a value outside int64 (log(0) = -inf -> sub = +inf) converts to the x86 "integer indefinite", INT64_MIN, which clamps to 0
+        const int64_t cast = (sub >= -0x1p63L && sub < 0x1p63L) ? static_cast<int64_t>(sub) : std::numeric_limits<int64_t>::min();
+        put(i, (uint64_t)std::max(int64_t(0), std::min(top, cast)));
+    }
+    return D2G_OK;
+}
+
+// cmp_core.cpp:323-325
+static inline long double g_b(long double b, long double arg) { return (1.L - std::pow(b, -arg)) / (1.L - 1.L / b); }
+
+// compressed branch of compare(), b-bit: cmp_core.cpp:406-423
+float d2g_epilogue_trunc_neq(uint64_t neq, size_t S, int regbytes, double lhc, double rhc, int measure, int k) {
+    const long double lhcard = lhc, rhcard = rhc, invdenom = 1.L / S;
+    const long double b2pow = -std::ldexp(1.L, -(regbytes * 8));
+    long double ret = std::max(0.L, std::fma((long double)neq, invdenom, b2pow) / (1.L + b2pow));
+    auto ucard = [&]() { return std::max((lhcard + rhcard) / (2.L - (1.L - ret)), 0.L); };
+    if (measure == D2G_INTERSECTION || measure == D2G_UNION_SIZE) {
+        const long double isz = ucard();
+        ret = measure == D2G_INTERSECTION ? isz : lhcard + rhcard - isz;
+    } else if (measure == D2G_CONTAINMENT) ret = ucard() * ret / lhcard;
+    else if (measure == D2G_POISSON_LLR) {
+        const double pm = -1. / std::max(1, k);
+        ret = ret ? double(std::log(2. * ret / (1. + ret)) * pm) : std::numeric_limits<double>::infinity();
+    } else if (measure == D2G_SYMMETRIC_CONTAINMENT) ret = ucard() * ret / std::min(lhcard, rhcard);
+    return finish(ret);
+}
+
+// compressed branch of compare(), setsketch: cmp_core.cpp:425-448, from alpha = g_b(b, gt/S) and beta = g_b(b, lt/S)
+static inline float trunc_gtlt_from(long double alpha, long double beta, long double lhcard, long double rhcard, int measure, int k) {
+    long double mu;
+    if (alpha + beta >= 1.) mu = lhcard + rhcard;
+    else mu = std::max((lhcard + rhcard) / (2.L - alpha - beta), 0.L);
+    long double ret = std::max(1.L - (alpha + beta), 0.L);
+    switch (measure) {
+        case D2G_INTERSECTION: ret *= mu; break;
+        case D2G_UNION_SIZE: ret = lhcard + rhcard - (ret * mu); break;
+        case D2G_CONTAINMENT: ret = ret * mu / lhcard; break;
+        case D2G_SYMMETRIC_CONTAINMENT: ret = (ret * mu) / std::min(lhcard, rhcard); break;
+        case D2G_POISSON_LLR: {
+            const double pm = -1. / std::max(1, k);
+            ret = ret ? double(std::log(2. * ret / (1. + ret)) * pm) : std::numeric_limits<double>::infinity();
+        } break;
+        default: ;
+    }
+    return finish(ret);
+}
+
+float d2g_epilogue_trunc_gtlt(uint64_t gt, uint64_t lt, size_t S, const long double *b, double lhc, double rhc, int measure, int k) {
+    const long double invdenom = 1.L / S;
+    return trunc_gtlt_from(g_b(*b, gt * invdenom), g_b(*b, lt * invdenom), lhc, rhc, measure, k);
+}
+
+// g_b(b, c/S) takes S+1 values: one table per run, no powl per pair
+static std::vector<long double> g_b_table(size_t S, long double b) {
+    std::vector<long double> t(S + 1);
+    const long double invdenom = 1.L / S;
+    for (size_t c = 0; c <= S; ++c) t[c] = g_b(b, c * invdenom);
+    return t;
+}
+
+// ca = neq (b == NULL: b-bit codes) or gt with cb = lt (setsketch codes with base *b)
+int d2g_epilogue_trunc_ut(const uint32_t *ca, const uint32_t *cb, const double *cards, size_t N, size_t S, size_t r0, size_t r1,
+                          int measure, int k, int regbytes, const long double *b, int nthreads, float *out) {
+    if (r0 > r1 || r1 > N || !S) return D2G_ERR_INVALID;
+    if (d2g_ut_count(N, r0, r1) == 0) return D2G_OK;
+    if (!ca || !cards || !out || (b && !cb)) return D2G_ERR_INVALID;
+    std::vector<size_t> off(r1 - r0 + 1, 0);
+    for (size_t i = r0; i < r1; ++i) off[i - r0 + 1] = off[i - r0] + (N - 1 - i);
+    std::vector<long double> gb;
+    if (b) gb = g_b_table(S, *b);
+    if (nthreads < 1) nthreads = 1;
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(dynamic, 4) num_threads(nthreads)
+#endif
+    for (size_t i = r0; i < r1; ++i) {
+        const size_t base = off[i - r0];
+        for (size_t j = i + 1; j < N; ++j) {
+            const size_t p = base + (j - i - 1);
+            if (!b) out[p] = d2g_epilogue_trunc_neq(ca[p], S, regbytes, cards[i], cards[j], measure, k);
+            else if (ca[p] > S || cb[p] > S) out[p] = std::numeric_limits<float>::quiet_NaN();     // not counts of S registers
+            else out[p] = trunc_gtlt_from(gb[ca[p]], gb[cb[p]], cards[i], cards[j], measure, k);
+        }
+    }
+    return D2G_OK;
+}
+
+// the same over a row-major block: rows [a0,a1) x columns [b0,b1) of the N x N matrix, compare(row, column)
+int d2g_epilogue_trunc_rect(const uint32_t *ca, const uint32_t *cb, const double *cards, size_t N, size_t S, size_t a0, size_t a1,
+                            size_t b0, size_t b1, int measure, int k, int regbytes, const long double *b, int nthreads, float *out) {
+    if (a0 > a1 || a1 > N || b0 > b1 || b1 > N || !S) return D2G_ERR_INVALID;
+    if (a0 == a1 || b0 == b1) return D2G_OK;
+    if (!ca || !cards || !out || (b && !cb)) return D2G_ERR_INVALID;
+    std::vector<long double> gb;
+    if (b) gb = g_b_table(S, *b);
+    if (nthreads < 1) nthreads = 1;
+    const size_t w = b1 - b0;
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(dynamic, 4) num_threads(nthreads)
+#endif
+    for (size_t i = a0; i < a1; ++i) {
+        for (size_t j = b0; j < b1; ++j) {
+            const size_t p = (i - a0) * w + (j - b0);
+            if (!b) out[p] = d2g_epilogue_trunc_neq(ca[p], S, regbytes, cards[i], cards[j], measure, k);
+            else if (ca[p] > S || cb[p] > S) out[p] = std::numeric_limits<float>::quiet_NaN();
+            else out[p] = trunc_gtlt_from(gb[ca[p]], gb[cb[p]], cards[i], cards[j], measure, k);
+        }
+    }
+    return D2G_OK;
+}
+
 size_t d2g_ut_count(size_t N, size_t r0, size_t r1) {
     if (r1 > N) r1 = N;
     if (r0 >= r1) return 0;

@@ -9,6 +9,9 @@ struct d2g_cmp_set {
     int algo = D2G_CMP_DIRECT;    // algorithm actually prepared
     d2g_dev<uint64_t> d_rows;     // [N][S]     row-major 64-bit patterns
     d2g_dev<uint64_t> d_cols;     // [S][Npad]  register-major (transposed), zero padded
+    // sets of truncated codes (algo == D2G_CMP_PLANES, d2g_k2_planes.hip): the only buffer of such a set
+    d2g_dev<uint32_t> d_cplanes;  // [ntb][cplanes][Nstride]: bit t%32 of word (t/32, p, j) = bit (cplanes-1-p) of code (j, t)
+    int cplanes = 0;              // bits per code: 8, 16 or 32
     // bit-sliced operand (algo == D2G_CMP_BITSLICE); all buffers are allocated once per set
     d2g_dev<uint32_t> own_planes, own_meta;   // what d_planes / d_meta point at when the set allocated them itself; empty in a set over the caller's operand
     uint32_t *d_planes = nullptr; // exchanged form [ntb][nbits_cap+1][Nstride]: bit x of word = bit b of id[32*tb+x][j], unique values
@@ -108,6 +111,10 @@ struct SpRider { uint32_t *out; size_t cnt; const uint32_t *vsrc; uint32_t vimm,
 
 struct PairShape;
 int  finish_shape(d2g_ctx *ctx, PairShape &sh, unsigned rb);   // d2g_k2.hip
+
+// d2g_k2_planes part (same shared object): (gt, lt) / equality counts of a set of truncated codes over one launch shape
+int  d2g_planes_gtlt(d2g_ctx *ctx, const d2g_cmp_set *set, const PairShape &sh, uint32_t *gt, uint32_t *lt, hipStream_t s);
+int  d2g_planes_eq(d2g_ctx *ctx, const d2g_cmp_set *set, const PairShape &sh, uint32_t *eq, hipStream_t s);
 
 // d2g_k2_bitslice part (same shared object)
 void d2g_bitslice_geometry(d2g_cmp_set *set);

@@ -203,6 +203,15 @@ void d2g_cmp_set_destroy(d2g_cmp_set *set) {
 
 int d2g_cmp_set_algo(const d2g_cmp_set *set) { return set ? set->algo : D2G_ERR_INVALID; }
 
+size_t d2g_cmp_set_operand_bytes(const d2g_cmp_set *set) {
+    if (!set) return 0;
+    return (set->d_rows.cap() + set->d_cols.cap()) * sizeof(uint64_t) +
+           (set->own_planes.cap() + set->d_stream.cap() + set->d_stream_s.cap() + set->d_cplanes.cap()) * sizeof(uint32_t);
+}
+
+// sets of truncated codes (d2g_k2_planes.hip) have no 64-bit patterns, no ids and no sparse path: what needs those refuses them
+#define D2G_NO_CODE_SET(ctx, set, what) D2G_CHECK(ctx, (set)->algo != D2G_CMP_PLANES, what ": not available for a set of truncated codes")
+
 // (re)load the operand: copy + transpose + (bitslice) ids/planes.  Everything is enqueued on `s`.
 static int cmp_set_load(d2g_ctx *ctx, d2g_cmp_set *set, const uint64_t *sig_bits_dev, hipStream_t s) {
     const size_t N = set->N, S = set->S;
@@ -269,6 +278,7 @@ int d2g_cmp_set_update_dev(d2g_ctx *ctx, d2g_cmp_set *set, const uint64_t *sig_b
     if (!ctx) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_update: set belongs to another context");
     D2G_CHECK(ctx, !set->borrowed, "cmp_set_update: this set wraps a caller-owned operand");
+    D2G_NO_CODE_SET(ctx, set, "cmp_set_update");
     D2G_CHECK(ctx, sig_bits_dev != nullptr, "cmp_set_update: null signatures");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     return cmp_set_load(ctx, set, sig_bits_dev, as_stream(stream));
@@ -322,6 +332,7 @@ int d2g_cmp_set_create(d2g_ctx *ctx, const uint64_t *sig_bits_host, size_t N, si
 
 int d2g_cmp_set_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint32_t *info4) {
     if (!ctx || !set || !info4) return D2G_ERR_INVALID;
+    D2G_NO_CODE_SET(ctx, set, "cmp_set_sparse_info");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     if (set->algo != D2G_CMP_BITSLICE) { info4[0] = info4[1] = info4[2] = info4[3] = 0; return D2G_OK; }
     return d2g_bitslice_sparse_info(ctx, set, as_stream(stream), info4);
@@ -329,6 +340,7 @@ int d2g_cmp_set_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, 
 
 int d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out) {
     if (!ctx || !set || !npairs) return D2G_ERR_INVALID;
+    D2G_NO_CODE_SET(ctx, set, "cmp_set_debug_pairs");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     *npairs = 0;
     if (set->algo != D2G_CMP_BITSLICE) return D2G_OK;
@@ -338,6 +350,7 @@ int d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, 
 int d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out8) {
     if (!ctx || !out8) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_sparse_detail: set belongs to another context");
+    D2G_NO_CODE_SET(ctx, set, "cmp_set_sparse_detail");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     for (int x = 0; x < 8; ++x) out8[x] = 0;
     if (set->algo != D2G_CMP_BITSLICE) { D2G_HIP(ctx, hipStreamSynchronize(as_stream(stream))); return D2G_OK; }
@@ -371,12 +384,14 @@ int d2g_cmp_eqcount_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size
     D2G_CHECK(ctx, out != nullptr, "cmp: null output");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     if (set->algo == D2G_CMP_BITSLICE) return d2g_bitslice_ut(ctx, set, r0, r1, out, nullptr, nullptr, as_stream(stream));
+    if (set->algo == D2G_CMP_PLANES) return d2g_planes_eq(ctx, set, ut_shape(set, r0, r1), out, as_stream(stream));
     return launch_direct<false>(ctx, set, ut_shape(set, r0, r1), StoreEq{out}, as_stream(stream));
 }
 
 int d2g_cmp_lut_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, const float *lut, float *out, void *stream) {
     if (!ctx) return D2G_ERR_INVALID;
     if (int rc = check_rows(ctx, set, r0, r1)) return rc;
+    D2G_NO_CODE_SET(ctx, set, "cmp_lut_ut");
     if (d2g_ut_count(set->N, r0, r1) == 0) return D2G_OK;
     D2G_CHECK(ctx, out != nullptr && lut != nullptr, "cmp: null output/lut");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
@@ -388,6 +403,7 @@ int d2g_cmp_lut_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r
 int d2g_cmp_ut_prefill_dev(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1, uint32_t *neq_out, const float *lut, float *out, void *stream) {
     if (!ctx) return D2G_ERR_INVALID;
     if (int rc = check_rows(ctx, set, r0, r1)) return rc;
+    D2G_NO_CODE_SET(ctx, set, "cmp_ut_prefill");
     if (d2g_ut_count(set->N, r0, r1) == 0) return D2G_OK;
     D2G_CHECK(ctx, (neq_out != nullptr) != (lut != nullptr && out != nullptr), "cmp prefill: give the count output, or the table and the float output");
     if (set->algo != D2G_CMP_BITSLICE) return D2G_OK;                  // the direct kernel writes every output itself
@@ -399,6 +415,7 @@ int d2g_cmp_ut_prefill_dev(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1,
 int d2g_cmp_ut_announce_dev(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1, uint32_t *neq_out, const float *lut, float *out) {
     if (!ctx) return D2G_ERR_INVALID;
     if (int rc = check_rows(ctx, set, r0, r1)) return rc;
+    D2G_NO_CODE_SET(ctx, set, "cmp_ut_announce");
     if (d2g_ut_count(set->N, r0, r1) == 0) return D2G_OK;
     if (set->algo != D2G_CMP_BITSLICE || set->borrowed) return D2G_OK;   // the direct kernel writes every output itself; a borrowed operand is never re-prepared
     if (!neq_out && !out) return d2g_bitslice_announce(ctx, set, r0, r1, nullptr, nullptr, nullptr);   // cancel: the set forgets the announced pointer
@@ -418,6 +435,10 @@ int d2g_cmp_gtlt_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t 
     if (int rc = check_rows(ctx, set, r0, r1)) return rc;
     if (d2g_ut_count(set->N, r0, r1) == 0) return D2G_OK;
     D2G_CHECK(ctx, gt != nullptr && lt != nullptr, "cmp: null output");
+    if (set->algo == D2G_CMP_PLANES) {
+        D2G_HIP(ctx, hipSetDevice(ctx->device));
+        return d2g_planes_gtlt(ctx, set, ut_shape(set, r0, r1), gt, lt, as_stream(stream));
+    }
     D2G_CHECK(ctx, set->d_rows != nullptr, "cmp: (gt,lt) needs the raw patterns: create the set with D2G_CMP_DIRECT");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     // order needs the raw patterns: the direct kernel on a DIRECT set
@@ -435,6 +456,7 @@ int d2g_cmp_eqcount_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, si
     PairShape sh{};
     sh.N = set->N; sh.i_lo = a0; sh.i_hi = a1; sh.j_lo = b0; sh.j_hi = b1; sh.ut = 0;
     if (set->algo == D2G_CMP_BITSLICE) return d2g_bitslice_rect(ctx, set, a0, a1, b0, b1, out, as_stream(stream));
+    if (set->algo == D2G_CMP_PLANES) return d2g_planes_eq(ctx, set, sh, out, as_stream(stream));
     return launch_direct<false>(ctx, set, sh, StoreEq{out}, as_stream(stream));
 }
 
@@ -445,10 +467,11 @@ int d2g_cmp_gtlt_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, size_
     D2G_CHECK(ctx, a0 <= a1 && a1 <= set->N && b0 <= b1 && b1 <= set->N, "cmp: rect out of bounds");
     if (a0 == a1 || b0 == b1) return D2G_OK;
     D2G_CHECK(ctx, gt != nullptr && lt != nullptr, "cmp: null output");
-    D2G_CHECK(ctx, set->d_rows != nullptr, "cmp: (gt,lt) needs the raw patterns: create the set with D2G_CMP_DIRECT");
+    D2G_CHECK(ctx, set->d_rows != nullptr || set->algo == D2G_CMP_PLANES, "cmp: (gt,lt) needs the raw patterns: create the set with D2G_CMP_DIRECT");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     PairShape sh{};
     sh.N = set->N; sh.i_lo = a0; sh.i_hi = a1; sh.j_lo = b0; sh.j_hi = b1; sh.ut = 0;
+    if (set->algo == D2G_CMP_PLANES) return d2g_planes_gtlt(ctx, set, sh, gt, lt, as_stream(stream));
     return launch_direct<true>(ctx, set, sh, StoreGtLt{gt, lt, (uint32_t)set->S}, as_stream(stream));
 }
 

@@ -155,7 +155,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     }
     if (what & D2G_WARM_K0) d2g_warm_k0();
     if (what & D2G_WARM_K1) d2g_warm_k1();
-    if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); }
+    if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); }
     if (what & D2G_WARM_K3) d2g_warm_k3();
     return D2G_OK;
 }

@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -46,6 +46,8 @@ void sketch_usage() {
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
                          "  --multiset/--bagminhash/-B [-m/--count-threshold c]   --parse-by-seq (one sketch per record of ONE file)\n"
                          "  --distance/--mash-distance --containment --symmetric-containment --intersection --union-size\n"
+                         "  --fastcmp/--regsize/--regbytes <8|4|2|1>   compare registers truncated to that many bytes (8: as sketched); logarithmic\n"
+                         "                         (setsketch) truncation unless --bbit-sigs selects b-bit signatures\n"
                          "  --batch-size n  -v\n"
                          "  --fmt-compat {10,11}   float text of PHYLIP/TSV output as fmt < 11 (default: fixed notation below 1e16) or\n"
                          "                         fmt >= 11 (exponent form from 1e7) prints it -- the reference's fmt is an unpinned submodule\n"
@@ -124,6 +126,8 @@ int parse_options(int argc, char **argv, Options &o) {
         {"parse-by-seq", no_argument, 0, OPT_PARSEBYSEQ},
         {"fmt-compat", required_argument, 0, OPT_FMTCOMPAT},
         {"gpu-stats", required_argument, 0, OPT_GPUSTATS},
+        {"fastcmp", required_argument, 0, OPT_FASTCMP}, {"regsize", required_argument, 0, OPT_FASTCMP}, {"regbytes", required_argument, 0, OPT_FASTCMP},
+        {"bbit-sigs", no_argument, 0, OPT_BBITSIGS},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
     std::vector<struct option> all(longopts, longopts + sizeof(longopts) / sizeof(longopts[0]) - 1);
@@ -180,6 +184,16 @@ int parse_options(int argc, char **argv, Options &o) {
                 }
                 break;
             case OPT_GPUSTATS: o.gpu_stats = optarg; break;
+            case OPT_FASTCMP: {                                                     // options.h:321-327
+                const double nb = std::atof(optarg);
+                if (nb != 8. && nb != 4. && nb != 2. && nb != 1.) {
+                    std::fprintf(stderr, "--fastcmp must have 8, 4, 2, or 1 as the argument. These are the only register sizes supported.\n");
+                    std::fprintf(stderr, "Exception See usage for --fastcmp instructions.\n");
+                    return 1 + 1;
+                }
+                o.regbytes = int(nb);
+            } break;
+            case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
             case OPT_UNSUPPORTED:
                 std::fprintf(stderr, "dashing2 (MI355X): option --%s is outside the hot-path scope of this build "

@@ -832,6 +832,9 @@ void rect_epilogue(const Options &o, const CmpShape &sh, size_t r0, size_t r1, c
         }
 }
 
+// a long double as a JSON number with every digit (--gpu-stats: the setsketch parameters a and b)
+std::string ldstr(long double v) { char b[64]; std::snprintf(b, sizeof b, "%.21Lg", v); return b; }
+
 // the D2G_* switches the context resolved when it was created (include/d2g.h: d2g_ctx_tuning)
 std::string tuning_json(d2g_ctx *ctx) {
     const int n = d2g_ctx_tuning(ctx, nullptr, 0);
@@ -1003,16 +1006,33 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
     const uint64_t *bits = reinterpret_cast<const uint64_t *>(res.sigs());
     const double *cards = res.cardinalities.data();
     std::vector<float> lut(S + 1);
-    const bool have_lut = d2g_epilogue_lut(S, o.measure, o.k, multiset, lut.data()) == D2G_OK;
-    const bool need_gtlt = !multiset && (S & (S - 1)) != 0;
+    // --fastcmp <4|2|1>: make_compressed (cmp_core.cpp:741) truncates the registers and compare() takes its compressed branch
+    // (:362-449), whatever the sketch space: (gt, lt) of setsketch codes, equal b-bit codes
+    const bool trunc = o.regbytes < 8, trunc_gtlt = trunc && !o.bbit_sigs;
+    std::vector<uint8_t> codes;
+    long double trunc_ab[2] = {0.L, 0.L};
+    if (trunc) {
+        if (!ns) die("Empty signatures; trying to compress registers but don't have any");
+        codes.resize(ns * S * size_t(o.regbytes));
+        double mm[2] = {0, 0};
+        char err[200];
+        if (d2g_regs_truncate(res.sigs(), ns, S, o.regbytes, o.bbit_sigs, codes.data(), trunc_ab, mm, int(o.workers()), err, sizeof err) != D2G_OK)
+            die(std::string("dashing2 (MI355X): ") + err);
+        if (trunc_gtlt)                                             // cmp_core.cpp:262
+            std::fprintf(stderr, "Truncated via setsketch, a = %0.20Lg and b = %0.24Lg from min, max regs %Lg, %Lg\n", trunc_ab[0], trunc_ab[1],
+                         static_cast<long double>(mm[0]), static_cast<long double>(mm[1]));
+    }
+    const bool have_lut = !trunc && d2g_epilogue_lut(S, o.measure, o.k, multiset, lut.data()) == D2G_OK;
+    const bool need_gtlt = trunc ? trunc_gtlt : (!multiset && (S & (S - 1)) != 0);
     {
         const std::vector<int> devs = job_devices(o);
-        if (devs.size() > 1 && !need_gtlt && ns >= 2) {
+        if (devs.size() > 1 && !need_gtlt && !trunc && ns >= 2) {
             if (cmp_core_multi(o, res, devs, have_lut, lut, multiset)) return;
         } else if (devs.size() > 1) {
             // said without -v: the user asked for several GPUs and gets one
             std::fprintf(stderr, "[d2g] D2G_DEVICES ignored for this job (%s): it runs on GPU %d alone\n",
-                         need_gtlt ? "a sketch size that is not a power of two needs (gt, lt) counts from the raw registers, which the gathered bit-plane operand does not hold"
+                         trunc ? "truncated registers (--fastcmp) are compared on one GPU"
+                         : need_gtlt ? "a sketch size that is not a power of two needs (gt, lt) counts from the raw registers, which the gathered bit-plane operand does not hold"
                                    : "fewer than two sketches", o.device);
         }
     }
@@ -1031,7 +1051,9 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
     }
     Emitter em(o, res);
     em.header();
-    check(ctx, d2g_cmp_set_create(ctx, bits, ns, S, need_gtlt ? int(D2G_CMP_DIRECT) : int(D2G_CMP_AUTO), &set), "d2g_cmp_set_create");
+    if (trunc) check(ctx, d2g_cmp_set_create_codes(ctx, codes.data(), ns, S, o.regbytes, &set), "d2g_cmp_set_create_codes");
+    else check(ctx, d2g_cmp_set_create(ctx, bits, ns, S, need_gtlt ? int(D2G_CMP_DIRECT) : int(D2G_CMP_AUTO), &set), "d2g_cmp_set_create");
+    std::vector<uint8_t>().swap(codes);
     const double t_set = now();
     DevBuf dlut(ctx, (S + 1) * sizeof(float));
     if (have_lut) check(ctx, d2g_memcpy_h2d(ctx, dlut.p, lut.data(), (S + 1) * sizeof(float), nullptr), "h2d lut");
@@ -1064,8 +1086,10 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
                         check(ctx, d2g_cmp_eqcount_ut_dev(ctx, set, r0, r1, (uint32_t *)da.p, nullptr), "d2g_cmp_eqcount_ut_dev");
                     }
                     check(ctx, d2g_memcpy_d2h(ctx, ca, da.p, cnt * 4, nullptr), "d2h");
-                    // x87 epilogue on the host (cmp_core.cpp:458-517)
-                    check(ctx, d2g_epilogue_ut(ca, need_gtlt ? cb : nullptr, cards, ns, S, r0, r1, o.measure, o.k, multiset,
+                    // x87 epilogue on the host (cmp_core.cpp:458-517; truncated registers: 406-448)
+                    if (trunc) check(ctx, d2g_epilogue_trunc_ut(ca, need_gtlt ? cb : nullptr, cards, ns, S, r0, r1, o.measure, o.k, o.regbytes,
+                                                                trunc_gtlt ? &trunc_ab[1] : nullptr, int(o.workers()), out), "d2g_epilogue_trunc_ut");
+                    else check(ctx, d2g_epilogue_ut(ca, need_gtlt ? cb : nullptr, cards, ns, S, r0, r1, o.measure, o.k, multiset,
                                                int(o.workers()), out), "d2g_epilogue_ut");
                 }
             } else if (cnt) {                                           // asymmetric / panel: emitrect.cpp:211-268
@@ -1076,7 +1100,9 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
                     check(ctx, d2g_cmp_eqcount_rect_dev(ctx, set, r0, r1, sh.c0, sh.c1, (uint32_t *)da.p, nullptr), "d2g_cmp_eqcount_rect_dev");
                 }
                 check(ctx, d2g_memcpy_d2h(ctx, ca, da.p, cnt * 4, nullptr), "d2h");
-                rect_epilogue(o, sh, r0, r1, ca, cb, cards, S, have_lut, lut, multiset, need_gtlt, out);
+                if (trunc) check(ctx, d2g_epilogue_trunc_rect(ca, need_gtlt ? cb : nullptr, cards, ns, S, r0, r1, sh.c0, sh.c1, o.measure, o.k, o.regbytes,
+                                                              trunc_gtlt ? &trunc_ab[1] : nullptr, int(o.workers()), out), "d2g_epilogue_trunc_rect");
+                else rect_epilogue(o, sh, r0, r1, ca, cb, cards, S, have_lut, lut, multiset, need_gtlt, out);
             }
             t_dev += now() - ta;
             if (sh.symmetric) eq.submit_rows(si, r0, r1, out, [ns](size_t i) { return ns - 1 - i; });
@@ -1088,14 +1114,16 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
         emit_busy = eq.t_busy;
         if (o.verbosity) std::fprintf(stderr, "[d2g] cmp: %zu sketches x S=%zu: upload+prepare+buffers %.3fs, %zu batches %.3fs wall (device+D2H+epilogue %.3fs busy, emit %.3fs busy, "
                                               "overlapped) (algo %s)\n", ns, S, t_loop - t0, nbatches, now() - t_loop, t_dev, emit_busy,
-                                      d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE ? "bitslice" : "direct");
+                                      d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE ? "bitslice" : d2g_cmp_set_algo(set) == D2G_CMP_PLANES ? "planes" : "direct");
     }
     if (g_stats.on) {
         const bool bs = d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE;
         g_stats.raw("cmp", std::string("{\"sketches\": ") + std::to_string(ns) + ", \"sketchsize\": " + std::to_string(S) + ", \"values\": " + std::to_string(sh.total_vals) +
-                    ", \"shape\": " + (sh.symmetric ? "\"upper triangle\"" : o.ok == PANEL ? "\"panel\"" : "\"square\"") + ", \"algo\": " + (bs ? "\"bitslice\"" : "\"direct\"") +
+                    ", \"shape\": " + (sh.symmetric ? "\"upper triangle\"" : o.ok == PANEL ? "\"panel\"" : "\"square\"") + ", \"algo\": " + (bs ? "\"bitslice\"" : trunc ? "\"planes\"" : "\"direct\"") +
+                    ", \"regbytes\": " + std::to_string(o.regbytes) + ", \"truncation\": " + (!trunc ? "null" : trunc_gtlt ? "\"setsketch\"" : "\"bbit\"") +
+                    ", \"a\": " + (trunc_gtlt ? ldstr(trunc_ab[0]) : std::string("null")) + ", \"b\": " + (trunc_gtlt ? ldstr(trunc_ab[1]) : std::string("null")) +
                     ", \"bit_planes\": " + (bs ? planes_json(ctx, set) : std::string("null")) + ", \"sparse_tiles\": " + (bs ? sparse_json(ctx, set) : std::string("null")) +
-                    ", \"algorithmic_bytes\": " + Stats::numstr(8.0 * double(S) * double(ns) + 4.0 * double(sh.total_vals)) + ", \"batches\": " + std::to_string(nbatches) +
+                    ", \"algorithmic_bytes\": " + Stats::numstr(double(o.regbytes) * double(S) * double(ns) + 4.0 * double(sh.total_vals)) + ", \"batches\": " + std::to_string(nbatches) +
                     ", \"slot_values\": " + std::to_string(cap) +
                     ", \"devices\": [{\"index\": " + std::to_string(o.device) + ", \"name\": " + Stats::esc(device_label(o.device)) + ", \"k2\": " + Stats::kernel_json(ctx, "k2") +
                     ", \"k2prep\": " + Stats::kernel_json(ctx, "k2prep") + "}]" +

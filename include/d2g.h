@@ -54,7 +54,8 @@ enum d2g_measure {
 enum d2g_cmp_algo {
     D2G_CMP_AUTO = 0,       /* bit-sliced when it applies, else direct */
     D2G_CMP_DIRECT = 1,     /* 64-bit register compare, LDS-tiled */
-    D2G_CMP_BITSLICE = 2    /* per-column dense ids -> bit planes -> v_bitop3/v_bcnt */
+    D2G_CMP_BITSLICE = 2,   /* per-column dense ids -> bit planes -> v_bitop3/v_bcnt */
+    D2G_CMP_PLANES = 3      /* sets of truncated codes (d2g_cmp_set_create_codes): bit planes of the codes, bit-serial order compare */
 };
 
 /* ---- runtime ------------------------------------------------------------ */
@@ -140,6 +141,37 @@ int      d2g_epilogue_ut(const uint32_t *ca, const uint32_t *cb, const double *c
  * value depends on neq only (power-of-two S in set space; any S in multiset space).
  * Returns D2G_ERR_UNSUPPORTED otherwise. lut_out has S+1 floats. */
 int      d2g_epilogue_lut(size_t sketchsize, int measure, int k, int multiset_space, float *lut_out);
+
+/* ---- truncated registers: the reference's --fastcmp <4|2|1> (alias --regsize, --regbytes) and --bbit-sigs --------
+ * make_compressed(), reference src/cmp_core.cpp:209-322: the n x S matrix of (densified) double signatures becomes
+ * codes of regbytes in {1, 2, 4} (codes_out: uint8/uint16/uint32 [n][S]).
+ *   bbit == 0, "setsketch" (:246-292): minreg/maxreg over the registers that are > 0 and != DBL_MAX, q = 254.3 / 65534 /
+ *     4294967294, b = expl(logl(max/min)/q), a = max/b (CSetSketch::optimal_parameters, src/setsketch.cpp:7-10),
+ *     code = max(0, min(int64(q + 1), (int64)(1.L - logl(sig/a) / log1pl(b - 1.L)))) in x87 long double.  A register <= 0
+ *     makes that cast undefined in C++; its code is DEFINED here as 0, which is what the reference's x86 build yields
+ *     (the conversion gives the "integer indefinite" INT64_MIN, and the clamp then 0).  ab_out[0] = a, ab_out[1] = b;
+ *     minmax_out (may be NULL) = {minreg, maxreg}.
+ *   bbit != 0 (:294-320): code = WangHash(bits(sig) ^ 0xa3407fb23cd20ef) >> (58 | 48 | 32): a byte code has SIX significant
+ *     bits -- the reference's shift table, kept.  ab_out = {0, 0}.
+ * Returns D2G_ERR_INVALID with a message in err (may be NULL) for: regbytes not in {1, 2, 4}; a matrix without any finite
+ * positive register; a register that is +inf; a or b zero, infinite or NaN (the reference falls back to b-bit codes there but
+ * keeps the (gt, lt) epilogue with b = 0 -- not reproduced, SURVEY's list of reference defects). */
+int      d2g_regs_truncate(const double *sigs /* [n][S] */, size_t n, size_t sketchsize, int regbytes, int bbit, void *codes_out,
+                           long double *ab_out /* [2] */, double *minmax_out /* [2] or NULL */, int nthreads, char *err, size_t errcap);
+/* the compressed branch of compare(), reference src/cmp_core.cpp:362-449, followed by 573-575 and the conversion to float:
+ * from the number of equal b-bit codes (:406-423; fmal(neq, 1.L/S, -2^-(8 regbytes)) is ONE rounding) ... */
+float    d2g_epilogue_trunc_neq(uint64_t neq, size_t sketchsize, int regbytes, double lhcard, double rhcard, int measure, int k);
+/* ... and from (#a>b, #a<b) of setsketch codes and their base *b (:425-448, g_b :323-325).  The sketch space plays no part. */
+float    d2g_epilogue_trunc_gtlt(uint64_t gt, uint64_t lt, size_t sketchsize, const long double *b, double lhcard, double rhcard,
+                                 int measure, int k);
+/* array forms (OpenMP) over rows [r0,r1) of the condensed upper triangle and over the row-major block rows [a0,a1) x columns
+ * [b0,b1), compare(row, column).  b == NULL: ca = neq of b-bit codes (cb unused); otherwise ca = gt, cb = lt, and g_b(b, c/S)
+ * is tabulated once for its S+1 arguments (no powl per pair). */
+int      d2g_epilogue_trunc_ut(const uint32_t *ca, const uint32_t *cb, const double *cards, size_t N, size_t sketchsize,
+                               size_t r0, size_t r1, int measure, int k, int regbytes, const long double *b, int nthreads, float *out);
+int      d2g_epilogue_trunc_rect(const uint32_t *ca, const uint32_t *cb, const double *cards, size_t N, size_t sketchsize,
+                                 size_t a0, size_t a1, size_t b0, size_t b1, int measure, int k, int regbytes,
+                                 const long double *b, int nthreads, float *out);
 
 /* ---- host ingest: FASTA/FASTQ(.gz) -> packed run stream (input of K1) -------------
  * Replaces the parsing half of bns::Encoder::for_each + kseq (reference call sites
@@ -430,6 +462,22 @@ int  d2g_cmp_eqcount_ut(d2g_ctx *ctx, const uint64_t *sig_bits, size_t N, size_t
 int  d2g_cmp_dist_ut(d2g_ctx *ctx, const uint64_t *sig_bits, const double *cards, size_t N,
                      size_t sketchsize, size_t r0, size_t r1, int measure, int k, int multiset_space,
                      int algo, int nthreads, float *out);
+
+/* ---- sets of truncated codes (d2g_regs_truncate) ----------------------------------------------------------------
+ * codes = [N][S] unsigned integers of regbytes in {1, 2, 4}.  The device keeps them as 8 * regbytes bit planes (about
+ * N * S * regbytes bytes, not N * S * 8); d2g_cmp_set_algo reports D2G_CMP_PLANES.  d2g_cmp_gtlt_ut_dev, d2g_cmp_gtlt_rect_dev,
+ * d2g_cmp_eqcount_ut_dev and d2g_cmp_eqcount_rect_dev work on such a set (order = the codes as unsigned integers, eq = S - gt - lt);
+ * d2g_cmp_lut_ut_dev, d2g_cmp_ut_prefill_dev, d2g_cmp_ut_announce_dev, d2g_cmp_set_export_operand_dev, d2g_cmp_set_update_dev and the
+ * sparse diagnostics (d2g_cmp_set_sparse_info, _sparse_detail, _debug_pairs) return D2G_ERR_INVALID for it and write nothing. */
+int  d2g_cmp_set_create_codes_dev(d2g_ctx *ctx, const void *codes_dev, size_t N, size_t sketchsize, int regbytes, void *stream,
+                                  d2g_cmp_set **out);
+int  d2g_cmp_set_create_codes(d2g_ctx *ctx, const void *codes_host, size_t N, size_t sketchsize, int regbytes, d2g_cmp_set **out);
+/* bytes of device memory the set's operand occupies (any kind of set) */
+size_t d2g_cmp_set_operand_bytes(const d2g_cmp_set *set);
+/* host-pointer convenience: truncate (d2g_regs_truncate), upload, count, epilogue (d2g_epilogue_trunc_ut) for rows [r0,r1) of the
+ * upper triangle.  sigs = densified double signatures [N][S]. */
+int  d2g_cmp_dist_trunc_ut(d2g_ctx *ctx, const double *sigs, const double *cards, size_t N, size_t sketchsize, size_t r0, size_t r1,
+                           int measure, int k, int regbytes, int bbit, int nthreads, float *out);
 
 /* ---- multi-GPU: RCCL communicator + row-sharded all-pairs engine ------------------------------------
  * Replaces nothing in the reference (it has no multi-process code); it is how the all-pairs seam
