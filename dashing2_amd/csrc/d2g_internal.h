@@ -74,12 +74,33 @@ struct d2g_tuning {
     }
 };
 void d2g_tuning_load(d2g_tuning &t);
+// what the switches that select K2 kernels and thresholds RESOLVE to (unset or invalid: the default).  Filled once per snapshot of the
+// switches (d2g_k2_tuning_resolve, right after d2g_tuning_load) and read as ctx->k2: nobody parses a switch where it is used.
+struct d2g_k2_tuning {
+    bool sparse = true;                 // D2G_BS_SPARSE: 0 = every launch walks every tile
+    size_t min_n = 8192;                // D2G_BS_SPARSE_MIN_N: below ~6000 sketches the extra launches cost more than the tiles they skip
+    int link = 1;                       // D2G_SP_LINK: 0 = no families (every sketch its own segment: the pair list alone; tests)
+    double tile_frac = 0.35;            // D2G_SP_TILE_FRAC: the segments may cover this fraction of all tiles before the dense walk is cheaper
+    int olink = 1;                      // D2G_SP_OLINK: 0 = the table form of the link passes even where the rank kernel left an owner per value (tests: the multi-GPU engine's form)
+    int emit_big = 0;                   // D2G_SP_EMIT_BIG: sp_emit_kernel counts with two words per value at every N (it does from N = 65 536 on; tests)
+    int ride = 63;                      // D2G_SP_RIDE: which kernels of the prepare carry an announced output's fill (d2g_cmp_ut_announce_dev) -- 1 column plan, 2 flatten, 4 count, 8 attach, 16 scan, 32 place; 0 = none, the launch fills (measurements)
+    int remember = 1;                   // D2G_SP_REMEMBER: 0 = every prepare runs the ordering, whatever the last one decided
+    size_t long_list = 786432;          // D2G_SP_LONG_LIST: a pair list of this many entries or more is binned and composed (the last prepare's length decides)
+    int predict = 1;                    // D2G_SP_PREDICT: 0 = no sample before the ordering of a set's first prepare (the ordering finds out by itself, as in round 5)
+    int list_form = 0;                  // D2G_SP_LIST_FORM: 1 = always entry by entry, 2 = always binned (tests, measurements)
+    size_t list_div = 8;                // D2G_SP_LIST_DIV: the pair list holds at most pairs / list_div entries (and at most 2^27)
+    bool sort = true;                   // D2G_BS_SORT: 0 = keep the caller's column order (A/B measurements, tests)
+    int tagbits_max = 31;               // D2G_BS_TAGBITS: 0 .. 30 (tests); unset or out of range: 31
+    int nsplit_req = 0;                 // D2G_BS_NSPLIT: 1, 2 or 4 rank workgroups per column where the hash space has that many partitions (tests / experiments); 0 = automatic
+};
+d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
 std::string d2g_k2_tuning_json(const d2g_ctx *ctx);   // (d2g_k2_bitslice.hip) {"D2G_BS_SPARSE_MIN_N": 8192, ...}: the resolved values of the same switches
 uint64_t d2g_k2_tuning_hash(const d2g_ctx *ctx);   // (d2g_k2_bitslice.hip) FNV-1a over the RESOLVED values of the switches that select K2 kernels and thresholds: what the ranks of one job must agree on
 
 struct d2g_ctx {
     int device = -1;
     d2g_tuning tune;
+    d2g_k2_tuning k2;                       // ... and what its K2 switches resolved to
     int num_cus = 0;
     std::string last_error;
     int timing = 0;                         // D2G_TIME_* mask (d2g_set_timing)

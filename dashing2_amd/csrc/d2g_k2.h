@@ -2,6 +2,128 @@
 #pragma once
 #include "d2g_internal.h"
 
+#include <algorithm>
+
+// part of an upper-triangle launch's fill, carried by a kernel of the prepare chain: the workgroups from `own` on write pieces
+// piece0 .. of 32 KB each (own = 0xFFFFFFFF: nobody rides)
+struct SpRider { uint32_t *out; size_t cnt; const uint32_t *vsrc; uint32_t vimm, own, piece0; };
+constexpr SpRider SP_NO_RIDER{nullptr, 0, nullptr, 0u, 0xFFFFFFFFu, 0u};
+constexpr int SP_FILL_PER_THREAD = 8, SP_FILL_THREADS = 256;   // sp_fill_kernel: a workgroup writes one piece of 32 KB
+inline size_t sp_fill_pieces(size_t cnt) { return div_up<size_t>(cnt / 4 + 1, (size_t)SP_FILL_THREADS * SP_FILL_PER_THREAD); }
+// ---- riders (sp_ride): the share of an announced output's fill that one hosting kernel of the prepare chain carries.  The weights are the
+// hosts' own durations at config 3 (us): each hides about what it lasts; the last host (place) takes what is left.
+constexpr unsigned SP_RW_PLAN = 6, SP_RW_FLATTEN = 5, SP_RW_COUNT = 5, SP_RW_ATTACH = 5, SP_RW_SCAN = 8, SP_RW_ALL = 35;
+
+// the output of the NEXT upper-triangle launch, announced ahead of the prepare (d2g_cmp_ut_announce_dev): the prepare's latency-bound
+// kernels (column plan, flatten, count, attach, scan, place: one to forty workgroups each) carry the fill as extra workgroups
+struct SpAnnounced {
+    uint32_t *out = nullptr; size_t cnt = 0; const uint32_t *vsrc = nullptr; uint32_t vimm = 0;   // the fill value = Store::value_from_mismatches(S, S): the count 0 (vsrc null), or lut[0] (read by the riders when they run)
+    uint32_t next = 0, total = 0;   // pieces of 32 KB handed out so far / in all (0: nothing rides in this prepare)
+    int mask = 0;                   // D2G_SP_RIDE: the kernels of this prepare that may carry pieces
+    void announce(uint32_t *o, size_t n, const uint32_t *src) { out = o; cnt = n; vsrc = src; vimm = 0; }
+    void cancel() { out = nullptr; }                  // nothing rides on the next prepare
+    void served() { out = nullptr; total = 0; }       // an announcement serves ONE prepare
+    // a prepare starts: every piece rides on it, or none (`carry` false: not the sparse path, or the launch will be dense and fill nothing; more pieces than a grid holds)
+    void begin(int ride_mask, bool carry) {
+        mask = ride_mask; next = 0;
+        const size_t pieces = sp_fill_pieces(cnt);
+        total = (out && carry && mask && pieces <= 0x7FFFFFFFu) ? (uint32_t)pieces : 0u;
+    }
+    uint32_t riding() const { return total; }         // pieces this prepare carries
+    SpRider take_all() { next = total; return SpRider{out, cnt, vsrc, vimm, 0u, 0u}; }   // a fill kernel of its own writes every piece: nothing left for the riders
+    // the share of a hosting kernel with `own` workgroups of its own (bit `bit` of the mask): `grid` = what to launch
+    SpRider take(unsigned own, unsigned weight, bool last, int bit, unsigned *grid) {
+        *grid = own;
+        if (next >= total || !(mask & bit)) return SP_NO_RIDER;
+        const uint32_t left = total - next;
+        uint32_t n = last ? left : (uint32_t)std::min<uint64_t>(left, ((uint64_t)total * weight + SP_RW_ALL - 1) / SP_RW_ALL);
+        n = std::min<uint32_t>(n, 0x7FFFFFFFu - own);
+        const SpRider r{out, cnt, vsrc, vimm, own, next};
+        next += n;
+        *grid = own + n;
+        return r;
+    }
+};
+
+// what is already written of the output of the next upper-triangle launch: by the engine at the start of its step (d2g_bitslice_prefill), or by
+// the riders of a prepare.  The next sparse launch skips that part of its fill.
+struct SpFilled {
+    uint32_t *out = nullptr;            // the output (null: nothing is filled)
+    size_t cnt = 0;                     // ... how many outputs that fill covered
+    size_t pieces = 0;                  // ... how many 32 KB pieces of it are written (all of them after an early fill; what rode on the prepare's kernels otherwise)
+    const uint32_t *src = nullptr;      // ... WHAT was written: the table whose first entry is the fill value (nullptr: the count 0)
+    bool by_riders = false;             // ... by the riders of a prepare (void once another prepare has run) or by d2g_cmp_ut_prefill_dev (valid until the next upper-triangle launch)
+    void set_early(uint32_t *o, size_t n, const uint32_t *s) { out = o; cnt = n; pieces = (size_t)-1; src = s; by_riders = false; }
+    void set_by_riders(const SpAnnounced &a) { out = a.out; cnt = a.cnt; pieces = a.next; src = a.vsrc; by_riders = true; }   // (the launch fills what is left)
+    // pieces [0, done_for) of a launch's `npieces` need no fill.  ADVICE r5: the same output, the same rows AND the same fill value -- a count
+    // launch into a buffer that was pre-filled for a table launch fills again
+    size_t done_for(const uint32_t *o, size_t n, const uint32_t *s, size_t npieces) const { return (out == o && cnt == n && src == s) ? std::min(pieces, npieces) : 0; }
+    void void_after_prepare() { if (by_riders) out = nullptr; }   // what an EARLIER prepare's riders wrote is void once another prepare has run (the caller may have used the buffer in between)
+    void clear() { out = nullptr; }                   // a launch has written (or filled) every output itself
+};
+
+// the words of mapped host memory the device writes and the host reads without synchronisation (SpState::h_gaveup / d_gaveup):
+//   GAVEUP     1 = the last ordering raised order[0] (the next prepare skips the ordering); the host writes it too, after a first look
+//   LIST_LEN   length of the last prepare's pair list (the permute launch)
+//   SUMS .. +3 the first look's raw sums E, F, shared values, planes (sp_sample_fin_kernel)
+//   TICKET     the word the first look's last workgroup writes when the sums are in
+enum SpMappedWord : uint32_t { SP_MW_GAVEUP = 0, SP_MW_LIST_LEN = 1, SP_MW_SUMS = 2, SP_MW_TICKET = 6, SP_MW_WORDS = 16 };
+
+// which way a prepare goes: the first look at the matrix, the remembered give-up, the form of the pair list
+struct SpDecision {
+    unsigned prepares = 0; bool skipped = false;   // prepares so far; the last one skipped the ordering
+    int skip_cached = -1;             // this prepare's reading of the remembered give-up (-1: not read yet)
+    bool sample_pending = false; uint32_t sample_ticket = 0;   // the first look's kernels are enqueued; the value their last workgroup writes to the ticket word when the sums are in
+    bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)
+    bool big = true;                  // this prepare enqueued the binned form of the pair list (sp_expect_long_list)
+    bool looked = false, looked_dense = false; uint32_t samp_sums[4] = {0, 0, 0, 0};   // the last prepare's first look: taken, its decision, its raw sums E, F, shared values, planes
+};
+
+// everything the sparse path of a set owns (sp_alloc builds one; a set without it takes the dense walk)
+struct SpState {
+    unsigned sp_launch = 0;       // sparse launches so far: the control words are double-buffered (a launch zeroes the next one's)
+    d2g_dev<uint32_t> d_stream_s;   // plane stream in sorted order
+    d2g_dev<uint32_t> d_sperm;      // [Nstride] sketch at sorted position p (0xFFFFFFFF = padding)
+    d2g_dev<uint32_t> d_sinv;       // [Npad]    sorted position of sketch j
+    d2g_dev<uint32_t> d_label;      // [2][Npad] union-find labels (-> segment starts after the sort) | root of every sketch
+    d2g_dev<uint32_t> d_owner;      // [S][owner_stride] one holder of every shared value (rank r -> owner[r - 1]); single-partition owning sets only
+    size_t owner_stride = 0;
+    d2g_dev<uint32_t> d_segend;     // [Npad]    end of the segment of root r (the sort's scan)
+    d2g_dev<uint32_t> d_posseg;     // [Npad][2] (start, end) of the segment sorted position p lies in (sp_place_kernel; the sub-tile test of the pair kernel and the pair list)
+    d2g_dev<uint32_t> d_hint;       // [2][Npad] per sketch the smallest holder of a value it shares (even / odd column pairs), 0xFFFFFFFF = none
+    d2g_dev<uint32_t> d_spz;        // ONE block the prepare clears: the arrays below
+    size_t spz_words = 0;
+    uint32_t *d_lcnt = nullptr;       // (this and d_gbm, d_order, d_plctl, d_fullctl, d_binc: inside d_spz) [Npad+1]  counting sort: sketches per root, then the placing cursors (= segment ends)
+    uint32_t *d_gbm = nullptr;        // 8 control words + the tile bitmap over ALL sorted row blocks (the segments' tiles); partial launches derive theirs from it
+    uint32_t *d_order = nullptr;      // [8] [0] 1 = the launches walk every tile of the caller's-order operand (dense), [2] deep label chains
+    uint32_t *d_plctl = nullptr;      // [12] [0] entries emitted into the pair list
+    d2g_dev<uint32_t> d_rowpos;     // [Nstride] launch rows: sorted position of launch row k
+    d2g_dev<uint32_t> d_rowk;       // [Npad]    launch row of sketch j (0xFFFFFFFF = not a row of this launch)
+    d2g_dev<uint32_t> d_rowstream;  // [planes][Nstride] row-coded words of the launch rows, gathered (partial launches)
+    d2g_dev<uint32_t> d_tiles, d_spctl; uint32_t *d_tilebm = nullptr;   // a partial launch's work list, 2 x 8 control words {tiles listed, flags, -, candidates} + its tile bitmap (inside d_spctl)
+    d2g_dev<uint32_t> d_tiles_full; uint32_t *d_fullctl = nullptr;   // work lists + control words (inside d_spz) of a whole-triangle launch, left by the prepare (sp_permute_kernel)
+    bool full_list_valid = false;
+    d2g_pinned<uint32_t> h_gaveup; uint32_t *d_gaveup = nullptr;   // SP_MW_WORDS words of mapped host memory (SpMappedWord) and their device address; no mapped memory: h_gaveup is null and d_gaveup a spare word of d_order
+    d2g_stream fill_stream; d2g_event fill_fork, fill_join;   // a LARGE announced output is filled beside the rank kernel (d2g_bitslice_prepare)
+    d2g_stream samp_stream; d2g_event samp_event;   // the first look runs beside the column plan and the planes kernel
+    d2g_dev<uint32_t> d_samp;       // [16][Npad] + 2: the first look at a matrix (sp_sample): registers shared with sixteen sampled sketches
+    SpDecision dec;
+    SpAnnounced announced;
+    SpFilled filled;
+    const uint32_t *last_ctl = nullptr;   // control words of the last sparse launch (d2g_cmp_set_sparse_info)
+    d2g_dev<unsigned long long> d_plist;   // pair list: (i | j << 32), i < j caller's indices, one entry per (pair in different segments, shared value)
+    size_t plist_cap = 0;
+    // the list BINNED by output region (band of 32 rows x chunk of 2^bin_cshift columns): what sp_compose_kernel reads
+    d2g_dev<unsigned long long> d_plist2;
+    uint32_t *d_binc = nullptr;                       // [nbins] entries per bin (inside the block the prepare clears)
+    d2g_dev<uint32_t> d_bstart;                     // [nbins + 1] first entry of every bin in d_plist2
+    d2g_dev<uint32_t> d_cw_ents; d2g_dev<unsigned long long> d_cw_vals; size_t cw_ecap = 0, cw_vcap = 0;   // sp_emit_kernel -> sp_pairs_kernel: the holders of the mixed values, one record per value
+    d2g_dev<uint32_t> d_hoff;                       // [bin_nwg][nbins] where the entries a counting workgroup met go inside their bin (sp_hist_body -> sp_bin_kernel)
+    uint32_t nbins = 0, bin_nch = 0, bin_cshift = 10, bin_nwg = 1;
+    bool bin_ok = true;                               // the bins fit (sp_bin_geometry): otherwise the list is applied entry by entry only
+    size_t tilebm_words = 0, tiles_cap = 0;
+};
+
 struct d2g_cmp_set {
     d2g_ctx *ctx = nullptr;
     size_t N = 0, S = 0;
@@ -44,70 +166,13 @@ struct d2g_cmp_set {
     // many registers -- a run of adjacent positions, the plane stream is built in THAT order, and an upper-triangle launch walks only
     // the 32 x 256 tiles a family's rows and columns meet in; pairs of DIFFERENT families that share a value by chance are counted from
     // a pair list; every other pair has 0 matches (the output is pre-filled with the value of 0).  Exact for any input.
-    bool sparse_ok = false;       // eligible and enabled (D2G_BS_SPARSE, D2G_BS_SPARSE_MIN_N)
-    unsigned sp_launch = 0;       // sparse launches so far: the control words are double-buffered (a launch zeroes the next one's)
+    std::unique_ptr<SpState> sp;  // everything that path owns; null: not eligible, switched off (D2G_BS_SPARSE, D2G_BS_SPARSE_MIN_N) or no memory for it -- the dense walk
+    bool sparse_ok() const { return sp != nullptr; }
     size_t ncols = 0;             // register columns the sparse path walks: S, or all ntb * 32 register slots of an engine-managed gathered operand
-    bool srt_valid = false;       // d_stream_s / d_sperm describe the operand last prepared
-    bool nat_valid = false;       // d_stream (caller's order; rectangular launches, dense launches) is up to date
-    d2g_dev<uint32_t> d_stream_s;   // plane stream in sorted order
-    d2g_dev<uint32_t> d_sperm;      // [Nstride] sketch at sorted position p (0xFFFFFFFF = padding)
-    d2g_dev<uint32_t> d_sinv;       // [Npad]    sorted position of sketch j
-    d2g_dev<uint32_t> d_label;      // [2][Npad] union-find labels (-> segment starts after the sort) | root of every sketch
-    d2g_dev<uint32_t> d_owner;      // [S][owner_stride] one holder of every shared value (rank r -> owner[r - 1]); single-partition owning sets only
-    size_t owner_stride = 0;
-    d2g_dev<uint32_t> d_segend;     // [Npad]    end of the segment of root r (the sort's scan)
-    d2g_dev<uint32_t> d_posseg;     // [Npad][2] (start, end) of the segment sorted position p lies in (sp_place_kernel; the sub-tile test of the pair kernel and the pair list)
-    d2g_dev<uint32_t> d_hint;       // [2][Npad] per sketch the smallest holder of a value it shares (even / odd column pairs), 0xFFFFFFFF = none
-    d2g_dev<uint32_t> d_spz;        // ONE block the prepare clears: the arrays below
-    size_t spz_words = 0;
-    uint32_t *d_lcnt = nullptr;       // (this and d_gbm, d_order, d_plctl, d_fullctl, d_binc: inside d_spz) [Npad+1]  counting sort: sketches per root, then the placing cursors (= segment ends)
-    uint32_t *d_gbm = nullptr;        // 8 control words + the tile bitmap over ALL sorted row blocks (the segments' tiles); partial launches derive theirs from it
-    uint32_t *d_order = nullptr;      // [8] [0] 1 = the launches walk every tile of the caller's-order operand (dense), [2] deep label chains
-    uint32_t *d_plctl = nullptr;      // [12] [0] entries emitted into the pair list
-    d2g_dev<uint32_t> d_rowpos;     // [Nstride] launch rows: sorted position of launch row k
-    d2g_dev<uint32_t> d_rowk;       // [Npad]    launch row of sketch j (0xFFFFFFFF = not a row of this launch)
-    d2g_dev<uint32_t> d_rowstream;  // [planes][Nstride] row-coded words of the launch rows, gathered (partial launches)
-    d2g_dev<uint32_t> d_tiles, d_spctl; uint32_t *d_tilebm = nullptr;   // a partial launch's work list, 2 x 8 control words {tiles listed, flags, -, candidates} + its tile bitmap (inside d_spctl)
-    d2g_dev<uint32_t> d_tiles_full; uint32_t *d_fullctl = nullptr;   // work lists + control words (inside d_spz) of a whole-triangle launch, left by the prepare (sp_permute_kernel)
-    bool full_list_valid = false;
-    d2g_pinned<uint32_t> h_gaveup; uint32_t *d_gaveup = nullptr;   // a word of mapped host memory and its device address: 1 = the last ordering raised order[0] (the next prepare skips the ordering); no mapped memory: d_gaveup is a spare word of d_order
-    unsigned sp_prepares = 0; bool sp_skipped = false;
-    d2g_stream fill_stream; d2g_event fill_fork, fill_join;   // a LARGE announced output is filled beside the rank kernel (d2g_bitslice_prepare)
-    d2g_stream samp_stream; d2g_event samp_event;   // the first look runs beside the column plan and the planes kernel
-    bool sample_pending = false; uint32_t sample_ticket = 0;   // the first look's kernels are enqueued; the word (h_gaveup[6]) their last workgroup writes when the sums are in
-    int skip_cached = -1;             // this prepare's reading of the remembered give-up (-1: not read yet)
-    d2g_dev<uint32_t> d_samp;       // [16][Npad] + 2: the first look at a matrix (sp_sample): registers shared with sixteen sampled sketches
-    bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)
-    bool sp_big = true;               // this prepare enqueued the binned form of the pair list (sp_expect_long_list)
-    bool looked = false, looked_dense = false; uint32_t samp_sums[4] = {0, 0, 0, 0};   // the last prepare's first look: taken, its decision, its raw sums E, F, shared values, planes
-    uint32_t *prefilled = nullptr;        // output the engine filled at the start of its step (d2g_bitslice_prefill): the next sparse launch into it skips its fill
-    size_t prefilled_cnt = 0;             // ... and how many outputs that fill covered
-    size_t prefilled_pieces = 0;          // ... and how many 32 KB pieces of it are written (all of them after an early fill; what rode on the prepare's kernels otherwise)
-    const uint32_t *prefilled_src = nullptr;   // ... and WHAT was written: the table whose first entry is the fill value (nullptr: the count 0) -- a launch with another store fills for itself
-    bool prefilled_by_riders = false;     // ... by the riders of a prepare (void once another prepare has run) or by d2g_cmp_ut_prefill_dev (valid until the next upper-triangle launch)
-    int ride_mask = 0;
-    // the output of the NEXT upper-triangle launch, announced ahead of the prepare (d2g_cmp_ut_announce_dev): the prepare's latency-bound
-    // kernels (column plan, flatten, count, attach, scan, place: one to forty workgroups each) carry the fill as extra workgroups
-    uint32_t *ride_out = nullptr; size_t ride_cnt = 0; const uint32_t *ride_vsrc = nullptr; uint32_t ride_vimm = 0;
-    uint32_t ride_next = 0, ride_total = 0;   // pieces of 32 KB handed out so far / in all (0: nothing rides in this prepare)
-    const uint32_t *last_ctl = nullptr;   // control words of the last sparse launch (d2g_cmp_set_sparse_info)
-    d2g_dev<unsigned long long> d_plist;   // pair list: (i | j << 32), i < j caller's indices, one entry per (pair in different segments, shared value)
-    size_t plist_cap = 0;
-    // the list BINNED by output region (band of 32 rows x chunk of 2^bin_cshift columns): what sp_compose_kernel reads
-    d2g_dev<unsigned long long> d_plist2;
-    uint32_t *d_binc = nullptr;                       // [nbins] entries per bin (inside the block the prepare clears)
-    d2g_dev<uint32_t> d_bstart;                     // [nbins + 1] first entry of every bin in d_plist2
-    d2g_dev<uint32_t> d_cw_ents; d2g_dev<unsigned long long> d_cw_vals; size_t cw_ecap = 0, cw_vcap = 0;   // sp_emit_kernel -> sp_pairs_kernel: the holders of the mixed values, one record per value
-    d2g_dev<uint32_t> d_hoff;                       // [bin_nwg][nbins] where the entries a counting workgroup met go inside their bin (sp_hist_body -> sp_bin_kernel)
-    uint32_t nbins = 0, bin_nch = 0, bin_cshift = 10, bin_nwg = 1;
-    bool bin_ok = true;                               // the bins fit (sp_bin_geometry): otherwise the list is applied entry by entry only
-    size_t tilebm_words = 0, tiles_cap = 0;
+    bool srt_valid = false;       // sp->d_stream_s / sp->d_sperm describe the operand last prepared
+    mutable bool nat_valid = false;   // d_stream (caller's order; rectangular launches, dense launches) is up to date (mutable: a launch on a const set writes it on demand, d2g_bitslice_ensure_natural)
 };
 constexpr int BS_CC_STRIDE = 8;
-
-// part of an upper-triangle launch's fill, carried by a kernel of the prepare chain: the workgroups from `own` on write pieces
-// piece0 .. of 32 KB each (own = 0xFFFFFFFF: nobody rides)
-struct SpRider { uint32_t *out; size_t cnt; const uint32_t *vsrc; uint32_t vimm, own, piece0; };
 
 struct PairShape;
 int  finish_shape(d2g_ctx *ctx, PairShape &sh, unsigned rb);   // d2g_k2.hip

@@ -206,7 +206,7 @@ int d2g_cmp_set_algo(const d2g_cmp_set *set) { return set ? set->algo : D2G_ERR_
 size_t d2g_cmp_set_operand_bytes(const d2g_cmp_set *set) {
     if (!set) return 0;
     return (set->d_rows.cap() + set->d_cols.cap()) * sizeof(uint64_t) +
-           (set->own_planes.cap() + set->d_stream.cap() + set->d_stream_s.cap() + set->d_cplanes.cap()) * sizeof(uint32_t);
+           (set->own_planes.cap() + set->d_stream.cap() + (set->sp ? set->sp->d_stream_s.cap() : 0) + set->d_cplanes.cap()) * sizeof(uint32_t);
 }
 
 // sets of truncated codes (d2g_k2_planes.hip) have no 64-bit patterns, no ids and no sparse path: what needs those refuses them
@@ -371,12 +371,6 @@ static int check_rows(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1
     return D2G_OK;
 }
 
-static PairShape ut_shape(const d2g_cmp_set *set, size_t r0, size_t r1) {
-    PairShape sh{};
-    sh.N = set->N; sh.i_lo = r0; sh.i_hi = r1; sh.j_lo = r0 + 1 < set->N ? r0 + 1 : set->N; sh.j_hi = set->N; sh.ut = 1;
-    return sh;
-}
-
 int d2g_cmp_eqcount_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, uint32_t *out, void *stream) {
     if (!ctx) return D2G_ERR_INVALID;
     if (int rc = check_rows(ctx, set, r0, r1)) return rc;
@@ -384,8 +378,8 @@ int d2g_cmp_eqcount_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size
     D2G_CHECK(ctx, out != nullptr, "cmp: null output");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     if (set->algo == D2G_CMP_BITSLICE) return d2g_bitslice_ut(ctx, set, r0, r1, out, nullptr, nullptr, as_stream(stream));
-    if (set->algo == D2G_CMP_PLANES) return d2g_planes_eq(ctx, set, ut_shape(set, r0, r1), out, as_stream(stream));
-    return launch_direct<false>(ctx, set, ut_shape(set, r0, r1), StoreEq{out}, as_stream(stream));
+    if (set->algo == D2G_CMP_PLANES) return d2g_planes_eq(ctx, set, ut_shape(set->N, r0, r1), out, as_stream(stream));
+    return launch_direct<false>(ctx, set, ut_shape(set->N, r0, r1), StoreEq{out}, as_stream(stream));
 }
 
 int d2g_cmp_lut_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, const float *lut, float *out, void *stream) {
@@ -396,7 +390,7 @@ int d2g_cmp_lut_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r
     D2G_CHECK(ctx, out != nullptr && lut != nullptr, "cmp: null output/lut");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     if (set->algo == D2G_CMP_BITSLICE) return d2g_bitslice_ut(ctx, set, r0, r1, nullptr, lut, out, as_stream(stream));
-    return launch_direct<false>(ctx, set, ut_shape(set, r0, r1), StoreLut{out, lut}, as_stream(stream));
+    return launch_direct<false>(ctx, set, ut_shape(set->N, r0, r1), StoreLut{out, lut}, as_stream(stream));
 }
 
 // The fill of an upper-triangle launch, enqueued AHEAD of it (include/d2g.h): exactly one of neq_out / (lut, out) is given.
@@ -418,8 +412,8 @@ int d2g_cmp_ut_announce_dev(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1
     D2G_NO_CODE_SET(ctx, set, "cmp_ut_announce");
     if (d2g_ut_count(set->N, r0, r1) == 0) return D2G_OK;
     if (set->algo != D2G_CMP_BITSLICE || set->borrowed) return D2G_OK;   // the direct kernel writes every output itself; a borrowed operand is never re-prepared
-    if (!neq_out && !out) return d2g_bitslice_announce(ctx, set, r0, r1, nullptr, nullptr, nullptr);   // cancel: the set forgets the announced pointer
-    D2G_CHECK(ctx, (neq_out != nullptr) != (lut != nullptr && out != nullptr), "cmp announce: give the count output, or the table and the float output");
+    // (no output at all: cancel -- the set forgets the announced pointer)
+    D2G_CHECK(ctx, (!neq_out && !out) || (neq_out != nullptr) != (lut != nullptr && out != nullptr), "cmp announce: give the count output, or the table and the float output");
     return d2g_bitslice_announce(ctx, set, r0, r1, neq_out, lut, out);
 }
 
@@ -437,12 +431,12 @@ int d2g_cmp_gtlt_ut_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t 
     D2G_CHECK(ctx, gt != nullptr && lt != nullptr, "cmp: null output");
     if (set->algo == D2G_CMP_PLANES) {
         D2G_HIP(ctx, hipSetDevice(ctx->device));
-        return d2g_planes_gtlt(ctx, set, ut_shape(set, r0, r1), gt, lt, as_stream(stream));
+        return d2g_planes_gtlt(ctx, set, ut_shape(set->N, r0, r1), gt, lt, as_stream(stream));
     }
     D2G_CHECK(ctx, set->d_rows != nullptr, "cmp: (gt,lt) needs the raw patterns: create the set with D2G_CMP_DIRECT");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     // order needs the raw patterns: the direct kernel on a DIRECT set
-    return launch_direct<true>(ctx, set, ut_shape(set, r0, r1), StoreGtLt{gt, lt, (uint32_t)set->S}, as_stream(stream));
+    return launch_direct<true>(ctx, set, ut_shape(set->N, r0, r1), StoreGtLt{gt, lt, (uint32_t)set->S}, as_stream(stream));
 }
 
 int d2g_cmp_eqcount_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, size_t a1, size_t b0, size_t b1,
@@ -453,8 +447,7 @@ int d2g_cmp_eqcount_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, si
     if (a0 == a1 || b0 == b1) return D2G_OK;
     D2G_CHECK(ctx, out != nullptr, "cmp: null output");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    PairShape sh{};
-    sh.N = set->N; sh.i_lo = a0; sh.i_hi = a1; sh.j_lo = b0; sh.j_hi = b1; sh.ut = 0;
+    const PairShape sh = rect_shape(set->N, a0, a1, b0, b1);
     if (set->algo == D2G_CMP_BITSLICE) return d2g_bitslice_rect(ctx, set, a0, a1, b0, b1, out, as_stream(stream));
     if (set->algo == D2G_CMP_PLANES) return d2g_planes_eq(ctx, set, sh, out, as_stream(stream));
     return launch_direct<false>(ctx, set, sh, StoreEq{out}, as_stream(stream));
@@ -469,8 +462,7 @@ int d2g_cmp_gtlt_rect_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, size_
     D2G_CHECK(ctx, gt != nullptr && lt != nullptr, "cmp: null output");
     D2G_CHECK(ctx, set->d_rows != nullptr || set->algo == D2G_CMP_PLANES, "cmp: (gt,lt) needs the raw patterns: create the set with D2G_CMP_DIRECT");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    PairShape sh{};
-    sh.N = set->N; sh.i_lo = a0; sh.i_hi = a1; sh.j_lo = b0; sh.j_hi = b1; sh.ut = 0;
+    const PairShape sh = rect_shape(set->N, a0, a1, b0, b1);
     if (set->algo == D2G_CMP_PLANES) return d2g_planes_gtlt(ctx, set, sh, gt, lt, as_stream(stream));
     return launch_direct<true>(ctx, set, sh, StoreGtLt{gt, lt, (uint32_t)set->S}, as_stream(stream));
 }

@@ -24,7 +24,6 @@
 #include <chrono>
 #include <cstring>
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 namespace {
@@ -461,7 +460,6 @@ inline unsigned sp_side_fill_grid(const d2g_ctx *ctx, uint32_t pieces, size_t wo
     const unsigned g = need <= 3700.0 ? cus / 2 : need <= 4400.0 ? cus * 3 / 4 : need <= 5000.0 ? cus * 3 / 2 : pieces;
     return std::max(1u, std::min<unsigned>(pieces, g));
 }
-constexpr SpRider SP_NO_RIDER{nullptr, 0, nullptr, 0u, 0xFFFFFFFFu, 0u};
 
 // ------------------------------------------------------------------ 1b. column plan
 // One workgroup, a kernel of its own.  (Letting the LAST workgroup of the rank kernel do this -- ticket counter -- was
@@ -905,10 +903,7 @@ int alloc_prepare_workspace(d2g_ctx *ctx, d2g_cmp_set *set) {
         const uint32_t nparts = set->T >> BS_LOG_TLDS_MAX;
         int want = 1;
         while (want < 4 && (uint32_t)want * 2 <= nparts && S * (size_t)want < (size_t)std::max(ctx->num_cus, 1)) want *= 2;
-        if (const char *e = ctx->tune.get("D2G_BS_NSPLIT")) {                 // tests / experiments
-            const int v = std::atoi(e);
-            if ((v == 1 || v == 2 || v == 4) && (uint32_t)v <= nparts) want = v;
-        }
+        if (ctx->k2.nsplit_req && (uint32_t)ctx->k2.nsplit_req <= nparts) want = ctx->k2.nsplit_req;   // D2G_BS_NSPLIT (tests / experiments)
         set->nsplit = want;
     }
     const char *what = "bitslice alloc";
@@ -922,10 +917,21 @@ int alloc_prepare_workspace(d2g_ctx *ctx, d2g_cmp_set *set) {
     set->d_meta = set->own_meta;
     return D2G_OK;
 }
-bool sort_columns(const d2g_ctx *ctx) {
-    const char *e = ctx->tune.get("D2G_BS_SORT");     // "0": keep the caller's column order (A/B measurements, tests)
-    return !(e && e[0] == '0');
+// the bit transpose of the ids (bs_planes_kernel): the plane stream and / or the exchange form (`forms`; the latter into `planes`).  `init`: what
+// the sparse path's ordering wants initialised by the same launch
+int launch_planes(d2g_ctx *ctx, const d2g_cmp_set *set, uint32_t *planes, int forms, const SpInit &init, hipStream_t s) {
+    const dim3 grid((unsigned)div_up<size_t>(set->Nstride, 256), (unsigned)set->ntb);
+    const bool split = set->logT > BS_LOG_TLDS_MAX && set->nsplit > 1;
+    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, set->d_ids, set->N, set->Npad,
+                       planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms, set->d_perm, set->d_colcnt, (const uint32_t *)nullptr, init);
+    D2G_HIP(ctx, hipGetLastError());
+    return D2G_OK;
 }
+// once armed: `s` waits for `ev` when the scope ends, however it ends
+struct JoinOnExit {
+    hipStream_t s; hipEvent_t ev = nullptr;
+    ~JoinOnExit() { if (ev) (void)hipStreamWaitEvent(s, ev, 0); }
+};
 }  // namespace
 
 // one-time allocation of the bit-sliced operand and its workspace
@@ -935,11 +941,10 @@ int d2g_bitslice_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     set->d_planes = set->own_planes;
     if (int rc = d2g_bitslice_alloc_stream(ctx, set)) return rc;
     set->ncols = set->S;
-    set->sparse_ok = sparse_enabled(ctx, set->N) && set->S < 65536;          // (the sparse kernel packs two mismatch counts into one LDS word)
-    if (set->sparse_ok && sp_alloc(ctx, set) != D2G_OK) { sp_free(set); (void)hipGetLastError(); set->sparse_ok = false; }
-    if (set->sparse_ok && set->nsplit == 1) {                            // one holder per shared value, left by the rank kernel (sp_olink_kernel)
-        set->owner_stride = set->N / 2 + 8;
-        if (set->d_owner.alloc(ctx, set->S * set->owner_stride, "bitslice owner alloc") != D2G_OK) (void)hipGetLastError();
+    if (sparse_enabled(ctx, set->N) && set->S < 65536 && sp_alloc(ctx, set) != D2G_OK) (void)hipGetLastError();   // (S: the sparse kernel packs two mismatch counts into one LDS word)
+    if (set->sparse_ok() && set->nsplit == 1) {                          // one holder per shared value, left by the rank kernel (sp_olink_kernel)
+        set->sp->owner_stride = set->N / 2 + 8;
+        if (set->sp->d_owner.alloc(ctx, set->S * set->sp->owner_stride, "bitslice owner alloc") != D2G_OK) (void)hipGetLastError();
     }   // no memory for the sparse path's buffers: the dense walk works without them
     return D2G_OK;
 }
@@ -949,63 +954,61 @@ int d2g_bitslice_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
 // overflowed on some column -- see d2g_bitslice_status)
 int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     const size_t N = set->N, S = set->S, Npad = set->Npad;
+    SpState *const sp = set->sp.get();
     // an announced output (d2g_cmp_ut_announce_dev): this prepare's latency-bound kernels carry its fill -- unless the ordering is going to
     // be skipped (the remembered give-up: the launch will be dense and fill nothing)
-    const bool sparse_path = set->sparse_ok && !set->export_only && !set->want_exchange;
-    set->ride_next = 0; set->ride_total = 0;
-    set->ride_mask = sp_tuning(ctx).ride;
-    // (the remembered word is device-written host memory read without synchronisation: read ONCE per prepare -- ADVICE r5 -- and handed down)
-    set->skip_cached = sparse_path ? (sp_will_skip(ctx, set) ? 1 : 0) : -1;
-    if (set->ride_out && sparse_path && set->ride_mask && set->skip_cached != 1)
-        set->ride_total = (uint32_t)std::min<size_t>(sp_fill_pieces(set->ride_cnt), 0x7FFFFFFFu);
-    if (sp_fill_pieces(set->ride_cnt) > 0x7FFFFFFFu) set->ride_total = 0;
-    bool side_fill = false;
-    if (set->ride_total >= SP_SIDE_FILL_PIECES) {
-        if (!set->fill_stream) {
-            if (set->fill_stream.create(hipStreamNonBlocking) != hipSuccess || set->fill_fork.create(hipEventDisableTiming) != hipSuccess ||
-                set->fill_join.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); set->fill_stream.reset(); set->fill_fork.reset(); set->fill_join.reset(); }
+    const bool sparse_path = sp && !set->export_only && !set->want_exchange;
+    JoinOnExit join{s};
+    if (sp) {
+        // (the remembered word is device-written host memory read without synchronisation: read ONCE per prepare -- ADVICE r5 -- and handed down)
+        sp->dec.skip_cached = sparse_path ? (sp_will_skip(ctx, *sp) ? 1 : 0) : -1;
+        sp->announced.begin(ctx->k2.ride, sparse_path && sp->dec.skip_cached != 1);
+    }
+    if (sp && sp->announced.riding() >= SP_SIDE_FILL_PIECES) {
+        if (!sp->fill_stream) {
+            if (sp->fill_stream.create(hipStreamNonBlocking) != hipSuccess || sp->fill_fork.create(hipEventDisableTiming) != hipSuccess ||
+                sp->fill_join.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); sp->fill_stream.reset(); sp->fill_fork.reset(); sp->fill_join.reset(); }
         }
-        if (set->fill_stream) {
+        if (sp->fill_stream) {
             // behind everything already on `s` (the transpose of this update; whoever read the output last), beside everything this prepare enqueues
-            hipStream_t fs = set->fill_stream;
-            D2G_HIP(ctx, hipEventRecord(set->fill_fork, s));
-            D2G_HIP(ctx, hipStreamWaitEvent(fs, set->fill_fork, 0));
-            const SpRider all{set->ride_out, set->ride_cnt, set->ride_vsrc, set->ride_vimm, 0u, 0u};
-            const unsigned fgrid = sp_side_fill_grid(ctx, set->ride_total, set->ride_cnt, N, S);
-            hipLaunchKernelGGL(sp_side_fill_kernel, dim3(fgrid), dim3(256), 0, fs, all, set->ride_total);
-            D2G_HIP(ctx, hipEventRecord(set->fill_join, fs));
-            set->ride_next = set->ride_total;                            // nothing left for the riders
-            side_fill = true;
+            hipStream_t fs = sp->fill_stream;
+            D2G_HIP(ctx, hipEventRecord(sp->fill_fork, s));
+            D2G_HIP(ctx, hipStreamWaitEvent(fs, sp->fill_fork, 0));
+            // from here on every return, failed or not, joins the fill back into `s`: the launch writes into the filled output, and after an
+            // error the caller must not find a fill still writing into its buffer, unordered with what it does next
+            join.ev = sp->fill_join;
+            const uint32_t pieces = sp->announced.riding();
+            const SpRider all = sp->announced.take_all();                // nothing left for the riders
+            const unsigned fgrid = sp_side_fill_grid(ctx, pieces, all.cnt, N, S);
+            hipLaunchKernelGGL(sp_side_fill_kernel, dim3(fgrid), dim3(256), 0, fs, all, pieces);
+            D2G_HIP(ctx, hipEventRecord(sp->fill_join, fs));
         }
     }
     // the status word meta[ntb] was zeroed by the transpose kernel that filled d_cols (no memset node in the chain)
+    const bool multi = set->logT > BS_LOG_TLDS_MAX;
+    const int nsplit = multi ? set->nsplit : 1;
     {
         const int logTl = set->logT < BS_LOG_TLDS_MAX ? set->logT : BS_LOG_TLDS_MAX;
         const size_t lds = (size_t(1) << logTl) * sizeof(uint32_t);
         void (*kern)(const uint64_t *, size_t, size_t, uint32_t, int, uint32_t *, uint32_t *, uint32_t *, int, uint32_t, int, uint32_t *, size_t) = bs_rank_kernel<false, false>;
-        const bool multi = set->logT > BS_LOG_TLDS_MAX;
         if (multi) kern = bs_rank_kernel<true, false>;
         else if (N <= (size_t)12 * BS_RANK_THREADS) kern = bs_rank_kernel<false, true>;     // PF * BS_RANK_THREADS
-        int tagbits_max = 31;
-        if (const char *e = ctx->tune.get("D2G_BS_TAGBITS")) { const int v = std::atoi(e); if (v >= 0 && v < 31) tagbits_max = v; }   // tests
         if (lds > 48 * 1024)
             D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int nsplit = multi ? set->nsplit : 1;
         // split passes tell their pending words from final ids by a tag and trust that ids[] holds nothing else that looks pending.  A
         // prepare that overflowed (status bit 0) may leave pending words behind, and the multi-GPU engine re-uses its exporter sets step
         // after step: ids[] starts from zero in every split prepare -- a few MB for the narrow column slices that are split
         if (nsplit > 1) D2G_HIP(ctx, hipMemsetAsync(set->d_ids, 0, S * Npad * sizeof(uint32_t), s));
         hipLaunchKernelGGL(kern, dim3((unsigned)(S * nsplit)), dim3(BS_RANK_THREADS), lds, s, set->d_cols, N, Npad, set->T, set->logT,
-                           set->d_ids, set->d_colcnt, set->d_meta + set->ntb, tagbits_max, (uint32_t)S, nsplit, nsplit == 1 ? set->d_owner : (uint32_t *)nullptr, set->owner_stride);
+                           set->d_ids, set->d_colcnt, set->d_meta + set->ntb, ctx->k2.tagbits_max, (uint32_t)S, nsplit,
+                           (sp && nsplit == 1) ? sp->d_owner.get() : (uint32_t *)nullptr, sp ? sp->owner_stride : 0);
         // a set's first prepare looks at its matrix before it orders it: the sample needs the ids only, so it stands HERE and the two kernels
         // below run while the host waits for its word (sp_sample_collect)
         if (sparse_path && sp_sample_due(ctx, set)) { if (int rc = sp_sample_enqueue(ctx, set, s)) return rc; }
-        unsigned g; const SpRider rd = sp_take_rider(set, 1, SP_RW_PLAN, false, &g, 1);
+        unsigned g = 1; const SpRider rd = sp ? sp->announced.take(1, SP_RW_PLAN, false, 1, &g) : SP_NO_RIDER;
         hipLaunchKernelGGL(bs_colplan_kernel, dim3(g), dim3(BS_PLAN_THREADS), 0, s, set->d_colcnt, (uint32_t)S, set->ntb, nsplit, set->d_perm,
-                           set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, sort_columns(ctx) ? 1 : 0, rd);
+                           set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, ctx->k2.sort ? 1 : 0, rd);
     }
-    dim3 grid((unsigned)div_up<size_t>(set->Nstride, 256), (unsigned)set->ntb);
-    const bool split = set->logT > BS_LOG_TLDS_MAX && set->nsplit > 1;
     if (sparse_path) {
         // sparse path (section 4): the caller's-order stream first (the dense walk and rectangular launches read it), then the families,
         // the pair list and the stream in family order
@@ -1014,38 +1017,28 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         // (a second queue for the caller's-order planes beside the ordering, and for the fill beside the tile list, was measured in round 4:
         // the kernels slow each other down by what the overlap hides and the events cost more: dropped)
         // (the planes kernel also initialises the ordering's arrays and clears the tile bitmap: no launch / memset of their own)
-        hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, set->d_ids, N, Npad,
-                           set->d_planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, BS_FORM_STREAM, set->d_perm, set->d_colcnt, (const uint32_t *)nullptr, sp_init_of(set));
+        if (int rc = launch_planes(ctx, set, set->d_planes, BS_FORM_STREAM, sp_init_of(set), s)) return rc;
         if (int rc = sp_sample_collect(ctx, set, s)) return rc;         // (the first look, enqueued behind the rank kernel: the host waits for its word here)
-        if (int rc = sp_prepare_order(ctx, set, split, s)) return rc;
+        if (int rc = sp_prepare_order(ctx, set, nsplit > 1, s)) return rc;
         if (int rc = sp_permute(ctx, set, s)) return rc;
-        if (side_fill) D2G_HIP(ctx, hipStreamWaitEvent(s, set->fill_join, 0));     // the launch writes into the filled output
         set->srt_valid = true; set->nat_valid = true;
-        if (set->ride_total) { set->prefilled = set->ride_out; set->prefilled_cnt = set->ride_cnt; set->prefilled_pieces = set->ride_next; set->prefilled_src = set->ride_vsrc; set->prefilled_by_riders = true; }   // (the launch fills what is left)
-        else if (set->prefilled_by_riders) set->prefilled = nullptr;        // what an EARLIER prepare's riders wrote is void once another prepare has run (the caller may have used the buffer in between)
-        set->ride_out = nullptr; set->ride_total = 0;                       // an announcement serves ONE prepare
+        if (sp->announced.riding()) sp->filled.set_by_riders(sp->announced);
+        else sp->filled.void_after_prepare();
+        sp->announced.served();
         D2G_HIP(ctx, hipGetLastError());
         return D2G_OK;
     }
-    set->ride_out = nullptr;
+    if (sp) sp->announced.served();
     const int forms = set->export_only ? BS_FORM_EXCHANGE : (BS_FORM_STREAM | (set->want_exchange ? BS_FORM_EXCHANGE : 0));
-    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, set->d_ids, N, Npad,
-                       set->export_only ? set->ex_planes : set->d_planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms,
-                       set->d_perm, set->d_colcnt, (const uint32_t *)nullptr, SpInit{});
+    if (int rc = launch_planes(ctx, set, set->export_only ? set->ex_planes : set->d_planes, forms, SpInit{}, s)) return rc;
     set->srt_valid = false; set->nat_valid = true;
-    D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
 }
 
 // the caller's-order stream of a set whose last prepare only wrote the sorted one (rectangular launches, exports)
-int d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *cset, hipStream_t s) {
-    d2g_cmp_set *set = const_cast<d2g_cmp_set *>(cset);
+int d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s) {
     if (set->nat_valid || set->borrowed || set->export_only) return D2G_OK;
-    dim3 grid((unsigned)div_up<size_t>(set->Nstride, 256), (unsigned)set->ntb);
-    const bool split = set->logT > BS_LOG_TLDS_MAX && set->nsplit > 1;
-    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, set->d_ids, set->N, set->Npad,
-                       set->d_planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, BS_FORM_STREAM, set->d_perm, set->d_colcnt, (const uint32_t *)nullptr, SpInit{});
-    D2G_HIP(ctx, hipGetLastError());
+    if (int rc = launch_planes(ctx, set, set->d_planes, BS_FORM_STREAM, SpInit{}, s)) return rc;
     set->nat_valid = true;
     return D2G_OK;
 }
@@ -1054,12 +1047,7 @@ int d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *cset, hipStream
 int d2g_bitslice_export(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     if (set->borrowed || set->want_exchange || set->export_only) return D2G_OK;
     set->want_exchange = true;
-    dim3 grid((unsigned)div_up<size_t>(set->Nstride, 256), (unsigned)set->ntb);
-    const bool split = set->logT > BS_LOG_TLDS_MAX && set->nsplit > 1;
-    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, set->d_ids, set->N, set->Npad,
-                       set->d_planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, BS_FORM_EXCHANGE, set->d_perm, set->d_colcnt, (const uint32_t *)nullptr, SpInit{});
-    D2G_HIP(ctx, hipGetLastError());
-    return D2G_OK;
+    return launch_planes(ctx, set, set->d_planes, BS_FORM_EXCHANGE, SpInit{}, s);
 }
 
 // ---- exporter sets: the multi-GPU engine's per-rank column slices (d2g_mgpu.hip)
@@ -1112,13 +1100,12 @@ int d2g_bitslice_status(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s) {
 
 int d2g_bitslice_ut(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, uint32_t *eq_out, const float *lut,
                     float *fout, hipStream_t s) {
-    PairShape sh{};
-    sh.N = set->N; sh.i_lo = r0; sh.i_hi = r1; sh.j_lo = r0 + 1 < set->N ? r0 + 1 : set->N; sh.j_hi = set->N; sh.ut = 1;
+    const PairShape sh = ut_shape(set->N, r0, r1);
     if (set->srt_valid) {
         if (eq_out) return launch_sparse(ctx, set, sh, StoreEq{eq_out}, eq_out, s);
         return launch_sparse(ctx, set, sh, StoreLut{fout, lut}, reinterpret_cast<uint32_t *>(fout), s);
     }
-    const_cast<d2g_cmp_set *>(set)->prefilled = nullptr;               // (an early fill is void once a launch has written every output itself)
+    if (set->sp) set->sp->filled.clear();                              // (an early fill is void once a launch has written every output itself)
     if (eq_out) return launch_bitslice(ctx, set, sh, StoreEq{eq_out}, s);
     return launch_bitslice(ctx, set, sh, StoreLut{fout, lut}, s);
 }
@@ -1130,28 +1117,24 @@ int d2g_bitslice_prefill(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1, u
 
 int d2g_bitslice_announce(d2g_ctx *, d2g_cmp_set *set, size_t r0, size_t r1, uint32_t *eq_out, const float *lut, float *fout) {
     const size_t cnt = d2g_ut_count(set->N, r0, r1);
-    set->ride_out = nullptr;
-    if (!eq_out && !fout) return D2G_OK;                               // the cancelling form: nothing rides on the next prepare
-    if (!cnt || !set->sparse_ok) return D2G_OK;
-    // the fill value = Store::value_from_mismatches(S, S): the count 0, or lut[0] (read by the riders when they run)
-    set->ride_out = eq_out ? eq_out : reinterpret_cast<uint32_t *>(fout);
-    set->ride_vsrc = eq_out ? nullptr : reinterpret_cast<const uint32_t *>(lut);
-    set->ride_vimm = 0;
-    set->ride_cnt = cnt;
+    if (!set->sp) return D2G_OK;
+    SpAnnounced &an = set->sp->announced;
+    an.cancel();
+    if (!cnt || (!eq_out && !fout)) return D2G_OK;                     // the cancelling form: nothing rides on the next prepare
+    if (eq_out) an.announce(eq_out, cnt, nullptr);
+    else an.announce(reinterpret_cast<uint32_t *>(fout), cnt, reinterpret_cast<const uint32_t *>(lut));
     return D2G_OK;
 }
 
 int d2g_bitslice_rect(d2g_ctx *ctx, const d2g_cmp_set *set, size_t a0, size_t a1, size_t b0, size_t b1, uint32_t *eq_out,
                       hipStream_t s) {
-    PairShape sh{};
-    sh.N = set->N; sh.i_lo = a0; sh.i_hi = a1; sh.j_lo = b0; sh.j_hi = b1; sh.ut = 0;
-    return launch_bitslice(ctx, set, sh, StoreEq{eq_out}, s);
+    return launch_bitslice(ctx, set, rect_shape(set->N, a0, a1, b0, b1), StoreEq{eq_out}, s);
 }
 
 // ---- sparse tiles on the multi-GPU engine's gathered operand (replicated: every rank orders and marks the whole operand itself --
 // the pair phase of a block-structured matrix shrinks by the fraction of tiles listed, the fixed costs stay per rank)
 int d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
-    if (!set->borrowed || set->sparse_ok) return D2G_OK;
+    if (!set->borrowed || set->sparse_ok()) return D2G_OK;
     set->ncols = (size_t)set->ntb * 32;
     if (!(sparse_enabled(ctx, set->N) && set->S < 65536)) return D2G_OK;
     const char *what = "bitslice sparse alloc";
@@ -1163,13 +1146,12 @@ int d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
         (void)hipGetLastError();
         return D2G_OK;
     }
-    if (sp_alloc(ctx, set) != D2G_OK) { sp_free(set); (void)hipGetLastError(); return D2G_OK; }
-    set->sparse_ok = true;
+    if (sp_alloc(ctx, set) != D2G_OK) (void)hipGetLastError();
     return D2G_OK;
 }
 
 int d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
-    if (!set->borrowed || !set->sparse_ok) return D2G_OK;
+    if (!set->borrowed || !set->sparse_ok()) return D2G_OK;
     dim3 grid((unsigned)div_up<size_t>(set->Npad, 256), (unsigned)set->ntb);
     hipLaunchKernelGGL(sp_unpack_kernel, grid, dim3(256), 0, s, set->d_planes, set->Nstride, set->nbits_cap, set->d_meta, set->N, set->Npad, set->d_ids, set->d_colcnt, sp_init_of(set));
     if (int rc = sp_prepare_order(ctx, set, false, s)) return rc;
@@ -1181,37 +1163,40 @@ int d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
 
 // the set's remembered decisions forgotten: its next prepare decides as a new set's first prepare does (measurements: bench.py's first_step_ms)
 void d2g_bitslice_forget(d2g_cmp_set *set) {
-    if (set->h_gaveup) { set->h_gaveup[0] = 0; set->h_gaveup[1] = 0; }
-    set->sp_prepares = 0; set->pred_valid = false;
+    if (!set->sp) return;
+    if (set->sp->h_gaveup) { set->sp->h_gaveup[SP_MW_GAVEUP] = 0; set->sp->h_gaveup[SP_MW_LIST_LEN] = 0; }
+    set->sp->dec.prepares = 0; set->sp->dec.pred_valid = false;
 }
 
 // diagnostics of the sparse path's LAST launch on this set (synchronises `s`): see d2g.h
 int d2g_bitslice_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint32_t *out4) {
     out4[0] = out4[1] = out4[2] = out4[3] = 0;
-    if (!set->srt_valid || !set->d_spctl) { D2G_HIP(ctx, hipStreamSynchronize(s)); return D2G_OK; }
+    if (!set->srt_valid || !set->sp) { D2G_HIP(ctx, hipStreamSynchronize(s)); return D2G_OK; }
+    const SpState &sp = *set->sp;
     uint32_t c[4] = {0, 0, 0, 0}, ord[4] = {0, 0, 0, 0}, pl = 0;
-    if (!set->last_ctl) { D2G_HIP(ctx, hipStreamSynchronize(s)); out4[0] = 1; return D2G_OK; }   // prepared, never launched
-    D2G_HIP(ctx, hipMemcpyAsync(c, set->last_ctl, sizeof c, hipMemcpyDeviceToHost, s));   // the control words the last launch used
-    D2G_HIP(ctx, hipMemcpyAsync(ord, set->d_order, sizeof ord, hipMemcpyDeviceToHost, s));
-    D2G_HIP(ctx, hipMemcpyAsync(&pl, set->d_plctl, sizeof pl, hipMemcpyDeviceToHost, s));
+    if (!sp.last_ctl) { D2G_HIP(ctx, hipStreamSynchronize(s)); out4[0] = 1; return D2G_OK; }   // prepared, never launched
+    D2G_HIP(ctx, hipMemcpyAsync(c, sp.last_ctl, sizeof c, hipMemcpyDeviceToHost, s));   // the control words the last launch used
+    D2G_HIP(ctx, hipMemcpyAsync(ord, sp.d_order, sizeof ord, hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipMemcpyAsync(&pl, sp.d_plctl, sizeof pl, hipMemcpyDeviceToHost, s));
     D2G_HIP(ctx, hipStreamSynchronize(s));
     const bool dense = (c[1] & 1u) || (size_t)c[0] * 5 > (size_t)c[3] * 2;
     // [2]: bit 0 the prepare decided for the dense walk, bit 1 the dense kernel ran, bit 2 tiles + pair list were used, bit 3 the caller's order was kept,
     //      bit 4 the last prepare skipped the ordering (the one before had given up: sp_prepare_order)
-    out4[0] = 1; out4[1] = c[0]; out4[2] = (ord[0] ? 1u : 0u) | (dense ? 2u : 4u) | (ord[0] ? 8u : 0u) | (set->sp_skipped ? 16u : 0u);
-    out4[3] = ord[0] ? 0u : (uint32_t)std::min<size_t>(pl, set->plist_cap);
+    out4[0] = 1; out4[1] = c[0]; out4[2] = (ord[0] ? 1u : 0u) | (dense ? 2u : 4u) | (ord[0] ? 8u : 0u) | (sp.dec.skipped ? 16u : 0u);
+    out4[3] = ord[0] ? 0u : (uint32_t)std::min<size_t>(pl, sp.plist_cap);
     return D2G_OK;
 }
 
 // diagnostics of the last prepare's first look and list form (synchronises `s`): see d2g.h
 int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out8) {
     uint32_t binned = 0;
-    if (set->d_plctl) D2G_HIP(ctx, hipMemcpyAsync(&binned, set->d_plctl + SP_PL_BINNED, 4, hipMemcpyDeviceToHost, s));   // (raised by sp_bin_kernel when the binned form ran)
+    if (set->sp) D2G_HIP(ctx, hipMemcpyAsync(&binned, set->sp->d_plctl + SP_PL_BINNED, 4, hipMemcpyDeviceToHost, s));   // (raised by sp_bin_kernel when the binned form ran)
     D2G_HIP(ctx, hipStreamSynchronize(s));
-    if (!set->sparse_ok) return D2G_OK;
-    out8[0] = set->looked ? 1 : 0; out8[1] = set->looked_dense ? 1 : 0;
-    if (set->looked) for (int x = 0; x < 4; ++x) out8[2 + x] = set->samp_sums[x];   // (a prepare that did not look reports no sums: those of an earlier look are not its own)
-    out8[6] = binned ? 1 : 0; out8[7] = set->bin_cshift;
+    if (!set->sp) return D2G_OK;
+    const SpState &sp = *set->sp;
+    out8[0] = sp.dec.looked ? 1 : 0; out8[1] = sp.dec.looked_dense ? 1 : 0;
+    if (sp.dec.looked) for (int x = 0; x < 4; ++x) out8[2 + x] = sp.dec.samp_sums[x];   // (a prepare that did not look reports no sums: those of an earlier look are not its own)
+    out8[6] = binned ? 1 : 0; out8[7] = sp.bin_cshift;
     return D2G_OK;
 }
 
@@ -1228,13 +1213,14 @@ int d2g_sparse_bin_geometry(size_t N, uint32_t *cshift, uint32_t *nch, uint32_t 
 // diagnostics: the pair list and the sorted order of the last prepare, copied to the host (synchronises `s`)
 int d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out /* [N] or null */) {
     *npairs = 0;
-    if (!set->srt_valid || !set->d_plctl) { D2G_HIP(ctx, hipStreamSynchronize(s)); return D2G_OK; }
+    if (!set->srt_valid || !set->sp) { D2G_HIP(ctx, hipStreamSynchronize(s)); return D2G_OK; }
+    const SpState &sp = *set->sp;
     uint32_t n = 0;
-    D2G_HIP(ctx, hipMemcpyAsync(&n, set->d_plctl, 4, hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipMemcpyAsync(&n, sp.d_plctl, 4, hipMemcpyDeviceToHost, s));
     D2G_HIP(ctx, hipStreamSynchronize(s));
-    const size_t m = std::min<size_t>(std::min<size_t>(n, set->plist_cap), cap);
-    if (m && pairs_out) D2G_HIP(ctx, hipMemcpy(pairs_out, set->d_plist, m * 8, hipMemcpyDeviceToHost));
-    if (root_out) D2G_HIP(ctx, hipMemcpy(root_out, set->d_label + set->Npad, set->N * 4, hipMemcpyDeviceToHost));
+    const size_t m = std::min<size_t>(std::min<size_t>(n, sp.plist_cap), cap);
+    if (m && pairs_out) D2G_HIP(ctx, hipMemcpy(pairs_out, sp.d_plist, m * 8, hipMemcpyDeviceToHost));
+    if (root_out) D2G_HIP(ctx, hipMemcpy(root_out, sp.d_label + set->Npad, set->N * 4, hipMemcpyDeviceToHost));
     *npairs = m;
     return D2G_OK;
 }
@@ -1242,23 +1228,20 @@ int d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s,
 // what the engines of one multi-GPU job must agree on: the RESOLVED values (a rank with D2G_SP_LINK=1 and one that leaves it unset resolve the
 // same kernels -- ADVICE r5: the textual form refused them as different)
 uint64_t d2g_k2_tuning_hash(const d2g_ctx *ctx) {
-    const SpTuning t = sp_tuning(ctx);
-    long long tag = -1, nsplit = 0;
-    if (const char *e = ctx->tune.get("D2G_BS_TAGBITS")) tag = std::atoi(e);
-    if (const char *e = ctx->tune.get("D2G_BS_NSPLIT")) nsplit = std::atoi(e);
+    const d2g_k2_tuning &t = ctx->k2;
     const long long v[] = {t.sparse, (long long)t.min_n, t.link, (long long)(t.tile_frac * 1e6), t.olink, t.emit_big, t.ride, t.remember, (long long)t.list_div, (long long)t.long_list,
-                           t.list_form, t.predict, sort_columns(ctx) ? 1 : 0, tag, nsplit};
+                           t.list_form, t.predict, t.sort ? 1 : 0, t.tagbits_max, t.nsplit_req};
     uint64_t h = 1469598103934665603ull;
     for (long long x : v) for (int b = 0; b < 8; ++b) { h ^= (uint64_t)(x >> (8 * b)) & 0xFF; h *= 1099511628211ull; }
     return h;
 }
 
 std::string d2g_k2_tuning_json(const d2g_ctx *ctx) {
-    const SpTuning t = sp_tuning(ctx);
+    const d2g_k2_tuning &t = ctx->k2;
     char b[640];
     std::snprintf(b, sizeof b, "{\"D2G_BS_SPARSE\": %d, \"D2G_BS_SPARSE_MIN_N\": %zu, \"D2G_BS_SORT\": %d, \"D2G_SP_LINK\": %d, \"D2G_SP_OLINK\": %d, \"D2G_SP_TILE_FRAC\": %.3f, "
                   "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d}",
-                  t.sparse ? 1 : 0, t.min_n, sort_columns(ctx) ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big);
+                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big);
     return b;
 }
 

@@ -17,6 +17,10 @@ struct PairShape {
     unsigned per_xcd;        // ceil(nvalid_total / 8)
 };
 
+// the two launch shapes (the tile grid is filled in by finish_shape): rows [r0, r1) of the upper triangle, and the rectangle [a0, a1) x [b0, b1)
+inline PairShape ut_shape(size_t N, size_t r0, size_t r1) { return PairShape{N, r0, r1, r0 + 1 < N ? r0 + 1 : N, N, 1}; }
+inline PairShape rect_shape(size_t N, size_t a0, size_t a1, size_t b0, size_t b1) { return PairShape{N, a0, a1, b0, b1, 0}; }
+
 // number of row tiles of column tile c (0-based within the launch) that hold a pair with j > i:
 // tile (rt, c) is wanted iff i_lo + rt*rb < 256*(ct0+c+1) - 1.  256 % rb == 0.
 __host__ __device__ __forceinline__ unsigned tiles_in_column(const PairShape &sh, unsigned c) {

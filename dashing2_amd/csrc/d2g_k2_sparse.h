@@ -994,7 +994,6 @@ __device__ __forceinline__ bool sp_dense_mode(const uint32_t *__restrict__ ctl, 
     return (ctl[1] & 1u) != 0 || (size_t)ctl[0] * 5 > (size_t)cand * 2;
 }
 
-constexpr int SP_FILL_PER_THREAD = 8, SP_FILL_THREADS = 256;
 template <class Store>
 __global__ __launch_bounds__(SP_FILL_THREADS) void sp_fill_kernel(uint32_t *__restrict__ out, size_t cnt, Store store, uint32_t S, const uint32_t *__restrict__ ctl, uint32_t cand, uint32_t piece0) {
     if (ctl && sp_dense_mode(ctl, cand)) return;                    // dense mode: the pair kernel writes every output (ctl == nullptr: an early fill, before the mode is known)
@@ -1371,117 +1370,72 @@ __global__ __launch_bounds__(64 * D2G_SP_KS) __attribute__((amdgpu_waves_per_eu(
 // ---- host side
 constexpr size_t SP_UNITE_STRIDE = 4;     // every 4th column pair takes part in the uniting pass (all of them: 18 -> 10 us at config 3, round 5)
 constexpr size_t SP_GRID_MULT = 4;        // workgroups of the sparse pair kernel, in units of what is resident at once (exactly one resident wave of them: 52 -> 85 us)
-struct SpTuning {
-    bool sparse = true;                 // D2G_BS_SPARSE: 0 = every launch walks every tile
-    size_t min_n = 8192;                // D2G_BS_SPARSE_MIN_N: below ~6000 sketches the extra launches cost more than the tiles they skip
-    int link = 1;                       // D2G_SP_LINK: 0 = no families (every sketch its own segment: the pair list alone; tests)
-    double tile_frac = 0.35;            // D2G_SP_TILE_FRAC: the segments may cover this fraction of all tiles before the dense walk is cheaper
-    int olink = 1;                      // D2G_SP_OLINK: 0 = the table form of the link passes even where the rank kernel left an owner per value (tests: the multi-GPU engine's form)
-    int emit_big = 0;                   // D2G_SP_EMIT_BIG: sp_emit_kernel counts with two words per value at every N (it does from N = 65 536 on; tests)
-    int ride = 63;                      // D2G_SP_RIDE: which kernels of the prepare carry an announced output's fill (d2g_cmp_ut_announce_dev) -- 1 column plan, 2 flatten, 4 count, 8 attach, 16 scan, 32 place; 0 = none, the launch fills (measurements)
-    int remember = 1;                   // D2G_SP_REMEMBER: 0 = every prepare runs the ordering, whatever the last one decided
-    size_t long_list = 786432;          // D2G_SP_LONG_LIST: a pair list of this many entries or more is binned and composed (the last prepare's length decides)
-    int predict = 1;                    // D2G_SP_PREDICT: 0 = no sample before the ordering of a set's first prepare (the ordering finds out by itself, as in round 5)
-    int list_form = 0;                  // D2G_SP_LIST_FORM: 1 = always entry by entry, 2 = always binned (tests, measurements)
-    size_t list_div = 8;                // D2G_SP_LIST_DIV: the pair list holds at most pairs / list_div entries (and at most 2^27)
-};
-SpTuning sp_tuning(const d2g_ctx *ctx) {
-    SpTuning v;
-    if (const char *e = ctx->tune.get("D2G_BS_SPARSE")) v.sparse = !(e[0] == '0');
-    if (const char *e = ctx->tune.get("D2G_BS_SPARSE_MIN_N")) v.min_n = (size_t)std::atoll(e);
-    if (const char *e = ctx->tune.get("D2G_SP_LINK")) v.link = std::atoi(e) != 0;
-    if (const char *e = ctx->tune.get("D2G_SP_TILE_FRAC")) { const double f = std::atof(e); if (f > 0 && f <= 1) v.tile_frac = f; }
-    if (const char *e = ctx->tune.get("D2G_SP_OLINK")) v.olink = std::atoi(e) != 0;
-    if (const char *e = ctx->tune.get("D2G_SP_EMIT_BIG")) v.emit_big = std::atoi(e) != 0;
-    if (const char *e = ctx->tune.get("D2G_SP_REMEMBER")) v.remember = std::atoi(e) != 0;
-    if (const char *e = ctx->tune.get("D2G_SP_RIDE")) v.ride = std::atoi(e) & 63;
-    if (const char *e = ctx->tune.get("D2G_SP_LONG_LIST")) { const long long d = std::atoll(e); if (d >= 0) v.long_list = (size_t)d; }
-    if (const char *e = ctx->tune.get("D2G_SP_PREDICT")) v.predict = std::atoi(e) != 0;
-    if (const char *e = ctx->tune.get("D2G_SP_LIST_FORM")) { const int d = std::atoi(e); if (d >= 0 && d <= 2) v.list_form = d; }
-    if (const char *e = ctx->tune.get("D2G_SP_LIST_DIV")) { const long d = std::atol(e); if (d >= 1 && d <= (1 << 20)) v.list_div = (size_t)d; }
-    return v;
-}
+bool sparse_enabled(const d2g_ctx *ctx, size_t N) { return ctx->k2.sparse && N >= 2 && N >= ctx->k2.min_n; }
 
-bool sparse_enabled(const d2g_ctx *ctx, size_t N) { const SpTuning t = sp_tuning(ctx); return t.sparse && N >= 2 && N >= t.min_n; }
-
-size_t sp_list_cap(const d2g_ctx *ctx, size_t N) {
-    const size_t pairs = N * (N - 1) / 2;
-    return std::max<size_t>(std::min<size_t>(pairs / sp_tuning(ctx).list_div, (size_t)1 << 27), 1024);
-}
-
+// builds the state aside and moves it into the set only when every buffer is there: a failure half-way gives everything back at once and the
+// set goes on without one (the dense walk)
 int sp_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
     const size_t Npad = set->Npad, Nstride = set->Nstride;
+    SpState sp;
     const size_t nrb = Npad / 32, ncb = Npad / BS_CB;
-    set->tilebm_words = nrb * ((ncb + 31) / 32) + 1;
-    set->tiles_cap = nrb * ((ncb + 7) / 8) * SP_SUBS;                        // per list: the sub-tiles of the tiles of every eighth column block
-    set->plist_cap = sp_list_cap(ctx, set->N);
+    sp.tilebm_words = nrb * ((ncb + 31) / 32) + 1;
+    sp.tiles_cap = nrb * ((ncb + 7) / 8) * SP_SUBS;                        // per list: the sub-tiles of the tiles of every eighth column block
+    sp.plist_cap = std::max<size_t>(std::min<size_t>(set->N * (set->N - 1) / 2 / ctx->k2.list_div, (size_t)1 << 27), 1024);   // pairs / D2G_SP_LIST_DIV entries, 2^27 at most
     // holders of mixed values: h holders make h - 1 pairs at least -- and a column has N holders at most; a record per mixed value: a pair at least each, N / 2 values per column at most
-    set->cw_ecap = std::min<size_t>(std::min<size_t>(2 * set->plist_cap, set->ncols * set->N), 0xFFFFFFF0u);
-    set->cw_vcap = std::min<size_t>(set->plist_cap, set->ncols * (set->N / 2 + 1));
+    sp.cw_ecap = std::min<size_t>(std::min<size_t>(2 * sp.plist_cap, set->ncols * set->N), 0xFFFFFFF0u);
+    sp.cw_vcap = std::min<size_t>(sp.plist_cap, set->ncols * (set->N / 2 + 1));
     // output bins of the pair list (sp_bin_geometry)
     const SpBinGeom bg = sp_bin_geometry(set->N);
-    set->bin_cshift = bg.cshift; set->bin_nch = bg.nch; set->nbins = bg.nbins; set->bin_ok = bg.ok;
+    sp.bin_cshift = bg.cshift; sp.bin_nch = bg.nch; sp.nbins = bg.nbins; sp.bin_ok = bg.ok;
     // one zero-initialised block per prepare: [counters Npad + 1 | 8 global control words + tile bitmap | order 8 | list control 8 | control words of a whole-triangle launch 16 | entries per bin | bin cursors]
-    set->spz_words = (Npad + 1) + (8 + set->tilebm_words) + 8 + 12 + SP_CTL_WORDS + (size_t)set->nbins;
+    sp.spz_words = (Npad + 1) + (8 + sp.tilebm_words) + 8 + 12 + SP_CTL_WORDS + (size_t)sp.nbins;
     // the workgroups that count (and then move) the list's entries: one per ~16 384 entries of a full list, at most two per CU
-    set->bin_nwg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)std::max(ctx->num_cus / 2, 1), div_up<size_t>(set->plist_cap, 16384)));   // (128 of them measured best at config 3: 64 / 128 / 512 / 1024 -> counting + moving 90 / 65 / 70 / 84 us)
+    sp.bin_nwg = (uint32_t)std::max<size_t>(1, std::min<size_t>((size_t)std::max(ctx->num_cus / 2, 1), div_up<size_t>(sp.plist_cap, 16384)));   // (128 of them measured best at config 3: 64 / 128 / 512 / 1024 -> counting + moving 90 / 65 / 70 / 84 us)
     const size_t planes_words = (size_t)set->ntb * set->nbits_cap + 1;
     const char *what = "bitslice sparse alloc";
     int rc;
-    if ((rc = set->d_stream_s.alloc(ctx, planes_words * 2 * Nstride, what)) ||
-        (rc = set->d_rowstream.alloc(ctx, planes_words * Nstride, what)) ||
-        (rc = set->d_sperm.alloc(ctx, Nstride, what)) ||
-        (rc = set->d_sinv.alloc(ctx, Npad, what)) ||
-        (rc = set->d_label.alloc(ctx, 2 * Npad, what)) ||
-        (rc = set->d_hint.alloc(ctx, 2 * Npad, what)) ||
-        (rc = set->d_segend.alloc(ctx, Npad, what)) ||
-        (rc = set->d_posseg.alloc(ctx, Npad * 2, what)) ||
-        (rc = set->d_spz.alloc(ctx, set->spz_words, what)) ||
-        (rc = set->d_rowpos.alloc(ctx, Nstride, what)) ||
-        (rc = set->d_rowk.alloc(ctx, Npad, what)) ||
-        (rc = set->d_spctl.alloc(ctx, 2 * SP_CTL_WORDS + set->tilebm_words, what)) ||
-        (rc = set->d_tiles.alloc(ctx, 8 * std::max<size_t>(set->tiles_cap, 1), what)) ||
-        (rc = set->d_tiles_full.alloc(ctx, 8 * std::max<size_t>(set->tiles_cap, 1), what)) ||
-        (rc = set->d_plist.alloc(ctx, set->plist_cap, what)) ||
-        (rc = set->d_plist2.alloc(ctx, set->plist_cap, what)) ||
-        (rc = set->d_bstart.alloc(ctx, (size_t)set->nbins + 1, what)) ||
-        (rc = set->d_samp.alloc(ctx, SP_SAMPLE_ROWS * Npad + 8, what)) ||
-        (rc = d2g_hip_status(ctx, hipMemset(set->d_samp, 0, (SP_SAMPLE_ROWS * Npad + 8) * 4), what)) ||
-        (rc = set->d_cw_ents.alloc(ctx, set->cw_ecap, what)) ||
-        (rc = set->d_cw_vals.alloc(ctx, set->cw_vcap * 2, what)) ||                      // (a record per value: 16 bytes)
-        (rc = set->d_hoff.alloc(ctx, std::max<size_t>((size_t)set->bin_nwg * set->nbins, 1), what))) return rc;
-    set->d_lcnt = set->d_spz;
-    set->d_gbm = set->d_lcnt + (Npad + 1);
-    set->d_order = set->d_gbm + 8 + set->tilebm_words;
-    set->d_plctl = set->d_order + 8;
-    set->d_fullctl = set->d_plctl + 12;
-    set->d_binc = set->d_fullctl + SP_CTL_WORDS;
-    set->d_tilebm = set->d_spctl + 2 * SP_CTL_WORDS;
-    if ((rc = d2g_hip_status(ctx, hipMemset(set->d_spctl, 0, 2 * SP_CTL_WORDS * 4), what))) return rc;
-    // one word of host memory the device can write: the remembered give-up (sp_prepare_order)
-    if (set->h_gaveup.alloc(ctx, 16, what, hipHostMallocMapped) == D2G_OK && hipHostGetDevicePointer((void **)&set->d_gaveup, set->h_gaveup, 0) == hipSuccess) std::memset(set->h_gaveup, 0, 64);   // (all 16 words: the first look's ticket word must not hold what an earlier owner of the page left)
-    else { (void)hipGetLastError(); set->h_gaveup.reset(); set->d_gaveup = set->d_order + 7; }   // (no mapped host memory: a spare device word, never read by the host)
-    set->sp_launch = 0;
-    return D2G_OK;
-}
-
-// sp_alloc failed half-way: the set goes on with the dense walk, and the sparse path's buffers go back now (not when the set is destroyed)
-void sp_free(d2g_cmp_set *set) {
-    for (d2g_dev<uint32_t> *p : {&set->d_stream_s, &set->d_sperm, &set->d_sinv, &set->d_label, &set->d_hint, &set->d_segend, &set->d_posseg, &set->d_spz, &set->d_rowpos, &set->d_rowk,
-                                 &set->d_rowstream, &set->d_tiles, &set->d_tiles_full, &set->d_spctl, &set->d_bstart, &set->d_hoff, &set->d_samp, &set->d_cw_ents}) p->reset();
-    set->d_plist.reset(); set->d_plist2.reset(); set->d_cw_vals.reset(); set->h_gaveup.reset();
-    set->fill_stream.reset(); set->fill_fork.reset(); set->fill_join.reset(); set->samp_stream.reset(); set->samp_event.reset();
-    set->d_gaveup = set->d_binc = set->d_tilebm = set->d_lcnt = set->d_gbm = set->d_order = set->d_plctl = set->d_fullctl = nullptr;
+    if ((rc = sp.d_stream_s.alloc(ctx, planes_words * 2 * Nstride, what)) ||
+        (rc = sp.d_rowstream.alloc(ctx, planes_words * Nstride, what)) ||
+        (rc = sp.d_sperm.alloc(ctx, Nstride, what)) ||
+        (rc = sp.d_sinv.alloc(ctx, Npad, what)) ||
+        (rc = sp.d_label.alloc(ctx, 2 * Npad, what)) ||
+        (rc = sp.d_hint.alloc(ctx, 2 * Npad, what)) ||
+        (rc = sp.d_segend.alloc(ctx, Npad, what)) ||
+        (rc = sp.d_posseg.alloc(ctx, Npad * 2, what)) ||
+        (rc = sp.d_spz.alloc(ctx, sp.spz_words, what)) ||
+        (rc = sp.d_rowpos.alloc(ctx, Nstride, what)) ||
+        (rc = sp.d_rowk.alloc(ctx, Npad, what)) ||
+        (rc = sp.d_spctl.alloc(ctx, 2 * SP_CTL_WORDS + sp.tilebm_words, what)) ||
+        (rc = sp.d_tiles.alloc(ctx, 8 * std::max<size_t>(sp.tiles_cap, 1), what)) ||
+        (rc = sp.d_tiles_full.alloc(ctx, 8 * std::max<size_t>(sp.tiles_cap, 1), what)) ||
+        (rc = sp.d_plist.alloc(ctx, sp.plist_cap, what)) ||
+        (rc = sp.d_plist2.alloc(ctx, sp.plist_cap, what)) ||
+        (rc = sp.d_bstart.alloc(ctx, (size_t)sp.nbins + 1, what)) ||
+        (rc = sp.d_samp.alloc(ctx, SP_SAMPLE_ROWS * Npad + 8, what)) ||
+        (rc = d2g_hip_status(ctx, hipMemset(sp.d_samp, 0, (SP_SAMPLE_ROWS * Npad + 8) * 4), what)) ||
+        (rc = sp.d_cw_ents.alloc(ctx, sp.cw_ecap, what)) ||
+        (rc = sp.d_cw_vals.alloc(ctx, sp.cw_vcap * 2, what)) ||                      // (a record per value: 16 bytes)
+        (rc = sp.d_hoff.alloc(ctx, std::max<size_t>((size_t)sp.bin_nwg * sp.nbins, 1), what))) return rc;
+    sp.d_lcnt = sp.d_spz;
+    sp.d_gbm = sp.d_lcnt + (Npad + 1);
+    sp.d_order = sp.d_gbm + 8 + sp.tilebm_words;
+    sp.d_plctl = sp.d_order + 8;
+    sp.d_fullctl = sp.d_plctl + 12;
+    sp.d_binc = sp.d_fullctl + SP_CTL_WORDS;
+    sp.d_tilebm = sp.d_spctl + 2 * SP_CTL_WORDS;
+    if ((rc = d2g_hip_status(ctx, hipMemset(sp.d_spctl, 0, 2 * SP_CTL_WORDS * 4), what))) return rc;
+    // host memory the device can write (SpMappedWord): the remembered give-up (sp_prepare_order), the list length, the first look
+    if (sp.h_gaveup.alloc(ctx, SP_MW_WORDS, what, hipHostMallocMapped) == D2G_OK && hipHostGetDevicePointer((void **)&sp.d_gaveup, sp.h_gaveup, 0) == hipSuccess) std::memset(sp.h_gaveup, 0, SP_MW_WORDS * 4);   // (every word: the first look's ticket word must not hold what an earlier owner of the page left)
+    else { (void)hipGetLastError(); sp.h_gaveup.reset(); sp.d_gaveup = sp.d_order + 7; }   // (no mapped host memory: a spare device word, never read by the host)
+    set->sp.reset(new (std::nothrow) SpState(std::move(sp)));
+    return set->sp ? D2G_OK : D2G_ERR_NOMEM;
 }
 
 // what the kernel in front of sp_prepare_order initialises for it: label[j] = j, the hints, and the zero block (counters,
 // tile bitmap + global control words, order words, list cursor)
 SpInit sp_init_of(const d2g_cmp_set *set) {
-    SpInit si;
-    si.label = set->d_label; si.n = (uint32_t)set->N;
-    si.ones = set->d_hint; si.owords = (uint32_t)(2 * set->Npad);
-    si.zero = set->d_spz; si.zwords = (uint32_t)set->spz_words;
-    return si;
+    const SpState &sp = *set->sp;
+    return SpInit{sp.d_label, sp.d_hint, sp.d_spz, (uint32_t)set->N, (uint32_t)(2 * set->Npad), (uint32_t)sp.spz_words};
 }
 
 // candidate tiles of a whole-triangle launch: the tiles on or above the diagonal of sorted positions
@@ -1584,58 +1538,42 @@ __global__ __launch_bounds__(256) void sp_sample_fin_kernel(uint32_t *__restrict
             acc3[2] = 0;
             // the host waits for THIS word (sp_sample_collect polls it: the kernels enqueued behind this one keep the device busy meanwhile)
             __threadfence_system();
-            __hip_atomic_store(&host_out[4], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(&host_out[SP_MW_TICKET - SP_MW_SUMS], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
 }
 
-// ---- riders (sp_ride): the share of an announced output's fill that one hosting kernel of the prepare chain carries.  The weights are the
-// hosts' own durations at config 3 (us): each hides about what it lasts; the last host (place) takes what is left.
-constexpr unsigned SP_RW_PLAN = 6, SP_RW_FLATTEN = 5, SP_RW_COUNT = 5, SP_RW_ATTACH = 5, SP_RW_SCAN = 8, SP_RW_ALL = 35;
-inline size_t sp_fill_pieces(size_t cnt) { return div_up<size_t>(cnt / 4 + 1, (size_t)SP_FILL_THREADS * SP_FILL_PER_THREAD); }
-SpRider sp_take_rider(d2g_cmp_set *set, unsigned own, unsigned weight, bool last, unsigned *grid, int bit) {
-    *grid = own;
-    if (set->ride_next >= set->ride_total || !(set->ride_mask & bit)) return SP_NO_RIDER;
-    const uint32_t left = set->ride_total - set->ride_next;
-    uint32_t n = last ? left : (uint32_t)std::min<uint64_t>(left, ((uint64_t)set->ride_total * weight + SP_RW_ALL - 1) / SP_RW_ALL);
-    n = std::min<uint32_t>(n, 0x7FFFFFFFu - own);
-    const SpRider r{set->ride_out, set->ride_cnt, set->ride_vsrc, set->ride_vimm, own, set->ride_next};
-    set->ride_next += n;
-    *grid = own + n;
-    return r;
+SpColWork sp_colwork_of(const SpState &sp) {
+    return SpColWork{sp.d_cw_ents, reinterpret_cast<uint4 *>(sp.d_cw_vals.get()), (uint32_t)std::min<size_t>(sp.cw_ecap, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(sp.cw_vcap, 0xFFFFFFFFu)};
 }
-SpColWork sp_colwork_of(const d2g_cmp_set *set) {
-    return SpColWork{set->d_cw_ents, reinterpret_cast<uint4 *>(set->d_cw_vals.get()), (uint32_t)std::min<size_t>(set->cw_ecap, 0xFFFFFFFFu), (uint32_t)std::min<size_t>(set->cw_vcap, 0xFFFFFFFFu)};
-}
-SpPairs sp_pairs_of(const d2g_cmp_set *set, const SpColWork &cw, const uint32_t *seg) {
-    return SpPairs{cw, seg, set->d_plctl, set->d_plist, (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu), set->d_order, set->d_gaveup, set->d_fullctl};
+SpPairs sp_pairs_of(const SpState &sp, const SpColWork &cw, const uint32_t *seg) {
+    return SpPairs{cw, seg, sp.d_plctl, sp.d_plist, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), sp.d_order, sp.d_gaveup, sp.d_fullctl};
 }
 // long list or short list?  What the set's LAST prepare left (its length, written to mapped host memory by the permute launch) decides which form
 // THIS prepare enqueues: the binned one (pairs kernel, counting workgroups, sp_bin_kernel; the launches compose) from `long_list` entries on, the
 // entry-by-entry one (nothing enqueued for it) below.  A set without history takes the binned form.  Read without synchronisation, like the
 // remembered give-up: a prepare still in flight has not written yet and the one before it decides.  Both forms are exact for any list.
-bool sp_expect_long_list(const d2g_ctx *ctx, const d2g_cmp_set *set) {
-    const SpTuning t = sp_tuning(ctx);
-    if (!set->bin_ok) return false;                                    // (more than SP_BIN_MAX bands: no bins)
-    if (t.list_form == 1) return false;
-    if (t.list_form == 2) return true;
-    if (set->pred_valid) return set->pred_entries >= (double)t.long_list;
-    if (!set->h_gaveup || set->sp_prepares == 0) return true;
-    const uint32_t n = ((volatile uint32_t *)set->h_gaveup)[1];
-    return n != 0xFFFFFFFFu && n >= t.long_list;
+bool sp_expect_long_list(const d2g_ctx *ctx, const SpState &sp) {
+    if (!sp.bin_ok) return false;                                    // (more than SP_BIN_MAX bands: no bins)
+    if (ctx->k2.list_form == 1) return false;
+    if (ctx->k2.list_form == 2) return true;
+    if (sp.dec.pred_valid) return sp.dec.pred_entries >= (double)ctx->k2.long_list;
+    if (!sp.h_gaveup || sp.dec.prepares == 0) return true;
+    const uint32_t n = ((volatile uint32_t *)sp.h_gaveup.get())[SP_MW_LIST_LEN];
+    return n != 0xFFFFFFFFu && n >= ctx->k2.long_list;
 }
 // will the next sp_prepare_order skip the ordering (the remembered give-up)?  Asked BEFORE it, by the prepare that decides whether anything rides
-bool sp_retry_due(const d2g_cmp_set *set) { return ((set->sp_prepares + 1) & 15u) == 0; }
-bool sp_will_skip(const d2g_ctx *ctx, const d2g_cmp_set *set) {
-    if (set->pred_valid) return set->pred_dense;                       // this prepare has looked at its matrix (sp_sample)
-    return sp_tuning(ctx).remember && set->h_gaveup && *(volatile uint32_t *)set->h_gaveup && !sp_retry_due(set);
+bool sp_retry_due(const SpState &sp) { return ((sp.dec.prepares + 1) & 15u) == 0; }
+bool sp_will_skip(const d2g_ctx *ctx, const SpState &sp) {
+    if (sp.dec.pred_valid) return sp.dec.pred_dense;                       // this prepare has looked at its matrix (sp_sample)
+    return ctx->k2.remember && sp.h_gaveup && ((volatile uint32_t *)sp.h_gaveup.get())[SP_MW_GAVEUP] && !sp_retry_due(sp);
 }
 // does this prepare look at its matrix first?  The set's first prepare, and the retry of a remembered give-up
 bool sp_sample_due(const d2g_ctx *ctx, const d2g_cmp_set *set) {
-    const SpTuning t = sp_tuning(ctx);
-    if (!t.predict || !set->d_samp || set->borrowed || set->nsplit > 1) return false;    // (a column several rank workgroups share has no single count of its shared values)
-    if (set->sp_prepares == 0) return true;
-    return t.remember && set->h_gaveup && *(volatile uint32_t *)set->h_gaveup && sp_retry_due(set);
+    const SpState &sp = *set->sp;
+    if (!ctx->k2.predict || !sp.d_samp || set->borrowed || set->nsplit > 1) return false;    // (a column several rank workgroups share has no single count of its shared values)
+    if (sp.dec.prepares == 0) return true;
+    return ctx->k2.remember && sp.h_gaveup && ((volatile uint32_t *)sp.h_gaveup.get())[SP_MW_GAVEUP] && sp_retry_due(sp);
 }
 
 // the sample (see sp_sample_kernel): SYNCHRONISES `s`.  Leaves the set's prediction (pred_valid, pred_dense, pred_entries) and the remembered word.
@@ -1644,38 +1582,40 @@ bool sp_sample_due(const d2g_ctx *ctx, const d2g_cmp_set *set) {
 // synchronisation itself and the launches behind it, which no longer run ahead of the device.)
 int sp_sample_enqueue(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     const size_t N = set->N, Npad = set->Npad;
-    if (!set->h_gaveup) return D2G_OK;                                   // (no mapped host memory: no sample)
+    SpState &sp = *set->sp;
+    if (!sp.h_gaveup) return D2G_OK;                                   // (no mapped host memory: no sample)
     { hipStreamCaptureStatus cs = hipStreamCaptureStatusNone; if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) { (void)hipGetLastError(); return D2G_OK; } }   // (a captured prepare cannot wait for the host)
     SpSampleRows rows;
     for (uint32_t k = 0; k < SP_SAMPLE_ROWS; ++k) rows.r[k] = (uint32_t)std::min<size_t>(N - 1, (size_t)(2 * k + 1) * N / (2 * SP_SAMPLE_ROWS));
-    uint32_t *acc3 = set->d_samp + SP_SAMPLE_ROWS * Npad;                // (the counters and the control words are zero: cleared at allocation, then by the kernel itself)
+    uint32_t *acc3 = sp.d_samp + SP_SAMPLE_ROWS * Npad;                // (the counters and the control words are zero: cleared at allocation, then by the kernel itself)
 #ifndef D2G_SP_SAMPLE_INLINE
     // on a stream of their own, behind the rank kernel: the column plan (ONE workgroup) and the planes kernel run beside them.  No join: the host
     // waits for the sample's word before it enqueues anything else, and nothing the two kernels read is written before the set's next prepare.
-    if (!set->samp_stream) {
-        if (set->samp_stream.create(hipStreamNonBlocking) != hipSuccess || set->samp_event.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); set->samp_stream.reset(); set->samp_event.reset(); }
+    if (!sp.samp_stream) {
+        if (sp.samp_stream.create(hipStreamNonBlocking) != hipSuccess || sp.samp_event.create(hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); sp.samp_stream.reset(); sp.samp_event.reset(); }
     }
-    if (set->samp_stream) {
-        D2G_HIP(ctx, hipEventRecord(set->samp_event, s));
-        D2G_HIP(ctx, hipStreamWaitEvent(set->samp_stream, set->samp_event, 0));
-        s = set->samp_stream;
+    if (sp.samp_stream) {
+        D2G_HIP(ctx, hipEventRecord(sp.samp_event, s));
+        D2G_HIP(ctx, hipStreamWaitEvent(sp.samp_stream, sp.samp_event, 0));
+        s = sp.samp_stream;
     }
 #endif
     const bool wide = sp_sample_field_bits(set->ncols) == 16;           // (d_samp holds SP_SAMPLE_ROWS words per sketch: 16-bit fields fill all of them)
     const dim3 sgrid((unsigned)div_up<size_t>(N, 256), (unsigned)div_up<size_t>(set->ncols, SP_SAMPLE_COLS)), fgrid((unsigned)div_up<size_t>(std::max(N, set->ncols), 256));
-    hipLaunchKernelGGL(wide ? sp_sample_kernel<16> : sp_sample_kernel<8>, sgrid, dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)set->ncols, rows, set->d_samp);
-    hipLaunchKernelGGL(wide ? sp_sample_fin_kernel<16> : sp_sample_fin_kernel<8>, fgrid, dim3(256), 0, s, set->d_samp, N, Npad, rows, acc3, set->d_gaveup + 2,
-                       set->d_colcnt, (uint32_t)set->ncols, set->nsplit, ++set->sample_ticket);
+    hipLaunchKernelGGL(wide ? sp_sample_kernel<16> : sp_sample_kernel<8>, sgrid, dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)set->ncols, rows, sp.d_samp);
+    hipLaunchKernelGGL(wide ? sp_sample_fin_kernel<16> : sp_sample_fin_kernel<8>, fgrid, dim3(256), 0, s, sp.d_samp, N, Npad, rows, acc3, sp.d_gaveup + SP_MW_SUMS,
+                       set->d_colcnt, (uint32_t)set->ncols, set->nsplit, ++sp.dec.sample_ticket);
     D2G_HIP(ctx, hipGetLastError());
-    set->sample_pending = true;
+    sp.dec.sample_pending = true;
     return D2G_OK;
 }
 // SYNCHRONISES `s`.  Leaves the set's prediction (pred_valid, pred_dense, pred_entries) and the remembered word.
 int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
-    if (!set->sample_pending) return D2G_OK;
-    set->sample_pending = false;
+    SpState &sp = *set->sp;
+    if (!sp.dec.sample_pending) return D2G_OK;
+    sp.dec.sample_pending = false;
     const size_t N = set->N;
-    volatile uint32_t *h = (volatile uint32_t *)set->h_gaveup;
+    volatile uint32_t *h = (volatile uint32_t *)sp.h_gaveup.get() + SP_MW_SUMS;   // E, F, shared values, planes
     // The two kernels stand right behind the rank kernel; the column plan and the planes kernel are enqueued behind them and run while the host
     // waits for the sample's word and enqueues what it decides -- the device does not idle over the decision.  Polling the mapped word costs a
     // few microseconds; hipStreamSynchronize would also wait for the kernels behind (and took ~50 us to return and refill the queue at
@@ -1683,26 +1623,26 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     {
         const auto t0 = std::chrono::steady_clock::now();
         uint32_t spins = 0;
-        while (__atomic_load_n(&set->h_gaveup[6], __ATOMIC_ACQUIRE) != set->sample_ticket) {
+        while (__atomic_load_n(&sp.h_gaveup[SP_MW_TICKET], __ATOMIC_ACQUIRE) != sp.dec.sample_ticket) {
             __builtin_ia32_pause();
-            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(250)) { D2G_HIP(ctx, hipStreamSynchronize(set->samp_stream ? set->samp_stream : s)); break; }
+            if ((++spins & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(250)) { D2G_HIP(ctx, hipStreamSynchronize(sp.samp_stream ? sp.samp_stream : s)); break; }
         }
     }
     const double scale = (double)N / (2.0 * SP_SAMPLE_ROWS), pairs = (double)N * (double)(N - 1) / 2.0;
-    set->pred_valid = true;
-    for (int x = 0; x < 4; ++x) set->samp_sums[x] = h[2 + x];            // (diagnostics: d2g_cmp_set_sparse_detail)
-    set->pred_entries = (double)h[2] * scale;
-    set->pred_family_pairs = (double)h[3] * scale;
-    const double values = (double)h[4], planes = set->ncols ? (double)h[5] / (double)set->ncols : 1.0;
+    sp.dec.pred_valid = true;
+    for (int x = 0; x < 4; ++x) sp.dec.samp_sums[x] = h[x];            // (diagnostics: d2g_cmp_set_sparse_detail)
+    sp.dec.pred_entries = (double)h[0] * scale;
+    sp.dec.pred_family_pairs = (double)h[1] * scale;
+    const double values = (double)h[2], planes = set->ncols ? (double)h[3] / (double)set->ncols : 1.0;
     // what each path would take BEYOND the prepare both share, in nanoseconds (constants measured at config 3 on MI355X, round 6: profiles/r06_k2_experiments.txt):
     // the dense walk costs 2 + 0.94 x planes ps per pair (426 us at 7 planes); the sparse path a chain of ordering kernels and the fill (66 us on a matrix
     // that shares nothing: 6.6 ns per sketch), 55 ps per list entry (pairs, counting, moving, composing), 77 ps per shared value (grouping its holders, its
     // record) and 9 x the dense rate per family pair (their tiles in the latency-bound sparse pair kernel, their holders in the link and emit passes:
     // ~100 us for 7.4e5 family pairs).  (the per-plane and per-sketch terms are those of 32 register groups, S = 1024: they go with the group count)
     const double g = (double)set->ntb / 32.0, per_pair = 0.002 + 0.00094 * planes * g;
-    const double dense_ns = pairs * per_pair, sparse_ns = (3.0 + 3.6 * g) * (double)N + 0.055 * set->pred_entries + 0.077 * values + 9.0 * per_pair * set->pred_family_pairs;
-    set->pred_dense = set->pred_entries > (double)set->plist_cap || sparse_ns > 0.97 * dense_ns;
-    set->h_gaveup[0] = set->pred_dense ? 1u : 0u;                      // what the next prepares go by (the device kernels that give up write the same word)
+    const double dense_ns = pairs * per_pair, sparse_ns = (3.0 + 3.6 * g) * (double)N + 0.055 * sp.dec.pred_entries + 0.077 * values + 9.0 * per_pair * sp.dec.pred_family_pairs;
+    sp.dec.pred_dense = sp.dec.pred_entries > (double)sp.plist_cap || sparse_ns > 0.97 * dense_ns;
+    sp.h_gaveup[SP_MW_GAVEUP] = sp.dec.pred_dense ? 1u : 0u;                      // what the next prepares go by (the device kernels that give up write the same word)
     return D2G_OK;
 }
 
@@ -1714,76 +1654,78 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
 // dense walk is always right.
 int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) {
     const size_t N = set->N, Npad = set->Npad, S = set->ncols;
+    SpState &sp = *set->sp;
     // (a prepare that has handed out riders on a REMEMBERED give-up goes through: its place kernel carries the rest of the fill; one that has just
     // looked at its matrix and found it dense skips -- the dense launch writes every output itself)
-    const bool remembered = set->skip_cached >= 0 ? set->skip_cached == 1 : sp_will_skip(ctx, set);      // (d2g_bitslice_prepare read the word already)
-    set->skip_cached = -1;
-    const bool skip = set->pred_valid ? set->pred_dense : (remembered && set->ride_total == 0);
-    set->sp_big = sp_expect_long_list(ctx, set);
-    ++set->sp_prepares;
-    set->looked = set->pred_valid; set->looked_dense = set->pred_valid && set->pred_dense;   // (diagnostics: d2g_cmp_set_sparse_detail)
-    set->pred_valid = false;                                           // (a prediction serves the prepare that made it)
+    const bool remembered = sp.dec.skip_cached >= 0 ? sp.dec.skip_cached == 1 : sp_will_skip(ctx, sp);      // (d2g_bitslice_prepare read the word already)
+    sp.dec.skip_cached = -1;
+    const bool skip = sp.dec.pred_valid ? sp.dec.pred_dense : (remembered && sp.announced.riding() == 0);
+    sp.dec.big = sp_expect_long_list(ctx, sp);
+    ++sp.dec.prepares;
+    sp.dec.looked = sp.dec.pred_valid; sp.dec.looked_dense = sp.dec.pred_valid && sp.dec.pred_dense;   // (diagnostics: d2g_cmp_set_sparse_detail)
+    sp.dec.pred_valid = false;                                           // (a prediction serves the prepare that made it)
     if (skip) {
-        hipLaunchKernelGGL(sp_giveup_kernel, dim3(1), dim3(64), 0, s, set->d_order, set->d_fullctl, (uint32_t)std::min<size_t>(sp_full_candidates(Npad), 0xFFFFFFFFu));
+        hipLaunchKernelGGL(sp_giveup_kernel, dim3(1), dim3(64), 0, s, sp.d_order, sp.d_fullctl, (uint32_t)std::min<size_t>(sp_full_candidates(Npad), 0xFFFFFFFFu));
         D2G_HIP(ctx, hipGetLastError());
-        set->sp_skipped = true;
+        sp.dec.skipped = true;
         return D2G_OK;
     }
-    set->sp_skipped = false;
+    sp.dec.skipped = false;
     const unsigned nb = (unsigned)div_up<size_t>(N, 256);
-    uint32_t *la = set->d_label, *lb = set->d_label + Npad;
-    const SpTuning tu = sp_tuning(ctx);
+    uint32_t *la = sp.d_label, *lb = sp.d_label + Npad;
+    const d2g_k2_tuning &tu = ctx->k2;
     if (tu.link && S >= 2) {
         const uint32_t cap = (uint32_t)std::min<size_t>(N / 2 + 1, 12288);              // shared values of a column that take part: 3 words each, 144 KB of LDS at most
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)sp_link_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 12));
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)sp_link_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 8));
         const unsigned npair = (unsigned)(S / 2);
         const uint32_t ustride = (uint32_t)std::max<size_t>(1, std::min<size_t>(SP_UNITE_STRIDE, npair / 32));   // at least 32 column pairs take part in the uniting pass
-        if (set->d_owner && !split && tu.olink) {                        // one holder per shared value at hand: the streaming form
+        if (sp.d_owner && !split && tu.olink) {                        // one holder per shared value at hand: the streaming form
             const unsigned nx = (unsigned)div_up<size_t>(N, 1024);
-            hipLaunchKernelGGL(sp_olink_kernel<0>, dim3(nx, npair), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)S, set->d_owner, set->owner_stride, 1u, la, set->d_hint);
-            { unsigned g; const SpRider rd = sp_take_rider(set, nb, SP_RW_FLATTEN, false, &g, 2); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
-            hipLaunchKernelGGL(sp_olink_kernel<1>, dim3(nx, div_up<unsigned>(npair, ustride)), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)S, set->d_owner, set->owner_stride, ustride, la, set->d_hint);
+            hipLaunchKernelGGL(sp_olink_kernel<0>, dim3(nx, npair), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, 1u, la, sp.d_hint);
+            { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
+            hipLaunchKernelGGL(sp_olink_kernel<1>, dim3(nx, div_up<unsigned>(npair, ustride)), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, ustride, la, sp.d_hint);
         } else {
             hipLaunchKernelGGL(sp_link_kernel<0>, dim3(npair), dim3(1024), (size_t)cap * 12, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, 1u,
-                               la, set->d_hint);
-            { unsigned g; const SpRider rd = sp_take_rider(set, nb, SP_RW_FLATTEN, false, &g, 2); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
+                               la, sp.d_hint);
+            { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
             hipLaunchKernelGGL(sp_link_kernel<1>, dim3(div_up<unsigned>(npair, ustride)), dim3(1024), (size_t)cap * 8, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, ustride,
-                               la, set->d_hint);
+                               la, sp.d_hint);
         }
     }
     const size_t ntile_all = (Npad / 32) * (Npad / BS_CB);
     const uint32_t seg_limit = (uint32_t)std::min<size_t>((size_t)((double)ntile_all * tu.tile_frac), 0x3FFFFFFF);
     // (one single-workgroup kernel for count + scan + place with the counters in LDS was measured at N = 10 000: 25 us against 19 for the three)
-    { unsigned g; const SpRider rd = sp_take_rider(set, nb, SP_RW_COUNT, false, &g, 4); hipLaunchKernelGGL(sp_count_kernel, dim3(g), dim3(256), 0, s, la, lb, N, set->d_lcnt, set->d_order, rd); }
+    { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_COUNT, false, 4, &g); hipLaunchKernelGGL(sp_count_kernel, dim3(g), dim3(256), 0, s, la, lb, N, sp.d_lcnt, sp.d_order, rd); }
     if (tu.link && S >= 2) {
-        unsigned g; const SpRider rd = sp_take_rider(set, nb, SP_RW_ATTACH, false, &g, 8);
-        hipLaunchKernelGGL(sp_attach_kernel, dim3(g), dim3(256), 0, s, lb, set->d_lcnt, set->d_hint, N, Npad, set->d_order, rd);
+        unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_ATTACH, false, 8, &g);
+        hipLaunchKernelGGL(sp_attach_kernel, dim3(g), dim3(256), 0, s, lb, sp.d_lcnt, sp.d_hint, N, Npad, sp.d_order, rd);
     }
     const uint32_t CW = (uint32_t)((Npad / BS_CB + 31) / 32);
-    { unsigned g; const SpRider rd = sp_take_rider(set, 1, SP_RW_SCAN, false, &g, 16);
-      hipLaunchKernelGGL(sp_scan_kernel, dim3(g), dim3(1024), 0, s, set->d_lcnt, N, set->d_order, la, set->d_segend, seg_limit, set->d_gaveup, rd); }    // la (labels) is dead after the count kernel: it keeps the segment starts
-    { unsigned g; const SpRider rd = sp_take_rider(set, (unsigned)div_up<size_t>(set->Nstride, 256), 0, true, &g, 32);
-      hipLaunchKernelGGL(sp_place_kernel, dim3(g), dim3(256), 0, s, lb, N, set->Nstride, set->d_lcnt, set->d_sperm, set->d_sinv, set->d_order,
-                         la, set->d_segend, CW, set->d_gbm + 8, reinterpret_cast<uint2 *>(set->d_posseg.get()), rd); }
+    { unsigned g; const SpRider rd = sp.announced.take(1, SP_RW_SCAN, false, 16, &g);
+      hipLaunchKernelGGL(sp_scan_kernel, dim3(g), dim3(1024), 0, s, sp.d_lcnt, N, sp.d_order, la, sp.d_segend, seg_limit, sp.d_gaveup, rd); }    // la (labels) is dead after the count kernel: it keeps the segment starts
+    { unsigned g; const SpRider rd = sp.announced.take((unsigned)div_up<size_t>(set->Nstride, 256), 0, true, 32, &g);
+      hipLaunchKernelGGL(sp_place_kernel, dim3(g), dim3(256), 0, s, lb, N, set->Nstride, sp.d_lcnt, sp.d_sperm, sp.d_sinv, sp.d_order,
+                         la, sp.d_segend, CW, sp.d_gbm + 8, reinterpret_cast<uint2 *>(sp.d_posseg.get()), rd); }
     // (a certificate pass in front -- one thread per (column, sketch) comparing the sketch's segment with that of its value's owner, so that
     // columns where nothing crosses a segment need no workgroup here -- was measured: 17 us for the pass, and the 17 stragglers a clean
     // collection of 10 000 leaves still put a mixed value into a hundred columns, whose workgroups take as long as before: 0.338 vs 0.329 ms)
-    const SpColWork cw = sp_colwork_of(set);
-    hipLaunchKernelGGL(sp_emit_kernel, dim3((unsigned)S), dim3(SP_EMIT_T), 0, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, lb, set->d_order,
-                       cw, set->d_plctl, (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu), set->d_gaveup, (N >= 65536 || tu.emit_big) ? 1 : 0);
+    const SpColWork cw = sp_colwork_of(sp);
+    hipLaunchKernelGGL(sp_emit_kernel, dim3((unsigned)S), dim3(SP_EMIT_T), 0, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, lb, sp.d_order,
+                       cw, sp.d_plctl, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), sp.d_gaveup, (N >= 65536 || tu.emit_big) ? 1 : 0);
     // the pairs of the mixed values: a kernel of its own when the list is expected to be long (it must be complete before the workgroups that
     // count it per bin, which ride on the permute launch); otherwise extra workgroups of the permute launch itself (sp_permute)
-    if (set->sp_big) hipLaunchKernelGGL(sp_pairs_kernel, dim3((unsigned)ctx->num_cus * 8), dim3(256), 0, s, sp_pairs_of(set, cw, lb));
+    if (sp.dec.big) hipLaunchKernelGGL(sp_pairs_kernel, dim3((unsigned)ctx->num_cus * 8), dim3(256), 0, s, sp_pairs_of(sp, cw, lb));
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
 }
 
 // the sorted stream + (in the same launch) the work lists of whole-triangle launches
-SpBins sp_bins_of(const d2g_cmp_set *set) { return SpBins{set->d_binc, set->d_bstart, set->nbins, set->bin_nch, set->bin_cshift}; }
+SpBins sp_bins_of(const SpState &sp) { return SpBins{sp.d_binc, sp.d_bstart, sp.nbins, sp.bin_nch, sp.bin_cshift}; }
 
 int sp_permute(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
-    if (set->sp_skipped) { set->full_list_valid = true; return D2G_OK; }   // the remembered give-up: sp_giveup_kernel left the control words of a dense launch
+    SpState &sp = *set->sp;
+    if (sp.dec.skipped) { sp.full_list_valid = true; return D2G_OK; }   // the remembered give-up: sp_giveup_kernel left the control words of a dense launch
     // (the sorted stream gathered straight from the ids -- one group per XCD so that the gathers hit its L2 -- instead of permuting the caller's-order
     // stream was measured again in round 5: 42 us against planes 19 + permute 21 at config 3, 208 against 113 at N = 50 000; round 4 without the XCD
     // mapping: 74)
@@ -1792,24 +1734,24 @@ int sp_permute(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     constexpr size_t LDS_PART = 128 * 1024;                         // otherwise: one coding, in parts of at most this
     const uint32_t H = both ? 1u : (uint32_t)div_up<size_t>(set->Nstride * 4, LDS_PART);
     const uint32_t part = (uint32_t)(div_up<size_t>(div_up<size_t>(set->Nstride, H), 4) * 4);
-    SpFullList fl{set->d_gbm + 8, (uint32_t)nrb, (uint32_t)ncb, (uint32_t)((ncb + 31) / 32), set->d_tiles_full, (uint32_t)set->tiles_cap, set->d_fullctl,
+    SpFullList fl{sp.d_gbm + 8, (uint32_t)nrb, (uint32_t)ncb, (uint32_t)((ncb + 31) / 32), sp.d_tiles_full, (uint32_t)sp.tiles_cap, sp.d_fullctl,
                   (uint32_t)std::min<size_t>(sp_full_candidates(set->Npad), 0xFFFFFFFFu), (uint32_t)div_up<size_t>(ntile, 1024), (uint32_t)set->N,
-                  reinterpret_cast<const uint2 *>(set->d_posseg.get())};
+                  reinterpret_cast<const uint2 *>(sp.d_posseg.get())};
     const size_t nperm = (size_t)set->ntb * set->nbits_cap * (both ? 1 : 2) * H;
-    const uint32_t plcap = (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu);
+    const uint32_t plcap = (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu);
     // behind the list builders: the workgroups that count a LONG list per output bin, or those that make the pairs of a short one
-    SpHist hs{set->d_plist, set->d_plctl, plcap, set->sp_big ? set->bin_nwg : (uint32_t)ctx->num_cus, sp_bins_of(set), set->d_hoff, set->sp_big ? 1 : 0,
-              set->h_gaveup ? set->d_gaveup + 1 : nullptr};
-    set->full_list_valid = nperm + fl.nwg + hs.nhw < 0x7FFFFFFFu;
-    if (!set->full_list_valid) { ctx->last_error = "bitslice sparse: the permute launch does not fit a grid"; return D2G_ERR_INTERNAL; }
-    const size_t lds = std::max<size_t>((size_t)part * (both ? 8 : 4), set->sp_big ? (size_t)set->nbins * 4 : 0);
+    SpHist hs{sp.d_plist, sp.d_plctl, plcap, sp.dec.big ? sp.bin_nwg : (uint32_t)ctx->num_cus, sp_bins_of(sp), sp.d_hoff, sp.dec.big ? 1 : 0,
+              sp.h_gaveup ? sp.d_gaveup + SP_MW_LIST_LEN : nullptr};
+    sp.full_list_valid = nperm + fl.nwg + hs.nhw < 0x7FFFFFFFu;
+    if (!sp.full_list_valid) { ctx->last_error = "bitslice sparse: the permute launch does not fit a grid"; return D2G_ERR_INTERNAL; }
+    const size_t lds = std::max<size_t>((size_t)part * (both ? 8 : 4), sp.dec.big ? (size_t)sp.nbins * 4 : 0);
     auto kern = both ? sp_permute_lds_kernel<true> : sp_permute_lds_kernel<false>;
     D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 157 * 1024));   // (+ ~2 KB of static LDS: the list builders, the pairs of a short list)
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nperm + fl.nwg + hs.nhw)), dim3(1024), lds, s, set->d_stream, set->d_stream_s, set->Nstride, set->d_meta,
-                       set->d_sperm, set->d_order, fl, (uint32_t)nperm, (uint32_t)set->nbits_cap, H, part, hs, sp_pairs_of(set, sp_colwork_of(set), set->d_label + set->Npad));
-    if (set->sp_big) {                                                  // the list, bin by bin (d_plist2): as many workgroups as the counting ones
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nperm + fl.nwg + hs.nhw)), dim3(1024), lds, s, set->d_stream, sp.d_stream_s, set->Nstride, set->d_meta,
+                       sp.d_sperm, sp.d_order, fl, (uint32_t)nperm, (uint32_t)set->nbits_cap, H, part, hs, sp_pairs_of(sp, sp_colwork_of(sp), sp.d_label + set->Npad));
+    if (sp.dec.big) {                                                  // the list, bin by bin (d_plist2): as many workgroups as the counting ones
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)sp_bin_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SP_BIN_MAX * 4));
-        hipLaunchKernelGGL(sp_bin_kernel, dim3(hs.nhw), dim3(1024), (size_t)set->nbins * 4, s, set->d_plist, set->d_plist2, set->d_plctl, plcap, hs.bn, set->d_hoff, set->d_order);
+        hipLaunchKernelGGL(sp_bin_kernel, dim3(hs.nhw), dim3(1024), (size_t)sp.nbins * 4, s, sp.d_plist, sp.d_plist2, sp.d_plctl, plcap, hs.bn, sp.d_hoff, sp.d_order);
     }
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
@@ -1853,20 +1795,19 @@ inline const uint32_t *sp_fill_source(const StoreLut &st) { return reinterpret_c
 template <class Store>
 int sp_prefill(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1, Store store, uint32_t *out_words, hipStream_t s) {
     const size_t cnt = d2g_ut_count(set->N, r0, r1);
-    if (!cnt || !set->sparse_ok) return D2G_OK;
-    hipLaunchKernelGGL((sp_fill_kernel<Store>), dim3((unsigned)std::min<size_t>(div_up<size_t>(cnt / 4 + 1, SP_FILL_THREADS * SP_FILL_PER_THREAD), (size_t)0x7FFFFFFF)), dim3(SP_FILL_THREADS), 0, s,
+    if (!cnt || !set->sparse_ok()) return D2G_OK;
+    hipLaunchKernelGGL((sp_fill_kernel<Store>), dim3((unsigned)std::min<size_t>(sp_fill_pieces(cnt), (size_t)0x7FFFFFFF)), dim3(SP_FILL_THREADS), 0, s,
                        out_words, cnt, store, (uint32_t)set->S, (const uint32_t *)nullptr, 0u, 0u);
     D2G_HIP(ctx, hipGetLastError());
-    set->prefilled = out_words; set->prefilled_cnt = cnt; set->prefilled_pieces = (size_t)-1;
-    set->prefilled_src = sp_fill_source(store); set->prefilled_by_riders = false;
+    set->sp->filled.set_early(out_words, cnt, sp_fill_source(store));
     return D2G_OK;
 }
 
 // One sparse launch on a set whose last prepare left a sorted operand.  The launch uses per-set scratch (work list, launch rows, control
 // words): launches on ONE set must be issued one after the other on ONE stream (include/d2g.h says so).
 template <class Store>
-int launch_sparse(d2g_ctx *ctx, const d2g_cmp_set *cset, PairShape sh, Store store, uint32_t *out_words, hipStream_t s) {
-    d2g_cmp_set *set = const_cast<d2g_cmp_set *>(cset);
+int launch_sparse(d2g_ctx *ctx, const d2g_cmp_set *set, PairShape sh, Store store, uint32_t *out_words, hipStream_t s) {
+    SpState &sp = *set->sp;                                                             // (per-launch scratch: reachable from a const set)
     const size_t N = set->N, Npad = set->Npad, r0 = sh.i_lo, r1 = sh.i_hi;
     if (r1 <= r0) return D2G_OK;
     const bool full = r0 == 0 && r1 == N;
@@ -1880,58 +1821,55 @@ int launch_sparse(d2g_ctx *ctx, const d2g_cmp_set *cset, PairShape sh, Store sto
     const uint32_t CW = (ncb + 31) / 32;                                                // words of a bitmap row (column blocks)
     // per launch: 16 control words (ctl[0] = tiles listed, ctl[1] = flags (bit 0: dense walk), [3] = candidates, [8..15] tiles per XCD list) + a partial launch's bitmap
     // double-buffered: this launch's list kernel clears the other set for the next launch (both start cleared: sp_alloc)
-    const bool own_list = !(full && set->full_list_valid);            // a whole-triangle launch walks the lists the prepare left (sp_permute)
-    uint32_t *const ctl = own_list ? set->d_spctl + SP_CTL_WORDS * (set->sp_launch & 1u) : set->d_fullctl;
-    uint32_t *const ctl_next = set->d_spctl + SP_CTL_WORDS * ((set->sp_launch + 1) & 1u);
-    if (own_list) ++set->sp_launch;
-    set->last_ctl = ctl;
+    const bool own_list = !(full && sp.full_list_valid);            // a whole-triangle launch walks the lists the prepare left (sp_permute)
+    uint32_t *const ctl = own_list ? sp.d_spctl + SP_CTL_WORDS * (sp.sp_launch & 1u) : sp.d_fullctl;
+    uint32_t *const ctl_next = sp.d_spctl + SP_CTL_WORDS * ((sp.sp_launch + 1) & 1u);
+    if (own_list) ++sp.sp_launch;
+    sp.last_ctl = ctl;
     if (!full) {
-        hipLaunchKernelGGL(sp_rows_kernel, dim3(1), dim3(1024), 0, s, set->d_sperm, N, (uint32_t)r0, (uint32_t)r1, (uint32_t)nrows_pad, set->d_rowpos, set->d_rowk, set->d_order);
+        hipLaunchKernelGGL(sp_rows_kernel, dim3(1), dim3(1024), 0, s, sp.d_sperm, N, (uint32_t)r0, (uint32_t)r1, (uint32_t)nrows_pad, sp.d_rowpos, sp.d_rowk, sp.d_order);
         hipLaunchKernelGGL(sp_gather_kernel, dim3((unsigned)div_up<size_t>(nrows_pad, 256), (unsigned)(set->ntb * set->nbits_cap)), dim3(256), 0, s,
-                           set->d_stream_s, set->Nstride, set->d_meta, set->ntb, set->d_rowpos, (uint32_t)nrows_pad, set->d_rowstream, set->Nstride, set->d_order);
-        hipLaunchKernelGGL(sp_rowbm_kernel, dim3((unsigned)div_up<size_t>((size_t)nrb * CW, 256)), dim3(256), 0, s, set->d_gbm + 8, set->d_rowpos, nrb, CW, set->d_tilebm, set->d_order);
+                           sp.d_stream_s, set->Nstride, set->d_meta, set->ntb, sp.d_rowpos, (uint32_t)nrows_pad, sp.d_rowstream, set->Nstride, sp.d_order);
+        hipLaunchKernelGGL(sp_rowbm_kernel, dim3((unsigned)div_up<size_t>((size_t)nrb * CW, 256)), dim3(256), 0, s, sp.d_gbm + 8, sp.d_rowpos, nrb, CW, sp.d_tilebm, sp.d_order);
     }
     const size_t ntile = (size_t)nrb * ncb;
     // candidates: every tile of a partial launch; the tiles on or above the diagonal of sorted positions of a full one
     const size_t cand = full ? sp_full_candidates(Npad) : ntile;
     const uint32_t cand32 = (uint32_t)std::min<size_t>(cand, 0xFFFFFFFFu);
-    const uint32_t *bm = full ? set->d_gbm + 8 : set->d_tilebm;
-    uint32_t *const tiles = own_list ? set->d_tiles : set->d_tiles_full;
+    const uint32_t *bm = full ? sp.d_gbm + 8 : sp.d_tilebm;
+    uint32_t *const tiles = own_list ? sp.d_tiles : sp.d_tiles_full;
     if (own_list)
         hipLaunchKernelGGL(sp_list_kernel, dim3((unsigned)div_up<size_t>(ntile, 1024)), dim3(1024), 0, s, bm, nrb, ncb, CW, full ? 1 : 0,
-                           tiles, (uint32_t)set->tiles_cap, ctl, cand32, set->d_order, ctl_next, (uint32_t)N, full ? (const uint32_t *)nullptr : set->d_rowpos,
-                           reinterpret_cast<const uint2 *>(set->d_posseg.get()));
-    SpArgs a{set->d_stream_s, set->Nstride, full ? (const uint32_t *)nullptr : set->d_rowstream, set->Nstride, set->d_meta, set->ntb, (uint32_t)set->S, (uint32_t)N,
-             set->d_sperm, set->d_rowpos, tiles, ctl, ncb, cand32, (uint32_t)set->tiles_cap, reinterpret_cast<const uint2 *>(set->d_posseg.get())};
+                           tiles, (uint32_t)sp.tiles_cap, ctl, cand32, sp.d_order, ctl_next, (uint32_t)N, full ? (const uint32_t *)nullptr : sp.d_rowpos,
+                           reinterpret_cast<const uint2 *>(sp.d_posseg.get()));
+    SpArgs a{sp.d_stream_s, set->Nstride, full ? (const uint32_t *)nullptr : sp.d_rowstream, set->Nstride, set->d_meta, set->ntb, (uint32_t)set->S, (uint32_t)N,
+             sp.d_sperm, sp.d_rowpos, tiles, ctl, ncb, cand32, (uint32_t)sp.tiles_cap, reinterpret_cast<const uint2 *>(sp.d_posseg.get())};
     // contiguous 32 KB per workgroup, workgroups in dispatch order: a streaming write (6.1 TB/s at N = 50 000: 825 us; the grid-stride loop over 16
     // workgroups per CU it replaces, whose iterations lie 16 MB apart, reached 4.6: 1105 us).  One store per thread is faster still (722-760 us) but when
     // the launch turns out dense all of its 19 M waves start only to return: 254 us instead of 34
     // (the multi-GPU engine fills a rank's slab at the START of its step, under the exchanges: d2g_bitslice_prefill)
-    {
-        // (pieces [0, prefilled_pieces) were written ahead of the launch: all of them by an early fill, some or all by the prepare's riders)
-        const size_t pieces = std::min<size_t>(sp_fill_pieces(cnt), (size_t)0x7FFFFFFF);
-        // (the same output, the same rows AND the same fill value -- a count launch into a buffer that was pre-filled for a table launch fills again)
-        const size_t done = (set->prefilled == out_words && set->prefilled_cnt == cnt && set->prefilled_src == sp_fill_source(store)) ? std::min<size_t>(set->prefilled_pieces, pieces) : 0;
-        if (done < pieces)
-            hipLaunchKernelGGL((sp_fill_kernel<Store>), dim3((unsigned)(pieces - done)), dim3(SP_FILL_THREADS), 0, s,
-                               out_words, cnt, store, (uint32_t)set->S, ctl, cand32, (uint32_t)done);
-    }
-    set->prefilled = nullptr;
+    // (pieces [0, done) were written ahead of the launch: all of them by an early fill, some or all by the prepare's riders)
+    const size_t pieces = std::min<size_t>(sp_fill_pieces(cnt), (size_t)0x7FFFFFFF);
+    const size_t done = sp.filled.done_for(out_words, cnt, sp_fill_source(store), pieces);
+    if (done < pieces)
+        hipLaunchKernelGGL((sp_fill_kernel<Store>), dim3((unsigned)(pieces - done)), dim3(SP_FILL_THREADS), 0, s,
+                           out_words, cnt, store, (uint32_t)set->S, ctl, cand32, (uint32_t)done);
+    sp.filled.clear();
     // a multiple of 8 (every XCD's list gets the same number of workgroups), four times what is resident at once: the lists differ in
     // length, and a workgroup that finds nothing at its index leaves at once -- the dispatcher evens the lists out sub-tile by sub-tile
     // (exactly one resident wave of workgroups took as long as the longest list: 52 -> 85 us at config 3)
     const unsigned grid = (unsigned)std::max<size_t>(8, std::min<size_t>(div_up<size_t>(ntile * SP_SUBS, 8) * 8, (size_t)ctx->num_cus * (4 * D2G_SP_WPE / D2G_SP_KS) * SP_GRID_MULT) / 8 * 8);
     // the pair list, composed region by region (before the pair kernel: that one STORES, see SpBins) -- when this set's prepare binned it
-    if (set->sp_big) {
+    if (sp.dec.big) {
         const uint32_t band0 = (uint32_t)(r0 >> 5), nband = (uint32_t)((r1 - 1) >> 5) - band0 + 1u;
-        const uint32_t ppb = (1u << set->bin_cshift) / SP_CMP_COLS;    // pieces of 1024 columns per chunk (1 up to ~23 000 sketches)
-        SpComposeArgs ca{set->d_plist2, sp_bins_of(set), ctl, cand32, (uint32_t)N, (uint32_t)set->S, (uint32_t)r0, (uint32_t)r1, band0, ppb};
-        const size_t nwg = (size_t)nband * set->bin_nch * ppb * (32 / SP_CMP_ROWS);
+        const uint32_t ppb = (1u << sp.bin_cshift) / SP_CMP_COLS;    // pieces of 1024 columns per chunk (1 up to ~23 000 sketches)
+        SpComposeArgs ca{sp.d_plist2, sp_bins_of(sp), ctl, cand32, (uint32_t)N, (uint32_t)set->S, (uint32_t)r0, (uint32_t)r1, band0, ppb};
+        const size_t nwg = (size_t)nband * sp.bin_nch * ppb * (32 / SP_CMP_ROWS);
         if (nwg >= 0x7FFFFFFFu) { ctx->last_error = "bitslice sparse: too many compose workgroups"; return D2G_ERR_UNSUPPORTED; }
         hipLaunchKernelGGL((sp_compose_kernel<Store>), dim3((unsigned)nwg), dim3(SP_CMP_T), 0, s, ca, sh, store);
     }
     // (a short list is applied entry by entry: the pair kernel's tail adds, the gated launch behind it turns the sums into table values)
-    SpPatchArgs pa{set->d_plist, set->d_plctl, (uint32_t)std::min<size_t>(set->plist_cap, 0xFFFFFFFFu), ctl, cand32, set->d_sinv, set->d_rowk, set->d_rowpos, reinterpret_cast<const uint2 *>(set->d_posseg.get()), (uint32_t)N, bm, CW, (uint32_t)r0, (uint32_t)r1, full ? 1 : 0, std::min<uint32_t>(grid, (uint32_t)ctx->num_cus * 8u)};
+    SpPatchArgs pa{sp.d_plist, sp.d_plctl, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), ctl, cand32, sp.d_sinv, sp.d_rowk, sp.d_rowpos, reinterpret_cast<const uint2 *>(sp.d_posseg.get()), (uint32_t)N, bm, CW, (uint32_t)r0, (uint32_t)r1, full ? 1 : 0, std::min<uint32_t>(grid, (uint32_t)ctx->num_cus * 8u)};
     hipLaunchKernelGGL((k2_bitslice_sparse_kernel<SP_JR, Store>), dim3(grid), dim3(64 * D2G_SP_KS), 0, s, a, sh, store, pa);
     // behind the gate: every tile of the caller's-order operand in dense mode; otherwise the second step of a short pair list (table epilogue)
     if (dsh.nvalid_total)

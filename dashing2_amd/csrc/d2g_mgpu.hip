@@ -371,7 +371,7 @@ int prepare_many(d2g_allpairs **es, int n, const uint64_t *const *rows, const in
         D2G_HIP(e->ctx, hipEventRecord(e->ev_pack, cs[i]));
         D2G_HIP(e->ctx, hipStreamWaitEvent(e->xs, e->ev_pack, 0));
         // the slab's fill (HBM-bound, depends on nothing) while the row -> column exchange is on the links
-        if (e->pre_out && e->full[bufs[i]] && e->full[bufs[i]]->sparse_ok) {
+        if (e->pre_out && e->full[bufs[i]] && e->full[bufs[i]]->sparse_ok()) {
             MG_TRY(pt_begin(e, D2G_PHASE_FILL, 0, cs[i]));
             MG_TRY(d2g_bitslice_prefill(e->ctx, e->full[bufs[i]], e->r0, e->r1, e->pre_lut ? nullptr : (uint32_t *)e->pre_out, e->pre_lut, e->pre_lut ? (float *)e->pre_out : nullptr, cs[i]));
             MG_TRY(pt_end(e, D2G_PHASE_FILL, 0, cs[i]));
@@ -413,7 +413,7 @@ int prepare_many(d2g_allpairs **es, int n, const uint64_t *const *rows, const in
         }
     for (int i = 0; i < n; ++i) {                                       // every group is here: the operand ordered for the sparse-tile pair phase
         d2g_allpairs *e = es[i];
-        if (!e->full[bufs[i]]->sparse_ok) continue;
+        if (!e->full[bufs[i]]->sparse_ok()) continue;
         D2G_HIP(e->ctx, hipSetDevice(e->ctx->device));
         MG_TRY(pt_begin(e, D2G_PHASE_ORDER, 0, cs[i]));
         MG_TRY(d2g_bitslice_managed_ready(e->ctx, e->full[bufs[i]], cs[i]));

@@ -19,11 +19,32 @@ void d2g_tuning_load(d2g_tuning &t) {
         if (const char *v = std::getenv(n)) t.kv.emplace_back(n, v);
 }
 
+d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t) {
+    d2g_k2_tuning v;
+    if (const char *e = t.get("D2G_BS_SPARSE")) v.sparse = !(e[0] == '0');
+    if (const char *e = t.get("D2G_BS_SPARSE_MIN_N")) v.min_n = (size_t)std::atoll(e);
+    if (const char *e = t.get("D2G_SP_LINK")) v.link = std::atoi(e) != 0;
+    if (const char *e = t.get("D2G_SP_TILE_FRAC")) { const double f = std::atof(e); if (f > 0 && f <= 1) v.tile_frac = f; }
+    if (const char *e = t.get("D2G_SP_OLINK")) v.olink = std::atoi(e) != 0;
+    if (const char *e = t.get("D2G_SP_EMIT_BIG")) v.emit_big = std::atoi(e) != 0;
+    if (const char *e = t.get("D2G_SP_REMEMBER")) v.remember = std::atoi(e) != 0;
+    if (const char *e = t.get("D2G_SP_RIDE")) v.ride = std::atoi(e) & 63;
+    if (const char *e = t.get("D2G_SP_LONG_LIST")) { const long long d = std::atoll(e); if (d >= 0) v.long_list = (size_t)d; }
+    if (const char *e = t.get("D2G_SP_PREDICT")) v.predict = std::atoi(e) != 0;
+    if (const char *e = t.get("D2G_SP_LIST_FORM")) { const int d = std::atoi(e); if (d >= 0 && d <= 2) v.list_form = d; }
+    if (const char *e = t.get("D2G_SP_LIST_DIV")) { const long d = std::atol(e); if (d >= 1 && d <= (1 << 20)) v.list_div = (size_t)d; }
+    if (const char *e = t.get("D2G_BS_SORT")) v.sort = !(e[0] == '0');
+    if (const char *e = t.get("D2G_BS_TAGBITS")) { const int d = std::atoi(e); if (d >= 0 && d < 31) v.tagbits_max = d; }
+    if (const char *e = t.get("D2G_BS_NSPLIT")) { const int d = std::atoi(e); if (d == 1 || d == 2 || d == 4) v.nsplit_req = d; }
+    return v;
+}
+
 extern "C" {
 
 int d2g_ctx_reload_tuning(d2g_ctx *c) {
     if (!c) return D2G_ERR_INVALID;
     d2g_tuning_load(c->tune);
+    c->k2 = d2g_k2_tuning_resolve(c->tune);
     return D2G_OK;
 }
 
@@ -66,6 +87,7 @@ int d2g_ctx_create(int device, d2g_ctx **out) {
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
     d2g_tuning_load(c->tune);
+    c->k2 = d2g_k2_tuning_resolve(c->tune);
     *out = c;
     return D2G_OK;
 }

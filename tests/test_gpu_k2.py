@@ -686,7 +686,8 @@ def test_k2_sparse_tiles_and_pair_list_equal_the_direct_kernel_and_the_oracle(gp
 def test_k2_fill_ahead_of_the_launch(gpu_ctx, d2g):
     """d2g_cmp_ut_prefill_dev: the fill of the next upper-triangle launch enqueued ahead of it -- before the operand is even prepared,
     on a second stream -- and the launch skips its own.  Same output as the plain launch: counts and table values, whole triangle and
-    a row range; a launch that takes the dense walk after an early fill; a set too small to fill (no-op)."""
+    a row range; a launch that takes the dense walk after an early fill; an early fill with another value than the launch's (the launch
+    fills again); a set too small to fill (no-op)."""
     import torch
     N, S = 9_000, 64
     dev = torch.device("cuda", 0)
@@ -737,6 +738,16 @@ def test_k2_fill_ahead_of_the_launch(gpu_ctx, d2g):
         cs.eqcount_ut_dev(got.data_ptr(), 0, N, st)
         torch.cuda.synchronize()
         assert torch.equal(got, want), k
+        if k == 0:
+            # an early fill with ANOTHER value (a table whose first entry is not the bits of the count 0), then a count launch into the
+            # same output and rows: the launch fills for itself
+            lut2 = torch.arange(S + 1, dtype=torch.float32, device=dev) + 0.5
+            got.fill_(-1)
+            cs.prefill_ut_dev(got.data_ptr(), 0, N, lut_dev_ptr=lut2.data_ptr(), stream=st)
+            cs.update_dev(t_dev.data_ptr(), st)
+            cs.eqcount_ut_dev(got.data_ptr(), 0, N, st)
+            torch.cuda.synchronize()
+            assert torch.equal(got, want)
         del t_dev
     cs.close()
     small = synth.synthetic_registers(300, S, nclusters=3, seed=1)
@@ -754,7 +765,8 @@ def test_k2_fill_carried_by_the_prepare(gpu_ctx, d2g, oracle):
     kernels carry the fill as extra workgroups, the launch skips its own.  Same output as the plain launch (every word of a buffer
     pre-set to garbage): counts and table values, a whole triangle and a row range (unaligned output pointer), oracle rows; a matrix
     whose launch takes the dense walk; the remembered give-up (nothing rides, the launch writes everything); an announcement that the
-    launch does not match (other rows / other output) is simply not used; an announcement serves one prepare only."""
+    launch does not match (other rows / other output / other fill value) is simply not used; an announcement serves one prepare only; a
+    cancelled announcement writes nothing; what riders wrote is void once another prepare has run."""
     import torch
     N, S = 9_000, 64
     dev = torch.device("cuda", 0)
@@ -819,6 +831,32 @@ def test_k2_fill_carried_by_the_prepare(gpu_ctx, d2g, oracle):
         cs.eqcount_ut_dev(got.data_ptr(), 0, N, st)
         torch.cuda.synchronize()
         assert torch.equal(got[:npairs], want), k
+        if k == 0:
+            buf = got[:npairs]
+            # another fill value: the riders fill with the first entry of a table (not the bits of the count 0), then a COUNT launch
+            # into the same output and rows -- it fills for itself
+            lut2 = torch.arange(S + 1, dtype=torch.float32, device=dev) + 0.5
+            got.fill_(-1)
+            cs.announce_ut_dev(buf.data_ptr(), 0, N, lut_dev_ptr=lut2.data_ptr())
+            cs.update_dev(t_dev.data_ptr(), st)
+            cs.eqcount_ut_dev(buf.data_ptr(), 0, N, st)
+            torch.cuda.synchronize()
+            assert torch.equal(buf, want)
+            # a cancelled announcement (all three pointers null): the next prepare writes nothing into the buffer
+            got.fill_(-1)
+            cs.announce_ut_dev(buf.data_ptr(), 0, N)
+            gpu_ctx._check(d2g.lib().d2g_cmp_ut_announce_dev(gpu_ctx._h, cs._h, 0, N, None, None, None))
+            cs.update_dev(t_dev.data_ptr(), st)
+            torch.cuda.synchronize()
+            assert bool((got == -1).all())
+            # what the riders of one prepare wrote is void after another prepare: the buffer was used in between
+            cs.announce_ut_dev(buf.data_ptr(), 0, N)
+            cs.update_dev(t_dev.data_ptr(), st)
+            got.fill_(-1)
+            cs.update_dev(t_dev.data_ptr(), st)
+            cs.eqcount_ut_dev(buf.data_ptr(), 0, N, st)
+            torch.cuda.synchronize()
+            assert torch.equal(buf, want)
         del t_dev
     cs.close()
 

@@ -406,6 +406,12 @@ def test_allpairs_refuses_ranks_with_different_switches(d2g, monkeypatch):
     ctx1.reload_tuning()
     assert ctx1.tuning().get("D2G_SP_LINK") is None
     d2g.allpairs_step_all(engs, rows, None, outs)
+    # what is compared is what the switches RESOLVE to: an out-of-range D2G_BS_TAGBITS selects the same kernels as leaving it unset
+    monkeypatch.setenv("D2G_BS_TAGBITS", "40")
+    ctx1.reload_tuning()
+    monkeypatch.delenv("D2G_BS_TAGBITS")
+    assert ctx0.tuning().get("D2G_BS_TAGBITS") is None and ctx1.tuning().get("D2G_BS_TAGBITS") == "40"
+    d2g.allpairs_step_all(engs, rows, None, outs)
     for r in range(W):
         ctxs[r].sync()
         engs[r].status()
