@@ -74,8 +74,9 @@ struct d2g_tuning {
     }
 };
 void d2g_tuning_load(d2g_tuning &t);
-// what the switches that select K2 kernels and thresholds RESOLVE to (unset or invalid: the default).  Filled once per snapshot of the
-// switches (d2g_k2_tuning_resolve, right after d2g_tuning_load) and read as ctx->k2: nobody parses a switch where it is used.
+// what the switches RESOLVE to (unset or invalid: the default).  The three records below are filled once per snapshot of the switches
+// (d2g_tuning_resolve, right after d2g_tuning_load) and read as ctx->k2 (K2 kernels and thresholds), ctx->k3_tune (the --multiset
+// chain) and ctx->mgpu_chunks (the multi-GPU engine): nobody parses a switch where it is used.
 struct d2g_k2_tuning {
     bool sparse = true;                 // D2G_BS_SPARSE: 0 = every launch walks every tile
     size_t min_n = 8192;                // D2G_BS_SPARSE_MIN_N: below ~6000 sketches the extra launches cost more than the tiles they skip
@@ -97,10 +98,37 @@ d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
 std::string d2g_k2_tuning_json(const d2g_ctx *ctx);   // (d2g_k2_bitslice.hip) {"D2G_BS_SPARSE_MIN_N": 8192, ...}: the resolved values of the same switches
 uint64_t d2g_k2_tuning_hash(const d2g_ctx *ctx);   // (d2g_k2_bitslice.hip) FNV-1a over the RESOLVED values of the switches that select K2 kernels and thresholds: what the ranks of one job must agree on
 
+// K3's bucket geometry (d2g_k3_bmh.hip), here because the defaults and limits of its switches are these constants
+constexpr int K3_MAXBBITS = 12;             // log2 of the most buckets per genome (LDS histogram)
+constexpr int K3_ROUND_KEYS = 1400;         // keys one table round is sized for (load <= 0.69 of the 2048-slot LDS count table)
+constexpr int K3_TARGET = 1024;             // mean keys per bucket aimed for
+constexpr int K3_L1BITS = 8;                // write fronts of the scatter = 2^K3_L1BITS; the other bucket bits are resolved by k3_refine_kernel
+constexpr uint64_t K3_SPLIT_MIN = 4 * 1400; // mean bucket size above which a genome's buckets are split once more
+struct d2g_k3_tuning {
+    bool compact = false;               // D2G_K3_COMPACT: 1 = 4-byte stored words and the tile-sorted split, where k allows it (k <= 21: decided per call)
+    bool light = true;                  // D2G_K3_LIGHT: 0 = the first pass in the heavy form too (no survivor queue in HBM)
+    uint32_t l1bits = K3_L1BITS;        // D2G_K3_L1BITS: 0 .. K3_MAXBBITS bucket bits the scatter resolves itself; the rest is k3_refine_kernel's
+    uint64_t bucket_keys = K3_TARGET;   // D2G_K3_BUCKET_KEYS: mean keys per bucket the generic path aims for (tests: small inputs with many buckets)
+    uint64_t sub_keys = K3_TARGET;      // D2G_K3_SUB_KEYS: mean keys per sub-range when a big genome's buckets are split once more
+    uint64_t split_min = 0;             // D2G_K3_SPLIT_MIN: buckets averaging more keys than this are split once more; 0 = automatic (by path: K3_ROUND_KEYS compact, K3_SPLIT_MIN generic)
+    size_t subbatch = 0;                // D2G_K3_SUBBATCH: 1 .. 8 genome ranges of the bucketing / counting pipeline; 0 = automatic (4 for >= 8 genomes and >= 2e8 k-mers, else 1)
+    uint32_t round_keys = K3_ROUND_KEYS;// D2G_K3_ROUND_KEYS: 1 .. K3_ROUND_KEYS keys per table round (tests force multi-round buckets on small inputs)
+    double guess_scale = 1.0;           // D2G_K3_GUESS_SCALE: factor on the first guess of the BagMinHash bound, genomes and explicit weighted sets alike (tests force the redo passes)
+    size_t grid_per_cu = 48;            // D2G_K3_GRID_PER_CU: 1 .. 256 workgroups of the main pass per CU
+    bool gq_scale_set = false;          // D2G_K3_GQ_SCALE was given (tests force the region overflow) ...
+    double gq_scale = 2.0;              // ... a survivor region holds this multiple of the survivors expected in it ...
+    uint64_t gq_slack = 256;            // ... plus this many entries: 1 when the scale was given, else 256 above 24 workgroups per CU and 1024 up to there
+};
+d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
+constexpr int MG_MAX_CHUNKS = 4;            // most chunks a rank's column slice is cut into inside one multi-GPU step (d2g_mgpu.hip)
+void d2g_tuning_resolve(d2g_ctx *ctx);      // (d2g_runtime.hip) d2g_tuning_load, then every record above
+
 struct d2g_ctx {
     int device = -1;
     d2g_tuning tune;
-    d2g_k2_tuning k2;                       // ... and what its K2 switches resolved to
+    d2g_k2_tuning k2;                       // ... and what its K2 switches resolved to,
+    d2g_k3_tuning k3_tune;                  // its K3 switches,
+    int mgpu_chunks = 0;                    // and D2G_MGPU_CHUNKS: 1 .. MG_MAX_CHUNKS; 0 = the engine's default (a function of the shape)
     int num_cus = 0;
     std::string last_error;
     int timing = 0;                         // D2G_TIME_* mask (d2g_set_timing)

@@ -34,22 +34,20 @@
 #include <new>
 #include <vector>
 
-#ifndef D2G_K3_EXP
-#define D2G_K3_EXP 0          // timing experiments (tools/build_variant.sh): 1 = scatter without stores, 2 = 4-byte stores (no main pass); 3 = main without the BagMinHash walk, 4 = main counting only
-#endif
-
 namespace {
 
 constexpr int K3_THREADS = 256;
-constexpr int K3_MAXBBITS = 12;
 constexpr int K3_MAXB = 1 << K3_MAXBBITS;   // buckets per genome (LDS histogram)
 constexpr int K3_TAB = 2048;                // LDS count-table slots (24.6 KB with the counts: 6 workgroups per CU)
-constexpr int K3_ROUND_KEYS = 1400;         // keys one table round is sized for (load <= 0.69)
-constexpr int K3_TARGET = 1024;             // mean keys per bucket aimed for
-constexpr int K3_L1BITS = 8;                // write fronts of the scatter = 2^K3_L1BITS; the other bucket bits are resolved by k3_refine_kernel
-constexpr uint64_t K3_SPLIT_MIN = 4 * 1400; // mean bucket size above which a genome's buckets are split once more
 constexpr uint64_t BMH_INF = 0x7FF0000000000000ull;
 constexpr int BMH_STACK = 72;
+
+enum K3Status : int {         // the device status word (d_status[0]): 0 until a kernel raises it
+    K3_TABLE_OVERFLOW = 1,    // a round's keys did not fit the LDS count table
+    K3_BAD_WEIGHT = 2,        // a weight outside (0, 2^53] (explicit weighted sets)
+    K3_STACK_OVERFLOW = 3,    // the BagMinHash descent ran out of its private stack
+    K3_REGION_OVERFLOW = 4,   // a survivor region of the light first pass filled up: the host repeats the pass in the heavy form
+};
 
 struct K3Args {
     KmerArgs km;
@@ -156,9 +154,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     d2g_for_each_kmer(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);
         const uint32_t slot = atomicAdd(&pos[bucket_of(key, b1)], 1u);
-        if (D2G_K3_EXP == 1) { if (slot == 0xFFFFFFFFu) keys[slot] = key; }                      // timing experiment: no stores
-        else if (D2G_K3_EXP == 2) reinterpret_cast<uint32_t *>(keys)[slot] = (uint32_t)key;      // timing experiment: 4-byte stores
-        else keys[slot] = key;
+        keys[slot] = key;
     });
 }
 
@@ -335,7 +331,6 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
         __syncthreads();
         // flush: runs average 16 words, so a quarter wave (16 lanes) copies one bucket's run at a time -- a wave
         // store covers four runs of ~64 B; no per-element search for the bucket
-        if (D2G_K3_EXP == 6) { __syncthreads(); continue; }          // timing experiment: no flush
         const uint32_t *toff = a.tile_off + tile * K3C_MAXB;
         const uint32_t q = tid >> 4, l16 = tid & 15;                 // 16 quarter-waves per workgroup
         for (uint32_t b = q; b < B; b += K1_THREADS / 16) {
@@ -413,7 +408,6 @@ __device__ bool count_round(const CountTab<C32> &t, const typename K3Key<C32>::T
             const bool mine = i < n && (R == 1 || K3Key<C32>::round_of(key, R, shift, bb) == r);
             if (mine && key == EMPTY) atomicAdd(t.ones, 1u);
             if (!mine || key == EMPTY) continue;
-            if (D2G_K3_EXP == 8) { if (key == 12345) atomicAdd(t.ones, 1u); continue; }   // timing experiment: loads, no inserts
             // one exit test per probe (structured-control-flow bookkeeping is SALU work: the first
             // version of this loop issued 30 scalar instructions per probe)
             uint32_t s = K3Key<C32>::slot(key);
@@ -465,7 +459,6 @@ __device__ bool insert_round(const CountTab<C32> &t, const typename K3Key<C32>::
             const bool mine = i < n && (R == 1 || K3Key<C32>::round_of(key, R, shift, bb) == r);
             n_ones += mine & (key == EMPTY);
             if (!mine || key == EMPTY) continue;
-            if (D2G_K3_EXP == 8) { if (key == 12345) atomicAdd(t.ones, 1u); continue; }   // timing experiment: loads, no inserts
             uint32_t s = K3Key<C32>::slot(key);
             if constexpr (GUARD) {
                 int probes = 0;
@@ -584,7 +577,7 @@ __device__ void bmh_locate(Proc P, uint64_t d, double w, uint32_t m, double boun
         const double uu = (double)((r1 >> 11) + 1) * 0x1p-53;        // (0, 1]
         if ((1.0 - uu) > bound * width * 1.000000001) return;   // see proc_next
         S.x = uu;
-        if (sp >= BMH_STACK) { atomicExch(status, 3); return; }        // cannot happen (<= one sibling per tree level); never silent
+        if (sp >= BMH_STACK) { atomicExch(status, K3_STACK_OVERFLOW); return; }        // cannot happen (<= one sibling per tree level); never silent
         stk[sp++] = S;
     };
     for (;;) {
@@ -713,17 +706,6 @@ __device__ uint64_t block_hmax(const uint64_t *h, uint32_t m, uint64_t *red) {
     v = red[0];
     for (int k = 1; k < K3_THREADS / 64; ++k) v = red[k] > v ? red[k] : v;
     return v;
-}
-
-__device__ double block_sum(double v, double *red) {
-    const int tid = threadIdx.x;
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    double s = red[0];
-    for (int k = 1; k < K3_THREADS / 64; ++k) s += red[k];
-    return s;
 }
 
 struct BmhArgs {
@@ -957,7 +939,6 @@ __global__ __launch_bounds__(K3_THREADS) __attribute__((amdgpu_waves_per_eu(LIGH
                 // first -- worth it when the per-element walk was heavy; the compaction, 3.5 ms per call with its three
                 // barriers per round, costs more than the 40 % idle lanes here.)
                 auto survivor = [&](const Proc &P, uint64_t d, double w, int tt) {
-                    if (D2G_K3_EXP == 5) return;                         // timing experiment: survivors dropped
                     const uint32_t slot = atomicAdd(&qn, 1u);
                     if constexpr (LIGHT) {
                         // the region's capacity is twice the expected count; qn keeps counting so that the end of the kernel sees an overflow
@@ -993,7 +974,7 @@ __global__ __launch_bounds__(K3_THREADS) __attribute__((amdgpu_waves_per_eu(LIGH
                     if (cc) {
                         const KT key = sh.key[e];
                         sh.key[e] = K3Key<C32>::EMPTY; sh.cnt[e] = 0;
-                        if (cc >= cmin && D2G_K3_EXP != 3 && D2G_K3_EXP != 4 && D2G_K3_EXP != 8) element(key, cc);
+                        if (cc >= cmin) element(key, cc);
                     }
                 }
                 if (tid == 0) {
@@ -1018,7 +999,7 @@ __global__ __launch_bounds__(K3_THREADS) __attribute__((amdgpu_waves_per_eu(LIGH
                 lo = hi;
             }
         }
-        if (!fine) { if (tid == 0) atomicExch(a.status, 1); return; }
+        if (!fine) { if (tid == 0) atomicExch(a.status, K3_TABLE_OVERFLOW); return; }
         // The bound is never tightened per workgroup: thousands of same-address atomics per genome serialise in L2
         // (measured 25 ms per 4e5 workgroups) and the guess is already within ~2x of the final maximum.
     }
@@ -1027,7 +1008,7 @@ __global__ __launch_bounds__(K3_THREADS) __attribute__((amdgpu_waves_per_eu(LIGH
     if constexpr (LIGHT) {
         if (tid == 0) {
             a.gq_n[blockIdx.x] = qn < gq_cap ? qn : gq_cap;
-            if (qn > gq_cap) atomicExch(a.status, 4);                    // the host repeats the pass with the heavy kernel
+            if (qn > gq_cap) atomicExch(a.status, K3_REGION_OVERFLOW);                    // the host repeats the pass with the heavy kernel
         }
     } else drain();
 }
@@ -1090,7 +1071,7 @@ __global__ __launch_bounds__(K3_THREADS) void k3_count_kernel(BmhArgs a) {
         uint32_t R = 1;
         while ((uint64_t)R * a.round_keys < rn) R <<= 1;
         for (uint32_t r = 0; r < R; ++r) {
-            if (!count_round<C32>(t, kb, rn, R, r, sbits, bb)) { if (tid == 0) atomicExch(a.status, 1); return; }
+            if (!count_round<C32>(t, kb, rn, R, r, sbits, bb)) { if (tid == 0) atomicExch(a.status, K3_TABLE_OVERFLOW); return; }
             const uint32_t ne = compact_elements<C32>(t, &sh.nelem, a.thr);
             const uint32_t j0 = sh.misc;
             if (a.out_keys)
@@ -1132,7 +1113,7 @@ __device__ __forceinline__ bool ws_fetch(const WsArgs &a, uint64_t idx, uint64_t
     d = a.ids[idx];
     w = a.w ? a.w[idx] : 1.0;
     if (!(w > 0.)) return false;                                   // BagMinHash2::update ignores w <= 0
-    if (!(w <= 0x1p53)) { atomicExch(status, 2); return false; }   // outside the level set (also NaN)
+    if (!(w <= 0x1p53)) { atomicExch(status, K3_BAD_WEIGHT); return false; }   // outside the level set (also NaN)
     return true;
 }
 
@@ -1184,7 +1165,6 @@ uint32_t ceil_log2(uint64_t x) { uint32_t b = 0; while ((1ull << b) < x) ++b; re
 
 // grow-only work buffers of the --multiset path (owned by a sketcher or by a one-shot call)
 struct d2g_k3_state {
-    d2g_ctx *ctx = nullptr;
     d2g_dev<uint32_t> d_gtab;        // g_bbits [n] + g_boff [n+1]
     d2g_dev<uint64_t> d_koff;        // [n+1]
     d2g_dev<uint32_t> d_bucket_cnt;
@@ -1194,10 +1174,8 @@ struct d2g_k3_state {
     d2g_dev<uint32_t> d_blk_coarse;
     d2g_dev<uint64_t> d_gq;     // survivors of the light first pass (QEntry)
     d2g_dev<uint64_t> d_gq_off;   // [grid+1] region offsets, then [grid] u32 counts
-    int light_overflows = 0;
     d2g_stream xs;                                   // second stream of the sub-batch pipeline
     d2g_event ev_a[8], ev_b;
-    int pipelined_calls = 0;
     d2g_dev<uint64_t> d_keys;
     d2g_dev<uint64_t> d_skeys;      // big inputs: keys regrouped by sub-range
     d2g_dev<uint32_t> d_gblk;        // compact path: first launch-plan block of each genome
@@ -1211,7 +1189,6 @@ struct d2g_k3_state {
     d2g_dev<int> d_status;                 // [0] status, [1] nredo
     d2g_dev<uint64_t> d_guess;
     d2g_dev<double> d_tw_bucket;
-    int last_nredo = 0;
     d2g_dev<uint32_t> d_redo;
     d2g_dev<uint32_t> d_out_counts;
     d2g_dev<uint32_t> d_bucket_nd;
@@ -1240,20 +1217,16 @@ struct K3Host {
 };
 
 int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_off, size_t n, int k, K3Host &kh) {
+    const d2g_k3_tuning &t = ctx->k3_tune;
     kh.gtab.assign(2 * n + 1, 0);
     kh.gk.assign(n, 0);
     kh.gblk.assign(n + 1, 0);
     kh.hb = k > 16 ? (uint32_t)(2 * k - 32) : 0u;
     // the compact path (4-byte stored words, tile-sorted split) halves the chain's HBM traffic but is ~11 % slower end to
     // end (one Wang mix per distinct k-mer moves into the issue-bound main pass): opt-in with D2G_K3_COMPACT=1, k <= 21
-    kh.compact = false;
-    if (const char *e = ctx->tune.get("D2G_K3_COMPACT")) if (e[0] == '1') kh.compact = kh.hb <= (uint32_t)K3C_MAXBBITS;
+    kh.compact = t.compact && kh.hb <= (uint32_t)K3C_MAXBBITS;
     uint64_t tb = 0;
-    uint64_t bucket_keys = K3_TARGET, sub_keys = K3_TARGET;
-    kh.l1bits = K3_L1BITS; kh.l2_tb0.clear(); kh.l2_bits.clear(); kh.l2_start.assign(n + 1, 0);
-    if (const char *e = ctx->tune.get("D2G_K3_L1BITS")) { const int v = std::atoi(e); if (v >= 0 && v <= K3_MAXBBITS) kh.l1bits = (uint32_t)v; }
-    if (const char *e = ctx->tune.get("D2G_K3_BUCKET_KEYS")) { const long v = std::atol(e); if (v >= 1) bucket_keys = (uint64_t)v; }
-    if (const char *e = ctx->tune.get("D2G_K3_SUB_KEYS")) { const long v = std::atol(e); if (v >= 1) sub_keys = (uint64_t)v; }
+    kh.l1bits = t.l1bits; kh.l2_tb0.clear(); kh.l2_bits.clear(); kh.l2_start.assign(n + 1, 0);
     for (size_t g = 0; g < n; ++g) {
         uint64_t nk = 0, chunks = 0;
         for (uint64_t r = genome_run_off[g]; r < genome_run_off[g + 1]; ++r) {
@@ -1265,7 +1238,7 @@ int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_
         kh.gblk[g + 1] = kh.gblk[g] + (uint32_t)div_up<uint64_t>(chunks, K1_BLOCK_CHUNKS);
         uint32_t bb;
         if (kh.compact) bb = std::max<uint32_t>(kh.hb, std::min<uint32_t>(K3C_MAXBBITS, ceil_log2((nk + K3C_TARGET - 1) / K3C_TARGET)));
-        else bb = std::min<uint32_t>(K3_MAXBBITS, ceil_log2((nk + bucket_keys - 1) / bucket_keys));
+        else bb = std::min<uint32_t>(K3_MAXBBITS, ceil_log2((nk + t.bucket_keys - 1) / t.bucket_keys));
         kh.gtab[g] = bb;
         kh.gtab[n + g] = (uint32_t)tb;
         kh.l2_start[g] = (uint32_t)kh.l2_tb0.size();
@@ -1287,14 +1260,13 @@ int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_
     // (the compact path aims for 4x larger buckets -- 64-byte runs in the tile sort -- and always splits them here into
     // table-sized sub-ranges: a table round that re-reads its whole key range made the main pass 55 % slower, and a
     // bucket staged in LDS for the rounds cost more in occupancy than it saved: 42 ms instead of 20)
-    uint64_t split_min = kh.compact ? K3_ROUND_KEYS : K3_SPLIT_MIN;
-    if (const char *e = ctx->tune.get("D2G_K3_SPLIT_MIN")) { const long v = std::atol(e); if (v >= 1) split_min = (uint64_t)v; }
+    const uint64_t split_min = t.split_min ? t.split_min : kh.compact ? K3_ROUND_KEYS : K3_SPLIT_MIN;
     kh.gsplit.assign(n, 0);
     kh.gsub.assign(n + 1, 0);
     for (size_t g = 0; g < n; ++g) {
         const uint64_t B = 1ull << kh.gtab[g], mean = kh.gk[g] / B;
         if (mean > split_min) {
-            kh.gsplit[g] = std::min<uint32_t>(K3_MAXBBITS, ceil_log2((mean + sub_keys - 1) / sub_keys));
+            kh.gsplit[g] = std::min<uint32_t>(K3_MAXBBITS, ceil_log2((mean + t.sub_keys - 1) / t.sub_keys));
             kh.any_split = true;
         }
         // + 1: the end of a genome's last sub-range gets its OWN entry.  Sharing it with the next split genome's first
@@ -1305,16 +1277,33 @@ int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_
     return D2G_OK;
 }
 
-// count (R11) + sketch (R12) of one staged batch; results stay on the device in st->d_h / st->d_tw
-int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, size_t nblk, const K3Host &kh, size_t n,
-           uint64_t xormask, size_t m, double thr, bool count_only, bool distinct_only = false) {
+enum class K3Mode { Sketch, Count, Distinct };   // registers and total weights (R12) / distinct (key, count) per bucket (R11) / their number only
+
+// count (R11) or sketch (R12) of one staged batch: what the caller fills in, the kernel arguments one stage prepares for the next, the stages
+struct K3Run {
+    d2g_ctx *ctx = nullptr; d2g_k3_state *st = nullptr; hipStream_t s = nullptr;
+    KmerArgs km; size_t nblk = 0;      // the launch plan of the staged batch
+    K3Host kh; size_t n = 0;           // its bucket layout (k3_layout); genomes
+    uint64_t xormask = 0; size_t m = 1; double thr = 0.;
+    uint64_t key_words = 0;            // d_keys in 8-byte words: a masked key per k-mer on the generic path, a 4-byte stored word on the compact one
+    K3Args ka{}; K3cArgs kc{};         // bucket(): the generic / the compact form
+    BmhArgs b{};                       // split, count, sketch
+    int run(K3Mode mode), upload_tables(), bucket_prepare(), bucket(size_t g_lo, size_t g_hi), split(), count(K3Mode mode);
+    int sketch(const std::vector<size_t> &sub), sketch_init(const std::vector<double> &guess), light_pass(const struct K3LightPlan &plan, bool pipeline);
+    std::vector<size_t> subbatches(K3Mode mode) const;
+    void init_registers() {            // registers to +inf, weights and redo flags to zero
+        hipLaunchKernelGGL(k3_bmh_init_kernel, dim3((unsigned)div_up<size_t>(std::max<size_t>(n * m, n), K3_THREADS)), dim3(K3_THREADS), 0, s, st->d_h, n * m, st->d_tw, st->d_redo, n);
+    }
+};
+
+// the tables every mode needs: bucket geometry and key offsets per genome, zeroed bucket counts and status
+int K3Run::upload_tables() {
     const uint32_t TB = kh.TB;
     if (int rc = st->d_gtab.grow(ctx, 2 * n + 1, 4096)) return rc;
     if (int rc = st->d_bucket_cnt.grow(ctx, (size_t)TB + 1, 4096)) return rc;
     if (int rc = st->d_bucket_off.grow(ctx, (size_t)TB + 1, 4096)) return rc;
     if (int rc = st->d_cursor.grow(ctx, (size_t)TB + 1, 4096)) return rc;
-    // 8 bytes of masked key per k-mer on the generic path, 4 bytes of stored word on the compact one
-    const uint64_t key_words = kh.compact ? (kh.total + 1) / 2 : kh.total;
+    key_words = kh.compact ? (kh.total + 1) / 2 : kh.total;
     if (int rc = st->d_keys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
     if (!st->d_status) if (int rc = st->d_status.alloc(ctx, 2, "k3 status alloc")) return rc;
     if (int rc = st->d_koff.grow(ctx, n + 1, 4096)) return rc;
@@ -1322,288 +1311,317 @@ int k3_run(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s, const KmerArgs &km, si
     D2G_HIP(ctx, hipMemcpyAsync(st->d_koff, kh.koff.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
     D2G_HIP(ctx, hipMemsetAsync(st->d_bucket_cnt, 0, ((size_t)TB + 1) * sizeof(uint32_t), s));
     D2G_HIP(ctx, hipMemsetAsync(st->d_status, 0, 2 * sizeof(int), s));
-    d2g_timer tm(ctx, &ctx->ev_k3, s);
-    // Sub-batch pipeline (generic path, sketching): the batch is cut into genome ranges; the bucketing passes of range j + 1
-    // (hist, scan, scatter, refine: bound by memory) run on the caller's stream while the counting pass of range j (bound by
-    // latency and instruction issue) runs on a second stream.  Ranges are independent: disjoint genomes, buckets, key regions.
-    K3Args ka;
-    std::memset(&ka, 0, sizeof(ka));
-    std::vector<size_t> sub{0, n};                                       // genome boundaries of the ranges
-    bool pipeline = false;
-    if (!kh.compact && !kh.any_split && !count_only && !D2G_K3_EXP && n >= 2 && kh.gblk[n] == nblk) {
-        size_t want = (n >= 8 && kh.total >= 200000000ull) ? 4 : 1;
-        if (const char *e = ctx->tune.get("D2G_K3_SUBBATCH")) { const int v = std::atoi(e); if (v >= 1 && v <= 8) want = (size_t)v; }
-        want = std::min(want, n);
-        if (want > 1) {
-            sub.assign(1, 0);
-            for (size_t j = 1; j < want; ++j) {                          // cut by k-mer count
-                const uint64_t target = kh.total / want * j;
-                size_t g = sub.back() + 1;
-                while (g < n - (want - j) && kh.koff[g] < target) ++g;
-                sub.push_back(g);
-            }
-            sub.push_back(n);
-            pipeline = true;
-        }
+    return D2G_OK;
+}
+
+// Sub-batch pipeline (generic path, sketching): the batch is cut into genome ranges; the bucketing passes of range j + 1
+// (hist, scan, scatter, refine: bound by memory) run on the caller's stream while the counting pass of range j (bound by
+// latency and instruction issue) runs on a second stream.  Ranges are independent: disjoint genomes, buckets, key regions.
+// Returns the genome boundaries of the ranges; {0, n}: one range, no pipeline.
+std::vector<size_t> K3Run::subbatches(K3Mode mode) const {
+    std::vector<size_t> sub{0, n};
+    if (kh.compact || kh.any_split || mode != K3Mode::Sketch || n < 2 || kh.gblk[n] != nblk) return sub;
+    size_t want = ctx->k3_tune.subbatch ? ctx->k3_tune.subbatch : (n >= 8 && kh.total >= 200000000ull) ? 4 : 1;
+    want = std::min(want, n);
+    if (want == 1) return sub;
+    sub.assign(1, 0);
+    for (size_t j = 1; j < want; ++j) {                                  // cut by k-mer count
+        const uint64_t target = kh.total / want * j;
+        size_t g = sub.back() + 1;
+        while (g < n - (want - j) && kh.koff[g] < target) ++g;
+        sub.push_back(g);
     }
-    auto stage_a = [&](size_t g_lo, size_t g_hi) {
-        K3Args a = ka;
-        const unsigned blk_lo = kh.gblk[g_lo], nb = (g_lo == 0 && g_hi == n) ? (unsigned)nblk : kh.gblk[g_hi] - blk_lo;
-        a.km.blk0 = blk_lo; a.g0 = (uint32_t)g_lo;
-        if (nb) hipLaunchKernelGGL(k3_hist_kernel, dim3(nb), dim3(K1_THREADS), 0, s, a);
-        hipLaunchKernelGGL(k3_scan_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(K3_THREADS), 0, s, a);
-        if (nb) hipLaunchKernelGGL(k3_scatter_kernel, dim3(nb), dim3(K1_THREADS), 0, s, a);
-        const unsigned l2_lo = kh.l2_start[g_lo], nl = kh.l2_start[g_hi] - l2_lo;
-        if (nb && nl && D2G_K3_EXP != 1 && D2G_K3_EXP != 2) {
-            a.l2_tb0 += l2_lo; a.l2_bits += l2_lo;
-            hipLaunchKernelGGL(k3_refine_kernel, dim3(nl), dim3(K3_THREADS), 0, s, a);
-        }
-    };
+    sub.push_back(n);
+    return sub;
+}
+
+// buffers, tables and kernel arguments of the bucketing passes
+int K3Run::bucket_prepare() {
     if (kh.compact) {
-        // 4-byte stored words, tile-sorted split: histogram per tile -> per-tile write offsets -> coalesced flush
         D2G_CHECK(ctx, kh.gblk[n] == nblk, "internal: K3 block layout disagrees with the launch plan");
-        const size_t ntiles = nblk * K1_CPT;
+        const size_t ntiles = std::max<size_t>(nblk * K1_CPT, 1);
         if (int rc = st->d_gblk.grow(ctx, n + 1, 4096)) return rc;
-        if (int rc = st->d_tile_cnt.grow(ctx, std::max<size_t>(ntiles, 1) * K3C_MAXB, 4096)) return rc;
-        if (int rc = st->d_tile_off.grow(ctx, std::max<size_t>(ntiles, 1) * K3C_MAXB, 4096)) return rc;
+        if (int rc = st->d_tile_cnt.grow(ctx, ntiles * K3C_MAXB, 4096)) return rc;
+        if (int rc = st->d_tile_off.grow(ctx, ntiles * K3C_MAXB, 4096)) return rc;
         D2G_HIP(ctx, hipMemcpyAsync(st->d_gblk, kh.gblk.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        K3cArgs c;
-        c.km = km; c.g_bbits = st->d_gtab; c.g_boff = st->d_gtab + n; c.g_koff = st->d_koff; c.g_blk = st->d_gblk;
-        c.tile_cnt = st->d_tile_cnt; c.tile_off = st->d_tile_off; c.bucket_cnt = st->d_bucket_cnt; c.bucket_off = st->d_bucket_off;
-        c.keys32 = reinterpret_cast<uint32_t *>(st->d_keys.get()); c.hb = kh.hb; c.TB = TB;
-        if (nblk) hipLaunchKernelGGL(k3c_hist_kernel, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, c);
-        hipLaunchKernelGGL(k3c_scan_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, c);
-        if (nblk) {
-            D2G_HIP(ctx, hipFuncSetAttribute((const void *)k3c_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K3cScatterLds)));
-            hipLaunchKernelGGL(k3c_scatter_kernel, dim3((unsigned)nblk), dim3(K1_THREADS), sizeof(K3cScatterLds), s, c);
-        }
-    } else {
-        K3Args a;
-        a.km = km; a.xormask = xormask;
-        a.g_bbits = st->d_gtab; a.g_boff = st->d_gtab + n; a.g_koff = st->d_koff;
-        a.bucket_cnt = st->d_bucket_cnt; a.bucket_off = st->d_bucket_off; a.cursor = st->d_cursor; a.keys = st->d_keys;
-        a.TB = TB;
-        a.l1bits = kh.l1bits; a.coarse = nullptr; a.l2_tb0 = nullptr; a.l2_bits = nullptr;
-        const size_t nl2 = kh.l2_tb0.size();
-        if (nl2) {
-            // the coarse keys borrow the sub-range buffer: k3_split_kernel (big inputs) runs after the refinement
-            if (int rc = st->d_skeys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
-            if (int rc = st->d_l2.grow(ctx, 2 * nl2, 4096)) return rc;
-            D2G_HIP(ctx, hipMemcpyAsync(st->d_l2, kh.l2_tb0.data(), nl2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            D2G_HIP(ctx, hipMemcpyAsync(st->d_l2 + nl2, kh.l2_bits.data(), nl2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            a.coarse = st->d_skeys; a.l2_tb0 = st->d_l2; a.l2_bits = st->d_l2 + nl2;
-        }
-        if (int rc = st->d_blk_coarse.grow(ctx, std::max<size_t>(nblk, 1) << kh.l1bits, 4096)) return rc;
-        a.blk_coarse = st->d_blk_coarse;
-        a.g0 = 0; a.n_genomes = (uint32_t)n;
-        ka = a;
-        if (!pipeline) stage_a(0, n);
+        kc.km = km; kc.g_bbits = st->d_gtab; kc.g_boff = st->d_gtab + n; kc.g_koff = st->d_koff; kc.g_blk = st->d_gblk;
+        kc.tile_cnt = st->d_tile_cnt; kc.tile_off = st->d_tile_off; kc.bucket_cnt = st->d_bucket_cnt; kc.bucket_off = st->d_bucket_off;
+        kc.keys32 = reinterpret_cast<uint32_t *>(st->d_keys.get()); kc.hb = kh.hb; kc.TB = kh.TB;
+        return D2G_OK;
     }
-    BmhArgs b;
-    std::memset(&b, 0, sizeof(b));
+    K3Args &a = ka;
+    a.km = km; a.xormask = xormask; a.g_bbits = st->d_gtab; a.g_boff = st->d_gtab + n; a.g_koff = st->d_koff;
+    a.bucket_cnt = st->d_bucket_cnt; a.bucket_off = st->d_bucket_off; a.cursor = st->d_cursor; a.keys = st->d_keys;
+    a.TB = kh.TB; a.l1bits = kh.l1bits; a.g0 = 0; a.n_genomes = (uint32_t)n;
+    const size_t nl2 = kh.l2_tb0.size();
+    if (nl2) {
+        // the coarse keys borrow the sub-range buffer: k3_split_kernel (big inputs) runs after the refinement
+        if (int rc = st->d_skeys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
+        if (int rc = st->d_l2.grow(ctx, 2 * nl2, 4096)) return rc;
+        D2G_HIP(ctx, hipMemcpyAsync(st->d_l2, kh.l2_tb0.data(), nl2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        D2G_HIP(ctx, hipMemcpyAsync(st->d_l2 + nl2, kh.l2_bits.data(), nl2 * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        a.coarse = st->d_skeys; a.l2_tb0 = st->d_l2; a.l2_bits = st->d_l2 + nl2;
+    }
+    if (int rc = st->d_blk_coarse.grow(ctx, std::max<size_t>(nblk, 1) << kh.l1bits, 4096)) return rc;
+    a.blk_coarse = st->d_blk_coarse;
+    return D2G_OK;
+}
+// the keys of genomes [g_lo, g_hi) into their buckets: hist -> scan -> scatter [-> refine].  The compact form (4-byte stored
+// words, tile-sorted split: histogram per tile -> per-tile write offsets -> coalesced flush) takes the whole batch only.
+int K3Run::bucket(size_t g_lo, size_t g_hi) {
+    if (kh.compact) {
+        const unsigned nb = (unsigned)nblk;
+        if (nb) hipLaunchKernelGGL(k3c_hist_kernel, dim3(nb), dim3(K1_THREADS), 0, s, kc);
+        hipLaunchKernelGGL(k3c_scan_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, kc);
+        if (nb) {
+            D2G_HIP(ctx, hipFuncSetAttribute((const void *)k3c_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K3cScatterLds)));
+            hipLaunchKernelGGL(k3c_scatter_kernel, dim3(nb), dim3(K1_THREADS), sizeof(K3cScatterLds), s, kc);
+        }
+        return D2G_OK;
+    }
+    K3Args a = ka;
+    const unsigned blk_lo = kh.gblk[g_lo], nb = (g_lo == 0 && g_hi == n) ? (unsigned)nblk : kh.gblk[g_hi] - blk_lo;
+    a.km.blk0 = blk_lo; a.g0 = (uint32_t)g_lo;
+    if (nb) hipLaunchKernelGGL(k3_hist_kernel, dim3(nb), dim3(K1_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k3_scan_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(K3_THREADS), 0, s, a);
+    if (nb) hipLaunchKernelGGL(k3_scatter_kernel, dim3(nb), dim3(K1_THREADS), 0, s, a);
+    const unsigned l2_lo = kh.l2_start[g_lo], nl = kh.l2_start[g_hi] - l2_lo;
+    if (nb && nl) {
+        a.l2_tb0 += l2_lo; a.l2_bits += l2_lo;
+        hipLaunchKernelGGL(k3_refine_kernel, dim3(nl), dim3(K3_THREADS), 0, s, a);
+    }
+    return D2G_OK;
+}
+
+// big inputs: the buckets of the genomes with gsplit[g] > 0 once more, into table-sized sub-ranges
+int K3Run::split() {
+    if (!kh.any_split) return D2G_OK;
+    if (int rc = st->d_skeys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
+    if (int rc = st->d_sub_off.grow(ctx, kh.gsub[n] + 1, 4096)) return rc;
+    if (int rc = st->d_gsplit.grow(ctx, n, 4096)) return rc;
+    if (int rc = st->d_gsub.grow(ctx, n + 1, 4096)) return rc;
+    D2G_HIP(ctx, hipMemcpyAsync(st->d_gsplit, kh.gsplit.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    D2G_HIP(ctx, hipMemcpyAsync(st->d_gsub, kh.gsub.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    b.g_split = st->d_gsplit; b.g_sub = st->d_gsub; b.sub_off = st->d_sub_off; b.skeys = st->d_skeys;
+    b.skeys32 = reinterpret_cast<uint32_t *>(st->d_skeys.get());
+    const unsigned gs = (unsigned)std::min<size_t>(kh.TB, (size_t)ctx->num_cus * 8);
+    hipLaunchKernelGGL(kh.compact ? k3_split_kernel<true> : k3_split_kernel<false>, dim3(gs), dim3(K3_THREADS), 0, s, b);
+    return D2G_OK;
+}
+
+// R11 alone: the distinct (key, count) of every bucket -- K3Mode::Distinct: only how many -- stay in st->d_out_* / d_bucket_nd
+int K3Run::count(K3Mode mode) {
+    if (mode == K3Mode::Count) {
+        if (int rc = st->d_out_keys.grow(ctx, std::max<uint64_t>(kh.total, 1), 4096)) return rc;
+        if (int rc = st->d_out_counts.grow(ctx, std::max<uint64_t>(kh.total, 1), 4096)) return rc;
+        b.out_keys = st->d_out_keys; b.out_counts = st->d_out_counts;
+    }
+    if (int rc = st->d_bucket_nd.grow(ctx, (size_t)kh.TB + 1, 4096)) return rc;
+    b.bucket_nd = st->d_bucket_nd;
+    if (kh.TB) hipLaunchKernelGGL(kh.compact ? k3_count_kernel<true> : k3_count_kernel<false>, dim3(kh.TB), dim3(K3_THREADS), 0, s, b);
+    return D2G_OK;
+}
+
+// first guess of every genome's bound: with no count threshold the total weight IS the k-mer count; with one it is an upper
+// bound (a too small guess only costs a second pass, which then knows the exact weight).  Tests scale it to force the redo path.
+std::vector<double> k3_guesses(const K3Host &kh, size_t m, double scale) {
+    std::vector<double> guess(kh.gk.size());
+    const double lnm = std::log((double)m);
+    for (size_t g = 0; g < guess.size(); ++g) guess[g] = scale * bmh_guess((double)std::max<uint64_t>(kh.gk[g], 1), (double)m, lnm);
+    return guess;
+}
+// strips of genome g expected to survive the first pass: at most gk in all (an element of count c has <= c), about gk * guess survive
+double k3_survivors(const K3Host &kh, const std::vector<double> &guess, size_t g) { return (double)kh.gk[g] * std::min(1.0, guess[g]); }
+
+// The light first pass as the host plans it: one launch over everything, or one per range of the pipeline.  Survivors go to per-workgroup
+// regions of a queue in HBM: gq_scale (twice) the survivors its buckets are expected to produce (a genome's spread evenly over its buckets) + gq_slack
+struct LightLaunch { uint32_t t0, t1, g0, g1; unsigned grid; size_t off_at, n_at; uint64_t entry0; };
+struct K3LightPlan {
+    std::vector<LightLaunch> ll;
+    std::vector<uint64_t> off;      // per launch [grid + 1] region offsets relative to the launch's first region (at off_at)
+    uint64_t entries = 0; size_t n_words = 0;   // all launches: queue entries; u32 survivor counts, which live behind `off` in the same buffer (n_at indexes u32)
+};
+K3LightPlan k3_plan_light(const K3Host &kh, const d2g_k3_tuning &t, const std::vector<double> &guess, int num_cus, const std::vector<size_t> &sub) {
+    K3LightPlan p;
+    const size_t n = kh.gk.size(), nr = sub.size() - 1;
+    for (size_t j = 0; j < nr; ++j) {
+        LightLaunch L;
+        L.g0 = (uint32_t)sub[j]; L.g1 = (uint32_t)sub[j + 1];
+        L.t0 = kh.gtab[n + sub[j]]; L.t1 = sub[j + 1] < n ? kh.gtab[n + sub[j + 1]] : kh.TB;
+        const size_t cap_grid = std::max<size_t>(1, (size_t)num_cus * t.grid_per_cu / (nr > 1 ? 2 : 1));
+        L.grid = (unsigned)std::min<size_t>(std::max<uint32_t>(L.t1 - L.t0, 1), cap_grid);
+        L.off_at = p.off.size(); L.n_at = p.n_words; L.entry0 = p.entries;
+        // workgroup w of the launch walks buckets [lo, hi) of [t0, t1), as k3_bmh_main_kernel cuts them
+        const uint32_t per = (L.t1 - L.t0 + L.grid - 1) / L.grid;
+        p.off.resize(L.off_at + L.grid + 1, 0);
+        uint64_t *off = p.off.data() + L.off_at;
+        size_t g = 0;
+        for (unsigned w = 0; w < L.grid; ++w) {
+            const uint64_t lo = (uint64_t)L.t0 + (uint64_t)w * per, hi = std::min<uint64_t>(lo + per, L.t1);
+            double e = 0.;
+            while (g < n && kh.gtab[n + g] + (1ull << kh.gtab[g]) <= lo) ++g;
+            for (size_t gg = g; lo < hi && gg < n && kh.gtab[n + gg] < hi; ++gg) {
+                const uint64_t b0 = kh.gtab[n + gg], B = 1ull << kh.gtab[gg];
+                const uint64_t ov = std::min<uint64_t>(hi, b0 + B) - std::max<uint64_t>(lo, b0);
+                e += k3_survivors(kh, guess, gg) * (double)ov / (double)B;
+            }
+            off[w + 1] = off[w] + (uint64_t)(t.gq_scale * e) + t.gq_slack;
+        }
+        p.entries += off[L.grid]; p.n_words += L.grid;
+        p.ll.push_back(L);
+    }
+    for (auto &L : p.ll) L.n_at += 2 * p.off.size();
+    return p;
+}
+
+// buffers of the sketch, the guesses on the device, registers to +inf
+int K3Run::sketch_init(const std::vector<double> &guess) {
+    const uint32_t TB = kh.TB;
+    if (int rc = st->d_h.grow(ctx, std::max<size_t>(n * m, 1), 4096)) return rc;
+    if (int rc = st->d_tw.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
+    if (int rc = st->d_guess.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
+    if (int rc = st->d_redo.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
+    if (int rc = st->d_tw_bucket.grow(ctx, (size_t)TB + 1, 4096)) return rc;
+    D2G_HIP(ctx, hipMemsetAsync(st->d_tw_bucket, 0, ((size_t)TB + 1) * sizeof(double), s));
+    D2G_HIP(ctx, hipMemcpyAsync(st->d_guess, guess.data(), n * sizeof(double), hipMemcpyHostToDevice, s));
+    b.h = st->d_h; b.tw = st->d_tw; b.tw_acc = reinterpret_cast<uint64_t *>(st->d_tw_bucket.get()); b.guess = st->d_guess; b.redo = st->d_redo;
+    b.nredo = reinterpret_cast<uint32_t *>(st->d_status + 1);
+    b.tb0 = 0; b.tb1 = TB; b.g0 = 0;
+    init_registers();
+    return D2G_OK;
+}
+// the main kernel of a batch's key form: light (survivors go to the queue in HBM) or heavy (they are walked in place)
+auto k3_main_kernel(bool compact, bool light) -> void (*)(BmhArgs) {
+    if (!compact) return light ? k3_bmh_main_kernel<false, true> : k3_bmh_main_kernel<false, false>;
+    return light ? k3_bmh_main_kernel<true, true> : k3_bmh_main_kernel<true, false>;
+}
+// the first pass in the light form: main, survivor and verify kernel per planned launch -- pipelined: on the second stream, behind its range's bucketing
+int K3Run::light_pass(const K3LightPlan &plan, bool pipeline) {
+    if (pipeline && !st->xs) {
+        D2G_HIP(ctx, st->xs.create(hipStreamNonBlocking));
+        for (auto &e : st->ev_a) D2G_HIP(ctx, e.create(hipEventDisableTiming));
+        D2G_HIP(ctx, st->ev_b.create(hipEventDisableTiming));
+    }
+    hipStream_t xs = pipeline ? (hipStream_t)st->xs : s;
+    for (size_t j = 0; j < (pipeline ? plan.ll.size() : 1); ++j) {
+        const LightLaunch &L = plan.ll[j];
+        BmhArgs x = b;
+        x.tb0 = L.t0; x.tb1 = L.t1; x.g0 = L.g0; x.redo_mode = 0;
+        x.gq = reinterpret_cast<QEntry *>(st->d_gq.get()) + L.entry0;
+        x.gq_off = st->d_gq_off + L.off_at;
+        x.gq_n = reinterpret_cast<uint32_t *>(st->d_gq_off.get()) + L.n_at;
+        if (pipeline) {
+            if (int rc = bucket(L.g0, L.g1)) return rc;
+            D2G_HIP(ctx, hipEventRecord(st->ev_a[j], s));
+            D2G_HIP(ctx, hipStreamWaitEvent(xs, st->ev_a[j], 0));
+        }
+        if (!pipeline || L.t1 > L.t0) {
+            hipLaunchKernelGGL(k3_main_kernel(kh.compact, true), dim3(L.grid), dim3(K3_THREADS), 0, xs, x);
+            hipLaunchKernelGGL(k3_bmh_survivor_kernel, dim3(L.grid), dim3(K3_THREADS), 0, xs, x);
+        }
+        if (pipeline) hipLaunchKernelGGL(k3_bmh_verify_kernel, dim3(L.g1 - L.g0), dim3(K3_THREADS), 0, xs, x);
+        else hipLaunchKernelGGL(k3_bmh_verify_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, b);
+    }
+    if (pipeline) {
+        D2G_HIP(ctx, hipEventRecord(st->ev_b, xs));
+        D2G_HIP(ctx, hipStreamWaitEvent(s, st->ev_b, 0));
+    }
+    return D2G_OK;
+}
+
+// R12: registers and total weights of the bucketed batch stay in st->d_h / st->d_tw.  `sub`: subbatches()
+int K3Run::sketch(const std::vector<size_t> &sub) {
+    const d2g_k3_tuning &t = ctx->k3_tune;
+    const uint32_t TB = kh.TB;
+    const std::vector<double> guess = k3_guesses(kh, m, t.guess_scale);
+    if (int rc = sketch_init(guess)) return rc;
+    // Workgroups own contiguous bucket ranges; 6 are resident per CU.  A grid of 8 per CU (r01) left a third of the ranges
+    // to a second, three-quarters-empty round: 9.0 ms.  With many more, smaller ranges the hardware's dispatch evens the
+    // tail out: 8.3 ms at 6 per CU, 7.9 at 12, 7.6 at 24, 7.3 at 48 and 64 (the survivor kernel follows: 1.9 -> 1.7 ms).
+    const unsigned main_grid = (unsigned)std::min<size_t>(TB, (size_t)ctx->num_cus * t.grid_per_cu);
+    bool light = TB > 0 && t.light;
+    if (light) {
+        // batches of read-sized inputs: the bound of a tiny input is above 1 and every element survives -- a queue of
+        // 24 bytes per k-mer would buy nothing; such batches keep the heavy form
+        double etot = 0.;
+        for (size_t g = 0; g < n; ++g) etot += k3_survivors(kh, guess, g);
+        if (etot > 0.125 * (double)kh.total) light = false;
+    }
+    bool pipeline = sub.size() > 2;
+    if (pipeline && !light) { if (int rc = bucket(0, n)) return rc; pipeline = false; }   // heavy first pass: one range
+    K3LightPlan plan;
+    if (light) {
+        plan = k3_plan_light(kh, t, guess, ctx->num_cus, sub);
+        if (int rc = st->d_gq.grow(ctx, (size_t)plan.entries * (sizeof(QEntry) / 8) + 8, 4096)) return rc;
+        if (int rc = st->d_gq_off.grow(ctx, plan.off.size() + (plan.n_words + 1) / 2 + 1, 4096)) return rc;
+        D2G_HIP(ctx, hipMemcpyAsync(st->d_gq_off, plan.off.data(), plan.off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    }
+    // The first pass walks every genome, light or heavy; a light pass in which a survivor region overflowed (the plan is an expectation) is
+    // done AGAIN in the heavy form; redo passes (heavy) then walk the genomes whose guess proved too small, under a larger one, until none is left.
+    enum { FirstLight, FirstHeavy, Redo } pass = light ? FirstLight : FirstHeavy;
+    for (int redos = 0;;) {
+        b.redo_mode = pass == Redo;
+        if (pass == FirstLight) { if (int rc = light_pass(plan, pipeline)) return rc; }
+        else {
+            if (TB) hipLaunchKernelGGL(k3_main_kernel(kh.compact, false), dim3(main_grid), dim3(K3_THREADS), 0, s, b);
+            hipLaunchKernelGGL(k3_bmh_verify_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, b);
+        }
+        int st2[2] = {0, 0};                                  // [0] kernel status, [1] genomes whose guess failed
+        D2G_HIP(ctx, hipMemcpyAsync(st2, st->d_status, sizeof(st2), hipMemcpyDeviceToHost, s));
+        D2G_HIP(ctx, hipStreamSynchronize(s));
+        if (pass == FirstLight && st2[0] == K3_REGION_OVERFLOW) {
+            D2G_HIP(ctx, hipMemsetAsync(st->d_status, 0, 2 * sizeof(int), s));
+            D2G_HIP(ctx, hipMemsetAsync(st->d_tw_bucket, 0, ((size_t)TB + 1) * sizeof(double), s));
+            init_registers();
+            pass = FirstHeavy;
+            continue;
+        }
+        if (st2[0] || !st2[1]) break;
+        D2G_CHECK(ctx, redos < 40, "internal: BagMinHash bound did not converge");
+        ++redos; pass = Redo;
+        D2G_HIP(ctx, hipMemsetAsync(st->d_status + 1, 0, sizeof(int), s));
+    }
+    return D2G_OK;
+}
+
+int K3Run::run(K3Mode mode) {
+    if (int rc = upload_tables()) return rc;
+    d2g_timer tm(ctx, &ctx->ev_k3, s);
+    const std::vector<size_t> sub = subbatches(mode);
+    if (int rc = bucket_prepare()) return rc;
+    if (sub.size() == 2) if (int rc = bucket(0, n)) return rc;      // pipelined: sketch() buckets range by range
     b.keys = st->d_keys; b.keys32 = reinterpret_cast<const uint32_t *>(st->d_keys.get()); b.g_bbits = st->d_gtab; b.hb = kh.hb; b.xormask = xormask;
     b.bucket_off = st->d_bucket_off; b.g_boff = st->d_gtab + n;
-    b.n = (uint32_t)n; b.TB = TB; b.m = (uint32_t)m; b.thr = thr; b.status = st->d_status;
-    if (kh.any_split) {
-        const uint64_t nsub = kh.gsub[n];
-        if (int rc = st->d_skeys.grow(ctx, std::max<uint64_t>(key_words, 1), 4096)) return rc;
-        if (int rc = st->d_sub_off.grow(ctx, nsub + 1, 4096)) return rc;
-        if (int rc = st->d_gsplit.grow(ctx, n, 4096)) return rc;
-        if (int rc = st->d_gsub.grow(ctx, n + 1, 4096)) return rc;
-        D2G_HIP(ctx, hipMemcpyAsync(st->d_gsplit, kh.gsplit.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-        D2G_HIP(ctx, hipMemcpyAsync(st->d_gsub, kh.gsub.data(), (n + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        b.g_split = st->d_gsplit; b.g_sub = st->d_gsub; b.sub_off = st->d_sub_off; b.skeys = st->d_skeys;
-        b.skeys32 = reinterpret_cast<uint32_t *>(st->d_skeys.get());
-        const unsigned gs = (unsigned)std::min<size_t>(TB, (size_t)ctx->num_cus * 8);
-        hipLaunchKernelGGL(kh.compact ? k3_split_kernel<true> : k3_split_kernel<false>, dim3(gs), dim3(K3_THREADS), 0, s, b);
-    }
-    b.round_keys = K3_ROUND_KEYS;
-    if (const char *e = ctx->tune.get("D2G_K3_ROUND_KEYS")) { const int v = std::atoi(e); if (v >= 1 && v <= K3_ROUND_KEYS) b.round_keys = (uint32_t)v; }
-    if (count_only) {
-        if (!distinct_only) {
-            if (int rc = st->d_out_keys.grow(ctx, std::max<uint64_t>(kh.total, 1), 4096)) return rc;
-            if (int rc = st->d_out_counts.grow(ctx, std::max<uint64_t>(kh.total, 1), 4096)) return rc;
-            b.out_keys = st->d_out_keys; b.out_counts = st->d_out_counts;
-        }
-        if (int rc = st->d_bucket_nd.grow(ctx, (size_t)TB + 1, 4096)) return rc;
-        b.bucket_nd = st->d_bucket_nd;
-        if (TB) hipLaunchKernelGGL(kh.compact ? k3_count_kernel<true> : k3_count_kernel<false>, dim3(TB), dim3(K3_THREADS), 0, s, b);
-    } else {
-        if (int rc = st->d_h.grow(ctx, std::max<size_t>(n * m, 1), 4096)) return rc;
-        if (int rc = st->d_tw.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
-        if (int rc = st->d_guess.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
-        if (int rc = st->d_redo.grow(ctx, std::max<size_t>(n, 1), 4096)) return rc;
-        if (int rc = st->d_tw_bucket.grow(ctx, (size_t)TB + 1, 4096)) return rc;
-        D2G_HIP(ctx, hipMemsetAsync(st->d_tw_bucket, 0, ((size_t)TB + 1) * sizeof(double), s));
-        // first guess: with no count threshold the total weight IS the k-mer count; with one it is an
-        // upper bound (a too small guess only costs a second pass, which then knows the exact weight)
-        double scale = 1.0;
-        if (const char *e = ctx->tune.get("D2G_K3_GUESS_SCALE")) { const double v = std::atof(e); if (v > 0.) scale = v; }   // tests force the redo path
-        std::vector<uint64_t> guess(n);
-        const double lnm = std::log((double)m);
-        for (size_t g = 0; g < n; ++g) {
-            const double gv = scale * bmh_guess((double)std::max<uint64_t>(kh.gk[g], 1), (double)m, lnm);
-            std::memcpy(&guess[g], &gv, 8);
-        }
-        D2G_HIP(ctx, hipMemcpyAsync(st->d_guess, guess.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-        b.h = st->d_h; b.tw = st->d_tw; b.tw_acc = reinterpret_cast<uint64_t *>(st->d_tw_bucket.get()); b.guess = st->d_guess; b.redo = st->d_redo;
-        b.nredo = reinterpret_cast<uint32_t *>(st->d_status + 1);
-        const size_t ninit = std::max<size_t>(n * m, n);
-        hipLaunchKernelGGL(k3_bmh_init_kernel, dim3((unsigned)div_up<size_t>(ninit, K3_THREADS)), dim3(K3_THREADS), 0, s,
-                           st->d_h, n * m, st->d_tw, st->d_redo, n);
-        // Workgroups own contiguous bucket ranges; 6 are resident per CU.  A grid of 8 per CU (r01) left a third of the ranges
-        // to a second, three-quarters-empty round: 9.0 ms.  With many more, smaller ranges the hardware's dispatch evens the
-        // tail out: 8.3 ms at 6 per CU, 7.9 at 12, 7.6 at 24, 7.3 at 48 and 64 (the survivor kernel follows: 1.9 -> 1.7 ms).
-        size_t per_cu = 48;
-        if (const char *e = ctx->tune.get("D2G_K3_GRID_PER_CU")) { const int v = std::atoi(e); if (v >= 1 && v <= 256) per_cu = (size_t)v; }
-        const unsigned main_grid = (unsigned)std::min<size_t>(TB, (size_t)ctx->num_cus * per_cu);
-        st->last_nredo = 0;
-        // First pass in the light form: survivors go to per-workgroup regions of a queue in HBM.  A region holds twice the
-        // survivors its buckets are expected to produce: genome g yields at most gk strips in all (an element of count c has
-        // <= c strips) and about gk * guess of them survive, spread evenly over its buckets.
-        bool light = TB > 0 && !D2G_K3_EXP;
-        if (const char *e = ctx->tune.get("D2G_K3_LIGHT")) if (e[0] == '0') light = false;
-        double gq_scale = 2.0;
-        uint64_t gq_slack = per_cu > 24 ? 256 : 1024;
-        if (const char *e = ctx->tune.get("D2G_K3_GQ_SCALE")) { gq_scale = std::max(0.0, std::atof(e)); gq_slack = 1; }   // tests force the overflow path
-        if (light) {
-            // batches of read-sized inputs: the bound of a tiny input is above 1 and every element survives -- a queue of
-            // 24 bytes per k-mer would buy nothing; such batches keep the heavy form
-            double etot = 0.;
-            for (size_t g = 0; g < n; ++g) { double gv; std::memcpy(&gv, &guess[g], 8); etot += (double)kh.gk[g] * std::min(1.0, gv); }
-            if (etot > 0.125 * (double)kh.total) light = false;
-        }
-        b.tb0 = 0; b.tb1 = TB; b.g0 = 0;
-        if (pipeline && !light) { stage_a(0, n); pipeline = false; }       // heavy first pass: one range
-        // per-workgroup survivor regions of one light launch over buckets [t0, t1): offsets relative to the launch's first region
-        auto gq_offsets = [&](uint32_t t0, uint32_t t1, unsigned grid, std::vector<uint64_t> &off) {
-            const uint32_t per = (t1 - t0 + grid - 1) / grid;
-            off.assign((size_t)grid + 1, 0);
-            size_t g = 0;
-            for (unsigned w = 0; w < grid; ++w) {
-                const uint64_t lo = (uint64_t)t0 + (uint64_t)w * per, hi = std::min<uint64_t>(lo + per, t1);
-                double e = 0.;
-                while (g < n && kh.gtab[n + g] + (1ull << kh.gtab[g]) <= lo) ++g;
-                for (size_t gg = g; lo < hi && gg < n && kh.gtab[n + gg] < hi; ++gg) {
-                    const uint64_t b0 = kh.gtab[n + gg], B = 1ull << kh.gtab[gg];
-                    const uint64_t ov = std::min<uint64_t>(hi, b0 + B) - std::max<uint64_t>(lo, b0);
-                    double gv; std::memcpy(&gv, &guess[gg], 8);
-                    const double eg = (double)kh.gk[gg] * std::min(1.0, gv);
-                    e += eg * (double)ov / (double)B;
-                }
-                off[w + 1] = off[w] + (uint64_t)(gq_scale * e) + gq_slack;
-            }
-        };
-        // launches of the light first pass: one over everything, or one per range of the pipeline
-        struct LightLaunch { uint32_t t0, t1, g0, g1; unsigned grid; size_t off_at, n_at; uint64_t entry0; };
-        std::vector<LightLaunch> ll;
-        if (light) {
-            std::vector<uint64_t> all_off;
-            uint64_t entries = 0;
-            size_t n_words = 0;
-            const size_t nr = sub.size() - 1;
-            for (size_t j = 0; j < nr; ++j) {
-                LightLaunch L;
-                L.g0 = (uint32_t)sub[j]; L.g1 = (uint32_t)sub[j + 1];
-                L.t0 = kh.gtab[n + sub[j]]; L.t1 = sub[j + 1] < n ? kh.gtab[n + sub[j + 1]] : TB;
-                const size_t cap_grid = std::max<size_t>(1, (size_t)ctx->num_cus * per_cu / (nr > 1 ? 2 : 1));
-                L.grid = (unsigned)std::min<size_t>(std::max<uint32_t>(L.t1 - L.t0, 1), cap_grid);
-                std::vector<uint64_t> off;
-                gq_offsets(L.t0, L.t1, L.grid, off);
-                L.off_at = all_off.size(); L.n_at = n_words; L.entry0 = entries;
-                all_off.insert(all_off.end(), off.begin(), off.end());
-                entries += off.back(); n_words += L.grid;
-                ll.push_back(L);
-            }
-            if (int rc = st->d_gq.grow(ctx, (size_t)entries * (sizeof(QEntry) / 8) + 8, 4096)) return rc;
-            if (int rc = st->d_gq_off.grow(ctx, all_off.size() + (n_words + 1) / 2 + 1, 4096)) return rc;
-            D2G_HIP(ctx, hipMemcpyAsync(st->d_gq_off, all_off.data(), all_off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-            for (auto &L : ll) L.n_at += 2 * all_off.size();                 // u32 index into the same buffer, behind the offsets
-        }
-        auto light_args = [&](const LightLaunch &L) {
-            BmhArgs x = b;
-            x.tb0 = L.t0; x.tb1 = L.t1; x.g0 = L.g0; x.redo_mode = 0;
-            x.gq = reinterpret_cast<QEntry *>(st->d_gq.get()) + L.entry0;
-            x.gq_off = st->d_gq_off + L.off_at;
-            x.gq_n = reinterpret_cast<uint32_t *>(st->d_gq_off.get()) + L.n_at;
-            return x;
-        };
-        void (*light_k)(BmhArgs) = k3_bmh_main_kernel<false, true>, (*heavy_k)(BmhArgs) = k3_bmh_main_kernel<false, false>;
-        if (kh.compact) { light_k = k3_bmh_main_kernel<true, true>; heavy_k = k3_bmh_main_kernel<true, false>; }
-        for (int pass = 0;; ++pass) {
-            b.redo_mode = pass > 0;
-            const bool lt = light && pass == 0;
-            const bool run = TB && D2G_K3_EXP != 1 && D2G_K3_EXP != 2 && D2G_K3_EXP != 6 && D2G_K3_EXP != 7;
-            if (lt && pipeline) {
-                if (!st->xs) {
-                    D2G_HIP(ctx, st->xs.create(hipStreamNonBlocking));
-                    for (auto &e : st->ev_a) D2G_HIP(ctx, e.create(hipEventDisableTiming));
-                    D2G_HIP(ctx, st->ev_b.create(hipEventDisableTiming));
-                }
-                for (size_t j = 0; j < ll.size(); ++j) {
-                    stage_a(ll[j].g0, ll[j].g1);
-                    D2G_HIP(ctx, hipEventRecord(st->ev_a[j], s));
-                    D2G_HIP(ctx, hipStreamWaitEvent(st->xs, st->ev_a[j], 0));
-                    const BmhArgs x = light_args(ll[j]);
-                    if (run && ll[j].t1 > ll[j].t0) {
-                        hipLaunchKernelGGL(light_k, dim3(ll[j].grid), dim3(K3_THREADS), 0, st->xs, x);
-                        hipLaunchKernelGGL(k3_bmh_survivor_kernel, dim3(ll[j].grid), dim3(K3_THREADS), 0, st->xs, x);
-                    }
-                    hipLaunchKernelGGL(k3_bmh_verify_kernel, dim3(ll[j].g1 - ll[j].g0), dim3(K3_THREADS), 0, st->xs, x);
-                }
-                D2G_HIP(ctx, hipEventRecord(st->ev_b, st->xs));
-                D2G_HIP(ctx, hipStreamWaitEvent(s, st->ev_b, 0));
-                st->pipelined_calls++;
-            } else {
-                if (run) {
-                    if (lt) {
-                        const BmhArgs x = light_args(ll[0]);
-                        hipLaunchKernelGGL(light_k, dim3(ll[0].grid), dim3(K3_THREADS), 0, s, x);
-                        hipLaunchKernelGGL(k3_bmh_survivor_kernel, dim3(ll[0].grid), dim3(K3_THREADS), 0, s, x);
-                    } else
-                        hipLaunchKernelGGL(heavy_k, dim3(main_grid), dim3(K3_THREADS), 0, s, b);
-                }
-                hipLaunchKernelGGL(k3_bmh_verify_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, b);
-            }
-            int st2[2] = {0, 0};                                  // [0] kernel status, [1] genomes whose guess failed
-            D2G_HIP(ctx, hipMemcpyAsync(st2, st->d_status, sizeof(st2), hipMemcpyDeviceToHost, s));
-            D2G_HIP(ctx, hipStreamSynchronize(s));
-            if (lt && st2[0] == 4) {
-                // a survivor region overflowed (the estimate above is an expectation): the pass again, in the heavy form
-                light = false;
-                D2G_HIP(ctx, hipMemsetAsync(st->d_status, 0, 2 * sizeof(int), s));
-                D2G_HIP(ctx, hipMemsetAsync(st->d_tw_bucket, 0, ((size_t)TB + 1) * sizeof(double), s));
-                hipLaunchKernelGGL(k3_bmh_init_kernel, dim3((unsigned)div_up<size_t>(ninit, K3_THREADS)), dim3(K3_THREADS), 0, s,
-                                   st->d_h, n * m, st->d_tw, st->d_redo, n);
-                st->light_overflows++;
-                --pass;
-                continue;
-            }
-            const int nredo = st2[1];
-            if (st2[0] || !nredo || D2G_K3_EXP) break;
-            st->last_nredo += nredo;
-            D2G_CHECK(ctx, pass < 40, "internal: BagMinHash bound did not converge");
-            D2G_HIP(ctx, hipMemsetAsync(st->d_status + 1, 0, sizeof(int), s));
-        }
-    }
+    b.n = (uint32_t)n; b.TB = kh.TB; b.m = (uint32_t)m; b.thr = thr; b.status = st->d_status; b.round_keys = ctx->k3_tune.round_keys;
+    if (int rc = split()) return rc;
+    if (int rc = mode == K3Mode::Sketch ? sketch(sub) : count(mode)) return rc;
     tm.stop();
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
 }
 
+// a final status word as the library's error: code and message (K3_REGION_OVERFLOW never leaves sketch())
+int k3_status_error(d2g_ctx *ctx, int status) {
+    if (status == K3_TABLE_OVERFLOW) { ctx->last_error = "internal: k-mer count table overflow"; return D2G_ERR_INTERNAL; }
+    if (status == K3_BAD_WEIGHT) { ctx->last_error = "BagMinHash weight outside (0, 2^53]"; return D2G_ERR_INVALID; }
+    if (status == K3_STACK_OVERFLOW) { ctx->last_error = "internal: BagMinHash process stack overflow"; return D2G_ERR_INTERNAL; }
+    return D2G_OK;
+}
 int k3_check_status(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s) {
     int status = 0;
     D2G_HIP(ctx, hipMemcpyAsync(&status, st->d_status, sizeof(int), hipMemcpyDeviceToHost, s));
     D2G_HIP(ctx, hipStreamSynchronize(s));
-    if (status == 1) { ctx->last_error = "internal: k-mer count table overflow"; return D2G_ERR_INTERNAL; }
-    if (status == 2) { ctx->last_error = "BagMinHash weight outside (0, 2^53]"; return D2G_ERR_INVALID; }
-    if (status == 3) { ctx->last_error = "internal: BagMinHash process stack overflow"; return D2G_ERR_INTERNAL; }
-    return D2G_OK;
+    return k3_status_error(ctx, status);
 }
 
-d2g_k3_state *k3_state_of(d2g_sketcher *sk) {
-    if (!sk->k3) { sk->k3 = new (std::nothrow) d2g_k3_state(); if (sk->k3) sk->k3->ctx = sk->ctx; }
-    return sk->k3;
+// what the sketcher's three entry points begin with: its work buffers, the batch staged on its stream, the bucket layout
+int k3_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
+             size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon, K3Run &r) {
+    if (!sk->k3) sk->k3 = new (std::nothrow) d2g_k3_state();
+    if (!sk->k3) return D2G_ERR_NOMEM;
+    r.ctx = sk->ctx; r.st = sk->k3; r.s = sk->stream; r.n = n;
+    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, &r.km, &r.nblk, nullptr)) return rc;
+    return k3_layout(r.ctx, run_len, genome_run_off, n, k, r.kh);
 }
 
 }  // namespace
@@ -1619,20 +1637,14 @@ int d2g_sketcher_run_bmh(d2g_sketcher *sk, const uint8_t *packed, size_t packed_
     D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 24), "sketchsize out of range");
     D2G_CHECK(ctx, (sig_out && total_weight_out) || n == 0, "null output");
     D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
-    d2g_k3_state *st = k3_state_of(sk);
-    if (!st) return D2G_ERR_NOMEM;
-    KmerArgs km;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, &km,
-                                    &nblk, nullptr)) return rc;
-    K3Host kh;
-    if (int rc = k3_layout(ctx, run_len, genome_run_off, n, k, kh)) return rc;
+    K3Run r;
+    if (int rc = k3_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, r)) return rc;
     if (n == 0) return D2G_OK;
-    hipStream_t s = sk->stream;
-    if (int rc = k3_run(ctx, st, s, km, nblk, kh, n, xormask, sketchsize, count_threshold, false)) return rc;
-    D2G_HIP(ctx, hipMemcpyAsync(sig_out, st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToHost, s));
-    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out, st->d_tw, n * sizeof(double), hipMemcpyDeviceToHost, s));
-    return k3_check_status(ctx, st, s);
+    r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
+    if (int rc = r.run(K3Mode::Sketch)) return rc;
+    D2G_HIP(ctx, hipMemcpyAsync(sig_out, r.st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToHost, r.s));
+    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out, r.st->d_tw, n * sizeof(double), hipMemcpyDeviceToHost, r.s));
+    return k3_check_status(ctx, r.st, r.s);
 }
 
 int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
@@ -1645,18 +1657,19 @@ int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pa
     D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->k3) { ctx->k3 = new (std::nothrow) d2g_k3_state(); if (!ctx->k3) return D2G_ERR_NOMEM; ctx->k3->ctx = ctx; }
-    d2g_k3_state *st = ctx->k3;
+    if (!ctx->k3) ctx->k3 = new (std::nothrow) d2g_k3_state();
+    if (!ctx->k3) return D2G_ERR_NOMEM;
     const size_t n = plan->n;
-    K3Host kh;
-    if (int rc = k3_layout(ctx, plan->h_run_len.data(), plan->h_genome_run_off.data(), n, plan->k, kh)) return rc;
+    K3Run r;
+    r.ctx = ctx; r.st = ctx->k3; r.s = as_stream(stream); r.n = n;
+    if (int rc = k3_layout(ctx, plan->h_run_len.data(), plan->h_genome_run_off.data(), n, plan->k, r.kh)) return rc;
     if (n == 0) return D2G_OK;
-    hipStream_t s = as_stream(stream);
-    if (int rc = k3_run(ctx, st, s, d2g_plan_args(plan, packed_dev, canon), plan->nblk, kh, n, xormask, sketchsize,
-                        count_threshold, false)) return rc;
-    D2G_HIP(ctx, hipMemcpyAsync(sig_out_dev, st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToDevice, s));
-    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out_dev, st->d_tw, n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    return k3_check_status(ctx, st, s);
+    r.km = d2g_plan_args(plan, packed_dev, canon); r.nblk = plan->nblk;
+    r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
+    if (int rc = r.run(K3Mode::Sketch)) return rc;
+    D2G_HIP(ctx, hipMemcpyAsync(sig_out_dev, r.st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToDevice, r.s));
+    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out_dev, r.st->d_tw, n * sizeof(double), hipMemcpyDeviceToDevice, r.s));
+    return k3_check_status(ctx, r.st, r.s);
 }
 
 int d2g_bmh_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
@@ -1677,21 +1690,16 @@ int d2g_sketcher_run_distinct(d2g_sketcher *sk, const uint8_t *packed, size_t pa
     if (!sk) return D2G_ERR_INVALID;
     d2g_ctx *ctx = sk->ctx;
     D2G_CHECK(ctx, ndistinct_out != nullptr || n == 0, "null output");
-    d2g_k3_state *st = k3_state_of(sk);
-    if (!st) return D2G_ERR_NOMEM;
-    KmerArgs km;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, &km,
-                                    &nblk, nullptr)) return rc;
-    K3Host kh;
-    if (int rc = k3_layout(ctx, run_len, genome_run_off, n, k, kh)) return rc;
+    K3Run r;
+    if (int rc = k3_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, r)) return rc;
     if (n == 0) return D2G_OK;
-    hipStream_t s = sk->stream;
-    if (int rc = k3_run(ctx, st, s, km, nblk, kh, n, xormask, 1, 0.0, true, true)) return rc;
-    if (int rc = k3_check_status(ctx, st, s)) return rc;
+    const K3Host &kh = r.kh;
+    r.xormask = xormask;
+    if (int rc = r.run(K3Mode::Distinct)) return rc;
+    if (int rc = k3_check_status(ctx, r.st, r.s)) return rc;
     std::vector<uint32_t> nd(kh.TB);
-    D2G_HIP(ctx, hipMemcpyAsync(nd.data(), st->d_bucket_nd, kh.TB * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    D2G_HIP(ctx, hipStreamSynchronize(s));
+    D2G_HIP(ctx, hipMemcpyAsync(nd.data(), r.st->d_bucket_nd, kh.TB * sizeof(uint32_t), hipMemcpyDeviceToHost, r.s));
+    D2G_HIP(ctx, hipStreamSynchronize(r.s));
     for (size_t g = 0; g < n; ++g) {
         uint64_t t = 0;
         for (uint32_t tb = kh.gtab[n + g]; tb < kh.gtab[n + g + 1]; ++tb) t += nd[tb];
@@ -1723,19 +1731,14 @@ int d2g_kmer_count(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, con
     if (int rc = d2g_sketcher_create(ctx, &sk)) return rc;
     int rc = D2G_OK;
     do {
-        d2g_k3_state *st = k3_state_of(sk);
-        if (!st) { rc = D2G_ERR_NOMEM; break; }
-        KmerArgs km;
-        size_t nblk = 0;
-        if ((rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, &km,
-                                     &nblk, nullptr))) break;
-        K3Host kh;
-        if ((rc = k3_layout(ctx, run_len, genome_run_off, n, k, kh))) break;
+        K3Run r;
+        if ((rc = k3_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, r))) break;
+        const K3Host &kh = r.kh; d2g_k3_state *st = r.st;
         for (size_t g = 0; g <= n; ++g) genome_off_out[g] = 0;
         if (n == 0) break;
-        hipStream_t s = sk->stream;
-        if ((rc = k3_run(ctx, st, s, km, nblk, kh, n, xormask, 1, count_threshold, true))) break;
-        if ((rc = k3_check_status(ctx, st, s))) break;
+        r.xormask = xormask; r.thr = count_threshold;
+        if ((rc = r.run(K3Mode::Count))) break;
+        if ((rc = k3_check_status(ctx, st, r.s))) break;
         // compact the per-bucket prefixes on the host (utility entry point, not the sketch path)
         std::vector<uint32_t> nd(kh.TB);
         std::vector<uint64_t> boff((size_t)kh.TB + 1);
@@ -1790,8 +1793,6 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
     std::vector<uint64_t> blo, guess(nsets);
     std::vector<double> tw(nsets, 0.);
     const double lnm = std::log((double)m);
-    double scale = 1.0;
-    if (const char *e = ctx->tune.get("D2G_K3_GUESS_SCALE")) { const double v = std::atof(e); if (v > 0.) scale = v; }
     for (size_t i = 0; i < nsets; ++i) {
         const uint64_t lo = set_off[i], hi = set_off[i + 1];
         double t = 0.;
@@ -1803,7 +1804,7 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
             } else if (w != w) { ctx->last_error = "BagMinHash weight is NaN"; return D2G_ERR_INVALID; }
         }
         tw[i] = t;
-        const double gv = t > 0. ? scale * bmh_guess(t, (double)m, lnm) : 0.;
+        const double gv = t > 0. ? ctx->k3_tune.guess_scale * bmh_guess(t, (double)m, lnm) : 0.;
         std::memcpy(&guess[i], &gv, 8);
         for (uint64_t e = lo; e < hi; e += chunk) {
             bset.push_back((uint32_t)i); blo.push_back(e); bcnt.push_back((uint32_t)std::min<uint64_t>(chunk, hi - e));
@@ -1873,9 +1874,7 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
     if (owner_out) K3_TRY(hipMemcpy(owner_out, d_arg, nsets * m * 8, hipMemcpyDeviceToHost));
     std::memcpy(total_weight_out, tw.data(), nsets * sizeof(double));
 #undef K3_TRY
-    if (status == 2) { ctx->last_error = "BagMinHash weight outside (0, 2^53]"; rc = D2G_ERR_INVALID; }
-    if (status == 3) { ctx->last_error = "internal: BagMinHash process stack overflow"; rc = D2G_ERR_INTERNAL; }
-    return rc;
+    return k3_status_error(ctx, status);
 }
 
 }  // extern "C"

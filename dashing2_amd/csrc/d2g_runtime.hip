@@ -1,5 +1,6 @@
 // d2g_runtime.hip -- context, device memory and timing plumbing of libd2g.
 #include "d2g_internal.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -39,12 +40,36 @@ d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t) {
     return v;
 }
 
+d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t) {
+    d2g_k3_tuning v;
+    if (const char *e = t.get("D2G_K3_COMPACT")) v.compact = e[0] == '1';
+    if (const char *e = t.get("D2G_K3_LIGHT")) v.light = !(e[0] == '0');
+    if (const char *e = t.get("D2G_K3_L1BITS")) { const int d = std::atoi(e); if (d >= 0 && d <= K3_MAXBBITS) v.l1bits = (uint32_t)d; }
+    if (const char *e = t.get("D2G_K3_BUCKET_KEYS")) { const long d = std::atol(e); if (d >= 1) v.bucket_keys = (uint64_t)d; }
+    if (const char *e = t.get("D2G_K3_SUB_KEYS")) { const long d = std::atol(e); if (d >= 1) v.sub_keys = (uint64_t)d; }
+    if (const char *e = t.get("D2G_K3_SPLIT_MIN")) { const long d = std::atol(e); if (d >= 1) v.split_min = (uint64_t)d; }
+    if (const char *e = t.get("D2G_K3_SUBBATCH")) { const int d = std::atoi(e); if (d >= 1 && d <= 8) v.subbatch = (size_t)d; }
+    if (const char *e = t.get("D2G_K3_ROUND_KEYS")) { const int d = std::atoi(e); if (d >= 1 && d <= K3_ROUND_KEYS) v.round_keys = (uint32_t)d; }
+    if (const char *e = t.get("D2G_K3_GUESS_SCALE")) { const double d = std::atof(e); if (d > 0.) v.guess_scale = d; }
+    if (const char *e = t.get("D2G_K3_GRID_PER_CU")) { const int d = std::atoi(e); if (d >= 1 && d <= 256) v.grid_per_cu = (size_t)d; }
+    if (const char *e = t.get("D2G_K3_GQ_SCALE")) { v.gq_scale_set = true; v.gq_scale = std::max(0.0, std::atof(e)); }
+    v.gq_slack = v.gq_scale_set ? 1 : v.grid_per_cu > 24 ? 256 : 1024;
+    return v;
+}
+
+void d2g_tuning_resolve(d2g_ctx *c) {
+    d2g_tuning_load(c->tune);
+    c->k2 = d2g_k2_tuning_resolve(c->tune);
+    c->k3_tune = d2g_k3_tuning_resolve(c->tune);
+    c->mgpu_chunks = 0;
+    if (const char *e = c->tune.get("D2G_MGPU_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= MG_MAX_CHUNKS) c->mgpu_chunks = v; }
+}
+
 extern "C" {
 
 int d2g_ctx_reload_tuning(d2g_ctx *c) {
     if (!c) return D2G_ERR_INVALID;
-    d2g_tuning_load(c->tune);
-    c->k2 = d2g_k2_tuning_resolve(c->tune);
+    d2g_tuning_resolve(c);
     return D2G_OK;
 }
 
@@ -86,8 +111,7 @@ int d2g_ctx_create(int device, d2g_ctx **out) {
     if (!c) return D2G_ERR_NOMEM;
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
-    d2g_tuning_load(c->tune);
-    c->k2 = d2g_k2_tuning_resolve(c->tune);
+    d2g_tuning_resolve(c);
     *out = c;
     return D2G_OK;
 }

@@ -126,6 +126,25 @@ def test_bmh_from_weighted_matches_oracle(gpu_ctx, d2g, oracle):
         gpu_ctx.bmh_from_weighted(np.array([1], np.uint64), np.array([2.0 ** 60]), np.array([0, 1], np.uint64), 16)
 
 
+def test_bmh_from_weighted_redo_passes_match_oracle(gpu_ctx, oracle, monkeypatch):
+    """D2G_K3_GUESS_SCALE=0.001 makes the first guess of every set's bound a thousand times too small, so the explicit-weights
+    entry point has to walk its sets again under raised guesses (its own redo loop, the switch's second reader).  Sets of
+    0, 7 and 2049 elements: 2049 is the smallest set that spans two workgroups of the 2048-element chunking."""
+    monkeypatch.setenv("D2G_K3_GUESS_SCALE", "0.001")
+    rng = np.random.default_rng(11)
+    S = 64
+    sets = [(rng.integers(0, 2 ** 63, n).astype(np.uint64), rng.random(n) * 10 ** rng.integers(-3, 6, n).astype(np.float64))
+            for n in (0, 7, 2049)]
+    ids = np.concatenate([s[0] for s in sets])
+    w = np.concatenate([s[1] for s in sets])
+    off = np.cumsum([0] + [len(s[0]) for s in sets]).astype(np.uint64)
+    sig, tw = gpu_ctx.bmh_from_weighted(ids, w, off, S)
+    for i, (si, wi) in enumerate(sets):
+        esig, etw = oracle.bmh_from_weighted(si, wi, S)
+        np.testing.assert_array_equal(sig[i].view(np.uint64), esig.view(np.uint64), err_msg=f"set {i}")
+        assert abs(tw[i] - etw) <= 1e-9 * max(1.0, etw)      # double sums in a different order
+
+
 def test_k3_multi_round_buckets_and_redo_paths(d2g, oracle, tmp_path):
     """fresh processes with the test hooks: D2G_K3_ROUND_KEYS=64 makes every bucket need several
     table rounds (the path genomes above ~5.7 Mbp take), D2G_K3_GUESS_SCALE=1e-3 makes the guessed
