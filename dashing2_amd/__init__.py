@@ -14,6 +14,7 @@ from .capi import (  # noqa: F401
     wang_hash, seed_mask, oph_xor_const, oph_m, oph_finalize, densify, epilogue_lut,
     epilogue_gtlt, epilogue_neq, host_epilogue_ut, operand_layout, sparse_bin_geometry, ut_count, ut_partition,
     regs_truncate, epilogue_trunc_neq, epilogue_trunc_gtlt, host_epilogue_trunc_ut, host_epilogue_trunc_rect,
+    knn_finish, KnnOverflow, TIME_KNN,
 )
 
 __all__ = [
@@ -24,4 +25,5 @@ __all__ = [
     "wang_hash", "seed_mask", "oph_xor_const", "oph_m", "oph_finalize", "densify", "epilogue_lut",
     "epilogue_gtlt", "epilogue_neq", "host_epilogue_ut", "operand_layout", "sparse_bin_geometry", "ut_count", "ut_partition",
     "regs_truncate", "epilogue_trunc_neq", "epilogue_trunc_gtlt", "host_epilogue_trunc_ut", "host_epilogue_trunc_rect",
+    "knn_finish", "KnnOverflow", "TIME_KNN",
 ]

@@ -18,6 +18,7 @@ BITSLICE_OPS_PER_GROUP_EXTRA = 1
 
 
 TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0 = 2, 4, 8, 16, 32          # include/d2g.h D2G_TIME_*
+TIME_KNN = 64
 
 
 class D2GError(RuntimeError):
@@ -171,6 +172,10 @@ SIGNATURES = {
     "d2g_cmp_set_create_codes": (_int, [_vp, _vp, _sz, _sz, _int, C.POINTER(_vp)]),
     "d2g_cmp_set_operand_bytes": (_sz, [_vp]),
     "d2g_cmp_dist_trunc_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _int, _vp]),
+    "d2g_cmp_knn_dev": (_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "d2g_knn_finish": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _int, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
+    "d2g_cmp_set_knn": (_int, [_vp, _vp, _sz, _sz, _vp, _int, _sz, _dbl, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "d2g_cmp_knn": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _sz, _dbl, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
 }
 
 
@@ -340,6 +345,39 @@ def host_epilogue_trunc_rect(ca, cb, cards, N, S, a0, a1, b0, b1, measure=SIMILA
     if rc:
         raise D2GError(rc)
     return out
+
+
+class KnnOverflow(ValueError):
+    """d2g_knn_finish met rows whose true count exceeds the slots they were given"""
+    def __init__(self, rows):
+        self.rows = rows
+        super().__init__(f"{rows} row(s) hold more candidates than their slots: re-run them with a cap that fits")
+
+
+def knn_finish(rowcnt, ids, counts, cap, lut, isdist=False):
+    """candidate lists (rowcnt [n], ids / counts [n][cap]) -> CSR (indptr u64 [n+1], indices u32, data f32) in the reference's order"""
+    rowcnt = np.ascontiguousarray(rowcnt, np.uint32)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    counts = np.ascontiguousarray(counts, np.uint32)
+    lut = np.ascontiguousarray(lut, np.float32)
+    n = rowcnt.size
+    assert ids.size >= n * cap and counts.size >= n * cap
+    indptr = np.zeros(n + 1, np.uint64)
+    need, over = _sz(), _sz()
+    rc = lib().d2g_knn_finish(_np_ptr(rowcnt), _np_ptr(ids), _np_ptr(counts), n, cap, _np_ptr(lut), lut.size - 1, int(bool(isdist)),
+                              _np_ptr(indptr), None, None, 0, C.byref(need), C.byref(over))
+    if over.value:
+        raise KnnOverflow(over.value)
+    if rc not in (0, -4):
+        raise D2GError(rc)
+    indices = np.empty(need.value, np.uint32)
+    data = np.empty(need.value, np.float32)
+    if need.value:
+        rc = lib().d2g_knn_finish(_np_ptr(rowcnt), _np_ptr(ids), _np_ptr(counts), n, cap, _np_ptr(lut), lut.size - 1, int(bool(isdist)),
+                                  _np_ptr(indptr), _np_ptr(indices), _np_ptr(data), need.value, None, None)
+        if rc:
+            raise D2GError(rc)
+    return indptr, indices, data
 
 
 def operand_layout(N, S):
@@ -673,6 +711,17 @@ class Context:
                                           int(multiset_space), algo, nthreads, _np_ptr(out)))
         return out
 
+    def cmp_knn(self, sig_bits_host, K=0, threshold=0.0, measure=SIMILARITY, k=31, multiset_space=False, r0=0, r1=None,
+                algo=CMP_AUTO, cap=0, band_rows=0):
+        """nearest neighbours of rows [r0,r1): top-K (all ties with the K-th best kept) or every pair at / beyond `threshold`;
+        returns CSR (indptr u64, indices u32, data f32), best first inside a row"""
+        a = np.ascontiguousarray(sig_bits_host)
+        assert a.dtype.itemsize == 8 and a.ndim == 2
+        N, S = a.shape
+        r1 = N if r1 is None else r1
+        return _knn_csr(self, r1 - r0, K, lambda ip, ix, dt, oc, need: lib().d2g_cmp_knn(
+            self._h, _np_ptr(a), N, S, r0, r1, measure, k, int(multiset_space), algo, K, float(threshold), cap, band_rows, ip, ix, dt, oc, need))
+
     # -- raw device memory (tests / bench without torch) ------------------------
     def malloc(self, nbytes):
         p = _vp()
@@ -689,6 +738,21 @@ class Context:
     def d2h(self, arr, dptr, stream=None):
         assert arr.flags["C_CONTIGUOUS"]
         self._check(lib().d2g_memcpy_d2h(self._h, _np_ptr(arr), dptr, arr.nbytes, stream))
+
+
+def _knn_csr(ctx, nrows, K, call):
+    """runs call(indptr, indices, data, out_cap, &needed) with a first guess of the output size and once more if it was short"""
+    indptr = np.zeros(nrows + 1, np.uint64)
+    guess = max(1, nrows * (2 * K + 16 if K else 64))
+    for _ in range(2):
+        indices, data = np.empty(guess, np.uint32), np.empty(guess, np.float32)
+        need = _sz()
+        rc = call(_np_ptr(indptr), _np_ptr(indices), _np_ptr(data), guess, C.byref(need))
+        if rc != -4:        # D2G_ERR_NOMEM with `need` set: the arrays were too small
+            break
+        guess = need.value
+    ctx._check(rc)
+    return indptr, indices[:need.value].copy(), data[:need.value].copy()
 
 
 class Sketcher:
@@ -920,6 +984,21 @@ class CmpSet:
 
     def eqcount_rect_dev(self, out_dev_ptr, a0, a1, b0, b1, stream=None):
         self.ctx._check(lib().d2g_cmp_eqcount_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, out_dev_ptr, stream))
+
+    def knn_dev(self, rowcnt_dev_ptr, ids_dev_ptr, counts_dev_ptr, cap, K=0, min_count=0, cls_dev_ptr=None, r0=0, r1=None,
+                band_rows=0, stream=None):
+        """d2g_cmp_knn_dev: per-row selection on the device (K == 0: threshold mode with min_count as the threshold)"""
+        r1 = self.N if r1 is None else r1
+        self.ctx._check(lib().d2g_cmp_knn_dev(self.ctx._h, self._h, r0, r1, K, min_count, cls_dev_ptr, cap, rowcnt_dev_ptr, ids_dev_ptr,
+                                              counts_dev_ptr, band_rows, stream))
+
+    def knn(self, lut, isdist=False, K=0, threshold=0.0, r0=0, r1=None, cap=0, band_rows=0):
+        """d2g_cmp_set_knn: CSR (indptr, indices, data) of rows [r0,r1) for the value table lut[S+1]"""
+        lut = np.ascontiguousarray(lut, np.float32)
+        assert lut.size == self.S + 1
+        r1 = self.N if r1 is None else r1
+        return _knn_csr(self.ctx, r1 - r0, K, lambda ip, ix, dt, oc, need: lib().d2g_cmp_set_knn(
+            self.ctx._h, self._h, r0, r1, _np_ptr(lut), int(bool(isdist)), K, float(threshold), cap, band_rows, ip, ix, dt, oc, need))
 
     def gtlt_rect_dev(self, gt_dev_ptr, lt_dev_ptr, a0, a1, b0, b1, stream=None):
         self.ctx._check(lib().d2g_cmp_gtlt_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, gt_dev_ptr, lt_dev_ptr, stream))

@@ -439,6 +439,39 @@ int d2g_ut_partition(size_t N, int nparts, size_t *bounds) {
     return D2G_OK;
 }
 
+// candidate lists of the selection kernel -> CSR in the order of the reference's neighbour lists: std::sort of (mult * value, id)
+// pairs (src/index_build.h:16 pqueue::sort, mult = -1 for similarities: index_build.cpp:184), then the sign flip of
+// src/cmp_core.cpp:787-793 -- the values written are the plain table entries.
+int d2g_knn_finish(const uint32_t *rowcnt, const uint32_t *ids, const uint32_t *counts, size_t nrows, size_t cap, const float *lut,
+                   size_t S, int isdist, uint64_t *indptr, uint32_t *indices, float *data, size_t out_cap, size_t *nnz_needed,
+                   size_t *overflow_rows) {
+    if (!indptr || !lut || (nrows && !rowcnt)) return D2G_ERR_INVALID;
+    size_t over = 0, nnz = 0;
+    for (size_t i = 0; i < nrows; ++i) { over += rowcnt[i] > cap; nnz += rowcnt[i]; }
+    if (overflow_rows) *overflow_rows = over;
+    if (over) return D2G_ERR_INVALID;
+    if (nnz && (!ids || !counts)) return D2G_ERR_INVALID;
+    for (size_t i = 0; i < nrows; ++i)
+        for (size_t e = 0; e < rowcnt[i]; ++e) if (counts[i * cap + e] > S) return D2G_ERR_INVALID;
+    indptr[0] = 0;
+    for (size_t i = 0; i < nrows; ++i) indptr[i + 1] = indptr[i] + rowcnt[i];
+    if (nnz_needed) *nnz_needed = nnz;
+    if (nnz > out_cap) return D2G_ERR_NOMEM;
+    if (nnz && (!indices || !data)) return D2G_ERR_INVALID;
+    const float mult = isdist ? 1.f : -1.f;
+    std::vector<std::pair<float, uint32_t>> row;
+    for (size_t i = 0; i < nrows; ++i) {
+        const size_t n = rowcnt[i];
+        row.resize(n);
+        for (size_t e = 0; e < n; ++e) row[e] = {mult * lut[counts[i * cap + e]], ids[i * cap + e]};
+        std::sort(row.begin(), row.end());
+        uint32_t *oi = indices + indptr[i];
+        float *od = data + indptr[i];
+        for (size_t e = 0; e < n; ++e) { oi[e] = row[e].second; od[e] = mult * row[e].first; }
+    }
+    return D2G_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

@@ -201,7 +201,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     }
     if (what & D2G_WARM_K0) d2g_warm_k0();
     if (what & D2G_WARM_K1) d2g_warm_k1();
-    if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); }
+    if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); d2g_warm_knn(); }
     if (what & D2G_WARM_K3) d2g_warm_k3();
     return D2G_OK;
 }
@@ -215,7 +215,7 @@ int d2g_device_name(int device, char *buf, size_t cap) {
 
 int d2g_set_timing(d2g_ctx *c, int enabled) {
     if (!c) return D2G_ERR_INVALID;
-    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3) : (enabled & ~1);
+    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN) : (enabled & ~1);
     return D2G_OK;
 }
 
@@ -227,6 +227,7 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;
     else if (!std::strcmp(which, "k3")) e = &c->ev_k3;
     else if (!std::strcmp(which, "k0")) e = &c->ev_k0;
+    else if (!std::strcmp(which, "knn")) e = &c->ev_knn;
     D2G_CHECK(c, e != nullptr, "d2g_kernel_ms: unknown kernel name");
     D2G_HIP(c, hipSetDevice(c->device));
     double sum = 0;

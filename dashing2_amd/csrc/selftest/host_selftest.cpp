@@ -98,6 +98,24 @@ int main() {
             for (int p = 0; p < parts; ++p) { REQUIRE(b[p] <= b[p + 1]); tot += d2g_ut_count(N, b[p], b[p + 1]); }
             REQUIRE(tot == N * (N - 1) / 2);
         }
+    // ---- neighbour lists: exactly-sized arrays (a read or write past a row's entries or past the outputs is an ASan report)
+    {
+        const size_t S = 8, n = 4, cap = 3;
+        const float lut[S + 1] = {0.f, 0.125f, 0.25f, 0.25f, 0.5f, 0.625f, 0.75f, 0.875f, 1.f};
+        const std::vector<uint32_t> rowcnt = {3, 0, 1, 2}, ids = {9, 4, 7, 0, 0, 0, 2, 0, 0, 5, 1}, cts = {2, 8, 3, 0, 0, 0, 1, 0, 0, 4, 4};   // the last row's third slot does not exist
+        std::vector<uint64_t> indptr(n + 1);
+        std::vector<uint32_t> indices(6);
+        std::vector<float> data(6);
+        size_t need = 0, over = 0;
+        REQUIRE(d2g_knn_finish(rowcnt.data(), ids.data(), cts.data(), n, cap, lut, S, 0, indptr.data(), nullptr, nullptr, 0, &need, &over) == D2G_ERR_NOMEM);
+        REQUIRE(need == 6 && over == 0 && indptr[4] == 6);
+        REQUIRE(d2g_knn_finish(rowcnt.data(), ids.data(), cts.data(), n, cap, lut, S, 0, indptr.data(), indices.data(), data.data(), 6, &need, &over) == D2G_OK);
+        REQUIRE(indices[0] == 4 && indices[1] == 7 && indices[2] == 9 && data[0] == 1.f && data[1] == 0.25f && data[2] == 0.25f && indices[4] == 1 && indices[5] == 5);
+        REQUIRE(d2g_knn_finish(rowcnt.data(), ids.data(), cts.data(), n, cap, lut, S, 1, indptr.data(), indices.data(), data.data(), 6, nullptr, nullptr) == D2G_OK);
+        REQUIRE(indices[0] == 7 && indices[1] == 9 && indices[2] == 4);
+        const std::vector<uint32_t> big = {4, 0, 1, 2};
+        REQUIRE(d2g_knn_finish(big.data(), ids.data(), cts.data(), n, cap, lut, S, 0, indptr.data(), indices.data(), data.data(), 6, &need, &over) == D2G_ERR_INVALID && over == 1);
+    }
     REQUIRE(d2g_wang_hash(133348) != 0 && d2g_seed_mask(0) == 0 && d2g_seed_mask(5) != 0);
     std::printf("host selftest OK\n");
     return 0;

@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -57,7 +57,13 @@ void sketch_usage() {
 void cmp_usage() {
     std::fprintf(stderr, "dashing2 cmp <opts> [fastas... (optional)]\n"
                          "--presketched\t To compute distances using a pre-sketched method (e.g., dashing2 sketch -o path), "
-                         "use this flag and pass in a single positional argument.\n");
+                         "use this flag and pass in a single positional argument.\n"
+                         "--topk/--top-k K\t Nearest neighbours instead of a matrix: for every sketch its K best (all ties with the K-th best are kept;\n"
+                         "\t\t a similarity of 0 is never a neighbour), best first, selected on the GPU -- always exhaustive (the reference's EXACT_KNN=1).\n"
+                         "--similarity-threshold T\t ... or every pair whose similarity is at least T (with --mash-distance: whose distance is at most T).\n"
+                         "\t\t Output: one line per sketch `name<TAB>neighbour:value...`, or with --binary-output CSR: u64 nids, u64 nnz,\n"
+                         "\t\t u64 indptr[nids+1], u32 indices[nnz], f32 data[nnz].  Similarity and --mash-distance, full 8-byte registers, one GPU;\n"
+                         "\t\t not with -Q, --square, --phylip, --fastcmp <4|2|1>.\n");
     sketch_usage();
 }
 
@@ -131,6 +137,12 @@ int parse_options(int argc, char **argv, Options &o) {
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
     std::vector<struct option> all(longopts, longopts + sizeof(longopts) / sizeof(longopts[0]) - 1);
+    if (o.is_cmp) {                                           // sparse outputs (options.h:73-75): `cmp` only in this build
+        all.push_back({"topk", required_argument, 0, OPT_TOPK});
+        all.push_back({"top-k", required_argument, 0, OPT_TOPK});
+        all.push_back({"similarity-threshold", required_argument, 0, OPT_SIMTHRESH});
+    }
+    bool saw_square = false, saw_phylip = false, gave_topk = false, gave_thresh = false;
     std::set<std::string> have;
     for (auto &x : all) have.insert(x.name);
     static const std::set<std::string> with_arg = {"topk", "top-k", "similarity-threshold", "fastcmp", "regsize", "regbytes",
@@ -163,8 +175,8 @@ int parse_options(int argc, char **argv, Options &o) {
             case OPT_CMPOUT: o.cmpout = optarg; break;
             case OPT_OUTPREF: o.outprefix = optarg; break;
             case OPT_BINARY: o.of = MACHINE_READABLE; break;
-            case OPT_PHYLIP: o.ok = PHYLIP; break;
-            case OPT_ASYM: o.ok = ASYMMETRIC_ALL_PAIRS; break;
+            case OPT_PHYLIP: o.ok = PHYLIP; saw_phylip = true; break;
+            case OPT_ASYM: o.ok = ASYMMETRIC_ALL_PAIRS; saw_square = true; break;
             case OPT_ISZ: o.measure = D2G_INTERSECTION; break;
             case OPT_USZ: o.measure = D2G_UNION_SIZE; break;
             case OPT_MASH: o.measure = D2G_POISSON_LLR; break;
@@ -193,6 +205,8 @@ int parse_options(int argc, char **argv, Options &o) {
                 }
                 o.regbytes = int(nb);
             } break;
+            case OPT_TOPK: o.topk = std::atoi(optarg); gave_topk = true; break;                             // options.h:308
+            case OPT_SIMTHRESH: o.min_similarity = std::atof(optarg); gave_thresh = true; break;       // options.h:309
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
             case OPT_UNSUPPORTED:
@@ -236,6 +250,30 @@ int parse_options(int argc, char **argv, Options &o) {
     if (o.w > o.k) {
         std::fprintf(stderr, "dashing2 (MI355X): windowed minimizers (-w > k) are outside this build's hot-path scope.\n");
         return 1 + 1;
+    }
+    if (o.is_cmp && (gave_topk || gave_thresh)) {
+        if (o.topk > 0 && o.min_similarity > 0.) {             // Dashing2DistOptions::validate, cmp_main.h:102-104
+            std::fprintf(stderr, "Exception invalid: nn > 0 and minsim > 0. Pick either top-k or minimum similarity. (Can't do both.)\n");
+            return 1 + 1;
+        }
+        const char *why = nullptr;
+        if (gave_topk && gave_thresh) why = "--topk and --similarity-threshold together, one of them without a positive argument";
+        else if (gave_topk && o.topk < 1) why = "--topk needs K >= 1";
+        else if (gave_thresh && !(o.min_similarity > 0.)) why = "--similarity-threshold needs T > 0";
+        else if (!o.qfile.empty()) why = "nearest neighbours of a query panel (-Q)";
+        else if (saw_square) why = "nearest neighbours together with --square / --asymmetric-all-pairs";
+        else if (saw_phylip) why = "nearest neighbours together with --phylip";
+        else if (o.regbytes < 8) why = "nearest neighbours of truncated registers (--fastcmp <4|2|1>)";
+        else if (o.measure != D2G_SIMILARITY && o.measure != D2G_POISSON_LLR)
+            why = "nearest neighbours by a cardinality-dependent measure (containment, symmetric containment, intersection, union size): its value is not a function of the equality count";
+        else if (!o.presketched && o.sspace == SPACE_SET && (o.sketchsize & (o.sketchsize - 1)) != 0)
+            why = "nearest neighbours with a sketch size that is not a power of two in set space: its value needs (gt, lt) counts, not the equality count";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): %s is outside the hot-path scope of this build "
+                                 "(--topk K >= 1 or --similarity-threshold T > 0; similarity or --mash-distance; 8-byte registers; one matrix).\n", why);
+            return 1 + 1;
+        }
+        o.ok = gave_topk ? KNN_GRAPH : NN_GRAPH_THRESHOLD;
     }
     return 0;
 }

@@ -37,6 +37,8 @@ struct Options {
     std::string gpu_stats;                // --gpu-stats FILE (not a reference flag): machine-readable record of the run (SURVEY 5 "Metrics")
     int regbytes = 8;                     // --fastcmp/--regsize/--regbytes <8|4|2|1> (options.h:321-327): below 8 the comparison runs on truncated registers (cmp_core.cpp:209-322)
     bool bbit_sigs = false;               // --bbit-sigs (options.h:101): b-bit truncation instead of the logarithmic (setsketch) one; no effect at 8 bytes
+    int topk = -1;                        // cmp --topk/--top-k K (options.h:308): ok = KNN_GRAPH, the K nearest neighbours of every sketch, ties with the K-th kept
+    double min_similarity = -1.;          // cmp --similarity-threshold T (options.h:309): ok = NN_GRAPH_THRESHOLD, every pair at T or beyond
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -112,7 +112,7 @@ struct Stats {
     }
 };
 Stats g_stats;
-constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3;
+constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN;
 
 // D2G_DEVICES = "all" | "0,1,2": the GPUs a job may spread over -- `sketch` deals its input groups to them (no collectives),
 // `cmp` shards the rows of the matrix (one exchange).  Default: the one device D2G_DEVICE names.  A list that repeats
@@ -990,6 +990,116 @@ bool cmp_core_multi(const Options &o, Result &res, const std::vector<int> &devs,
     return true;
 }
 
+// ------------------------------------------------------------------------------------ cmp: nearest neighbours
+// The reason a --topk / --similarity-threshold job is outside this build's scope, or null.  Flag combinations are refused while the
+// options are parsed (d2_options.cpp); what is only known once the inputs are (the sketch space and size of --presketched files) here.
+const char *knn_refusal(const Options &o, size_t S) {
+    if (o.sspace == SPACE_SET && (S & (S - 1)) != 0)
+        return "nearest neighbours with a sketch size that is not a power of two in set space: its value needs (gt, lt) counts, not the equality count";
+    if (o.sspace == SPACE_PSET) return "nearest neighbours of ProbMinHash sketches";
+    return nullptr;
+}
+[[noreturn]] void knn_refuse(const char *why) {
+    std::fprintf(stderr, "dashing2 (MI355X): %s is outside the hot-path scope of this build.\n", why);
+    std::exit(1);
+}
+// the sketch size a --presketched job will find in its file(s) (load_results), from their sizes alone; 0: unknown
+size_t presketched_sketchsize(const Options &o) {
+    if (o.paths.empty()) return 0;
+    if (o.paths.size() > 1) { const size_t fs = filesize(o.paths.front()); return fs >= 8 ? (fs - 8) / 8 : 0; }
+    uint64_t hdr[2] = {0, 0};
+    std::FILE *fp = std::fopen(o.paths.front().c_str(), "rb");
+    if (!fp) return 0;
+    const bool ok = std::fread(hdr, 8, 2, fp) == 2;
+    std::fclose(fp);
+    return ok ? size_t(hdr[1]) : 0;
+}
+
+// emit_neighbors, src/emitnn.cpp:12-52: CSR (u64 nids, u64 nnz, u64 indptr[nids+1], u32 indices[nnz], f32 data[nnz]) or one text line
+// per sketch.  fmt's "{:0.8g}" of a float is printf's "%.8g" of the same value by fmt's documented semantics (PARITY UNPINNED: the
+// reference's fmt submodule is absent).
+void emit_neighbors(const Options &o, const Result &res, const std::vector<uint64_t> &indptr, const std::vector<uint32_t> &indices,
+                    const std::vector<float> &data) {
+    const std::string outp = (o.cmpout.empty() || o.cmpout.front() == '-') ? "/dev/stdout" : o.cmpout;
+    std::FILE *fp = outp == "/dev/stdout" ? stdout : std::fopen(outp.c_str(), "wb");
+    if (!fp) die("Failed to open file " + outp + " for writing");
+    const size_t ns = indptr.size() - 1, nnz = indices.size();
+    bool good = true;
+    if (o.of == HUMAN_READABLE) {
+        std::string text = "#Collection\tNeighbor lists -- name:distance, separated by tabs\n";
+        char buf[64];
+        for (size_t i = 0; i < ns; ++i) {
+            text += res.names[i];
+            for (uint64_t e = indptr[i]; e < indptr[i + 1]; ++e) {
+                text += '\t'; text += res.names[indices[e]]; text += ':';
+                text.append(buf, size_t(std::snprintf(buf, sizeof buf, "%.8g", double(data[e]))));
+            }
+            text += '\n';
+            if (text.size() >= (size_t(1) << 22) || i + 1 == ns) { good = good && std::fwrite(text.data(), 1, text.size(), fp) == text.size(); text.clear(); }
+        }
+        if (!text.empty()) good = good && std::fwrite(text.data(), 1, text.size(), fp) == text.size();
+    } else {
+        const uint64_t dims[2] = {uint64_t(ns), uint64_t(nnz)};
+        good = std::fwrite(dims, 8, 2, fp) == 2 && std::fwrite(indptr.data(), 8, indptr.size(), fp) == indptr.size() &&
+               std::fwrite(indices.data(), 4, nnz, fp) == nnz && std::fwrite(data.data(), 4, nnz, fp) == nnz;
+    }
+    good = good && std::fflush(fp) == 0;
+    if (fp != stdout) std::fclose(fp);
+    if (!good) die("Failed to write neighbor lists to " + outp);
+}
+
+// cmp_core.cpp:776-799 with build_exact_graph (index_build.cpp:166-228): the selection runs on the GPU (d2g_cmp_set_knn), only the
+// neighbours come back.  Always exhaustive; all ties with the K-th best are kept.
+void cmp_core_knn(const Options &o, const Result &res, d2g_ctx *ctx, const std::vector<float> &lut, double t_densify) {
+    const size_t ns = res.names.size(), S = o.sketchsize;
+    const bool isdist = o.measure == D2G_POISSON_LLR;          // distance(measure), cmp_main.h:44-49, for the two measures in scope
+    const bool topk = o.ok == KNN_GRAPH;
+    const size_t K = topk ? size_t(o.topk) : 0;
+    const double T = topk ? 0. : o.min_similarity;
+    const double t0 = now();
+    d2g_cmp_set *set = nullptr;
+    check(ctx, d2g_cmp_set_create(ctx, reinterpret_cast<const uint64_t *>(res.sigs()), ns, S, int(D2G_CMP_AUTO), &set), "d2g_cmp_set_create");
+    const double t_set = now();
+    std::vector<uint64_t> indptr(ns + 1, 0), ip;
+    std::vector<uint32_t> indices;
+    std::vector<float> data;
+    constexpr size_t ROWS = 16384;                             // rows per call: a chunk whose lists outgrow the guess is the only thing run twice
+    size_t nnz = 0, reruns = 0;
+    for (size_t r0 = 0; r0 < ns; r0 += ROWS) {
+        const size_t r1 = std::min(ns, r0 + ROWS), n = r1 - r0;
+        size_t room = n * (topk ? 2 * std::min(K, ns) + 16 : 64), need = 0;
+        ip.resize(n + 1);
+        for (int attempt = 0;; ++attempt) {
+            indices.resize(nnz + room); data.resize(nnz + room);
+            const int rc = d2g_cmp_set_knn(ctx, set, r0, r1, lut.data(), isdist, K, T, 0, 0, ip.data(), indices.data() + nnz, data.data() + nnz, room, &need);
+            if (rc == D2G_ERR_NOMEM && attempt == 0 && need > room) { room = need; ++reruns; continue; }
+            check(ctx, rc, "d2g_cmp_set_knn");
+            break;
+        }
+        for (size_t i = 0; i < n; ++i) indptr[r0 + i + 1] = nnz + ip[i + 1];
+        nnz += need;
+    }
+    indices.resize(nnz); data.resize(nnz);
+    const double t_sel = now();
+    emit_neighbors(o, res, indptr, indices, data);
+    const double t_emit = now();
+    if (o.verbosity) std::fprintf(stderr, "[d2g] cmp %s: %zu sketches x S=%zu: upload+prepare %.3fs, selection %.3fs (%zu neighbours, %zu chunk(s) run twice), emit %.3fs\n",
+                                  topk ? "--topk" : "--similarity-threshold", ns, S, t_set - t0, t_sel - t_set, nnz, reruns, t_emit - t_sel);
+    if (g_stats.on) {
+        const bool bs = d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE;
+        g_stats.raw("cmp", std::string("{\"sketches\": ") + std::to_string(ns) + ", \"sketchsize\": " + std::to_string(S) + ", \"values\": " + std::to_string(nnz) +
+                    ", \"shape\": " + (topk ? "\"topk\"" : "\"similarity threshold\"") + ", \"topk\": " + (topk ? std::to_string(K) : std::string("null")) +
+                    ", \"threshold\": " + (topk ? std::string("null") : Stats::numstr(T)) + ", \"algo\": " + (bs ? "\"bitslice\"" : "\"direct\"") +
+                    ", \"neighbours\": " + std::to_string(nnz) + ", \"chunks_run_twice\": " + std::to_string(reruns) +
+                    ", \"bytes_to_host\": " + Stats::numstr(8.0 * double(nnz) + 4.0 * double(ns)) +
+                    ", \"devices\": [{\"index\": " + std::to_string(o.device) + ", \"name\": " + Stats::esc(device_label(o.device)) + ", \"k2\": " + Stats::kernel_json(ctx, "k2") +
+                    ", \"knn\": " + Stats::kernel_json(ctx, "knn") + ", \"k2prep\": " + Stats::kernel_json(ctx, "k2prep") + "}]" +
+                    ", \"wall_s\": {\"densify_scan\": " + Stats::numstr(t_densify) + ", \"upload_prepare\": " + Stats::numstr(t_set - t0) +
+                    ", \"count_select_d2h_finish\": " + Stats::numstr(t_sel - t_set) + ", \"emit\": " + Stats::numstr(t_emit - t_sel) + "}}");
+    }
+    if (g_release_at_exit) d2g_cmp_set_destroy(set);
+}
+
 void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_core.cpp:615-751 (dense outputs)
     const size_t ns = res.names.size(), S = o.sketchsize;
     if (res.nsigs() != ns * S) die("Empty signatures; trying to compare but don't have any");
@@ -1024,6 +1134,14 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
     }
     const bool have_lut = !trunc && d2g_epilogue_lut(S, o.measure, o.k, multiset, lut.data()) == D2G_OK;
     const bool need_gtlt = trunc ? trunc_gtlt : (!multiset && (S & (S - 1)) != 0);
+    if (o.ok == KNN_GRAPH || o.ok == NN_GRAPH_THRESHOLD) {          // cmp_core.cpp:776-799
+        if (const char *why = knn_refusal(o, S)) knn_refuse(why);
+        if (!have_lut) knn_refuse("nearest neighbours of values that are not a function of the equality count");
+        if (job_devices(o).size() > 1)
+            std::fprintf(stderr, "[d2g] D2G_DEVICES ignored for this job (%s): it runs on GPU %d alone\n", "the nearest-neighbour selection runs on one GPU", o.device);
+        cmp_core_knn(o, res, ctx, lut, t_densify);
+        return;
+    }
     {
         const std::vector<int> devs = job_devices(o);
         if (devs.size() > 1 && !need_gtlt && !trunc && ns >= 2) {
@@ -1181,8 +1299,6 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
     o.device = job_devices(o)[0];
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "cmp");
-    LazyCtx lctx(o, D2G_WARM_COPY | D2G_WARM_K2 | (o.presketched ? 0 : (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
-    Result res;
     if (o.presketched) {
         // suffix sniffing, cmp_main.cpp:305-351
         const std::string &p0 = o.paths.empty() ? std::string() : o.paths.front();
@@ -1205,6 +1321,13 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
         else if (suf == ".opss") { o.sspace = SPACE_SET; o.kmer_result = ONE_PERM; }
         else if (suf == ".kmerset64" || suf == ".kmerset128")
             die("k-mer set comparison is outside this build's hot-path scope");
+    }
+    if (o.ok == KNN_GRAPH || o.ok == NN_GRAPH_THRESHOLD)            // refused before a context exists
+        if (const size_t S = o.presketched ? presketched_sketchsize(o) : o.sketchsize)
+            if (const char *why = knn_refusal(o, S)) knn_refuse(why);
+    LazyCtx lctx(o, D2G_WARM_COPY | D2G_WARM_K2 | (o.presketched ? 0 : (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
+    Result res;
+    if (o.presketched) {
         load_results(o, res);
     } else {
         if (o.paths.empty()) { std::fprintf(stderr, "No paths provided. See usage.\n"); cmp_usage(); return 1; }

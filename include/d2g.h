@@ -104,6 +104,7 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
 #define D2G_TIME_K2PREP 8
 #define D2G_TIME_K3     16
 #define D2G_TIME_K0     32
+#define D2G_TIME_KNN    64      /* "knn": the selection kernel of d2g_cmp_knn_dev (its count walk is logged as "k2") */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -478,6 +479,52 @@ size_t d2g_cmp_set_operand_bytes(const d2g_cmp_set *set);
  * upper triangle.  sigs = densified double signatures [N][S]. */
 int  d2g_cmp_dist_trunc_ut(d2g_ctx *ctx, const double *sigs, const double *cards, size_t N, size_t sketchsize, size_t r0, size_t r1,
                            int measure, int k, int regbytes, int bbit, int nthreads, float *out);
+
+/* ---- K2e: nearest neighbours -- per-row selection on the device (cmp --topk / --similarity-threshold) ----------------
+ * Replaces build_exact_graph (reference src/index_build.cpp:166-228) + the sign flip of src/cmp_core.cpp:787-793, for values that are
+ * a MONOTONE function of the equality count (where d2g_epilogue_lut succeeds): both modes are then "list every j != i with
+ * neq(i, j) >= t_i".  Only the listed neighbours leave the device, never the N x N matrix.  Always exhaustive (the reference's
+ * EXACT_KNN=1 route), and ALL ties with the K-th best value are kept (the reference's stated intent, which its heap loop does
+ * not reach: SURVEY F12).
+ *
+ * d2g_cmp_knn_dev, rows [r0, r1) of any kind of set: the counts of a band of `band_rows` rows x all N columns go into scratch of
+ * the context (d2g_cmp_eqcount_rect_dev), then one workgroup per row selects.
+ *   K == 0: threshold mode, t_i = min_count for every row (min_count = S + 1: nobody passes).
+ *   K >= 1: top-K mode.  Only counts >= min_count are eligible (1 where a value of 0 is never a neighbour, 0 for distances);
+ *           t_i = the K-th largest eligible count of row i, or min_count when the row has fewer than K eligible columns.
+ *           cls_dev (may be NULL) = S + 1 words, cls[e] = the smallest count whose VALUE equals that of e: t_i is lowered to
+ *           cls[t_i], so that a tie class of the K-th best value that spans several counts is kept whole.
+ * The self pair is excluded by INDEX (duplicates list each other).  Row i - r0 owns slots [(i - r0) cap, (i - r0 + 1) cap) of
+ * ids_dev / counts_dev: its qualifying columns in ASCENDING j with their counts -- bit-reproducible -- and rowcnt_dev[i - r0] is the
+ * TRUE number even beyond cap; nothing is written past a row's slots (cap == 0: counting only, ids_dev / counts_dev may be NULL).
+ * band_rows == 0: the default (a band of at most 64 MB).  Enqueues on `stream`, does not synchronise.  The band lives in the context:
+ * the selection launches of ONE context must be issued on ONE stream. */
+int  d2g_cmp_knn_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, size_t K, uint32_t min_count,
+                     const uint32_t *cls_dev, size_t cap, uint32_t *rowcnt_dev /* [r1-r0] */, uint32_t *ids_dev /* [r1-r0][cap] */,
+                     uint32_t *counts_dev /* [r1-r0][cap] */, size_t band_rows, void *stream);
+/* Host half (no context): candidate lists -> CSR in the reference's order.  value = lut[count] (lut: sketchsize + 1 floats); inside a
+ * row best value first -- descending (isdist == 0) or ascending (isdist != 0) -- and equal values by ascending id: std::sort of
+ * (+-value, id), src/index_build.h:16; the values written are the plain lut entries.  indptr_out has nrows + 1 entries and is
+ * always written; *nnz_needed (may be NULL) = the entries the lists hold; indices_out / data_out are written only when out_cap
+ * holds them all, D2G_ERR_NOMEM otherwise.  A row with rowcnt > cap is INCOMPLETE: *overflow_rows (may be NULL) counts such rows, and
+ * if there is one the call writes nothing else and returns D2G_ERR_INVALID (re-run those rows with a cap that fits); a count above
+ * sketchsize is D2G_ERR_INVALID too.  Nothing is read past the first min(rowcnt, cap) slots of a row. */
+int  d2g_knn_finish(const uint32_t *rowcnt, const uint32_t *ids, const uint32_t *counts, size_t nrows, size_t cap, const float *lut,
+                    size_t sketchsize, int isdist, uint64_t *indptr_out /* [nrows+1] */, uint32_t *indices_out, float *data_out,
+                    size_t out_cap, size_t *nnz_needed, size_t *overflow_rows);
+/* Host-pointer form over a prepared set: exactly one of K >= 1 (top-K) and threshold > 0 ((double)value >= threshold, or <= for
+ * isdist) selects the mode.  lut (host, sketchsize + 1 floats) must be monotone in the count -- non-decreasing for similarities,
+ * non-increasing for distances (D2G_ERR_INVALID otherwise); in top-K mode with isdist == 0 a value of 0 is never a neighbour
+ * (src/index_build.cpp:194).  Runs the rows in chunks with `cap` slots each (0 = a default from K), re-runs ONLY the rows whose
+ * rowcnt exceeded cap with a cap that fits, finishes (d2g_knn_finish) and synchronises.  Outputs as d2g_knn_finish. */
+int  d2g_cmp_set_knn(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, const float *lut, int isdist, size_t K,
+                     double threshold, size_t cap, size_t band_rows, uint64_t *indptr_out /* [r1-r0+1] */, uint32_t *indices_out,
+                     float *data_out, size_t out_cap, size_t *nnz_needed);
+/* ... and from the N x S matrix itself: upload, prepare, table (d2g_epilogue_lut: D2G_ERR_UNSUPPORTED where the value is not a
+ * function of the equality count alone), d2g_cmp_set_knn.  isdist = the reference's distance(measure), src/cmp_main.h:44-49. */
+int  d2g_cmp_knn(d2g_ctx *ctx, const uint64_t *sig_bits, size_t N, size_t sketchsize, size_t r0, size_t r1, int measure, int k,
+                 int multiset_space, int algo, size_t K, double threshold, size_t cap, size_t band_rows,
+                 uint64_t *indptr_out /* [r1-r0+1] */, uint32_t *indices_out, float *data_out, size_t out_cap, size_t *nnz_needed);
 
 /* ---- multi-GPU: RCCL communicator + row-sharded all-pairs engine ------------------------------------
  * Replaces nothing in the reference (it has no multi-process code); it is how the all-pairs seam
