@@ -580,16 +580,19 @@ class Context:
         self._check(lib().d2g_bmh_sketch_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, count_threshold,
                                              sig_dev_ptr, tw_dev_ptr, stream))
 
-    def kmer_count_seqpack(self, sp: "SeqPack", canon=True, xormask=0, count_threshold=0.0):
-        """-> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
-        packed, rs, rl, go = sp.arrays()
+    def kmer_count(self, packed, run_start, run_len, genome_run_off, k, canon=True, xormask=0, count_threshold=0.0):
+        """host arrays (any run table over `packed`) -> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
+        packed = np.ascontiguousarray(packed, np.uint8)
+        rs = np.ascontiguousarray(run_start, np.uint64)
+        rl = np.ascontiguousarray(run_len, np.uint32)
+        go = np.ascontiguousarray(genome_run_off, np.uint64)
         n = go.size - 1
-        cap = int(sum(sp.nkmers(g) for g in range(n)))
+        cap = int(rl.astype(np.int64).sum()) - (k - 1) * rl.size if rl.size else 0
         keys = np.empty(max(cap, 1), np.uint64)
         counts = np.empty(max(cap, 1), np.uint32)
         off = np.zeros(n + 1, np.uint64)
         self._check(lib().d2g_kmer_count(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                         _np_ptr(go), n, sp.k, int(canon), xormask, count_threshold,
+                                         _np_ptr(go), n, k, int(canon), xormask, count_threshold,
                                          _np_ptr(keys), _np_ptr(counts), cap, _np_ptr(off)))
         out = []
         for g in range(n):
@@ -597,6 +600,11 @@ class Context:
             o = np.argsort(k_, kind="stable")
             out.append((k_[o].copy(), c_[o].copy()))
         return out
+
+    def kmer_count_seqpack(self, sp: "SeqPack", canon=True, xormask=0, count_threshold=0.0):
+        """-> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
+        packed, rs, rl, go = sp.arrays()
+        return self.kmer_count(packed, rs, rl, go, sp.k, canon, xormask, count_threshold)
 
     def kmer_distinct_seqpack(self, sp: "SeqPack", canon=True, xormask=0):
         """-> uint64[n]: exact number of distinct masked k-mers per genome"""
@@ -826,12 +834,15 @@ class Sketcher:
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(cnt * np.dtype(dt).itemsize,)).view(dt).copy()
         return arr(rs, nr, np.uint64), arr(rl, nr, np.uint32), arr(go, n + 1, np.uint64), arr(nk, n, np.uint64), int(nb.value)
 
-    def run_ingested(self, runs, S, canon=True, xormask=0):
-        """K1 over the stream ingested last (packed == NULL): -> regs u64 [n][m]"""
-        rs, rl, go = runs[0], runs[1], runs[2]
+    def run_ingested(self, runs, S, canon=True, xormask=0, k=None):
+        """K1 over the stream ingested last (packed == NULL): -> regs u64 [n][m].  `runs` may be any run table inside the stream's
+        extent, and k any k its runs allow (default: the k of the ingest)"""
+        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
+                      np.ascontiguousarray(runs[2], np.uint64))
         n = go.size - 1
         regs = np.empty((n, oph_m(S)), np.uint64)
-        self.ctx._check(lib().d2g_sketcher_run(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n, self.k, int(canon),
+        self.ctx._check(lib().d2g_sketcher_run(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
+                                               self.k if k is None else k, int(canon),
                                                xormask, S, _np_ptr(regs)))
         return regs
 
