@@ -939,11 +939,12 @@ class CmpSet:
         return sparse_info_dict(a)
 
     def sparse_detail(self, stream=None):
-        """-> dict of the last prepare's first look (its decision and raw sums) and list form (synchronises; zeros without a sparse path)"""
-        a = np.zeros(8, np.uint64)
+        """-> dict of the last prepare's first look (its decision and raw sums), list form and schedule -- "merged" (column plan and planes inside
+        launches of the ordering) or "classic" -- with the kernels it enqueued, the transpose included (synchronises; zeros without a sparse path)"""
+        a = np.zeros(10, np.uint64)
         self.ctx._check(lib().d2g_cmp_set_sparse_detail(self.ctx._h, self._h, stream, a.ctypes.data))
         return {"looked": bool(a[0]), "looked_dense": bool(a[1]), "entries": int(a[2]), "family_pairs": int(a[3]), "shared_values": int(a[4]),
-                "planes": int(a[5]), "binned": bool(a[6]), "bin_cshift": int(a[7])}
+                "planes": int(a[5]), "binned": bool(a[6]), "bin_cshift": int(a[7]), "schedule": "merged" if a[8] else "classic", "prepare_kernels": int(a[9])}
 
     def debug_pairs(self, cap=1 << 24, stream=None):
         """-> (pairs [n][2] uint32: the pair list of the last prepare (i < j), roots [N] uint32: the family root of every sketch)"""

@@ -10,9 +10,37 @@ struct SpRider { uint32_t *out; size_t cnt; const uint32_t *vsrc; uint32_t vimm,
 constexpr SpRider SP_NO_RIDER{nullptr, 0, nullptr, 0u, 0xFFFFFFFFu, 0u};
 constexpr int SP_FILL_PER_THREAD = 8, SP_FILL_THREADS = 256;   // sp_fill_kernel: a workgroup writes one piece of 32 KB
 inline size_t sp_fill_pieces(size_t cnt) { return div_up<size_t>(cnt / 4 + 1, (size_t)SP_FILL_THREADS * SP_FILL_PER_THREAD); }
-// ---- riders (sp_ride): the share of an announced output's fill that one hosting kernel of the prepare chain carries.  The weights are the
-// hosts' own durations at config 3 (us): each hides about what it lasts; the last host (place) takes what is left.
+// ---- riders (sp_ride): the share of an announced output's fill that one hosting kernel of the prepare chain carries, in parts of SP_RW_ALL; the
+// last host (place) takes what is left.  Classic schedule: the hosts' own durations at config 3 (us) -- column plan, flatten, count, attach and scan are
+// one to forty workgroups on an idle chip and each hides about what it lasts.  Merged schedule (d2g_bitslice_prepare): the hosts of bits 1 and 2 are the
+// launches that CONTAIN the column plan (link pass 0) and flatten (the planes body); they last ~20 and ~17 us but stream the ids themselves, so their
+// shares are not their durations but what was fitted on the GPU (profiles/k2_merged_prepare.txt section 4): the step is flat between 3 and 8 parts for
+// either of them, and 2 us slower with 12 parts on the link launch or with fewer than ~8 on the two together (the rest lands on place).
+#ifndef D2G_SP_RW_M_LINK0
+#define D2G_SP_RW_M_LINK0 8
+#endif
+#ifndef D2G_SP_RW_M_PLANES
+#define D2G_SP_RW_M_PLANES 5
+#endif
 constexpr unsigned SP_RW_PLAN = 6, SP_RW_FLATTEN = 5, SP_RW_COUNT = 5, SP_RW_ATTACH = 5, SP_RW_SCAN = 8, SP_RW_ALL = 35;
+constexpr unsigned SP_RW_M_LINK0 = D2G_SP_RW_M_LINK0, SP_RW_M_PLANES = D2G_SP_RW_M_PLANES;
+
+// start-of-prepare work of the sparse path's ordering, carried by a kernel that runs anyway (k2_transpose_kernel for a set that owns its operand,
+// sp_unpack_kernel for the multi-GPU engine's gathered one) instead of a launch and memsets of its own: label[j] = j, `owords` words at `ones` set to
+// all-ones (the hints), `zwords` words at `zero` cleared (counters, linked flags, tile bitmap + control words, order words, the pair list's cursor).
+// Nothing between that kernel and the first link pass touches these arrays (the rank kernel and the first look's two kernels have buffers of their own).
+struct SpInit {
+    uint32_t *label = nullptr, *ones = nullptr, *zero = nullptr;
+    uint32_t n = 0, owords = 0, zwords = 0;
+};
+#ifdef __HIPCC__
+__device__ __forceinline__ void sp_init_part(const SpInit &si, size_t lin, size_t nthreads) {
+    if (!si.label) return;
+    if (lin < si.n) si.label[lin] = (uint32_t)lin;
+    for (size_t x = lin; x < si.owords; x += nthreads) si.ones[x] = 0xFFFFFFFFu;
+    for (size_t x = lin; x < si.zwords; x += nthreads) si.zero[x] = 0;
+}
+#endif
 
 // the output of the NEXT upper-triangle launch, announced ahead of the prepare (d2g_cmp_ut_announce_dev): the prepare's latency-bound
 // kernels (column plan, flatten, count, attach, scan, place: one to forty workgroups each) carry the fill as extra workgroups
@@ -72,6 +100,7 @@ enum SpMappedWord : uint32_t { SP_MW_GAVEUP = 0, SP_MW_LIST_LEN = 1, SP_MW_SUMS 
 // which way a prepare goes: the first look at the matrix, the remembered give-up, the form of the pair list
 struct SpDecision {
     unsigned prepares = 0; bool skipped = false;   // prepares so far; the last one skipped the ordering
+    bool merged = false; unsigned kernels = 0;     // the last prepare: it ran the merged schedule (d2g_bitslice_prepare); the kernels it enqueued, the transpose included (diagnostics)
     int skip_cached = -1;             // this prepare's reading of the remembered give-up (-1: not read yet)
     bool sample_pending = false; uint32_t sample_ticket = 0;   // the first look's kernels are enqueued; the value their last workgroup writes to the ticket word when the sums are in
     bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)
@@ -193,7 +222,8 @@ int  d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream
 int  d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set);
 int  d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s);
 int  d2g_bitslice_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint32_t *out4);
-int  d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out8);
+int  d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out10);
+SpInit d2g_bitslice_sp_init(const d2g_cmp_set *set);   // what the transpose in front of the set's prepare initialises for its ordering (nothing: a set without sparse state)
 int  d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out);
 int  d2g_bitslice_status(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s);   // synchronises; D2G_ERR_INTERNAL on overflow
 // exporter set over an N x S_local column slice (no operand of its own); d2g_bitslice_prepare_slice transposes + prepares it

@@ -50,11 +50,14 @@ int finish_shape(d2g_ctx *ctx, PairShape &sh, unsigned rb) {
 namespace {
 
 // ---------------------------------------------------------------- transpose [N][S] -> [S][Npad]
-// zero2: two words the bit-sliced prepare that follows wants cleared (its status word and the plan ticket), or null
+// zero2: two words the bit-sliced prepare that follows wants cleared (its status word and the spare word behind it, which nothing reads), or null
+// si: what the sparse path's ordering of that prepare wants initialised (SpInit; spread over the grid's threads) -- here, in front of the whole prepare,
+// so that the ordering's first link pass can stand anywhere behind the rank kernel
 __global__ __launch_bounds__(256) void k2_transpose_kernel(const uint64_t *__restrict__ rows, uint64_t *__restrict__ cols,
-                                                           size_t N, size_t S, size_t Npad, uint32_t *zero2) {
+                                                           size_t N, size_t S, size_t Npad, uint32_t *zero2, SpInit si) {
     __shared__ uint64_t tile[32][33];
     if (zero2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 2) zero2[threadIdx.x] = 0;
+    sp_init_part(si, ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x, (size_t)gridDim.x * gridDim.y * 256);   // (the grid has >= 8 Npad threads)
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
     const size_t n0 = (size_t)blockIdx.y * 32, s0 = (size_t)blockIdx.x * 32;
     for (int r = ty; r < 32; r += 8) {
@@ -72,9 +75,9 @@ __global__ __launch_bounds__(256) void k2_transpose_kernel(const uint64_t *__res
 // both ways -- 46.3 us on average (27.7 at best) against 42.7 (25.5) for the kernel above in the bench's step.  The average is not a
 // bytes-in-flight problem: the step before left 200 MB of freshly filled output behind, and whatever kernel comes next shares the HBM with
 // that write-back.)
-void launch_transpose(d2g_ctx *, const uint64_t *rows, uint64_t *cols, size_t N, size_t S, size_t Npad, uint32_t *zero2, hipStream_t s) {
+void launch_transpose(d2g_ctx *, const uint64_t *rows, uint64_t *cols, size_t N, size_t S, size_t Npad, uint32_t *zero2, const SpInit &si, hipStream_t s) {
     dim3 grid((unsigned)div_up<size_t>(S, 32), (unsigned)div_up<size_t>(Npad, 32));
-    hipLaunchKernelGGL(k2_transpose_kernel, grid, dim3(256), 0, s, rows, cols, N, S, Npad, zero2);
+    hipLaunchKernelGGL(k2_transpose_kernel, grid, dim3(256), 0, s, rows, cols, N, S, Npad, zero2, si);
 }
 
 // ---------------------------------------------------------------- direct compare kernel
@@ -218,7 +221,8 @@ static int cmp_set_load(d2g_ctx *ctx, d2g_cmp_set *set, const uint64_t *sig_bits
     // only the DIRECT kernel reads the row-major operand; bit-sliced sets transpose straight from the caller's buffer
     if (set->d_rows) D2G_HIP(ctx, hipMemcpyAsync(set->d_rows, sig_bits_dev, N * S * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     d2g_timer tm(ctx, &ctx->ev_k2prep, s);
-    launch_transpose(ctx, sig_bits_dev, set->d_cols, N, S, set->Npad, set->algo == D2G_CMP_BITSLICE ? set->d_meta + set->ntb : nullptr, s);
+    launch_transpose(ctx, sig_bits_dev, set->d_cols, N, S, set->Npad, set->algo == D2G_CMP_BITSLICE ? set->d_meta + set->ntb : nullptr,
+                     set->algo == D2G_CMP_BITSLICE ? d2g_bitslice_sp_init(set) : SpInit{}, s);
     int rc = D2G_OK;
     if (set->algo == D2G_CMP_BITSLICE) rc = d2g_bitslice_prepare(ctx, set, s);
     tm.stop();
@@ -232,7 +236,7 @@ static int cmp_set_load(d2g_ctx *ctx, d2g_cmp_set *set, const uint64_t *sig_bits
 // exporter sets (d2g_mgpu.hip): transpose the N x S_local slice and prepare it into the export target; timed as "k2prep"
 int d2g_bitslice_prepare_slice(d2g_ctx *ctx, d2g_cmp_set *set, const uint64_t *rows_dev, hipStream_t s) {
     d2g_timer tm(ctx, &ctx->ev_k2prep, s);
-    launch_transpose(ctx, rows_dev, set->d_cols, set->N, set->S, set->Npad, set->d_meta + set->ntb, s);
+    launch_transpose(ctx, rows_dev, set->d_cols, set->N, set->S, set->Npad, set->d_meta + set->ntb, d2g_bitslice_sp_init(set), s);
     const int rc = d2g_bitslice_prepare(ctx, set, s);
     tm.stop();
     if (rc) return rc;
@@ -347,14 +351,14 @@ int d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, 
     return d2g_bitslice_debug_read(ctx, set, as_stream(stream), pairs_out, cap, npairs, root_out);
 }
 
-int d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out8) {
-    if (!ctx || !out8) return D2G_ERR_INVALID;
+int d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out10) {
+    if (!ctx || !out10) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_sparse_detail: set belongs to another context");
     D2G_NO_CODE_SET(ctx, set, "cmp_set_sparse_detail");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    for (int x = 0; x < 8; ++x) out8[x] = 0;
+    for (int x = 0; x < 10; ++x) out10[x] = 0;
     if (set->algo != D2G_CMP_BITSLICE) { D2G_HIP(ctx, hipStreamSynchronize(as_stream(stream))); return D2G_OK; }
-    return d2g_bitslice_sparse_detail(ctx, set, as_stream(stream), out8);
+    return d2g_bitslice_sparse_detail(ctx, set, as_stream(stream), out10);
 }
 
 int d2g_cmp_set_status(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream) {

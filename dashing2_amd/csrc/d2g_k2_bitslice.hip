@@ -421,7 +421,8 @@ __device__ __forceinline__ size_t stream_slot_wave(const uint32_t *meta, int tb)
 // ------------------------------------------------------------------ riders
 // The fill of an upper-triangle launch (every output = "no register equal", 4 bytes per pair: 200 MB at config 3, 31 us of pure HBM
 // writes) depends on nothing the prepare computes, and six kernels of the prepare chain are one to forty workgroups waiting out
-// dependent round trips on an otherwise idle chip (column plan, flatten, count, attach, scan, place: 36 us together at config 3).  When the
+// dependent round trips on an otherwise idle chip (column plan, flatten, count, attach, scan, place: 36 us together at config 3; in the merged schedule
+// the first two hosts are the launches that CONTAIN the column plan and flatten: sp_link0_plan_kernel, bs_planes_flatten_kernel).  When the
 // output is announced ahead of the prepare (d2g_cmp_ut_announce_dev) those kernels are launched with extra workgroups BEHIND their own --
 // the dispatcher starts workgroups in index order, the kernel's own work is never queued behind a rider -- each writing one 32 KB piece.
 // (The same fill on a second stream was measured in rounds 4 and 5: the two cross-stream dependencies cost more than the fill.)
@@ -462,7 +463,8 @@ inline unsigned sp_side_fill_grid(const d2g_ctx *ctx, uint32_t pieces, size_t wo
 }
 
 // ------------------------------------------------------------------ 1b. column plan
-// One workgroup, a kernel of its own.  (Letting the LAST workgroup of the rank kernel do this -- ticket counter -- was
+// One workgroup: a kernel of its own in the classic schedule, block 0 of the link launch in the merged one (sp_link0_plan_kernel, d2g_k2_sparse.h: it
+// needs nothing but the rank kernel's counts, and nothing in that launch needs what it writes).  (Letting the LAST workgroup of the rank kernel do this -- ticket counter -- was
 // measured: with an agent-scope fence per workgroup the rank kernel went 52 -> 111 us at config 3, every fence writes the
 // XCD's L2 back; fence-free, with returning device-scope atomics for the counts and the ticket, 52 -> 81 us.  The
 // separate launch costs ~7 us.)  Input: colcnt[t][h] = shared values split h of the rank kernel found in column t.  Output:
@@ -478,15 +480,29 @@ constexpr int BS_PLAN_MAXS = 4096;                // slots sorted in LDS; larger
 constexpr uint32_t BS_NOCOL = 0xFFFFFFFFu;
 __device__ __forceinline__ int plane_class(uint32_t d2) { return d2 == 0 ? 1 : 32 - __clz(d2 + 1); }   // = live_planes(D2 + 1)
 
-__global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(uint32_t *__restrict__ colcnt, uint32_t S, int ntb, int nsplit,
-                                                                       uint32_t *__restrict__ perm, uint32_t *__restrict__ meta,
-                                                                       const uint32_t *__restrict__ status, uint32_t *__restrict__ ex_meta,
-                                                                       uint32_t *__restrict__ ex_status, int sort, SpRider rider) {
-    SP_RIDE_OR_WORK(rider);
-    __shared__ uint32_t d2s[BS_PLAN_MAXS];
-    __shared__ uint16_t perm_s[BS_PLAN_MAXS];
-    __shared__ uint32_t cell[32 * (BS_PLAN_MAXS / 64)];   // (class, 64-slot chunk) counts, then their exclusive prefix
-    __shared__ uint32_t wave_tot[BS_PLAN_THREADS / 64];
+// The plan's body for a block of T threads (T = BS_PLAN_THREADS in the kernel of its own; 256 as block 0 of the merged link launch, sp_link0_plan_kernel):
+// correct for any Spad <= BS_PLAN_MAXS, and for the identity order beyond.  LDS (the caller's): d2s[Spad], perm_s[Spad], cell[32 * ceil(Spad / 64)],
+// wave_tot[T / 64] -- bs_plan_lds_words(Spad) words in all, laid out by BsPlanLds.
+struct BsPlanArgs {
+    uint32_t *colcnt; uint32_t S; int ntb, nsplit; uint32_t *perm, *meta; const uint32_t *status; uint32_t *ex_meta, *ex_status; int sort;
+};
+struct BsPlanLds { uint32_t *d2s, *cell, *wave_tot; uint16_t *perm_s; };
+__host__ __device__ inline uint32_t bs_plan_sorted(uint32_t Spad, int sort) { return sort && Spad <= (uint32_t)BS_PLAN_MAXS; }
+__host__ __device__ inline size_t bs_plan_lds_words(uint32_t Spad, int sort) {      // (identity order: no LDS)
+    return bs_plan_sorted(Spad, sort) ? (size_t)Spad + 32 * (size_t)((Spad + 63) / 64) + 16 + (Spad + 1) / 2 : 0;
+}
+__device__ __forceinline__ BsPlanLds bs_plan_lds(uint32_t *base, uint32_t Spad) {
+    const uint32_t ncell = 32 * ((Spad + 63) / 64);
+    return BsPlanLds{base, base + Spad, base + Spad + ncell, reinterpret_cast<uint16_t *>(base + Spad + ncell + 16)};
+}
+template <int T>
+__device__ __forceinline__ void bs_colplan_body(const BsPlanArgs &pa, const BsPlanLds &l) {
+    static_assert(T % 64 == 0 && T <= 1024 && BS_PLAN_MAXS % T == 0 && (32 * (BS_PLAN_MAXS / 64)) % T == 0, "bs_colplan_body: block size");
+    uint32_t *const colcnt = pa.colcnt, *const perm = pa.perm, *const meta = pa.meta, *const ex_meta = pa.ex_meta;
+    const uint32_t S = pa.S;
+    const int ntb = pa.ntb, nsplit = pa.nsplit;
+    uint32_t *const d2s = l.d2s, *const cell = l.cell, *const wave_tot = l.wave_tot;
+    uint16_t *const perm_s = l.perm_s;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t Spad = (uint32_t)ntb * 32u;
     auto column_total = [&](uint32_t t) {             // D2 of column t; leaves the per-split offsets behind
@@ -495,13 +511,13 @@ __global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(uint32_t *_
         colcnt[(size_t)t * BS_CC_STRIDE + 4] = run;
         return run;
     };
-    if (tid == 0 && ex_status) *ex_status = *status;
-    if (!sort || Spad > BS_PLAN_MAXS) {                // identity order
-        for (uint32_t t = tid; t < S; t += BS_PLAN_THREADS) (void)column_total(t);
-        for (uint32_t p = tid; p < Spad; p += BS_PLAN_THREADS) perm[p] = p < S ? p : BS_NOCOL;
+    if (tid == 0 && pa.ex_status) *pa.ex_status = *pa.status;
+    if (!bs_plan_sorted(Spad, pa.sort)) {              // identity order
+        for (uint32_t t = tid; t < S; t += T) (void)column_total(t);
+        for (uint32_t p = tid; p < Spad; p += T) perm[p] = p < S ? p : BS_NOCOL;
         __threadfence();
         __syncthreads();
-        for (int g = tid; g < ntb; g += BS_PLAN_THREADS) {
+        for (int g = tid; g < ntb; g += T) {
             uint32_t mx = 0;
             for (uint32_t x = 0; x < 32; ++x) { const uint32_t t = (uint32_t)g * 32 + x; if (t < S) mx = max(mx, colcnt[(size_t)t * BS_CC_STRIDE + 4]); }
             meta[g] = mx + 1;
@@ -510,14 +526,14 @@ __global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(uint32_t *_
         return;
     }
     const uint32_t nchunk = (Spad + 63) / 64, ncell = 32 * nchunk;
-    for (uint32_t c = tid; c < ncell; c += BS_PLAN_THREADS) cell[c] = 0;
+    for (uint32_t c = tid; c < ncell; c += T) cell[c] = 0;
     __syncthreads();
-    constexpr int IT = BS_PLAN_MAXS / BS_PLAN_THREADS;
-    uint32_t mycell[IT], myrank[IT];
+    constexpr int IT = BS_PLAN_MAXS / T;
+    uint32_t mine[IT];                                                 // (cell << 6 | rank inside the cell: one register per slot -- the merged link launch shares its register budget with the link pass)
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
-        const uint32_t t = (uint32_t)it * BS_PLAN_THREADS + tid;      // a wave covers the 64 consecutive slots of chunk t / 64
-        mycell[it] = 0; myrank[it] = 0;
+        const uint32_t t = (uint32_t)it * T + tid;                    // a wave covers the 64 consecutive slots of chunk t / 64
+        mine[it] = 0;
         if (t - lane < Spad) {                                         // wave-uniform
             uint32_t d2 = 0;
             int cls = 0;                                               // class 0 = padding: sorted behind every real column
@@ -528,39 +544,48 @@ __global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(uint32_t *_
                 const int k = __shfl(cls, __ffsll((long long)todo) - 1);
                 const unsigned long long m = __ballot(cls == k && t < Spad);
                 const uint32_t ci = (uint32_t)(31 - k) * nchunk + t / 64;   // descending class, ascending slot
-                if (cls == k && t < Spad) { mycell[it] = ci; myrank[it] = __popcll(m & ((1ull << lane) - 1)); }
+                if (cls == k && t < Spad) mine[it] = ci << 6 | (uint32_t)__popcll(m & ((1ull << lane) - 1));
                 if (lane == 0) cell[(uint32_t)(31 - k) * nchunk + (t - lane) / 64] = __popcll(m);
                 todo &= ~m;
             }
         }
     }
     __syncthreads();
-    {   // exclusive prefix over the cells (<= 2048): two per thread
-        const uint32_t c0 = 2u * tid, a = c0 < ncell ? cell[c0] : 0u, b = c0 + 1 < ncell ? cell[c0 + 1] : 0u;
-        uint32_t incl = a + b;
+    {   // exclusive prefix over the cells (<= 2048): CPT consecutive ones per thread
+        constexpr int CPT = 32 * (BS_PLAN_MAXS / 64) / T;
+        const uint32_t c0 = (uint32_t)CPT * tid;
+        uint32_t v[CPT], sum = 0;
+#pragma unroll
+        for (int x = 0; x < CPT; ++x) { v[x] = c0 + x < ncell ? cell[c0 + x] : 0u; sum += v[x]; }
+        uint32_t incl = sum;
         for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(incl, o); if (lane >= o) incl += x; }
         if (lane == 63) wave_tot[wave] = incl;
         __syncthreads();
-        uint32_t woff = 0;
-        for (int w = 0; w < wave; ++w) woff += wave_tot[w];
-        const uint32_t ex = woff + incl - (a + b);
-        if (c0 < ncell) cell[c0] = ex;
-        if (c0 + 1 < ncell) cell[c0 + 1] = ex + a;
+        uint32_t ex = incl - sum;
+        for (int w = 0; w < wave; ++w) ex += wave_tot[w];
+#pragma unroll
+        for (int x = 0; x < CPT; ++x) { if (c0 + x < ncell) cell[c0 + x] = ex; ex += v[x]; }
     }
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < IT; ++it) {
-        const uint32_t t = (uint32_t)it * BS_PLAN_THREADS + tid;
-        if (t < Spad) perm_s[cell[mycell[it]] + myrank[it]] = (uint16_t)t;
+        const uint32_t t = (uint32_t)it * T + tid;
+        if (t < Spad) perm_s[cell[mine[it] >> 6] + (mine[it] & 63u)] = (uint16_t)t;
     }
     __syncthreads();
-    for (uint32_t p = tid; p < Spad; p += BS_PLAN_THREADS) { const uint32_t t = perm_s[p]; perm[p] = t < S ? t : BS_NOCOL; }
-    for (int g = tid; g < ntb; g += BS_PLAN_THREADS) {
+    for (uint32_t p = tid; p < Spad; p += T) { const uint32_t t = perm_s[p]; perm[p] = t < S ? t : BS_NOCOL; }
+    for (int g = tid; g < ntb; g += T) {
         uint32_t mx = 0;
         for (uint32_t x = 0; x < 32; ++x) mx = max(mx, d2s[perm_s[(uint32_t)g * 32 + x]]);
         meta[g] = mx + 1;
         if (ex_meta) ex_meta[g] = mx + 1;
     }
+}
+
+__global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(BsPlanArgs pa, SpRider rider) {
+    SP_RIDE_OR_WORK(rider);
+    extern __shared__ __attribute__((aligned(16))) uint32_t plan_lds[];
+    bs_colplan_body<BS_PLAN_THREADS>(pa, bs_plan_lds(plan_lds, (uint32_t)pa.ntb * 32u));
 }
 
 // Writes both forms of the operand:
@@ -571,29 +596,22 @@ __global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(uint32_t *_
 //                                        pointer simply advances by one block per plane (no per-plane address selection).
 // Register slot x of group tb holds column perm[32 tb + x] (bs_colplan_kernel).
 constexpr int BS_FORM_STREAM = 1, BS_FORM_EXCHANGE = 2;
-// start-of-prepare work of the sparse path (section 4) carried by a kernel that runs anyway (bs_planes_kernel, sp_unpack_kernel)
-// instead of a launch and memsets of its own: label[j] = j, `owords` words at `ones` set to all-ones (the hints), `zwords` words at
-// `zero` cleared (counters, linked flags, tile bitmap + control words, order words, the pair list's cursor)
-struct SpInit {
-    uint32_t *label = nullptr, *ones = nullptr, *zero = nullptr;
-    uint32_t n = 0, owords = 0, zwords = 0;
-};
-__device__ __forceinline__ void sp_init_part(const SpInit &si, size_t lin, size_t nthreads) {
-    if (!si.label) return;
-    if (lin < si.n) si.label[lin] = (uint32_t)lin;
-    for (size_t x = lin; x < si.owords; x += nthreads) si.ones[x] = 0xFFFFFFFFu;
-    for (size_t x = lin; x < si.zwords; x += nthreads) si.zero[x] = 0;
-}
 constexpr size_t BS_SLACK = 64;          // words behind position Npad of every plane (Nstride = Npad + BS_SLACK)
+struct BsPlanesArgs {
+    const uint32_t *ids; size_t N, Npad; uint32_t *planes, *stream; size_t Nstride; int nbits_cap; const uint32_t *meta; int forms;
+    const uint32_t *perm, *colcnt, *sperm;
+};
+BsPlanesArgs planes_args_of(const d2g_cmp_set *set, uint32_t *planes, int forms) {
+    return BsPlanesArgs{set->d_ids, set->N, set->Npad, planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms, set->d_perm, set->d_colcnt, nullptr};
+}
+// the body of workgroup (bx, tb) of the grid ceil(Nstride / 256) x ntb: 256 threads (bs_planes_kernel; the merged planes launch, bs_planes_flatten_kernel)
 template <bool SPLIT>
-__global__ __launch_bounds__(256) void bs_planes_kernel(const uint32_t *__restrict__ ids, size_t N, size_t Npad,
-                                                        uint32_t *__restrict__ planes, uint32_t *__restrict__ stream,
-                                                        size_t Nstride, int nbits_cap, const uint32_t *__restrict__ meta, int forms,
-                                                        const uint32_t *__restrict__ perm, const uint32_t *__restrict__ colcnt,
-                                                        const uint32_t *__restrict__ sperm, SpInit si) {
-    const size_t jpos = (size_t)blockIdx.x * 256 + threadIdx.x;   // position in the operand
-    const size_t tb = blockIdx.y;
-    sp_init_part(si, tb * ((size_t)gridDim.x * 256) + jpos, (size_t)gridDim.x * 256 * gridDim.y);
+__device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx, size_t tb) {
+    const uint32_t *__restrict__ ids = a.ids, *__restrict__ meta = a.meta, *__restrict__ perm = a.perm, *__restrict__ colcnt = a.colcnt, *__restrict__ sperm = a.sperm;
+    uint32_t *__restrict__ planes = a.planes, *__restrict__ stream = a.stream;
+    const size_t N = a.N, Npad = a.Npad, Nstride = a.Nstride;
+    const int nbits_cap = a.nbits_cap, forms = a.forms;
+    const size_t jpos = bx * 256 + threadIdx.x;   // position in the operand
     const size_t slot = (forms & BS_FORM_STREAM) ? stream_slot_wave(meta, (int)tb) : 0;     // (every lane still here)
     if (jpos >= Nstride) return;
     // sperm: the operand written in another order -- position p holds sketch sperm[p] (stream form only; unused: the sparse path permutes the finished stream)
@@ -639,6 +657,8 @@ __global__ __launch_bounds__(256) void bs_planes_kernel(const uint32_t *__restri
         dst[(size_t)nbits_cap * Nstride] = uw;
     }
 }
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void bs_planes_kernel(BsPlanesArgs a) { bs_planes_body<SPLIT>(a, blockIdx.x, blockIdx.y); }
 
 // plane stream of an operand that arrived in the exchanged form (the gathered operand of the multi-GPU path,
 // d2g_cmp_set_from_planes_dev)
@@ -917,13 +937,11 @@ int alloc_prepare_workspace(d2g_ctx *ctx, d2g_cmp_set *set) {
     set->d_meta = set->own_meta;
     return D2G_OK;
 }
-// the bit transpose of the ids (bs_planes_kernel): the plane stream and / or the exchange form (`forms`; the latter into `planes`).  `init`: what
-// the sparse path's ordering wants initialised by the same launch
-int launch_planes(d2g_ctx *ctx, const d2g_cmp_set *set, uint32_t *planes, int forms, const SpInit &init, hipStream_t s) {
+// the bit transpose of the ids (bs_planes_kernel): the plane stream and / or the exchange form (`forms`; the latter into `planes`)
+int launch_planes(d2g_ctx *ctx, const d2g_cmp_set *set, uint32_t *planes, int forms, hipStream_t s) {
     const dim3 grid((unsigned)div_up<size_t>(set->Nstride, 256), (unsigned)set->ntb);
     const bool split = set->logT > BS_LOG_TLDS_MAX && set->nsplit > 1;
-    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, set->d_ids, set->N, set->Npad,
-                       planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms, set->d_perm, set->d_colcnt, (const uint32_t *)nullptr, init);
+    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, planes_args_of(set, planes, forms));
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
 }
@@ -1002,22 +1020,38 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         hipLaunchKernelGGL(kern, dim3((unsigned)(S * nsplit)), dim3(BS_RANK_THREADS), lds, s, set->d_cols, N, Npad, set->T, set->logT,
                            set->d_ids, set->d_colcnt, set->d_meta + set->ntb, ctx->k2.tagbits_max, (uint32_t)S, nsplit,
                            (sp && nsplit == 1) ? sp->d_owner.get() : (uint32_t *)nullptr, sp ? sp->owner_stride : 0);
+        if (sp) sp->dec.kernels = 2 + (join.ev ? 1 : 0);               // the transpose in front of this prepare, the rank kernel (, the side fill)
         // a set's first prepare looks at its matrix before it orders it: the sample needs the ids only, so it stands HERE and the two kernels
         // below run while the host waits for its word (sp_sample_collect)
-        if (sparse_path && sp_sample_due(ctx, set)) { if (int rc = sp_sample_enqueue(ctx, set, s)) return rc; }
-        unsigned g = 1; const SpRider rd = sp ? sp->announced.take(1, SP_RW_PLAN, false, 1, &g) : SP_NO_RIDER;
-        hipLaunchKernelGGL(bs_colplan_kernel, dim3(g), dim3(BS_PLAN_THREADS), 0, s, set->d_colcnt, (uint32_t)S, set->ntb, nsplit, set->d_perm,
-                           set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, ctx->k2.sort ? 1 : 0, rd);
+        const bool look = sparse_path && sp_sample_due(ctx, set);
+        if (look) { if (int rc = sp_sample_enqueue(ctx, set, s)) return rc; if (sp->dec.sample_pending) sp->dec.kernels += 2; }
+        // Two schedules from here on.  Behind the rank kernel the chain A = column plan -> planes (reads colcnt and ids; writes perm, meta, the caller's-order
+        // stream) and the chain B = the ordering (link pass 0 -> flatten -> link pass 1 -> count -> attach -> scan -> place -> emit: reads ids, owner, labels;
+        // writes labels, hints, counts, sperm / sinv, tile bitmap, list) meet only in sp_permute.
+        //   classic   A in front of B, kernel by kernel: rank, plan, planes, link 0, flatten, link 1, count, attach, scan, place, emit, permute
+        //   merged    A inside launches of B (sp_launch_merged):   rank, [plan + link 0], [flatten + planes], link 1, count, attach, scan, place, emit, permute
+        //             (two launches and ~9 us fewer per step at config 3: profiles/k2_merged_prepare.txt)
+        // The merged one needs the streaming link form on unsplit columns, and a prepare whose path is known when it is enqueued: the first prepare of a set and
+        // the retry of a remembered give-up decide between dense and sparse on the host BEHIND the rank kernel (the first look) -- link pass 0 must not be
+        // enqueued before that -- and a remembered give-up runs no ordering at all.  Exporter and exchange sets have no ordering.  D2G_K2_MERGE=0: classic.
+        const bool merged = sparse_path && !look && ctx->k2.merge && nsplit == 1 && sp->d_owner && ctx->k2.olink && ctx->k2.link && sp->dec.skip_cached != 1;
+        if (sp) sp->dec.merged = merged;
+        if (!merged) {
+            unsigned g = 1; const SpRider rd = sp ? sp->announced.take(1, SP_RW_PLAN, false, 1, &g) : SP_NO_RIDER;
+            const BsPlanArgs pa{set->d_colcnt, (uint32_t)S, set->ntb, nsplit, set->d_perm, set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, ctx->k2.sort ? 1 : 0};
+            hipLaunchKernelGGL(bs_colplan_kernel, dim3(g), dim3(BS_PLAN_THREADS), bs_plan_lds_words((uint32_t)set->ntb * 32u, pa.sort) * 4, s, pa, rd);
+            if (sp) sp->dec.kernels += 1;
+        }
     }
     if (sparse_path) {
-        // sparse path (section 4): the caller's-order stream first (the dense walk and rectangular launches read it), then the families,
-        // the pair list and the stream in family order
+        // sparse path (section 4): the caller's-order stream (the dense walk and rectangular launches read it), the families, the pair list and
+        // the stream in family order
         // (gathering the ids through d_sperm inside bs_planes_kernel was measured: 74 us instead of 18 at config 3 -- 1024 columns of
         // uncoalesced 4-byte loads; permuting the finished stream touches 256 rows of words and leaves the caller's-order stream valid)
         // (a second queue for the caller's-order planes beside the ordering, and for the fill beside the tile list, was measured in round 4:
         // the kernels slow each other down by what the overlap hides and the events cost more: dropped)
-        // (the planes kernel also initialises the ordering's arrays and clears the tile bitmap: no launch / memset of their own)
-        if (int rc = launch_planes(ctx, set, set->d_planes, BS_FORM_STREAM, sp_init_of(set), s)) return rc;
+        // (the ordering's arrays and the tile bitmap were initialised by the transpose in front of this prepare: no launch / memset of their own)
+        if (!sp->dec.merged) { if (int rc = launch_planes(ctx, set, set->d_planes, BS_FORM_STREAM, s)) return rc; sp->dec.kernels += 1; }
         if (int rc = sp_sample_collect(ctx, set, s)) return rc;         // (the first look, enqueued behind the rank kernel: the host waits for its word here)
         if (int rc = sp_prepare_order(ctx, set, nsplit > 1, s)) return rc;
         if (int rc = sp_permute(ctx, set, s)) return rc;
@@ -1030,15 +1064,18 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     }
     if (sp) sp->announced.served();
     const int forms = set->export_only ? BS_FORM_EXCHANGE : (BS_FORM_STREAM | (set->want_exchange ? BS_FORM_EXCHANGE : 0));
-    if (int rc = launch_planes(ctx, set, set->export_only ? set->ex_planes : set->d_planes, forms, SpInit{}, s)) return rc;
+    if (int rc = launch_planes(ctx, set, set->export_only ? set->ex_planes : set->d_planes, forms, s)) return rc;
+    if (sp) sp->dec.kernels += 1;
     set->srt_valid = false; set->nat_valid = true;
     return D2G_OK;
 }
 
+SpInit d2g_bitslice_sp_init(const d2g_cmp_set *set) { return sp_init_of(set); }
+
 // the caller's-order stream of a set whose last prepare only wrote the sorted one (rectangular launches, exports)
 int d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s) {
     if (set->nat_valid || set->borrowed || set->export_only) return D2G_OK;
-    if (int rc = launch_planes(ctx, set, set->d_planes, BS_FORM_STREAM, SpInit{}, s)) return rc;
+    if (int rc = launch_planes(ctx, set, set->d_planes, BS_FORM_STREAM, s)) return rc;
     set->nat_valid = true;
     return D2G_OK;
 }
@@ -1047,7 +1084,7 @@ int d2g_bitslice_ensure_natural(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_
 int d2g_bitslice_export(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     if (set->borrowed || set->want_exchange || set->export_only) return D2G_OK;
     set->want_exchange = true;
-    return launch_planes(ctx, set, set->d_planes, BS_FORM_EXCHANGE, SpInit{}, s);
+    return launch_planes(ctx, set, set->d_planes, BS_FORM_EXCHANGE, s);
 }
 
 // ---- exporter sets: the multi-GPU engine's per-rank column slices (d2g_mgpu.hip)
@@ -1153,6 +1190,7 @@ int d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
 int d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     if (!set->borrowed || !set->sparse_ok()) return D2G_OK;
     dim3 grid((unsigned)div_up<size_t>(set->Npad, 256), (unsigned)set->ntb);
+    set->sp->dec.merged = false; set->sp->dec.kernels = 1;            // (diagnostics: the unpack kernel, then the classic chain)
     hipLaunchKernelGGL(sp_unpack_kernel, grid, dim3(256), 0, s, set->d_planes, set->Nstride, set->nbits_cap, set->d_meta, set->N, set->Npad, set->d_ids, set->d_colcnt, sp_init_of(set));
     if (int rc = sp_prepare_order(ctx, set, false, s)) return rc;
     if (int rc = sp_permute(ctx, set, s)) return rc;
@@ -1188,7 +1226,7 @@ int d2g_bitslice_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s
 }
 
 // diagnostics of the last prepare's first look and list form (synchronises `s`): see d2g.h
-int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out8) {
+int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out8) {   // (out8: ten words)
     uint32_t binned = 0;
     if (set->sp) D2G_HIP(ctx, hipMemcpyAsync(&binned, set->sp->d_plctl + SP_PL_BINNED, 4, hipMemcpyDeviceToHost, s));   // (raised by sp_bin_kernel when the binned form ran)
     D2G_HIP(ctx, hipStreamSynchronize(s));
@@ -1197,6 +1235,7 @@ int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t
     out8[0] = sp.dec.looked ? 1 : 0; out8[1] = sp.dec.looked_dense ? 1 : 0;
     if (sp.dec.looked) for (int x = 0; x < 4; ++x) out8[2 + x] = sp.dec.samp_sums[x];   // (a prepare that did not look reports no sums: those of an earlier look are not its own)
     out8[6] = binned ? 1 : 0; out8[7] = sp.bin_cshift;
+    out8[8] = sp.dec.merged ? 1 : 0; out8[9] = sp.dec.kernels;
     return D2G_OK;
 }
 
@@ -1230,7 +1269,7 @@ int d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s,
 uint64_t d2g_k2_tuning_hash(const d2g_ctx *ctx) {
     const d2g_k2_tuning &t = ctx->k2;
     const long long v[] = {t.sparse, (long long)t.min_n, t.link, (long long)(t.tile_frac * 1e6), t.olink, t.emit_big, t.ride, t.remember, (long long)t.list_div, (long long)t.long_list,
-                           t.list_form, t.predict, t.sort ? 1 : 0, t.tagbits_max, t.nsplit_req};
+                           t.list_form, t.predict, t.sort ? 1 : 0, t.tagbits_max, t.nsplit_req, t.merge};
     uint64_t h = 1469598103934665603ull;
     for (long long x : v) for (int b = 0; b < 8; ++b) { h ^= (uint64_t)(x >> (8 * b)) & 0xFF; h *= 1099511628211ull; }
     return h;
@@ -1240,8 +1279,8 @@ std::string d2g_k2_tuning_json(const d2g_ctx *ctx) {
     const d2g_k2_tuning &t = ctx->k2;
     char b[640];
     std::snprintf(b, sizeof b, "{\"D2G_BS_SPARSE\": %d, \"D2G_BS_SPARSE_MIN_N\": %zu, \"D2G_BS_SORT\": %d, \"D2G_SP_LINK\": %d, \"D2G_SP_OLINK\": %d, \"D2G_SP_TILE_FRAC\": %.3f, "
-                  "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d}",
-                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big);
+                  "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d, \"D2G_K2_MERGE\": %d}",
+                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big, t.merge);
     return b;
 }
 

@@ -161,13 +161,17 @@ __global__ __launch_bounds__(1024) void sp_link_kernel(const uint32_t *__restric
 // that find no link take the owner as their hint and are attached afterwards.  MODE 1: the first matcher of a value whose label differs from the
 // owner's (bit 31 of the owner word, set with one atomic) unites the two trees.
 constexpr uint32_t SP_OWNER_MASK = 0x7FFFFFFFu;
+struct SpOlinkArgs { const uint32_t *ids; size_t N, Npad; uint32_t ncols; uint32_t *owner; size_t ostride; uint32_t stride; uint32_t *label, *hint; };
+// the body of workgroup (bx, by) of the grid ceil(N / 1024) x column pairs: 256 threads (sp_olink_kernel; MODE 0 also in the merged link launch, sp_link0_plan_kernel)
 template <int MODE>
-__global__ __launch_bounds__(256) void sp_olink_kernel(const uint32_t *__restrict__ ids, size_t N, size_t Npad, uint32_t ncols, uint32_t *__restrict__ owner, size_t ostride,
-                                                       uint32_t stride, uint32_t *label, uint32_t *__restrict__ hint) {
-    const size_t pair = (size_t)blockIdx.y * stride;
+__device__ __forceinline__ void sp_olink_body(const SpOlinkArgs &a, size_t bx, size_t by) {
+    const uint32_t *__restrict__ ids = a.ids;
+    uint32_t *__restrict__ owner = a.owner, *label = a.label, *__restrict__ hint = a.hint;
+    const size_t N = a.N, Npad = a.Npad, ostride = a.ostride;
+    const size_t pair = by * a.stride;
     const size_t t1 = 2 * pair, t2 = t1 + 1;
-    if (t2 >= ncols) return;
-    const size_t j0 = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (t2 >= a.ncols) return;
+    const size_t j0 = (bx * 256 + threadIdx.x) * 4;
     if (j0 >= N) return;
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
     const u32x4 w1 = *reinterpret_cast<const u32x4 *>(ids + t1 * Npad + j0);       // (Npad is a multiple of 256: aligned; the padding holds id 0)
@@ -202,14 +206,15 @@ __global__ __launch_bounds__(256) void sp_olink_kernel(const uint32_t *__restric
         }
     }
 }
+template <int MODE>
+__global__ __launch_bounds__(256) void sp_olink_kernel(SpOlinkArgs a) { sp_olink_body<MODE>(a, blockIdx.x, blockIdx.y); }
 
 // every label straight at its root (the walk halves the path behind it; plain loads and stores: a label is only ever replaced by an
 // ancestor, so racing with itself is harmless).  Between the two link passes: the uniting pass compares LABELS, and two members of a
 // family the propagation has put under one root still carry different earlier members until this ran (without it every matcher walked
 // to the roots through device-scope loads: 140 us at config 3 instead of 15).
-__global__ __launch_bounds__(256) void sp_flatten_kernel(uint32_t *label, size_t N, SpRider rider) {
-    SP_RIDE_OR_WORK(rider);
-    const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void sp_flatten_body(uint32_t *label, size_t N, size_t bx) {
+    const size_t j = bx * 256 + threadIdx.x;
     if (j >= N) return;
     uint32_t l = (uint32_t)j;
     for (int h = 0; h < 64; ++h) {
@@ -220,6 +225,38 @@ __global__ __launch_bounds__(256) void sp_flatten_kernel(uint32_t *label, size_t
         l = p;
     }
     if (label[l] == l) label[j] = l;
+}
+__global__ __launch_bounds__(256) void sp_flatten_kernel(uint32_t *label, size_t N, SpRider rider) {
+    SP_RIDE_OR_WORK(rider);
+    sp_flatten_body(label, N, blockIdx.x);
+}
+
+// ---- the merged schedule's two launches (d2g_bitslice_prepare): behind the rank kernel the column plan -> planes chain and the ordering's link passes
+// do not depend on each other until sp_permute, so the former rides INSIDE launches of the latter -- independent workgroups of one grid, as the fill's
+// riders do: no fence, no ticket, no second stream.  No body of a launch reads what another body of the same launch writes:
+//   link launch    column plan   reads colcnt[t][0..nsplit) (rank kernel), status      writes colcnt[t][0..4], perm, meta (+ the export target)
+//                  link pass 0   reads ids, owner, label, (hint)                        writes label, hint
+//                  riders                                                                write the announced output
+//   planes launch  flatten       reads / writes label
+//                  planes        reads ids, perm, meta (colcnt: split ranks only)       writes the caller's-order stream
+//                  riders                                                                write the announced output
+// One block shape per launch (256 threads): the plan's body runs with 256 threads as block 0 -- the lowest index, so that the one workgroup everything in the
+// NEXT launch waits for tends to start first; flatten's forty workgroups stand in front of the planes' for the same reason.  The 2-D grids are linearised.
+// (Measured, profiles/k2_merged_prepare.txt: the planes workgroups beside link pass 1, beside the scan's one workgroup, and handed out in shares to flatten /
+// count / attach / place like the fill's riders -- the step takes the same time within 2 us: the planes body moves 60 MB itself and every host already
+// carries a share of the fill, so it costs ~13 us of chain time wherever it stands.  The plan and flatten, a few workgroups each, do disappear.)
+__global__ __launch_bounds__(256) void sp_link0_plan_kernel(BsPlanArgs pa, SpOlinkArgs la, uint32_t nx, SpRider rider) {
+    SP_RIDE_OR_WORK(rider);
+    extern __shared__ __attribute__((aligned(16))) uint32_t plan_lds[];
+    if (blockIdx.x == 0) { bs_colplan_body<256>(pa, bs_plan_lds(plan_lds, (uint32_t)pa.ntb * 32u)); return; }
+    const uint32_t b = blockIdx.x - 1u;                                 // (nx = 0: no link pass, the grid ends here)
+    sp_olink_body<0>(la, b % nx, b / nx);
+}
+__global__ __launch_bounds__(256) void bs_planes_flatten_kernel(BsPlanesArgs a, uint32_t gx, uint32_t nflat, uint32_t *label, SpRider rider) {
+    SP_RIDE_OR_WORK(rider);
+    if (blockIdx.x < nflat) { sp_flatten_body(label, a.N, blockIdx.x); return; }
+    const uint32_t b = blockIdx.x - nflat;
+    bs_planes_body<false>(a, b % gx, b / gx);
 }
 
 // Behind the count kernel (the roots are final, root[] and cnt[] say who is alone): a sketch ALONE under its root joins the family its hints
@@ -1434,6 +1471,7 @@ int sp_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
 // what the kernel in front of sp_prepare_order initialises for it: label[j] = j, the hints, and the zero block (counters,
 // tile bitmap + global control words, order words, list cursor)
 SpInit sp_init_of(const d2g_cmp_set *set) {
+    if (!set->sp) return SpInit{};
     const SpState &sp = *set->sp;
     return SpInit{sp.d_label, sp.d_hint, sp.d_spz, (uint32_t)set->N, (uint32_t)(2 * set->Npad), (uint32_t)sp.spz_words};
 }
@@ -1646,6 +1684,23 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     return D2G_OK;
 }
 
+// the merged schedule's two launches (sp_link0_plan_kernel, bs_planes_flatten_kernel): column plan + link pass 0 (`l0`; null: a single column, no link
+// pass), then flatten (`nflat` workgroups; none for a single column) + planes.  Bits 1 and 2 of D2G_SP_RIDE name these two launches.
+int sp_launch_merged(d2g_ctx *ctx, d2g_cmp_set *set, const SpOlinkArgs *l0, unsigned nx, unsigned npair, unsigned nflat, hipStream_t s) {
+    SpState &sp = *set->sp;
+    const BsPlanArgs pa{set->d_colcnt, (uint32_t)set->S, set->ntb, 1, set->d_perm, set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, ctx->k2.sort ? 1 : 0};
+    const size_t nlink = (size_t)nx * npair, gx = div_up<size_t>(set->Nstride, 256), nplanes = gx * (size_t)set->ntb;
+    D2G_CHECK(ctx, 1 + nlink < 0x40000000u && nflat + nplanes < 0x40000000u, "bitslice sparse: a merged launch does not fit a grid");
+    unsigned g;
+    SpRider rd = sp.announced.take((unsigned)(1 + nlink), SP_RW_M_LINK0, false, 1, &g);
+    hipLaunchKernelGGL(sp_link0_plan_kernel, dim3(g), dim3(256), bs_plan_lds_words((uint32_t)set->ntb * 32u, pa.sort) * 4, s, pa, l0 ? *l0 : SpOlinkArgs{}, (uint32_t)nx, rd);
+    rd = sp.announced.take((unsigned)(nflat + nplanes), SP_RW_M_PLANES, false, 2, &g);
+    hipLaunchKernelGGL(bs_planes_flatten_kernel, dim3(g), dim3(256), 0, s, planes_args_of(set, set->d_planes, BS_FORM_STREAM), (uint32_t)gx, (uint32_t)nflat, sp.d_label.get(), rd);
+    sp.dec.kernels += 2;
+    D2G_HIP(ctx, hipGetLastError());
+    return D2G_OK;
+}
+
 // labels -> counting sort -> d_sperm / d_sinv -> pair list + segment tiles.  All on `s`, no host round trip.
 // where the path does not pay (one family, heavy noise, adversarial columns) the ordering that finds it out costs 0.05-0.2 ms
 // per prepare.  The decision is REMEMBERED per set: the kernels that raise order[0] also write a word in host-visible memory; a later
@@ -1664,7 +1719,9 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
     ++sp.dec.prepares;
     sp.dec.looked = sp.dec.pred_valid; sp.dec.looked_dense = sp.dec.pred_valid && sp.dec.pred_dense;   // (diagnostics: d2g_cmp_set_sparse_detail)
     sp.dec.pred_valid = false;                                           // (a prediction serves the prepare that made it)
+    D2G_CHECK(ctx, !(skip && sp.dec.merged), "bitslice sparse: the merged schedule was chosen for a prepare that skips the ordering");
     if (skip) {
+        ++sp.dec.kernels;
         hipLaunchKernelGGL(sp_giveup_kernel, dim3(1), dim3(64), 0, s, sp.d_order, sp.d_fullctl, (uint32_t)std::min<size_t>(sp_full_candidates(Npad), 0xFFFFFFFFu));
         D2G_HIP(ctx, hipGetLastError());
         sp.dec.skipped = true;
@@ -1682,20 +1739,30 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
         const uint32_t ustride = (uint32_t)std::max<size_t>(1, std::min<size_t>(SP_UNITE_STRIDE, npair / 32));   // at least 32 column pairs take part in the uniting pass
         if (sp.d_owner && !split && tu.olink) {                        // one holder per shared value at hand: the streaming form
             const unsigned nx = (unsigned)div_up<size_t>(N, 1024);
-            hipLaunchKernelGGL(sp_olink_kernel<0>, dim3(nx, npair), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, 1u, la, sp.d_hint);
-            { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
-            hipLaunchKernelGGL(sp_olink_kernel<1>, dim3(nx, div_up<unsigned>(npair, ustride)), dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, ustride, la, sp.d_hint);
+            const SpOlinkArgs l0{set->d_ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, 1u, la, sp.d_hint};
+            SpOlinkArgs l1 = l0; l1.stride = ustride;
+            if (!sp.dec.merged) {
+                hipLaunchKernelGGL(sp_olink_kernel<0>, dim3(nx, npair), dim3(256), 0, s, l0);
+                { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
+                sp.dec.kernels += 2;
+            } else if (int rc = sp_launch_merged(ctx, set, &l0, nx, npair, nb, s)) return rc;
+            hipLaunchKernelGGL(sp_olink_kernel<1>, dim3(nx, div_up<unsigned>(npair, ustride)), dim3(256), 0, s, l1);
+            sp.dec.kernels += 1;
         } else {
             hipLaunchKernelGGL(sp_link_kernel<0>, dim3(npair), dim3(1024), (size_t)cap * 12, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, 1u,
                                la, sp.d_hint);
             { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
             hipLaunchKernelGGL(sp_link_kernel<1>, dim3(div_up<unsigned>(npair, ustride)), dim3(1024), (size_t)cap * 8, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, ustride,
                                la, sp.d_hint);
+            sp.dec.kernels += 3;
         }
+    } else if (sp.dec.merged) {                                        // (one column: no link pass -- the plan alone, then the planes alone)
+        if (int rc = sp_launch_merged(ctx, set, nullptr, 0, 0, 0, s)) return rc;
     }
     const size_t ntile_all = (Npad / 32) * (Npad / BS_CB);
     const uint32_t seg_limit = (uint32_t)std::min<size_t>((size_t)((double)ntile_all * tu.tile_frac), 0x3FFFFFFF);
     // (one single-workgroup kernel for count + scan + place with the counters in LDS was measured at N = 10 000: 25 us against 19 for the three)
+    sp.dec.kernels += 4 + ((tu.link && S >= 2) ? 1 : 0) + (sp.dec.big ? 1 : 0);   // count, (attach,) scan, place, emit, (pairs)
     { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_COUNT, false, 4, &g); hipLaunchKernelGGL(sp_count_kernel, dim3(g), dim3(256), 0, s, la, lb, N, sp.d_lcnt, sp.d_order, rd); }
     if (tu.link && S >= 2) {
         unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_ATTACH, false, 8, &g);
@@ -1747,6 +1814,7 @@ int sp_permute(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     const size_t lds = std::max<size_t>((size_t)part * (both ? 8 : 4), sp.dec.big ? (size_t)sp.nbins * 4 : 0);
     auto kern = both ? sp_permute_lds_kernel<true> : sp_permute_lds_kernel<false>;
     D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 157 * 1024));   // (+ ~2 KB of static LDS: the list builders, the pairs of a short list)
+    sp.dec.kernels += 1 + (sp.dec.big ? 1 : 0);                        // permute (, bin)
     hipLaunchKernelGGL(kern, dim3((unsigned)(nperm + fl.nwg + hs.nhw)), dim3(1024), lds, s, set->d_stream, sp.d_stream_s, set->Nstride, set->d_meta,
                        sp.d_sperm, sp.d_order, fl, (uint32_t)nperm, (uint32_t)set->nbits_cap, H, part, hs, sp_pairs_of(sp, sp_colwork_of(sp), sp.d_label + set->Npad));
     if (sp.dec.big) {                                                  // the list, bin by bin (d_plist2): as many workgroups as the counting ones

@@ -386,8 +386,10 @@ int  d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream,
 /* diagnostics of the last prepare's sparse path (synchronises `stream`; all 0 for a set without one): [0] 1 = the prepare took the first look at its
  * matrix (sixteen sampled sketches against all), [1] 1 = the first look decided for the dense walk, [2..5] that look's raw sums (0 without one): register
  * counts below 4 (E), pairs at 4 or more (F), shared values over all columns, id planes over all columns; [6] 1 = the pair list went through
- * the binned + composed form, [7] the set's bin width (log2 of the columns of a chunk).  Nothing in the product reads these back. */
-int  d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out8);
+ * the binned + composed form, [7] the set's bin width (log2 of the columns of a chunk), [8] the schedule of the last prepare: 1 = merged (column plan and
+ * planes inside launches of the ordering), 0 = classic (kernel by kernel: D2G_K2_MERGE=0, a first look, a remembered give-up, the table form of the link
+ * passes, split rank passes), [9] the kernels that prepare enqueued, the transpose included.  out10: TEN words.  Nothing in the product reads these back. */
+int  d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out10);
 /* the output bins of the pair list of a set of N sketches (bands of 32 rows x chunks of 2^cshift columns): what a set's allocation computes.
  * binned_ok = 0: more bands than bins fit, the list is applied entry by entry (nbins = 0).  Host arithmetic, no context. */
 int  d2g_sparse_bin_geometry(size_t N, uint32_t *cshift, uint32_t *nch, uint32_t *nbins, int *binned_ok);

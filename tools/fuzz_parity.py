@@ -94,7 +94,7 @@ def main():
                 # entry or binned + composed, with or without the first look at the matrix; the other half takes the default (dense walk
                 # below 8192 sketches)
                 for var in ("D2G_SP_RIDE", "D2G_BS_SPARSE_MIN_N", "D2G_SP_LINK", "D2G_SP_TILE_FRAC", "D2G_SP_LIST_DIV", "D2G_SP_OLINK", "D2G_SP_REMEMBER", "D2G_SP_EMIT_BIG",
-                            "D2G_SP_LIST_FORM", "D2G_SP_PREDICT"):
+                            "D2G_SP_LIST_FORM", "D2G_SP_PREDICT", "D2G_K2_MERGE"):
                     os.environ.pop(var, None)
                 if rng.random() < 0.5:
                     os.environ["D2G_BS_SPARSE_MIN_N"] = "1"
@@ -110,6 +110,8 @@ def main():
                         os.environ["D2G_SP_OLINK"] = "0"                                      # the link passes in their table form
                     if rng.random() < 0.3:
                         os.environ["D2G_SP_EMIT_BIG"] = "1"                                   # the pair-list kernel's form for N >= 65 536
+                    if rng.random() < 0.3:
+                        os.environ["D2G_K2_MERGE"] = "0"                                      # the prepare's classic schedule (merged: needs D2G_SP_PREDICT=0 on a one-shot set)
                     os.environ["D2G_SP_REMEMBER"] = "0"                                       # one-shot sets: every prepare decides afresh
                 ctx.reload_tuning()
                 r = rng.random()
