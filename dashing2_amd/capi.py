@@ -19,6 +19,7 @@ BITSLICE_OPS_PER_GROUP_EXTRA = 1
 
 TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0 = 2, 4, 8, 16, 32          # include/d2g.h D2G_TIME_*
 TIME_KNN = 64
+TIME_DEDUP = 128
 
 
 class D2GError(RuntimeError):
@@ -176,6 +177,10 @@ SIGNATURES = {
     "d2g_knn_finish": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _int, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
     "d2g_cmp_set_knn": (_int, [_vp, _vp, _sz, _sz, _vp, _int, _sz, _dbl, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "d2g_cmp_knn": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _sz, _dbl, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    "d2g_cmp_dedup_dev": (_int, [_vp, _vp, C.c_uint32, _vp, _vp, _sz, _vp]),
+    "d2g_dedup_clusters": (_int, [_vp, _sz, _vp, _vp, C.POINTER(_sz)]),
+    "d2g_cmp_set_dedup": (_int, [_vp, _vp, _vp, _dbl, _sz, _vp]),
+    "d2g_cmp_dedup": (_int, [_vp, _vp, _sz, _sz, _int, _int, _int, _int, _dbl, _sz, _vp]),
 }
 
 
@@ -378,6 +383,20 @@ def knn_finish(rowcnt, ids, counts, cap, lut, isdist=False):
         if rc:
             raise D2GError(rc)
     return indptr, indices, data
+
+
+def dedup_clusters(assign):
+    """assign [N] (the representative of every sketch) -> (indptr u64 [C+1], indices u32 [N]): clusters in creation order, the
+    representative first, then the members in input order"""
+    assign = np.ascontiguousarray(assign, np.uint32)
+    n = assign.size
+    indptr = np.zeros(n + 1, np.uint64)
+    indices = np.empty(n, np.uint32)
+    nc = _sz()
+    rc = lib().d2g_dedup_clusters(_np_ptr(assign), n, _np_ptr(indptr), _np_ptr(indices), C.byref(nc))
+    if rc:
+        raise D2GError(rc)
+    return indptr[:nc.value + 1].copy(), indices
 
 
 def operand_layout(N, S):
@@ -730,6 +749,15 @@ class Context:
         return _knn_csr(self, r1 - r0, K, lambda ip, ix, dt, oc, need: lib().d2g_cmp_knn(
             self._h, _np_ptr(a), N, S, r0, r1, measure, k, int(multiset_space), algo, K, float(threshold), cap, band_rows, ip, ix, dt, oc, need))
 
+    def cmp_dedup(self, sig_bits_host, threshold, measure=SIMILARITY, k=31, multiset_space=False, algo=CMP_AUTO, band_rows=0):
+        """greedy clustering in input order (cmp --greedy): -> assign u32 [N], the representative of every sketch"""
+        a = np.ascontiguousarray(sig_bits_host)
+        assert a.dtype.itemsize == 8 and a.ndim == 2
+        N, S = a.shape
+        out = np.empty(N, np.uint32)
+        self._check(lib().d2g_cmp_dedup(self._h, _np_ptr(a), N, S, measure, k, int(multiset_space), algo, float(threshold), band_rows, _np_ptr(out)))
+        return out
+
     # -- raw device memory (tests / bench without torch) ------------------------
     def malloc(self, nbytes):
         p = _vp()
@@ -1011,6 +1039,18 @@ class CmpSet:
         r1 = self.N if r1 is None else r1
         return _knn_csr(self.ctx, r1 - r0, K, lambda ip, ix, dt, oc, need: lib().d2g_cmp_set_knn(
             self.ctx._h, self._h, r0, r1, _np_ptr(lut), int(bool(isdist)), K, float(threshold), cap, band_rows, ip, ix, dt, oc, need))
+
+    def dedup_dev(self, assign_dev_ptr, min_count, cls_dev_ptr=None, band_rows=0, stream=None):
+        """d2g_cmp_dedup_dev: greedy clustering of the whole set on the device, assign_dev_ptr = u32 [N]"""
+        self.ctx._check(lib().d2g_cmp_dedup_dev(self.ctx._h, self._h, min_count, cls_dev_ptr, assign_dev_ptr, band_rows, stream))
+
+    def dedup(self, lut, threshold, band_rows=0):
+        """d2g_cmp_set_dedup: -> assign u32 [N] for the non-decreasing value table lut[S+1]"""
+        lut = np.ascontiguousarray(lut, np.float32)
+        assert lut.size == self.S + 1
+        out = np.empty(self.N, np.uint32)
+        self.ctx._check(lib().d2g_cmp_set_dedup(self.ctx._h, self._h, _np_ptr(lut), float(threshold), band_rows, _np_ptr(out)))
+        return out
 
     def gtlt_rect_dev(self, gt_dev_ptr, lt_dev_ptr, a0, a1, b0, b1, stream=None):
         self.ctx._check(lib().d2g_cmp_gtlt_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, gt_dev_ptr, lt_dev_ptr, stream))

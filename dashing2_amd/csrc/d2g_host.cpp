@@ -472,6 +472,24 @@ int d2g_knn_finish(const uint32_t *rowcnt, const uint32_t *ids, const uint32_t *
     return D2G_OK;
 }
 
+// assign[] of the greedy clustering -> dedup_core's (ids, constituents) as one CSR: clusters in creation order, which is the
+// ascending order of their representatives (a representative is the first sketch of its cluster in input order)
+int d2g_dedup_clusters(const uint32_t *assign, size_t N, uint64_t *indptr, uint32_t *indices, size_t *nclusters) {
+    if (!indptr || !nclusters || (N && (!assign || !indices))) return D2G_ERR_INVALID;
+    for (size_t i = 0; i < N; ++i)
+        if (assign[i] > i || assign[assign[i]] != assign[i]) return D2G_ERR_INVALID;
+    std::vector<uint32_t> cid(N);                             // cluster of a representative; then the next free slot of a cluster
+    size_t C = 0;
+    for (size_t i = 0; i < N; ++i) if (assign[i] == i) cid[i] = (uint32_t)C++;
+    std::vector<uint64_t> fill(C + 1, 0);
+    for (size_t i = 0; i < N; ++i) ++fill[cid[assign[i]] + 1];
+    indptr[0] = 0;
+    for (size_t c = 0; c < C; ++c) { indptr[c + 1] = indptr[c] + fill[c + 1]; fill[c] = indptr[c]; }
+    for (size_t i = 0; i < N; ++i) indices[fill[cid[assign[i]]]++] = (uint32_t)i;     // in input order: the representative comes first
+    *nclusters = C;
+    return D2G_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------

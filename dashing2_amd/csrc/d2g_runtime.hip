@@ -202,7 +202,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     }
     if (what & D2G_WARM_K0) d2g_warm_k0();
     if (what & D2G_WARM_K1) d2g_warm_k1();
-    if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); d2g_warm_knn(); }
+    if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); d2g_warm_knn(); d2g_warm_dedup(); }
     if (what & D2G_WARM_K3) d2g_warm_k3();
     return D2G_OK;
 }
@@ -216,33 +216,39 @@ int d2g_device_name(int device, char *buf, size_t cap) {
 
 int d2g_set_timing(d2g_ctx *c, int enabled) {
     if (!c) return D2G_ERR_INVALID;
-    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN) : (enabled & ~1);
+    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP) : (enabled & ~1);
     return D2G_OK;
 }
 
 int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *avg_ms, float *last_ms) {
     if (!c || !which) return D2G_ERR_INVALID;
-    d2g_evlog *e = nullptr;
+    d2g_evlog *e = nullptr, *e2 = nullptr;                   // e2: a second log summed under the same name
     if (!std::strcmp(which, "k1")) e = &c->ev_k1;
     else if (!std::strcmp(which, "k2")) e = &c->ev_k2;
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;
     else if (!std::strcmp(which, "k3")) e = &c->ev_k3;
     else if (!std::strcmp(which, "k0")) e = &c->ev_k0;
     else if (!std::strcmp(which, "knn")) e = &c->ev_knn;
+    else if (!std::strcmp(which, "dedup")) { e = &c->ev_dedup; e2 = &c->ev_dedup_resolve; }
+    else if (!std::strcmp(which, "dedup_resolve")) e = &c->ev_dedup_resolve;
     D2G_CHECK(c, e != nullptr, "d2g_kernel_ms: unknown kernel name");
     D2G_HIP(c, hipSetDevice(c->device));
     double sum = 0;
     float last = 0.f;
-    for (size_t i = 0; i < e->a.size(); ++i) {
-        D2G_HIP(c, hipEventSynchronize(e->b[i]));
-        D2G_HIP(c, hipEventElapsedTime(&last, e->a[i], e->b[i]));
-        sum += last;
+    int n = 0;
+    for (d2g_evlog *l : {e, e2}) {
+        if (!l) continue;
+        for (size_t i = 0; i < l->a.size(); ++i) {
+            D2G_HIP(c, hipEventSynchronize(l->b[i]));
+            D2G_HIP(c, hipEventElapsedTime(&last, l->a[i], l->b[i]));
+            sum += last;
+        }
+        n += (int)l->a.size();
     }
-    const int n = (int)e->a.size();
     if (count) *count = n;
     if (avg_ms) *avg_ms = n ? (float)(sum / n) : 0.f;
     if (last_ms) *last_ms = last;
-    if (reset) { e->a.clear(); e->b.clear(); }
+    if (reset) for (d2g_evlog *l : {e, e2}) if (l) { l->a.clear(); l->b.clear(); }
     return D2G_OK;
 }
 

@@ -116,6 +116,18 @@ int main() {
         const std::vector<uint32_t> big = {4, 0, 1, 2};
         REQUIRE(d2g_knn_finish(big.data(), ids.data(), cts.data(), n, cap, lut, S, 0, indptr.data(), indices.data(), data.data(), 6, &need, &over) == D2G_ERR_INVALID && over == 1);
     }
+    // ---- greedy clusters: exactly-sized arrays; a malformed assignment is refused before anything is indexed with it
+    {
+        const std::vector<uint32_t> assign = {0, 0, 2, 3, 3, 0};
+        std::vector<uint64_t> indptr(assign.size() + 1);
+        std::vector<uint32_t> indices(assign.size());
+        size_t nc = 99;
+        REQUIRE(d2g_dedup_clusters(assign.data(), assign.size(), indptr.data(), indices.data(), &nc) == D2G_OK && nc == 3);
+        REQUIRE(indptr[1] == 3 && indptr[2] == 4 && indptr[3] == 6 && indices[0] == 0 && indices[1] == 1 && indices[2] == 5 && indices[3] == 2 && indices[5] == 4);
+        for (const std::vector<uint32_t> &bad : {std::vector<uint32_t>{1, 1}, {0, 2, 2}, {0, 0, 1}, {0, 4000000000u}})
+            REQUIRE(d2g_dedup_clusters(bad.data(), bad.size(), indptr.data(), indices.data(), &nc) == D2G_ERR_INVALID);
+        REQUIRE(d2g_dedup_clusters(nullptr, 0, indptr.data(), nullptr, &nc) == D2G_OK && nc == 0 && indptr[0] == 0);
+    }
     REQUIRE(d2g_wang_hash(133348) != 0 && d2g_seed_mask(0) == 0 && d2g_seed_mask(5) != 0);
     std::printf("host selftest OK\n");
     return 0;

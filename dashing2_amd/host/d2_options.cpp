@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -63,7 +63,13 @@ void cmp_usage() {
                          "--similarity-threshold T\t ... or every pair whose similarity is at least T (with --mash-distance: whose distance is at most T).\n"
                          "\t\t Output: one line per sketch `name<TAB>neighbour:value...`, or with --binary-output CSR: u64 nids, u64 nnz,\n"
                          "\t\t u64 indptr[nids+1], u32 indices[nnz], f32 data[nnz].  Similarity and --mash-distance, full 8-byte registers, one GPU;\n"
-                         "\t\t not with -Q, --square, --phylip, --fastcmp <4|2|1>.\n");
+                         "\t\t not with -Q, --square, --phylip, --fastcmp <4|2|1>.\n"
+                         "--greedy T[E]\t Greedy clustering (dereplication) instead of a matrix: in input order, a sketch joins the cluster whose\n"
+                         "\t\t representative is most similar to it if that similarity is at least T (T <= 0: 0.9), else it founds a cluster; it is\n"
+                         "\t\t compared with representatives only.  Clustered on the GPU, always exhaustively (with or without the E suffix).\n"
+                         "\t\t Output: `Cluster-c<TAB>name:id...` per cluster, representative first, or with --binary-output u64 nclusters, u64 nnz,\n"
+                         "\t\t u64 indptr[nclusters+1], u32 ids[nnz].  Similarity only, full 8-byte registers, one GPU; not with the F suffix, -Q,\n"
+                         "\t\t --square, --phylip, --topk, --similarity-threshold, --fastcmp <4|2|1>.\n");
     sketch_usage();
 }
 
@@ -141,8 +147,9 @@ int parse_options(int argc, char **argv, Options &o) {
         all.push_back({"topk", required_argument, 0, OPT_TOPK});
         all.push_back({"top-k", required_argument, 0, OPT_TOPK});
         all.push_back({"similarity-threshold", required_argument, 0, OPT_SIMTHRESH});
+        all.push_back({"greedy", required_argument, 0, OPT_GREEDY});
     }
-    bool saw_square = false, saw_phylip = false, gave_topk = false, gave_thresh = false;
+    bool saw_square = false, saw_phylip = false, gave_topk = false, gave_thresh = false, greedy_fasta = false;
     std::set<std::string> have;
     for (auto &x : all) have.insert(x.name);
     static const std::set<std::string> with_arg = {"topk", "top-k", "similarity-threshold", "fastcmp", "regsize", "regbytes",
@@ -207,6 +214,11 @@ int parse_options(int argc, char **argv, Options &o) {
             } break;
             case OPT_TOPK: o.topk = std::atoi(optarg); gave_topk = true; break;                             // options.h:308
             case OPT_SIMTHRESH: o.min_similarity = std::atof(optarg); gave_thresh = true; break;       // options.h:309
+            case OPT_GREEDY: {                                                      // options.h:310-318
+                char *eptr;
+                o.greedy = true; o.greedy_t = std::strtod(optarg, &eptr);
+                for (; *eptr; ++eptr) if ((*eptr | 32) == 'f') greedy_fasta = true;    // 'e' (exhaustive): the only route here
+            } break;
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
             case OPT_UNSUPPORTED:
@@ -250,6 +262,27 @@ int parse_options(int argc, char **argv, Options &o) {
     if (o.w > o.k) {
         std::fprintf(stderr, "dashing2 (MI355X): windowed minimizers (-w > k) are outside this build's hot-path scope.\n");
         return 1 + 1;
+    }
+    if (o.is_cmp && o.greedy) {
+        const char *why = nullptr;
+        if (greedy_fasta) why = "--greedy with the F suffix (FASTA output of the representatives' sequences)";
+        else if (gave_topk || gave_thresh) why = "--greedy together with --topk / --similarity-threshold";
+        else if (!o.qfile.empty()) why = "greedy clustering of a query panel (-Q)";
+        else if (saw_square) why = "--greedy together with --square / --asymmetric-all-pairs";
+        else if (saw_phylip) why = "--greedy together with --phylip";
+        else if (o.regbytes < 8) why = "greedy clustering of truncated registers (--fastcmp <4|2|1>)";
+        else if (o.measure == D2G_POISSON_LLR)
+            why = "greedy clustering by --mash-distance (with a distance the reference founds a new cluster when the nearest representative is closer than T)";
+        else if (o.measure != D2G_SIMILARITY)
+            why = "greedy clustering by a cardinality-dependent measure (containment, symmetric containment, intersection, union size): its value is not a function of the equality count";
+        else if (!o.presketched && o.sspace == SPACE_SET && (o.sketchsize & (o.sketchsize - 1)) != 0)
+            why = "greedy clustering with a sketch size that is not a power of two in set space: its value needs (gt, lt) counts, not the equality count";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): %s is outside the hot-path scope of this build "
+                                 "(--greedy T or TE; similarity; 8-byte registers; one matrix).\n", why);
+            return 1 + 1;
+        }
+        o.ok = DEDUP;
     }
     if (o.is_cmp && (gave_topk || gave_thresh)) {
         if (o.topk > 0 && o.min_similarity > 0.) {             // Dashing2DistOptions::validate, cmp_main.h:102-104

@@ -39,6 +39,8 @@ struct Options {
     bool bbit_sigs = false;               // --bbit-sigs (options.h:101): b-bit truncation instead of the logarithmic (setsketch) one; no effect at 8 bytes
     int topk = -1;                        // cmp --topk/--top-k K (options.h:308): ok = KNN_GRAPH, the K nearest neighbours of every sketch, ties with the K-th kept
     double min_similarity = -1.;          // cmp --similarity-threshold T (options.h:309): ok = NN_GRAPH_THRESHOLD, every pair at T or beyond
+    bool greedy = false;                  // cmp --greedy T[E] (options.h:310-318): ok = DEDUP, greedy clustering in input order; always the exhaustive route (the E suffix is accepted, the LSH route is out of scope)
+    double greedy_t = 0.;                 // ... its threshold as parsed (printed in the header); <= 0 clusters at the reference's default of 0.9 (dedup_core.cpp:264)
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -96,9 +96,9 @@ struct Stats {
     void num(const std::string &k, double v) { raw(k, numstr(v)); }
     void str(const std::string &k, const std::string &v) { raw(k, esc(v)); }
     // {"launches": n, "avg_ms": a, "total_ms": n a} of one timed kernel family on one context (synchronises on its events)
-    static std::string kernel_json(d2g_ctx *ctx, const char *which) {
+    static std::string kernel_json(d2g_ctx *ctx, const char *which, bool reset = true) {
         int n = 0; float avg = 0, last = 0;
-        if (d2g_kernel_ms(ctx, which, 1, &n, &avg, &last) != D2G_OK) return "null";
+        if (d2g_kernel_ms(ctx, which, reset, &n, &avg, &last) != D2G_OK) return "null";
         return "{\"launches\": " + std::to_string(n) + ", \"avg_ms\": " + numstr(avg) + ", \"total_ms\": " + numstr(double(avg) * n) + "}";
     }
     void write() {
@@ -112,7 +112,7 @@ struct Stats {
     }
 };
 Stats g_stats;
-constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN;
+constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP;
 
 // D2G_DEVICES = "all" | "0,1,2": the GPUs a job may spread over -- `sketch` deals its input groups to them (no collectives),
 // `cmp` shards the rows of the matrix (one exchange).  Default: the one device D2G_DEVICE names.  A list that repeats
@@ -1100,6 +1100,78 @@ void cmp_core_knn(const Options &o, const Result &res, d2g_ctx *ctx, const std::
     if (g_release_at_exit) d2g_cmp_set_destroy(set);
 }
 
+// ------------------------------------------------------------------------------------ cmp: greedy clustering
+// What only the inputs tell (the sketch space and size of --presketched files); the flag combinations are refused in d2_options.cpp.
+const char *dedup_refusal(const Options &o, size_t S) {
+    if (o.sspace == SPACE_SET && (S & (S - 1)) != 0)
+        return "greedy clustering with a sketch size that is not a power of two in set space: its value needs (gt, lt) counts, not the equality count";
+    if (o.sspace == SPACE_PSET) return "greedy clustering of ProbMinHash sketches";
+    return nullptr;
+}
+
+// dedup_emit, src/dedup_core.cpp:400-451 (text and binary forms; the FASTA form is out of scope).  The two doubles of the header are
+// fmt's "{}" (format_double; PARITY UNPINNED like the other fmt rows).
+void emit_clusters(const Options &o, const Result &res, const std::vector<uint64_t> &indptr, const std::vector<uint32_t> &indices, size_t nclusters) {
+    const std::string outp = (o.cmpout.empty() || o.cmpout.front() == '-') ? "/dev/stdout" : o.cmpout;
+    std::FILE *fp = outp == "/dev/stdout" ? stdout : std::fopen(outp.c_str(), "wb");
+    if (!fp) die("Failed to open file " + outp + " for writing");
+    const size_t ns = res.names.size();
+    bool good = true;
+    if (o.of == HUMAN_READABLE) {
+        char avg[64], thr[64];
+        avg[format_double(double(ns) / double(nclusters), avg)] = 0;     // 0 items: 0 / 0 = "nan" (fmt prints -nan as "-nan"; x86 gives the negative one)
+        thr[format_double(o.greedy_t, thr)] = 0;
+        std::string text = "#Clustering " + std::to_string(ns) + " items yielded " + std::to_string(nclusters) + " clusters of average size " + avg +
+                           ", separated by minimum similarity " + thr + "\n";
+        for (size_t c = 0; c < nclusters; ++c) {
+            text += "Cluster-" + std::to_string(c);
+            for (uint64_t e = indptr[c]; e < indptr[c + 1]; ++e) { text += '\t'; text += res.names[indices[e]]; text += ':'; text += std::to_string(indices[e]); }
+            text += '\n';
+            if (text.size() >= (size_t(1) << 22)) { good = good && std::fwrite(text.data(), 1, text.size(), fp) == text.size(); text.clear(); }
+        }
+        if (!text.empty()) good = good && std::fwrite(text.data(), 1, text.size(), fp) == text.size();
+    } else {
+        const uint64_t dims[2] = {uint64_t(nclusters), uint64_t(ns)};    // nnz = every item once
+        good = std::fwrite(dims, 8, 2, fp) == 2 && std::fwrite(indptr.data(), 8, nclusters + 1, fp) == nclusters + 1 &&
+               std::fwrite(indices.data(), 4, ns, fp) == ns;
+    }
+    good = good && std::fflush(fp) == 0;
+    if (fp != stdout) std::fclose(fp);
+    if (!good) die("Failed to write clusters to " + outp);
+}
+
+// cmp_core.cpp:800-805 with the exhaustive branch of dedup_core (dedup_core.cpp:262-283): clustered on the GPU (d2g_cmp_set_dedup), only
+// the representative of every sketch comes back.
+void cmp_core_dedup(const Options &o, const Result &res, d2g_ctx *ctx, const std::vector<float> &lut, double t_densify) {
+    const size_t ns = res.names.size(), S = o.sketchsize;
+    const double t0 = now();
+    d2g_cmp_set *set = nullptr;
+    check(ctx, d2g_cmp_set_create(ctx, reinterpret_cast<const uint64_t *>(res.sigs()), ns, S, int(D2G_CMP_AUTO), &set), "d2g_cmp_set_create");
+    const double t_set = now();
+    std::vector<uint32_t> assign(ns), indices(ns);
+    std::vector<uint64_t> indptr(ns + 1, 0);
+    check(ctx, d2g_cmp_set_dedup(ctx, set, lut.data(), o.greedy_t, 0, assign.data()), "d2g_cmp_set_dedup");
+    size_t nclusters = 0;
+    if (d2g_dedup_clusters(assign.data(), ns, indptr.data(), indices.data(), &nclusters) != D2G_OK) die("dashing2 (MI355X): the clustering came back malformed");
+    const double t_sel = now();
+    emit_clusters(o, res, indptr, indices, nclusters);
+    const double t_emit = now();
+    if (o.verbosity) std::fprintf(stderr, "[d2g] cmp --greedy: %zu sketches x S=%zu: upload+prepare %.3fs, clustering %.3fs (%zu clusters), emit %.3fs\n",
+                                  ns, S, t_set - t0, t_sel - t_set, nclusters, t_emit - t_sel);
+    if (g_stats.on) {
+        const bool bs = d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE;
+        const std::string resolve_json = Stats::kernel_json(ctx, "dedup_resolve", false);     // a part of "dedup": read before that one clears both
+        g_stats.raw("cmp", std::string("{\"sketches\": ") + std::to_string(ns) + ", \"sketchsize\": " + std::to_string(S) + ", \"shape\": \"greedy\"" +
+                    ", \"threshold\": " + Stats::numstr(o.greedy_t) + ", \"clusters\": " + std::to_string(nclusters) + ", \"algo\": " + (bs ? "\"bitslice\"" : "\"direct\"") +
+                    ", \"bytes_to_host\": " + Stats::numstr(4.0 * double(ns)) +
+                    ", \"devices\": [{\"index\": " + std::to_string(o.device) + ", \"name\": " + Stats::esc(device_label(o.device)) + ", \"k2\": " + Stats::kernel_json(ctx, "k2") +
+                    ", \"dedup_resolve\": " + resolve_json + ", \"dedup\": " + Stats::kernel_json(ctx, "dedup") + ", \"k2prep\": " + Stats::kernel_json(ctx, "k2prep") + "}]" +
+                    ", \"wall_s\": {\"densify_scan\": " + Stats::numstr(t_densify) + ", \"upload_prepare\": " + Stats::numstr(t_set - t0) +
+                    ", \"count_cluster_d2h\": " + Stats::numstr(t_sel - t_set) + ", \"emit\": " + Stats::numstr(t_emit - t_sel) + "}}");
+    }
+    if (g_release_at_exit) d2g_cmp_set_destroy(set);
+}
+
 void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_core.cpp:615-751 (dense outputs)
     const size_t ns = res.names.size(), S = o.sketchsize;
     if (res.nsigs() != ns * S) die("Empty signatures; trying to compare but don't have any");
@@ -1140,6 +1212,14 @@ void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_cor
         if (job_devices(o).size() > 1)
             std::fprintf(stderr, "[d2g] D2G_DEVICES ignored for this job (%s): it runs on GPU %d alone\n", "the nearest-neighbour selection runs on one GPU", o.device);
         cmp_core_knn(o, res, ctx, lut, t_densify);
+        return;
+    }
+    if (o.ok == DEDUP) {                                            // cmp_core.cpp:800-805
+        if (const char *why = dedup_refusal(o, S)) knn_refuse(why);
+        if (!have_lut) knn_refuse("greedy clustering of values that are not a function of the equality count");
+        if (job_devices(o).size() > 1)
+            std::fprintf(stderr, "[d2g] D2G_DEVICES ignored for this job (%s): it runs on GPU %d alone\n", "the greedy clustering runs on one GPU", o.device);
+        cmp_core_dedup(o, res, ctx, lut, t_densify);
         return;
     }
     {
@@ -1325,6 +1405,9 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
     if (o.ok == KNN_GRAPH || o.ok == NN_GRAPH_THRESHOLD)            // refused before a context exists
         if (const size_t S = o.presketched ? presketched_sketchsize(o) : o.sketchsize)
             if (const char *why = knn_refusal(o, S)) knn_refuse(why);
+    if (o.ok == DEDUP)
+        if (const size_t S = o.presketched ? presketched_sketchsize(o) : o.sketchsize)
+            if (const char *why = dedup_refusal(o, S)) knn_refuse(why);
     LazyCtx lctx(o, D2G_WARM_COPY | D2G_WARM_K2 | (o.presketched ? 0 : (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
     Result res;
     if (o.presketched) {

@@ -1,10 +1,15 @@
 // fmtcheck <table> [fmt-compat]: reads "<hexbits>\t<expected>" lines, checks d2h::format_float; used by tests/test_host.py
+// fmtcheck --double <number>...: prints d2h::format_double of every argument (strtod: decimal or hex-float text), one per line
 #include "fmtfloat.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 int main(int argc, char **argv) {
     if (argc < 2) return 2;
+    if (!std::strcmp(argv[1], "--double")) {
+        for (int i = 2; i < argc; ++i) { char out[64]; out[d2h::format_double(std::strtod(argv[i], nullptr), out)] = 0; std::printf("%s\n", out); }
+        return 0;
+    }
     if (argc > 2 && !d2h::set_fmt_compat(std::atoi(argv[2]))) return 2;
     std::FILE *f = std::fopen(argv[1], "r");
     if (!f) return 2;

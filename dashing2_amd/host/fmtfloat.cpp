@@ -17,16 +17,16 @@ bool set_fmt_compat(int fmt_major) {
 }
 int fmt_compat() { return g_exp_upper == 16 ? 10 : 11; }
 
-size_t format_float(float v, char *out) {
+template <class F> static size_t format_fp(F v, char *out, int exp_upper) {
     char *p = out;
     if (std::signbit(v)) { *p++ = '-'; v = -v; }
     if (std::isinf(v)) { std::memcpy(p, "inf", 3); return size_t(p - out) + 3; }
     if (std::isnan(v)) { std::memcpy(p, "nan", 3); return size_t(p - out) + 3; }
-    if (v == 0.f) { *p++ = '0'; return size_t(p - out); }
+    if (v == F(0)) { *p++ = '0'; return size_t(p - out); }
     // shortest round-trip digits in scientific form: d[.ddd]e[+-]XX
-    char sci[32];
+    char sci[40];
     auto res = std::to_chars(sci, sci + sizeof(sci), v, std::chars_format::scientific);
-    char digits[16];
+    char digits[24];
     int nd = 0;
     const char *q = sci;
     for (; q < res.ptr && *q != 'e'; ++q)
@@ -40,7 +40,7 @@ size_t format_float(float v, char *out) {
         if (neg) exp10 = -exp10;
     }
     while (nd > 1 && digits[nd - 1] == '0') --nd;         // (to_chars never pads, defensive)
-    if (exp10 >= -4 && exp10 < g_exp_upper) {
+    if (exp10 >= -4 && exp10 < exp_upper) {
         if (exp10 >= nd - 1) {                            // integer: digits then zeros
             std::memcpy(p, digits, nd); p += nd;
             for (int i = 0; i < exp10 - (nd - 1); ++i) *p++ = '0';
@@ -65,5 +65,8 @@ size_t format_float(float v, char *out) {
     *p++ = char('0' + ae % 10);
     return size_t(p - out);
 }
+
+size_t format_float(float v, char *out) { return format_fp(v, out, g_exp_upper); }
+size_t format_double(double v, char *out) { return format_fp(v, out, 16); }
 
 }  // namespace d2h

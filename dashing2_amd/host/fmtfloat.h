@@ -13,6 +13,8 @@ namespace d2h {
 constexpr int FMT_MAX_FLOAT_CHARS = 48;
 // writes the text (no terminator) at out, returns its length
 size_t format_float(float v, char *out);
+// ... and of a double: the fixed range is [-4, 16) in every fmt (digits10 + 1 of a double is 16), --fmt-compat does not matter
+size_t format_double(double v, char *out);
 bool set_fmt_compat(int fmt_major);   // 10 (default) or 11; false for anything else
 int  fmt_compat();
 }  // namespace d2h

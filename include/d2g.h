@@ -105,6 +105,8 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
 #define D2G_TIME_K3     16
 #define D2G_TIME_K0     32
 #define D2G_TIME_KNN    64      /* "knn": the selection kernel of d2g_cmp_knn_dev (its count walk is logged as "k2") */
+#define D2G_TIME_DEDUP  128     /* "dedup": the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the in-order
+                                 * step alone; the count walk is logged as "k2") */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -527,6 +529,36 @@ int  d2g_cmp_set_knn(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1,
 int  d2g_cmp_knn(d2g_ctx *ctx, const uint64_t *sig_bits, size_t N, size_t sketchsize, size_t r0, size_t r1, int measure, int k,
                  int multiset_space, int algo, size_t K, double threshold, size_t cap, size_t band_rows,
                  uint64_t *indptr_out /* [r1-r0+1] */, uint32_t *indices_out, float *data_out, size_t out_cap, size_t *nnz_needed);
+
+/* ---- K2f: greedy clustering on the device (cmp --greedy T) ---------------------------------------------------------------
+ * Replaces the exhaustive branch of dedup_core (reference src/dedup_core.cpp:262-283) for values that are a NON-DECREASING function
+ * of the equality count: in INPUT order, sketch i joins the representative with the largest value -- among equal values the one
+ * with the smallest index -- if that value reaches the threshold, and founds a cluster otherwise.  A sketch is compared with
+ * representatives only (A~B, B~C, A!~C gives {A,B},{C}).  Only assign[N] leaves the device.
+ *
+ * d2g_cmp_dedup_dev, any kind of set: a count c qualifies iff cls[c] >= min_count, "largest value" is the largest cls[c].
+ *   cls_dev (NULL = identity) = S + 1 words, cls[e] = the smallest count whose VALUE equals that of e (so cls[e] <= e);
+ *   min_count = the smallest count whose value reaches the threshold (S + 1: nobody ever joins).
+ *   assign_dev[i] = the representative of i's cluster (i itself for a representative); every word of [0, N) is written, nothing else.
+ * Rows are taken in bands of band_rows (0 = a default; at most 256, larger requests are cut to that: the in-order step is
+ * sequential in the band) whose counts go into scratch of the context.  Enqueues on `stream`, does not synchronise; the calls of
+ * ONE context that use the scratch band (this and d2g_cmp_knn_dev) must be issued on ONE stream.  N = 0 does nothing. */
+int  d2g_cmp_dedup_dev(d2g_ctx *ctx, const d2g_cmp_set *set, uint32_t min_count, const uint32_t *cls_dev /* [S+1] or NULL */,
+                       uint32_t *assign_dev /* [N] */, size_t band_rows, void *stream);
+/* Host half (no context): assign -> clusters in creation order (= ascending representative), inside a cluster the representative
+ * first, then its members in input order (dedup_emit's ids / constituents, src/dedup_core.cpp:400-451).  indptr_out has room for
+ * N + 1 entries, of which *nclusters + 1 are written; indices_out has N.  D2G_ERR_INVALID (nothing promised about the outputs) if
+ * assign[i] > i or assign[assign[i]] != assign[i]. */
+int  d2g_dedup_clusters(const uint32_t *assign, size_t N, uint64_t *indptr_out, uint32_t *indices_out /* [N] */, size_t *nclusters);
+/* Host-pointer form over a prepared set.  lut (host, sketchsize + 1 floats) must be non-decreasing (D2G_ERR_INVALID otherwise);
+ * simt = (float)(threshold > 0 ? threshold : 0.9), i joins iff !(value < simt) in float (dedup_core.cpp:264,276).  Runs the whole
+ * set, copies back 4 N bytes and synchronises. */
+int  d2g_cmp_set_dedup(d2g_ctx *ctx, const d2g_cmp_set *set, const float *lut, double threshold, size_t band_rows,
+                       uint32_t *assign_out /* host [N] */);
+/* ... and from the N x S matrix itself.  D2G_ERR_UNSUPPORTED where d2g_epilogue_lut fails, or for a distance (D2G_POISSON_LLR): with
+ * one the reference's test founds a new cluster exactly when the nearest representative is CLOSER than the threshold. */
+int  d2g_cmp_dedup(d2g_ctx *ctx, const uint64_t *sig_bits, size_t N, size_t sketchsize, int measure, int k, int multiset_space,
+                   int algo, double threshold, size_t band_rows, uint32_t *assign_out /* host [N] */);
 
 /* ---- multi-GPU: RCCL communicator + row-sharded all-pairs engine ------------------------------------
  * Replaces nothing in the reference (it has no multi-process code); it is how the all-pairs seam
