@@ -114,6 +114,7 @@ SIGNATURES = {
     "d2g_seqpack_add_path_by_record": (_int, [_vp, C.c_char_p]),
     "d2g_seqpack_add_fastx_by_record": (_int, [_vp, C.c_char_p, _sz]),
     "d2g_seqpack_name": (C.c_char_p, [_vp, _sz]),
+    "d2g_bmh_check_weights": (_int, [_vp, _vp, _sz, _sz, _dbl, C.c_char_p, _sz]),
     "d2g_bmh_from_weighted": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     "d2g_bmh_from_weighted_ids": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "d2g_ut_count": (_sz, [_sz, _sz, _sz]),
@@ -350,6 +351,18 @@ def host_epilogue_trunc_rect(ca, cb, cards, N, S, a0, a1, b0, b1, measure=SIMILA
     if rc:
         raise D2GError(rc)
     return out
+
+
+def bmh_check_weights(weights, set_off, S, scale=1.0):
+    """the host-side checks of Context.bmh_from_weighted / _ids without a device: raises D2GError for a NaN weight, a weight above
+    2^53, a set_off that is not monotone, and a non-empty set whose total weight is too small for S (its bound would not stay finite)"""
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64)
+    set_off = np.ascontiguousarray(set_off, np.uint64)
+    assert w is None or w.size >= int(set_off.max(initial=0))
+    err = C.create_string_buffer(256)
+    rc = lib().d2g_bmh_check_weights(_np_ptr(w), _np_ptr(set_off), set_off.size - 1, S, scale, err, 256)
+    if rc:
+        raise D2GError(rc, err.value.decode())
 
 
 class KnnOverflow(ValueError):

@@ -1770,6 +1770,38 @@ int d2g_kmer_count(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, con
     return rc;
 }
 
+// Every host-side check of the weights of explicit sets, without a context.  The last one keeps the walk finite: a set's first guess of
+// its bound is scale * bmh_guess(W), the redo loop of d2g_bmh_from_weighted_ids multiplies a guess by 16 and gives up after 40 passes, so
+// a first guess below 2^1024 / 16^40 = 2^864 stays finite through every pass.  An infinite bound prunes nothing (proc_next ends on
+// P.x <= bound, which inf <= inf satisfies), and the walk of such a set would not end.
+constexpr double BMH_GUESS_LIMIT = 0x1p864;
+int d2g_bmh_check_weights(const double *weights, const uint64_t *set_off, size_t nsets, size_t sketchsize, double scale, char *err,
+                          size_t errcap) {
+    auto fail = [&](const char *fmt, unsigned long long set) {
+        if (err && errcap) std::snprintf(err, errcap, fmt, set);
+        return D2G_ERR_INVALID;
+    };
+    if (err && errcap) err[0] = 0;
+    if (!set_off) return fail("null argument", 0);
+    if (!(sketchsize >= 1 && sketchsize < (1ull << 24))) return fail("sketchsize out of range", 0);
+    if (!(scale > 0.)) return fail("guess scale not positive", 0);
+    for (size_t i = 0; i < nsets; ++i) if (!(set_off[i] <= set_off[i + 1])) return fail("set_off not monotone", 0);
+    const double m = (double)sketchsize, lnm = std::log(m);
+    for (size_t i = 0; i < nsets; ++i) {
+        double t = 0.;
+        for (uint64_t e = set_off[i]; e < set_off[i + 1]; ++e) {
+            const double w = weights ? weights[e] : 1.0;
+            if (w > 0.) {
+                if (!(w <= 0x1p53)) return fail("BagMinHash weight outside (0, 2^53] (set %llu)", i);
+                t += w;
+            } else if (w != w) return fail("BagMinHash weight is NaN (set %llu)", i);
+        }
+        if (t > 0. && !(scale * bmh_guess(t, m, lnm) < BMH_GUESS_LIMIT))
+            return fail("BagMinHash set %llu: total weight too small for the sketch size (the pruning bound would not stay finite)", i);
+    }
+    return D2G_OK;
+}
+
 int d2g_bmh_from_weighted(d2g_ctx *ctx, const uint64_t *ids, const double *weights, const uint64_t *set_off, size_t nsets,
                           size_t sketchsize, double *sig_out, double *total_weight_out) {
     return d2g_bmh_from_weighted_ids(ctx, ids, weights, set_off, nsets, sketchsize, sig_out, total_weight_out, nullptr);
@@ -1784,7 +1816,13 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
     if (nsets == 0) return D2G_OK;
     const uint64_t total = set_off[nsets];
     D2G_CHECK(ctx, total == 0 || ids != nullptr, "null ids");
-    for (size_t i = 0; i < nsets; ++i) D2G_CHECK(ctx, set_off[i] <= set_off[i + 1], "set_off not monotone");
+    {   // every check of the weights, before anything is allocated or launched
+        char err[160];
+        if (d2g_bmh_check_weights(weights, set_off, nsets, sketchsize, ctx->k3_tune.guess_scale, err, sizeof err) != D2G_OK) {
+            ctx->last_error = err;
+            return D2G_ERR_INVALID;
+        }
+    }
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     const size_t m = sketchsize;
     // total weights on the host (the caller's arrays are host arrays): the result, and the first guess of the bound
@@ -1798,10 +1836,7 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
         double t = 0.;
         for (uint64_t e = lo; e < hi; ++e) {
             const double w = weights ? weights[e] : 1.0;
-            if (w > 0.) {
-                if (!(w <= 0x1p53)) { ctx->last_error = "BagMinHash weight outside (0, 2^53]"; return D2G_ERR_INVALID; }
-                t += w;
-            } else if (w != w) { ctx->last_error = "BagMinHash weight is NaN"; return D2G_ERR_INVALID; }
+            if (w > 0.) t += w;                                      // the same sum, in the same order, as d2g_bmh_check_weights
         }
         tw[i] = t;
         const double gv = t > 0. ? ctx->k3_tune.guess_scale * bmh_guess(t, (double)m, lnm) : 0.;

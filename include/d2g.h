@@ -319,7 +319,17 @@ int d2g_sketcher_run_distinct(d2g_sketcher *sk, const uint8_t *packed, size_t pa
 /* BagMinHash of explicit weighted sets (reference src/wsketch.cpp:54-73 minwise_det and 17-51
  * minhash_rowwise_csr: h.update(id, weight) per element): set i = elements
  * [set_off[i], set_off[i+1]); weights == NULL means 1.0; weights <= 0 are ignored (as
- * BagMinHash2::update does), weights above 2^53 or NaN are rejected. */
+ * BagMinHash2::update does), weights above 2^53 or NaN are rejected, and so is a set whose total weight
+ * is too small for the sketch size (d2g_bmh_check_weights). */
+/* the host-side checks of d2g_bmh_from_weighted / _ids on their own (no context, no device): D2G_ERR_INVALID with a message
+ * in err (may be NULL) for a NaN weight, a weight above 2^53, a set_off that is not monotone, a sketchsize outside
+ * [1, 2^24), and for a non-empty set whose TOTAL weight W is too small for the sketch size: the first guess of its pruning
+ * bound, scale * 1.25 (S / W) (ln S + 8.58), must be below 2^864 -- the walk raises a failed guess 16-fold at most 40 times
+ * (16^40 = 2^160), and a bound that reached +inf would prune nothing and never end.  At scale 1 (the library's, unless
+ * D2G_K3_GUESS_SCALE says otherwise) that refuses totals below about 1e-252 at S = 2^24 - 1 and about 1e-259 at S = 1;
+ * single tiny weights inside a set of ordinary total are fine.  d2g_bmh_from_weighted / _ids run it first. */
+int d2g_bmh_check_weights(const double *weights /* NULL = all 1.0 */, const uint64_t *set_off /* [nsets+1] */, size_t nsets,
+                          size_t sketchsize, double scale, char *err, size_t errcap);
 int d2g_bmh_from_weighted(d2g_ctx *ctx, const uint64_t *ids, const double *weights,
                           const uint64_t *set_off /* [nsets+1] */, size_t nsets, size_t sketchsize,
                           double *sig_out /* host [nsets][S] */, double *total_weight_out /* host [nsets] */);

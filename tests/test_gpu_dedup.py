@@ -293,3 +293,48 @@ def test_dedup_kernels_are_timed(gpu_ctx, d2g):
     assert resolve[0] == 3 and both[0] == 5 and both[1] > 0       # three bands: three in-order steps, two per-row launches (the first band has no earlier column)
     assert walk[0] >= 3
     assert gpu_ctx.kernel_ms("dedup")[0] == 0 and gpu_ctx.kernel_ms("dedup_resolve")[0] == 0
+
+
+# ---- rows longer than one trip of dedup_best_kernel's unrolled loop ------------------------------------------------------
+# the per-row kernel advances by UNROLL * THREADS = 1024 columns: N = 2500 takes two full trips and a third that is partly past
+# the end of the row.  (Every matrix above has N <= 1000: one trip.)
+LONG_N, LONG_S = 2500, 64
+
+
+def far_representatives(values, assign, T, band):
+    """from the REFERENCE result: rows whose representative lies at an index >= 1024 in an earlier band, and rows that join a
+    representative below 1024 although a qualifying representative at >= 1024 precedes them"""
+    N = values.shape[0]
+    isrep = assign == np.arange(N)
+    simt = R.simt_of(T)
+    far = near_despite_far = 0
+    for i in np.nonzero(~isrep)[0]:
+        r = int(assign[i])
+        if r >= 1024:
+            far += r // band < i // band
+        else:
+            reps = np.nonzero(isrep[1024:i])[0] + 1024
+            near_despite_far += bool(np.any(values[i, reps] >= simt))
+    return far, near_despite_far
+
+
+@pytest.mark.parametrize("shuffled", [False, True], ids=["generator-order", "shuffled"])
+def test_dedup_rows_of_more_than_one_trip(gpu_ctx, d2g, shuffled):
+    """T in {0.1, 0.25}, bands of 33 rows and the default (and of one row for one T), bit-sliced and direct sets.  After the
+    shuffle the best representative of a row is found in the second or third trip, or must win against qualifying ones there."""
+    N, S = LONG_N, LONG_S
+    m = families(N, S, shuffled)
+    cls = K.class_table(m.lut)
+    for T in (0.1, 0.25):
+        exp = m.ref(T)
+        assert 2 <= np.sum(exp == np.arange(N)) <= N - 1
+        if shuffled:
+            for band in (33, 256):
+                far, near_despite_far = far_representatives(m.values, exp, T, band)
+                assert far >= 10 and near_despite_far >= 10, (T, band, far, near_despite_far)
+        for algo in (d2g.CMP_BITSLICE, d2g.CMP_DIRECT):
+            cs = m.set(gpu_ctx, algo)
+            assert cs.algo == algo
+            for band in ((33, 0, 1) if algo == d2g.CMP_BITSLICE and T == 0.25 else (33, 0)):
+                got = run_dev(gpu_ctx, cs, N, min_count_of(m.lut, T), cls if band else None, band)
+                same(got, exp, f"dev algo {algo} band {band} T {T}")

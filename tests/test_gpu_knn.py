@@ -311,3 +311,41 @@ def test_knn_kernel_is_timed(gpu_ctx, d2g):
     finally:
         gpu_ctx.set_timing(0)
     assert n[0] >= 3 and n[1] > 0                                   # three bands: at least three selection launches
+
+
+# ---- rows longer than one trip of the selection kernel's unrolled loops ------------------------------------------------
+# knn_select_kernel and count_at_least advance by UNROLL * THREADS = 1024 columns: N = 2500 takes two full trips and a third that
+# is partly past the end of the row.  (Every matrix above has N <= 1000: one trip.)
+LONG_N, LONG_S = 2500, 64
+
+
+def long_matrix(shuffled):
+    key = ("families-long", shuffled)
+    if key not in _CACHE:
+        sigs = R.family_sigs(LONG_N, LONG_S, seed=LONG_N * 7 + LONG_S)
+        if shuffled:
+            sigs = sigs[np.random.default_rng(LONG_N + LONG_S).permutation(LONG_N)]
+        _CACHE[key] = Matrix(sigs)
+    return _CACHE[key]
+
+
+@pytest.mark.parametrize("shuffled", [False, True], ids=["generator-order", "shuffled"])
+def test_knn_dev_rows_of_more_than_one_trip(gpu_ctx, d2g, shuffled):
+    """top-K at K in {1, 5, 64}, the thresholds S / 4 and 0, bands of 33 rows and the default, a row range that starts past column
+    1024, on bit-sliced and direct sets.  In generator order a family is a run of neighbouring rows, so every row from 1024 on
+    lists columns of the second or third trip; after the shuffle the rows below 1024 do too."""
+    N, S = LONG_N, LONG_S
+    m = long_matrix(shuffled)
+    _, cls = lut_and_classes(d2g, S, d2g.SIMILARITY)
+    listed = R.select_by_count(m.cnt, 5, 1, cls)[1]
+    assert listed[:, 1024:2048].any(axis=1).sum() >= 400 and listed[:, 2048:].any(axis=1).sum() >= 400
+    assert listed[:1024, 1024:].any(axis=1).sum() >= (500 if shuffled else 1)
+    for algo in (d2g.CMP_BITSLICE, d2g.CMP_DIRECT):
+        cs = m.set(gpu_ctx, d2g, algo)
+        assert cs.algo == algo
+        for band in ((33, 0) if algo == d2g.CMP_BITSLICE else (0,)):
+            for K in (1, 5, 64):
+                check_dev(gpu_ctx, cs, m.cnt, K, 1, cls, cap=K + 8, band_rows=band, what=f"algo {algo} band {band} K {K}")
+            check_dev(gpu_ctx, cs, m.cnt, 0, S // 4, None, cap=48, band_rows=band, what=f"algo {algo} band {band} threshold S / 4")
+            check_dev(gpu_ctx, cs, m.cnt, 0, 0, None, cap=40, band_rows=band, what=f"algo {algo} band {band} threshold 0")
+        check_dev(gpu_ctx, cs, m.cnt, 5, 1, cls, cap=3, r0=1030, r1=N - 7, band_rows=33, what=f"algo {algo} rows 1030..N-7")
