@@ -372,7 +372,7 @@ def sketch_main(argv):
     args, passthrough = ap.parse_known_args(argv)
     if "WORLD_SIZE" not in os.environ:
         # no launcher: the product path -- ONE `dashing2 sketch` process whose C++ host deals the input groups to a pair of device
-        # threads per GPU (D2G_DEVICES; dashing2_main.cpp: sketch_core).  The rank-per-GPU form below is what runs under a launcher.
+        # threads per GPU (D2G_DEVICES; host/sketch_cmd.cpp: sketch_core).  The rank-per-GPU form below is what runs under a launcher.
         import subprocess
         exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "bin", "dashing2")
         env = dict(os.environ)

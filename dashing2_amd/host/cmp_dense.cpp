@@ -1,0 +1,462 @@
+// cmp_dense.cpp -- the dense outputs of `dashing2 cmp` / `sketch --cmpout`: condensed triangle, square matrix, panel.  Mirrors
+//   cmp_core (densify)       src/cmp_core.cpp:686-718,746-751
+//   emit_rectangular         src/emitrect.cpp:108-403
+// on one GPU or, rows dealt round-robin, on several (D2G_DEVICES).
+#include "cli_common.h"
+#include "fmtfloat.h"
+#include "slot_queue.h"
+#include <functional>
+#include <memory>
+
+namespace d2h {
+
+namespace {
+
+// ------------------------------------------------------------------------------------ emit
+struct Emitter {
+    const Options &o;
+    const Result &res;
+    std::FILE *fp = nullptr;
+    bool own = false;
+    // Binary matrices leave through ONE buffered stream.  Measured and dropped: (round 3) a shared mapping of the output filled by
+    // all threads -- copy 0.74 -> 0.57 s for config 4's 5 GB, but unmapping the dirty pages cost another 0.51 s on the box's overlay
+    // file system; (round 4) the batch cut into 4 MiB pieces that 8 threads pwrite() at their offsets -- no gain at all (config 3:
+    // 22 ms either way, config 4: 0.50 s either way, ~10 GB/s): buffered writes to one file serialise on its inode lock.
+    Emitter(const Options &oo, const Result &r) : o(oo), res(r) {
+        const std::string outp = (o.cmpout.empty() || o.cmpout.front() == '-') ? "/dev/stdout" : o.cmpout;   // emitrect.cpp:114-115
+        if (outp == "/dev/stdout") fp = stdout;
+        else { fp = std::fopen(outp.c_str(), "wb"); own = true; }
+        if (!fp) die("Failed to open path " + outp + " for writing");
+        static std::vector<char> buf(1 << 22);
+        std::setvbuf(fp, buf.data(), _IOFBF, buf.size());
+    }
+    ~Emitter() { if (fp) { std::fflush(fp); if (own) std::fclose(fp); } }
+    void header() {                                                     // emitrect.cpp:136-151
+        if (o.of != HUMAN_READABLE) return;
+        const size_t ns = res.names.size();
+        if (o.ok == PHYLIP) { std::fprintf(fp, "%zu\n", ns); return; }
+        const char *label = o.ok == ASYMMETRIC_ALL_PAIRS ? "Asymmetric pairwise" : o.ok == PANEL ? "Panel (Query/Refernce)" : "Symmetric pairwise";
+        std::fprintf(fp, "#Dashing2 %s Output\n", label);
+        std::fprintf(fp, "#Dashing2Options: %s\n", o.to_string().c_str());
+        // not a reference line: written only when --fmt-compat was given, so that the default output stays byte-identical to
+        // emitrect.cpp:138-147 while a deliberate choice of float layout is on record in the file it shaped
+        if (o.fmt_compat) std::fprintf(fp, "#Dashing2FloatText: fmt-compat=%d\n", o.fmt_compat);
+        std::fputs("#Sources", fp);
+        for (size_t i = 0; i < ns; ++i) { std::fputc('\t', fp); std::fwrite(res.names[i].data(), 1, res.names[i].size(), fp); }
+        std::fputc('\n', fp);
+    }
+    // rows [r0, r1); row i has nvals(i) values starting at data + off(i)
+    template <class NV> void rows(size_t r0, size_t r1, const float *data, NV nvals) {
+        if (o.of == MACHINE_READABLE) {                                  // emitrect.cpp:189-192
+            size_t tot = 0;
+            for (size_t i = r0; i < r1; ++i) tot += nvals(i);
+            if (std::fwrite(data, sizeof(float), tot, fp) != tot) die("Failed to write rows " + std::to_string(r0) + "-" + std::to_string(r1) + " to disk");
+            return;
+        }
+        const size_t n = r1 - r0;
+        std::vector<size_t> off(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + nvals(r0 + i);
+        std::vector<std::string> text(n);
+#ifdef _OPENMP
+        #pragma omp parallel for schedule(dynamic, 8) num_threads(o.workers())
+#endif
+        for (size_t r = 0; r < n; ++r) {                                 // emitrect.cpp:172-187
+            const size_t i = r0 + r;
+            std::string &s = text[r];
+            std::string fn = (res.names.size() > i && !res.names[i].empty()) ? res.names[i] : std::string("E") + std::to_string(i);
+            if (fn.size() < 9) fn.append(9 - fn.size(), ' ');
+            const size_t nv = off[r + 1] - off[r];
+            s.reserve(fn.size() + 2 * (i + 1) + nv * 12 + 2);
+            s = fn;
+            if (o.ok == SYMMETRIC_ALL_PAIRS) for (size_t t = 0; t < i + 1; ++t) s += "\t-";     // print_tabs, emitrect.cpp:40-66
+            char buf[FMT_MAX_FLOAT_CHARS + 1];
+            const float *p = data + off[r];
+            for (size_t j = 0; j < nv; ++j) {
+                buf[0] = '\t';
+                const size_t l = format_float(p[j], buf + 1);
+                s.append(buf, l + 1);
+            }
+            s += '\n';
+        }
+        for (const auto &s : text)
+            if (std::fwrite(s.data(), 1, s.size(), fp) != s.size()) die("Failed to write text rows");
+    }
+};
+
+// Row batches flow device -> host slot -> emitter thread: the kernel + D2H (+ host x87 epilogue) of batch i+1 run while
+// batch i is formatted / written (the CLI ran kernel -> D2H -> emit strictly in series per 512 MiB batch).
+// The queue itself is slot_queue.h (exercised under ThreadSanitizer by `make tsan`).
+struct EmitJob { size_t r0, r1; const float *data; std::function<size_t(size_t)> nvals; };
+struct EmitQueue : SlotQueue<EmitJob> {
+    EmitQueue(Emitter &em, int nslots) : SlotQueue<EmitJob>(nslots, [&em](const EmitJob &j) { em.rows(j.r0, j.r1, j.data, j.nvals); }) {}
+};
+
+// values per row batch: a slot is one batch's staging; three slots cycle device -> host epilogue -> emitter.  Small jobs take small
+// slots (more batches cost little: the pair kernel is launched per row range), big jobs 64 MiB ones.
+size_t cmp_slot_values(size_t total_vals) {
+    size_t v = std::min<size_t>(size_t(1) << 24, std::max<size_t>(size_t(1) << 22, total_vals / 12));
+    if (const char *e = std::getenv("D2G_CMP_SLOT_VALUES")) { const long long x = std::atoll(e); if (x >= 1) v = size_t(x); }   // tests: tiny slots
+    return v;
+}
+
+// ------------------------------------------------------------------------------------ the job
+// the shape of a dense comparison job (src/emitrect.cpp:211-323): which rows are emitted, how many values each has
+struct CmpShape {
+    bool symmetric; size_t ns, nrows, c0, c1, ncol, total_vals, widest;
+    CmpShape(const Options &o, const Result &res) {
+        ns = res.names.size();
+        symmetric = o.ok == SYMMETRIC_ALL_PAIRS || o.ok == PHYLIP;
+        const size_t nq = res.nq, nf = o.ok == PANEL ? ns - nq : ns;
+        c0 = o.ok == PANEL ? nf : 0; c1 = ns; ncol = symmetric ? 0 : c1 - c0;
+        nrows = symmetric ? ns : nf;
+        total_vals = symmetric ? ns * (ns - 1) / 2 : nf * ncol;
+        widest = symmetric ? (ns ? ns - 1 : 0) : ncol;
+    }
+    // the batch of rows starting at r0 that fits `cap` values -> (r1, values)
+    std::pair<size_t, size_t> batch(size_t r0, size_t cap) const {
+        size_t r1 = r0, cnt = 0;
+        if (symmetric) while (r1 < ns && (cnt == 0 || cnt + (ns - 1 - r1) <= cap)) { cnt += ns - 1 - r1; ++r1; }
+        else { r1 = std::min(nrows, r0 + std::max<size_t>(1, cap / std::max<size_t>(ncol, 1))); cnt = (r1 - r0) * ncol; }
+        return {r1, cnt};
+    }
+    const char *name(const Options &o) const { return symmetric ? "upper triangle" : o.ok == PANEL ? "panel" : "square"; }
+};
+
+// One dense job: what is counted on the device and how a count becomes the float that is written.
+//   have_lut   the value is a table of the equality count alone (a triangle then comes back from the device as floats: `fused`)
+//   need_gtlt  the value needs (gt, lt) counts: a sketch size that is not a power of two, setsketch-truncated registers
+//   trunc      --fastcmp: the registers were truncated to o.regbytes; trunc_b: the setsketch base (null for b-bit codes)
+struct DenseJob {
+    const Options &o;
+    const CmpShape sh;
+    const size_t S;
+    const double *cards;
+    const bool have_lut, need_gtlt, trunc, multiset;
+    const std::vector<float> &lut;
+    const long double *trunc_b;
+    const size_t cap;                                                   // values per row batch
+    DenseJob(const Options &oo, const Result &res, bool lutv, bool gtlt, bool tr, bool ms, const std::vector<float> &l, const long double *tb)
+        : o(oo), sh(oo, res), S(oo.sketchsize), cards(res.cardinalities.data()), have_lut(lutv), need_gtlt(gtlt), trunc(tr), multiset(ms), lut(l), trunc_b(tb),
+          cap(std::max<size_t>(1, std::min(std::max(cmp_slot_values(sh.total_vals), sh.widest), std::max<size_t>(sh.total_vals, 1)))) {}
+    bool fused() const { return have_lut && sh.symmetric; }
+};
+struct Batch { size_t r0, r1, cnt; };
+// where one GPU computes its batches: the operand, the table, the counts of the batch in flight
+struct DenseDevice {
+    d2g_ctx *ctx; const d2g_cmp_set *set;
+    DevBuf dlut, da;
+    std::unique_ptr<DevBuf> db;
+    DenseDevice(const DenseJob &j, d2g_ctx *c, const d2g_cmp_set *s) : ctx(c), set(s), dlut(c, (j.S + 1) * sizeof(float)), da(c, j.cap * 4) {
+        if (j.have_lut) check(ctx, d2g_memcpy_h2d(ctx, dlut.p, j.lut.data(), (j.S + 1) * sizeof(float), nullptr), "h2d lut");
+        if (j.need_gtlt) db.reset(new DevBuf(c, j.cap * 4));
+    }
+};
+// plain memory: nothing to page-lock, nothing for a helper thread to do
+struct HostSlot {
+    HostBuf out, ca, cb;
+    explicit HostSlot(const DenseJob &j) : out(j.cap * 4), ca(j.fused() ? 4 : j.cap * 4), cb(j.need_gtlt ? j.cap * 4 : 4) {}
+};
+
+// counts of a rectangular batch -> floats (emitrect.cpp:211-268 call compare(i, j) per cell: cmp_core.cpp:458-517)
+void rect_epilogue(const DenseJob &j, const Batch &bt, const uint32_t *ca, const uint32_t *cb, float *out) {
+    const Options &o = j.o;
+    const CmpShape &sh = j.sh;
+    const size_t S = j.S;
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(dynamic, 4) num_threads(o.workers())
+#endif
+    for (size_t i = bt.r0; i < bt.r1; ++i)
+        for (size_t c = sh.c0; c < sh.c1; ++c) {
+            const size_t p = (i - bt.r0) * sh.ncol + (c - sh.c0);
+            out[p] = j.have_lut ? j.lut[ca[p]]
+                   : j.multiset ? d2g_epilogue_neq(ca[p], S, j.cards[i], j.cards[c], o.measure, o.k)
+                   : j.need_gtlt ? d2g_epilogue_gtlt(ca[p], cb[p], S, j.cards[i], j.cards[c], o.measure, o.k)
+                                 : d2g_epilogue_gtlt(S - ca[p], 0, S, j.cards[i], j.cards[c], o.measure, o.k);
+        }
+}
+
+// starts the pair kernel of one batch on a device (asynchronous): triangle rows emitrect.cpp:290-323, rectangle rows :211-268
+void launch_batch(const DenseJob &j, DenseDevice &d, const Batch &bt) {
+    if (!bt.cnt) return;
+    uint32_t *a = (uint32_t *)d.da.p, *b = d.db ? (uint32_t *)d.db->p : nullptr;
+    if (j.sh.symmetric) {
+        if (j.have_lut) check(d.ctx, d2g_cmp_lut_ut_dev(d.ctx, d.set, bt.r0, bt.r1, (const float *)d.dlut.p, (float *)d.da.p, nullptr), "d2g_cmp_lut_ut_dev");
+        else if (j.need_gtlt) check(d.ctx, d2g_cmp_gtlt_ut_dev(d.ctx, d.set, bt.r0, bt.r1, a, b, nullptr), "d2g_cmp_gtlt_ut_dev");
+        else check(d.ctx, d2g_cmp_eqcount_ut_dev(d.ctx, d.set, bt.r0, bt.r1, a, nullptr), "d2g_cmp_eqcount_ut_dev");
+    } else {
+        if (j.need_gtlt) check(d.ctx, d2g_cmp_gtlt_rect_dev(d.ctx, d.set, bt.r0, bt.r1, j.sh.c0, j.sh.c1, a, b, nullptr), "d2g_cmp_gtlt_rect_dev");
+        else check(d.ctx, d2g_cmp_eqcount_rect_dev(d.ctx, d.set, bt.r0, bt.r1, j.sh.c0, j.sh.c1, a, nullptr), "d2g_cmp_eqcount_rect_dev");
+    }
+}
+
+// copies the batch back into a host slot and finishes it there (x87 epilogue on the host: cmp_core.cpp:458-517; truncated
+// registers: 406-448), then hands its rows to the emitter thread
+void finish_batch(const DenseJob &j, DenseDevice &d, const Batch &bt, EmitQueue &eq, int si, HostSlot &sl) {
+    const Options &o = j.o;
+    const CmpShape &sh = j.sh;
+    const size_t ns = sh.ns, S = j.S;
+    float *out = sl.out.as<float>();
+    uint32_t *ca = sl.ca.as<uint32_t>(), *cb = j.need_gtlt ? sl.cb.as<uint32_t>() : nullptr;
+    if (bt.cnt && j.fused()) check(d.ctx, d2g_memcpy_d2h(d.ctx, out, d.da.p, bt.cnt * 4, nullptr), "d2h");
+    else if (bt.cnt) {
+        if (cb) check(d.ctx, d2g_memcpy_d2h(d.ctx, cb, d.db->p, bt.cnt * 4, nullptr), "d2h");
+        check(d.ctx, d2g_memcpy_d2h(d.ctx, ca, d.da.p, bt.cnt * 4, nullptr), "d2h");
+        const int nt = int(o.workers());
+        if (sh.symmetric && j.trunc) check(d.ctx, d2g_epilogue_trunc_ut(ca, cb, j.cards, ns, S, bt.r0, bt.r1, o.measure, o.k, o.regbytes, j.trunc_b, nt, out), "d2g_epilogue_trunc_ut");
+        else if (sh.symmetric) check(d.ctx, d2g_epilogue_ut(ca, cb, j.cards, ns, S, bt.r0, bt.r1, o.measure, o.k, j.multiset, nt, out), "d2g_epilogue_ut");
+        else if (j.trunc) check(d.ctx, d2g_epilogue_trunc_rect(ca, cb, j.cards, ns, S, bt.r0, bt.r1, sh.c0, sh.c1, o.measure, o.k, o.regbytes, j.trunc_b, nt, out), "d2g_epilogue_trunc_rect");
+        else rect_epilogue(j, bt, ca, cb, out);
+    }
+    if (sh.symmetric) eq.submit(si, EmitJob{bt.r0, bt.r1, out, [ns](size_t i) { return ns - 1 - i; }});
+    else { const size_t ncol = sh.ncol; eq.submit(si, EmitJob{bt.r0, bt.r1, out, [ncol](size_t) { return ncol; }}); }
+}
+
+// ------------------------------------------------------------------------------------ --gpu-stats
+// a long double as a JSON number with every digit (the setsketch parameters a and b)
+std::string ldstr(long double v) { char b[64]; std::snprintf(b, sizeof b, "%.21Lg", v); return b; }
+
+// what the sparse-tile path did on the last upper-triangle launch of the set (include/d2g.h: d2g_cmp_set_sparse_info)
+std::string sparse_json(d2g_ctx *ctx, const d2g_cmp_set *set) {
+    uint32_t i4[4] = {0, 0, 0, 0};
+    if (d2g_cmp_set_sparse_info(ctx, set, nullptr, i4) != D2G_OK) return "null";
+    return Json::object().boolean("sorted_operand", i4[0]).integer("tiles_listed_last_launch", i4[1]).boolean("dense_decided_by_prepare", i4[2] & 1)
+        .boolean("dense_kernel_ran", i4[2] & 2).boolean("tiles_and_pair_list", i4[2] & 4).boolean("callers_order_kept", i4[2] & 8).integer("pairs_listed", i4[3]).text();
+}
+std::string planes_json(d2g_ctx *ctx, const d2g_cmp_set *set) {
+    unsigned md = 0; int nb = 0; float mean = 0;
+    if (d2g_cmp_set_planes(ctx, set, nullptr, &md, &nb, &mean) != D2G_OK) return "null";
+    return Json::object().integer("max", nb).num("mean", mean).integer("max_shared_values_per_column_plus1", md).text();
+}
+Json k2_device_json(int dev, d2g_ctx *ctx) {
+    Json e = device_json(dev);
+    e.raw("k2", kernel_json(ctx, "k2")).raw("k2prep", kernel_json(ctx, "k2prep"));
+    return e;
+}
+
+// ------------------------------------------------------------------------------------ several GPUs
+// A dense comparison job over several GPUs from ONE process (the reference's seam is the single call
+// emit_rectangular(opts, result), src/cmp_core.cpp:746-751).  Every GPU gets a contiguous block of rows of the signature matrix; one
+// exchange (d2g_allpairs_prepare_all: all-to-all of column slices, sharded prepare, all-gather of the bit planes over RCCL/xGMI)
+// leaves the whole bit-sliced operand on every GPU; row batches -- of the condensed triangle (emitrect.cpp:290-323), of the square
+// matrix (--square, :249-268) or of the reference x query panel (-Q, :211-247) -- are then dealt to the GPUs round-robin, computed
+// concurrently, and emitted in row order through the slot queue: byte-identical to the single-GPU output.
+// Returns false (nothing emitted yet) when the sharded bit-sliced prepare overflowed its rank table on some rank -- an adversarial /
+// extremely skewed register column at N > 21 845: the caller then takes the single-GPU path, whose AUTO algorithm falls back to the
+// direct kernel.
+struct MultiGpu {
+    const int W;
+    std::vector<d2g_ctx *> ctxs;
+    std::vector<d2g_comm *> comms;
+    std::vector<d2g_allpairs *> engs;
+    explicit MultiGpu(const std::vector<int> &devs) : W(int(devs.size())), ctxs(W, nullptr), comms(W, nullptr), engs(W, nullptr) {
+        for (int r = 0; r < W; ++r) {
+            const int rc = d2g_ctx_create(devs[r], &ctxs[r]);
+            if (rc != D2G_OK) die(std::string("D2G_DEVICES: d2g_ctx_create(") + std::to_string(devs[r]) + "): " + d2g_strerror(rc));
+            if (g_stats.on) (void)d2g_set_timing(ctxs[r], TIME_ALL);
+        }
+        check(ctxs[0], d2g_comm_create_all(ctxs.data(), W, comms.data()), "d2g_comm_create_all");
+    }
+    // uploads every rank's block of rows and runs the exchange; false: the prepare overflowed on some rank
+    bool prepare(const uint64_t *bits, size_t ns, size_t S) {
+        std::vector<const uint64_t *> rows(W, nullptr);
+        std::vector<void *> rowbuf(W, nullptr);
+        for (int r = 0; r < W; ++r) {
+            check(ctxs[r], d2g_allpairs_create(ctxs[r], comms[r], ns, S, &engs[r]), "d2g_allpairs_create");
+            size_t lo = 0, hi = 0;
+            d2g_allpairs_rows_held(engs[r], &lo, &hi);
+            check(ctxs[r], d2g_malloc(ctxs[r], std::max<size_t>((hi - lo) * S, 1) * 8, &rowbuf[r]), "d2g_malloc");
+            if (hi > lo) check(ctxs[r], d2g_memcpy_h2d(ctxs[r], rowbuf[r], bits + lo * S, (hi - lo) * S * 8, nullptr), "h2d rows");
+            rows[r] = static_cast<const uint64_t *>(rowbuf[r]);
+        }
+        check(ctxs[0], d2g_allpairs_prepare_all(engs.data(), W, rows.data(), nullptr), "d2g_allpairs_prepare_all");
+        bool overflow = false;
+        for (int r = 0; r < W; ++r) {
+            const int st = d2g_allpairs_status(engs[r], nullptr);      // every rank sees every rank's status word
+            if (st == D2G_ERR_INTERNAL) overflow = true;
+            else check(ctxs[r], st, "d2g_allpairs_status");
+            check(ctxs[r], d2g_free(ctxs[r], rowbuf[r]), "d2g_free");
+        }
+        return !overflow;
+    }
+    const char *transport() const { return d2g_comm_is_rccl(comms[0]) ? "RCCL" : "loopback"; }
+    ~MultiGpu() { for (int r = 0; r < W; ++r) { d2g_allpairs_destroy(engs[r]); d2g_comm_destroy(comms[r]); d2g_ctx_destroy(ctxs[r]); } }
+};
+
+bool cmp_core_multi(const DenseJob &job, Result &res, const std::vector<int> &devs) {
+    const Options &o = job.o;
+    const CmpShape &sh = job.sh;
+    const size_t ns = sh.ns, S = job.S;
+    const double t0 = now();
+    MultiGpu mg(devs);
+    const int W = mg.W;
+    if (!mg.prepare(reinterpret_cast<const uint64_t *>(res.sigs()), ns, S)) {
+        std::fprintf(stderr, "[d2g] multi-GPU bit-sliced prepare overflowed on a skewed register column: falling back to one GPU\n");
+        return false;
+    }
+    const double t_prep = now() - t0;
+    Emitter em(o, res);
+    em.header();
+    std::vector<std::unique_ptr<DenseDevice>> dd(W);
+    for (int r = 0; r < W; ++r) dd[r].reset(new DenseDevice(job, mg.ctxs[r], d2g_allpairs_operand(mg.engs[r])));
+    const int NSLOT = 2 * W + 1;
+    std::vector<std::unique_ptr<HostSlot>> slots(NSLOT);
+    for (auto &sl : slots) sl.reset(new HostSlot(job));
+    double t_dev = 0, emit_busy = 0;
+    const double t_loop = now();
+    size_t nbatches = 0;
+    {
+        EmitQueue eq(em, NSLOT);
+        for (size_t next = 0; next < sh.nrows;) {
+            // one round: up to W consecutive row batches, one per GPU, launched back to back (asynchronous) ...
+            std::vector<Batch> round;
+            const double ta = now();
+            for (int r = 0; r < W && next < sh.nrows; ++r) {
+                const auto b = sh.batch(next, job.cap);
+                round.push_back({next, b.first, b.second});
+                launch_batch(job, *dd[r], round.back());
+                next = b.first;
+            }
+            // ... drained in row order into free slots; the emitter thread writes slot i while the next ones are copied / finished
+            for (size_t b = 0; b < round.size(); ++b) {
+                const int si = eq.acquire();
+                finish_batch(job, *dd[b], round[b], eq, si, *slots[si]);
+                ++nbatches;
+            }
+            t_dev += now() - ta;
+        }
+        eq.finish();
+        emit_busy = eq.t_busy;
+    }
+    if (o.verbosity) std::fprintf(stderr, "[d2g] cmp on %d GPUs (%s): %zu sketches x S=%zu: upload+exchange+prepare %.3fs, %zu batches %.3fs wall (device+D2H+epilogue %.3fs busy, emit %.3fs busy, overlapped)\n",
+                                  W, mg.transport(), ns, S, t_prep, nbatches, now() - t_loop, t_dev, emit_busy);
+    if (g_stats.on) {
+        Json dj = Json::array();
+        for (int r = 0; r < W; ++r) dj.push(k2_device_json(devs[r], mg.ctxs[r]));
+        g_stats.nest("cmp", Json::object().integer("sketches", ns).integer("sketchsize", S).integer("values", sh.total_vals).str("shape", sh.name(o)).str("algo", "bitslice")
+                     .str("transport", mg.transport()).integer("exchange_chunks", d2g_allpairs_chunks(mg.engs[0])).raw("bit_planes", planes_json(mg.ctxs[0], d2g_allpairs_operand(mg.engs[0])))
+                     .num("algorithmic_bytes", 8.0 * double(S) * double(ns) + 4.0 * double(sh.total_vals)).integer("batches", nbatches).integer("slot_values", job.cap).nest("devices", dj)
+                     .nest("wall_s", Json::object().num("upload_exchange_prepare", t_prep).num("batches", now() - t_loop).num("device_d2h_epilogue_busy", t_dev).num("emit_busy", emit_busy)));
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------ one GPU
+// `codes`: the truncated registers of a --fastcmp job (consumed), else empty
+void cmp_core_single(const DenseJob &job, Result &res, d2g_ctx *ctx, std::vector<uint8_t> &codes, const long double *trunc_ab, double t_densify) {
+    const Options &o = job.o;
+    const CmpShape &sh = job.sh;
+    const size_t ns = sh.ns, S = job.S;
+    d2g_cmp_set *set = nullptr;
+    const double t0 = now();
+    constexpr int NSLOT = 3;
+    std::unique_ptr<HostSlot> slots[NSLOT];
+    for (auto &sl : slots) sl.reset(new HostSlot(job));
+    Emitter em(o, res);
+    em.header();
+    if (job.trunc) check(ctx, d2g_cmp_set_create_codes(ctx, codes.data(), ns, S, o.regbytes, &set), "d2g_cmp_set_create_codes");
+    else check(ctx, d2g_cmp_set_create(ctx, reinterpret_cast<const uint64_t *>(res.sigs()), ns, S, job.need_gtlt ? int(D2G_CMP_DIRECT) : int(D2G_CMP_AUTO), &set), "d2g_cmp_set_create");
+    std::vector<uint8_t>().swap(codes);
+    const double t_set = now();
+    DenseDevice dev(job, ctx, set);
+    const double t_bufs = now();
+    if (o.verbosity) std::fprintf(stderr, "[d2g] cmp set-up: host slots + header + operand upload + prepare %.3fs, device buffers %.3fs (slots of %zu values)\n",
+                                  t_set - t0, t_bufs - t_set, job.cap);
+    double t_dev = 0, emit_busy = 0;
+    size_t nbatches = 0;
+    const double t_loop = now();
+    {
+        EmitQueue eq(em, NSLOT);
+        for (size_t r0 = 0; r0 < sh.nrows;) {
+            const auto b = sh.batch(r0, job.cap);
+            const Batch bt{r0, b.first, b.second};
+            const int si = eq.acquire();
+            const double ta = now();
+            launch_batch(job, dev, bt);
+            finish_batch(job, dev, bt, eq, si, *slots[si]);
+            t_dev += now() - ta;
+            r0 = bt.r1;
+            ++nbatches;
+        }
+        eq.finish();
+        emit_busy = eq.t_busy;
+        if (o.verbosity) std::fprintf(stderr, "[d2g] cmp: %zu sketches x S=%zu: upload+prepare+buffers %.3fs, %zu batches %.3fs wall (device+D2H+epilogue %.3fs busy, emit %.3fs busy, "
+                                              "overlapped) (algo %s)\n", ns, S, t_loop - t0, nbatches, now() - t_loop, t_dev, emit_busy,
+                                      d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE ? "bitslice" : d2g_cmp_set_algo(set) == D2G_CMP_PLANES ? "planes" : "direct");
+    }
+    if (g_stats.on) {
+        const bool bs = d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE, ab = job.trunc && job.need_gtlt;
+        Json dj = Json::array();
+        g_stats.nest("cmp", Json::object().integer("sketches", ns).integer("sketchsize", S).integer("values", sh.total_vals).str("shape", sh.name(o))
+                     .str("algo", bs ? "bitslice" : job.trunc ? "planes" : "direct").integer("regbytes", o.regbytes)
+                     .raw("truncation", !job.trunc ? "null" : ab ? "\"setsketch\"" : "\"bbit\"").raw("a", ab ? ldstr(trunc_ab[0]) : "null").raw("b", ab ? ldstr(trunc_ab[1]) : "null")
+                     .raw("bit_planes", bs ? planes_json(ctx, set) : "null").raw("sparse_tiles", bs ? sparse_json(ctx, set) : "null")
+                     .num("algorithmic_bytes", double(o.regbytes) * double(S) * double(ns) + 4.0 * double(sh.total_vals)).integer("batches", nbatches).integer("slot_values", job.cap)
+                     .nest("devices", dj.push(k2_device_json(o.device, ctx)))
+                     .nest("wall_s", Json::object().num("densify_scan", t_densify).num("slots_header_upload_prepare", t_set - t0).num("batches", now() - t_loop)
+                           .num("device_d2h_epilogue_busy", t_dev).num("emit_busy", emit_busy)));
+    }
+    if (g_release_at_exit) d2g_cmp_set_destroy(set);
+}
+
+}  // namespace
+
+// the D2G_* switches the context resolved when it was created (include/d2g.h: d2g_ctx_tuning)
+std::string context_switches_json(d2g_ctx *ctx) {
+    const int n = d2g_ctx_tuning(ctx, nullptr, 0);
+    if (n < 0) return "null";
+    std::string buf((size_t)n + 1, '\0');
+    d2g_ctx_tuning(ctx, &buf[0], buf.size());
+    buf.resize((size_t)n);
+    return buf;
+}
+
+void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_core.cpp:615-751
+    const size_t ns = res.names.size(), S = o.sketchsize;
+    if (res.nsigs() != ns * S) die("Empty signatures; trying to compare but don't have any");
+    const bool multiset = o.sspace != SPACE_SET;
+    double t_densify = 0;
+    if (o.kmer_result == ONE_PERM) {                                // cmp_core.cpp:686-718
+        size_t nfilled = 0;
+        const double td = now();
+        check(ctx, d2g_densify(res.sigs(), ns, S, &nfilled, int(o.workers())), "d2g_densify");
+        t_densify = now() - td;
+        if (o.verbosity) std::fprintf(stderr, "[d2g] densify scan %.3fs\n", t_densify);
+        if (o.verbosity && nfilled) std::fprintf(stderr, "Densified a total of %zu/%zu entries\n", nfilled, S * ns);
+    }
+    std::vector<float> lut(S + 1);
+    // --fastcmp <4|2|1>: make_compressed (cmp_core.cpp:741) truncates the registers and compare() takes its compressed branch
+    // (:362-449), whatever the sketch space: (gt, lt) of setsketch codes, equal b-bit codes
+    const bool trunc = o.regbytes < 8, trunc_gtlt = trunc && !o.bbit_sigs;
+    std::vector<uint8_t> codes;
+    long double trunc_ab[2] = {0.L, 0.L};
+    if (trunc) {
+        if (!ns) die("Empty signatures; trying to compress registers but don't have any");
+        codes.resize(ns * S * size_t(o.regbytes));
+        double mm[2] = {0, 0};
+        char err[200];
+        if (d2g_regs_truncate(res.sigs(), ns, S, o.regbytes, o.bbit_sigs, codes.data(), trunc_ab, mm, int(o.workers()), err, sizeof err) != D2G_OK)
+            die(std::string("dashing2 (MI355X): ") + err);
+        if (trunc_gtlt)                                             // cmp_core.cpp:262
+            std::fprintf(stderr, "Truncated via setsketch, a = %0.20Lg and b = %0.24Lg from min, max regs %Lg, %Lg\n", trunc_ab[0], trunc_ab[1],
+                         static_cast<long double>(mm[0]), static_cast<long double>(mm[1]));
+    }
+    const bool have_lut = !trunc && d2g_epilogue_lut(S, o.measure, o.k, multiset, lut.data()) == D2G_OK;
+    const bool need_gtlt = trunc ? trunc_gtlt : (!multiset && (S & (S - 1)) != 0);
+    if (const char *sparse = sparse_job_name(o)) {                  // cmp_core.cpp:776-805
+        refuse_sparse_job_out_of_scope(sparse, o, S);
+        if (!have_lut) refuse_out_of_scope(std::string(sparse) + " of values that are not a function of the equality count");
+        if (o.ok == DEDUP) { note_devices_ignored(o, "the greedy clustering runs on one GPU"); cmp_core_dedup(o, res, ctx, lut, t_densify); }
+        else { note_devices_ignored(o, "the nearest-neighbour selection runs on one GPU"); cmp_core_knn(o, res, ctx, lut, t_densify); }
+        return;
+    }
+    const DenseJob job(o, res, have_lut, need_gtlt, trunc, multiset, lut, trunc_gtlt ? &trunc_ab[1] : nullptr);
+    const std::vector<int> devs = job_devices(o);
+    if (devs.size() > 1 && !need_gtlt && !trunc && ns >= 2) {
+        if (cmp_core_multi(job, res, devs)) return;
+    } else note_devices_ignored(o, trunc ? "truncated registers (--fastcmp) are compared on one GPU"
+                                   : need_gtlt ? "a sketch size that is not a power of two needs (gt, lt) counts from the raw registers, which the gathered bit-plane operand does not hold"
+                                               : "fewer than two sketches");
+    cmp_core_single(job, res, ctx, codes, trunc_ab, t_densify);
+}
+
+}  // namespace d2h

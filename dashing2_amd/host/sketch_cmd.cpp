@@ -1,0 +1,391 @@
+// sketch_cmd.cpp -- `dashing2 sketch`: FASTX on disk -> stacked sketches, cache files, names.  Mirrors, for the in-scope options,
+//   sketch_main              src/sketch_main.cpp:23-152
+//   sketch_core + formats    src/sketch_core.cpp:14-31,108-161 ; src/fastxsketch.cpp:302-424,554-610
+//   makedest (cache names)   src/fastxmerge.cpp:70-120
+//   --parse-by-seq           src/fastxsketchbyseq.cpp:102-268,270-531
+#include "cli_common.h"
+#include "ingest_pipeline.h"
+#include <array>
+#include <cinttypes>
+#include <memory>
+#include <new>
+
+namespace d2h {
+
+namespace {
+
+// src/fastxmerge.cpp:70-120 for DNA, unspaced, w <= k: OPH set sketches and exact-counting multiset sketches
+std::string makedest(const Options &o, const std::string &path) {
+    std::string ret = path.substr(0, path.find_first_of(' '));
+    if (!o.outprefix.empty()) ret = o.outprefix + '/' + trim_folder(path);
+    if (o.seedseed != 0) ret += ".seed" + std::to_string(o.seedseed);
+    if (o.canon) ret += ".rc_canon";
+    ret += ".sketchsize" + std::to_string(o.sketchsize);
+    ret += ".k" + std::to_string(o.k);
+    if (o.count_threshold > 0) {
+        // fastxmerge.cpp:91-95 prints std::to_string(double) when fmod(threshold, 1) != 0 -- but Dashing2Options::count_threshold_ is a
+        // uint32_t (d2.h:103) filled by std::atoi (options.h:352), so that branch cannot be reached from the reference's CLI
+        // either: `-m 2.7` is 2 there and here.  The integer branch: std::to_string(int(count_threshold_)).
+        ret += ".ct_threshold" + std::to_string(int(o.count_threshold));
+    }
+    if (o.sspace != SPACE_SET) ret += ".ExactCounting";   // to_string(ct()), src/enums.cpp:47; fastxmerge.cpp:96-100
+    ret += o.sspace == SPACE_SET ? ".SetSpace" : ".MultisetSpace";   // to_string(sspace), src/enums.cpp:40-46
+    ret += ".DNA";                                        // bns::to_string(rht_) (absent bonsai; expected "DNA")
+    // to_suffix, src/enums.cpp:28-38, gives ".bmh" for BagMinHash.  Multiset sketches of this build follow the repository's
+    // BMH-D2G spec (the reference's sketch/bmh.h is absent): same layout, incomparable register values.  They get their own
+    // suffix so that a --cache directory shared with a stock dashing2 can never mix the two silently.
+    ret += o.sspace == SPACE_SET ? ".opss" : ".d2gbmh";
+    return ret;
+}
+
+// one cached sketch: [f64 card][f64 x S]   (src/fastxsketch.cpp:60-112,556-607)
+bool load_cached(const std::string &path, double *sig, double *card, size_t S) {
+    if (filesize(path) != 8 + 8 * S) {
+        if (isfile(path)) std::fprintf(stderr, "Expected %zu bytes of sketch, found %zu\n", S * 8, filesize(path) - 8);
+        return false;
+    }
+    std::FILE *fp = std::fopen(path.c_str(), "rb");
+    if (!fp) return false;
+    const bool ok = std::fread(card, 8, 1, fp) == 1 && std::fread(sig, 8, S, fp) == S;
+    std::fclose(fp);
+    return ok;
+}
+void write_cached(const std::string &path, const double *sig, double card, size_t S) {
+    std::FILE *fp = std::fopen(path.c_str(), "wb");
+    if (!fp) die("Failed to open file " + path + " for writing sketch.");
+    if (std::fwrite(&card, 8, 1, fp) != 1 || std::fwrite(sig, 8, S, fp) != S) die("Failed to write sketch " + path);
+    std::fclose(fp);
+}
+
+// stacked output: [u64 N][u64 S][f64 card x N][f64 x N*S]   (sketch_core.cpp:130-140, fastxsketch.cpp:236-240)
+void write_stacked(const Result &res, const Options &o) {
+    const size_t N = res.names.size(), S = o.sketchsize;
+    if (o.outfile.empty()) return;
+    if (o.outfile == "-" || o.outfile == "/dev/stdout")
+        die("Not yet supported: writing stacked sketches to file streams. This may change.");     // sketch_core.cpp:141-144
+    std::FILE *fp = std::fopen(o.outfile.c_str(), "wb");
+    if (!fp) die("Failed to open file " + o.outfile + " for in-place modification");
+    const uint64_t hdr[2] = {uint64_t(N), uint64_t(S)};
+    if (std::fwrite(hdr, 8, 2, fp) != 2 || std::fwrite(res.cardinalities.data(), 8, N, fp) != N ||
+        std::fwrite(res.signatures.data(), 8, N * S, fp) != N * S) die("Failed to write " + o.outfile);
+    std::fclose(fp);
+    // <out>.names.txt (sketch_core.cpp:146-161, enums.h:160 "%0.24g")
+    const std::string nf = o.outfile + ".names.txt";
+    if (!(fp = std::fopen(nf.c_str(), "wb"))) die("Failed to open outfile at " + nf);
+    std::fputs("#Name\tCardinality\n", fp);
+    for (size_t i = 0; i < N; ++i) {
+        std::fwrite(res.names[i].data(), 1, res.names[i].size(), fp);
+        std::fprintf(fp, "\t%0.24g", res.cardinalities[i]);
+        std::fputc('\n', fp);
+    }
+    std::fclose(fp);
+}
+
+// x87 finalisation (getcard / data, src/oph.h:240-263) and cache files leave the device threads through a small queue
+struct Fin { size_t g; std::vector<uint64_t> regs; std::vector<double> sigs, cards; };
+
+constexpr const char *SKETCH_KERNELS[3] = {"k0", "k1", "k3"};
+struct KAcc { int launches = 0; double total_ms = 0; };
+
+// What the device threads of one sketch job share.  `const` members and what they point to are read-only while the threads run.
+struct DeviceSide {
+    const Options &o;
+    const std::vector<size_t> &todo;
+    const GroupPlan &plan;
+    IngestPipeline &pipe;
+    BoundedQueue<Fin> &finq;
+    const std::vector<int> devs;
+    d2g_ctx *const first_ctx;                             // the context of thread 0; every other thread makes its own
+    std::mutex mu;                                        // guards everything below: each thread adds its sums once, as it ends
+    double t_gpu = 0;
+    uint64_t total_bases = 0;
+    size_t n_dev_groups = 0, n_host_groups = 0;
+    std::vector<std::array<KAcc, 3>> kacc;                // per device: k0, k1, k3
+    std::vector<size_t> groups_of;                        // per device
+
+    // sketches one group: the raw bytes parsed on the device, or the stream the host parser packed -> Fin; true: parsed on the device
+    bool sketch_group(d2g_ctx *ctx, d2g_sketcher *sk, IngestGroup &r, Fin &f, uint64_t &nb) {
+        const size_t S = o.sketchsize, b = plan.groups[r.g].first, e = plan.groups[r.g].second, n = e - b;
+        const uint64_t xormask = d2g_seed_mask(o.seedseed);                 // d2.h:224 -> enums.cpp:131-140
+        // the packed run stream of the group: parsed on the device (packed == NULL below), or by the host parser
+        const uint8_t *packed = nullptr; size_t packed_bytes = 0, nrun = 0;
+        const uint64_t *run_start = nullptr, *goff = nullptr; const uint32_t *run_len = nullptr;
+        bool on_device = false;
+        if (r.buf >= 0) {
+            const int rc = d2g_sketcher_ingest_fasta(sk, r.raw, r.raw_bytes, r.foff.data(), r.flen.data(), r.foff.size(), r.gfo.data(), n, o.k);
+            if (rc == D2G_OK) check(ctx, d2g_sketcher_ingested_runs(sk, &run_start, &run_len, &nrun, &goff, nullptr, &nb), "d2g_sketcher_ingested_runs");
+            pipe.release_buffer(r);
+            if (rc == D2G_ERR_UNSUPPORTED) {                            // e.g. a '+' line further down: the host parser takes the group
+                check(ctx, d2g_seqpack_create(o.k, &r.sp), "d2g_seqpack_create");
+                for (size_t x = b; x < e; ++x)
+                    if (d2g_seqpack_add_path(r.sp, o.paths[todo[x]].c_str()) != D2G_OK) die("Failed to open " + o.paths[todo[x]]);
+            } else check(ctx, rc, "d2g_sketcher_ingest_fasta");
+            on_device = rc == D2G_OK;
+        }
+        if (r.sp) {
+            packed = d2g_seqpack_packed(r.sp); packed_bytes = d2g_seqpack_packed_bytes(r.sp);
+            run_start = d2g_seqpack_run_start(r.sp); run_len = d2g_seqpack_run_len(r.sp); nrun = d2g_seqpack_nruns(r.sp);
+            goff = d2g_seqpack_genome_run_off(r.sp); nb = d2g_seqpack_nbases(r.sp);
+        }
+        if (o.sspace == SPACE_MULTISET) {
+            // fastxsketch.cpp:425-445: Counter -> BagMinHash; cardinality = total weight, signature = data()[0..S)
+            f.sigs.resize(n * S); f.cards.resize(n);
+            check(ctx, d2g_sketcher_run_bmh(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S,
+                                            double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh");
+        } else {
+            f.regs.resize(n * d2g_oph_m(S));
+            check(ctx, d2g_sketcher_run(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data()),
+                  "d2g_sketcher_run");
+        }
+        return on_device;
+    }
+
+    // one device thread: its own context + sketcher (a d2g_ctx is used by one thread at a time), groups until the pipeline ends
+    void run(d2g_ctx *ctx, size_t di) {
+        if (!ctx) {                                                         // every thread but the first makes its own context, in parallel
+            const int rc = d2g_ctx_create(devs[di], &ctx);
+            if (rc != D2G_OK) die(std::string("d2g_ctx_create (device thread, GPU ") + std::to_string(devs[di]) + "): " + d2g_strerror(rc));
+            if (g_stats.on) (void)d2g_set_timing(ctx, TIME_ALL);
+        }
+        d2g_sketcher *sk = nullptr;
+        check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+        double gpu = 0; uint64_t bases = 0; size_t ndevg = 0, nhostg = 0;
+        for (IngestGroup r; pipe.next(r);) {
+            if (r.failed()) continue;                                       // error recorded by the pipeline; drain the queue
+            const double t1 = now();
+            Fin f{r.g, {}, {}, {}};
+            uint64_t nb = 0;
+            ++(sketch_group(ctx, sk, r, f, nb) ? ndevg : nhostg);
+            gpu += now() - t1; bases += nb;
+            finq.push(std::move(f));
+            pipe.release(r);
+        }
+        std::array<KAcc, 3> mine;
+        if (g_stats.on)
+            for (int x = 0; x < 3; ++x) {
+                int n = 0; float avg = 0, last = 0;
+                if (d2g_kernel_ms(ctx, SKETCH_KERNELS[x], 1, &n, &avg, &last) == D2G_OK) { mine[x].launches = n; mine[x].total_ms = double(avg) * n; }
+            }
+        if (g_release_at_exit) { d2g_sketcher_destroy(sk); if (ctx != first_ctx) d2g_ctx_destroy(ctx); }
+        std::lock_guard<std::mutex> lk(mu);
+        t_gpu += gpu; total_bases += bases; n_dev_groups += ndevg; n_host_groups += nhostg;
+        groups_of[di] += ndevg + nhostg;
+        for (int x = 0; x < 3; ++x) { kacc[di][x].launches += mine[x].launches; kacc[di][x].total_ms += mine[x].total_ms; }
+    }
+};
+
+}  // namespace
+
+// Host ingest pipeline (ingest_pipeline.h).  Reader threads read() whole groups of FASTA files into staging
+// buffers, or parse and pack them themselves; device threads own a GPU context each: one uploads a group's raw bytes, K0 parses
+// and 2-bit-packs them on the device (d2g_sketcher_ingest_fasta), K1 / K3 sketch the stream; a finisher thread finalises the
+// registers (x87) and writes the cache files.  Inputs the device parser refuses (gz members, FASTQ, leading junk: first byte is
+// not '>') are parsed by the host parser (d2g_seqpack) on the reader thread instead, group by group.
+// WHICH PARSER IS THE DEFAULT -- measured, 1000 x 5 Mbp FASTA in the page cache, 16 usable cores (profiles/r03_e2e_cli.txt):
+// read()ing a group into staging costs a core as much as read()ing + packing it (22 vs 19 ms per 43 MB: the copy out of the
+// page cache into memory that is not cache-resident is the expensive half, and the packer works on a 5 MB buffer that
+// stays in L2), the device threads are not the bottleneck either way, and 0.8 GB of page-locked staging adds ~0.07 s of
+// teardown when the process exits.  So the device parser buys nothing end to end on this host and the HOST parser stays
+// the default; D2G_DEVICE_PARSE=1 selects the hybrid (device parser whenever a staging buffer is free).
+// The staging buffers are plain memory the readers fill at once; they are page-locked (d2g_host_register) as soon as the
+// GPU context exists, so neither the context creation nor the pinning delays the reading.
+void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
+    const double t_enter = now();
+    const size_t N = o.paths.size(), S = o.sketchsize, m = d2g_oph_m(S);
+    if (!N) die("Can't sketch empty path set");
+    res.names = o.paths;                                                // fastxsketch.cpp:625
+    res.destination_files.resize(N);
+    res.cardinalities.assign(N, -1.);
+    res.signatures.assign(N * S, 0.);
+    std::vector<size_t> todo;
+    std::vector<std::string> lines;                                     // o.paths[todo[t]]
+    for (size_t i = 0; i < N; ++i) {
+        res.destination_files[i] = makedest(o, o.paths[i]);
+        if (o.cache && isfile(res.destination_files[i]) &&
+            load_cached(res.destination_files[i], &res.signatures[i * S], &res.cardinalities[i], S))
+            continue;                                                   // fastxsketch.cpp:327-373
+        todo.push_back(i);
+        lines.push_back(o.paths[i]);
+    }
+    size_t limit = size_t(48) << 20;
+    if (const char *e = std::getenv("D2G_GROUP_BYTES")) { const long long v = std::atoll(e); if (v >= 1) limit = size_t(v); }   // tests: many small groups
+    const GroupPlan plan = plan_groups(lines, limit);
+    const auto &groups = plan.groups;
+    const double t_setup = now();
+    const std::vector<int> devs = job_devices(o);
+    const bool force_host = std::getenv("D2G_DEVICE_PARSE") == nullptr || std::getenv("D2G_HOST_PARSE") != nullptr || devs.size() > 1;
+    const IngestConfig cfg = ingest_config(plan, o.k, size_t(o.workers()), force_host);
+    std::unique_ptr<IngestPipeline> pipe;
+    try { pipe.reset(new IngestPipeline(lines, plan, cfg)); } catch (const std::bad_alloc &) { die("out of memory (ingest staging)"); }
+    d2g_ctx *ctx = lctx.get();                                          // the readers are busy: now wait for the GPU context
+    double t_pin = now();
+    for (const auto &b : pipe->buffers()) check(ctx, d2g_host_register(ctx, b.first, b.second), "d2g_host_register");
+    t_pin = now() - t_pin;
+    BoundedQueue<Fin> finq(groups.size() + 1);                          // never full: the device threads do not wait for the finisher
+    double t_fin = 0;                                                   // written by the finisher only, read after its join
+    std::thread finisher([&] {
+        for (Fin f; finq.pop(f);) {
+            const double t0 = now();
+            const size_t b = groups[f.g].first, e = groups[f.g].second, n = e - b;
+            if (!f.regs.empty()) {
+                f.sigs.resize(n * S); f.cards.resize(n);
+                check(nullptr, d2g_oph_finalize(f.regs.data(), n, m, S, f.sigs.data(), f.cards.data(), 2), "d2g_oph_finalize");
+            }
+            for (size_t t = b; t < e; ++t) {                            // results land by input index
+                const size_t i = todo[t];
+                std::memcpy(&res.signatures[i * S], &f.sigs[(t - b) * S], S * sizeof(double));   // fastxsketch.cpp:610
+                res.cardinalities[i] = f.cards[t - b];
+                if (o.cache) write_cached(res.destination_files[i], &f.sigs[(t - b) * S], f.cards[t - b], S);
+            }
+            t_fin += now() - t0;
+        }
+    });
+    // Device threads: two per GPU, each with its own context + sketcher -- the upload of one group overlaps the kernels and the
+    // synchronisations of the other.  D2G_DEVICES names several GPUs: every GPU gets its pair of threads and all of them take groups
+    // from the one pipeline (inputs dealt to the GPUs as they come free: file-sharded, no collectives -- SURVEY 8e; the loop being
+    // sharded is the reference's `for` over files, src/fastxsketch.cpp:302); the stacked output is in input order whatever GPU
+    // sketched a group.
+    int ndev = groups.size() > 1 ? 2 : 1;
+    if (const char *e = std::getenv("D2G_DEVICE_THREADS")) { const int v = std::atoi(e); if (v >= 1 && v <= 8) ndev = v; }
+    const size_t nthreads_dev = std::max<size_t>(1, std::min<size_t>(size_t(ndev) * devs.size(), std::max<size_t>(groups.size(), 1)));
+    DeviceSide ds{o, todo, plan, *pipe, finq, devs, ctx, {}, 0, 0, 0, 0, std::vector<std::array<KAcc, 3>>(devs.size()), std::vector<size_t>(devs.size(), 0)};
+    std::vector<std::thread> more;
+    const double t_dev0 = now();
+    for (size_t t = 1; t < nthreads_dev; ++t) more.emplace_back([&ds, t, ndev] { ds.run(nullptr, t / size_t(ndev)); });
+    const double t_dev1 = now();
+    ds.run(ctx, 0);
+    for (auto &th : more) th.join();
+    const double t_dev2 = now();
+    finq.close();
+    finisher.join();
+    if (o.verbosity) std::fprintf(stderr, "[d2g] device side: %zu device threads over %zu GPU(s) (started in %.3fs), device loops %.3fs wall, drain of the finisher %.3fs\n", nthreads_dev,
+                                  devs.size(), t_dev1 - t_dev0, t_dev2 - t_dev1, now() - t_dev2);
+    pipe->join();
+    const double t_pipe = now();
+    // the staging buffers stay page-locked until the process ends (it leaves through _exit): unpinning 0.8 GB costs more than
+    // the whole device work of a small job; D2G_FULL_TEARDOWN=1 releases them
+    if (g_release_at_exit) for (const auto &b : pipe->buffers()) (void)d2g_host_unregister(ctx, b.first);
+    else pipe->abandon_buffers();
+    if (!pipe->error().empty()) die(pipe->error());
+    if (o.verbosity) std::fprintf(stderr, "[d2g] sketched %zu inputs (%" PRIu64 " bases in the packed streams) in %zu groups (%zu parsed on the device, %zu by the host "
+                                          "parser): reader threads %.3fs in all (%.3fs reading raw groups, %.3fs reading + packing, the rest waiting for queue space) over %zu threads, device threads: H2D+K0+K1+D2H %.3fs busy in all, finisher thread: x87 finalise+cache %.3fs; "
+                                          "%zu staging buffers of %zu MiB page-locked in %.3fs\n",
+                                  todo.size(), ds.total_bases, groups.size(), ds.n_dev_groups, ds.n_host_groups, pipe->t_readers(), pipe->t_read_raw(), pipe->t_host_pack(), cfg.readers,
+                                  ds.t_gpu, t_fin, cfg.nbufs, cfg.buf_bytes >> 20, t_pin);
+    if (o.verbosity) std::fprintf(stderr, "[d2g] sketch wall: setup (stat, cache probe) %.3fs, ingest pipeline %.3fs\n", t_setup - t_enter, t_pipe - t_setup);
+    if (g_stats.on) {
+        Json dj = Json::array();
+        for (size_t d = 0; d < devs.size(); ++d) {
+            Json e = device_json(devs[d]);
+            e.integer("groups", ds.groups_of[d]);
+            for (int x = 0; x < 3; ++x) e.nest(SKETCH_KERNELS[x], Json::object().integer("launches", ds.kacc[d][x].launches).num("total_ms", ds.kacc[d][x].total_ms));
+            dj.push(e);
+        }
+        const bool multiset = o.sspace == SPACE_MULTISET;
+        // ceil(L/4) + 8 m per input (set sketches), + 8 for the total weight of a multiset sketch
+        const double alg = double((ds.total_bases + 3) / 4) + double(todo.size()) * (8.0 * double(multiset ? S : m) + (multiset ? 8.0 : 0.0));
+        g_stats.nest("sketch", Json::object().integer("inputs", N).integer("sketched", todo.size()).integer("from_cache", N - todo.size()).integer("k", o.k)
+                     .integer("sketchsize", S).str("space", multiset ? "multiset (K3: counts + BagMinHash)" : "set (K1: OPH)").integer("groups", groups.size())
+                     .integer("groups_parsed_on_device", ds.n_dev_groups).integer("bases", ds.total_bases).num("algorithmic_bytes", alg)
+                     .integer("device_threads", nthreads_dev).integer("parser_threads", cfg.readers).nest("devices", dj)
+                     .nest("wall_s", Json::object().num("setup", t_setup - t_enter).num("ingest_pipeline", t_pipe - t_setup).num("device_loops", t_dev2 - t_dev1)
+                           .num("device_threads_busy_sum", ds.t_gpu).num("parser_threads_sum", pipe->t_readers()).num("finisher_x87_and_cache", t_fin)));
+    }
+    pipe.reset();
+    write_stacked(res, o);
+}
+
+// --parse-by-seq (sketch_core.cpp:23-29 -> fastxsketchbyseq.cpp:102-268,270-531): one sketch per record of
+// ONE input file; OPH set sketches (cardinality = exact distinct k-mer count when the estimate is below
+// 10 S, lines 415-430) or multiset sketches; names are the record names.
+void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
+    if (o.paths.size() != 1)
+        die("parse-by-seq currently only handles one file at a time. To process multiple files, simply concatenate them into one file, and run dashing2 on that.");
+    const size_t S = o.sketchsize, m = d2g_oph_m(S);
+    const uint64_t xormask = d2g_seed_mask(o.seedseed);
+    d2g_seqpack *sp = nullptr;
+    check(nullptr, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
+    if (d2g_seqpack_add_path_by_record(sp, o.paths[0].c_str()) != D2G_OK) die("Failed to read from " + o.paths[0]);
+    d2g_ctx *ctx = lctx.get();
+    const size_t N = d2g_seqpack_ngenomes(sp);
+    res.names.resize(N);
+    for (size_t i = 0; i < N; ++i) res.names[i] = d2g_seqpack_name(sp, i);
+    res.destination_files.assign(N, std::string());
+    res.cardinalities.assign(N, 0.);
+    res.signatures.assign(N * S, 0.);
+    const size_t total_bytes = d2g_seqpack_packed_bytes(sp);
+    const uint8_t *packed = d2g_seqpack_packed(sp);
+    const uint64_t *run_start = d2g_seqpack_run_start(sp), *goff = d2g_seqpack_genome_run_off(sp);
+    const uint32_t *run_len = d2g_seqpack_run_len(sp);
+    d2g_sketcher *sk = nullptr;
+    check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+    std::vector<uint64_t> regs, rs_rel, goff_rel, ndist;
+    std::vector<double> sigs, cards;
+    const size_t max_rec = std::max<size_t>(1, (size_t(64) << 20) / m);            // <= 512 MiB of registers per launch
+    for (size_t g0 = 0; g0 < N;) {
+        // batch [g0, g1): bounded by records and by packed bytes (the slice is re-based so that only it is uploaded)
+        size_t g1 = g0;
+        const uint64_t r0 = goff[g0];
+        const uint64_t base0 = r0 < goff[N] ? (run_start[r0] & ~uint64_t(15)) : 0;
+        while (g1 < N && g1 - g0 < max_rec) {
+            const uint64_t r1 = goff[g1 + 1];
+            const uint64_t endb = r1 > r0 ? run_start[r1 - 1] + run_len[r1 - 1] : base0;
+            if (g1 > g0 && endb - base0 > (uint64_t(192) << 20)) break;            // ~48 MB of packed bases
+            ++g1;
+        }
+        const size_t n = g1 - g0, r1 = goff[g1], nrun = r1 - r0;
+        rs_rel.resize(nrun); goff_rel.resize(n + 1);
+        for (size_t r = 0; r < nrun; ++r) rs_rel[r] = run_start[r0 + r] - base0;
+        for (size_t g = 0; g <= n; ++g) goff_rel[g] = goff[g0 + g] - r0;
+        const uint8_t *pk = packed + base0 / 4;
+        const uint64_t endb = nrun ? run_start[r1 - 1] + run_len[r1 - 1] : base0;
+        const size_t pk_bytes = std::min<size_t>(total_bytes - base0 / 4, (endb - base0 + 3) / 4 + 64);   // slice + its 64 readable pad bytes
+        sigs.resize(n * S); cards.resize(n);
+        if (o.sspace == SPACE_MULTISET) {
+            check(ctx, d2g_sketcher_run_bmh(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k, o.canon,
+                                            xormask, S, double(o.count_threshold), sigs.data(), cards.data()), "d2g_sketcher_run_bmh");
+        } else {
+            regs.resize(n * m);
+            check(ctx, d2g_sketcher_run(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k, o.canon,
+                                        xormask, S, regs.data()), "d2g_sketcher_run");
+            check(ctx, d2g_oph_finalize(regs.data(), n, m, S, sigs.data(), cards.data(), int(o.workers())), "d2g_oph_finalize");
+            bool need = false;
+            for (size_t i = 0; i < n; ++i) {
+                if (std::isnan(cards[i])) cards[i] = 0.;                              // fastxsketchbyseq.cpp:410-414
+                need |= cards[i] < 10. * double(S);
+            }
+            if (need) {                                                               // lines 415-430: exact distinct count
+                ndist.resize(n);
+                check(ctx, d2g_sketcher_run_distinct(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k,
+                                                     o.canon, xormask, ndist.data()), "d2g_sketcher_run_distinct");
+                for (size_t i = 0; i < n; ++i) if (cards[i] < 10. * double(S)) cards[i] = double(ndist[i]);
+            }
+        }
+        std::memcpy(&res.signatures[g0 * S], sigs.data(), n * S * sizeof(double));
+        std::memcpy(&res.cardinalities[g0], cards.data(), n * sizeof(double));
+        g0 = g1;
+    }
+    d2g_sketcher_destroy(sk);
+    d2g_seqpack_destroy(sp);
+    write_stacked(res, o);
+}
+
+int sketch_main(int argc, char **argv) {                          // src/sketch_main.cpp:23-152
+    Options o;
+    if (int rc = parse_options(argc, argv, o)) return rc - 1;
+    apply_fmt_compat(o);
+    if (o.paths.empty()) { std::fprintf(stderr, "No paths provided. See usage.\n"); sketch_usage(); return 1; }
+    o.device = job_devices(o)[0];
+    g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
+    g_stats.str("command", "sketch");
+    LazyCtx lctx(o, D2G_WARM_COPY | (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : D2G_WARM_K2));
+    Result res;
+    if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
+    if (o.verbosity) std::fprintf(stderr, "[d2g] GPU context %.3fs + warm-up %.3fs on a helper thread, under the host ingest\n", lctx.t_create, lctx.t_warm);
+    res.nq = o.nq;
+    if (!o.cmpout.empty()) cmp_core(o, res, lctx.get());           // sketch_main.cpp:144-148
+    g_stats.nest("context", Json::object().num("create_s", lctx.t_create).num("warmup_s", lctx.t_warm).raw("switches", context_switches_json(lctx.get())));
+    return 0;
+}
+
+}  // namespace d2h

@@ -16,7 +16,7 @@
 // files written here carry valid weighted-minhash sketches that are comparable among themselves, not with
 // files written by a stock dashing2.  The reference's `to_sigs<uint64_t>()` ("hashes") is also absent source:
 // the bit patterns of the register doubles are written in its place (injective, equality-preserving).
-#include "../../include/d2g.h"
+#include "cli_common.h"
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -44,11 +44,6 @@ int wsketch_usage() {                                             // wsketch.cpp
     return 1;
 }
 
-[[noreturn]] void wdie(const std::string &msg) {
-    std::fprintf(stderr, "Exception %s\n", msg.c_str());
-    std::exit(1);
-}
-
 // whole file as T (reference: FReader::getvec / fromfile, wsketch.cpp:113-129; .gz/.xz/.bz2 go through the
 // same external decompressors, wsketch.cpp:92-109)
 template <class T>
@@ -59,7 +54,7 @@ std::vector<T> read_vec(const std::string &path) {
     else if (ends(".xz")) cmd = "xz -dc ";
     else if (ends(".bz2")) cmd = "bzip2 -dc ";
     std::FILE *fp = cmd.empty() ? std::fopen(path.c_str(), "rb") : ::popen((cmd + path).c_str(), "r");
-    if (!fp) wdie("Failed to open path '" + path + "' for reading");
+    if (!fp) die("Failed to open path '" + path + "' for reading");
     std::vector<T> ret;
     T buf[4096];
     for (size_t n; (n = std::fread(buf, sizeof(T), 4096, fp)) > 0;) ret.insert(ret.end(), buf, buf + n);
@@ -89,8 +84,8 @@ std::vector<uint64_t> read_ids(const std::string &path, bool u32) {
 
 void write_file(const std::string &path, const void *data, size_t nbytes) {
     std::FILE *fp = std::fopen(path.c_str(), "wb");
-    if (!fp) wdie("Failed to open " + path);
-    if (nbytes && std::fwrite(data, 1, nbytes, fp) != nbytes) wdie("Failed to write " + path);
+    if (!fp) die("Failed to open " + path);
+    if (nbytes && std::fwrite(data, 1, nbytes, fp) != nbytes) die("Failed to write " + path);
     std::fclose(fp);
 }
 
@@ -127,13 +122,13 @@ int wsketch_main(int argc, char **argv) {
         return wsketch_usage();
     }
     if (outpref.empty()) outpref = argv[optind];
-    if (sketchsize < 1) wdie("sketch size must be positive");
+    if (sketchsize < 1) die("sketch size must be positive");
 
     auto open_ctx = []() {
         d2g_ctx *ctx = nullptr;
         const char *dv = std::getenv("D2G_DEVICE");
         const int rc = d2g_ctx_create(dv ? std::atoi(dv) : 0, &ctx);
-        if (rc != D2G_OK) wdie(std::string("dashing2 (MI355X) needs a gfx950 GPU; d2g_ctx_create: ") + d2g_strerror(rc) + " (there is no CPU fallback)");
+        if (rc != D2G_OK) die(std::string("dashing2 (MI355X) needs a gfx950 GPU; d2g_ctx_create: ") + d2g_strerror(rc) + " (there is no CPU fallback)");
         return ctx;
     };
     auto run = [&](d2g_ctx *ctx, const std::vector<uint64_t> &set_off, const std::vector<double> *w, std::vector<double> &sigs,
@@ -147,7 +142,7 @@ int wsketch_main(int argc, char **argv) {
         sigs.assign(nsets * sketchsize, 0.); tw.assign(nsets, 0.); owner.assign(nsets * sketchsize, ~0ull);
         const int rc = d2g_bmh_from_weighted_ids(ctx, pos.data(), w ? w->data() : nullptr, set_off.data(), nsets, sketchsize, sigs.data(),
                                                  tw.data(), owner.data());
-        if (rc != D2G_OK) wdie(std::string("d2g_bmh_from_weighted_ids: ") + d2g_strerror(rc) + " (" + d2g_last_error(ctx) + ")");
+        if (rc != D2G_OK) die(std::string("d2g_bmh_from_weighted_ids: ") + d2g_strerror(rc) + " (" + d2g_last_error(ctx) + ")");
     };
 
     if (diff == 3) {                                               // CSR: wsketch.cpp:297-349
@@ -159,12 +154,12 @@ int wsketch_main(int argc, char **argv) {
         const std::vector<uint64_t> ids = read_ids(idpath, u32);
         std::vector<uint64_t> indptr = ip32 ? [&] { const auto v = read_vec<uint32_t>(ippath); return std::vector<uint64_t>(v.begin(), v.end()); }()
                                             : read_vec<uint64_t>(ippath);
-        if (indptr.size() < 2) wdie("No sketches found in file; this suggests there was an error.");
+        if (indptr.size() < 2) die("No sketches found in file; this suggests there was an error.");
         std::vector<double> weights;
         const bool have_w = !cpath.empty() && cpath != "-";
         if (have_w) weights = read_weights(cpath, f32);
-        if (indptr.back() > ids.size() || (have_w && weights.size() < indptr.back())) wdie("indptr runs past the id / weight arrays");
-        for (size_t i = 0; i + 1 < indptr.size(); ++i) if (indptr[i] > indptr[i + 1]) wdie("indptr is not monotone");
+        if (indptr.back() > ids.size() || (have_w && weights.size() < indptr.back())) die("indptr runs past the id / weight arrays");
+        for (size_t i = 0; i + 1 < indptr.size(); ++i) if (indptr[i] > indptr[i + 1]) die("indptr is not monotone");
         const uint64_t nsketches = indptr.size() - 1;
         // sets are addressed relative to indptr[0] (the reference indexes weights[j], indices[j] for j in [indptr[i], indptr[i+1]))
         const uint64_t base = indptr.front();
@@ -189,17 +184,17 @@ int wsketch_main(int argc, char **argv) {
         }
         {   // stacked registers: [u64 n][u64 S][f64 total weight x n][f64 x n*S]  -- the `cmp --presketched` layout
             std::FILE *fp = std::fopen((outpref + ".sampled.regs.stacked" + tail + ".f64").c_str(), "wb");
-            if (!fp) wdie("Failed to open " + outpref + ".sampled.regs.stacked" + tail + ".f64");
+            if (!fp) die("Failed to open " + outpref + ".sampled.regs.stacked" + tail + ".f64");
             const uint64_t hdr[2] = {nsketches, sketchsize};
             if (std::fwrite(hdr, 8, 2, fp) != 2 || std::fwrite(tw.data(), 8, tw.size(), fp) != tw.size() ||
                 std::fwrite(sigs.data(), 8, sigs.size(), fp) != sigs.size())
-                wdie("Failed to write MH registers to disk.");
+                die("Failed to write MH registers to disk.");
             std::fclose(fp);
         }
         write_file(outpref + ".sampled.hashes.stacked" + tail + ".i64", sigs.data(), sigs.size() * 8);   // to_sigs<uint64_t>(): see header
         {
             std::FILE *fp = std::fopen((outpref + ".sampled.info.txt").c_str(), "wb");
-            if (!fp) wdie("Failed to open " + outpref + ".sampled.info.txt");
+            if (!fp) die("Failed to open " + outpref + ".sampled.info.txt");
             for (double t : tw) std::fprintf(fp, "%0.30Lg\n", (long double)t);                           // nlfmt<long double>, enums.h:164
             std::fclose(fp);
         }
@@ -216,7 +211,7 @@ int wsketch_main(int argc, char **argv) {
     std::vector<double> weights;
     if (!cpath.empty()) {
         weights = read_weights(cpath, f32 == -2 ? 0 : f32);        // the 1-D reader has no uint32 branch (wsketch.cpp:217-223)
-        if (weights.size() != ids.size()) wdie("weight and id files hold different numbers of elements");
+        if (weights.size() != ids.size()) die("weight and id files hold different numbers of elements");
     }
     d2g_ctx *ctx = open_ctx();
     std::vector<uint64_t> set_off = {0, ids.size()};
@@ -227,7 +222,7 @@ int wsketch_main(int argc, char **argv) {
     write_file(outpref + ".sampled.indices.u64", sigs.data(), sigs.size() * 8);      // tuple element 1 = to_sigs<uint64_t>(): see header
     {
         std::FILE *fp = std::fopen((outpref + ".sampled.hashes.f64").c_str(), "wb");
-        if (!fp) wdie("Failed to open sigpath " + outpref + ".sampled.hashes.f64");
+        if (!fp) die("Failed to open sigpath " + outpref + ".sampled.hashes.f64");
         const double t = tw[0];
         std::fwrite(&t, 8, 1, fp);
         std::fwrite(sigs.data(), 8, sigs.size(), fp);

@@ -827,3 +827,62 @@ def test_cli_gpu_stats_json(genomes, tmp_path):
     # an unknown flag is still rejected like the reference does (options.h:290-304)
     r = subprocess.run([EXE, "cmp", "--gpu-statz", "x", str(o)], capture_output=True)
     assert r.returncode != 0 and b"not found in expected set" in r.stderr
+
+
+def test_cli_sketch_missing_input_among_many_groups(genomes, tmp_path):
+    """A path that does not exist in the middle of many one-input groups: the failed group is still queued (empty), every device
+    thread drains the queue, and the run ends with `Failed to open <path>`, exit code 1 and no stacked file -- with the host
+    parser, with the hybrid of device and host parser, and with the device threads of two (loopback) GPUs."""
+    missing = str(tmp_path / "missing.fa")
+    paths = genomes * 3
+    paths = paths[:len(paths) // 2] + [missing] + paths[len(paths) // 2:]
+    lst = tmp_path / "l.txt"
+    lst.write_text("".join(p + "\n" for p in paths))
+    out = tmp_path / "out"
+    envs = [{"D2G_GROUP_BYTES": "1000"}]
+    envs.append(dict(envs[-1], D2G_DEVICE_PARSE="1"))
+    envs.append(dict(envs[-1], D2G_DEVICES="0,0"))
+    for env in envs:
+        r = subprocess.run([EXE, "sketch", "-p", "3", "-F", str(lst), "-o", str(out)], capture_output=True, env=dict(os.environ, **env), timeout=120)
+        assert r.returncode == 1, (env, r.stderr.decode()[-1500:])
+        assert ("Failed to open " + missing).encode() in r.stderr, (env, r.stderr.decode()[-1500:])
+        assert not out.exists(), env
+
+
+def _key_paths(x, prefix=""):
+    """The set of key paths of a JSON value: list elements collapse to `[]`, the contents of context.switches are left out."""
+    if isinstance(x, dict) and prefix != "context.switches":
+        return set().union(*[_key_paths(v, prefix + "." + k if prefix else k) for k, v in x.items()]) if x else {prefix}
+    if isinstance(x, list):
+        return set().union(*[_key_paths(v, prefix + "[]") for v in x]) if x else {prefix}
+    return {prefix}
+
+
+def _stats_key_jobs(genomes, d):
+    """name -> sorted key paths of the --gpu-stats object of five jobs over the 7-genome fixture at S = 256."""
+    import json
+    k, S = 31, 256
+    st, o = d / "keys_st.json", d / "keys_s.bin"
+    cmp_ = ["cmp", "--presketched", "-k", str(k), "--cmpout", str(d / "keys_c.out"), "--gpu-stats", str(st)]
+    jobs = [("sketch --cmpout", ["sketch", "-k", str(k), "-S", str(S), "-o", str(o), "--cmpout", str(d / "keys_c.out"), "--gpu-stats", str(st)] + genomes, {}),
+            ("cmp --presketched", cmp_ + [str(o)], {}),
+            ("cmp --presketched D2G_DEVICES=0,0", cmp_ + [str(o)], {"D2G_DEVICES": "0,0"}),
+            ("cmp --topk 7", cmp_ + ["--topk", "7", str(o)], {}),
+            ("cmp --greedy 0.25", cmp_ + ["--greedy", "0.25", str(o)], {})]
+    got = {}
+    for name, args, env in jobs:
+        _run(args, env=dict(os.environ, **env))
+        got[name] = sorted(_key_paths(json.loads(st.read_text())))
+    return got
+
+
+def test_cli_gpu_stats_keys_are_stable(genomes, tmp_path):
+    """The --gpu-stats object keeps its keys at their nesting: for sketch + --cmpout, dense cmp on one and on two (loopback) GPUs,
+    --topk and --greedy, the set of key paths equals tests/cli_stats_keys.json (written from the CLI as it was before its source was
+    split by job)."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "cli_stats_keys.json")))
+    got = _stats_key_jobs(genomes, tmp_path)
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], (name, sorted(set(got[name]) ^ set(want[name])))

@@ -467,8 +467,10 @@ def test_missing_rccl_is_an_error_code_not_a_crash():
 
 
 def test_host_threading_under_thread_sanitizer():
-    """the two host pipelines of the CLI -- parser pool -> bounded queue -> consumer over d2g_seqpack, and producer -> slot
-    queue -> emitter thread over the float formatter -- built with -fsanitize=thread (csrc `make tsan`): no report, exit 0"""
+    """the two host pipelines of the CLI, from the headers the CLI itself compiles -- the ingest of `sketch` (host/ingest_pipeline.h,
+    host/bounded_queue.h: reader threads -> staging buffers or d2g_seqpack -> ready queue -> several consumers -> finisher, with its
+    error and back-pressure paths and the group planner), and producer -> slot queue -> emitter thread over the float formatter --
+    built with -fsanitize=thread (csrc `make tsan`): no report, exit 0"""
     r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "dashing2_amd", "csrc"), "tsan"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "host threads selftest OK" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
     assert "ThreadSanitizer" not in r.stdout + r.stderr
