@@ -14,7 +14,7 @@ from .capi import (  # noqa: F401
     wang_hash, seed_mask, oph_xor_const, oph_m, oph_finalize, densify, epilogue_lut,
     epilogue_gtlt, epilogue_neq, host_epilogue_ut, operand_layout, sparse_bin_geometry, ut_count, ut_partition,
     regs_truncate, epilogue_trunc_neq, epilogue_trunc_gtlt, host_epilogue_trunc_ut, host_epilogue_trunc_rect,
-    knn_finish, KnnOverflow, TIME_KNN, dedup_clusters, TIME_DEDUP, bmh_check_weights,
+    knn_finish, KnnOverflow, TIME_KNN, dedup_clusters, TIME_DEDUP, bmh_check_weights, wang_hash_inverse, oph_kmer_ids,
 )
 
 __all__ = [
@@ -25,5 +25,5 @@ __all__ = [
     "wang_hash", "seed_mask", "oph_xor_const", "oph_m", "oph_finalize", "densify", "epilogue_lut",
     "epilogue_gtlt", "epilogue_neq", "host_epilogue_ut", "operand_layout", "sparse_bin_geometry", "ut_count", "ut_partition",
     "regs_truncate", "epilogue_trunc_neq", "epilogue_trunc_gtlt", "host_epilogue_trunc_ut", "host_epilogue_trunc_rect",
-    "knn_finish", "KnnOverflow", "TIME_KNN", "dedup_clusters", "TIME_DEDUP", "bmh_check_weights",
+    "knn_finish", "KnnOverflow", "TIME_KNN", "dedup_clusters", "TIME_DEDUP", "bmh_check_weights", "wang_hash_inverse", "oph_kmer_ids",
 ]

@@ -63,6 +63,8 @@ SIGNATURES = {
     "d2g_set_timing": (_int, [_vp, _int]),
     "d2g_kernel_ms": (_int, [_vp, _cp, _int, C.POINTER(_int), C.POINTER(_f32), C.POINTER(_f32)]),
     "d2g_wang_hash": (_u64, [_u64]),
+    "d2g_wang_hash_inverse": (_u64, [_u64]),
+    "d2g_oph_kmer_ids": (_int, [_vp, _sz, _sz, _sz, _vp]),
     "d2g_seed_mask": (_u64, [_u64]),
     "d2g_oph_xor_const": (_u64, []),
     "d2g_oph_m": (_sz, [_sz]),
@@ -100,6 +102,9 @@ SIGNATURES = {
     "d2g_oph_plan_nkmers": (_u64, [_vp]),
     "d2g_oph_plan_nbases": (_u64, [_vp]),
     "d2g_oph_sketch_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, _vp, _vp]),
+    "d2g_oph_count_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, _vp, _vp, _vp]),
+    "d2g_oph_sketch_counts": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp, _vp]),
+    "d2g_sketcher_run_counts": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp, _vp]),
     "d2g_sketcher_create": (_int, [_vp, C.POINTER(_vp)]),
     "d2g_sketcher_destroy": (None, [_vp]),
     "d2g_sketcher_run": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp]),
@@ -222,6 +227,21 @@ def _np_ptr(a):
 # ---------------------------------------------------------------- host-side primitives
 def wang_hash(x):
     return int(lib().d2g_wang_hash(x & 0xFFFFFFFFFFFFFFFF))
+
+
+def wang_hash_inverse(x):
+    return int(lib().d2g_wang_hash_inverse(x & 0xFFFFFFFFFFFFFFFF))
+
+
+def oph_kmer_ids(regs, S):
+    """regs u64 [n][m] -> ids u64 [n][S]: the masked k-mer behind each of the first S registers (DHasher::inverse)"""
+    regs = np.ascontiguousarray(regs, np.uint64)
+    n, m = regs.shape
+    ids = np.empty((n, S), np.uint64)
+    rc = lib().d2g_oph_kmer_ids(_np_ptr(regs), n, m, S, _np_ptr(ids))
+    if rc:
+        raise D2GError(rc)
+    return ids
 
 
 def seed_mask(seed):
@@ -592,6 +612,25 @@ class Context:
         packed, rs, rl, go = sp.arrays()
         return self.oph_sketch(packed, rs, rl, go, sp.k, S, canon, xormask)
 
+    def oph_sketch_counts(self, packed, run_start, run_len, genome_run_off, k, S, canon=True, xormask=0):
+        """host arrays -> (regs u64 [n][m], counts u32 [n][m]): K1, then how often the k-mer behind each register occurred"""
+        packed = np.ascontiguousarray(packed, np.uint8)
+        run_start = np.ascontiguousarray(run_start, np.uint64)
+        run_len = np.ascontiguousarray(run_len, np.uint32)
+        genome_run_off = np.ascontiguousarray(genome_run_off, np.uint64)
+        n = genome_run_off.size - 1
+        m = oph_m(S)
+        regs = np.empty((n, m), np.uint64)
+        counts = np.empty((n, m), np.uint32)
+        self._check(lib().d2g_oph_sketch_counts(self._h, _np_ptr(packed), packed.size, _np_ptr(run_start), _np_ptr(run_len),
+                                                run_start.size, _np_ptr(genome_run_off), n, k, int(canon), xormask, S,
+                                                _np_ptr(regs), _np_ptr(counts)))
+        return regs, counts
+
+    def oph_sketch_counts_seqpack(self, sp: SeqPack, S, canon=True, xormask=0):
+        packed, rs, rl, go = sp.arrays()
+        return self.oph_sketch_counts(packed, rs, rl, go, sp.k, S, canon, xormask)
+
     def sketcher(self):
         return Sketcher(self)
 
@@ -683,6 +722,10 @@ class Context:
 
     def oph_sketch_dev(self, plan, packed_dev_ptr, S, regs_dev_ptr, canon=True, xormask=0, stream=None):
         self._check(lib().d2g_oph_sketch_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, regs_dev_ptr, stream))
+
+    def oph_count_dev(self, plan, packed_dev_ptr, S, regs_dev_ptr, counts_dev_ptr, canon=True, xormask=0, stream=None):
+        """counts u32 [n][m] of the k-mers whose id equals the register they map to, for any registers; does not synchronise"""
+        self._check(lib().d2g_oph_count_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, regs_dev_ptr, counts_dev_ptr, stream))
 
     # -- K2 ------------------------------------------------------------------
     def cmp_set(self, sig_bits_host, algo=CMP_AUTO):
@@ -821,6 +864,27 @@ class Sketcher:
         self.ctx._check(lib().d2g_sketcher_run(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
                                                _np_ptr(go), n, sp.k, int(canon), xormask, S, _np_ptr(regs)))
         return regs
+
+    def run_counts(self, sp, S, canon=True, xormask=0):
+        """-> (regs u64 [n][m], counts u32 [n][m])"""
+        packed, rs, rl, go = sp.arrays()
+        n = go.size - 1
+        regs = np.empty((n, oph_m(S)), np.uint64)
+        counts = np.empty((n, oph_m(S)), np.uint32)
+        self.ctx._check(lib().d2g_sketcher_run_counts(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
+                                                      _np_ptr(go), n, sp.k, int(canon), xormask, S, _np_ptr(regs), _np_ptr(counts)))
+        return regs, counts
+
+    def run_counts_ingested(self, runs, S, canon=True, xormask=0, k=None):
+        """run_counts over the stream ingested last (packed == NULL)"""
+        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
+                      np.ascontiguousarray(runs[2], np.uint64))
+        n = go.size - 1
+        regs = np.empty((n, oph_m(S)), np.uint64)
+        counts = np.empty((n, oph_m(S)), np.uint32)
+        self.ctx._check(lib().d2g_sketcher_run_counts(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
+                                                      self.k if k is None else k, int(canon), xormask, S, _np_ptr(regs), _np_ptr(counts)))
+        return regs, counts
 
     def run_bmh(self, sp, S, canon=True, xormask=0, count_threshold=0.0):
         packed, rs, rl, go = sp.arrays()

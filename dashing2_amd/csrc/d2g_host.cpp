@@ -56,6 +56,21 @@ uint64_t d2g_wang_hash(uint64_t k) {
     return k;
 }
 
+// sketch::hash::WangHash::inverse (absent third-party source): the steps of the mix above undone from the last to the first.
+// y = x + (x << s) and y = ~x + (x << s) are undone s more low bits per substitution, y = x ^ (x >> s) s more high bits; the
+// multiplications by 21 = 1 + 4 + 16 and 265 = 1 + 8 + 256 by their inverses modulo 2^64.
+uint64_t d2g_wang_hash_inverse(uint64_t k) {
+    uint64_t t;
+    t = k - (k << 31); t = k - (t << 31); k = k - (t << 31);                              // k += k << 31
+    t = k ^ (k >> 28); t = k ^ (t >> 28); k = k ^ (t >> 28);                              // k ^= k >> 28
+    k *= 0xcf3cf3cf3cf3cf3dull;                                                          // k *= 21
+    t = k; for (int i = 0; i < 4; ++i) t = k ^ (t >> 14); k = t;                          // k ^= k >> 14
+    k *= 0xd38ff08b1c03dd39ull;                                                          // k *= 265
+    t = k ^ (k >> 24); t = k ^ (t >> 24); k = k ^ (t >> 24);                              // k ^= k >> 24
+    t = ~k; for (int i = 0; i < 3; ++i) t = ~(k - (t << 21)); k = t;                      // k = ~k + (k << 21)
+    return k;
+}
+
 // enums.cpp:133-139
 uint64_t d2g_seed_mask(uint64_t seedseed) { return seedseed ? d2g_wang_hash(seedseed) : 0; }
 
@@ -66,6 +81,15 @@ uint64_t d2g_oph_xor_const(void) {
 }
 
 size_t d2g_oph_m(size_t S) { return S + (S & 1); }   // oph.h:143-146
+
+// ids(), oph.h:264-271 with decode = DHasher::inverse (oph.h:50-52,81-83); the first S of every m (fastxsketch.cpp:619-620)
+int d2g_oph_kmer_ids(const uint64_t *regs, size_t n, size_t m, size_t S, uint64_t *ids_out) {
+    if (S > m || (n && S && (!regs || !ids_out))) return D2G_ERR_INVALID;
+    const uint64_t c = d2g_oph_xor_const();
+    for (size_t i = 0; i < n; ++i)
+        for (size_t r = 0; r < S; ++r) ids_out[i * S + r] = c ^ d2g_wang_hash_inverse(regs[i * m + r]);
+    return D2G_OK;
+}
 
 // oph.h:240-247
 double d2g_oph_card(const uint64_t *regs, size_t m) {

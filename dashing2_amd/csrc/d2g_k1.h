@@ -51,6 +51,7 @@ struct d2g_sketcher {
     d2g_stream stream;
     d2g_dev<uint8_t> d_packed;                             // grow-only, like the buffers below
     d2g_dev<uint64_t> d_regs;
+    d2g_dev<uint32_t> d_counts;                            // d2g_sketcher_run_counts: one u32 per register
     d2g_dev<uint8_t> d_arena; d2g_pinned<uint8_t> h_arena; // the launch tables: device copy and its pinned source
     d2g_pinned<uint8_t> h_stage;                           // pinned staging of the packed stream
     d2g_k3_state *k3 = nullptr;                            // --multiset work buffers (d2g_k3_bmh.hip)

@@ -65,6 +65,53 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
     }
 }
 
+// K1b: how often the k-mer behind each FINAL register occurred (LazyOnePermSetSketch::update's counts_, oph.h:207-209, read by
+// idcounts(), oph.h:272-277).  A second walk in K1's decomposition, in a launch of its own after K1: a register is final only once
+// every workgroup of its genome has merged.  The workgroup keeps its genome's m registers (8 m bytes) and m u32 counters (4 m) in
+// LDS: 12 m bytes.  A k-mer counts when its id EQUALS the register it maps to -- an empty register (~0) is compared like any
+// other value, so a k-mer whose id is 2^64-1 counts (`cref += (rref == id)`, oph.h:209).
+struct K1CountArgs {
+    KmerArgs km;
+    const uint64_t *regs;          // [n][m], final
+    uint32_t *counts_out;          // [n][m], pre-filled with 0
+    uint64_t xormask;
+    uint64_t ophxor;
+    uint32_t m;
+};
+
+template <bool POW2, bool USE_LDS>
+__global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
+    const int tid = threadIdx.x;
+    const uint32_t g = a.km.blk_genome[blockIdx.x];
+    const uint32_t m = a.m;
+    const uint64_t *greg = a.regs + (size_t)g * m;
+    uint32_t *gcnt = a.counts_out + (size_t)g * m;
+    uint32_t *lcnt = reinterpret_cast<uint32_t *>(lreg + m);
+
+    if (USE_LDS) {
+        for (uint32_t i = tid; i < m; i += K1_THREADS) { lreg[i] = greg[i]; lcnt[i] = 0; }
+        __syncthreads();
+    }
+    const uint64_t xormask = a.xormask, ophxor = a.ophxor;
+    d2g_for_each_kmer(a.km, [&](uint64_t x) {
+        const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
+        const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
+        if (USE_LDS) {
+            if (lreg[idx] == id) (void)atomicAdd(&lcnt[idx], 1u);     // result unused: a non-returning ds_add_u32
+        } else {
+            if (greg[idx] == id) (void)atomicAdd(&gcnt[idx], 1u);
+        }
+    });
+    if (USE_LDS) {
+        __syncthreads();
+        for (uint32_t i = tid; i < m; i += K1_THREADS) {
+            const uint32_t c = lcnt[i];
+            if (c) (void)atomicAdd(&gcnt[i], c);
+        }
+    }
+}
+
 template <class T>
 static int upload(d2g_ctx *ctx, const std::vector<T> &h, d2g_dev<T> &d) {
     if (int rc = d.alloc(ctx, std::max<size_t>(h.size(), 1), "oph plan alloc")) return rc;
@@ -131,6 +178,39 @@ int launch_k1(d2g_ctx *ctx, K1Args a, size_t nblk, size_t m, hipStream_t s) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), use_lds ? lds : 0, s, a);
     tm.stop();
     D2G_HIP(ctx, hipGetLastError());
+    return D2G_OK;
+}
+
+// registers + counters in LDS while 12 m bytes fit the 128 KB K1 asks for at most (m <= 10 922); beyond, against HBM/L2
+int launch_k1_count(d2g_ctx *ctx, K1CountArgs a, size_t nblk, size_t m, hipStream_t s) {
+    const bool pow2 = (m & (m - 1)) == 0;
+    const size_t lds = m * (sizeof(uint64_t) + sizeof(uint32_t));
+    const bool use_lds = lds <= 128 * 1024;
+    auto kern = pow2 ? (use_lds ? k1_oph_count_kernel<true, true> : k1_oph_count_kernel<true, false>)
+                     : (use_lds ? k1_oph_count_kernel<false, true> : k1_oph_count_kernel<false, false>);
+    if (use_lds && lds > 48 * 1024)
+        D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    d2g_timer tm(ctx, &ctx->ev_k1count, s);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), use_lds ? lds : 0, s, a);
+    tm.stop();
+    D2G_HIP(ctx, hipGetLastError());
+    return D2G_OK;
+}
+
+// the counting forms with host outputs return uint32 counts without the reference's wrap (idcounts() copies doubles into
+// uint32, oph.h:272-277): a genome that could reach 2^32 is refused, before anything is staged or launched.  Tables that the
+// plan builder will reject (null, not monotone, a run shorter than k) are left to it.
+int check_count_range(d2g_ctx *ctx, const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k) {
+    if (!genome_run_off || (nrun && !run_len) || k < 1) return D2G_OK;
+    for (size_t g = 0; g < n; ++g) {
+        uint64_t nk = 0;
+        for (uint64_t r = genome_run_off[g]; r < genome_run_off[g + 1] && r < nrun; ++r)
+            if (run_len[r] >= (uint32_t)k) nk += (uint64_t)run_len[r] - k + 1;
+        if (nk >= (1ull << 32)) {
+            ctx->last_error = "k-mer counts of a genome with 2^32 k-mers or more (the reference's uint32 counts wrap there)";
+            return D2G_ERR_UNSUPPORTED;
+        }
+    }
     return D2G_OK;
 }
 
@@ -222,6 +302,62 @@ int d2g_oph_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, con
     return rc;
 }
 
+int d2g_oph_count_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
+                      size_t sketchsize, const uint64_t *regs_dev, uint32_t *counts_out_dev, void *stream) {
+    if (!ctx || !plan) return D2G_ERR_INVALID;
+    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
+    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    D2G_CHECK(ctx, regs_dev != nullptr && counts_out_dev != nullptr, "null regs or counts_out");
+    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
+    D2G_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = as_stream(stream);
+    const size_t m = d2g_oph_m(sketchsize);
+    // counts_ start at 0: oph.h:148,234
+    D2G_HIP(ctx, hipMemsetAsync(counts_out_dev, 0, plan->n * m * sizeof(uint32_t), s));
+    if (plan->nblk == 0) return D2G_OK;
+    D2G_CHECK(ctx, packed_dev != nullptr, "null packed stream");
+    K1CountArgs a;
+    a.km = d2g_plan_args(plan, packed_dev, canon);
+    a.regs = regs_dev; a.counts_out = counts_out_dev; a.xormask = xormask; a.ophxor = d2g_oph_xor_const();
+    a.m = (uint32_t)m;
+    return launch_k1_count(ctx, a, plan->nblk, m, s);
+}
+
+int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                          const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
+                          int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
+    if (!ctx) return D2G_ERR_INVALID;
+    D2G_CHECK(ctx, (regs_out != nullptr && counts_out != nullptr) || n == 0, "null regs_out or counts_out");
+    int rc = check_count_range(ctx, run_len, nrun, genome_run_off, n, k);
+    if (rc) return rc;
+    d2g_oph_plan *plan = nullptr;
+    if ((rc = d2g_oph_plan_create(ctx, run_start, run_len, nrun, genome_run_off, n, k, &plan))) return rc;
+    const std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> plan_owner(plan, d2g_oph_plan_destroy);
+    if (nrun) {
+        uint64_t maxend = 0;
+        for (size_t r = 0; r < nrun; ++r) maxend = std::max<uint64_t>(maxend, run_start[r] + run_len[r]);
+        if (packed_bytes < (maxend + 3) / 4 + 64) {
+            ctx->last_error = "packed stream lacks the 64-byte tail pad";
+            return D2G_ERR_INVALID;
+        }
+    }
+    const size_t m = d2g_oph_m(sketchsize);
+    d2g_dev<uint8_t> d_packed;
+    d2g_dev<uint64_t> d_regs;
+    d2g_dev<uint32_t> d_counts;
+    if ((rc = d_packed.alloc(ctx, std::max<size_t>(packed_bytes, 4), "oph sketch alloc")) ||
+        (rc = d_regs.alloc(ctx, std::max<size_t>(n * m, 1), "oph sketch alloc")) ||
+        (rc = d_counts.alloc(ctx, std::max<size_t>(n * m, 1), "oph sketch alloc"))) return rc;
+    if (packed_bytes) D2G_HIP(ctx, hipMemcpy(d_packed, packed, packed_bytes, hipMemcpyHostToDevice));
+    if ((rc = d2g_oph_sketch_dev(ctx, plan, d_packed, canon, xormask, sketchsize, d_regs, nullptr)) ||
+        (rc = d2g_oph_count_dev(ctx, plan, d_packed, canon, xormask, sketchsize, d_regs, d_counts, nullptr))) return rc;
+    if (n) {
+        D2G_HIP(ctx, hipMemcpy(regs_out, d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        D2G_HIP(ctx, hipMemcpy(counts_out, d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    return D2G_OK;
+}
+
 void d2g_sketcher_destroy(d2g_sketcher *sk) {
     if (!sk) return;
     (void)hipSetDevice(sk->ctx->device);
@@ -264,6 +400,40 @@ int d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_byte
         if (int rc = launch_k1(ctx, a, nblk, m, s)) return rc;
     }
     if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipStreamSynchronize(s));
+    return D2G_OK;
+}
+
+int d2g_sketcher_run_counts(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                            const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
+                            uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
+    if (!sk) return D2G_ERR_INVALID;
+    d2g_ctx *ctx = sk->ctx;
+    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    D2G_CHECK(ctx, (regs_out != nullptr && counts_out != nullptr) || n == 0, "null regs_out or counts_out");
+    if (int rc = check_count_range(ctx, run_len, nrun, genome_run_off, n, k)) return rc;      // before the stage touches the device stream
+    K1Args a;
+    size_t nblk = 0;
+    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon,
+                                    &a.km, &nblk, nullptr)) return rc;
+    const size_t m = d2g_oph_m(sketchsize), nm = std::max<size_t>(n * m, 1);
+    if (int rc = sk->d_regs.grow(ctx, nm, 4096)) return rc;
+    if (int rc = sk->d_counts.grow(ctx, nm, 4096)) return rc;
+    hipStream_t s = sk->stream;
+    D2G_HIP(ctx, hipMemsetAsync(sk->d_regs, 0xFF, nm * sizeof(uint64_t), s));
+    D2G_HIP(ctx, hipMemsetAsync(sk->d_counts, 0, nm * sizeof(uint32_t), s));
+    if (nblk) {
+        a.regs_out = sk->d_regs; a.xormask = xormask; a.ophxor = d2g_oph_xor_const();
+        a.m = (uint32_t)m;
+        if (int rc = launch_k1(ctx, a, nblk, m, s)) return rc;
+        K1CountArgs c;
+        c.km = a.km; c.regs = sk->d_regs; c.counts_out = sk->d_counts; c.xormask = xormask; c.ophxor = a.ophxor; c.m = a.m;
+        if (int rc = launch_k1_count(ctx, c, nblk, m, s)) return rc;
+    }
+    if (n) {
+        D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    }
     D2G_HIP(ctx, hipStreamSynchronize(s));
     return D2G_OK;
 }
@@ -335,4 +505,8 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_by
     return D2G_OK;
 }
 
-void d2g_warm_k1() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_kernel<true, true>)); }
+void d2g_warm_k1() {
+    hipFuncAttributes a;
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_kernel<true, true>));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_count_kernel<true, true>));
+}

@@ -224,6 +224,7 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     if (!c || !which) return D2G_ERR_INVALID;
     d2g_evlog *e = nullptr, *e2 = nullptr;                   // e2: a second log summed under the same name
     if (!std::strcmp(which, "k1")) e = &c->ev_k1;
+    else if (!std::strcmp(which, "k1count")) e = &c->ev_k1count;
     else if (!std::strcmp(which, "k2")) e = &c->ev_k2;
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;
     else if (!std::strcmp(which, "k3")) e = &c->ev_k3;

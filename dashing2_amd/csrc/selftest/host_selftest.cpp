@@ -129,6 +129,19 @@ int main() {
         REQUIRE(d2g_dedup_clusters(nullptr, 0, indptr.data(), nullptr, &nc) == D2G_OK && nc == 0 && indptr[0] == 0);
     }
     REQUIRE(d2g_wang_hash(133348) != 0 && d2g_seed_mask(0) == 0 && d2g_seed_mask(5) != 0);
+    // ---- the k-mers behind registers: exactly-sized arrays, odd S (the last of every m is not read into the output)
+    for (uint64_t x : {uint64_t(0), ~uint64_t(0), uint64_t(133348), rng(), rng()})
+        REQUIRE(d2g_wang_hash_inverse(d2g_wang_hash(x)) == x && d2g_wang_hash(d2g_wang_hash_inverse(x)) == x);
+    for (size_t S : {1, 2, 5, 64}) {
+        const size_t m = d2g_oph_m(S), n = 3;
+        std::vector<uint64_t> regs(n * m), ids(n * S);
+        for (auto &x : regs) x = (rng() % 3 == 0) ? ~0ull : rng();
+        REQUIRE(d2g_oph_kmer_ids(regs.data(), n, m, S, ids.data()) == D2G_OK);
+        for (size_t i = 0; i < n; ++i)
+            for (size_t r = 0; r < S; ++r) REQUIRE(d2g_wang_hash(ids[i * S + r] ^ d2g_oph_xor_const()) == regs[i * m + r]);
+        REQUIRE(d2g_oph_kmer_ids(regs.data(), n, m, m + 1, ids.data()) == D2G_ERR_INVALID);
+        REQUIRE(d2g_oph_kmer_ids(nullptr, 0, m, S, nullptr) == D2G_OK);
+    }
     std::printf("host selftest OK\n");
     return 0;
 }

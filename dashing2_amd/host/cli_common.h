@@ -28,6 +28,9 @@ struct Result {                              // SketchingResult, src/fastxsketch
     double *sigs() { return signatures.data(); }
     const double *sigs() const { return signatures.data(); }
     size_t nsigs() const { return signatures.size(); }
+    std::vector<uint64_t> kmers;             // kmers_ [N][S]: the masked k-mer behind every register (-s / -N with -o)
+    std::vector<float> kmercounts;           // kmercounts_ [N][S] (-N with -o): floats, src/fastxsketch.h:45
+    std::vector<std::string> kmercountfiles; // kmercountfiles_ [N] (-N): named in <out>.names.txt, never written for OPH
     size_t nq = 0;
 };
 

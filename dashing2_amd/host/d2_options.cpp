@@ -45,6 +45,9 @@ void sketch_usage() {
                          "  --cmpout/--distout/--cmp-outfile out   --phylip   --binary-output   --asymmetric-all-pairs\n"
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
                          "  --multiset/--bagminhash/-B [-m/--count-threshold c]   --parse-by-seq (one sketch per record of ONE file)\n"
+                         "  -s/--save-kmers        with -o out: out.kmer64 (24-byte header, then per input the masked k-mer behind each of its S\n"
+                         "                         registers) and out.kmer64.names.txt; set sketches (OPH) only, not with --parse-by-seq\n"
+                         "  -N/--save-kmercounts   -s, and out.kmercounts.f64: how often each of those k-mers occurred in its input (float32)\n"
                          "  --distance/--mash-distance --containment --symmetric-containment --intersection --union-size\n"
                          "  --fastcmp/--regsize/--regbytes <8|4|2|1>   compare registers truncated to that many bytes (8: as sketched); logarithmic\n"
                          "                         (setsketch) truncation unless --bbit-sigs selects b-bit signatures\n"
@@ -140,6 +143,7 @@ int parse_options(int argc, char **argv, Options &o) {
         {"gpu-stats", required_argument, 0, OPT_GPUSTATS},
         {"fastcmp", required_argument, 0, OPT_FASTCMP}, {"regsize", required_argument, 0, OPT_FASTCMP}, {"regbytes", required_argument, 0, OPT_FASTCMP},
         {"bbit-sigs", no_argument, 0, OPT_BBITSIGS},
+        {"save-kmers", no_argument, 0, 's'}, {"save-kmercounts", no_argument, 0, 'N'},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
     std::vector<struct option> all(longopts, longopts + sizeof(longopts) / sizeof(longopts[0]) - 1);
@@ -171,6 +175,8 @@ int parse_options(int argc, char **argv, Options &o) {
             case 'o': o.outfile = optarg; break;
             case 'C': o.canon = false; break;
             case 'W': o.cache = true; break;
+            case 's': o.save_kmers = true; break;                                  // options.h:347
+            case 'N': o.save_kmers = o.save_kmercounts = true; break;              // options.h:346
             case 'Z': o.kmer_result = ONE_PERM; break;
             case 'v': ++o.verbosity; break;
             case 'L': {
@@ -252,6 +258,13 @@ int parse_options(int argc, char **argv, Options &o) {
     if (o.sspace == SPACE_SET && o.count_threshold > 0) {
         std::fprintf(stderr, "dashing2 (MI355X): -m/--count-threshold with set sketches (OPH min-count filtering, oph.h:186-205) "
                              "is outside this build's hot-path scope; it is supported with --multiset.\n");
+        return 1 + 1;
+    }
+    if (o.save_kmers && !o.presketched && (o.sspace != SPACE_SET || o.parse_by_seq)) {     // with --presketched nothing is sketched: ignored
+        std::fprintf(stderr, "dashing2 (MI355X): %s together with %s is outside the hot-path scope of this build "
+                             "(the k-mers and counts behind the registers are saved for One-Permutation set sketches of whole inputs).\n",
+                     o.save_kmercounts ? "-N/--save-kmercounts" : "-s/--save-kmers",
+                     o.sspace == SPACE_MULTISET ? "--multiset" : o.sspace != SPACE_SET ? "a sketch space other than the set space" : "--parse-by-seq");
         return 1 + 1;
     }
     if (o.k > 32) {

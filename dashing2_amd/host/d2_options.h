@@ -19,6 +19,8 @@ struct Options {
     bool is_cmp = false;
     int k = -1, w = -1, nt = -1;
     bool canon = true, cache = false, presketched = false;
+    bool save_kmers = false;              // -s/--save-kmers (options.h:347): <out>.kmer64 + <out>.kmer64.names.txt, the masked k-mer behind every OPH register
+    bool save_kmercounts = false;         // -N/--save-kmercounts (options.h:346; sets save_kmers too): <out>.kmercounts.f64, how often that k-mer occurred
     bool parse_by_seq = false;            // --parse-by-seq (options.h:378): one sketch per FASTX record of ONE input file
     size_t sketchsize = 1024;
     uint64_t seedseed = 0;

@@ -57,6 +57,35 @@ void write_cached(const std::string &path, const double *sig, double card, size_
     std::fclose(fp);
 }
 
+// does this job save the k-mers (and counts) behind the registers?  Only next to a stacked output file (fastxsketch.cpp:236-244);
+// without one the reference keeps them in memory and drops them
+bool saves_kmers(const Options &o) { return o.save_kmers && !o.outfile.empty() && o.outfile != "-" && o.outfile != "/dev/stdout"; }
+
+// <out>.kmer64: [u32 dtype = DNA | canon << 8][u32 S][u32 k][u32 w][u64 seedseed], then N x S u64 (fastxsketch.cpp:245-259,619-620);
+// <out>.kmer64.names.txt: the input lines (:260-263); <out>.kmercounts.f64: N x S float32 (sketch_core.cpp:162-171)
+void write_kmer_files(const Result &res, const Options &o) {
+    if (res.kmers.empty() && res.kmercounts.empty()) return;
+    std::FILE *fp;
+    if (!res.kmers.empty()) {
+        const std::string kf = o.outfile + ".kmer64", nf = kf + ".names.txt";
+        if (!(fp = std::fopen(kf.c_str(), "wb"))) die("Failed to open " + kf + " for writing.");
+        const uint32_t hdr[4] = {uint32_t(0) | (uint32_t(o.canon) << 8), uint32_t(o.sketchsize), uint32_t(o.k), uint32_t(o.w < 0 ? o.k : o.w)};
+        const uint64_t seed = o.seedseed;
+        if (std::fwrite(hdr, 4, 4, fp) != 4 || std::fwrite(&seed, 8, 1, fp) != 1 ||
+            std::fwrite(res.kmers.data(), 8, res.kmers.size(), fp) != res.kmers.size()) die("Failed to write " + kf);
+        std::fclose(fp);
+        if (!(fp = std::fopen(nf.c_str(), "wb"))) die("Failed to open " + nf + " for writing.");
+        for (const auto &n : res.names) { std::fwrite(n.data(), 1, n.size(), fp); std::fputc('\n', fp); }
+        std::fclose(fp);
+    }
+    if (!res.kmercounts.empty()) {
+        const std::string cf = o.outfile + ".kmercounts.f64";
+        if (!(fp = std::fopen(cf.c_str(), "wb"))) return;                 // the reference fails silently here (sketch_core.cpp:168-170)
+        if (std::fwrite(res.kmercounts.data(), sizeof(float), res.kmercounts.size(), fp) != res.kmercounts.size()) die("Failed to write " + cf);
+        std::fclose(fp);
+    }
+}
+
 // stacked output: [u64 N][u64 S][f64 card x N][f64 x N*S]   (sketch_core.cpp:130-140, fastxsketch.cpp:236-240)
 void write_stacked(const Result &res, const Options &o) {
     const size_t N = res.names.size(), S = o.sketchsize;
@@ -76,15 +105,18 @@ void write_stacked(const Result &res, const Options &o) {
     for (size_t i = 0; i < N; ++i) {
         std::fwrite(res.names[i].data(), 1, res.names[i].size(), fp);
         std::fprintf(fp, "\t%0.24g", res.cardinalities[i]);
+        if (!res.kmercountfiles.empty()) { std::fputc('\t', fp); std::fwrite(res.kmercountfiles[i].data(), 1, res.kmercountfiles[i].size(), fp); }   // sketch_core.cpp:156-157
         std::fputc('\n', fp);
     }
     std::fclose(fp);
+    write_kmer_files(res, o);
 }
 
 // x87 finalisation (getcard / data, src/oph.h:240-263) and cache files leave the device threads through a small queue
-struct Fin { size_t g; std::vector<uint64_t> regs; std::vector<double> sigs, cards; };
+struct Fin { size_t g; std::vector<uint64_t> regs; std::vector<double> sigs, cards; std::vector<uint32_t> counts; };   // counts: [n][m] with -N
 
-constexpr const char *SKETCH_KERNELS[3] = {"k0", "k1", "k3"};
+constexpr int NSK = 4;
+constexpr const char *SKETCH_KERNELS[NSK] = {"k0", "k1", "k3", "k1count"};   // k1count: reported only by jobs that count (-N with -o)
 struct KAcc { int launches = 0; double total_ms = 0; };
 
 // What the device threads of one sketch job share.  `const` members and what they point to are read-only while the threads run.
@@ -95,12 +127,13 @@ struct DeviceSide {
     IngestPipeline &pipe;
     BoundedQueue<Fin> &finq;
     const std::vector<int> devs;
+    const bool count_kmers;                               // -N with -o: K1 is followed by its count pass
     d2g_ctx *const first_ctx;                             // the context of thread 0; every other thread makes its own
     std::mutex mu;                                        // guards everything below: each thread adds its sums once, as it ends
     double t_gpu = 0;
     uint64_t total_bases = 0;
     size_t n_dev_groups = 0, n_host_groups = 0;
-    std::vector<std::array<KAcc, 3>> kacc;                // per device: k0, k1, k3
+    std::vector<std::array<KAcc, NSK>> kacc;              // per device: k0, k1, k3, k1count
     std::vector<size_t> groups_of;                        // per device
 
     // sketches one group: the raw bytes parsed on the device, or the stream the host parser packed -> Fin; true: parsed on the device
@@ -134,8 +167,14 @@ struct DeviceSide {
                                             double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh");
         } else {
             f.regs.resize(n * d2g_oph_m(S));
-            check(ctx, d2g_sketcher_run(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data()),
-                  "d2g_sketcher_run");
+            if (count_kmers) {                                          // fastxsketch.cpp:590-591: idcounts()
+                f.counts.resize(n * d2g_oph_m(S));
+                check(ctx, d2g_sketcher_run_counts(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data(),
+                                                   f.counts.data()), "d2g_sketcher_run_counts");
+            } else {
+                check(ctx, d2g_sketcher_run(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data()),
+                      "d2g_sketcher_run");
+            }
         }
         return on_device;
     }
@@ -153,16 +192,16 @@ struct DeviceSide {
         for (IngestGroup r; pipe.next(r);) {
             if (r.failed()) continue;                                       // error recorded by the pipeline; drain the queue
             const double t1 = now();
-            Fin f{r.g, {}, {}, {}};
+            Fin f{r.g, {}, {}, {}, {}};
             uint64_t nb = 0;
             ++(sketch_group(ctx, sk, r, f, nb) ? ndevg : nhostg);
             gpu += now() - t1; bases += nb;
             finq.push(std::move(f));
             pipe.release(r);
         }
-        std::array<KAcc, 3> mine;
+        std::array<KAcc, NSK> mine;
         if (g_stats.on)
-            for (int x = 0; x < 3; ++x) {
+            for (int x = 0; x < NSK; ++x) {
                 int n = 0; float avg = 0, last = 0;
                 if (d2g_kernel_ms(ctx, SKETCH_KERNELS[x], 1, &n, &avg, &last) == D2G_OK) { mine[x].launches = n; mine[x].total_ms = double(avg) * n; }
             }
@@ -170,7 +209,7 @@ struct DeviceSide {
         std::lock_guard<std::mutex> lk(mu);
         t_gpu += gpu; total_bases += bases; n_dev_groups += ndevg; n_host_groups += nhostg;
         groups_of[di] += ndevg + nhostg;
-        for (int x = 0; x < 3; ++x) { kacc[di][x].launches += mine[x].launches; kacc[di][x].total_ms += mine[x].total_ms; }
+        for (int x = 0; x < NSK; ++x) { kacc[di][x].launches += mine[x].launches; kacc[di][x].total_ms += mine[x].total_ms; }
     }
 };
 
@@ -197,11 +236,21 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
     res.destination_files.resize(N);
     res.cardinalities.assign(N, -1.);
     res.signatures.assign(N * S, 0.);
+    const bool want_ids = saves_kmers(o), want_counts = want_ids && o.save_kmercounts;
+    if (o.save_kmercounts) res.kmercountfiles.resize(N);                // fastxsketch.cpp:280-282
+    if (want_ids) res.kmers.assign(N * S, 0);                           // :293-298
+    if (want_counts) res.kmercounts.assign(N * S, 0.f);
     std::vector<size_t> todo;
     std::vector<std::string> lines;                                     // o.paths[todo[t]]
     for (size_t i = 0; i < N; ++i) {
         res.destination_files[i] = makedest(o, o.paths[i]);
-        if (o.cache && isfile(res.destination_files[i]) &&
+        if (o.save_kmercounts) {                                        // fastxsketch.cpp:314,317,326: named, never written for OPH
+            const std::string &d = res.destination_files[i];
+            res.kmercountfiles[i] = d.substr(0, d.find_last_of('.')) + ".kmercounts.f64";
+        }
+        // with -s / -N the reference's cache test also wants per-input k-mer files (fastxsketch.cpp:327-331), which its OPH branch
+        // never writes: it always sketches again.  So does this build; the caches are still written.
+        if (o.cache && !o.save_kmers && isfile(res.destination_files[i]) &&
             load_cached(res.destination_files[i], &res.signatures[i * S], &res.cardinalities[i], S))
             continue;                                                   // fastxsketch.cpp:327-373
         todo.push_back(i);
@@ -224,6 +273,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
     BoundedQueue<Fin> finq(groups.size() + 1);                          // never full: the device threads do not wait for the finisher
     double t_fin = 0;                                                   // written by the finisher only, read after its join
     std::thread finisher([&] {
+        std::vector<uint64_t> ids;
         for (Fin f; finq.pop(f);) {
             const double t0 = now();
             const size_t b = groups[f.g].first, e = groups[f.g].second, n = e - b;
@@ -231,8 +281,14 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
                 f.sigs.resize(n * S); f.cards.resize(n);
                 check(nullptr, d2g_oph_finalize(f.regs.data(), n, m, S, f.sigs.data(), f.cards.data(), 2), "d2g_oph_finalize");
             }
+            if (want_ids) {                                             // ids(): oph.h:264-271
+                ids.resize(n * S);
+                check(nullptr, d2g_oph_kmer_ids(f.regs.data(), n, m, S, ids.data()), "d2g_oph_kmer_ids");
+            }
             for (size_t t = b; t < e; ++t) {                            // results land by input index
                 const size_t i = todo[t];
+                if (want_ids) std::memcpy(&res.kmers[i * S], &ids[(t - b) * S], S * sizeof(uint64_t));         // fastxsketch.cpp:619-620
+                if (want_counts) for (size_t r = 0; r < S; ++r) res.kmercounts[i * S + r] = float(f.counts[(t - b) * m + r]);   // :621-622
                 std::memcpy(&res.signatures[i * S], &f.sigs[(t - b) * S], S * sizeof(double));   // fastxsketch.cpp:610
                 res.cardinalities[i] = f.cards[t - b];
                 if (o.cache) write_cached(res.destination_files[i], &f.sigs[(t - b) * S], f.cards[t - b], S);
@@ -248,7 +304,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
     int ndev = groups.size() > 1 ? 2 : 1;
     if (const char *e = std::getenv("D2G_DEVICE_THREADS")) { const int v = std::atoi(e); if (v >= 1 && v <= 8) ndev = v; }
     const size_t nthreads_dev = std::max<size_t>(1, std::min<size_t>(size_t(ndev) * devs.size(), std::max<size_t>(groups.size(), 1)));
-    DeviceSide ds{o, todo, plan, *pipe, finq, devs, ctx, {}, 0, 0, 0, 0, std::vector<std::array<KAcc, 3>>(devs.size()), std::vector<size_t>(devs.size(), 0)};
+    DeviceSide ds{o, todo, plan, *pipe, finq, devs, want_counts, ctx, {}, 0, 0, 0, 0, std::vector<std::array<KAcc, NSK>>(devs.size()), std::vector<size_t>(devs.size(), 0)};
     std::vector<std::thread> more;
     const double t_dev0 = now();
     for (size_t t = 1; t < nthreads_dev; ++t) more.emplace_back([&ds, t, ndev] { ds.run(nullptr, t / size_t(ndev)); });
@@ -278,7 +334,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
         for (size_t d = 0; d < devs.size(); ++d) {
             Json e = device_json(devs[d]);
             e.integer("groups", ds.groups_of[d]);
-            for (int x = 0; x < 3; ++x) e.nest(SKETCH_KERNELS[x], Json::object().integer("launches", ds.kacc[d][x].launches).num("total_ms", ds.kacc[d][x].total_ms));
+            for (int x = 0; x < (want_counts ? NSK : NSK - 1); ++x) e.nest(SKETCH_KERNELS[x], Json::object().integer("launches", ds.kacc[d][x].launches).num("total_ms", ds.kacc[d][x].total_ms));
             dj.push(e);
         }
         const bool multiset = o.sspace == SPACE_MULTISET;

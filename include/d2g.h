@@ -95,7 +95,7 @@ int         d2g_device_name(int device, char *buf, size_t cap);
 int         d2g_memcpy_h2d(d2g_ctx *ctx, void *dst_dev, const void *src_host, size_t nbytes, void *stream);
 int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, size_t nbytes, void *stream);
 /* Per-launch HIP-event timing of the dominant kernels.  With timing enabled every launch of
- * the K1 kernel ("k1"), the K0 ingest chain ("k0"), the K3 chain ("k3"), the K2 pair kernel ("k2") and the K2 prepare chain ("k2prep") is
+ * the K1 kernel ("k1"), its count pass ("k1count", also under D2G_TIME_K1), the K0 ingest chain ("k0"), the K3 chain ("k3"), the K2 pair kernel ("k2") and the K2 prepare chain ("k2prep") is
  * bracketed by events recorded on the launch stream; nothing synchronises until d2g_kernel_ms,
  * which reports the number of logged launches, their average and the last duration (ms) and
  * optionally clears the log. */
@@ -119,8 +119,15 @@ uint64_t d2g_wang_hash(uint64_t x);
 uint64_t d2g_seed_mask(uint64_t seedseed);
 /* DHasher xor constant seed_ ^ 0x533f8c2151b20f97: reference src/oph.h:44-53,59,142 */
 uint64_t d2g_oph_xor_const(void);
+/* sketch::hash::WangHash::inverse: d2g_wang_hash_inverse(d2g_wang_hash(x)) == x for every x */
+uint64_t d2g_wang_hash_inverse(uint64_t x);
 /* LazyOnePermSetSketch ctor: m = S rounded up to even. reference src/oph.h:143-146 */
 size_t   d2g_oph_m(size_t sketchsize);
+/* ids(): the masked k-mer behind every register, DHasher::inverse (reference src/oph.h:50-52,81-83,162-164,264-271):
+ * ids_out[i][r] = d2g_oph_xor_const() ^ d2g_wang_hash_inverse(regs[i][r]) for r < S, the first S of every m (reference
+ * src/fastxsketch.cpp:619-620).  This is maskfn(kmer) = d2g_wang_hash(kmer ^ xormask), which the reference's invmaskfn turns back
+ * into bases.  An empty register (~0) decodes like any other value. */
+int      d2g_oph_kmer_ids(const uint64_t *regs /* [n][m] */, size_t n, size_t m, size_t sketchsize, uint64_t *ids_out /* [n][S] */);
 /* getcard(): reference src/oph.h:240-247 */
 double   d2g_oph_card(const uint64_t *regs, size_t m);
 /* data(): u64 registers -> double signatures. reference src/oph.h:248-263 */
@@ -239,6 +246,22 @@ int  d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *p
                         int canon, uint64_t xormask, size_t sketchsize,
                         uint64_t *regs_out_dev /* [n][m] */, void *stream);
 
+/* K1b: how often the k-mer behind each register occurred -- LazyOnePermSetSketch's counts_ / idcounts() (reference
+ * src/oph.h:207-209,272-277; call site src/fastxsketch.cpp:590-591,621-622).  counts_out[g][r] = number of k-mers of genome g whose
+ * OPH id equals regs[g][r] and maps to register r; defined for ANY regs, not only K1's output (a value no k-mer has counts 0).
+ * An empty register (~0) is compared like any other value: a k-mer whose id is 2^64-1 counts, as in the reference.
+ * Writes every word of [n][m]; launched on `stream` (after the launch that produced regs), does not synchronise. */
+int  d2g_oph_count_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev,
+                       int canon, uint64_t xormask, size_t sketchsize,
+                       const uint64_t *regs_dev /* [n][m] */, uint32_t *counts_out_dev /* [n][m] */, void *stream);
+/* K1, then the count pass over K1's registers: d2g_oph_sketch's inputs and registers, plus the counts.  A genome with 2^32
+ * k-mers or more is D2G_ERR_UNSUPPORTED (the reference's uint32 copy of its counts wraps there; that is not reproduced). */
+int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
+                          const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                          const uint64_t *genome_run_off, size_t n,
+                          int k, int canon, uint64_t xormask, size_t sketchsize,
+                          uint64_t *regs_out /* host [n][m] */, uint32_t *counts_out /* host [n][m] */);
+
 /* persistent form for host ingest pipelines: grow-only device buffers, one pinned-arena upload of
  * the launch tables per call, own stream.  Same arguments and result as d2g_oph_sketch. */
 typedef struct d2g_sketcher d2g_sketcher;
@@ -248,6 +271,12 @@ int  d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_byt
                       const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                       const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
                       size_t sketchsize, uint64_t *regs_out /* host [n][m] */);
+
+/* the same with the counts of d2g_oph_sketch_counts (packed == NULL after d2g_sketcher_ingest_fasta works as for d2g_sketcher_run) */
+int  d2g_sketcher_run_counts(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
+                             const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                             const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                             size_t sketchsize, uint64_t *regs_out /* host [n][m] */, uint32_t *counts_out /* host [n][m] */);
 
 /* ---- K0: FASTA bytes -> packed run stream on the GPU (host ingest pipelines) ------
  * Replaces, for plain FASTA inputs, the host parser + 2-bit packer (d2g_seqpack_*; reference call sites
