@@ -260,7 +260,11 @@ int eng_alloc_buffer(d2g_allpairs *e, int b) {
     e->full[b]->managed = true;                                             // the engine derives the plane stream, chunk by chunk
     e->full[b]->status_words = e->d_meta[b] + e->ng;
     e->full[b]->n_status = (int)nstat;
-    return d2g_bitslice_managed_sparse_alloc(ctx, e->full[b]);      // N >= 8192: buffers of the sparse-tile path (ids, order, tile bitmaps)
+    if (int rc = d2g_bitslice_managed_sparse_alloc(ctx, e->full[b])) return rc;   // N >= 8192: buffers of the sparse-tile path (ids, order, tile bitmaps)
+    // the buffers above were zeroed on the null stream; their first users run on the caller's stream or on the engine's own, which may be
+    // non-blocking streams that nothing orders behind it (buffer 1 is allocated inside the first pipelined call, right in front of its work)
+    D2G_HIP(ctx, hipStreamSynchronize(nullptr));
+    return D2G_OK;
 }
 
 // phase timing: begin/end bracket a phase's enqueue on stream s (no-ops unless enabled)
@@ -328,8 +332,11 @@ int phase_prepare(d2g_allpairs *e, int c, int b, hipStream_t s) {
     const int bm = e->blk(e->rank, c);
     if (!e->w_blk(bm)) return D2G_OK;                                  // more ranks (x chunks) than register groups: nothing here
     D2G_HIP(e->ctx, hipSetDevice(e->ctx->device));
-    if (!e->local[c])
+    if (!e->local[c]) {
         if (int rc = d2g_bitslice_exporter_create(e->ctx, e->N, e->w_blk(bm), &e->local[c])) return rc;
+        // the exporter's workspace was zeroed on the null stream; `s` may be a non-blocking stream, which nothing orders behind that
+        D2G_HIP(e->ctx, hipStreamSynchronize(nullptr));
+    }
     // my groups go straight to their place in the gathered operand, with their meta and this block's status word
     d2g_bitslice_set_export_target(e->local[c], e->d_planes[b] + e->gpos[bm] * e->gw, e->d_meta[b] + e->gpos[bm], e->d_meta[b] + e->ng + bm);
     return d2g_bitslice_prepare_slice(e->ctx, e->local[c], e->recv_chunk(c), s);
@@ -473,6 +480,25 @@ int check_group(d2g_allpairs **es, int n) {
         }
     }
     return D2G_OK;
+}
+
+// The loopback transport moves bytes when a comm group closes, by matching every send with its peer's recv: a call that drives only some
+// of the ranks -- a per-rank entry point on a multi-rank loopback group -- could never find its peers' transfers.  It is refused HERE, before
+// anything is enqueued: no pack into a send buffer another call may be filling, no fill of the announced output, nothing pending in the group.
+int check_loopback_whole(d2g_allpairs *const *es, int n) {
+    const d2g_comm *c = es[0]->comm;
+    if (!c->lg) return D2G_OK;
+    const char *msg = "allpairs: the ranks of a loopback group of d2g_comm_create_all are driven together, each exactly once, through "
+                      "d2g_allpairs_prepare_all / d2g_allpairs_step_all; the per-rank entry points need a communicator whose peers are other threads or processes";
+    std::vector<char> seen(c->lg->members.size(), 0);
+    bool ok = (size_t)n == seen.size();
+    for (int i = 0; ok && i < n; ++i) {
+        const d2g_comm *ci = es[i]->comm;
+        ok = ci->lg == c->lg && ci->rank >= 0 && (size_t)ci->rank < seen.size() && !seen[ci->rank];
+        if (ok) seen[ci->rank] = 1;
+    }
+    if (!ok) for (int i = 0; i < n; ++i) es[i]->ctx->last_error = msg;           // whichever context the caller asks
+    return ok ? D2G_OK : D2G_ERR_INVALID;
 }
 
 }  // namespace
@@ -738,6 +764,7 @@ int d2g_allpairs_sparse_info(d2g_allpairs *e, uint32_t *info4) {
 
 int d2g_allpairs_prepare_all(d2g_allpairs **engs, int n, const uint64_t *const *rows_dev, void *const *streams) {
     if (int rc = check_group(engs, n)) return rc;
+    if (int rc = check_loopback_whole(engs, n)) return rc;
     std::vector<int> bufs(n, 0);
     std::vector<hipStream_t> ss(n);
     for (int i = 0; i < n; ++i) {
@@ -804,6 +831,7 @@ int d2g_allpairs_enqueue_lut_dev(d2g_allpairs *e, const uint64_t *my_rows_dev, c
     if (!e) return D2G_ERR_INVALID;
     d2g_ctx *ctx = e->ctx;
     D2G_CHECK(ctx, lut_dev && out_dev, "allpairs: null lut/output");
+    if (int rc = check_loopback_whole(&e, 1)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t main = as_stream(stream);
     if (!e->ps) {

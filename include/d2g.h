@@ -609,7 +609,15 @@ int  d2g_cmp_dedup(d2g_ctx *ctx, const uint64_t *sig_bits, size_t N, size_t sket
  *   - one process driving several GPUs (the `dashing2 cmp` CLI): d2g_comm_create_all + the `_all` entry
  *     points, which issue each collective phase for all ranks inside one RCCL group.
  * RCCL is loaded at first use (dlopen); contexts that share a device get a loopback transport instead
- * (device copies ordered by events) so that the whole path can be exercised on one GPU. */
+ * (device copies ordered by events; D2G_COMM_LOOPBACK=1 asks for it over distinct devices too) so that the whole
+ * path can be exercised on one GPU.  The ranks of a loopback group are driven together through the `_all` entry
+ * points, each rank exactly once per call: a per-rank entry point
+ * (d2g_allpairs_prepare_dev / _step_*_dev / _enqueue_lut_dev) on such a group returns D2G_ERR_INVALID before it
+ * enqueues anything (it could never meet its peers' transfers), and the group stays usable.
+ * An engine allocates on first use: its operand buffers at create (the second one in the first pipelined call), a
+ * rank's exporter sets in its first prepare.  Each of these zeroes its buffers on the null stream and waits for that
+ * on the host (hipStreamSynchronize(NULL)) before it returns, so that work on a non-blocking stream cannot overtake
+ * the zeroing: the first prepare / first pipelined call of an engine blocks the host briefly, later ones do not. */
 typedef struct d2g_comm d2g_comm;
 #define D2G_COMM_ID_BYTES 128
 int  d2g_comm_unique_id(void *id_out /* D2G_COMM_ID_BYTES */);                       /* ncclGetUniqueId */

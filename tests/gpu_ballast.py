@@ -1,0 +1,12 @@
+"""Ballast for the GPU tests that call the library on a stream that is still busy."""
+
+_ballast = {}
+
+
+def keep_busy(torch):
+    """a millisecond or two of work on torch's current stream, so that what is queued behind it has not begun when the
+    library is called.  ONE tensor serves every caller: streams that are kept busy at the same time race on its contents, which nobody reads"""
+    if "t" not in _ballast:
+        _ballast["t"] = torch.zeros(1 << 25, dtype=torch.int64, device="cuda")
+    for _ in range(8):
+        _ballast["t"].add_(1)

@@ -18,6 +18,7 @@ import pytest
 
 import oph_kmers_ref as R
 import sketch_dev_cases as V
+from gpu_ballast import keep_busy
 
 pytestmark = pytest.mark.gpu
 
@@ -63,18 +64,6 @@ class Out:
 
     def assert_untouched(self):
         assert (self.words() == self.fill).all(), "a refused or empty call wrote to its output"
-
-
-_ballast = {}
-
-
-def keep_busy(torch):
-    """a millisecond or two of work on torch's current stream, so that what is queued behind it has not begun when the
-    library is called"""
-    if "t" not in _ballast:
-        _ballast["t"] = torch.zeros(1 << 25, dtype=torch.int64, device="cuda")
-    for _ in range(8):
-        _ballast["t"].add_(1)
 
 
 def device_bytes(torch, arr):
