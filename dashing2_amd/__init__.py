@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     epilogue_gtlt, epilogue_neq, host_epilogue_ut, operand_layout, sparse_bin_geometry, ut_count, ut_partition,
     regs_truncate, epilogue_trunc_neq, epilogue_trunc_gtlt, host_epilogue_trunc_ut, host_epilogue_trunc_rect,
     knn_finish, KnnOverflow, TIME_KNN, dedup_clusters, TIME_DEDUP, bmh_check_weights, wang_hash_inverse, oph_kmer_ids,
+    KmerFilter, TIME_FILTER,
 )
 
 __all__ = [
@@ -26,4 +27,5 @@ __all__ = [
     "epilogue_gtlt", "epilogue_neq", "host_epilogue_ut", "operand_layout", "sparse_bin_geometry", "ut_count", "ut_partition",
     "regs_truncate", "epilogue_trunc_neq", "epilogue_trunc_gtlt", "host_epilogue_trunc_ut", "host_epilogue_trunc_rect",
     "knn_finish", "KnnOverflow", "TIME_KNN", "dedup_clusters", "TIME_DEDUP", "bmh_check_weights", "wang_hash_inverse", "oph_kmer_ids",
+    "KmerFilter", "TIME_FILTER",
 ]

@@ -20,6 +20,7 @@ BITSLICE_OPS_PER_GROUP_EXTRA = 1
 TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0 = 2, 4, 8, 16, 32          # include/d2g.h D2G_TIME_*
 TIME_KNN = 64
 TIME_DEDUP = 128
+TIME_FILTER = 256
 
 
 class D2GError(RuntimeError):
@@ -105,6 +106,13 @@ SIGNATURES = {
     "d2g_oph_count_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, _vp, _vp, _vp]),
     "d2g_oph_sketch_counts": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp, _vp]),
     "d2g_sketcher_run_counts": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp, _vp]),
+    "d2g_kmer_filter_create_dev": (_int, [_vp, _vp, _vp, _int, _vp, C.POINTER(_vp)]),
+    "d2g_kmer_filter_create": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _int, _int, C.POINTER(_vp)]),
+    "d2g_kmer_filter_destroy": (None, [_vp]),
+    "d2g_kmer_filter_info": (_int, [_vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_sz)]),
+    "d2g_kmer_filter_contains": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "d2g_oph_plan_set_filter": (_int, [_vp, _vp]),
+    "d2g_sketcher_set_filter": (_int, [_vp, _vp]),
     "d2g_sketcher_create": (_int, [_vp, C.POINTER(_vp)]),
     "d2g_sketcher_destroy": (None, [_vp]),
     "d2g_sketcher_run": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp]),
@@ -720,6 +728,21 @@ class Context:
                                               _np_ptr(genome_run_off), genome_run_off.size - 1, k, C.byref(h)))
         return OphPlan(self, h, genome_run_off.size - 1)
 
+    # -- K1f (--filterset: k-mers every sketch skips) ---------------------------
+    def kmer_filter(self, sp: "SeqPack", canon=True):
+        """the k-mers of ALL genomes of `sp` as one device-resident set (host-pointer form; synchronises)"""
+        packed, rs, rl, go = sp.arrays()
+        h = _vp()
+        self._check(lib().d2g_kmer_filter_create(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, sp.k,
+                                                 int(canon), C.byref(h)))
+        return KmerFilter(self, h, sp.k, bool(canon))
+
+    def kmer_filter_dev(self, plan, packed_dev_ptr, canon=True, stream=None):
+        """the same from a plan and a device-resident packed stream; enqueues on `stream`"""
+        h = _vp()
+        self._check(lib().d2g_kmer_filter_create_dev(self._h, plan._h, packed_dev_ptr, int(canon), stream, C.byref(h)))
+        return KmerFilter(self, h, None, bool(canon))
+
     def oph_sketch_dev(self, plan, packed_dev_ptr, S, regs_dev_ptr, canon=True, xormask=0, stream=None):
         self._check(lib().d2g_oph_sketch_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, regs_dev_ptr, stream))
 
@@ -857,6 +880,20 @@ class Sketcher:
         ctx._check(lib().d2g_sketcher_create(ctx._h, C.byref(h)))
         self._h = h
 
+    def set_filter(self, filt):
+        """attach a KmerFilter (None detaches): every run* of this sketcher skips its k-mers.  The sketcher keeps it alive."""
+        self.ctx._check(lib().d2g_sketcher_set_filter(self._h, filt._h if filt is not None else None))
+        self._filter = filt
+
+    def run_distinct(self, sp, canon=True, xormask=0):
+        """-> distinct k-mers per genome, u64 [n] (exact)"""
+        packed, rs, rl, go = sp.arrays()
+        n = go.size - 1
+        nd = np.zeros(n, np.uint64)
+        self.ctx._check(lib().d2g_sketcher_run_distinct(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
+                                                        _np_ptr(go), n, sp.k, int(canon), xormask, _np_ptr(nd)))
+        return nd
+
     def run(self, sp, S, canon=True, xormask=0):
         packed, rs, rl, go = sp.arrays()
         n = go.size - 1
@@ -985,9 +1022,41 @@ class PinnedArray:
     __del__ = close
 
 
+class KmerFilter:
+    """Device-resident set of the raw 2-bit k-mers of a filter input (d2g_kmer_filter)."""
+
+    def __init__(self, ctx, h, k, canon):
+        self.ctx, self._h, self.k, self.canon = ctx, h, k, canon
+
+    def info(self):
+        """-> (k-mer occurrences put in, distinct keys held, bytes of the device table); synchronises"""
+        no, nd, tb = _u64(), _u64(), _sz()
+        self.ctx._check(lib().d2g_kmer_filter_info(self.ctx._h, self._h, C.byref(no), C.byref(nd), C.byref(tb)))
+        return int(no.value), int(nd.value), int(tb.value)
+
+    def contains(self, kmers):
+        """membership of raw 2-bit k-mers (canonical ones for a canon filter) through the device probe the walker uses -> bool [n]"""
+        kmers = np.ascontiguousarray(kmers, np.uint64)
+        out = np.zeros(kmers.size, np.uint8)
+        self.ctx._check(lib().d2g_kmer_filter_contains(self.ctx._h, self._h, _np_ptr(kmers), kmers.size, _np_ptr(out)))
+        return out.astype(bool)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().d2g_kmer_filter_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 class OphPlan:
     def __init__(self, ctx, h, n):
         self.ctx, self._h, self.n = ctx, h, n
+
+    def set_filter(self, filt):
+        """attach a KmerFilter (None detaches): oph_sketch_dev, oph_count_dev and bmh_sketch_dev on this plan skip its k-mers"""
+        self.ctx._check(lib().d2g_oph_plan_set_filter(self._h, filt._h if filt is not None else None))
+        self._filter = filt
 
     @property
     def nkmers(self):

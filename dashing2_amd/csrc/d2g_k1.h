@@ -13,8 +13,25 @@ struct PlanHost {
 int d2g_build_plan_host(d2g_ctx *ctx, const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n,
                         int k, PlanHost &p);
 
+// K1f: the k-mers of a --filterset input as an open-addressing table of raw 2-bit k-mers in device memory (d2g_filter.hip)
+struct d2g_kmer_filter {
+    d2g_ctx *ctx = nullptr;
+    int k = 0, canon = 0;
+    uint64_t noccurrences = 0;                 // k-mers put in, duplicates counted (the reference's data_.size())
+    uint64_t slots = 0;                        // a power of two >= 2 * noccurrences (>= 16)
+    d2g_dev<uint64_t> d_tab;                   // [slots] keys, then [0] the all-ones flag, [1] the distinct keys in the slots
+};
+// the filter a plan or sketcher carries must fit the call: same context, k and canon (nullptr fits everything)
+int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon);
+// table pointer, mask and shift into the walker's arguments (nullptr: no filter); the caller has run d2g_filter_check
+void d2g_filter_args(const d2g_kmer_filter *f, KmerArgs *km);
+// K3 lays its key regions out from the k-mers per genome, which a filter makes data: one walk of the launch plan counts the
+// survivors of every genome (host array [n]); synchronises `s`
+int d2g_filter_survivors(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n, uint64_t *out, hipStream_t s);
+
 struct d2g_oph_plan {
     d2g_ctx *ctx = nullptr;
+    const d2g_kmer_filter *filter = nullptr;   // VIEW (d2g_oph_plan_set_filter)
     int k = 0;
     size_t n = 0, nrun = 0, nblk = 0;
     uint64_t nkmers = 0, nbases = 0;
@@ -38,6 +55,7 @@ inline KmerArgs d2g_plan_args(const d2g_oph_plan *plan, const uint8_t *packed_de
     a.blk_genome = plan->d_blk_genome; a.blk_chunk0 = plan->d_blk_chunk0; a.blk_nchunks = plan->d_blk_nchunks;
     a.blk_run_lo = plan->d_blk_run_lo; a.blk_run_hi = plan->d_blk_run_hi;
     a.k = plan->k; a.canon = canon; a.blk0 = 0;
+    d2g_filter_args(plan->filter, &a);
     return a;
 }
 
@@ -48,6 +66,7 @@ struct d2g_k3_state;
 struct d2g_k0_state;
 struct d2g_sketcher {
     d2g_ctx *ctx = nullptr;
+    const d2g_kmer_filter *filter = nullptr;               // VIEW (d2g_sketcher_set_filter)
     d2g_stream stream;
     d2g_dev<uint8_t> d_packed;                             // grow-only, like the buffers below
     d2g_dev<uint64_t> d_regs;

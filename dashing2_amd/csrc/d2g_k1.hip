@@ -30,7 +30,7 @@ struct K1Args {
     uint32_t m;
 };
 
-template <bool POW2, bool USE_LDS>
+template <bool POW2, bool USE_LDS, bool FILT>
 __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
     const int tid = threadIdx.x;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
         __syncthreads();
     }
     const uint64_t xormask = a.xormask, ophxor = a.ophxor;
-    d2g_for_each_kmer(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
         const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
         // Schismatic<uint32_t>::mod(size_t): argument narrowed to 32 bits (oph.h:184)
         const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
@@ -79,7 +79,7 @@ struct K1CountArgs {
     uint32_t m;
 };
 
-template <bool POW2, bool USE_LDS>
+template <bool POW2, bool USE_LDS, bool FILT>
 __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
     const int tid = threadIdx.x;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a)
         __syncthreads();
     }
     const uint64_t xormask = a.xormask, ophxor = a.ophxor;
-    d2g_for_each_kmer(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
         const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
         const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
         if (USE_LDS) {
@@ -170,8 +170,10 @@ int launch_k1(d2g_ctx *ctx, K1Args a, size_t nblk, size_t m, hipStream_t s) {
     const bool pow2 = (m & (m - 1)) == 0;
     const size_t lds = m * sizeof(uint64_t);
     const bool use_lds = lds <= 128 * 1024;
-    auto kern = pow2 ? (use_lds ? k1_oph_kernel<true, true> : k1_oph_kernel<true, false>)
-                     : (use_lds ? k1_oph_kernel<false, true> : k1_oph_kernel<false, false>);
+    void (*const kerns[8])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
+                                      k1_oph_kernel<false, true, true>,   k1_oph_kernel<true, false, false>, k1_oph_kernel<true, false, true>,
+                                      k1_oph_kernel<true, true, false>,   k1_oph_kernel<true, true, true>};
+    auto kern = kerns[pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
     if (use_lds && lds > 48 * 1024)
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     d2g_timer tm(ctx, &ctx->ev_k1, s);
@@ -186,8 +188,11 @@ int launch_k1_count(d2g_ctx *ctx, K1CountArgs a, size_t nblk, size_t m, hipStrea
     const bool pow2 = (m & (m - 1)) == 0;
     const size_t lds = m * (sizeof(uint64_t) + sizeof(uint32_t));
     const bool use_lds = lds <= 128 * 1024;
-    auto kern = pow2 ? (use_lds ? k1_oph_count_kernel<true, true> : k1_oph_count_kernel<true, false>)
-                     : (use_lds ? k1_oph_count_kernel<false, true> : k1_oph_count_kernel<false, false>);
+    void (*const kerns[8])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
+                                           k1_oph_count_kernel<false, true, false>,  k1_oph_count_kernel<false, true, true>,
+                                           k1_oph_count_kernel<true, false, false>,  k1_oph_count_kernel<true, false, true>,
+                                           k1_oph_count_kernel<true, true, false>,   k1_oph_count_kernel<true, true, true>};
+    auto kern = kerns[pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
     if (use_lds && lds > 48 * 1024)
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     d2g_timer tm(ctx, &ctx->ev_k1count, s);
@@ -253,6 +258,7 @@ int d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pa
     D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
     D2G_CHECK(ctx, regs_out_dev != nullptr, "null regs_out");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
+    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = as_stream(stream);
     const size_t m = d2g_oph_m(sketchsize);
@@ -309,6 +315,7 @@ int d2g_oph_count_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pac
     D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
     D2G_CHECK(ctx, regs_dev != nullptr && counts_out_dev != nullptr, "null regs or counts_out");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
+    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = as_stream(stream);
     const size_t m = d2g_oph_m(sketchsize);
@@ -444,6 +451,7 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_by
                        const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                        KmerArgs *out, size_t *nblk_out, PlanHost *ph_out) {
     d2g_ctx *ctx = sk->ctx;
+    if (int rc = d2g_filter_check(ctx, sk->filter, k, canon)) return rc;   // before the stream, the buffers or an output are touched
     uint64_t ingested_bases = 0;
     const bool use_ingested = packed == nullptr && d2g_k0_ingested(sk, &ingested_bases);
     D2G_CHECK(ctx, nrun == 0 || (run_start && (packed || use_ingested)), "null input");
@@ -501,12 +509,15 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_by
     out->blk_run_lo = reinterpret_cast<const uint32_t *>(sk->d_arena + o_lo);
     out->blk_run_hi = reinterpret_cast<const uint32_t *>(sk->d_arena + o_hi);
     out->k = k; out->canon = canon; out->blk0 = 0;
+    d2g_filter_args(sk->filter, out);
     *nblk_out = nblk;
     return D2G_OK;
 }
 
 void d2g_warm_k1() {
     hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_kernel<true, true>));
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_count_kernel<true, true>));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_kernel<true, true, false>));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_count_kernel<true, true, false>));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k1_oph_kernel<true, true, true>));     // the filtered forms live in this code object too
+    d2g_warm_filter();
 }

@@ -72,6 +72,7 @@ struct K3Args {
 
 __device__ __forceinline__ uint32_t bucket_of(uint64_t key, uint32_t bb) { return bb ? (uint32_t)(key >> (64 - bb)) : 0u; }
 
+template <bool FILT>
 __global__ __launch_bounds__(K1_THREADS) void k3_hist_kernel(K3Args a) {
     __shared__ uint32_t hist[K3_MAXB];
     const int tid = threadIdx.x;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_hist_kernel(K3Args a) {
     for (uint32_t i = tid; i < B; i += K1_THREADS) hist[i] = 0;
     __syncthreads();
     const uint64_t xormask = a.xormask;
-    d2g_for_each_kmer(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);              // maskfn: src/enums.h:136-140
         atomicAdd(&hist[bucket_of(key, bb)], 1u);
     });
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(K3_THREADS) void k3_scan_kernel(K3Args a) {
 // genomes with more than 2^l1bits buckets are split in two levels: here by the top l1bits of the bucket index -- the
 // coarse bucket's region is the union of its buckets' regions, reserved through the cursor of its first bucket -- and
 // then by the remaining bits, per coarse bucket, in k3_refine_kernel (<= 2^(12 - l1bits) fronts per workgroup there).
+template <bool FILT>
 __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     // ONE LDS array: first the workgroup's count per (coarse) bucket, then (after one 64-bit reservation
     // per bucket) the next write position relative to the genome's first key -- a genome holds < 2^32
@@ -151,7 +153,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     }
     __syncthreads();
     uint64_t *keys = (sb ? a.coarse : a.keys) + koff;
-    d2g_for_each_kmer(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);
         const uint32_t slot = atomicAdd(&pos[bucket_of(key, b1)], 1u);
         keys[slot] = key;
@@ -233,6 +235,7 @@ struct K3cArgs {
     uint32_t TB;
 };
 
+template <bool FILT>
 __global__ __launch_bounds__(K1_THREADS) void k3c_hist_kernel(K3cArgs a) {
     __shared__ uint32_t cnt[K3C_MAXB];
     const int tid = threadIdx.x;
@@ -241,7 +244,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_hist_kernel(K3cArgs a) {
     for (int it = 0; it < K1_CPT; ++it) {
         for (uint32_t i = tid; i < B; i += K1_THREADS) cnt[i] = 0;
         __syncthreads();
-        d2g_for_each_kmer_its(a.km, it, it + 1, [&](uint64_t x) { atomicAdd(&cnt[k3c_bucket(x, bb, hb)], 1u); });
+        d2g_for_each_kmer_its<FILT>(a.km, it, it + 1, [&](uint64_t x) { atomicAdd(&cnt[k3c_bucket(x, bb, hb)], 1u); });
         __syncthreads();
         // a tile holds at most 16384 k-mers: the counts fit u16
         uint16_t *dst = a.tile_cnt + ((size_t)blockIdx.x * K1_CPT + it) * K3C_MAXB;
@@ -299,6 +302,7 @@ struct K3cScatterLds {
     uint32_t wsum[K1_THREADS / 64];
 };
 
+template <bool FILT>
 __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char k3c_lds_raw[];
     K3cScatterLds &L = *reinterpret_cast<K3cScatterLds *>(k3c_lds_raw);
@@ -325,7 +329,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
         if (tid == K1_THREADS - 1) L.lbase[K3C_MAXB] = run;
         __syncthreads();
         if (total == 0) continue;                                    // uniform: every thread computed the same total
-        d2g_for_each_kmer_its(a.km, it, it + 1, [&](uint64_t x) {
+        d2g_for_each_kmer_its<FILT>(a.km, it, it + 1, [&](uint64_t x) {
             L.stage[atomicAdd(&L.lcur[k3c_bucket(x, bb, hb)], 1u)] = (uint32_t)x;
         });
         __syncthreads();
@@ -1216,17 +1220,16 @@ struct K3Host {
     std::vector<uint32_t> l2_start;          // [n+1] first entry of genome g in the two arrays above
 };
 
+int k3_layout_buckets(d2g_ctx *ctx, size_t n, K3Host &kh);
+// k-mers and launch-plan blocks per genome from the run table, then the bucket layout those k-mer counts ask for
 int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_off, size_t n, int k, K3Host &kh) {
     const d2g_k3_tuning &t = ctx->k3_tune;
-    kh.gtab.assign(2 * n + 1, 0);
     kh.gk.assign(n, 0);
     kh.gblk.assign(n + 1, 0);
     kh.hb = k > 16 ? (uint32_t)(2 * k - 32) : 0u;
     // the compact path (4-byte stored words, tile-sorted split) halves the chain's HBM traffic but is ~11 % slower end to
     // end (one Wang mix per distinct k-mer moves into the issue-bound main pass): opt-in with D2G_K3_COMPACT=1, k <= 21
     kh.compact = t.compact && kh.hb <= (uint32_t)K3C_MAXBBITS;
-    uint64_t tb = 0;
-    kh.l1bits = t.l1bits; kh.l2_tb0.clear(); kh.l2_bits.clear(); kh.l2_start.assign(n + 1, 0);
     for (size_t g = 0; g < n; ++g) {
         uint64_t nk = 0, chunks = 0;
         for (uint64_t r = genome_run_off[g]; r < genome_run_off[g + 1]; ++r) {
@@ -1234,8 +1237,22 @@ int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_
             nk += rk; chunks += div_up<uint64_t>(rk, K1_CHUNK);
         }
         D2G_CHECK(ctx, nk < (1ull << 32), "--multiset: more than 2^32 k-mers in one input");
-        kh.gk[g] = nk; kh.total += nk;
+        kh.gk[g] = nk;
         kh.gblk[g + 1] = kh.gblk[g] + (uint32_t)div_up<uint64_t>(chunks, K1_BLOCK_CHUNKS);
+    }
+    return k3_layout_buckets(ctx, n, kh);
+}
+// everything that follows from kh.gk: buckets, key offsets, sub-ranges.  Run again by K3Run::run when a k-mer filter is attached,
+// over the k-mers that SURVIVE it -- the chain then lays out, guesses and splits exactly as for an input that never held the others.
+int k3_layout_buckets(d2g_ctx *ctx, size_t n, K3Host &kh) {
+    const d2g_k3_tuning &t = ctx->k3_tune;
+    kh.gtab.assign(2 * n + 1, 0);
+    kh.total = 0; kh.any_split = false;
+    uint64_t tb = 0;
+    kh.l1bits = t.l1bits; kh.l2_tb0.clear(); kh.l2_bits.clear(); kh.l2_start.assign(n + 1, 0);
+    for (size_t g = 0; g < n; ++g) {
+        const uint64_t nk = kh.gk[g];
+        kh.total += nk;
         uint32_t bb;
         if (kh.compact) bb = std::max<uint32_t>(kh.hb, std::min<uint32_t>(K3C_MAXBBITS, ceil_log2((nk + K3C_TARGET - 1) / K3C_TARGET)));
         else bb = std::min<uint32_t>(K3_MAXBBITS, ceil_log2((nk + t.bucket_keys - 1) / t.bucket_keys));
@@ -1371,20 +1388,23 @@ int K3Run::bucket_prepare() {
 int K3Run::bucket(size_t g_lo, size_t g_hi) {
     if (kh.compact) {
         const unsigned nb = (unsigned)nblk;
-        if (nb) hipLaunchKernelGGL(k3c_hist_kernel, dim3(nb), dim3(K1_THREADS), 0, s, kc);
+        const bool filt = km.ftab != nullptr;           // hist and scatter must drop the same k-mers: one switch for both
+        if (nb) hipLaunchKernelGGL(filt ? k3c_hist_kernel<true> : k3c_hist_kernel<false>, dim3(nb), dim3(K1_THREADS), 0, s, kc);
         hipLaunchKernelGGL(k3c_scan_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, kc);
         if (nb) {
-            D2G_HIP(ctx, hipFuncSetAttribute((const void *)k3c_scatter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K3cScatterLds)));
-            hipLaunchKernelGGL(k3c_scatter_kernel, dim3(nb), dim3(K1_THREADS), sizeof(K3cScatterLds), s, kc);
+            const auto scatter = filt ? k3c_scatter_kernel<true> : k3c_scatter_kernel<false>;
+            D2G_HIP(ctx, hipFuncSetAttribute((const void *)scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K3cScatterLds)));
+            hipLaunchKernelGGL(scatter, dim3(nb), dim3(K1_THREADS), sizeof(K3cScatterLds), s, kc);
         }
         return D2G_OK;
     }
     K3Args a = ka;
     const unsigned blk_lo = kh.gblk[g_lo], nb = (g_lo == 0 && g_hi == n) ? (unsigned)nblk : kh.gblk[g_hi] - blk_lo;
     a.km.blk0 = blk_lo; a.g0 = (uint32_t)g_lo;
-    if (nb) hipLaunchKernelGGL(k3_hist_kernel, dim3(nb), dim3(K1_THREADS), 0, s, a);
+    const bool filt = km.ftab != nullptr;               // hist and scatter must drop the same k-mers: one switch for both
+    if (nb) hipLaunchKernelGGL(filt ? k3_hist_kernel<true> : k3_hist_kernel<false>, dim3(nb), dim3(K1_THREADS), 0, s, a);
     hipLaunchKernelGGL(k3_scan_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(K3_THREADS), 0, s, a);
-    if (nb) hipLaunchKernelGGL(k3_scatter_kernel, dim3(nb), dim3(K1_THREADS), 0, s, a);
+    if (nb) hipLaunchKernelGGL(filt ? k3_scatter_kernel<true> : k3_scatter_kernel<false>, dim3(nb), dim3(K1_THREADS), 0, s, a);
     const unsigned l2_lo = kh.l2_start[g_lo], nl = kh.l2_start[g_hi] - l2_lo;
     if (nb && nl) {
         a.l2_tb0 += l2_lo; a.l2_bits += l2_lo;
@@ -1585,6 +1605,12 @@ int K3Run::sketch(const std::vector<size_t> &sub) {
 }
 
 int K3Run::run(K3Mode mode) {
+    if (km.ftab) {
+        // a filtered k-mer is invisible to everything downstream: count the survivors per genome first (one more walk and a host
+        // round trip, paid only by filtered calls) and lay the chain out for them
+        if (int rc = d2g_filter_survivors(ctx, km, nblk, n, kh.gk.data(), s)) return rc;
+        if (int rc = k3_layout_buckets(ctx, n, kh)) return rc;
+    }
     if (int rc = upload_tables()) return rc;
     d2g_timer tm(ctx, &ctx->ev_k3, s);
     const std::vector<size_t> sub = subbatches(mode);
@@ -1656,6 +1682,7 @@ int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pa
     D2G_CHECK(ctx, (sig_out_dev && total_weight_out_dev) || plan->n == 0, "null output");
     D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
+    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->k3) ctx->k3 = new (std::nothrow) d2g_k3_state();
     if (!ctx->k3) return D2G_ERR_NOMEM;
@@ -1914,4 +1941,8 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
 
 }  // extern "C"
 
-void d2g_warm_k3() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k3_scan_kernel)); }
+void d2g_warm_k3() {
+    hipFuncAttributes a;
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&k3_scan_kernel));     // one code object: the filtered walkers come with it
+    d2g_warm_filter();                                                                   // a filtered K3 call counts its survivors first
+}

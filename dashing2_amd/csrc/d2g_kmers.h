@@ -35,7 +35,23 @@ struct KmerArgs {
     int k;
     int canon;
     uint32_t blk0;                 // first launch-plan block of this launch (a launch may cover a sub-range of the plan)
+    // K1f, --filterset (d2g_filter.hip): open-addressing table of RAW (canonical when canon) k-mers; nullptr = no filter.
+    // Read only by the FILT instantiations of the walker below.
+    const uint64_t *ftab;          // [fmask + 1] keys, D2G_FILTER_EMPTY = free slot; [fmask + 1] != 0: the all-ones k-mer is in the set
+    uint32_t fmask;                // slots - 1 (a power of two, >= twice the k-mers put in: the probe always ends)
+    uint32_t fshift;               // 64 - log2(slots)
 };
+
+// the all-ones k-mer (T x 32, forward) is a legal key and the value of a free slot: its membership is a flag behind the table
+constexpr uint64_t D2G_FILTER_EMPTY = ~0ull;
+__device__ __forceinline__ uint32_t d2g_filter_slot(uint64_t x, uint32_t shift) { return (uint32_t)((x * 0x9E3779B97F4A7C15ull) >> shift); }
+// is k-mer x in the table?  v = the key at x's home slot, loaded by the caller (sixteen independent loads in front of sixteen answers)
+__device__ __forceinline__ bool d2g_filter_hit(const KmerArgs &a, uint64_t x, uint64_t v) {
+    if (x == D2G_FILTER_EMPTY) return a.ftab[(size_t)a.fmask + 1] != 0;
+    uint32_t s = d2g_filter_slot(x, a.fshift);
+    while (v != x && v != D2G_FILTER_EMPTY) { s = (s + 1) & a.fmask; v = a.ftab[s]; }
+    return v == x;
+}
 
 // funnel shift: low 32 bits of (hi:lo) >> sh, 0 <= sh < 32
 __device__ __forceinline__ uint32_t fsr(uint32_t hi, uint32_t lo, uint32_t sh) {
@@ -45,7 +61,9 @@ __device__ __forceinline__ uint32_t fsr(uint32_t hi, uint32_t lo, uint32_t sh) {
 // f(x) once per k-mer of the chunks this lane owns in workgroup blockIdx.x; x = canonical
 // (min(fwd, revcomp)) or forward 2-bit k-mer.  A lane owns chunk (it * K1_THREADS + tid).
 // IT0 <= it < IT1: the passes ("tiles" of K1_THREADS chunks = K1_THREADS * K1_CHUNK k-mers) of the workgroup to walk
-template <class F>
+// FILT: f sees only the k-mers that are NOT in a.ftab (the reference's `!opts.fs_->in_set(maskfn(x))`, src/fastxsketch.cpp:387) --
+// a template flag, so that the unfiltered instantiations are the code they were (profiles/filter_resource_usage.txt)
+template <bool FILT = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0, int it1, F &&f) {
     const int tid = threadIdx.x;
     const uint32_t b = blockIdx.x + a.blk0;
@@ -101,6 +119,23 @@ __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0
             const uint32_t W = wi == 0 ? M0 : wi == 1 ? M1 : wi == 2 ? M2 : M3;
             const int ebase = wi * 16;
             if (ebase >= n) break;
+            if constexpr (FILT) {
+                // the sixteen k-mers of the word first, each with the load of its home slot: sixteen random reads in flight
+                // instead of one dependent round trip per k-mer
+                uint64_t xs[16], vs[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const uint64_t cb = (W >> (2 * e)) & 3u;
+                    fwd = ((fwd << 2) | cb) & kmask;
+                    rc = (rc >> 2) | ((3 - cb) << rcshift);
+                    xs[e] = canon ? (fwd < rc ? fwd : rc) : fwd;
+                    vs[e] = ebase + e < n ? a.ftab[d2g_filter_slot(xs[e], a.fshift)] : 0;
+                }
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    if (ebase + e < n && !d2g_filter_hit(a, xs[e], vs[e])) f(xs[e]);
+                continue;
+            }
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const uint64_t cb = (W >> (2 * e)) & 3u;
@@ -112,7 +147,7 @@ __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0
     }
 }
 
-template <class F>
+template <bool FILT = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer(const KmerArgs &a, F &&f) {
-    d2g_for_each_kmer_its(a, 0, K1_CPT, static_cast<F &&>(f));
+    d2g_for_each_kmer_its<FILT>(a, 0, K1_CPT, static_cast<F &&>(f));
 }

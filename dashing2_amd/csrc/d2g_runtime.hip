@@ -216,7 +216,7 @@ int d2g_device_name(int device, char *buf, size_t cap) {
 
 int d2g_set_timing(d2g_ctx *c, int enabled) {
     if (!c) return D2G_ERR_INVALID;
-    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP) : (enabled & ~1);
+    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER) : (enabled & ~1);
     return D2G_OK;
 }
 
@@ -225,6 +225,7 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     d2g_evlog *e = nullptr, *e2 = nullptr;                   // e2: a second log summed under the same name
     if (!std::strcmp(which, "k1")) e = &c->ev_k1;
     else if (!std::strcmp(which, "k1count")) e = &c->ev_k1count;
+    else if (!std::strcmp(which, "filter")) e = &c->ev_filter;
     else if (!std::strcmp(which, "k2")) e = &c->ev_k2;
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;
     else if (!std::strcmp(which, "k3")) e = &c->ev_k3;

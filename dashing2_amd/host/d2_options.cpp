@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -48,6 +48,9 @@ void sketch_usage() {
                          "  -s/--save-kmers        with -o out: out.kmer64 (24-byte header, then per input the masked k-mer behind each of its S\n"
                          "                         registers) and out.kmer64.names.txt; set sketches (OPH) only, not with --parse-by-seq\n"
                          "  -N/--save-kmercounts   -s, and out.kmercounts.f64: how often each of those k-mers occurred in its input (float32)\n"
+                         "  --filterset <paths>    skip every k-mer of these FASTA/FASTQ(.gz) files (several paths: one argument, space-separated) in all\n"
+                         "                         inputs, before anything is sketched or counted: adapters, phiX, rRNA, a host genome.  Same -k and\n"
+                         "                         canonicalisation as the sketch; `<paths>:K` is accepted as the reference accepts it; binary k-mer files not\n"
                          "  --distance/--mash-distance --containment --symmetric-containment --intersection --union-size\n"
                          "  --fastcmp/--regsize/--regbytes <8|4|2|1>   compare registers truncated to that many bytes (8: as sketched); logarithmic\n"
                          "                         (setsketch) truncation unless --bbit-sigs selects b-bit signatures\n"
@@ -110,6 +113,7 @@ std::string Options::to_string() const {    // src/d2.cpp:10-43 (fields that exi
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";%s", "Fastx");
     if (!outprefix.empty()) pos += std::snprintf(buf + pos, sizeof buf - pos, ";outprefix:%s", outprefix.c_str());
     if (canon) pos += std::snprintf(buf + pos, sizeof buf - pos, ";canon");
+    if (filterset_built) pos += std::snprintf(buf + pos, sizeof buf - pos, ";FilterSetSortedHashSet-size=%llu", (unsigned long long)filterset_size);   // d2.cpp:38-40, filterset.h:82
     return std::string(buf, pos);
 }
 
@@ -144,6 +148,7 @@ int parse_options(int argc, char **argv, Options &o) {
         {"fastcmp", required_argument, 0, OPT_FASTCMP}, {"regsize", required_argument, 0, OPT_FASTCMP}, {"regbytes", required_argument, 0, OPT_FASTCMP},
         {"bbit-sigs", no_argument, 0, OPT_BBITSIGS},
         {"save-kmers", no_argument, 0, 's'}, {"save-kmercounts", no_argument, 0, 'N'},
+        {"filterset", required_argument, 0, OPT_FILTERSET},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
     std::vector<struct option> all(longopts, longopts + sizeof(longopts) / sizeof(longopts[0]) - 1);
@@ -225,6 +230,7 @@ int parse_options(int argc, char **argv, Options &o) {
                 o.greedy = true; o.greedy_t = std::strtod(optarg, &eptr);
                 for (; *eptr; ++eptr) if ((*eptr | 32) == 'f') greedy_fasta = true;    // 'e' (exhaustive): the only route here
             } break;
+            case OPT_FILTERSET: o.filterset_arg = optarg; break;                    // options.h:509-511
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
             case OPT_UNSUPPORTED:
@@ -266,6 +272,16 @@ int parse_options(int argc, char **argv, Options &o) {
                      o.save_kmercounts ? "-N/--save-kmercounts" : "-s/--save-kmers",
                      o.sspace == SPACE_MULTISET ? "--multiset" : o.sspace != SPACE_SET ? "a sketch space other than the set space" : "--parse-by-seq");
         return 1 + 1;
+    }
+    if (!o.filterset_arg.empty() && !o.presketched) {         // Dashing2Options::filterset, d2.cpp:45-49; with --presketched nothing is sketched: ignored
+        const size_t i = o.filterset_arg.find_last_of(':');
+        if (i != std::string::npos && (o.filterset_arg[i + 1] & 0xdf) != 'K') {
+            // the reference's binary-k-mer-file arm: for plain files it opens an EMPTY path (d2.cpp:61-63), and it wants pre-masked values
+            std::fprintf(stderr, "dashing2 (MI355X): --filterset %s (a suffix after the last ':' that does not begin with K: a binary k-mer file) "
+                                 "is outside the hot-path scope of this build; give the FASTA/FASTQ file(s) whose k-mers are to be skipped.\n", o.filterset_arg.c_str());
+            return 1 + 1;
+        }
+        o.filterset = o.filterset_arg.substr(0, i);
     }
     if (o.k > 32) {
         std::fprintf(stderr, "dashing2 (MI355X): k = %d > 32 uses the reference's rolling-hash encoder "

@@ -43,6 +43,10 @@ struct Options {
     double min_similarity = -1.;          // cmp --similarity-threshold T (options.h:309): ok = NN_GRAPH_THRESHOLD, every pair at T or beyond
     bool greedy = false;                  // cmp --greedy T[E] (options.h:310-318): ok = DEDUP, greedy clustering in input order; always the exhaustive route (the E suffix is accepted, the LSH route is out of scope)
     double greedy_t = 0.;                 // ... its threshold as parsed (printed in the header); <= 0 clusters at the reference's default of 0.9 (dedup_core.cpp:264)
+    std::string filterset_arg;            // --filterset <arg> as given (options.h:509-511)
+    std::string filterset;                // ... and its sequence path line (d2.cpp:45-49): the k-mers of these FASTX files are skipped by every sketch
+    mutable bool filterset_built = false; // the sketching leg has built the filter (it runs on a const Options) ...
+    mutable uint64_t filterset_size = 0;  // ... of this many k-mer occurrences: FilterSet::data_.size(), printed by to_string()
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -112,6 +112,43 @@ void write_stacked(const Result &res, const Options &o) {
     write_kmer_files(res, o);
 }
 
+// --filterset (Dashing2Options::filterset, src/d2.cpp:45-98; asked per k-mer at src/fastxsketch.cpp:387): the filter file(s) are
+// parsed and 2-bit-packed ONCE per job, as one sketch input line is; every GPU context of the job builds its own table from that
+// stream (a table lives in one context's device memory) and attaches it to its sketcher before the first batch.
+struct JobFilter {
+    d2g_seqpack *sp = nullptr;                            // null: no --filterset
+    std::mutex mu;
+    bool reported = false;                                // --gpu-stats "filter": the first table built speaks for all
+    explicit JobFilter(const Options &o) {
+        if (o.filterset.empty()) return;
+        check(nullptr, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
+        if (d2g_seqpack_add_path(sp, o.filterset.c_str()) != D2G_OK) die("Failed to open file " + o.filterset + " for reading");   // d2.cpp:63
+        o.filterset_built = true;
+        o.filterset_size = d2g_seqpack_nkmers(sp, 0);     // occurrences: the reference sorts but never deduplicates (filterset.h:82)
+        if (o.cache) std::fprintf(stderr, "dashing2 (MI355X): warning: --cache with --filterset: cache file names do not carry the filter "
+                                          "(fastxmerge.cpp:70-120); existing caches are loaded as they are, filtered or not.\n");
+    }
+    ~JobFilter() { if (sp) d2g_seqpack_destroy(sp); }
+    // the table of one context, attached to its sketcher; the filter lives until the process ends (or D2G_FULL_TEARDOWN's caller frees it)
+    d2g_kmer_filter *attach(d2g_ctx *ctx, d2g_sketcher *sk, const Options &o) {
+        if (!sp) return nullptr;
+        d2g_kmer_filter *f = nullptr;
+        check(ctx, d2g_kmer_filter_create(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp), d2g_seqpack_run_len(sp),
+                                          d2g_seqpack_nruns(sp), o.k, o.canon, &f), "d2g_kmer_filter_create");
+        check(ctx, d2g_sketcher_set_filter(sk, f), "d2g_sketcher_set_filter");
+        std::lock_guard<std::mutex> lk(mu);
+        if (g_stats.on && !reported) {
+            reported = true;
+            uint64_t nocc = 0, ndist = 0; size_t bytes = 0;
+            check(ctx, d2g_kmer_filter_info(ctx, f, &nocc, &ndist, &bytes), "d2g_kmer_filter_info");
+            int n = 0; float avg = 0, last = 0;
+            (void)d2g_kernel_ms(ctx, "filter", 1, &n, &avg, &last);
+            g_stats.nest("filter", Json::object().integer("kmers", nocc).integer("distinct", ndist).integer("table_bytes", bytes).num("build_ms", last));
+        }
+        return f;
+    }
+};
+
 // x87 finalisation (getcard / data, src/oph.h:240-263) and cache files leave the device threads through a small queue
 struct Fin { size_t g; std::vector<uint64_t> regs; std::vector<double> sigs, cards; std::vector<uint32_t> counts; };   // counts: [n][m] with -N
 
@@ -126,6 +163,7 @@ struct DeviceSide {
     const GroupPlan &plan;
     IngestPipeline &pipe;
     BoundedQueue<Fin> &finq;
+    JobFilter &filter;
     const std::vector<int> devs;
     const bool count_kmers;                               // -N with -o: K1 is followed by its count pass
     d2g_ctx *const first_ctx;                             // the context of thread 0; every other thread makes its own
@@ -188,6 +226,7 @@ struct DeviceSide {
         }
         d2g_sketcher *sk = nullptr;
         check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+        d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);              // before the first group
         double gpu = 0; uint64_t bases = 0; size_t ndevg = 0, nhostg = 0;
         for (IngestGroup r; pipe.next(r);) {
             if (r.failed()) continue;                                       // error recorded by the pipeline; drain the queue
@@ -205,7 +244,7 @@ struct DeviceSide {
                 int n = 0; float avg = 0, last = 0;
                 if (d2g_kernel_ms(ctx, SKETCH_KERNELS[x], 1, &n, &avg, &last) == D2G_OK) { mine[x].launches = n; mine[x].total_ms = double(avg) * n; }
             }
-        if (g_release_at_exit) { d2g_sketcher_destroy(sk); if (ctx != first_ctx) d2g_ctx_destroy(ctx); }
+        if (g_release_at_exit) { d2g_sketcher_destroy(sk); d2g_kmer_filter_destroy(kf); if (ctx != first_ctx) d2g_ctx_destroy(ctx); }
         std::lock_guard<std::mutex> lk(mu);
         t_gpu += gpu; total_bases += bases; n_dev_groups += ndevg; n_host_groups += nhostg;
         groups_of[di] += ndevg + nhostg;
@@ -237,6 +276,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
     res.cardinalities.assign(N, -1.);
     res.signatures.assign(N * S, 0.);
     const bool want_ids = saves_kmers(o), want_counts = want_ids && o.save_kmercounts;
+    JobFilter filter(o);
     if (o.save_kmercounts) res.kmercountfiles.resize(N);                // fastxsketch.cpp:280-282
     if (want_ids) res.kmers.assign(N * S, 0);                           // :293-298
     if (want_counts) res.kmercounts.assign(N * S, 0.f);
@@ -304,7 +344,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
     int ndev = groups.size() > 1 ? 2 : 1;
     if (const char *e = std::getenv("D2G_DEVICE_THREADS")) { const int v = std::atoi(e); if (v >= 1 && v <= 8) ndev = v; }
     const size_t nthreads_dev = std::max<size_t>(1, std::min<size_t>(size_t(ndev) * devs.size(), std::max<size_t>(groups.size(), 1)));
-    DeviceSide ds{o, todo, plan, *pipe, finq, devs, want_counts, ctx, {}, 0, 0, 0, 0, std::vector<std::array<KAcc, NSK>>(devs.size()), std::vector<size_t>(devs.size(), 0)};
+    DeviceSide ds{o, todo, plan, *pipe, finq, filter, devs, want_counts, ctx, {}, 0, 0, 0, 0, std::vector<std::array<KAcc, NSK>>(devs.size()), std::vector<size_t>(devs.size(), 0)};
     std::vector<std::thread> more;
     const double t_dev0 = now();
     for (size_t t = 1; t < nthreads_dev; ++t) more.emplace_back([&ds, t, ndev] { ds.run(nullptr, t / size_t(ndev)); });
@@ -375,6 +415,8 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     const uint32_t *run_len = d2g_seqpack_run_len(sp);
     d2g_sketcher *sk = nullptr;
     check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+    JobFilter filter(o);
+    d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);                         // fastxsketchbyseq.cpp:327,370,383,420-423
     std::vector<uint64_t> regs, rs_rel, goff_rel, ndist;
     std::vector<double> sigs, cards;
     const size_t max_rec = std::max<size_t>(1, (size_t(64) << 20) / m);            // <= 512 MiB of registers per launch
@@ -422,6 +464,7 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
         g0 = g1;
     }
     d2g_sketcher_destroy(sk);
+    d2g_kmer_filter_destroy(kf);
     d2g_seqpack_destroy(sp);
     write_stacked(res, o);
 }

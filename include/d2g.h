@@ -83,7 +83,8 @@ int         d2g_host_register(d2g_ctx *ctx, void *hptr, size_t nbytes);
 int         d2g_host_unregister(d2g_ctx *ctx, void *hptr);
 /* Pays one-time costs NOW -- on whatever thread calls it, e.g. a helper thread that has just created the context while the main
  * thread is still reading its inputs -- instead of inside the first real operation: D2G_WARM_COPY = the runtime's copy machinery
- * (the first host<->device copy of a process costs ~30 ms, whatever its size), D2G_WARM_K* = the code objects of a kernel family. */
+ * (the first host<->device copy of a process costs ~30 ms, whatever its size), D2G_WARM_K* = the code objects of a kernel family
+ * (D2G_WARM_K1 and D2G_WARM_K3 include the filtered instantiations of their k-mer walkers and the filter's own kernels). */
 #define D2G_WARM_COPY 1
 #define D2G_WARM_K0   2
 #define D2G_WARM_K1   4
@@ -95,7 +96,7 @@ int         d2g_device_name(int device, char *buf, size_t cap);
 int         d2g_memcpy_h2d(d2g_ctx *ctx, void *dst_dev, const void *src_host, size_t nbytes, void *stream);
 int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, size_t nbytes, void *stream);
 /* Per-launch HIP-event timing of the dominant kernels.  With timing enabled every launch of
- * the K1 kernel ("k1"), its count pass ("k1count", also under D2G_TIME_K1), the K0 ingest chain ("k0"), the K3 chain ("k3"), the K2 pair kernel ("k2") and the K2 prepare chain ("k2prep") is
+ * the K1 kernel ("k1"), its count pass ("k1count", also under D2G_TIME_K1), the K0 ingest chain ("k0"), the build of a k-mer filter ("filter"), the K3 chain ("k3"), the K2 pair kernel ("k2") and the K2 prepare chain ("k2prep") is
  * bracketed by events recorded on the launch stream; nothing synchronises until d2g_kernel_ms,
  * which reports the number of logged launches, their average and the last duration (ms) and
  * optionally clears the log. */
@@ -107,6 +108,7 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
 #define D2G_TIME_KNN    64      /* "knn": the selection kernel of d2g_cmp_knn_dev (its count walk is logged as "k2") */
 #define D2G_TIME_DEDUP  128     /* "dedup": the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the in-order
                                  * step alone; the count walk is logged as "k2") */
+#define D2G_TIME_FILTER 256     /* "filter": the build of a k-mer filter's table (d2g_kmer_filter_create*) */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -277,6 +279,38 @@ int  d2g_sketcher_run_counts(d2g_sketcher *sk, const uint8_t *packed, size_t pac
                              const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                              const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
                              size_t sketchsize, uint64_t *regs_out /* host [n][m] */, uint32_t *counts_out /* host [n][m] */);
+
+/* ---- K1f: --filterset, k-mers that every sketch skips ---------------------------
+ * Replaces FilterSet in its sorted-hash-set form (reference src/filterset.h:35-222, built at src/d2.cpp:45-98) and its test
+ * `if(!opts.fs_ || !opts.fs_->in_set(maskfn(x))) func(maskfn(x))` (src/fastxsketch.cpp:385-398, src/fastxsketchbyseq.cpp:327,370,383):
+ * the k-mers of the filter input -- enumerated exactly as a sketch input's are, with the sketch's k and canonicalisation -- sit in an
+ * open-addressing table in device memory, and the k-mer walker of K1, K1b and K3 hands on only the k-mers that are NOT in it.  A
+ * filtered k-mer is invisible to everything downstream: OPH registers, their counts, the exact counter behind --multiset (registers,
+ * total weight, the count threshold applied to what remains) and the distinct count; an input whose k-mers are all filtered behaves
+ * like an input without k-mers.  The table holds RAW 2-bit k-mers (maskfn is a bijection), so it does not depend on the seed or
+ * xormask of the sketch calls; it does depend on k and canon.  A filter without k-mers is legal and filters nothing. */
+typedef struct d2g_kmer_filter d2g_kmer_filter;
+/* device-resident: plan + packed stream of the filter input (all its "genomes" go into ONE set); enqueues on stream */
+int  d2g_kmer_filter_create_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, void *stream,
+                                d2g_kmer_filter **out);
+/* host-pointer form: the packed-run-stream arguments of d2g_oph_sketch (so a d2g_seqpack feeds it); synchronises */
+int  d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
+                            size_t nrun, int k, int canon, d2g_kmer_filter **out);
+void d2g_kmer_filter_destroy(d2g_kmer_filter *filter);
+/* k-mer occurrences put in (duplicates counted: the reference's data_.size()), distinct keys held, bytes of the device table;
+ * synchronises the device */
+int  d2g_kmer_filter_info(d2g_ctx *ctx, const d2g_kmer_filter *filter, uint64_t *noccurrences, uint64_t *ndistinct, size_t *table_bytes);
+/* membership of n raw 2-bit k-mers (host arrays; canonical ones for a canon filter), through the SAME device probe the walker uses */
+int  d2g_kmer_filter_contains(d2g_ctx *ctx, const d2g_kmer_filter *filter, const uint64_t *kmers, size_t n, uint8_t *out);
+/* attach (NULL detaches).  The filter must outlive the plan / sketcher or be detached first.  A filter of another context, k or
+ * canon makes the SKETCH call return D2G_ERR_INVALID, before it writes anything.  More than 2^31 k-mers: D2G_ERR_UNSUPPORTED at
+ * creation; no memory for the table: D2G_ERR_NOMEM (never a smaller table).
+ * A plan's filter is honoured by d2g_oph_sketch_dev, d2g_oph_count_dev and d2g_bmh_sketch_dev; a sketcher's by every
+ * d2g_sketcher_run*, packed == NULL (K0-ingested) included.  --multiset calls with a filter walk the input once more, first, to count
+ * the surviving k-mers per genome (their layout depends on it) and wait for that count.  The one-shot host-pointer entry points
+ * (d2g_oph_sketch, d2g_bmh_sketch, d2g_kmer_count, ...) take no filter. */
+int  d2g_oph_plan_set_filter(d2g_oph_plan *plan, const d2g_kmer_filter *filter);
+int  d2g_sketcher_set_filter(d2g_sketcher *sk, const d2g_kmer_filter *filter);
 
 /* ---- K0: FASTA bytes -> packed run stream on the GPU (host ingest pipelines) ------
  * Replaces, for plain FASTA inputs, the host parser + 2-bit packer (d2g_seqpack_*; reference call sites
