@@ -102,6 +102,39 @@ void d2g_warm_filter() {
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&filter_build_kernel));
 }
 
+// the table of the k-mers that the walk of `km` over nblk blocks enumerates (nkmers of them), built on `s`; whatever filter km
+// carries plays no part in building one
+static int filter_build(d2g_ctx *ctx, KmerArgs km, size_t nblk, uint64_t nkmers, int k, int canon, hipStream_t s, d2g_kmer_filter **out) {
+    if (nkmers > (1ull << 31)) {
+        ctx->last_error = "k-mer filter of more than 2^31 k-mers (its table would pass 2^32 slots)";
+        return D2G_ERR_UNSUPPORTED;
+    }
+    D2G_HIP(ctx, hipSetDevice(ctx->device));
+    d2g_kmer_filter *f = new (std::nothrow) d2g_kmer_filter();
+    if (!f) return D2G_ERR_NOMEM;
+    std::unique_ptr<d2g_kmer_filter, void (*)(d2g_kmer_filter *)> owner(f, d2g_kmer_filter_destroy);
+    f->ctx = ctx; f->k = k; f->canon = canon != 0; f->noccurrences = nkmers;
+    f->slots = 16;
+    while (f->slots < 2 * f->noccurrences) f->slots <<= 1;
+    if (int rc = f->d_tab.alloc(ctx, f->slots + 2, "k-mer filter table")) return rc;      // out of memory: D2G_ERR_NOMEM, no smaller table
+    d2g_timer tm(ctx, &ctx->ev_filter, s);
+    D2G_HIP(ctx, hipMemsetAsync(f->d_tab, 0xFF, f->slots * sizeof(uint64_t), s));
+    D2G_HIP(ctx, hipMemsetAsync(f->d_tab + f->slots, 0, 2 * sizeof(uint64_t), s));
+    if (nblk) {
+        FilterBuildArgs a;
+        KmerArgs self;
+        d2g_filter_args(f, &self);
+        a.km = km;
+        a.km.ftab = nullptr;
+        a.tab = f->d_tab; a.mask = self.fmask; a.shift = self.fshift;
+        hipLaunchKernelGGL(filter_build_kernel, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a);
+    }
+    tm.stop();
+    D2G_HIP(ctx, hipGetLastError());
+    *out = owner.release();
+    return D2G_OK;
+}
+
 extern "C" {
 
 void d2g_kmer_filter_destroy(d2g_kmer_filter *f) {
@@ -117,60 +150,27 @@ int d2g_kmer_filter_create_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uin
     D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
     D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
-    if (plan->nkmers > (1ull << 31)) {
-        ctx->last_error = "k-mer filter of more than 2^31 k-mers (its table would pass 2^32 slots)";
-        return D2G_ERR_UNSUPPORTED;
-    }
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = as_stream(stream);
-    d2g_kmer_filter *f = new (std::nothrow) d2g_kmer_filter();
-    if (!f) return D2G_ERR_NOMEM;
-    std::unique_ptr<d2g_kmer_filter, void (*)(d2g_kmer_filter *)> owner(f, d2g_kmer_filter_destroy);
-    f->ctx = ctx; f->k = plan->k; f->canon = canon != 0; f->noccurrences = plan->nkmers;
-    f->slots = 16;
-    while (f->slots < 2 * f->noccurrences) f->slots <<= 1;
-    if (int rc = f->d_tab.alloc(ctx, f->slots + 2, "k-mer filter table")) return rc;      // out of memory: D2G_ERR_NOMEM, no smaller table
-    d2g_timer tm(ctx, &ctx->ev_filter, s);
-    D2G_HIP(ctx, hipMemsetAsync(f->d_tab, 0xFF, f->slots * sizeof(uint64_t), s));
-    D2G_HIP(ctx, hipMemsetAsync(f->d_tab + f->slots, 0, 2 * sizeof(uint64_t), s));
-    if (plan->nblk) {
-        FilterBuildArgs a;
-        KmerArgs self;
-        d2g_filter_args(f, &self);
-        a.km = d2g_plan_args(plan, packed_dev, canon);
-        a.km.ftab = nullptr;                                      // whatever filter the PLAN carries plays no part in building one
-        a.tab = f->d_tab; a.mask = self.fmask; a.shift = self.fshift;
-        hipLaunchKernelGGL(filter_build_kernel, dim3((unsigned)plan->nblk), dim3(K1_THREADS), 0, s, a);
-    }
-    tm.stop();
-    D2G_HIP(ctx, hipGetLastError());
-    *out = owner.release();
-    return D2G_OK;
+    return filter_build(ctx, d2g_plan_args(plan, packed_dev, canon), plan->nblk, plan->nkmers, plan->k, canon, as_stream(stream), out);
 }
 
 int d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
                            size_t nrun, int k, int canon, d2g_kmer_filter **out) {
+    const uint64_t gro[2] = {0, nrun};                            // all runs feed ONE set
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, gro, 1, k, canon};
     if (!ctx || !out) return D2G_ERR_INVALID;
     *out = nullptr;
-    const uint64_t gro[2] = {0, nrun};                            // all runs feed ONE set
-    d2g_oph_plan *plan = nullptr;
-    if (int rc = d2g_oph_plan_create(ctx, run_start, run_len, nrun, gro, 1, k, &plan)) return rc;
-    const std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> plan_owner(plan, d2g_oph_plan_destroy);
-    if (nrun) {
-        D2G_CHECK(ctx, packed != nullptr, "null packed stream");
-        uint64_t maxend = 0;
-        for (size_t r = 0; r < nrun; ++r) maxend = std::max<uint64_t>(maxend, run_start[r] + run_len[r]);
-        D2G_CHECK(ctx, packed_bytes >= (maxend + 3) / 4 + 64, "packed stream lacks the 64-byte tail pad");
-    }
-    d2g_dev<uint8_t> d_packed;
-    if (int rc = d_packed.alloc(ctx, std::max<size_t>(packed_bytes, 4), "k-mer filter stream")) return rc;
-    if (packed_bytes && nrun) D2G_HIP(ctx, hipMemcpy(d_packed, packed, packed_bytes, hipMemcpyHostToDevice));
-    d2g_kmer_filter *f = nullptr;
-    if (int rc = d2g_kmer_filter_create_dev(ctx, plan, d_packed, canon, nullptr, &f)) return rc;
-    const hipError_t e = hipStreamSynchronize(nullptr);           // the stream and the plan are released on return
-    if (e != hipSuccess) { d2g_kmer_filter_destroy(f); return d2g_hip_status(ctx, e, "k-mer filter build"); }
-    *out = f;
-    return D2G_OK;
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) -> int {
+        KmerArgs km;
+        size_t nblk = 0;
+        PlanHost ph;
+        if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, &ph)) return rc;
+        d2g_kmer_filter *f = nullptr;
+        if (int rc = filter_build(ctx, km, nblk, ph.nkmers, k, canon, sk->stream, &f)) return rc;
+        const hipError_t e = hipStreamSynchronize(sk->stream);    // the stream and the staged input are released on return
+        if (e != hipSuccess) { d2g_kmer_filter_destroy(f); return d2g_hip_status(ctx, e, "k-mer filter build"); }
+        *out = f;
+        return D2G_OK;
+    });
 }
 
 int d2g_kmer_filter_info(d2g_ctx *ctx, const d2g_kmer_filter *f, uint64_t *noccurrences, uint64_t *ndistinct, size_t *table_bytes) {

@@ -4,14 +4,11 @@
 #include "d2g_kmers.h"
 #include <vector>
 
-// host-side launch plan: 64-k-mer chunks per run, <= K1_BLOCK_CHUNKS chunks of one genome per workgroup
-struct PlanHost {
-    std::vector<uint64_t> chunk_off, bc0;
-    std::vector<uint32_t> bg, bn, blo, bhi;
-    uint64_t nkmers = 0, nbases = 0;
-};
-int d2g_build_plan_host(d2g_ctx *ctx, const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n,
-                        int k, PlanHost &p);
+// the plan unit's checks for a caller with a context: a refusal's text goes to last_error
+inline int d2g_plan_err(d2g_ctx *ctx, int rc, const std::string &err) {
+    if (rc) ctx->last_error = err;
+    return rc;
+}
 
 // K1f: the k-mers of a --filterset input as an open-addressing table of raw 2-bit k-mers in device memory (d2g_filter.hip)
 struct d2g_kmer_filter {
@@ -37,24 +34,26 @@ struct d2g_oph_plan {
     uint64_t nkmers = 0, nbases = 0;
     std::vector<uint32_t> h_run_len;           // host copies kept for K3's bucket layout
     std::vector<uint64_t> h_genome_run_off;
-    d2g_dev<uint64_t> d_run_start;
-    d2g_dev<uint32_t> d_run_len;
-    d2g_dev<uint64_t> d_run_chunk_off;
-    d2g_dev<uint32_t> d_blk_genome;
-    d2g_dev<uint64_t> d_blk_chunk0;
-    d2g_dev<uint32_t> d_blk_nchunks;
-    d2g_dev<uint32_t> d_blk_run_lo;
-    d2g_dev<uint32_t> d_blk_run_hi;
+    PlanLayout lay;                            // the eight launch tables: pieces of ONE device buffer, as the sketcher ships them
+    d2g_dev<uint8_t> d_arena;
+    // the tables K3 lays its buckets out from (host copies; no stream: a plan is applied to any)
+    PackedRuns runs(int canon) const { return {nullptr, 0, nullptr, h_run_len.data(), nrun, h_genome_run_off.data(), n, k, canon}; }
 };
 
-
-inline KmerArgs d2g_plan_args(const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon) {
-    KmerArgs a;
+// the ONLY place that points a walker's arguments at launch tables: `arena_dev` holds them as `lay` says (d2g_plan_fill)
+inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &lay, const uint8_t *packed_dev, int k, int canon) {
+    KmerArgs a{};
+    auto u64 = [&](size_t at) { return reinterpret_cast<const uint64_t *>(arena_dev + at); };
+    auto u32 = [&](size_t at) { return reinterpret_cast<const uint32_t *>(arena_dev + at); };
     a.packed = reinterpret_cast<const uint32_t *>(packed_dev);
-    a.run_start = plan->d_run_start; a.run_len = plan->d_run_len; a.run_chunk_off = plan->d_run_chunk_off;
-    a.blk_genome = plan->d_blk_genome; a.blk_chunk0 = plan->d_blk_chunk0; a.blk_nchunks = plan->d_blk_nchunks;
-    a.blk_run_lo = plan->d_blk_run_lo; a.blk_run_hi = plan->d_blk_run_hi;
-    a.k = plan->k; a.canon = canon; a.blk0 = 0;
+    a.run_start = u64(lay.run_start); a.run_len = u32(lay.run_len); a.run_chunk_off = u64(lay.run_chunk_off);
+    a.blk_genome = u32(lay.blk_genome); a.blk_chunk0 = u64(lay.blk_chunk0); a.blk_nchunks = u32(lay.blk_nchunks);
+    a.blk_run_lo = u32(lay.blk_run_lo); a.blk_run_hi = u32(lay.blk_run_hi);
+    a.k = k; a.canon = canon; a.blk0 = 0;
+    return a;
+}
+inline KmerArgs d2g_plan_args(const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon) {
+    KmerArgs a = d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon);
     d2g_filter_args(plan->filter, &a);
     return a;
 }
@@ -82,8 +81,15 @@ void d2g_k0_invalidate(d2g_sketcher *sk);
 
 
 // validate + upload one batch (launch tables in one pinned-arena copy, packed stream through the
-// pinned stage) on sk->stream; fills `out` with device pointers, `nblk` with the grid size.
-// packed == nullptr: the stream d2g_sketcher_ingest_fasta left in the device buffer is used as it is.
-int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
-                       const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
-                       KmerArgs *out, size_t *nblk, PlanHost *ph_out);
+// pinned stage) on sk->stream; fills `out` with device pointers, `nblk` with the grid size, `ph_out` (if given) with the plan.
+// in.packed == nullptr: the stream d2g_sketcher_ingest_fasta left in the device buffer is used as it is.
+int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &in, KmerArgs *out, size_t *nblk, PlanHost *ph_out);
+
+// A host-pointer one-shot is the sketcher form on a sketcher that lives for one call: f(sk), and the sketcher goes on every path.
+template <class F> int d2g_with_sketcher(d2g_ctx *ctx, F &&f) {
+    if (!ctx) return D2G_ERR_INVALID;
+    d2g_sketcher *sk = nullptr;
+    if (int rc = d2g_sketcher_create(ctx, &sk)) return rc;
+    const std::unique_ptr<d2g_sketcher, void (*)(d2g_sketcher *)> owner(sk, d2g_sketcher_destroy);
+    return f(sk);
+}

@@ -112,10 +112,83 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a)
     }
 }
 
-template <class T>
-static int upload(d2g_ctx *ctx, const std::vector<T> &h, d2g_dev<T> &d) {
-    if (int rc = d.alloc(ctx, std::max<size_t>(h.size(), 1), "oph plan alloc")) return rc;
-    if (!h.empty()) D2G_HIP(ctx, hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
+// the instantiations, indexed by POW2 * 4 + USE_LDS * 2 + FILT
+void (*const k1_kernels[8])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
+                                       k1_oph_kernel<false, true, true>,   k1_oph_kernel<true, false, false>, k1_oph_kernel<true, false, true>,
+                                       k1_oph_kernel<true, true, false>,   k1_oph_kernel<true, true, true>};
+void (*const k1_count_kernels[8])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
+                                                  k1_oph_count_kernel<false, true, false>,  k1_oph_count_kernel<false, true, true>,
+                                                  k1_oph_count_kernel<true, false, false>,  k1_oph_count_kernel<true, false, true>,
+                                                  k1_oph_count_kernel<true, true, false>,   k1_oph_count_kernel<true, true, true>};
+
+// one workgroup per block of the plan; its genome's m registers (K1: 8 bytes each; the count pass: 8 + 4) in LDS while they
+// fit the 128 KB asked for at most (m <= 16 384; m <= 10 922), beyond against HBM/L2
+template <class Args>
+int launch_k1_any(d2g_ctx *ctx, void (*const kerns[8])(Args), const Args &a, size_t nblk, size_t lds_per_reg, d2g_evlog *ev, hipStream_t s) {
+    const size_t m = a.m;
+    const bool pow2 = (m & (m - 1)) == 0;
+    const size_t lds = m * lds_per_reg;
+    const bool use_lds = lds <= 128 * 1024;
+    auto kern = kerns[pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
+    if (use_lds && lds > 48 * 1024)
+        D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    d2g_timer tm(ctx, ev, s);
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), use_lds ? lds : 0, s, a);
+    tm.stop();
+    D2G_HIP(ctx, hipGetLastError());
+    return D2G_OK;
+}
+
+// K1 over a staged batch or an applied plan: empty registers for n genomes, then the walk (if there is a block to walk)
+int k1_fill_regs(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n, size_t m, uint64_t xormask, uint64_t *regs_dev, hipStream_t s) {
+    D2G_HIP(ctx, hipMemsetAsync(regs_dev, 0xFF, n * m * sizeof(uint64_t), s));       // registers_ initialise to T(-1): oph.h:147,233
+    if (nblk == 0) return D2G_OK;
+    const K1Args a{km, regs_dev, xormask, d2g_oph_xor_const(), (uint32_t)m};
+    return launch_k1_any(ctx, k1_kernels, a, nblk, sizeof(uint64_t), &ctx->ev_k1, s);
+}
+
+// K1b over the same batch, behind K1 on the same stream: zero counters, then the second walk
+int k1_fill_counts(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n, size_t m, uint64_t xormask, const uint64_t *regs_dev,
+                   uint32_t *counts_dev, hipStream_t s) {
+    D2G_HIP(ctx, hipMemsetAsync(counts_dev, 0, n * m * sizeof(uint32_t), s));        // counts_ start at 0: oph.h:148,234
+    if (nblk == 0) return D2G_OK;
+    const K1CountArgs a{km, regs_dev, counts_dev, xormask, d2g_oph_xor_const(), (uint32_t)m};
+    return launch_k1_any(ctx, k1_count_kernels, a, nblk, sizeof(uint64_t) + sizeof(uint32_t), &ctx->ev_k1count, s);
+}
+
+// what the plan forms check alike, before the device is touched
+int check_dev_call(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, size_t sketchsize) {
+    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
+    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
+    D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
+    return d2g_filter_check(ctx, plan->filter, plan->k, canon);
+}
+
+// the sketcher forms: the batch staged on the sketcher's stream, K1 (and K1b) behind it, the results copied back, ONE wait
+int sketcher_run(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out,
+                 bool counts) {
+    if (!sk) return D2G_ERR_INVALID;
+    d2g_ctx *ctx = sk->ctx;
+    const size_t n = in.n;
+    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    D2G_CHECK(ctx, (regs_out != nullptr && (counts_out != nullptr || !counts)) || n == 0, counts ? "null regs_out or counts_out" : "null regs_out");
+    if (counts) {                                                                     // before the stage touches the device stream
+        std::string err;
+        if (int rc = d2g_plan_err(ctx, d2g_plan_check_count_range(in, err), err)) return rc;
+    }
+    KmerArgs km;
+    size_t nblk = 0;
+    if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, nullptr)) return rc;
+    const size_t m = d2g_oph_m(sketchsize), nm = std::max<size_t>(n * m, 1);
+    if (int rc = sk->d_regs.grow(ctx, nm, 4096)) return rc;
+    if (counts) if (int rc = sk->d_counts.grow(ctx, nm, 4096)) return rc;
+    hipStream_t s = sk->stream;
+    if (int rc = k1_fill_regs(ctx, km, nblk, n, m, xormask, sk->d_regs, s)) return rc;
+    if (counts) if (int rc = k1_fill_counts(ctx, km, nblk, n, m, xormask, sk->d_regs, sk->d_counts, s)) return rc;
+    if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (n && counts) D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipStreamSynchronize(s));
     return D2G_OK;
 }
 
@@ -132,242 +205,54 @@ void d2g_oph_plan_destroy(d2g_oph_plan *p) {
 uint64_t d2g_oph_plan_nkmers(const d2g_oph_plan *p) { return p ? p->nkmers : 0; }
 uint64_t d2g_oph_plan_nbases(const d2g_oph_plan *p) { return p ? p->nbases : 0; }
 
-}  // extern "C"
-
-int d2g_build_plan_host(d2g_ctx *ctx, const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, PlanHost &p) {
-    D2G_CHECK(ctx, genome_run_off && (nrun == 0 || run_len), "oph plan: null table");
-    if (k < 1 || k > 32) { ctx->last_error = "k must be in [1,32] (exact 2-bit encoding path)"; return D2G_ERR_UNSUPPORTED; }
-    D2G_CHECK(ctx, genome_run_off[n] == nrun, "oph plan: genome_run_off[n] != nrun");
-    D2G_CHECK(ctx, nrun < (1ull << 32), "oph plan: too many runs");
-    p.chunk_off.assign(nrun + 1, 0);
-    for (size_t r = 0; r < nrun; ++r) {
-        D2G_CHECK(ctx, run_len[r] >= (uint32_t)k, "run shorter than k");
-        const uint64_t nk = (uint64_t)run_len[r] - k + 1;
-        p.chunk_off[r + 1] = p.chunk_off[r] + div_up<uint64_t>(nk, K1_CHUNK);
-        p.nkmers += nk;
-        p.nbases += run_len[r];
-    }
-    for (size_t g = 0; g < n; ++g) {
-        const size_t r0 = genome_run_off[g], r1 = genome_run_off[g + 1];
-        D2G_CHECK(ctx, r1 >= r0 && r1 <= nrun, "genome_run_off not monotone");
-        const uint64_t cbeg = p.chunk_off[r0], cend = p.chunk_off[r1];
-        size_t r = r0;
-        for (uint64_t c = cbeg; c < cend; c += K1_BLOCK_CHUNKS) {
-            const uint32_t nc = (uint32_t)std::min<uint64_t>(K1_BLOCK_CHUNKS, cend - c);
-            while (p.chunk_off[r + 1] <= c) ++r;
-            size_t rl = r;
-            while (p.chunk_off[rl + 1] < c + nc) ++rl;
-            p.bg.push_back((uint32_t)g); p.bc0.push_back(c); p.bn.push_back(nc);
-            p.blo.push_back((uint32_t)r); p.bhi.push_back((uint32_t)rl + 1);
-        }
-    }
-    D2G_CHECK(ctx, p.bg.size() < (1ull << 31), "oph plan: too many workgroups; sketch in smaller batches");
-    return D2G_OK;
-}
-
-namespace {
-int launch_k1(d2g_ctx *ctx, K1Args a, size_t nblk, size_t m, hipStream_t s) {
-    const bool pow2 = (m & (m - 1)) == 0;
-    const size_t lds = m * sizeof(uint64_t);
-    const bool use_lds = lds <= 128 * 1024;
-    void (*const kerns[8])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
-                                      k1_oph_kernel<false, true, true>,   k1_oph_kernel<true, false, false>, k1_oph_kernel<true, false, true>,
-                                      k1_oph_kernel<true, true, false>,   k1_oph_kernel<true, true, true>};
-    auto kern = kerns[pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
-    if (use_lds && lds > 48 * 1024)
-        D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    d2g_timer tm(ctx, &ctx->ev_k1, s);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), use_lds ? lds : 0, s, a);
-    tm.stop();
-    D2G_HIP(ctx, hipGetLastError());
-    return D2G_OK;
-}
-
-// registers + counters in LDS while 12 m bytes fit the 128 KB K1 asks for at most (m <= 10 922); beyond, against HBM/L2
-int launch_k1_count(d2g_ctx *ctx, K1CountArgs a, size_t nblk, size_t m, hipStream_t s) {
-    const bool pow2 = (m & (m - 1)) == 0;
-    const size_t lds = m * (sizeof(uint64_t) + sizeof(uint32_t));
-    const bool use_lds = lds <= 128 * 1024;
-    void (*const kerns[8])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
-                                           k1_oph_count_kernel<false, true, false>,  k1_oph_count_kernel<false, true, true>,
-                                           k1_oph_count_kernel<true, false, false>,  k1_oph_count_kernel<true, false, true>,
-                                           k1_oph_count_kernel<true, true, false>,   k1_oph_count_kernel<true, true, true>};
-    auto kern = kerns[pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
-    if (use_lds && lds > 48 * 1024)
-        D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    d2g_timer tm(ctx, &ctx->ev_k1count, s);
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), use_lds ? lds : 0, s, a);
-    tm.stop();
-    D2G_HIP(ctx, hipGetLastError());
-    return D2G_OK;
-}
-
-// the counting forms with host outputs return uint32 counts without the reference's wrap (idcounts() copies doubles into
-// uint32, oph.h:272-277): a genome that could reach 2^32 is refused, before anything is staged or launched.  Tables that the
-// plan builder will reject (null, not monotone, a run shorter than k) are left to it.
-int check_count_range(d2g_ctx *ctx, const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k) {
-    if (!genome_run_off || (nrun && !run_len) || k < 1) return D2G_OK;
-    for (size_t g = 0; g < n; ++g) {
-        uint64_t nk = 0;
-        for (uint64_t r = genome_run_off[g]; r < genome_run_off[g + 1] && r < nrun; ++r)
-            if (run_len[r] >= (uint32_t)k) nk += (uint64_t)run_len[r] - k + 1;
-        if (nk >= (1ull << 32)) {
-            ctx->last_error = "k-mer counts of a genome with 2^32 k-mers or more (the reference's uint32 counts wrap there)";
-            return D2G_ERR_UNSUPPORTED;
-        }
-    }
-    return D2G_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                         const uint64_t *genome_run_off, size_t n, int k, d2g_oph_plan **out) {
+    const PackedRuns in{nullptr, 0, run_start, run_len, nrun, genome_run_off, n, k, 0};      // a plan is made without a stream
     if (!ctx || !out) return D2G_ERR_INVALID;
     *out = nullptr;
-    D2G_CHECK(ctx, nrun == 0 || run_start, "d2g_oph_plan_create: null table");
     PlanHost ph;
-    if (int rc = d2g_build_plan_host(ctx, run_len, nrun, genome_run_off, n, k, ph)) return rc;
+    std::string err;
+    if (int rc = d2g_plan_err(ctx, d2g_plan_build(in, ph, err), err)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    d2g_oph_plan *p = new (std::nothrow) d2g_oph_plan();
+    std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> p(new (std::nothrow) d2g_oph_plan(), d2g_oph_plan_destroy);
     if (!p) return D2G_ERR_NOMEM;
     p->ctx = ctx; p->k = k; p->n = n; p->nrun = nrun;
     p->h_run_len.assign(run_len, run_len + nrun);
     p->h_genome_run_off.assign(genome_run_off, genome_run_off + n + 1);
     p->nkmers = ph.nkmers; p->nbases = ph.nbases; p->nblk = ph.bg.size();
-    std::vector<uint64_t> rs(run_start, run_start + nrun);
-    std::vector<uint32_t> rl(run_len, run_len + nrun);
-    int rc;
-    if ((rc = upload(ctx, rs, p->d_run_start)) || (rc = upload(ctx, rl, p->d_run_len)) ||
-        (rc = upload(ctx, ph.chunk_off, p->d_run_chunk_off)) || (rc = upload(ctx, ph.bg, p->d_blk_genome)) ||
-        (rc = upload(ctx, ph.bc0, p->d_blk_chunk0)) || (rc = upload(ctx, ph.bn, p->d_blk_nchunks)) ||
-        (rc = upload(ctx, ph.blo, p->d_blk_run_lo)) || (rc = upload(ctx, ph.bhi, p->d_blk_run_hi))) {
-        d2g_oph_plan_destroy(p);
-        return rc;
-    }
-    *out = p;
+    p->lay = d2g_plan_layout(nrun, p->nblk);
+    std::vector<uint8_t> h(p->lay.total);
+    d2g_plan_fill(h.data(), p->lay, in, ph);
+    if (int rc = p->d_arena.alloc(ctx, h.size(), "oph plan alloc")) return rc;
+    D2G_HIP(ctx, hipMemcpy(p->d_arena, h.data(), h.size(), hipMemcpyHostToDevice));
+    *out = p.release();
     return D2G_OK;
 }
 
 int d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon,
                        uint64_t xormask, size_t sketchsize, uint64_t *regs_out_dev, void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    if (int rc = check_dev_call(ctx, plan, packed_dev, canon, sketchsize)) return rc;
     D2G_CHECK(ctx, regs_out_dev != nullptr, "null regs_out");
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = as_stream(stream);
-    const size_t m = d2g_oph_m(sketchsize);
-    // registers_ initialise to T(-1): oph.h:147,233
-    D2G_HIP(ctx, hipMemsetAsync(regs_out_dev, 0xFF, plan->n * m * sizeof(uint64_t), s));
-    if (plan->nblk == 0) return D2G_OK;
-    D2G_CHECK(ctx, packed_dev != nullptr, "null packed stream");
-    K1Args a;
-    a.km = d2g_plan_args(plan, packed_dev, canon);
-    a.regs_out = regs_out_dev; a.xormask = xormask; a.ophxor = d2g_oph_xor_const();
-    a.m = (uint32_t)m;
-    return launch_k1(ctx, a, plan->nblk, m, s);
-}
-
-int d2g_oph_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
-                   const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
-                   int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
-    if (!ctx) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, regs_out != nullptr || n == 0, "null regs_out");
-    d2g_oph_plan *plan = nullptr;
-    int rc = d2g_oph_plan_create(ctx, run_start, run_len, nrun, genome_run_off, n, k, &plan);
-    if (rc) return rc;
-    const std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> plan_owner(plan, d2g_oph_plan_destroy);
-    // the kernel reads up to 20 bytes past a chunk's first word: require the documented pad
-    if (nrun) {
-        uint64_t maxend = 0;
-        for (size_t r = 0; r < nrun; ++r) maxend = std::max<uint64_t>(maxend, run_start[r] + run_len[r]);
-        if (packed_bytes < (maxend + 3) / 4 + 64) {
-            ctx->last_error = "packed stream lacks the 64-byte tail pad";
-            return D2G_ERR_INVALID;
-        }
-    }
-    const size_t m = d2g_oph_m(sketchsize);
-    d2g_dev<uint8_t> d_packed;
-    d2g_dev<uint64_t> d_regs;
-    if ((rc = d_packed.alloc(ctx, std::max<size_t>(packed_bytes, 4), "oph sketch alloc")) ||
-        (rc = d_regs.alloc(ctx, std::max<size_t>(n * m, 1), "oph sketch alloc"))) return rc;
-    hipError_t e;
-    if (packed_bytes && (e = hipMemcpy(d_packed, packed, packed_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-        ctx->last_error = hipGetErrorString(e); return D2G_ERR_HIP;
-    }
-    rc = d2g_oph_sketch_dev(ctx, plan, d_packed, canon, xormask, sketchsize, d_regs, nullptr);
-    if (rc == D2G_OK && n) {
-        e = hipMemcpy(regs_out, d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); rc = D2G_ERR_HIP; }
-    }
-    return rc;
+    return k1_fill_regs(ctx, d2g_plan_args(plan, packed_dev, canon), plan->nblk, plan->n, d2g_oph_m(sketchsize), xormask, regs_out_dev,
+                        as_stream(stream));
 }
 
 int d2g_oph_count_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
                       size_t sketchsize, const uint64_t *regs_dev, uint32_t *counts_out_dev, void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    if (int rc = check_dev_call(ctx, plan, packed_dev, canon, sketchsize)) return rc;
     D2G_CHECK(ctx, regs_dev != nullptr && counts_out_dev != nullptr, "null regs or counts_out");
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = as_stream(stream);
-    const size_t m = d2g_oph_m(sketchsize);
-    // counts_ start at 0: oph.h:148,234
-    D2G_HIP(ctx, hipMemsetAsync(counts_out_dev, 0, plan->n * m * sizeof(uint32_t), s));
-    if (plan->nblk == 0) return D2G_OK;
-    D2G_CHECK(ctx, packed_dev != nullptr, "null packed stream");
-    K1CountArgs a;
-    a.km = d2g_plan_args(plan, packed_dev, canon);
-    a.regs = regs_dev; a.counts_out = counts_out_dev; a.xormask = xormask; a.ophxor = d2g_oph_xor_const();
-    a.m = (uint32_t)m;
-    return launch_k1_count(ctx, a, plan->nblk, m, s);
-}
-
-int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
-                          const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
-                          int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
-    if (!ctx) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, (regs_out != nullptr && counts_out != nullptr) || n == 0, "null regs_out or counts_out");
-    int rc = check_count_range(ctx, run_len, nrun, genome_run_off, n, k);
-    if (rc) return rc;
-    d2g_oph_plan *plan = nullptr;
-    if ((rc = d2g_oph_plan_create(ctx, run_start, run_len, nrun, genome_run_off, n, k, &plan))) return rc;
-    const std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> plan_owner(plan, d2g_oph_plan_destroy);
-    if (nrun) {
-        uint64_t maxend = 0;
-        for (size_t r = 0; r < nrun; ++r) maxend = std::max<uint64_t>(maxend, run_start[r] + run_len[r]);
-        if (packed_bytes < (maxend + 3) / 4 + 64) {
-            ctx->last_error = "packed stream lacks the 64-byte tail pad";
-            return D2G_ERR_INVALID;
-        }
-    }
-    const size_t m = d2g_oph_m(sketchsize);
-    d2g_dev<uint8_t> d_packed;
-    d2g_dev<uint64_t> d_regs;
-    d2g_dev<uint32_t> d_counts;
-    if ((rc = d_packed.alloc(ctx, std::max<size_t>(packed_bytes, 4), "oph sketch alloc")) ||
-        (rc = d_regs.alloc(ctx, std::max<size_t>(n * m, 1), "oph sketch alloc")) ||
-        (rc = d_counts.alloc(ctx, std::max<size_t>(n * m, 1), "oph sketch alloc"))) return rc;
-    if (packed_bytes) D2G_HIP(ctx, hipMemcpy(d_packed, packed, packed_bytes, hipMemcpyHostToDevice));
-    if ((rc = d2g_oph_sketch_dev(ctx, plan, d_packed, canon, xormask, sketchsize, d_regs, nullptr)) ||
-        (rc = d2g_oph_count_dev(ctx, plan, d_packed, canon, xormask, sketchsize, d_regs, d_counts, nullptr))) return rc;
-    if (n) {
-        D2G_HIP(ctx, hipMemcpy(regs_out, d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        D2G_HIP(ctx, hipMemcpy(counts_out, d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    return D2G_OK;
+    return k1_fill_counts(ctx, d2g_plan_args(plan, packed_dev, canon), plan->nblk, plan->n, d2g_oph_m(sketchsize), xormask, regs_dev,
+                          counts_out_dev, as_stream(stream));
 }
 
 void d2g_sketcher_destroy(d2g_sketcher *sk) {
     if (!sk) return;
     (void)hipSetDevice(sk->ctx->device);
+    (void)hipStreamSynchronize(sk->stream);      // a call that failed behind its stage may have left copies from the pinned buffers in flight
     if (sk->k3) d2g_k3_state_destroy(sk->k3);
     if (sk->k0) d2g_k0_state_destroy(sk->k0);
     delete sk;
@@ -389,126 +274,65 @@ int d2g_sketcher_create(d2g_ctx *ctx, d2g_sketcher **out) {
 int d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                      const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                      uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
-    if (!sk) return D2G_ERR_INVALID;
-    d2g_ctx *ctx = sk->ctx;
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
-    D2G_CHECK(ctx, regs_out != nullptr || n == 0, "null regs_out");
-    K1Args a;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon,
-                                    &a.km, &nblk, nullptr)) return rc;
-    const size_t m = d2g_oph_m(sketchsize);
-    if (int rc = sk->d_regs.grow(ctx, std::max<size_t>(n * m, 1), 4096)) return rc;
-    hipStream_t s = sk->stream;
-    D2G_HIP(ctx, hipMemsetAsync(sk->d_regs, 0xFF, std::max<size_t>(n * m, 1) * sizeof(uint64_t), s));   // registers_ = T(-1): oph.h:147,233
-    if (nblk) {
-        a.regs_out = sk->d_regs; a.xormask = xormask; a.ophxor = d2g_oph_xor_const();
-        a.m = (uint32_t)m;
-        if (int rc = launch_k1(ctx, a, nblk, m, s)) return rc;
-    }
-    if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    D2G_HIP(ctx, hipStreamSynchronize(s));
-    return D2G_OK;
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return sketcher_run(sk, in, xormask, sketchsize, regs_out, nullptr, false);
 }
 
 int d2g_sketcher_run_counts(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                             const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                             uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
-    if (!sk) return D2G_ERR_INVALID;
-    d2g_ctx *ctx = sk->ctx;
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
-    D2G_CHECK(ctx, (regs_out != nullptr && counts_out != nullptr) || n == 0, "null regs_out or counts_out");
-    if (int rc = check_count_range(ctx, run_len, nrun, genome_run_off, n, k)) return rc;      // before the stage touches the device stream
-    K1Args a;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon,
-                                    &a.km, &nblk, nullptr)) return rc;
-    const size_t m = d2g_oph_m(sketchsize), nm = std::max<size_t>(n * m, 1);
-    if (int rc = sk->d_regs.grow(ctx, nm, 4096)) return rc;
-    if (int rc = sk->d_counts.grow(ctx, nm, 4096)) return rc;
-    hipStream_t s = sk->stream;
-    D2G_HIP(ctx, hipMemsetAsync(sk->d_regs, 0xFF, nm * sizeof(uint64_t), s));
-    D2G_HIP(ctx, hipMemsetAsync(sk->d_counts, 0, nm * sizeof(uint32_t), s));
-    if (nblk) {
-        a.regs_out = sk->d_regs; a.xormask = xormask; a.ophxor = d2g_oph_xor_const();
-        a.m = (uint32_t)m;
-        if (int rc = launch_k1(ctx, a, nblk, m, s)) return rc;
-        K1CountArgs c;
-        c.km = a.km; c.regs = sk->d_regs; c.counts_out = sk->d_counts; c.xormask = xormask; c.ophxor = a.ophxor; c.m = a.m;
-        if (int rc = launch_k1_count(ctx, c, nblk, m, s)) return rc;
-    }
-    if (n) {
-        D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-        D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    }
-    D2G_HIP(ctx, hipStreamSynchronize(s));
-    return D2G_OK;
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, true);
+}
+
+int d2g_oph_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                   const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
+                   int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, regs_out, nullptr, false); });
+}
+
+int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                          const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
+                          int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, true); });
 }
 
 }  // extern "C"
 
-int d2g_sketcher_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
-                       const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
-                       KmerArgs *out, size_t *nblk_out, PlanHost *ph_out) {
+int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerArgs *out, size_t *nblk_out, PlanHost *ph_out) {
     d2g_ctx *ctx = sk->ctx;
-    if (int rc = d2g_filter_check(ctx, sk->filter, k, canon)) return rc;   // before the stream, the buffers or an output are touched
+    PackedRuns in = caller;
+    if (int rc = d2g_filter_check(ctx, sk->filter, in.k, in.canon)) return rc;   // before the stream, the buffers or an output are touched
     uint64_t ingested_bases = 0;
-    const bool use_ingested = packed == nullptr && d2g_k0_ingested(sk, &ingested_bases);
-    D2G_CHECK(ctx, nrun == 0 || (run_start && (packed || use_ingested)), "null input");
-    if (use_ingested) packed_bytes = (size_t)((ingested_bases + 3) / 4 + 64);        // the device stream's extent (zero-padded by the ingest)
+    const bool use_ingested = in.packed == nullptr && d2g_k0_ingested(sk, &ingested_bases);
+    D2G_CHECK(ctx, in.nrun == 0 || (in.run_start && (in.packed || use_ingested)), "null input");   // refused with an ingested stream left usable
+    if (use_ingested) in.packed_bytes = (size_t)((ingested_bases + 3) / 4 + 64);      // the device stream's extent (zero-padded by the ingest)
     else d2g_k0_invalidate(sk);                                                       // the device buffer is about to be overwritten
     PlanHost ph_local;
     PlanHost &ph = ph_out ? *ph_out : ph_local;
-    if (int rc = d2g_build_plan_host(ctx, run_len, nrun, genome_run_off, n, k, ph)) return rc;
-    if (nrun) {
-        uint64_t maxend = 0;
-        for (size_t r = 0; r < nrun; ++r) maxend = std::max<uint64_t>(maxend, run_start[r] + run_len[r]);
-        D2G_CHECK(ctx, packed_bytes >= (maxend + 3) / 4 + 64, "packed stream lacks the 64-byte tail pad");
-    }
+    std::string err;
+    if (int rc = d2g_plan_err(ctx, d2g_plan_build(in, ph, err), err)) return rc;
+    if (int rc = d2g_plan_err(ctx, d2g_plan_check_tail(in, err), err)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nblk = ph.bg.size();
     if (!use_ingested)
-        if (int rc = sk->d_packed.grow(ctx, std::max<size_t>(packed_bytes, 4), 4096)) return rc;
-    // arena layout (256-byte aligned pieces)
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    size_t off = 0;
-    const size_t o_rs = off;  off = al(off + nrun * 8);
-    const size_t o_co = off;  off = al(off + (nrun + 1) * 8);
-    const size_t o_c0 = off;  off = al(off + nblk * 8);
-    const size_t o_rl = off;  off = al(off + nrun * 4);
-    const size_t o_bg = off;  off = al(off + nblk * 4);
-    const size_t o_bn = off;  off = al(off + nblk * 4);
-    const size_t o_lo = off;  off = al(off + nblk * 4);
-    const size_t o_hi = off;  off = al(off + nblk * 4);
-    if (int rc = sk->d_arena.grow(ctx, off, 65536)) return rc;
-    if (int rc = sk->h_arena.grow(ctx, off, 65536)) return rc;
-    uint8_t *h = sk->h_arena;
-    if (nrun) { std::memcpy(h + o_rs, run_start, nrun * 8); std::memcpy(h + o_rl, run_len, nrun * 4); }
-    std::memcpy(h + o_co, ph.chunk_off.data(), (nrun + 1) * 8);
-    if (nblk) {
-        std::memcpy(h + o_c0, ph.bc0.data(), nblk * 8); std::memcpy(h + o_bg, ph.bg.data(), nblk * 4);
-        std::memcpy(h + o_bn, ph.bn.data(), nblk * 4);  std::memcpy(h + o_lo, ph.blo.data(), nblk * 4);
-        std::memcpy(h + o_hi, ph.bhi.data(), nblk * 4);
-    }
+        if (int rc = sk->d_packed.grow(ctx, std::max<size_t>(in.packed_bytes, 4), 4096)) return rc;
+    const PlanLayout lay = d2g_plan_layout(in.nrun, nblk);
+    if (int rc = sk->d_arena.grow(ctx, lay.total, 65536)) return rc;
+    if (int rc = sk->h_arena.grow(ctx, lay.total, 65536)) return rc;
+    d2g_plan_fill(sk->h_arena, lay, in, ph);
     hipStream_t s = sk->stream;
-    D2G_HIP(ctx, hipMemcpyAsync(sk->d_arena, h, off, hipMemcpyHostToDevice, s));
-    if (packed_bytes && !use_ingested) {
+    D2G_HIP(ctx, hipMemcpyAsync(sk->d_arena, sk->h_arena, lay.total, hipMemcpyHostToDevice, s));
+    if (in.packed && in.packed_bytes) {
         // pageable source: stage through our own pinned buffer (the runtime would otherwise pin the
         // caller's pages on the fly, which contends with parser threads on the process' mm locks)
-        if (int rc = sk->h_stage.grow(ctx, packed_bytes, 65536)) return rc;
-        std::memcpy(sk->h_stage, packed, packed_bytes);
-        D2G_HIP(ctx, hipMemcpyAsync(sk->d_packed, sk->h_stage, packed_bytes, hipMemcpyHostToDevice, s));
+        if (int rc = sk->h_stage.grow(ctx, in.packed_bytes, 65536)) return rc;
+        std::memcpy(sk->h_stage, in.packed, in.packed_bytes);
+        D2G_HIP(ctx, hipMemcpyAsync(sk->d_packed, sk->h_stage, in.packed_bytes, hipMemcpyHostToDevice, s));
     }
-    out->packed = reinterpret_cast<const uint32_t *>(sk->d_packed.get());
-    out->run_start = reinterpret_cast<const uint64_t *>(sk->d_arena + o_rs);
-    out->run_len = reinterpret_cast<const uint32_t *>(sk->d_arena + o_rl);
-    out->run_chunk_off = reinterpret_cast<const uint64_t *>(sk->d_arena + o_co);
-    out->blk_genome = reinterpret_cast<const uint32_t *>(sk->d_arena + o_bg);
-    out->blk_chunk0 = reinterpret_cast<const uint64_t *>(sk->d_arena + o_c0);
-    out->blk_nchunks = reinterpret_cast<const uint32_t *>(sk->d_arena + o_bn);
-    out->blk_run_lo = reinterpret_cast<const uint32_t *>(sk->d_arena + o_lo);
-    out->blk_run_hi = reinterpret_cast<const uint32_t *>(sk->d_arena + o_hi);
-    out->k = k; out->canon = canon; out->blk0 = 0;
+    *out = d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon);
     d2g_filter_args(sk->filter, out);
     *nblk_out = nblk;
     return D2G_OK;

@@ -1222,8 +1222,10 @@ struct K3Host {
 
 int k3_layout_buckets(d2g_ctx *ctx, size_t n, K3Host &kh);
 // k-mers and launch-plan blocks per genome from the run table, then the bucket layout those k-mer counts ask for
-int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_off, size_t n, int k, K3Host &kh) {
+int k3_layout(d2g_ctx *ctx, const PackedRuns &in, K3Host &kh) {
     const d2g_k3_tuning &t = ctx->k3_tune;
+    const size_t n = in.n;
+    const int k = in.k;
     kh.gk.assign(n, 0);
     kh.gblk.assign(n + 1, 0);
     kh.hb = k > 16 ? (uint32_t)(2 * k - 32) : 0u;
@@ -1232,8 +1234,8 @@ int k3_layout(d2g_ctx *ctx, const uint32_t *run_len, const uint64_t *genome_run_
     kh.compact = t.compact && kh.hb <= (uint32_t)K3C_MAXBBITS;
     for (size_t g = 0; g < n; ++g) {
         uint64_t nk = 0, chunks = 0;
-        for (uint64_t r = genome_run_off[g]; r < genome_run_off[g + 1]; ++r) {
-            const uint64_t rk = (uint64_t)run_len[r] - k + 1;
+        for (uint64_t r = in.genome_run_off[g]; r < in.genome_run_off[g + 1]; ++r) {
+            const uint64_t rk = (uint64_t)in.run_len[r] - k + 1;
             nk += rk; chunks += div_up<uint64_t>(rk, K1_CHUNK);
         }
         D2G_CHECK(ctx, nk < (1ull << 32), "--multiset: more than 2^32 k-mers in one input");
@@ -1640,14 +1642,91 @@ int k3_check_status(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s) {
     return k3_status_error(ctx, status);
 }
 
-// what the sketcher's three entry points begin with: its work buffers, the batch staged on its stream, the bucket layout
-int k3_stage(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
-             size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon, K3Run &r) {
+// what the sketcher's three forms begin with: its work buffers, the batch staged on its stream, the bucket layout
+int k3_stage(d2g_sketcher *sk, const PackedRuns &in, K3Run &r) {
     if (!sk->k3) sk->k3 = new (std::nothrow) d2g_k3_state();
     if (!sk->k3) return D2G_ERR_NOMEM;
-    r.ctx = sk->ctx; r.st = sk->k3; r.s = sk->stream; r.n = n;
-    if (int rc = d2g_sketcher_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, &r.km, &r.nblk, nullptr)) return rc;
-    return k3_layout(r.ctx, run_len, genome_run_off, n, k, r.kh);
+    r.ctx = sk->ctx; r.st = sk->k3; r.s = sk->stream; r.n = in.n;
+    if (int rc = d2g_sketcher_stage(sk, in, &r.km, &r.nblk, nullptr)) return rc;
+    return k3_layout(r.ctx, in, r.kh);
+}
+
+int sketcher_run_bmh(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, double count_threshold, double *sig_out,
+                     double *total_weight_out) {
+    if (!sk) return D2G_ERR_INVALID;
+    d2g_ctx *ctx = sk->ctx;
+    const size_t n = in.n;
+    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 24), "sketchsize out of range");
+    D2G_CHECK(ctx, (sig_out && total_weight_out) || n == 0, "null output");
+    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
+    K3Run r;
+    if (int rc = k3_stage(sk, in, r)) return rc;
+    if (n == 0) return D2G_OK;
+    r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
+    if (int rc = r.run(K3Mode::Sketch)) return rc;
+    D2G_HIP(ctx, hipMemcpyAsync(sig_out, r.st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToHost, r.s));
+    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out, r.st->d_tw, n * sizeof(double), hipMemcpyDeviceToHost, r.s));
+    return k3_check_status(ctx, r.st, r.s);
+}
+
+int sketcher_run_distinct(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, uint64_t *ndistinct_out) {
+    if (!sk) return D2G_ERR_INVALID;
+    d2g_ctx *ctx = sk->ctx;
+    const size_t n = in.n;
+    D2G_CHECK(ctx, ndistinct_out != nullptr || n == 0, "null output");
+    K3Run r;
+    if (int rc = k3_stage(sk, in, r)) return rc;
+    if (n == 0) return D2G_OK;
+    const K3Host &kh = r.kh;
+    r.xormask = xormask;
+    if (int rc = r.run(K3Mode::Distinct)) return rc;
+    if (int rc = k3_check_status(ctx, r.st, r.s)) return rc;
+    std::vector<uint32_t> nd(kh.TB);
+    D2G_HIP(ctx, hipMemcpyAsync(nd.data(), r.st->d_bucket_nd, kh.TB * sizeof(uint32_t), hipMemcpyDeviceToHost, r.s));
+    D2G_HIP(ctx, hipStreamSynchronize(r.s));
+    for (size_t g = 0; g < n; ++g) {
+        uint64_t t = 0;
+        for (uint32_t tb = kh.gtab[n + g]; tb < kh.gtab[n + g + 1]; ++tb) t += nd[tb];
+        ndistinct_out[g] = t;
+    }
+    return D2G_OK;
+}
+
+// the distinct (key, count) of every genome, compacted on the host (utility form, not the sketch path)
+int sketcher_kmer_count(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, double count_threshold, uint64_t *keys_out,
+                        uint32_t *counts_out, size_t cap, uint64_t *genome_off_out) {
+    d2g_ctx *ctx = sk->ctx;
+    const size_t n = in.n;
+    K3Run r;
+    if (int rc = k3_stage(sk, in, r)) return rc;
+    const K3Host &kh = r.kh; d2g_k3_state *st = r.st;
+    for (size_t g = 0; g <= n; ++g) genome_off_out[g] = 0;
+    if (n == 0) return D2G_OK;
+    r.xormask = xormask; r.thr = count_threshold;
+    if (int rc = r.run(K3Mode::Count)) return rc;
+    if (int rc = k3_check_status(ctx, st, r.s)) return rc;
+    std::vector<uint32_t> nd(kh.TB);
+    std::vector<uint64_t> boff((size_t)kh.TB + 1);
+    std::vector<uint64_t> hk(std::max<uint64_t>(kh.total, 1));
+    std::vector<uint32_t> hc(std::max<uint64_t>(kh.total, 1));
+    D2G_HIP(ctx, hipMemcpy(nd.data(), st->d_bucket_nd, kh.TB * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    D2G_HIP(ctx, hipMemcpy(boff.data(), st->d_bucket_off, ((size_t)kh.TB + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (kh.total) {
+        D2G_HIP(ctx, hipMemcpy(hk.data(), st->d_out_keys, kh.total * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        D2G_HIP(ctx, hipMemcpy(hc.data(), st->d_out_counts, kh.total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    size_t w = 0;
+    for (size_t g = 0; g < n; ++g) {
+        genome_off_out[g] = w;
+        for (uint32_t tb = kh.gtab[n + g]; tb < kh.gtab[n + g + 1]; ++tb) {
+            D2G_CHECK(ctx, w + nd[tb] <= cap, "d2g_kmer_count: output capacity too small");
+            std::memcpy(keys_out + w, hk.data() + boff[tb], nd[tb] * sizeof(uint64_t));
+            std::memcpy(counts_out + w, hc.data() + boff[tb], nd[tb] * sizeof(uint32_t));
+            w += nd[tb];
+        }
+    }
+    genome_off_out[n] = w;
+    return D2G_OK;
 }
 
 }  // namespace
@@ -1658,19 +1737,8 @@ int d2g_sketcher_run_bmh(d2g_sketcher *sk, const uint8_t *packed, size_t packed_
                          const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                          uint64_t xormask, size_t sketchsize, double count_threshold, double *sig_out,
                          double *total_weight_out) {
-    if (!sk) return D2G_ERR_INVALID;
-    d2g_ctx *ctx = sk->ctx;
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 24), "sketchsize out of range");
-    D2G_CHECK(ctx, (sig_out && total_weight_out) || n == 0, "null output");
-    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
-    K3Run r;
-    if (int rc = k3_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, r)) return rc;
-    if (n == 0) return D2G_OK;
-    r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
-    if (int rc = r.run(K3Mode::Sketch)) return rc;
-    D2G_HIP(ctx, hipMemcpyAsync(sig_out, r.st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToHost, r.s));
-    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out, r.st->d_tw, n * sizeof(double), hipMemcpyDeviceToHost, r.s));
-    return k3_check_status(ctx, r.st, r.s);
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return sketcher_run_bmh(sk, in, xormask, sketchsize, count_threshold, sig_out, total_weight_out);
 }
 
 int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
@@ -1689,7 +1757,7 @@ int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pa
     const size_t n = plan->n;
     K3Run r;
     r.ctx = ctx; r.st = ctx->k3; r.s = as_stream(stream); r.n = n;
-    if (int rc = k3_layout(ctx, plan->h_run_len.data(), plan->h_genome_run_off.data(), n, plan->k, r.kh)) return rc;
+    if (int rc = k3_layout(ctx, plan->runs(canon), r.kh)) return rc;
     if (n == 0) return D2G_OK;
     r.km = d2g_plan_args(plan, packed_dev, canon); r.nblk = plan->nblk;
     r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
@@ -1702,99 +1770,37 @@ int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pa
 int d2g_bmh_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                    const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                    uint64_t xormask, size_t sketchsize, double count_threshold, double *sig_out, double *total_weight_out) {
-    if (!ctx) return D2G_ERR_INVALID;
-    d2g_sketcher *sk = nullptr;
-    if (int rc = d2g_sketcher_create(ctx, &sk)) return rc;
-    const int rc = d2g_sketcher_run_bmh(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon,
-                                        xormask, sketchsize, count_threshold, sig_out, total_weight_out);
-    d2g_sketcher_destroy(sk);
-    return rc;
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) {
+        return sketcher_run_bmh(sk, in, xormask, sketchsize, count_threshold, sig_out, total_weight_out);
+    });
 }
 
 int d2g_sketcher_run_distinct(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                               const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                               uint64_t xormask, uint64_t *ndistinct_out) {
-    if (!sk) return D2G_ERR_INVALID;
-    d2g_ctx *ctx = sk->ctx;
-    D2G_CHECK(ctx, ndistinct_out != nullptr || n == 0, "null output");
-    K3Run r;
-    if (int rc = k3_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, r)) return rc;
-    if (n == 0) return D2G_OK;
-    const K3Host &kh = r.kh;
-    r.xormask = xormask;
-    if (int rc = r.run(K3Mode::Distinct)) return rc;
-    if (int rc = k3_check_status(ctx, r.st, r.s)) return rc;
-    std::vector<uint32_t> nd(kh.TB);
-    D2G_HIP(ctx, hipMemcpyAsync(nd.data(), r.st->d_bucket_nd, kh.TB * sizeof(uint32_t), hipMemcpyDeviceToHost, r.s));
-    D2G_HIP(ctx, hipStreamSynchronize(r.s));
-    for (size_t g = 0; g < n; ++g) {
-        uint64_t t = 0;
-        for (uint32_t tb = kh.gtab[n + g]; tb < kh.gtab[n + g + 1]; ++tb) t += nd[tb];
-        ndistinct_out[g] = t;
-    }
-    return D2G_OK;
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return sketcher_run_distinct(sk, in, xormask, ndistinct_out);
 }
 
 int d2g_kmer_distinct(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                       const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                       uint64_t xormask, uint64_t *ndistinct_out) {
-    if (!ctx) return D2G_ERR_INVALID;
-    d2g_sketcher *sk = nullptr;
-    if (int rc = d2g_sketcher_create(ctx, &sk)) return rc;
-    const int rc = d2g_sketcher_run_distinct(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon,
-                                             xormask, ndistinct_out);
-    d2g_sketcher_destroy(sk);
-    return rc;
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run_distinct(sk, in, xormask, ndistinct_out); });
 }
 
 int d2g_kmer_count(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                    const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                    uint64_t xormask, double count_threshold, uint64_t *keys_out, uint32_t *counts_out, size_t cap,
                    uint64_t *genome_off_out) {
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
     if (!ctx) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, genome_off_out != nullptr, "null genome_off_out");
     D2G_CHECK(ctx, cap == 0 || (keys_out && counts_out), "null output");
-    d2g_sketcher *sk = nullptr;
-    if (int rc = d2g_sketcher_create(ctx, &sk)) return rc;
-    int rc = D2G_OK;
-    do {
-        K3Run r;
-        if ((rc = k3_stage(sk, packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon, r))) break;
-        const K3Host &kh = r.kh; d2g_k3_state *st = r.st;
-        for (size_t g = 0; g <= n; ++g) genome_off_out[g] = 0;
-        if (n == 0) break;
-        r.xormask = xormask; r.thr = count_threshold;
-        if ((rc = r.run(K3Mode::Count))) break;
-        if ((rc = k3_check_status(ctx, st, r.s))) break;
-        // compact the per-bucket prefixes on the host (utility entry point, not the sketch path)
-        std::vector<uint32_t> nd(kh.TB);
-        std::vector<uint64_t> boff((size_t)kh.TB + 1);
-        hipError_t e;
-        if ((e = hipMemcpy(nd.data(), st->d_bucket_nd, kh.TB * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess ||
-            (e = hipMemcpy(boff.data(), st->d_bucket_off, ((size_t)kh.TB + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess) {
-            ctx->last_error = hipGetErrorString(e); rc = D2G_ERR_HIP; break;
-        }
-        std::vector<uint64_t> hk(std::max<uint64_t>(kh.total, 1));
-        std::vector<uint32_t> hc(std::max<uint64_t>(kh.total, 1));
-        if (kh.total &&
-            ((e = hipMemcpy(hk.data(), st->d_out_keys, kh.total * sizeof(uint64_t), hipMemcpyDeviceToHost)) != hipSuccess ||
-             (e = hipMemcpy(hc.data(), st->d_out_counts, kh.total * sizeof(uint32_t), hipMemcpyDeviceToHost)) != hipSuccess)) {
-            ctx->last_error = hipGetErrorString(e); rc = D2G_ERR_HIP; break;
-        }
-        size_t w = 0;
-        for (size_t g = 0; g < n && rc == D2G_OK; ++g) {
-            genome_off_out[g] = w;
-            for (uint32_t tb = kh.gtab[n + g]; tb < kh.gtab[n + g + 1]; ++tb) {
-                if (w + nd[tb] > cap) { ctx->last_error = "d2g_kmer_count: output capacity too small"; rc = D2G_ERR_INVALID; break; }
-                std::memcpy(keys_out + w, hk.data() + boff[tb], nd[tb] * sizeof(uint64_t));
-                std::memcpy(counts_out + w, hc.data() + boff[tb], nd[tb] * sizeof(uint32_t));
-                w += nd[tb];
-            }
-        }
-        genome_off_out[n] = w;
-    } while (0);
-    d2g_sketcher_destroy(sk);
-    return rc;
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) {
+        return sketcher_kmer_count(sk, in, xormask, count_threshold, keys_out, counts_out, cap, genome_off_out);
+    });
 }
 
 // Every host-side check of the weights of explicit sets, without a context.  The last one keeps the walk finite: a set's first guess of

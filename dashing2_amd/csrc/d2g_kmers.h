@@ -2,11 +2,7 @@
 // the reference's bns::Encoder::for_each over 2-bit packed runs (call site src/fastxsketch.cpp:416-417).
 #pragma once
 #include "d2g_internal.h"
-
-constexpr int K1_THREADS = 256;
-constexpr int K1_CHUNK = 64;          // k-mers per lane-chunk
-constexpr int K1_CPT = 4;             // chunks per lane (16 measured 3% slower: fewer, longer workgroups)
-constexpr int K1_BLOCK_CHUNKS = K1_THREADS * K1_CPT;
+#include "d2g_plan.h"                 // K1_THREADS, K1_CHUNK, K1_CPT, K1_BLOCK_CHUNKS: the geometry the plan is built for
 
 // Thomas Wang's 64-bit mix (sketch::hash::WangHash::hash; call sites src/enums.h:138, src/oph.h:49)
 __device__ __forceinline__ uint64_t wang64(uint64_t k) {
@@ -21,7 +17,7 @@ __device__ __forceinline__ uint64_t wang64(uint64_t k) {
 }
 
 // launch plan of one batch of genomes: 64-k-mer chunks per run, <= K1_BLOCK_CHUNKS chunks of ONE
-// genome per workgroup (built on the host by build_plan_host, d2g_k1.hip)
+// genome per workgroup (built on the host by d2g_plan_build, d2g_plan.cpp)
 struct KmerArgs {
     const uint32_t *packed;        // 16 bases per dword, base p at bits [2(p%16), +2)
     const uint64_t *run_start;

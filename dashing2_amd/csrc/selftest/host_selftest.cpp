@@ -2,7 +2,10 @@
 // densify, epilogues, partition) under AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize` in
 // dashing2_amd/csrc; the reference has the same kind of target: Makefile:102-103).  No GPU, no HIP: only the
 // functions that never touch a device.  Exit code 0 = no finding (the sanitizers abort on any).
+// Also the sketch side's input checks and launch plan (d2g_plan.cpp): the grid arithmetic whose indices the kernels trust.
 #include "../../../include/d2g.h"
+#include "../d2g_plan.h"
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -13,7 +16,156 @@
 
 #define REQUIRE(c) do { if (!(c)) { std::fprintf(stderr, "selftest failed: %s (line %d)\n", #c, __LINE__); return 1; } } while (0)
 
+// ---- the launch plan, by brute force against its own tables.  Runs lie back to back from base 0.
+struct Runs {
+    std::vector<uint64_t> rs, go;
+    std::vector<uint32_t> rl;
+    Runs(std::vector<uint32_t> lens, std::vector<uint64_t> off) : go(std::move(off)), rl(std::move(lens)) {
+        uint64_t at = 0;
+        for (uint32_t l : rl) { rs.push_back(at); at += l; }
+    }
+    PackedRuns view(int k, size_t packed_bytes = 0) const { return {nullptr, packed_bytes, rs.data(), rl.data(), rl.size(), go.data(), go.size() - 1, k, 1}; }
+};
+
+static int check_plan(const Runs &t, int k) {
+    const PackedRuns in = t.view(k);
+    PlanHost p;
+    std::string err;
+    REQUIRE(d2g_plan_build(in, p, err) == D2G_OK && err.empty());
+    const size_t nrun = in.nrun, nblk = p.bg.size();
+    REQUIRE(p.chunk_off.size() == nrun + 1 && p.chunk_off[0] == 0);
+    REQUIRE(p.bc0.size() == nblk && p.bn.size() == nblk && p.blo.size() == nblk && p.bhi.size() == nblk);
+    uint64_t nk = 0, nb = 0;
+    for (size_t r = 0; r < nrun; ++r) {
+        const uint64_t rk = (uint64_t)t.rl[r] - k + 1;
+        REQUIRE(p.chunk_off[r + 1] - p.chunk_off[r] == (rk + K1_CHUNK - 1) / K1_CHUNK);
+        nk += rk; nb += t.rl[r];
+    }
+    REQUIRE(p.nkmers == nk && p.nbases == nb);
+    size_t b = 0;
+    for (size_t g = 0; g < in.n; ++g) {                              // a genome's blocks tile its chunks in order: no gap, no overlap
+        uint64_t c = p.chunk_off[t.go[g]];
+        const uint64_t cend = p.chunk_off[t.go[g + 1]];
+        for (; c < cend; ++b) {
+            REQUIRE(b < nblk && p.bg[b] == g && p.bc0[b] == c);
+            REQUIRE(p.bn[b] >= 1 && p.bn[b] <= (uint32_t)K1_BLOCK_CHUNKS && c + p.bn[b] <= cend);
+            for (size_t r = 0; r < nrun; ++r) {                      // [run_lo, run_hi) = the runs that own one of its chunks
+                const bool owns = p.chunk_off[r] < c + p.bn[b] && p.chunk_off[r + 1] > c;
+                REQUIRE(owns == (r >= p.blo[b] && r < p.bhi[b]));
+            }
+            c += p.bn[b];
+        }
+        REQUIRE(c == cend);
+    }
+    REQUIRE(b == nblk);
+    // the tables through the one layout: an exactly-sized arena (a write past a piece's end into the next is a wrong read-back,
+    // past the last an ASan report)
+    const PlanLayout l = d2g_plan_layout(nrun, nblk);
+    std::vector<uint8_t> arena(l.total, 0xEE);
+    d2g_plan_fill(arena.data(), l, in, p);
+    auto same = [&](size_t at, const void *src, size_t bytes) { return bytes == 0 || std::memcmp(arena.data() + at, src, bytes) == 0; };
+    REQUIRE(same(l.run_start, t.rs.data(), nrun * 8) && same(l.run_len, t.rl.data(), nrun * 4) && same(l.run_chunk_off, p.chunk_off.data(), (nrun + 1) * 8));
+    REQUIRE(same(l.blk_chunk0, p.bc0.data(), nblk * 8) && same(l.blk_genome, p.bg.data(), nblk * 4) && same(l.blk_nchunks, p.bn.data(), nblk * 4));
+    REQUIRE(same(l.blk_run_lo, p.blo.data(), nblk * 4) && same(l.blk_run_hi, p.bhi.data(), nblk * 4));
+    return 0;
+}
+
+static int check_layout(size_t nrun, size_t nblk) {
+    const PlanLayout l = d2g_plan_layout(nrun, nblk);
+    const std::pair<size_t, size_t> pieces[8] = {{l.run_start, nrun * 8}, {l.run_chunk_off, (nrun + 1) * 8}, {l.blk_chunk0, nblk * 8}, {l.run_len, nrun * 4},
+                                                 {l.blk_genome, nblk * 4}, {l.blk_nchunks, nblk * 4}, {l.blk_run_lo, nblk * 4}, {l.blk_run_hi, nblk * 4}};
+    size_t end = 0;
+    for (const auto &pc : pieces) {                                  // 256-byte aligned, ascending, disjoint, inside total
+        REQUIRE(pc.first % 256 == 0 && pc.first >= end);
+        end = pc.first + pc.second;
+    }
+    REQUIRE(l.run_start == 0 && end <= l.total);
+    return 0;
+}
+
+static int plan_selftest() {
+    const int k = 31;
+    const uint32_t one = k, wg = K1_BLOCK_CHUNKS * K1_CHUNK;         // a run of one k-mer; the k-mers of a full workgroup
+    std::vector<Runs> seams = {
+        Runs({one}, {0, 1}),                                         // a run of exactly k bases
+        Runs({64 + k - 1, 65 + k - 1}, {0, 1, 2}),                   // 64 and 65 k-mers: one chunk, and one k-mer into a second
+        Runs({wg + k - 1, wg + 1 + k - 1}, {0, 1, 2}),               // exactly K1_BLOCK_CHUNKS chunks, and K1_BLOCK_CHUNKS + 1
+        Runs(std::vector<uint32_t>(3000, one), {0, 3000}),           // blocks of many runs; the last one short
+        Runs({1000 * 64 + k - 1, 100 * 64 + k - 1, one}, {0, 2, 3}), // the second run straddles two blocks
+        Runs({500, 77}, {0, 0, 1, 1, 2, 2}),                         // genomes without a run: first, in the middle, last
+        Runs({}, {0}),                                               // n = 0, nrun = 0
+        Runs({}, {0, 0, 0}),
+    };
+    for (const Runs &t : seams) if (check_plan(t, k)) return 1;
+    for (int kk : {1, 32}) {
+        if (check_plan(Runs({(uint32_t)kk, 32, 64 + (uint32_t)kk - 1, 64 + (uint32_t)kk, wg + (uint32_t)kk}, {0, 2, 2, 5}), kk)) return 1;
+    }
+    {   // the seams really are where the comments say
+        PlanHost p; std::string err;
+        REQUIRE(d2g_plan_build(seams[2].view(k), p, err) == D2G_OK && p.bg.size() == 3 && p.bn[0] == 1024 && p.bn[1] == 1024 && p.bn[2] == 1);
+        PlanHost q;
+        REQUIRE(d2g_plan_build(seams[3].view(k), q, err) == D2G_OK && q.bg.size() == 3 && q.bhi[0] - q.blo[0] == 1024 && q.bn[2] == 3000 - 2048);
+        PlanHost s;
+        REQUIRE(d2g_plan_build(seams[4].view(k), s, err) == D2G_OK && s.bg.size() == 3 && s.bhi[0] == 2 && s.blo[1] == 1 && s.bg[2] == 1);
+    }
+    // refusals
+    {
+        const Runs t({100, 50}, {0, 1, 2});
+        PlanHost p; std::string err;
+        for (int bad : {0, 33, -1}) REQUIRE(d2g_plan_build(t.view(bad), p, err) == D2G_ERR_UNSUPPORTED && !err.empty());
+        REQUIRE(d2g_plan_build(Runs({100, 30}, {0, 1, 2}).view(31), p, err) == D2G_ERR_INVALID);     // a run shorter than k
+        REQUIRE(d2g_plan_build(Runs({100, 50}, {0, 1, 1}).view(31), p, err) == D2G_ERR_INVALID);     // genome_run_off[n] != nrun
+        REQUIRE(d2g_plan_build(Runs({100, 50}, {0, 1, 3}).view(31), p, err) == D2G_ERR_INVALID);
+        REQUIRE(d2g_plan_build(Runs({100, 50}, {0, 2, 1, 2}).view(31), p, err) == D2G_ERR_INVALID);  // not monotone
+        PackedRuns in = t.view(31);
+        in.genome_run_off = nullptr;
+        REQUIRE(d2g_plan_build(in, p, err) == D2G_ERR_INVALID);
+        in = t.view(31); in.run_len = nullptr;
+        REQUIRE(d2g_plan_build(in, p, err) == D2G_ERR_INVALID);
+        in = t.view(31); in.run_start = nullptr;
+        REQUIRE(d2g_plan_build(in, p, err) == D2G_ERR_INVALID);
+        const Runs none({}, {0, 0});                                                                 // no run: no run table is needed
+        in = none.view(31); in.run_len = nullptr; in.run_start = nullptr;
+        PlanHost e;
+        REQUIRE(d2g_plan_build(in, e, err) == D2G_OK && e.bg.empty());
+    }
+    // the tail pad: 64 bytes behind the byte of the last base, wherever in its byte that base lies; the LONGEST reach counts
+    for (uint32_t len : {41u, 42u, 44u}) {                           // last base at 0, 1, 3 modulo 4
+        const Runs t({len}, {0, 1});
+        const size_t need = (len + 3) / 4 + 64;
+        std::string err;
+        REQUIRE(d2g_plan_check_tail(t.view(1, need), err) == D2G_OK && err.empty());
+        REQUIRE(d2g_plan_check_tail(t.view(1, need - 1), err) == D2G_ERR_INVALID && !err.empty());
+        Runs back({8, len}, {0, 2});                                 // the run that reaches furthest is listed first
+        back.rs = {len, 0};
+        REQUIRE(d2g_plan_check_tail(back.view(1, (len + 8 + 3) / 4 + 64), err) == D2G_OK);
+        REQUIRE(d2g_plan_check_tail(back.view(1, (len + 8 + 3) / 4 + 63), err) == D2G_ERR_INVALID);
+    }
+    {
+        std::string err;
+        REQUIRE(d2g_plan_check_tail(Runs({}, {0, 0}).view(31, 0), err) == D2G_OK);
+    }
+    // the count range: 2^32 - 1 k-mers in a genome pass, 2^32 are refused; tables the builder rejects are left to it
+    {
+        std::string err;
+        const uint32_t half = 1u << 31;
+        REQUIRE(d2g_plan_check_count_range(Runs({half, half - 1}, {0, 2}).view(1), err) == D2G_OK && err.empty());
+        REQUIRE(d2g_plan_check_count_range(Runs({half, half}, {0, 2}).view(1), err) == D2G_ERR_UNSUPPORTED && err.find("2^32") != std::string::npos);
+        REQUIRE(d2g_plan_check_count_range(Runs({half, half}, {0, 1, 2}).view(1), err) == D2G_OK);   // two genomes of 2^31
+        const Runs big({half, half}, {0, 2});
+        PackedRuns in = big.view(1);
+        in.run_len = nullptr;
+        REQUIRE(d2g_plan_check_count_range(in, err) == D2G_OK);
+        in.genome_run_off = nullptr;
+        REQUIRE(d2g_plan_check_count_range(in, err) == D2G_OK);
+    }
+    for (size_t nrun : {0, 1, 31, 32, 33, 3000})
+        for (size_t nblk : {0, 1, 63, 64, 65, 1030}) if (check_layout(nrun, nblk)) return 1;
+    return 0;
+}
+
 int main() {
+    if (plan_selftest()) return 1;
     std::mt19937_64 rng(7);
     // ---- seqpack: messy FASTA / FASTQ, lower case, N runs, short records, CRLF, no trailing newline, every k
     std::string fa;

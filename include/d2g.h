@@ -231,6 +231,8 @@ uint64_t        d2g_seqpack_nbases(const d2g_seqpack *sp);           /* bases st
  *   genome_run_off [n+1] runs of genome g are [genome_run_off[g], genome_run_off[g+1])
  * k-mers never span runs (window resets at non-ACGT bytes and record boundaries).
  * Output: regs_out[n][m] (m = d2g_oph_m(S)), each register = min OPH id of its bucket or ~0.
+ * This and the other host-pointer one-shots (d2g_oph_sketch_counts, d2g_kmer_filter_create, d2g_bmh_sketch, d2g_kmer_count,
+ * d2g_kmer_distinct) are the d2g_sketcher form of the call on a sketcher that lives for that call: convenient, not for loops.
  */
 int d2g_oph_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
                    const uint64_t *run_start, const uint32_t *run_len, size_t nrun,

@@ -3,7 +3,7 @@ and d2g_bmh_sketch_dev -- against the expected values of sketch_dev_cases.py, wh
 compared bit for bit (BagMinHash registers as uint64).
 
 What these forms do not share with the host-pointer and sketcher forms, and what is aimed at it here:
-    launch tables    the plan's eight device buffers, re-used over other packed buffers and other base pointers (b, d)
+    launch tables    the plan's device copy of them, re-used over other packed buffers and other base pointers (b, d)
     stream           the caller's, null or not; K1 and the count pass do not synchronise.  Every case runs on the null stream and on a
                      torch side stream.  On the side stream the library is called while the stream is still busy and the packed buffer
                      still holds ANOTHER input: the copy of the right input is queued on that stream just before the call, and the
@@ -126,6 +126,32 @@ def assert_k3(got, exp, what):
     np.testing.assert_array_equal(got[0].view(np.uint64), exp[0].view(np.uint64), err_msg=what + ": registers")
 
 
+class AsSeqPack:
+    """a layout where a Sketcher's run* and Context.kmer_filter want a SeqPack"""
+
+    def __init__(self, lay, k):
+        self.lay, self.k = lay, k
+
+    def arrays(self):
+        return (np.array(self.lay.packed),) + tuple(np.array(a) for a in self.lay.tables())
+
+
+def assert_host_forms(gpu_ctx, lay, k, S, canon, xormask, exp, what):
+    """the host-pointer forms of K1 over the layout's own arrays -- the one-shots d2g_oph_sketch and d2g_oph_sketch_counts, and
+    d2g_sketcher_run and d2g_sketcher_run_counts on one sketcher -- against the expected (registers, counts), bit for bit"""
+    sp = AsSeqPack(lay, k)
+    sk = gpu_ctx.sketcher()
+    got = [("d2g_oph_sketch", gpu_ctx.oph_sketch(lay.packed, *lay.tables(), k, S, canon=canon, xormask=xormask), None),
+           ("d2g_oph_sketch_counts",) + gpu_ctx.oph_sketch_counts(lay.packed, *lay.tables(), k, S, canon=canon, xormask=xormask),
+           ("d2g_sketcher_run", sk.run(sp, S, canon, xormask), None),
+           ("d2g_sketcher_run_counts",) + sk.run_counts(sp, S, canon, xormask)]
+    sk.close()
+    for form, regs, cnts in got:
+        np.testing.assert_array_equal(regs, exp[0], err_msg=f"{what}: {form}: registers")
+        if cnts is not None:
+            np.testing.assert_array_equal(cnts, exp[1], err_msg=f"{what}: {form}: counts")
+
+
 # ---------------------------------------------------------------- a. K1 at the plan's seams
 @pytest.mark.parametrize("xormask", [0, V.SEEDED], ids=["mask0", "seeded"])
 @pytest.mark.parametrize("canon", [True, False], ids=["canon", "fwd"])
@@ -133,7 +159,7 @@ def assert_k3(got, exp, what):
 def test_k1_at_the_plans_seams(gpu_ctx, torch, side, k, canon, xormask):
     """genomes of 1, 63, 64, 65, 65 536, 65 537 and 131 073 k-mers (a lane chunk, a workgroup's share, three workgroups that merge in
     HBM) at m = 1000, 1024, 16 384 (the last in LDS), 16 386 (the first in HBM and no power of two: k1_oph_kernel<false, false>) and
-    20 000; the count pass leaves LDS above m = 10 922.  At the two HBM sizes the host-pointer form takes the same input"""
+    20 000; the count pass leaves LDS above m = 10 922.  At the two HBM sizes the host-pointer forms take the same input"""
     lay, other = V.seams(k), V.seams(k, 3101)
     A, B = device_bytes(torch, lay.packed), device_bytes(torch, other.packed)
     plan = gpu_ctx.oph_plan(*lay.tables(), k)
@@ -143,8 +169,7 @@ def test_k1_at_the_plans_seams(gpu_ctx, torch, side, k, canon, xormask):
         got = run_k1(gpu_ctx, torch, side, plan, lay.n, A, B, S, canon, xormask)
         assert_k1(got, exp, f"{lay} S {S}")
         if S > 16384 and side is None:
-            host = gpu_ctx.oph_sketch(lay.packed, *lay.tables(), k, S, canon=canon, xormask=xormask)
-            np.testing.assert_array_equal(host, exp[0], err_msg=f"{lay} S {S}: d2g_oph_sketch")
+            assert_host_forms(gpu_ctx, lay, k, S, canon, xormask, exp, f"{lay} S {S}")
     plan.close()
 
 
@@ -159,6 +184,38 @@ def test_k1_through_other_tables_over_the_same_bytes(gpu_ctx, torch, side, which
     for S, canon, xormask in ((1000, True, V.SEEDED), (16385, False, 0)):
         got = run_k1(gpu_ctx, torch, side, plan, lay.n, A, B, S, canon, xormask)
         assert_k1(got, lay.oph(k, canon, xormask, S), f"{lay} S {S}")
+    plan.close()
+
+
+FRONT_DOORS = [(lambda w=w: V.variant(w, 31), 31, V.SEEDED) for w in V.VARIANTS] + [
+    (V.multiset_slots, V.K3_K, 0), (lambda: V.k3_reuse_step(1), V.K3_K, 0), (lambda: V.nothing(3), V.K3_K, 0)]
+
+
+@pytest.mark.parametrize("case", FRONT_DOORS, ids=list(V.VARIANTS) + ["multiset_slots", "one_and_none", "nothing3"])
+def test_every_front_door_gives_the_same(gpu_ctx, torch, case):
+    """one layout through every way in.  K1: the one-shots, a sketcher and plan + *_dev give the layout's own expected registers and
+    counts, so the same bits as each other, at S = 64 and S = 1000.  The filter: d2g_kmer_filter_create and plan +
+    d2g_kmer_filter_create_dev over the same runs hold the same set -- the occurrences and distinct k-mers that the layout's bases
+    hold, every one of its k-mers and none of 64 that it does not hold"""
+    make, k, xormask = case
+    lay, canon = make(), True
+    A = device_bytes(torch, lay.packed)
+    plan = gpu_ctx.oph_plan(*lay.tables(), k)
+    for S in (64, 1000):
+        exp = lay.oph(k, canon, xormask, S)
+        assert_k1(run_k1(gpu_ctx, torch, None, plan, lay.n, A, None, S, canon, xormask), exp, f"{lay} S {S}: plan + dev")
+        assert_host_forms(gpu_ctx, lay, k, S, canon, xormask, exp, f"{lay} S {S}")
+    kmers = np.concatenate([V.kmers_np(lay.run_codes(r), k, canon) for r in range(lay.nrun)] + [np.zeros(0, np.uint64)])
+    held = np.unique(kmers)
+    absent = np.random.default_rng(3800).integers(0, 1 << (2 * k), 80, dtype=np.uint64)
+    absent = absent[~np.isin(absent, held)][:64]
+    assert absent.size == 64
+    ask = np.concatenate([kmers, absent])
+    filters = [gpu_ctx.kmer_filter(AsSeqPack(lay, k), canon), gpu_ctx.kmer_filter_dev(plan, A.data_ptr(), canon)]
+    for f, form in zip(filters, ("d2g_kmer_filter_create", "plan + d2g_kmer_filter_create_dev")):
+        assert f.info()[:2] == (kmers.size, held.size), f"{lay}: {form}"
+        np.testing.assert_array_equal(f.contains(ask), np.arange(ask.size) < kmers.size, err_msg=f"{lay}: {form}")
+        f.close()
     plan.close()
 
 
@@ -218,16 +275,6 @@ def test_k3_through_other_tables_over_the_same_bytes(gpu_ctx, torch, side, which
         got = run_k3(gpu_ctx, torch, side, plan, lay.n, A, B, S, thr, canon=canon, xormask=xormask)
         assert_k3(got, lay.bmh(k, canon, xormask, S, thr), f"{lay} S {S} threshold {thr} canon {canon}")
     plan.close()
-
-
-class AsSeqPack:
-    """a layout where Sketcher.run_bmh wants a SeqPack"""
-
-    def __init__(self, lay, k):
-        self.lay, self.k = lay, k
-
-    def arrays(self):
-        return (np.array(self.lay.packed),) + tuple(np.array(a) for a in self.lay.tables())
 
 
 def test_k3_work_state_is_reused_by_every_call(gpu_ctx, torch):
