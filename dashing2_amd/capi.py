@@ -106,6 +106,9 @@ SIGNATURES = {
     "d2g_oph_count_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, _vp, _vp, _vp]),
     "d2g_oph_sketch_counts": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp, _vp]),
     "d2g_sketcher_run_counts": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp, _vp]),
+    "d2g_oph_sketch_mincount": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, C.c_uint32, _vp, _vp]),
+    "d2g_sketcher_run_mincount": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, C.c_uint32, _vp, _vp]),
+    "d2g_oph_sketch_mincount_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, C.c_uint32, _vp, _vp]),
     "d2g_kmer_filter_create_dev": (_int, [_vp, _vp, _vp, _int, _vp, C.POINTER(_vp)]),
     "d2g_kmer_filter_create": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _int, _int, C.POINTER(_vp)]),
     "d2g_kmer_filter_destroy": (None, [_vp]),
@@ -639,6 +642,21 @@ class Context:
         packed, rs, rl, go = sp.arrays()
         return self.oph_sketch_counts(packed, rs, rl, go, sp.k, S, canon, xormask)
 
+    def oph_sketch_mincount_seqpack(self, sp: SeqPack, S, mincount, canon=True, xormask=0, counts=False):
+        """One-Permutation registers over the k-mers seen at least `mincount` times (sketch -m; mincount < 2: the plain sketch)
+        -> regs u64 [n][m], or (regs, counts u32 [n][m]) with counts=True"""
+        packed, rs, rl, go = sp.arrays()
+        n = go.size - 1
+        regs = np.empty((n, oph_m(S)), np.uint64)
+        cnts = np.empty((n, oph_m(S)), np.uint32) if counts else None
+        self._check(lib().d2g_oph_sketch_mincount(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
+                                                  sp.k, int(canon), xormask, S, mincount, _np_ptr(regs), _np_ptr(cnts) if counts else None))
+        return (regs, cnts) if counts else regs
+
+    def oph_sketch_mincount_dev(self, plan, packed_dev_ptr, S, mincount, regs_dev_ptr, canon=True, xormask=0, stream=None):
+        """the device-resident form; synchronises `stream`.  Counts: oph_count_dev over regs_dev_ptr"""
+        self._check(lib().d2g_oph_sketch_mincount_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, mincount, regs_dev_ptr, stream))
+
     def sketcher(self):
         return Sketcher(self)
 
@@ -922,6 +940,26 @@ class Sketcher:
         self.ctx._check(lib().d2g_sketcher_run_counts(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
                                                       self.k if k is None else k, int(canon), xormask, S, _np_ptr(regs), _np_ptr(counts)))
         return regs, counts
+
+    def _run_mincount(self, packed, nbytes, rs, rl, go, k, S, mincount, canon, xormask, counts):
+        n = go.size - 1
+        regs = np.empty((n, oph_m(S)), np.uint64)
+        cnts = np.empty((n, oph_m(S)), np.uint32) if counts else None
+        self.ctx._check(lib().d2g_sketcher_run_mincount(self._h, packed, nbytes, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n, k,
+                                                        int(canon), xormask, S, mincount, _np_ptr(regs), _np_ptr(cnts) if counts else None))
+        return (regs, cnts) if counts else regs
+
+    def run_mincount(self, sp, S, mincount, canon=True, xormask=0, counts=False):
+        """registers over the k-mers seen at least `mincount` times (mincount < 2: run / run_counts) -> regs u64 [n][m], or
+        (regs, counts u32 [n][m]) with counts=True"""
+        packed, rs, rl, go = sp.arrays()
+        return self._run_mincount(_np_ptr(packed), packed.size, rs, rl, go, sp.k, S, mincount, canon, xormask, counts)
+
+    def run_mincount_ingested(self, runs, S, mincount, canon=True, xormask=0, counts=False, k=None):
+        """run_mincount over the stream ingested last (packed == NULL)"""
+        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
+                      np.ascontiguousarray(runs[2], np.uint64))
+        return self._run_mincount(None, 0, rs, rl, go, self.k if k is None else k, S, mincount, canon, xormask, counts)
 
     def run_bmh(self, sp, S, canon=True, xormask=0, count_threshold=0.0):
         packed, rs, rl, go = sp.arrays()

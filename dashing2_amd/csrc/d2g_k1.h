@@ -85,6 +85,11 @@ void d2g_k0_invalidate(d2g_sketcher *sk);
 // in.packed == nullptr: the stream d2g_sketcher_ingest_fasta left in the device buffer is used as it is.
 int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &in, KmerArgs *out, size_t *nblk, PlanHost *ph_out);
 
+// K3o (d2g_k3_bmh.hip) behind the min-count entry points of d2g_k1.hip: the batch is staged (or a plan applied) and `regs_dev` [n][m]
+// pre-set to ~0 on `s`; lowers the registers over the k-mers seen at least `mincount` (>= 2) times, waits for the status word
+int d2g_k3_ophmin(d2g_ctx *ctx, d2g_k3_state **st, const PackedRuns &in, const KmerArgs &km, size_t nblk, uint64_t xormask, size_t m,
+                  uint32_t mincount, uint64_t *regs_dev, hipStream_t s);
+
 // A host-pointer one-shot is the sketcher form on a sketcher that lives for one call: f(sk), and the sketcher goes on every path.
 template <class F> int d2g_with_sketcher(d2g_ctx *ctx, F &&f) {
     if (!ctx) return D2G_ERR_INVALID;

@@ -192,6 +192,38 @@ int sketcher_run(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_
     return D2G_OK;
 }
 
+// sketch -m c: registers over the k-mers seen at least `mincount` times (K3o, d2g_k3_bmh.hip), then -- counts_out given -- K1b over
+// those registers: LazyOnePermSetSketch's counts_ under set_mincount (oph.h:188-205) is what K1b defines for any registers.
+// mincount < 2 is the plain sketch (set_mincount only takes effect above 1: oph.h:154-159)
+int sketcher_run_mincount(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out,
+                          uint32_t *counts_out) {
+    if (!sk) return D2G_ERR_INVALID;
+    const bool counts = counts_out != nullptr;
+    if (mincount < 2) return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, counts);
+    d2g_ctx *ctx = sk->ctx;
+    const size_t n = in.n;
+    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    D2G_CHECK(ctx, regs_out != nullptr || n == 0, "null regs_out");
+    if (counts) {
+        std::string err;
+        if (int rc = d2g_plan_err(ctx, d2g_plan_check_count_range(in, err), err)) return rc;
+    }
+    KmerArgs km;
+    size_t nblk = 0;
+    if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, nullptr)) return rc;
+    const size_t m = d2g_oph_m(sketchsize), nm = std::max<size_t>(n * m, 1);
+    if (int rc = sk->d_regs.grow(ctx, nm, 4096)) return rc;
+    if (counts) if (int rc = sk->d_counts.grow(ctx, nm, 4096)) return rc;
+    hipStream_t s = sk->stream;
+    D2G_HIP(ctx, hipMemsetAsync(sk->d_regs, 0xFF, n * m * sizeof(uint64_t), s));
+    if (nblk) if (int rc = d2g_k3_ophmin(ctx, &sk->k3, in, km, nblk, xormask, m, mincount, sk->d_regs, s)) return rc;
+    if (counts) if (int rc = k1_fill_counts(ctx, km, nblk, n, m, xormask, sk->d_regs, sk->d_counts, s)) return rc;
+    if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    if (n && counts) D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipStreamSynchronize(s));
+    return D2G_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -249,6 +281,25 @@ int d2g_oph_count_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pac
                           counts_out_dev, as_stream(stream));
 }
 
+int d2g_oph_sketch_mincount_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
+                                size_t sketchsize, uint32_t mincount, uint64_t *regs_out_dev, void *stream) {
+    if (!ctx || !plan) return D2G_ERR_INVALID;
+    if (int rc = check_dev_call(ctx, plan, packed_dev, canon, sketchsize)) return rc;
+    D2G_CHECK(ctx, regs_out_dev != nullptr || plan->n == 0, "null regs_out");
+    D2G_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = as_stream(stream);
+    const size_t m = d2g_oph_m(sketchsize);
+    const KmerArgs km = d2g_plan_args(plan, packed_dev, canon);
+    if (mincount < 2) {
+        if (int rc = k1_fill_regs(ctx, km, plan->nblk, plan->n, m, xormask, regs_out_dev, s)) return rc;
+    } else {
+        D2G_HIP(ctx, hipMemsetAsync(regs_out_dev, 0xFF, plan->n * m * sizeof(uint64_t), s));
+        if (plan->nblk) return d2g_k3_ophmin(ctx, &ctx->k3, plan->runs(canon), km, plan->nblk, xormask, m, mincount, regs_out_dev, s);
+    }
+    D2G_HIP(ctx, hipStreamSynchronize(s));
+    return D2G_OK;
+}
+
 void d2g_sketcher_destroy(d2g_sketcher *sk) {
     if (!sk) return;
     (void)hipSetDevice(sk->ctx->device);
@@ -297,6 +348,22 @@ int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_byt
                           int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
     return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, true); });
+}
+
+int d2g_sketcher_run_mincount(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                              const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
+                              uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out, uint32_t *counts_out) {
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return sketcher_run_mincount(sk, in, xormask, sketchsize, mincount, regs_out, counts_out);
+}
+
+int d2g_oph_sketch_mincount(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                            const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
+                            uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out, uint32_t *counts_out) {
+    const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) {
+        return sketcher_run_mincount(sk, in, xormask, sketchsize, mincount, regs_out, counts_out);
+    });
 }
 
 }  // extern "C"

@@ -1093,6 +1093,60 @@ __global__ __launch_bounds__(K3_THREADS) void k3_count_kernel(BmhArgs a) {
     if (tid == 0) a.bucket_nd[tb] = sh.misc;
 }
 
+// K3o (sketch -m c, set space): One-Permutation registers over the k-mers that occur at least c times.  LazyOnePermSetSketch::update
+// under set_mincount(c) (reference src/oph.h:154-159,188-205) ends, whatever the order of the k-mers, with register r = the smallest OPH
+// id among the DISTINCT k-mers that map to r and occur >= c times (~0 if none): an id is counted for as long as the register is above
+// it, and can never win once the register is at or below it.  So the bucket walk of k3_count_kernel selects (the host passes
+// thr = c - 1: for integer counts `count > c - 1` is `count >= c`), and every survivor lowers its register with
+// global_atomic_umin_x2 behind a plain read, as k3_bmh_main_kernel does.  No LDS stage in front of the atomics: a genome's buckets
+// are walked by as many workgroups, each sees ~1/B of the survivors, and of D survivors only ~m ln(D / m) pass the read filter at all.
+struct OphMinArgs {
+    BmhArgs b;                   // h = the registers [n][m], pre-set to ~0; thr = c - 1; m = d2g_oph_m(S)
+    uint64_t ophxor;             // d2g_oph_xor_const()
+};
+
+template <bool C32>
+__global__ __launch_bounds__(K3_THREADS) void k3_ophmin_kernel(OphMinArgs oa) {
+    typedef typename K3Key<C32>::T KT;
+    __shared__ SharedK3<C32> sh;
+    const BmhArgs &a = oa.b;
+    const int tid = threadIdx.x;
+    const uint32_t tb = blockIdx.x;
+    const uint64_t o0 = a.bucket_off[tb], nk = a.bucket_off[tb + 1] - o0;
+    if (nk == 0) return;
+    const CountTab<C32> t{sh.key, sh.cnt, &sh.ones};
+    const uint32_t g = genome_of_bucket(a.g_boff, a.n, tb);
+    const uint32_t sbits = a.g_split ? a.g_split[g] : 0u;
+    const uint32_t bb = C32 ? a.g_bbits[g] : 0u;
+    const uint32_t nranges = 1u << sbits;
+    const uint64_t sub0 = sbits ? a.g_sub[g] + ((uint64_t)(tb - a.g_boff[g]) << sbits) : 0;
+    const uint32_t m = a.m;
+    const bool pow2 = (m & (m - 1)) == 0;
+    const uint64_t ophxor = oa.ophxor;
+    uint64_t *hg = a.h + (size_t)g * m;
+    for (uint32_t rg = 0; rg < nranges; ++rg) {
+        const uint64_t lo = sbits ? a.sub_off[sub0 + rg] : o0;
+        const uint64_t rn = sbits ? a.sub_off[sub0 + rg + 1] - lo : nk;
+        if (rn == 0) continue;
+        const KT *kb = (C32 ? (const KT *)(sbits ? a.skeys32 : a.keys32) : (const KT *)(sbits ? a.skeys : a.keys)) + lo;
+        uint32_t R = 1;
+        while ((uint64_t)R * a.round_keys < rn) R <<= 1;
+        for (uint32_t r = 0; r < R; ++r) {
+            if (!count_round<C32>(t, kb, rn, R, r, sbits, bb)) { if (tid == 0) atomicExch(a.status, K3_TABLE_OVERFLOW); return; }
+            const uint32_t ne = compact_elements<C32>(t, &sh.nelem, a.thr);
+            for (uint32_t e = tid; e < ne; e += K3_THREADS) {
+                uint64_t key;
+                if constexpr (C32) key = wang64(k3c_kmer(sh.key[e], tb - a.g_boff[g], bb, a.hb) ^ a.xormask);
+                else key = sh.key[e];
+                const uint64_t id = wang64(key ^ ophxor);                 // DHasher: oph.h:44-53
+                const uint32_t idx = pow2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);   // oph.h:184, as K1
+                if (id < hg[idx]) atomicMin((unsigned long long *)&hg[idx], (unsigned long long)id);
+            }
+            __syncthreads();                                              // the next round clears the table
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // explicit weighted sets (wsketch.cpp:54-73 minwise_det / 17-51 rowwise CSR): elements come
 // from (id, weight) arrays instead of the count table
@@ -1296,7 +1350,9 @@ int k3_layout_buckets(d2g_ctx *ctx, size_t n, K3Host &kh) {
     return D2G_OK;
 }
 
-enum class K3Mode { Sketch, Count, Distinct };   // registers and total weights (R12) / distinct (key, count) per bucket (R11) / their number only
+// registers and total weights (R12) / distinct (key, count) per bucket (R11) / their number only / One-Permutation registers over the
+// k-mers counted at least thr + 1 times (K3o)
+enum class K3Mode { Sketch, Count, Distinct, OphMin };
 
 // count (R11) or sketch (R12) of one staged batch: what the caller fills in, the kernel arguments one stage prepares for the next, the stages
 struct K3Run {
@@ -1307,7 +1363,8 @@ struct K3Run {
     uint64_t key_words = 0;            // d_keys in 8-byte words: a masked key per k-mer on the generic path, a 4-byte stored word on the compact one
     K3Args ka{}; K3cArgs kc{};         // bucket(): the generic / the compact form
     BmhArgs b{};                       // split, count, sketch
-    int run(K3Mode mode), upload_tables(), bucket_prepare(), bucket(size_t g_lo, size_t g_hi), split(), count(K3Mode mode);
+    uint64_t *oph_regs = nullptr;      // OphMin: the caller's registers [n][m] (device), pre-set to ~0 on this stream
+    int run(K3Mode mode), upload_tables(), bucket_prepare(), bucket(size_t g_lo, size_t g_hi), split(), count(K3Mode mode), ophmin();
     int sketch(const std::vector<size_t> &sub), sketch_init(const std::vector<double> &guess), light_pass(const struct K3LightPlan &plan, bool pipeline);
     std::vector<size_t> subbatches(K3Mode mode) const;
     void init_registers() {            // registers to +inf, weights and redo flags to zero
@@ -1441,6 +1498,14 @@ int K3Run::count(K3Mode mode) {
     if (int rc = st->d_bucket_nd.grow(ctx, (size_t)kh.TB + 1, 4096)) return rc;
     b.bucket_nd = st->d_bucket_nd;
     if (kh.TB) hipLaunchKernelGGL(kh.compact ? k3_count_kernel<true> : k3_count_kernel<false>, dim3(kh.TB), dim3(K3_THREADS), 0, s, b);
+    return D2G_OK;
+}
+
+// K3o: one workgroup per bucket, as count(); the registers are the caller's
+int K3Run::ophmin() {
+    b.h = oph_regs;
+    const OphMinArgs oa{b, d2g_oph_xor_const()};
+    if (kh.TB) hipLaunchKernelGGL(kh.compact ? k3_ophmin_kernel<true> : k3_ophmin_kernel<false>, dim3(kh.TB), dim3(K3_THREADS), 0, s, oa);
     return D2G_OK;
 }
 
@@ -1622,7 +1687,7 @@ int K3Run::run(K3Mode mode) {
     b.bucket_off = st->d_bucket_off; b.g_boff = st->d_gtab + n;
     b.n = (uint32_t)n; b.TB = kh.TB; b.m = (uint32_t)m; b.thr = thr; b.status = st->d_status; b.round_keys = ctx->k3_tune.round_keys;
     if (int rc = split()) return rc;
-    if (int rc = mode == K3Mode::Sketch ? sketch(sub) : count(mode)) return rc;
+    if (int rc = mode == K3Mode::Sketch ? sketch(sub) : mode == K3Mode::OphMin ? ophmin() : count(mode)) return rc;
     tm.stop();
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
@@ -1730,6 +1795,22 @@ int sketcher_kmer_count(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask
 }
 
 }  // namespace
+
+// K3o behind the entry points of d2g_k1.hip: the batch is staged (or a plan applied) and `regs_dev` [n][m] pre-set to ~0 on `s`;
+// lowers the registers over the k-mers seen at least `mincount` (>= 2) times and waits for the status word.  `*st` is made on first use.
+int d2g_k3_ophmin(d2g_ctx *ctx, d2g_k3_state **st, const PackedRuns &in, const KmerArgs &km, size_t nblk, uint64_t xormask, size_t m,
+                  uint32_t mincount, uint64_t *regs_dev, hipStream_t s) {
+    if (!*st) *st = new (std::nothrow) d2g_k3_state();
+    if (!*st) return D2G_ERR_NOMEM;
+    K3Run r;
+    r.ctx = ctx; r.st = *st; r.s = s; r.n = in.n;
+    if (int rc = k3_layout(ctx, in, r.kh)) return rc;
+    if (in.n == 0) return D2G_OK;
+    r.km = km; r.nblk = nblk;
+    r.xormask = xormask; r.m = m; r.thr = (double)(mincount - 1); r.oph_regs = regs_dev;
+    if (int rc = r.run(K3Mode::OphMin)) return rc;
+    return k3_check_status(ctx, r.st, r.s);
+}
 
 extern "C" {
 

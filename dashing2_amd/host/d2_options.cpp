@@ -44,7 +44,10 @@ void sketch_usage() {
                          "  -F/--ffile paths.txt -Q/--qfile queries.txt  -o/--outfile stacked.bin\n"
                          "  --cmpout/--distout/--cmp-outfile out   --phylip   --binary-output   --asymmetric-all-pairs\n"
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
-                         "  --multiset/--bagminhash/-B [-m/--count-threshold c]   --parse-by-seq (one sketch per record of ONE file)\n"
+                         "  --multiset/--bagminhash/-B   --parse-by-seq (one sketch per record of ONE file)\n"
+                         "  -m/--count-threshold c   set sketches (OPH) of whole inputs: only k-mers seen at least c times are sketched (c < 2: all);\n"
+                         "                         with --multiset: only k-mers seen MORE than c times.  In set space not with --parse-by-seq or\n"
+                         "                         --presketched, and only where the sketches are written (-o, --cache or --cmpout)\n"
                          "  -s/--save-kmers        with -o out: out.kmer64 (24-byte header, then per input the masked k-mer behind each of its S\n"
                          "                         registers) and out.kmer64.names.txt; set sketches (OPH) only, not with --parse-by-seq\n"
                          "  -N/--save-kmercounts   -s, and out.kmercounts.f64: how often each of those k-mers occurred in its input (float32)\n"
@@ -262,9 +265,23 @@ int parse_options(int argc, char **argv, Options &o) {
     o.nq = o.paths.size() - nref;
     if (o.sspace != SPACE_SET && o.kmer_result == ONE_PERM) o.kmer_result = FULL_SETSKETCH;   // sketch_main.cpp:124-127
     if (o.sspace == SPACE_SET && o.count_threshold > 0) {
-        std::fprintf(stderr, "dashing2 (MI355X): -m/--count-threshold with set sketches (OPH min-count filtering, oph.h:186-205) "
-                             "is outside this build's hot-path scope; it is supported with --multiset.\n");
-        return 1 + 1;
+        // OPH min-count filtering (oph.h:186-205) is built for One-Permutation set sketches of whole inputs that are WRITTEN somewhere.
+        // What the parent refused and this build still does not do stays refused as it was:
+        const char *why = nullptr;
+        int status = 1;
+        if (o.presketched) why = "--presketched (nothing is sketched: the threshold belongs to the sketch job that wrote the file)";
+        else if (o.parse_by_seq) {
+            // under --parse-by-seq the reference replaces the cardinality of small sketches by the exact distinct count
+            // (fastxsketchbyseq.cpp:415-430), which has not been worked through with a min-count
+            why = "--parse-by-seq in set space (it is built for sketches of whole inputs)";
+            status = 2;                                       // a combination of accepted options, not an option out of scope (those leave with 1)
+        } else if (!o.is_cmp && o.outfile.empty() && o.cmpout.empty() && !o.cache)
+            why = "a sketch job that writes nothing (no -o, --cache or --cmpout: the counted sketches would be dropped)";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): -m/--count-threshold with set sketches (OPH min-count filtering, oph.h:186-205) together with %s "
+                                 "is outside this build's hot-path scope; it is supported with --multiset.\n", why);
+            return status + 1;
+        }
     }
     if (o.save_kmers && !o.presketched && (o.sspace != SPACE_SET || o.parse_by_seq)) {     // with --presketched nothing is sketched: ignored
         std::fprintf(stderr, "dashing2 (MI355X): %s together with %s is outside the hot-path scope of this build "

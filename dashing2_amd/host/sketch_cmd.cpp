@@ -205,7 +205,11 @@ struct DeviceSide {
                                             double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh");
         } else {
             f.regs.resize(n * d2g_oph_m(S));
-            if (count_kmers) {                                          // fastxsketch.cpp:590-591: idcounts()
+            if (o.count_threshold >= 2) {                               // fastxsketch.cpp:192: set_mincount(count_threshold_); with -N idcounts() too
+                if (count_kmers) f.counts.resize(n * d2g_oph_m(S));
+                check(ctx, d2g_sketcher_run_mincount(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S,
+                                                     o.count_threshold, f.regs.data(), count_kmers ? f.counts.data() : nullptr), "d2g_sketcher_run_mincount");
+            } else if (count_kmers) {                                          // fastxsketch.cpp:590-591: idcounts()
                 f.counts.resize(n * d2g_oph_m(S));
                 check(ctx, d2g_sketcher_run_counts(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data(),
                                                    f.counts.data()), "d2g_sketcher_run_counts");
@@ -477,7 +481,7 @@ int sketch_main(int argc, char **argv) {                          // src/sketch_
     o.device = job_devices(o)[0];
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "sketch");
-    LazyCtx lctx(o, D2G_WARM_COPY | (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : D2G_WARM_K2));
+    LazyCtx lctx(o, D2G_WARM_COPY | (o.sspace == SPACE_MULTISET || o.count_threshold >= 2 ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : D2G_WARM_K2));
     Result res;
     if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
     if (o.verbosity) std::fprintf(stderr, "[d2g] GPU context %.3fs + warm-up %.3fs on a helper thread, under the host ingest\n", lctx.t_create, lctx.t_warm);

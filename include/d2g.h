@@ -282,6 +282,34 @@ int  d2g_sketcher_run_counts(d2g_sketcher *sk, const uint8_t *packed, size_t pac
                              const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
                              size_t sketchsize, uint64_t *regs_out /* host [n][m] */, uint32_t *counts_out /* host [n][m] */);
 
+/* ---- K3o: sketch -m c in set space: registers over the k-mers seen at least c times ----
+ * LazyOnePermSetSketch under set_mincount(c) (reference src/oph.h:154-159,188-205; src/fastxsketch.cpp:192).  Its per-register map of
+ * candidates ends, whatever the order of the k-mers, at: register r = the smallest OPH id among the DISTINCT k-mers that map to r and
+ * occur >= c times (~0 if none); counts r = every occurrence of the k-mer whose id equals the final register -- what d2g_oph_count_dev
+ * defines for any registers (so an empty register counts the occurrences of a k-mer whose id is 2^64-1, even fewer than c).
+ * The input's k-mers are counted exactly by K3's bucketed LDS tables (a filter's k-mers do not count towards c), the selection is the
+ * new kernel k3_ophmin_kernel, the counts are K1b over the new registers on the same stream.  Note the convention: this keeps
+ * count >= c, --multiset's count_threshold keeps count > threshold (src/counter.h:124).
+ * mincount < 2 is the plain sketch: what d2g_sketcher_run / _run_counts (d2g_oph_sketch_dev) return, bit for bit.
+ * counts_out may be NULL (no count pass); with it, a genome of 2^32 k-mers or more is refused as by d2g_oph_sketch_counts.  Null
+ * regs_out with n > 0 and a sketchsize out of range are D2G_ERR_INVALID before anything is written; n = 0 is D2G_OK.
+ * The _dev form synchronises `stream` before it returns (the status word of the kernels is checked), like d2g_bmh_sketch_dev;
+ * counts for it: d2g_oph_count_dev over regs_out_dev. */
+int d2g_oph_sketch_mincount(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
+                            const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                            const uint64_t *genome_run_off, size_t n,
+                            int k, int canon, uint64_t xormask, size_t sketchsize, uint32_t mincount,
+                            uint64_t *regs_out /* host [n][m] */, uint32_t *counts_out /* host [n][m] or NULL */);
+int d2g_oph_sketch_mincount_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev,
+                                int canon, uint64_t xormask, size_t sketchsize, uint32_t mincount,
+                                uint64_t *regs_out_dev /* [n][m] */, void *stream);
+/* persistent form (packed == NULL after d2g_sketcher_ingest_fasta works as for d2g_sketcher_run) */
+int d2g_sketcher_run_mincount(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
+                              const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                              const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                              size_t sketchsize, uint32_t mincount,
+                              uint64_t *regs_out /* host [n][m] */, uint32_t *counts_out /* host [n][m] or NULL */);
+
 /* ---- K1f: --filterset, k-mers that every sketch skips ---------------------------
  * Replaces FilterSet in its sorted-hash-set form (reference src/filterset.h:35-222, built at src/d2.cpp:45-98) and its test
  * `if(!opts.fs_ || !opts.fs_->in_set(maskfn(x))) func(maskfn(x))` (src/fastxsketch.cpp:385-398, src/fastxsketchbyseq.cpp:327,370,383):
@@ -307,7 +335,7 @@ int  d2g_kmer_filter_contains(d2g_ctx *ctx, const d2g_kmer_filter *filter, const
 /* attach (NULL detaches).  The filter must outlive the plan / sketcher or be detached first.  A filter of another context, k or
  * canon makes the SKETCH call return D2G_ERR_INVALID, before it writes anything.  More than 2^31 k-mers: D2G_ERR_UNSUPPORTED at
  * creation; no memory for the table: D2G_ERR_NOMEM (never a smaller table).
- * A plan's filter is honoured by d2g_oph_sketch_dev, d2g_oph_count_dev and d2g_bmh_sketch_dev; a sketcher's by every
+ * A plan's filter is honoured by d2g_oph_sketch_dev, d2g_oph_count_dev, d2g_oph_sketch_mincount_dev and d2g_bmh_sketch_dev; a sketcher's by every
  * d2g_sketcher_run*, packed == NULL (K0-ingested) included.  --multiset calls with a filter walk the input once more, first, to count
  * the surviving k-mers per genome (their layout depends on it) and wait for that count.  The one-shot host-pointer entry points
  * (d2g_oph_sketch, d2g_bmh_sketch, d2g_kmer_count, ...) take no filter. */
