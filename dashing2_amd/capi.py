@@ -21,6 +21,7 @@ TIME_K1, TIME_K2, TIME_K2PREP, TIME_K3, TIME_K0 = 2, 4, 8, 16, 32          # inc
 TIME_KNN = 64
 TIME_DEDUP = 128
 TIME_FILTER = 256
+TIME_KSET = 512
 
 
 class D2GError(RuntimeError):
@@ -124,6 +125,21 @@ SIGNATURES = {
     "d2g_bmh_sketch": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, C.c_double, _vp, _vp]),
     "d2g_kmer_count": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, C.c_double, _vp, _vp, _sz, _vp]),
     "d2g_kmer_distinct": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _vp]),
+    "d2g_kmer_sets": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, C.c_double, _vp, _vp, _sz, _vp, _vp]),
+    "d2g_sketcher_run_sets": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, C.c_double, _vp, _vp, _sz, _vp, _vp]),
+    "d2g_kmer_sets_dev": (_int, [_vp, _vp, _vp, _int, _u64, C.c_double, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "d2g_kset_check": (_int, [_vp, _vp, _vp, _sz, C.c_char_p, _sz]),
+    "d2g_kset_create": (_int, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_vp)]),
+    "d2g_kset_create_dev": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, C.POINTER(_vp)]),
+    "d2g_kset_destroy": (None, [_vp]),
+    "d2g_kset_size": (_sz, [_vp]),
+    "d2g_kset_device_bytes": (_sz, [_vp]),
+    "d2g_kset_slice_bits": (_int, [_vp]),
+    "d2g_kset_isz_ut_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "d2g_kset_isz_rect_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "d2g_epilogue_exact": (_f32, [_u64, _dbl, _dbl, _int, _int]),
+    "d2g_epilogue_exact_ut": (_int, [_vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp]),
+    "d2g_epilogue_exact_rect": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _int, _int, _int, _vp]),
     "d2g_sketcher_run_distinct": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _vp]),
     "d2g_sketcher_ingest_fasta": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int]),
     "d2g_sketcher_ingested_runs": (_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_sz), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
@@ -382,6 +398,47 @@ def host_epilogue_trunc_rect(ca, cb, cards, N, S, a0, a1, b0, b1, measure=SIMILA
     if rc:
         raise D2GError(rc)
     return out
+
+
+def epilogue_exact(isz, lhcard, rhcard, measure=SIMILARITY, k=31):
+    """the exact branch of compare() (--set, --countdict): intersection size and the two cardinalities -> float32"""
+    return float(lib().d2g_epilogue_exact(int(isz), lhcard, rhcard, measure, k))
+
+
+def host_epilogue_exact_ut(isz, cards, N, r0, r1, measure=SIMILARITY, k=31, nthreads=0):
+    """exact intersection sizes (uint64) of rows [r0,r1) of the condensed upper triangle -> float32"""
+    isz = np.ascontiguousarray(isz, np.uint64)
+    cards = np.ascontiguousarray(cards, np.float64)
+    out = np.empty(isz.size, np.float32)
+    rc = lib().d2g_epilogue_exact_ut(_np_ptr(isz), _np_ptr(cards), N, r0, r1, measure, k, nthreads or (os.cpu_count() or 1), _np_ptr(out))
+    if rc:
+        raise D2GError(rc)
+    return out
+
+
+def host_epilogue_exact_rect(isz, cards, N, a0, a1, b0, b1, measure=SIMILARITY, k=31, nthreads=0):
+    """the same over the row-major block rows [a0,a1) x columns [b0,b1)"""
+    isz = np.ascontiguousarray(isz, np.uint64)
+    cards = np.ascontiguousarray(cards, np.float64)
+    out = np.empty((a1 - a0, b1 - b0), np.float32)
+    rc = lib().d2g_epilogue_exact_rect(_np_ptr(isz), _np_ptr(cards), N, a0, a1, b0, b1, measure, k, nthreads or (os.cpu_count() or 1),
+                                       _np_ptr(out))
+    if rc:
+        raise D2GError(rc)
+    return out
+
+
+def kset_check(keys, counts, set_off):
+    """the host-side check of Context.kset without a device: raises D2GError for a set_off that is not monotone, a set whose keys are
+    not strictly ascending (unsorted or duplicated), and a count of 0"""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    counts = None if counts is None else np.ascontiguousarray(counts, np.uint32)
+    set_off = np.ascontiguousarray(set_off, np.uint64)
+    assert keys.size >= int(set_off.max(initial=0)) and (counts is None or counts.size == keys.size)
+    err = C.create_string_buffer(256)
+    rc = lib().d2g_kset_check(_np_ptr(keys), _np_ptr(counts), _np_ptr(set_off), set_off.size - 1, err, 256)
+    if rc:
+        raise D2GError(rc, err.value.decode())
 
 
 def bmh_check_weights(weights, set_off, S, scale=1.0):
@@ -702,6 +759,42 @@ class Context:
         """-> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
         packed, rs, rl, go = sp.arrays()
         return self.kmer_count(packed, rs, rl, go, sp.k, canon, xormask, count_threshold)
+
+    def kmer_sets_seqpack(self, sp: "SeqPack", canon=True, xormask=0, count_threshold=0.0, counts=True):
+        """the exact k-mer sets, sorted on the device -> (keys uint64[total], counts uint32[total] or None, set_off uint64[n+1],
+        cards uint64[n][2] = (distinct keys, sum of the counts))"""
+        packed, rs, rl, go = sp.arrays()
+        n = go.size - 1
+        cap = sum(sp.nkmers(g) for g in range(n))
+        keys = np.empty(max(cap, 1), np.uint64)
+        cnts = np.empty(max(cap, 1), np.uint32) if counts else None
+        off = np.zeros(n + 1, np.uint64)
+        cards = np.zeros((n, 2), np.uint64)
+        self._check(lib().d2g_kmer_sets(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n, sp.k,
+                                        int(canon), xormask, count_threshold, _np_ptr(keys), _np_ptr(cnts), cap, _np_ptr(off), _np_ptr(cards)))
+        total = int(off[n])
+        return keys[:total], (cnts[:total] if counts else None), off, cards
+
+    def kmer_sets_dev(self, plan, packed_dev_ptr, keys_dev_ptr, counts_dev_ptr, cap, set_off_dev_ptr, cards_dev_ptr, canon=True, xormask=0,
+                      count_threshold=0.0, stream=None):
+        """the device-resident form; synchronises `stream`"""
+        self._check(lib().d2g_kmer_sets_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, count_threshold, keys_dev_ptr, counts_dev_ptr,
+                                            cap, set_off_dev_ptr, cards_dev_ptr, stream))
+
+    def kset(self, keys, counts, set_off):
+        """host arrays (sorted sets, e.g. loaded files) -> KSet; refuses unsorted or duplicated keys"""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        counts = None if counts is None else np.ascontiguousarray(counts, np.uint32)
+        set_off = np.ascontiguousarray(set_off, np.uint64)
+        h = _vp()
+        self._check(lib().d2g_kset_create(self._h, _np_ptr(keys), _np_ptr(counts), _np_ptr(set_off), set_off.size - 1, C.byref(h)))
+        return KSet(self, h)
+
+    def kset_dev(self, keys_dev_ptr, counts_dev_ptr, set_off_dev_ptr, nsets, stream=None):
+        """the device arrays of kmer_sets_dev -> KSet (copied)"""
+        h = _vp()
+        self._check(lib().d2g_kset_create_dev(self._h, keys_dev_ptr, counts_dev_ptr, set_off_dev_ptr, nsets, stream, C.byref(h)))
+        return KSet(self, h)
 
     def kmer_distinct_seqpack(self, sp: "SeqPack", canon=True, xormask=0):
         """-> uint64[n]: exact number of distinct masked k-mers per genome"""
@@ -1082,6 +1175,35 @@ class KmerFilter:
     def close(self):
         if getattr(self, "_h", None):
             lib().d2g_kmer_filter_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class KSet:
+    """Device-resident sorted exact k-mer sets with their slice table (d2g_kset)."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+        self.N = int(lib().d2g_kset_size(h))
+
+    @property
+    def device_bytes(self):
+        return int(lib().d2g_kset_device_bytes(self._h))
+
+    @property
+    def slice_bits(self):
+        return int(lib().d2g_kset_slice_bits(self._h))
+
+    def isz_ut_dev(self, r0, r1, out_dev_ptr, stream=None):
+        self.ctx._check(lib().d2g_kset_isz_ut_dev(self.ctx._h, self._h, r0, r1, out_dev_ptr, stream))
+
+    def isz_rect_dev(self, a0, a1, b0, b1, out_dev_ptr, stream=None):
+        self.ctx._check(lib().d2g_kset_isz_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, out_dev_ptr, stream))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().d2g_kset_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -439,6 +439,86 @@ int d2g_epilogue_trunc_rect(const uint32_t *ca, const uint32_t *cb, const double
     return D2G_OK;
 }
 
+// ---- exact k-mer sets (--set, --countdict): the exact branch of compare(), cmp_core.cpp:518-575
+// CORRECT_RES (:519-526) on `double res = isz_size` (:559), assigned to the long double ret, then :573-575.  UNION_SIZE has no arm
+// there and falls through to the intersection; here it is the union weighted_compare computed and compare() dropped.
+float d2g_epilogue_exact(uint64_t isz, double lhc, double rhc, int measure, int k) {
+    double res = (double)isz;
+    if (measure == D2G_SYMMETRIC_CONTAINMENT) res = res / std::min(lhc, rhc);
+    else if (measure == D2G_POISSON_LLR || measure == D2G_SIMILARITY) {
+        res = res / (lhc + rhc - res);
+        if (measure == D2G_POISSON_LLR) {
+            const double pm = -1. / std::max(1, k);                 // sim2dist(auto x) with x = double, :361
+            res = res ? std::log(2. * res / (1. + res)) * pm : std::numeric_limits<double>::infinity();
+        }
+    } else if (measure == D2G_CONTAINMENT) res /= lhc;
+    else if (measure == D2G_UNION_SIZE) res = lhc + rhc - res;
+    return finish(res);
+}
+
+int d2g_epilogue_exact_ut(const uint64_t *isz, const double *cards, size_t N, size_t r0, size_t r1, int measure, int k, int nthreads,
+                          float *out) {
+    if (r0 > r1 || r1 > N) return D2G_ERR_INVALID;
+    if (d2g_ut_count(N, r0, r1) == 0) return D2G_OK;
+    if (!isz || !cards || !out) return D2G_ERR_INVALID;
+    std::vector<size_t> off(r1 - r0 + 1, 0);
+    for (size_t i = r0; i < r1; ++i) off[i - r0 + 1] = off[i - r0] + (N - 1 - i);
+    if (nthreads < 1) nthreads = 1;
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(dynamic, 4) num_threads(nthreads)
+#endif
+    for (size_t i = r0; i < r1; ++i)
+        for (size_t j = i + 1; j < N; ++j) {
+            const size_t p = off[i - r0] + (j - i - 1);
+            out[p] = d2g_epilogue_exact(isz[p], cards[i], cards[j], measure, k);
+        }
+    return D2G_OK;
+}
+
+int d2g_epilogue_exact_rect(const uint64_t *isz, const double *cards, size_t N, size_t a0, size_t a1, size_t b0, size_t b1, int measure,
+                            int k, int nthreads, float *out) {
+    if (a0 > a1 || a1 > N || b0 > b1 || b1 > N) return D2G_ERR_INVALID;
+    if (a0 == a1 || b0 == b1) return D2G_OK;
+    if (!isz || !cards || !out) return D2G_ERR_INVALID;
+    if (nthreads < 1) nthreads = 1;
+    const size_t w = b1 - b0;
+#ifdef _OPENMP
+    #pragma omp parallel for schedule(dynamic, 4) num_threads(nthreads)
+#endif
+    for (size_t i = a0; i < a1; ++i)
+        for (size_t j = b0; j < b1; ++j) {
+            const size_t p = (i - a0) * w + (j - b0);
+            out[p] = d2g_epilogue_exact(isz[p], cards[i], cards[j], measure, k);
+        }
+    return D2G_OK;
+}
+
+// what d2g_kset_create asks of host arrays before anything reaches a device: the pair kernel's searches and its slice table are
+// only right over strictly ascending keys
+int d2g_kset_check(const uint64_t *keys, const uint32_t *counts, const uint64_t *set_off, size_t nsets, char *err, size_t errcap) {
+    auto fail = [&](const char *fmt, unsigned long long a, unsigned long long b) {
+        if (err && errcap) std::snprintf(err, errcap, fmt, a, b);
+        return (int)D2G_ERR_INVALID;
+    };
+    auto fail0 = [&](const char *msg) {
+        if (err && errcap) std::snprintf(err, errcap, "%s", msg);
+        return (int)D2G_ERR_INVALID;
+    };
+    if (!set_off) return fail0("d2g_kset: null set_off");
+    for (size_t i = 0; i < nsets; ++i)
+        if (set_off[i + 1] < set_off[i]) return fail("d2g_kset: set_off decreases at set %llu (to %llu)", i, set_off[i + 1]);
+    if (nsets && set_off[nsets] > set_off[0] && !keys) return fail0("d2g_kset: null keys");
+    for (size_t i = 0; i < nsets; ++i)
+        for (uint64_t e = set_off[i]; e < set_off[i + 1]; ++e) {
+            if (e > set_off[i] && keys[e] <= keys[e - 1])
+                return fail(keys[e] == keys[e - 1] ? "d2g_kset: set %llu holds a key twice (entry %llu): keys must be strictly ascending"
+                                                   : "d2g_kset: set %llu is not sorted (entry %llu): keys must be strictly ascending",
+                            i, e - set_off[i]);
+            if (counts && counts[e] == 0) return fail("d2g_kset: set %llu has a count of 0 (entry %llu)", i, e - set_off[i]);
+        }
+    return D2G_OK;
+}
+
 size_t d2g_ut_count(size_t N, size_t r0, size_t r1) {
     if (r1 > N) r1 = N;
     if (r0 >= r1) return 0;

@@ -119,6 +119,12 @@ struct d2g_k3_tuning {
     bool gq_scale_set = false;          // D2G_K3_GQ_SCALE was given (tests force the region overflow) ...
     double gq_scale = 2.0;              // ... a survivor region holds this multiple of the survivors expected in it ...
     uint64_t gq_slack = 256;            // ... plus this many entries: 1 when the scale was given, else 256 above 24 workgroups per CU and 1024 up to there
+    uint64_t sort_keys = K3_TARGET;     // D2G_K3S_RANGE_KEYS: 1 .. K3_TARGET mean keys per sort range of the sorted emission, K3s (tests: small inputs with many ranges)
+};
+// the exact-set compare (d2g_kset_cmp.hip)
+struct d2g_kset_tuning {
+    int split = 0;                      // D2G_KSET_SPLIT: workgroups a tile's slice range is cut across: 1 = the one-workgroup route (plain stores), >= 2 = the atomic route with that many; 0 = automatic
+    int pbits = -1;                     // D2G_KSET_PBITS: 0 .. 20 key bits that cut the key space into slices (tests); -1 = from the largest set
 };
 d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
 constexpr int MG_MAX_CHUNKS = 4;            // most chunks a rank's column slice is cut into inside one multi-GPU step (d2g_mgpu.hip)
@@ -129,6 +135,7 @@ struct d2g_ctx {
     d2g_tuning tune;
     d2g_k2_tuning k2;                       // ... and what its K2 switches resolved to,
     d2g_k3_tuning k3_tune;                  // its K3 switches,
+    d2g_kset_tuning kset;                   // the exact-set compare's,
     int mgpu_chunks = 0;                    // and D2G_MGPU_CHUNKS: 1 .. MG_MAX_CHUNKS; 0 = the engine's default (a function of the shape)
     int num_cus = 0;
     std::string last_error;
@@ -136,6 +143,7 @@ struct d2g_ctx {
     d2g_evlog ev_k1, ev_k2, ev_k2prep, ev_k3, ev_k0, ev_knn;
     d2g_evlog ev_k1count;                   // "k1count": the count pass after K1 (d2g_oph_count_dev), timed under D2G_TIME_K1
     d2g_evlog ev_filter;                    // "filter": the build of a k-mer filter's table (d2g_kmer_filter_create_dev), under D2G_TIME_FILTER
+    d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
     d2g_evlog ev_dedup, ev_dedup_resolve;   // "dedup" = both: the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the latter alone)
     struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3_bmh.hip)
     d2g_dev<uint32_t> knn_band;             // [band rows][N] equality counts the selection kernel reads (d2g_knn.hip); grow-only
@@ -170,7 +178,7 @@ inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
 struct d2g_timer {
     d2g_evlog *ev; hipStream_t s; bool on;
     d2g_timer(d2g_ctx *c, d2g_evlog *e, hipStream_t st) : ev(e), s(st), on(false) {
-        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : D2G_TIME_K3;
+        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : D2G_TIME_K3;
         on = (c->timing & bit) != 0;
         if (on) {
             d2g_event x, y;
@@ -184,7 +192,7 @@ struct d2g_timer {
 
 // one per translation unit with kernels: makes the runtime load that unit's code object now (hipFuncGetAttributes on one of
 // its kernels) instead of at its first launch
-void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_knn(); void d2g_warm_dedup();
+void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_knn(); void d2g_warm_dedup();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

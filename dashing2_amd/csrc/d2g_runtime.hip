@@ -13,6 +13,7 @@ static const char *const kTuningNames[] = {
     "D2G_MGPU_CHUNKS",
     "D2G_K3_COMPACT", "D2G_K3_L1BITS", "D2G_K3_BUCKET_KEYS", "D2G_K3_SUB_KEYS", "D2G_K3_SPLIT_MIN", "D2G_K3_SUBBATCH", "D2G_K3_ROUND_KEYS",
     "D2G_K3_GUESS_SCALE", "D2G_K3_GRID_PER_CU", "D2G_K3_LIGHT", "D2G_K3_GQ_SCALE",
+    "D2G_K3S_RANGE_KEYS", "D2G_KSET_SPLIT", "D2G_KSET_PBITS",
 };
 void d2g_tuning_load(d2g_tuning &t) {
     t.kv.clear();
@@ -55,6 +56,7 @@ d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t) {
     if (const char *e = t.get("D2G_K3_GRID_PER_CU")) { const int d = std::atoi(e); if (d >= 1 && d <= 256) v.grid_per_cu = (size_t)d; }
     if (const char *e = t.get("D2G_K3_GQ_SCALE")) { v.gq_scale_set = true; v.gq_scale = std::max(0.0, std::atof(e)); }
     v.gq_slack = v.gq_scale_set ? 1 : v.grid_per_cu > 24 ? 256 : 1024;
+    if (const char *e = t.get("D2G_K3S_RANGE_KEYS")) { const long d = std::atol(e); if (d >= 1 && d <= K3_TARGET) v.sort_keys = (uint64_t)d; }
     return v;
 }
 
@@ -62,6 +64,9 @@ void d2g_tuning_resolve(d2g_ctx *c) {
     d2g_tuning_load(c->tune);
     c->k2 = d2g_k2_tuning_resolve(c->tune);
     c->k3_tune = d2g_k3_tuning_resolve(c->tune);
+    c->kset = d2g_kset_tuning();
+    if (const char *e = c->tune.get("D2G_KSET_SPLIT")) { const int v = std::atoi(e); if (v >= 1 && v <= 65535) c->kset.split = v; }
+    if (const char *e = c->tune.get("D2G_KSET_PBITS")) { const int v = std::atoi(e); if (v >= 0 && v <= 20) c->kset.pbits = v; }
     c->mgpu_chunks = 0;
     if (const char *e = c->tune.get("D2G_MGPU_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= MG_MAX_CHUNKS) c->mgpu_chunks = v; }
 }
@@ -204,6 +209,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     if (what & D2G_WARM_K1) d2g_warm_k1();
     if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); d2g_warm_knn(); d2g_warm_dedup(); }
     if (what & D2G_WARM_K3) d2g_warm_k3();
+    if (what & D2G_WARM_KSET) d2g_warm_kset();
     return D2G_OK;
 }
 int d2g_device_name(int device, char *buf, size_t cap) {
@@ -216,7 +222,7 @@ int d2g_device_name(int device, char *buf, size_t cap) {
 
 int d2g_set_timing(d2g_ctx *c, int enabled) {
     if (!c) return D2G_ERR_INVALID;
-    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER) : (enabled & ~1);
+    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET) : (enabled & ~1);
     return D2G_OK;
 }
 
@@ -229,6 +235,9 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     else if (!std::strcmp(which, "k2")) e = &c->ev_k2;
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;
     else if (!std::strcmp(which, "k3")) e = &c->ev_k3;
+    else if (!std::strcmp(which, "k3s")) e = &c->ev_k3s;
+    else if (!std::strcmp(which, "kset")) e = &c->ev_kset;
+    else if (!std::strcmp(which, "ksetprep")) e = &c->ev_ksetprep;
     else if (!std::strcmp(which, "k0")) e = &c->ev_k0;
     else if (!std::strcmp(which, "knn")) e = &c->ev_knn;
     else if (!std::strcmp(which, "dedup")) { e = &c->ev_dedup; e2 = &c->ev_dedup_resolve; }

@@ -34,6 +34,13 @@ struct Result {                              // SketchingResult, src/fastxsketch
     size_t nq = 0;
 };
 
+// the exact k-mer sets of an --set / --countdict job, input by input (keys ascending); Result carries their names and cardinalities
+struct ExactSets {
+    bool weighted = false;                   // --countdict: counts[i] runs beside keys[i]
+    std::vector<std::vector<uint64_t>> keys;
+    std::vector<std::vector<uint32_t>> counts;
+};
+
 // The process leaves through _exit once its outputs are closed (main): releasing device memory and unpinning hundreds of MB
 // one buffer at a time just before that costs tens of milliseconds and buys nothing.  D2G_FULL_TEARDOWN=1 releases everything.
 inline const bool g_release_at_exit = std::getenv("D2G_FULL_TEARDOWN") != nullptr;
@@ -107,7 +114,7 @@ struct Stats {
     }
 };
 inline Stats g_stats;
-constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER;
+constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET;
 
 // {"launches": n, "avg_ms": a, "total_ms": n a} of one timed kernel family on one context (synchronises on its events)
 inline std::string kernel_json(d2g_ctx *ctx, const char *which, bool reset = true) {
@@ -193,9 +200,13 @@ struct HostBuf {
 void sketch_core(Result &res, const Options &o, LazyCtx &lctx);
 void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx);
 int sketch_main(int argc, char **argv);
+// --set / --countdict: per input, the key file (and count file) is loaded -- --presketched, or --cache and a complete file set -- or
+// the input's exact set is computed on the GPU and the files are written
+void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es);
 void apply_fmt_compat(Options &o);                                 // dashing2_main.cpp
 // cmp_dense.cpp: every cmp output of an Options / Result pair; hands nearest neighbours and clustering on to cmp_sparse.cpp
 void cmp_core(const Options &o, Result &res, d2g_ctx *ctx);
+void cmp_core_exact(const Options &o, Result &res, d2g_ctx *ctx, const ExactSets &es);   // the same outputs from exact intersections
 std::string context_switches_json(d2g_ctx *ctx);
 // cmp_sparse.cpp: --topk / --similarity-threshold / --greedy (the values are a table of the equality count: `lut`)
 const char *sparse_job_name(const Options &o);                     // "nearest neighbours" / "greedy clustering"; null: a dense job

@@ -410,6 +410,61 @@ std::string context_switches_json(d2g_ctx *ctx) {
     return buf;
 }
 
+// --set / --countdict: the same dense outputs from EXACT intersections.  Replaces the exact branch of compare() (cmp_core.cpp:518-575:
+// per pair, both files opened and merged with one fread per element) -- the sets go to the device once (d2g_kset), row batches of
+// u64 intersection sizes come back (d2g_kset_isz_*_dev), d2g_epilogue_exact_* turns them into the measure in double, as CORRECT_RES does.
+void cmp_core_exact(const Options &o, Result &res, d2g_ctx *ctx, const ExactSets &es) {
+    const CmpShape sh(o, res);
+    const size_t ns = sh.ns;
+    const double t0 = now();
+    std::vector<uint64_t> off(ns + 1, 0);
+    for (size_t i = 0; i < ns; ++i) off[i + 1] = off[i] + es.keys[i].size();
+    std::vector<uint64_t> keys(std::max<uint64_t>(off[ns], 1));
+    std::vector<uint32_t> counts(es.weighted ? std::max<uint64_t>(off[ns], 1) : 0);
+    for (size_t i = 0; i < ns; ++i) {
+        std::copy(es.keys[i].begin(), es.keys[i].end(), keys.begin() + off[i]);
+        if (es.weighted) std::copy(es.counts[i].begin(), es.counts[i].end(), counts.begin() + off[i]);
+    }
+    d2g_kset *ks = nullptr;
+    check(ctx, d2g_kset_create(ctx, keys.data(), es.weighted ? counts.data() : nullptr, off.data(), ns, &ks), "d2g_kset_create");
+    std::vector<uint64_t>().swap(keys); std::vector<uint32_t>().swap(counts);
+    const double t_set = now();
+    Emitter em(o, res);
+    em.header();
+    const size_t cap = std::max<size_t>(1, std::min(std::max(cmp_slot_values(sh.total_vals), sh.widest), std::max<size_t>(sh.total_vals, 1)));
+    DevBuf d(ctx, cap * 8);
+    std::vector<uint64_t> isz(cap);
+    std::vector<float> out(cap);
+    const int nt = int(o.workers());
+    size_t nbatches = 0;
+    for (size_t r0 = 0; r0 < sh.nrows; ++nbatches) {
+        const auto b = sh.batch(r0, cap);
+        const size_t r1 = b.first, cnt = b.second;
+        if (cnt) {
+            if (sh.symmetric) check(ctx, d2g_kset_isz_ut_dev(ctx, ks, r0, r1, (uint64_t *)d.p, nullptr), "d2g_kset_isz_ut_dev");
+            else check(ctx, d2g_kset_isz_rect_dev(ctx, ks, r0, r1, sh.c0, sh.c1, (uint64_t *)d.p, nullptr), "d2g_kset_isz_rect_dev");
+            check(ctx, d2g_memcpy_d2h(ctx, isz.data(), d.p, cnt * 8, nullptr), "d2h");
+            if (sh.symmetric) check(ctx, d2g_epilogue_exact_ut(isz.data(), res.cardinalities.data(), ns, r0, r1, o.measure, o.k, nt, out.data()), "d2g_epilogue_exact_ut");
+            else check(ctx, d2g_epilogue_exact_rect(isz.data(), res.cardinalities.data(), ns, r0, r1, sh.c0, sh.c1, o.measure, o.k, nt, out.data()), "d2g_epilogue_exact_rect");
+        }
+        if (sh.symmetric) em.rows(r0, r1, out.data(), [ns](size_t i) { return ns - 1 - i; });
+        else { const size_t ncol = sh.ncol; em.rows(r0, r1, out.data(), [ncol](size_t) { return ncol; }); }
+        r0 = r1;
+    }
+    if (o.verbosity) std::fprintf(stderr, "[d2g] exact cmp: %zu sets, %llu keys (%zu bytes resident, 2^%d slices): upload + slice table %.3fs, %zu batches %.3fs\n", ns,
+                                  (unsigned long long)off[ns], d2g_kset_device_bytes(ks), d2g_kset_slice_bits(ks), t_set - t0, nbatches, now() - t_set);
+    if (g_stats.on) {
+        Json dj = Json::array();
+        Json e = device_json(o.device);
+        e.raw("kset", kernel_json(ctx, "kset")).raw("ksetprep", kernel_json(ctx, "ksetprep"));
+        g_stats.nest("cmp", Json::object().integer("sets", ns).integer("keys", off[ns]).integer("values", sh.total_vals).str("shape", sh.name(o))
+                     .str("algo", es.weighted ? "exact count dictionaries" : "exact k-mer sets").integer("resident_bytes", d2g_kset_device_bytes(ks))
+                     .integer("slice_bits", d2g_kset_slice_bits(ks)).integer("batches", nbatches).integer("slot_values", cap).nest("devices", dj.push(e))
+                     .nest("wall_s", Json::object().num("upload_slice_table", t_set - t0).num("batches", now() - t_set)));
+    }
+    if (g_release_at_exit) d2g_kset_destroy(ks);
+}
+
 void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_core.cpp:615-751
     const size_t ns = res.names.size(), S = o.sketchsize;
     if (res.nsigs() != ns * S) die("Empty signatures; trying to compare but don't have any");

@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -54,6 +54,12 @@ void sketch_usage() {
                          "  --filterset <paths>    skip every k-mer of these FASTA/FASTQ(.gz) files (several paths: one argument, space-separated) in all\n"
                          "                         inputs, before anything is sketched or counted: adapters, phiX, rRNA, a host genome.  Same -k and\n"
                          "                         canonicalisation as the sketch; `<paths>:K` is accepted as the reference accepts it; binary k-mer files not\n"
+                         "  --set/-H               no sketch: the exact set of distinct k-mers of every input, sorted on the GPU.  Writes, per input,\n"
+                         "                         <input>[.seed<s>][.rc_canon].k<k>[.ct_threshold<c>].FullMmerSet.DNA.kmerset64 ([f64 card][u64 keys]) next to it or\n"
+                         "                         under --outprefix; --cmpout / cmp give the EXACT Jaccard, containment, intersection, ... of every pair\n"
+                         "  --countdict/-J         the same with every k-mer's count (<...>.kmercounts.f64): exact weighted Jaccard, sum of min counts.\n"
+                         "                         -m c keeps the k-mers seen MORE than c times.  Not with -o, --multiset, --parse-by-seq, -s/-N, --fastcmp <8,\n"
+                         "                         --topk, --similarity-threshold, --greedy, several GPUs; cmp --presketched *.kmerset64 is --set\n"
                          "  --distance/--mash-distance --containment --symmetric-containment --intersection --union-size\n"
                          "  --fastcmp/--regsize/--regbytes <8|4|2|1>   compare registers truncated to that many bytes (8: as sketched); logarithmic\n"
                          "                         (setsketch) truncation unless --bbit-sigs selects b-bit signatures\n"
@@ -111,7 +117,8 @@ std::string Options::to_string() const {    // src/d2.cpp:10-43 (fields that exi
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";sketchsize:%zu", sketchsize);
     if (count_threshold > 0) pos += std::snprintf(buf + pos, sizeof buf - pos, ";%u", count_threshold);
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";sketchtype:%s",
-                         kmer_result == ONE_PERM ? "onepermsetsketch"
+                         exact ? (exact == 2 ? "mmerset64,kmercountsf64" : "mmerset64")     // d2.cpp:24,26
+                         : kmer_result == ONE_PERM ? "onepermsetsketch"
                          : (sspace == SPACE_SET ? "fullsetsketch" : sspace == SPACE_MULTISET ? "bagminhash" : "probminhash"));
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";%s", "Fastx");
     if (!outprefix.empty()) pos += std::snprintf(buf + pos, sizeof buf - pos, ";outprefix:%s", outprefix.c_str());
@@ -152,6 +159,7 @@ int parse_options(int argc, char **argv, Options &o) {
         {"bbit-sigs", no_argument, 0, OPT_BBITSIGS},
         {"save-kmers", no_argument, 0, 's'}, {"save-kmercounts", no_argument, 0, 'N'},
         {"filterset", required_argument, 0, OPT_FILTERSET},
+        {"set", no_argument, 0, OPT_SET}, {"countdict", no_argument, 0, 'J'},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
     std::vector<struct option> all(longopts, longopts + sizeof(longopts) / sizeof(longopts[0]) - 1);
@@ -161,7 +169,7 @@ int parse_options(int argc, char **argv, Options &o) {
         all.push_back({"similarity-threshold", required_argument, 0, OPT_SIMTHRESH});
         all.push_back({"greedy", required_argument, 0, OPT_GREEDY});
     }
-    bool saw_square = false, saw_phylip = false, gave_topk = false, gave_thresh = false, greedy_fasta = false;
+    bool saw_square = false, saw_phylip = false, gave_topk = false, gave_thresh = false, greedy_fasta = false, gave_set = false, gave_countdict = false;
     std::set<std::string> have;
     for (auto &x : all) have.insert(x.name);
     static const std::set<std::string> with_arg = {"topk", "top-k", "similarity-threshold", "fastcmp", "regsize", "regbytes",
@@ -233,6 +241,8 @@ int parse_options(int argc, char **argv, Options &o) {
                 o.greedy = true; o.greedy_t = std::strtod(optarg, &eptr);
                 for (; *eptr; ++eptr) if ((*eptr | 32) == 'f') greedy_fasta = true;    // 'e' (exhaustive): the only route here
             } break;
+            case OPT_SET: case 'H': gave_set = true; break;                          // options.h:348
+            case 'J': gave_countdict = true; break;                                 // options.h:349
             case OPT_FILTERSET: o.filterset_arg = optarg; break;                    // options.h:509-511
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
@@ -263,8 +273,29 @@ int parse_options(int argc, char **argv, Options &o) {
         for (std::string l; std::getline(ifs, l);) o.paths.push_back(l);
     }
     o.nq = o.paths.size() - nref;
+    if (gave_set || gave_countdict) {
+        // exact k-mer sets / count dictionaries: what they do not combine with in this build, each named
+        o.exact = gave_countdict ? 2 : 1;
+        const char *const mode = gave_countdict ? "--countdict/-J" : "--set/-H";
+        const char *why = nullptr;
+        const char *e = std::getenv("D2G_DEVICES");
+        if (gave_set && gave_countdict) why = "--set/-H (one of the two, not both)";
+        else if (!o.outfile.empty()) why = "-o/--outfile (the stacked file of an exact job holds bottom-k hashes that only the reference's LSH index reads, and "
+                                          "its bottomk() under-runs on inputs with fewer k-mers than the sketch size; the per-input files and --cmpout are the outputs)";
+        else if (o.sspace != SPACE_SET) why = "--multiset (a sketch space; an exact job sketches nothing)";
+        else if (o.parse_by_seq) why = "--parse-by-seq (the reference throws \"Not yet supported\" there, cmp_core.cpp:630)";
+        else if (o.save_kmers) why = "-s/--save-kmers or -N/--save-kmercounts (they save what lies behind sketch registers; an exact job has none)";
+        else if (o.regbytes < 8) why = "--fastcmp/--regsize/--regbytes below 8 (there are no registers to truncate)";
+        else if (gave_topk || gave_thresh) why = "--topk / --similarity-threshold (the reference routes these through an LSH index over bottom-k hashes)";
+        else if (o.greedy) why = "--greedy (the reference routes it through an LSH index over bottom-k hashes)";
+        else if (e && *e && (std::strcmp(e, "all") == 0 || std::strchr(e, ','))) why = "D2G_DEVICES naming several GPUs (exact sets are kept and compared on one GPU)";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): %s together with %s is outside the hot-path scope of this build.\n", mode, why);
+            return 1 + 1;
+        }
+    }
     if (o.sspace != SPACE_SET && o.kmer_result == ONE_PERM) o.kmer_result = FULL_SETSKETCH;   // sketch_main.cpp:124-127
-    if (o.sspace == SPACE_SET && o.count_threshold > 0) {
+    if (o.sspace == SPACE_SET && o.count_threshold > 0 && !o.exact) {
         // OPH min-count filtering (oph.h:186-205) is built for One-Permutation set sketches of whole inputs that are WRITTEN somewhere.
         // What the parent refused and this build still does not do stays refused as it was:
         const char *why = nullptr;

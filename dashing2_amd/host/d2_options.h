@@ -47,6 +47,8 @@ struct Options {
     std::string filterset;                // ... and its sequence path line (d2.cpp:45-49): the k-mers of these FASTX files are skipped by every sketch
     mutable bool filterset_built = false; // the sketching leg has built the filter (it runs on a const Options) ...
     mutable uint64_t filterset_size = 0;  // ... of this many k-mer occurrences: FilterSet::data_.size(), printed by to_string()
+    int exact = 0;                        // --set/-H = 1 (FULL_MMER_SET), --countdict/-J = 2 (FULL_MMER_COUNTDICT) (options.h:153,348-349): no sketch, the exact
+                                          // k-mer set / count dictionary of every input; kept iff count > count_threshold; cmp gives exact values
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -6,6 +6,7 @@
 //   cmp_core, dense outputs  src/cmp_core.cpp:686-751, emitrect.cpp  cmp_dense.cpp (slot_queue.h)
 //   neighbours, clustering   src/emitnn.cpp, src/dedup_core.cpp      cmp_sparse.cpp
 #include "cli_common.h"
+#include "exact_files.h"
 #include "fmtfloat.h"
 #include <fstream>
 #include <unistd.h>
@@ -105,8 +106,10 @@ void sniff_presketched_suffix(Options &o) {
     else if (suf == ".pmh") { o.sspace = SPACE_PSET; o.kmer_result = FULL_SETSKETCH; }
     else if (suf == ".ss") { o.sspace = SPACE_SET; o.kmer_result = FULL_SETSKETCH; }
     else if (suf == ".opss") { o.sspace = SPACE_SET; o.kmer_result = ONE_PERM; }
-    else if (suf == ".kmerset64" || suf == ".kmerset128")
-        die("k-mer set comparison is outside this build's hot-path scope");
+    // cmp_main.cpp:335,343 compare the suffix with "mmerseq64" without its dot and the .kmerset64 arm never selects the count dictionary:
+    // *.kmerset64 is --set unless --countdict was given
+    else if (suf == ".kmerset64") { if (!o.exact) o.exact = 1; }
+    else if (suf == ".kmerset128") die("128-bit k-mer set comparison is outside this build's hot-path scope");
 }
 
 int cmp_main(int argc, char **argv) {                             // src/cmp_main.cpp:200-366
@@ -119,11 +122,23 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "cmp");
     if (o.presketched) sniff_presketched_suffix(o);
+    if (o.exact && sparse_job_name(o)) refuse_out_of_scope(std::string(sparse_job_name(o)) + " of exact k-mer sets (*.kmerset64)");
+    if (o.exact && o.presketched)                                   // a missing file is named before a context is asked for
+        for (const auto &p : o.paths) {
+            uint64_t sz = 0;
+            if (!exact_file_size(p, &sz)) die("File does not exist at " + p);
+            if (o.exact == 2 && !exact_file_size(exact_count_file(p), &sz)) die("File does not exist at " + exact_count_file(p));
+        }
     if (const char *sparse = sparse_job_name(o))                    // refused before a context exists
         if (const size_t S = o.presketched ? presketched_sketchsize(o) : o.sketchsize) refuse_sparse_job_out_of_scope(sparse, o, S);
-    LazyCtx lctx(o, D2G_WARM_COPY | D2G_WARM_K2 | (o.presketched ? 0 : (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
+    LazyCtx lctx(o, D2G_WARM_COPY | (o.exact ? D2G_WARM_KSET : D2G_WARM_K2) | (o.presketched ? 0 : (o.sspace == SPACE_MULTISET || o.exact ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
     Result res;
-    if (o.presketched) {
+    ExactSets es;
+    if (o.exact) {
+        if (o.paths.empty()) { std::fprintf(stderr, "No paths provided. See usage.\n"); cmp_usage(); return 1; }
+        exact_sets_job(res, o, lctx, es);
+        res.nq = o.presketched ? 0 : o.nq;
+    } else if (o.presketched) {
         load_results(o, res);
     } else {
         if (o.paths.empty()) { std::fprintf(stderr, "No paths provided. See usage.\n"); cmp_usage(); return 1; }
@@ -137,7 +152,7 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
     g_stats.nest("context", Json::object().num("create_s", lctx.t_create).num("warmup_s", lctx.t_warm).num("inputs_loaded_s", t_wait - t_begin)
                  .num("waited_for_context_s", now() - t_wait).raw("switches", context_switches_json(ctx)));
     const double t_cmp = now();
-    cmp_core(o, res, ctx);
+    if (o.exact) cmp_core_exact(o, res, ctx, es); else cmp_core(o, res, ctx);
     if (o.verbosity) std::fprintf(stderr, "[d2g] cmp_core %.3fs in all (densify, upload, batches, closing the output)\n", now() - t_cmp);
     return 0;
 }

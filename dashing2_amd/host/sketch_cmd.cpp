@@ -4,6 +4,7 @@
 //   makedest (cache names)   src/fastxmerge.cpp:70-120
 //   --parse-by-seq           src/fastxsketchbyseq.cpp:102-268,270-531
 #include "cli_common.h"
+#include "exact_files.h"
 #include "ingest_pipeline.h"
 #include <array>
 #include <cinttypes>
@@ -473,6 +474,96 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     write_stacked(res, o);
 }
 
+// --set / --countdict (fastxsketch.cpp:425-441,462-524): Counter::finalize(vector&, vector&, threshold) per input, on the GPU
+// (d2g_sketcher_run_sets: K3's exact counts, sorted on the device), the key file and the count file per input -- always written, with
+// or without --cache (:462).  Inputs are parsed by the host parser and go to the device in batches of about 32 MB of packed bases.
+// Loaded instead: every path of a --presketched job; with --cache an input whose file set is complete (the count file too under
+// --countdict).  A loaded set's cardinality never comes from the key file's header (exact_files.h).
+void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es) {
+    const size_t N = o.paths.size();
+    if (!N) die(o.presketched ? "No paths provided to --presketched" : "Can't sketch empty path set");
+    const bool weighted = o.exact == 2;
+    const ExactNameOpts no{o.k, o.canon, o.seedseed, o.count_threshold, o.outprefix};
+    es.weighted = weighted;
+    es.keys.assign(N, {}); es.counts.assign(N, {});
+    res.destination_files.resize(N);
+    res.cardinalities.assign(N, 0.);
+    if (weighted) res.kmercountfiles.resize(N);
+    std::string err;
+    std::vector<size_t> todo;
+    for (size_t i = 0; i < N; ++i) {
+        const std::string kf = o.presketched ? o.paths[i] : exact_key_file(no, o.paths[i]);
+        res.destination_files[i] = kf;
+        if (weighted) res.kmercountfiles[i] = exact_count_file(kf);
+        uint64_t sz = 0;
+        const bool complete = exact_file_size(kf, &sz) && (!weighted || exact_file_size(res.kmercountfiles[i], &sz));
+        if (o.presketched || (o.cache && complete)) {
+            if (!exact_load(kf, weighted, es.keys[i], es.counts[i], res.cardinalities[i], err)) die(err);
+        } else todo.push_back(i);
+    }
+    // names: the input lines (fastxsketch.cpp:625); --presketched: the reference leaves names_ empty, rows print as E<i> (emitrect.cpp:145,176)
+    res.names.clear();
+    for (size_t i = 0; i < N; ++i) res.names.push_back(o.presketched ? "E" + std::to_string(i) : o.paths[i]);
+    size_t nbatches = 0; uint64_t nkeys = 0;
+    KAcc k3, k3s;
+    const double t0 = now();
+    if (!todo.empty()) {
+        JobFilter filter(o);
+        d2g_ctx *ctx = lctx.get();
+        d2g_sketcher *sk = nullptr;
+        check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+        d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);
+        const uint64_t xormask = d2g_seed_mask(o.seedseed);
+        size_t limit = size_t(32) << 20;
+        if (const char *e = std::getenv("D2G_GROUP_BYTES")) { const long long v = std::atoll(e); if (v >= 1) limit = size_t(v); }   // tests: many small batches
+        d2g_seqpack *sp = nullptr;
+        check(ctx, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
+        std::vector<uint64_t> keys, off, cards;
+        std::vector<uint32_t> counts;
+        for (size_t t0i = 0; t0i < todo.size();) {
+            d2g_seqpack_clear(sp);
+            size_t t1 = t0i;
+            while (t1 < todo.size() && (t1 == t0i || d2g_seqpack_packed_bytes(sp) < limit)) {
+                if (d2g_seqpack_add_path(sp, o.paths[todo[t1]].c_str()) != D2G_OK) die("Failed to open " + o.paths[todo[t1]]);
+                ++t1;
+            }
+            const size_t n = t1 - t0i;
+            uint64_t cap = 0;
+            for (size_t g = 0; g < n; ++g) cap += d2g_seqpack_nkmers(sp, g);
+            keys.resize(std::max<uint64_t>(cap, 1)); off.resize(n + 1); cards.resize(2 * n);
+            if (weighted) counts.resize(std::max<uint64_t>(cap, 1));
+            check(ctx, d2g_sketcher_run_sets(sk, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp), d2g_seqpack_run_len(sp),
+                                             d2g_seqpack_nruns(sp), d2g_seqpack_genome_run_off(sp), n, o.k, o.canon, xormask, double(o.count_threshold),
+                                             keys.data(), weighted ? counts.data() : nullptr, cap, off.data(), cards.data()), "d2g_sketcher_run_sets");
+            for (size_t g = 0; g < n; ++g) {
+                const size_t i = todo[t0i + g], ne = size_t(off[g + 1] - off[g]);
+                es.keys[i].assign(keys.begin() + off[g], keys.begin() + off[g + 1]);
+                if (weighted) es.counts[i].assign(counts.begin() + off[g], counts.begin() + off[g + 1]);
+                res.cardinalities[i] = double(cards[2 * g + (weighted ? 1 : 0)]);   // fastxsketch.cpp:439-441: also the header that is written
+                std::fprintf(stderr, "Writing saved sketch to %s\n", res.destination_files[i].c_str());   // :463
+                if (!exact_write(res.destination_files[i], res.cardinalities[i], es.keys[i].data(), weighted ? es.counts[i].data() : nullptr, ne, err)) die(err);
+                nkeys += ne;
+            }
+            ++nbatches;
+            t0i = t1;
+        }
+        if (g_stats.on) {
+            int n = 0; float avg = 0, last = 0;
+            if (d2g_kernel_ms(ctx, "k3", 1, &n, &avg, &last) == D2G_OK) { k3.launches = n; k3.total_ms = double(avg) * n; }
+            if (d2g_kernel_ms(ctx, "k3s", 1, &n, &avg, &last) == D2G_OK) { k3s.launches = n; k3s.total_ms = double(avg) * n; }
+        }
+        d2g_seqpack_destroy(sp);
+        if (g_release_at_exit) { d2g_sketcher_destroy(sk); d2g_kmer_filter_destroy(kf); }
+    }
+    if (o.verbosity) std::fprintf(stderr, "[d2g] exact k-mer sets: %zu inputs, %zu loaded, %zu computed in %zu batches (%" PRIu64 " keys) in %.3fs\n", N, N - todo.size(), todo.size(),
+                                  nbatches, nkeys, now() - t0);
+    if (g_stats.on)
+        g_stats.nest("sketch", Json::object().integer("inputs", N).integer("sketched", todo.size()).integer("from_cache", N - todo.size()).integer("k", o.k)
+                     .str("space", weighted ? "exact count dictionaries (K3 counts + K3s sort)" : "exact k-mer sets (K3 counts + K3s sort)").integer("batches", nbatches)
+                     .integer("keys", nkeys).nest("k3", Json::object().integer("launches", k3.launches).num("total_ms", k3.total_ms))
+                     .nest("k3s", Json::object().integer("launches", k3s.launches).num("total_ms", k3s.total_ms)).num("wall_s", now() - t0));
+}
+
 int sketch_main(int argc, char **argv) {                          // src/sketch_main.cpp:23-152
     Options o;
     if (int rc = parse_options(argc, argv, o)) return rc - 1;
@@ -481,12 +572,14 @@ int sketch_main(int argc, char **argv) {                          // src/sketch_
     o.device = job_devices(o)[0];
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "sketch");
-    LazyCtx lctx(o, D2G_WARM_COPY | (o.sspace == SPACE_MULTISET || o.count_threshold >= 2 ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : D2G_WARM_K2));
+    LazyCtx lctx(o, D2G_WARM_COPY | (o.sspace == SPACE_MULTISET || o.count_threshold >= 2 || o.exact ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : o.exact ? D2G_WARM_KSET : D2G_WARM_K2));
     Result res;
-    if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
+    ExactSets es;
+    if (o.exact) exact_sets_job(res, o, lctx, es);
+    else if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
     if (o.verbosity) std::fprintf(stderr, "[d2g] GPU context %.3fs + warm-up %.3fs on a helper thread, under the host ingest\n", lctx.t_create, lctx.t_warm);
     res.nq = o.nq;
-    if (!o.cmpout.empty()) cmp_core(o, res, lctx.get());           // sketch_main.cpp:144-148
+    if (!o.cmpout.empty()) { if (o.exact) cmp_core_exact(o, res, lctx.get(), es); else cmp_core(o, res, lctx.get()); }   // sketch_main.cpp:144-148
     g_stats.nest("context", Json::object().num("create_s", lctx.t_create).num("warmup_s", lctx.t_warm).raw("switches", context_switches_json(lctx.get())));
     return 0;
 }

@@ -90,6 +90,7 @@ int         d2g_host_unregister(d2g_ctx *ctx, void *hptr);
 #define D2G_WARM_K1   4
 #define D2G_WARM_K2   8
 #define D2G_WARM_K3   16
+#define D2G_WARM_KSET 32
 int         d2g_warmup(d2g_ctx *ctx, int what);
 /* "<marketing name> (<gcn arch>, <n> CUs)" of a device, for logs and --gpu-stats */
 int         d2g_device_name(int device, char *buf, size_t cap);
@@ -109,6 +110,8 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
 #define D2G_TIME_DEDUP  128     /* "dedup": the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the in-order
                                  * step alone; the count walk is logged as "k2") */
 #define D2G_TIME_FILTER 256     /* "filter": the build of a k-mer filter's table (d2g_kmer_filter_create*) */
+#define D2G_TIME_KSET   512     /* "k3s": the sorted emission of d2g_kmer_sets* (behind the count chain, which is logged as "k3"); "kset": the exact
+                                 * pair kernel of d2g_kset_isz_*_dev; "ksetprep": the slice table of a d2g_kset */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -753,6 +756,65 @@ int  d2g_allpairs_sparse_info(d2g_allpairs *eng, uint32_t *info4);
  * other still has in flight on the buffers they share. */
 int  d2g_allpairs_enqueue_lut_dev(d2g_allpairs *eng, const uint64_t *my_rows_dev, const float *lut_dev, float *out_dev,
                                   void *stream, int input_ready);
+
+/* ---- K3s + K2g: exact k-mer sets, --set and --countdict (reference src/counter.h:78-117, src/fastxsketch.cpp:425-524,
+ * src/wcompare.cpp:145-187, src/cmp_core.cpp:518-575) ----------------------------------------------------------------
+ * E_g = the pairs (h, c) of every DISTINCT masked k-mer h = maskfn(kmer) of input g and its number of occurrences c, kept iff
+ * c > count_threshold (the Counter's convention, src/counter.h:87), ascending by h.  d2g_kmer_sets is d2g_kmer_count WITH the
+ * reference's sort, done on the device: set g = keys_out / counts_out [set_off_out[g], set_off_out[g+1]), strictly ascending keys;
+ * counts_out may be NULL (keys only).  cards_out [n][2]: cards_out[2g] = |E_g| (the cardinality under --set), cards_out[2g+1] = the
+ * integer sum of E_g's counts (under --countdict, src/fastxsketch.cpp:441).  cap = capacity of keys_out and counts_out in entries
+ * (the total k-mer count always suffices); a cap that is too small is D2G_ERR_INVALID with a message that names the need, and
+ * NOTHING is written to any output.  The _dev form takes device pointers, honours the plan's k-mer filter and synchronises
+ * `stream` (twice: for the total, and for the status word of the kernels), like d2g_bmh_sketch_dev. */
+int d2g_kmer_sets(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
+                  const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                  const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                  double count_threshold, uint64_t *keys_out, uint32_t *counts_out /* or NULL */, size_t cap,
+                  uint64_t *set_off_out /* [n+1] */, uint64_t *cards_out /* [n][2] */);
+/* persistent form (same buffers/stream as d2g_sketcher_run; honours the sketcher's k-mer filter) */
+int d2g_sketcher_run_sets(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
+                          const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                          const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                          double count_threshold, uint64_t *keys_out, uint32_t *counts_out /* or NULL */, size_t cap,
+                          uint64_t *set_off_out /* [n+1] */, uint64_t *cards_out /* [n][2] */);
+int d2g_kmer_sets_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
+                      double count_threshold, uint64_t *keys_dev, uint32_t *counts_dev /* or NULL */, size_t cap,
+                      uint64_t *set_off_dev /* [n+1] */, uint64_t *cards_dev /* [n][2] */, void *stream);
+/* A d2g_kset owns N such sets in device memory (keys, optional counts, offsets) and a table that cuts every set at the same 2^p
+ * key values.  isz(i, j) = sum over the keys both sets hold of min(w_i, w_j), w = 1 without counts, = the count with them: an
+ * integer, returned exactly as u64.  There is no floating point on the device path.
+ * d2g_kset_check: the host-side check of d2g_kset_create on its own (no context, no device): D2G_ERR_INVALID with a message in
+ * err (may be NULL) for a set_off that is not monotone and for a set whose keys are not STRICTLY ascending (unsorted, duplicate);
+ * with counts, for a count of 0.
+ * d2g_kset_create copies host arrays (loaded files) after that check; it refuses with D2G_ERR_NOMEM and a message that names the bytes
+ * needed and the bytes free when the sets do not fit in device memory (there is no out-of-core path).
+ * d2g_kset_create_dev copies the device arrays d2g_kmer_sets_dev produced (set_off_dev is read once, after `stream` is waited for;
+ * the arrays are the caller's to free afterwards).  It trusts their order. */
+typedef struct d2g_kset d2g_kset;
+int    d2g_kset_check(const uint64_t *keys, const uint32_t *counts /* or NULL */, const uint64_t *set_off /* [nsets+1] */, size_t nsets,
+                      char *err, size_t errcap);
+int    d2g_kset_create(d2g_ctx *ctx, const uint64_t *keys, const uint32_t *counts /* or NULL */, const uint64_t *set_off /* [nsets+1] */,
+                       size_t nsets, d2g_kset **out);
+int    d2g_kset_create_dev(d2g_ctx *ctx, const uint64_t *keys_dev, const uint32_t *counts_dev /* or NULL */, const uint64_t *set_off_dev,
+                           size_t nsets, void *stream, d2g_kset **out);
+void   d2g_kset_destroy(d2g_kset *ks);
+size_t d2g_kset_size(const d2g_kset *ks);                    /* N */
+size_t d2g_kset_device_bytes(const d2g_kset *ks);            /* resident bytes: keys, counts, offsets, slice table */
+int    d2g_kset_slice_bits(const d2g_kset *ks);              /* p */
+/* rows [r0, r1) of the condensed upper triangle, in the order of d2g_cmp_eqcount_ut_dev: d2g_ut_count(N, r0, r1) u64 */
+int    d2g_kset_isz_ut_dev(d2g_ctx *ctx, const d2g_kset *ks, size_t r0, size_t r1, uint64_t *out_dev, void *stream);
+/* the row-major block rows [a0, a1) x columns [b0, b1), isz(row, column) (--square, -Q) */
+int    d2g_kset_isz_rect_dev(d2g_ctx *ctx, const d2g_kset *ks, size_t a0, size_t a1, size_t b0, size_t b1, uint64_t *out_dev, void *stream);
+/* the exact branch of compare(), src/cmp_core.cpp:518-575 (CORRECT_RES), in double, then the cast to float: with res = (double)isz,
+ * SIMILARITY res / (lhcard + rhcard - res); POISSON_LLR (--mash-distance) sim2dist of that; CONTAINMENT res / lhcard;
+ * SYMMETRIC_CONTAINMENT res / min(lhcard, rhcard); INTERSECTION res; UNION_SIZE lhcard + rhcard - res (the reference has no arm for
+ * it and returns res: not reproduced).  NaN or Inf becomes the maximum (:573-575): two empty inputs take that route. */
+float  d2g_epilogue_exact(uint64_t isz, double lhcard, double rhcard, int measure, int k);
+int    d2g_epilogue_exact_ut(const uint64_t *isz, const double *cards, size_t N, size_t r0, size_t r1, int measure, int k, int nthreads,
+                             float *out);
+int    d2g_epilogue_exact_rect(const uint64_t *isz, const double *cards, size_t N, size_t a0, size_t a1, size_t b0, size_t b1,
+                               int measure, int k, int nthreads, float *out);
 
 /* ---- multi-GPU row partition (host arithmetic; emitrect.cpp:290-323 row order) ----
  * Splits rows [0,N) into `nparts` contiguous ranges with (near-)equal pair counts.
