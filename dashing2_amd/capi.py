@@ -22,6 +22,7 @@ TIME_KNN = 64
 TIME_DEDUP = 128
 TIME_FILTER = 256
 TIME_KSET = 512
+TIME_SCREEN = 1024
 
 
 class D2GError(RuntimeError):
@@ -115,6 +116,20 @@ SIGNATURES = {
     "d2g_kmer_filter_destroy": (None, [_vp]),
     "d2g_kmer_filter_info": (_int, [_vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_sz)]),
     "d2g_kmer_filter_contains": (_int, [_vp, _vp, _vp, _sz, _vp]),
+    "d2g_screen_create": (_int, [_vp, _vp, _sz, _sz, _int, _int, _u64, _sz, C.POINTER(_vp)]),
+    "d2g_screen_destroy": (None, [_vp]),
+    "d2g_screen_table_slots": (_int, [_u64, C.POINTER(_u64)]),
+    "d2g_screen_reset": (_int, [_vp, _vp]),
+    "d2g_screen_info": (_int, [_vp, _vp, C.POINTER(_u64), C.POINTER(_sz), C.POINTER(_sz)]),
+    "d2g_screen_fed": (_int, [_vp, _vp, _sz, C.POINTER(_u64)]),
+    "d2g_screen_set_fed": (_int, [_vp, _vp, _sz, _u64]),
+    "d2g_screen_add_dev": (_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "d2g_sketcher_run_screen": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _vp, _vp]),
+    "d2g_screen_result": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "d2g_screen_key_counts": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "d2g_epilogue_contain": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "d2g_mem_info": (_int, [_vp, C.POINTER(_sz), C.POINTER(_sz)]),
+    "d2g_seqpack_add_file": (_int, [_vp, _cp]),
     "d2g_oph_plan_set_filter": (_int, [_vp, _vp]),
     "d2g_sketcher_set_filter": (_int, [_vp, _vp]),
     "d2g_sketcher_create": (_int, [_vp, C.POINTER(_vp)]),
@@ -258,6 +273,29 @@ def wang_hash(x):
 
 def wang_hash_inverse(x):
     return int(lib().d2g_wang_hash_inverse(x & 0xFFFFFFFFFFFFFFFF))
+
+
+SCREEN_MAX_KEYS = 1 << 30                                               # include/d2g.h D2G_SCREEN_MAX_KEYS
+
+
+def screen_table_slots(ndistinct):
+    """slots of the table of a screen with that many distinct keys (host, no GPU); D2GError beyond SCREEN_MAX_KEYS"""
+    s = _u64()
+    rc = lib().d2g_screen_table_slots(ndistinct, C.byref(s))
+    if rc:
+        raise D2GError(rc)
+    return int(s.value)
+
+
+def epilogue_contain(matches, matchsums, S):
+    """contain's table from the device's integer sums -> (coverage f32, depth f32), shaped like matches (host, no GPU)"""
+    m = np.ascontiguousarray(matches, np.uint32)
+    s = np.ascontiguousarray(matchsums, np.uint32)
+    cov, dep = np.empty(m.shape, np.float32), np.empty(m.shape, np.float32)
+    rc = lib().d2g_epilogue_contain(_np_ptr(m), _np_ptr(s), m.size, S, _np_ptr(cov), _np_ptr(dep))
+    if rc:
+        raise D2GError(rc)
+    return cov, dep
 
 
 def oph_kmer_ids(regs, S):
@@ -559,6 +597,12 @@ class SeqPack:
         if rc:
             raise D2GError(rc, str(path))
 
+    def add_file(self, path):
+        """one genome from ONE file, its name taken as it stands (spaces included)"""
+        rc = lib().d2g_seqpack_add_file(self._h, os.fsencode(path))
+        if rc:
+            raise D2GError(rc, str(path))
+
     def add_path_by_record(self, path):
         rc = lib().d2g_seqpack_add_path_by_record(self._h, os.fsencode(path))
         if rc:
@@ -839,6 +883,21 @@ class Context:
                                               _np_ptr(genome_run_off), genome_run_off.size - 1, k, C.byref(h)))
         return OphPlan(self, h, genome_run_off.size - 1)
 
+    # -- K1s (contain: reads screened against a k-mer database) ----------------
+    def screen(self, keys, k, canon=True, xormask=0, nrows=1):
+        """keys u64 [nrefs][S] (masked, a .kmer64 payload) -> Screen with nrows rows of counters"""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        nrefs, S = keys.shape
+        h = _vp()
+        self._check(lib().d2g_screen_create(self._h, _np_ptr(keys), nrefs, S, k, int(canon), xormask, nrows, C.byref(h)))
+        return Screen(self, h, nrefs, S, k, canon, nrows)
+
+    def mem_info(self):
+        """-> (free, total) bytes of device memory"""
+        f, t = _sz(), _sz()
+        self._check(lib().d2g_mem_info(self._h, C.byref(f), C.byref(t)))
+        return int(f.value), int(t.value)
+
     # -- K1f (--filterset: k-mers every sketch skips) ---------------------------
     def kmer_filter(self, sp: "SeqPack", canon=True):
         """the k-mers of ALL genomes of `sp` as one device-resident set (host-pointer form; synchronises)"""
@@ -995,6 +1054,23 @@ class Sketcher:
         """attach a KmerFilter (None detaches): every run* of this sketcher skips its k-mers.  The sketcher keeps it alive."""
         self.ctx._check(lib().d2g_sketcher_set_filter(self._h, filt._h if filt is not None else None))
         self._filter = filt
+
+    def run_screen(self, sp, screen, genome_row, canon=True):
+        """the k-mers of genome g of the pack count towards row genome_row[g] of the Screen; synchronises"""
+        packed, rs, rl, go = sp.arrays()
+        n = go.size - 1
+        rows = np.ascontiguousarray(genome_row, np.uint32)
+        assert rows.size == n
+        self.ctx._check(lib().d2g_sketcher_run_screen(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
+                                                      sp.k, int(canon), screen._h, _np_ptr(rows)))
+
+    def run_screen_ingested(self, runs, screen, genome_row, canon=True, k=None):
+        """run_screen over the stream ingested last (packed == NULL)"""
+        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
+                      np.ascontiguousarray(runs[2], np.uint64))
+        rows = np.ascontiguousarray(genome_row, np.uint32)
+        self.ctx._check(lib().d2g_sketcher_run_screen(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), go.size - 1,
+                                                      self.k if k is None else k, int(canon), screen._h, _np_ptr(rows)))
 
     def run_distinct(self, sp, canon=True, xormask=0):
         """-> distinct k-mers per genome, u64 [n] (exact)"""
@@ -1175,6 +1251,57 @@ class KmerFilter:
     def close(self):
         if getattr(self, "_h", None):
             lib().d2g_kmer_filter_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Screen:
+    """Device-resident k-mer database with rows of hit counters (d2g_screen)."""
+
+    def __init__(self, ctx, h, nrefs, S, k, canon, nrows):
+        self.ctx, self._h, self.nrefs, self.S, self.k, self.canon, self.nrows = ctx, h, nrefs, S, k, canon, nrows
+
+    def info(self):
+        """-> (distinct keys, bytes of the table, bytes of the counters)"""
+        nd, tb, cb = _u64(), _sz(), _sz()
+        self.ctx._check(lib().d2g_screen_info(self.ctx._h, self._h, C.byref(nd), C.byref(tb), C.byref(cb)))
+        return int(nd.value), int(tb.value), int(cb.value)
+
+    def reset(self):
+        self.ctx._check(lib().d2g_screen_reset(self.ctx._h, self._h))
+
+    def fed(self, row):
+        n = _u64()
+        self.ctx._check(lib().d2g_screen_fed(self.ctx._h, self._h, row, C.byref(n)))
+        return int(n.value)
+
+    def set_fed(self, row, nkmers):
+        self.ctx._check(lib().d2g_screen_set_fed(self.ctx._h, self._h, row, nkmers))
+
+    def add_dev(self, plan, packed_dev_ptr, genome_row, stream=None):
+        rows = np.ascontiguousarray(genome_row, np.uint32)
+        assert rows.size == plan.n
+        self.ctx._check(lib().d2g_screen_add_dev(self.ctx._h, self._h, plan._h, packed_dev_ptr, _np_ptr(rows), stream))
+
+    def result(self, row0=0, nrows=None):
+        """-> (matches u32 [nrows][nrefs], matchsums u32 [nrows][nrefs]); synchronises"""
+        nrows = self.nrows - row0 if nrows is None else nrows
+        m = np.zeros((nrows, self.nrefs), np.uint32)
+        s = np.zeros((nrows, self.nrefs), np.uint32)
+        self.ctx._check(lib().d2g_screen_result(self.ctx._h, self._h, row0, nrows, _np_ptr(m), _np_ptr(s)))
+        return m, s
+
+    def key_counts(self, row):
+        """-> (distinct masked keys u64 [D] ascending, the row's count of each u32 [D])"""
+        D = self.info()[0]
+        keys, cnt = np.zeros(D, np.uint64), np.zeros(D, np.uint32)
+        self.ctx._check(lib().d2g_screen_key_counts(self.ctx._h, self._h, row, _np_ptr(keys), _np_ptr(cnt)))
+        return keys, cnt
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().d2g_screen_destroy(self._h)
             self._h = None
 
     __del__ = close

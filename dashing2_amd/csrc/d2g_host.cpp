@@ -23,7 +23,28 @@
 #include <immintrin.h>
 #ifdef _OPENMP
 #include <omp.h>
+#include <parallel/algorithm>
 #endif
+
+// K1s (d2g_screen.hip), the host work of d2g_screen_create, here because this file is built with OpenMP: the distinct keys of a database
+// in ascending order, their raw k-mers (WangInverse(key) ^ xormask) and, for every database position, the rank of its key among them
+void d2g_screen_rank_keys(const uint64_t *keys, size_t n, uint64_t xormask, std::vector<uint64_t> &distinct, std::vector<uint64_t> &raw,
+                          std::vector<uint32_t> &rank) {
+    distinct.assign(keys, keys + n);
+#ifdef _OPENMP
+    __gnu_parallel::sort(distinct.begin(), distinct.end());
+#else
+    std::sort(distinct.begin(), distinct.end());
+#endif
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    distinct.shrink_to_fit();
+    raw.resize(distinct.size());
+    rank.resize(n);
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < distinct.size(); ++i) raw[i] = d2g_wang_hash_inverse(distinct[i]) ^ xormask;
+#pragma omp parallel for schedule(static)
+    for (size_t i = 0; i < n; ++i) rank[i] = (uint32_t)(std::lower_bound(distinct.begin(), distinct.end(), keys[i]) - distinct.begin());
+}
 
 extern "C" {
 
@@ -519,6 +540,30 @@ int d2g_kset_check(const uint64_t *keys, const uint32_t *counts, const uint64_t 
     return D2G_OK;
 }
 
+// K1s: slots of a screen's table = the power of two >= 2 D, >= 16.  The probe numbers slots in a uint32 where ~0 means "not in the
+// table" and `slots` itself names the all-ones k-mer behind them (d2g_filter_find, d2g_kmers.h): both need slots <= 2^31, D <= 2^30.
+int d2g_screen_table_slots(uint64_t ndistinct, uint64_t *slots) {
+    if (!slots) return D2G_ERR_INVALID;
+    *slots = 0;
+    if (ndistinct > D2G_SCREEN_MAX_KEYS) return D2G_ERR_UNSUPPORTED;
+    uint64_t s = 16;
+    while (s < 2 * ndistinct) s <<= 1;
+    *slots = s;
+    return D2G_OK;
+}
+
+// contain's table (src/contain_main.cpp:221,237-241): `cmatptr[j] = ssiv * matches[j]` is a double product narrowed to float,
+// `cstatsptr[j] = matchsums[j] / matches[j]` the quotient of two uint32 -- the floor of the mean depth -- converted to float
+int d2g_epilogue_contain(const uint32_t *matches, const uint32_t *matchsums, size_t n, size_t S, float *coverage, float *depth) {
+    if (S == 0 || (n && (!matches || !matchsums || !coverage || !depth))) return D2G_ERR_INVALID;
+    const double ssiv = 1. / double(S);
+    for (size_t i = 0; i < n; ++i) {
+        coverage[i] = matches[i] ? float(ssiv * matches[i]) : 0.f;
+        depth[i] = matches[i] ? float(matchsums[i] / matches[i]) : 0.f;
+    }
+    return D2G_OK;
+}
+
 size_t d2g_ut_count(size_t N, size_t r0, size_t r1) {
     if (r1 > N) r1 = N;
     if (r0 >= r1) return 0;
@@ -1011,6 +1056,17 @@ int d2g_seqpack_add_path(d2g_seqpack *sp, const char *line) {
     }
     sp->end_genome();
     return rc;
+}
+// one genome from ONE file whose name is taken as it stands, spaces included (`contain` never splits a query path)
+int d2g_seqpack_add_file(d2g_seqpack *sp, const char *path) {
+    if (!sp || !path) return D2G_ERR_INVALID;
+    sp->unpad();
+    static thread_local std::vector<char> buf;
+    size_t len = 0;
+    const bool ok = slurp(path, buf, len);
+    if (ok) { sp->reserve_bases(len); sp->feed_fastx(buf.data(), len); }
+    sp->end_genome();
+    return ok ? D2G_OK : D2G_ERR_IO;
 }
 // --parse-by-seq: one genome per record of the (space-separated) files of `line`
 int d2g_seqpack_add_path_by_record(d2g_seqpack *sp, const char *line) {

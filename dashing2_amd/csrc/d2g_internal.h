@@ -144,12 +144,16 @@ struct d2g_ctx {
     d2g_evlog ev_k1count;                   // "k1count": the count pass after K1 (d2g_oph_count_dev), timed under D2G_TIME_K1
     d2g_evlog ev_filter;                    // "filter": the build of a k-mer filter's table (d2g_kmer_filter_create_dev), under D2G_TIME_FILTER
     d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
+    d2g_evlog ev_screen, ev_screenreduce, ev_screenbuild;   // under D2G_TIME_SCREEN (d2g_screen.hip): "screen" = the count walk, "screenreduce" = d2g_screen_result's kernel, "screenbuild" = a screen's table
     d2g_evlog ev_dedup, ev_dedup_resolve;   // "dedup" = both: the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the latter alone)
     struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3_bmh.hip)
     d2g_dev<uint32_t> knn_band;             // [band rows][N] equality counts the selection kernel reads (d2g_knn.hip); grow-only
     d2g_dev<unsigned long long> dedup_keys; // one key per row of a band: its best representative of earlier bands (d2g_dedup.hip)
 };
 void d2g_k3_state_destroy(struct d2g_k3_state *st);
+// (d2g_host.cpp) the host ranking behind d2g_screen_create: distinct keys ascending, their raw k-mers, the rank of every position's key
+void d2g_screen_rank_keys(const uint64_t *keys, size_t n, uint64_t xormask, std::vector<uint64_t> &distinct, std::vector<uint64_t> &raw,
+                          std::vector<uint32_t> &rank);
 inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
     if (e == hipSuccess) return D2G_OK;
     ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
@@ -178,7 +182,7 @@ inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
 struct d2g_timer {
     d2g_evlog *ev; hipStream_t s; bool on;
     d2g_timer(d2g_ctx *c, d2g_evlog *e, hipStream_t st) : ev(e), s(st), on(false) {
-        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : D2G_TIME_K3;
+        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
         on = (c->timing & bit) != 0;
         if (on) {
             d2g_event x, y;
@@ -192,7 +196,7 @@ struct d2g_timer {
 
 // one per translation unit with kernels: makes the runtime load that unit's code object now (hipFuncGetAttributes on one of
 // its kernels) instead of at its first launch
-void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_knn(); void d2g_warm_dedup();
+void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -48,6 +48,16 @@ __device__ __forceinline__ bool d2g_filter_hit(const KmerArgs &a, uint64_t x, ui
     while (v != x && v != D2G_FILTER_EMPTY) { s = (s + 1) & a.fmask; v = a.ftab[s]; }
     return v == x;
 }
+// K1s (d2g_screen.hip): the same probe, answering WHERE x sits -- its slot, fmask + 1 for the all-ones k-mer (held behind the slots),
+// D2G_FILTER_NOSLOT when x is not in the table.  Both special values are real slot numbers of a table of 2^32 slots: a table asked
+// through this has at most 2^31 (d2g_screen_table_slots refuses more), so fmask + 1 <= 2^31 neither wraps nor meets ~0.
+constexpr uint32_t D2G_FILTER_NOSLOT = ~0u;
+__device__ __forceinline__ uint32_t d2g_filter_find(const KmerArgs &a, uint64_t x, uint64_t v) {
+    if (x == D2G_FILTER_EMPTY) return a.ftab[(size_t)a.fmask + 1] != 0 ? a.fmask + 1 : D2G_FILTER_NOSLOT;
+    uint32_t s = d2g_filter_slot(x, a.fshift);
+    while (v != x && v != D2G_FILTER_EMPTY) { s = (s + 1) & a.fmask; v = a.ftab[s]; }
+    return v == x ? s : D2G_FILTER_NOSLOT;
+}
 
 // funnel shift: low 32 bits of (hi:lo) >> sh, 0 <= sh < 32
 __device__ __forceinline__ uint32_t fsr(uint32_t hi, uint32_t lo, uint32_t sh) {
@@ -59,7 +69,9 @@ __device__ __forceinline__ uint32_t fsr(uint32_t hi, uint32_t lo, uint32_t sh) {
 // IT0 <= it < IT1: the passes ("tiles" of K1_THREADS chunks = K1_THREADS * K1_CHUNK k-mers) of the workgroup to walk
 // FILT: f sees only the k-mers that are NOT in a.ftab (the reference's `!opts.fs_->in_set(maskfn(x))`, src/fastxsketch.cpp:387) --
 // a template flag, so that the unfiltered instantiations are the code they were (profiles/filter_resource_usage.txt)
-template <bool FILT = false, class F>
+// HITS (with FILT): the third mode, K1s -- f(x, slot) for the k-mers that ARE in a.ftab, slot as d2g_filter_find gives it; a miss
+// does nothing.  The other instantiations stay the code they were (profiles/screen_resource_usage.txt)
+template <bool FILT = false, bool HITS = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0, int it1, F &&f) {
     const int tid = threadIdx.x;
     const uint32_t b = blockIdx.x + a.blk0;
@@ -127,9 +139,18 @@ __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0
                     xs[e] = canon ? (fwd < rc ? fwd : rc) : fwd;
                     vs[e] = ebase + e < n ? a.ftab[d2g_filter_slot(xs[e], a.fshift)] : 0;
                 }
+                if constexpr (HITS) {
 #pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    if (ebase + e < n && !d2g_filter_hit(a, xs[e], vs[e])) f(xs[e]);
+                    for (int e = 0; e < 16; ++e)
+                        if (ebase + e < n) {
+                            const uint32_t slot = d2g_filter_find(a, xs[e], vs[e]);
+                            if (slot != D2G_FILTER_NOSLOT) f(xs[e], slot);
+                        }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        if (ebase + e < n && !d2g_filter_hit(a, xs[e], vs[e])) f(xs[e]);
+                }
                 continue;
             }
 #pragma unroll
@@ -137,13 +158,15 @@ __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0
                 const uint64_t cb = (W >> (2 * e)) & 3u;
                 fwd = ((fwd << 2) | cb) & kmask;
                 rc = (rc >> 2) | ((3 - cb) << rcshift);
-                if (ebase + e < n) f(canon ? (fwd < rc ? fwd : rc) : fwd);
+                if constexpr (!HITS)                             // (the hit mode left through the FILT arm; its f takes two arguments)
+                    if (ebase + e < n) f(canon ? (fwd < rc ? fwd : rc) : fwd);
             }
         }
     }
 }
 
-template <bool FILT = false, class F>
+template <bool FILT = false, bool HITS = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer(const KmerArgs &a, F &&f) {
-    d2g_for_each_kmer_its<FILT>(a, 0, K1_CPT, static_cast<F &&>(f));
+    static_assert(FILT || !HITS, "the hit mode walks a table");
+    d2g_for_each_kmer_its<FILT, HITS>(a, 0, K1_CPT, static_cast<F &&>(f));
 }

@@ -152,6 +152,15 @@ int d2g_free(d2g_ctx *c, void *dptr) {
     D2G_HIP(c, hipFree(dptr));
     return D2G_OK;
 }
+int d2g_mem_info(d2g_ctx *c, size_t *free_bytes, size_t *total_bytes) {
+    if (!c) return D2G_ERR_INVALID;
+    D2G_HIP(c, hipSetDevice(c->device));
+    size_t f = 0, t = 0;
+    D2G_HIP(c, hipMemGetInfo(&f, &t));
+    if (free_bytes) *free_bytes = f;
+    if (total_bytes) *total_bytes = t;
+    return D2G_OK;
+}
 int d2g_malloc_host(d2g_ctx *c, size_t nbytes, void **hptr) {
     if (!c || !hptr) return D2G_ERR_INVALID;
     D2G_HIP(c, hipSetDevice(c->device));
@@ -210,6 +219,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); d2g_warm_knn(); d2g_warm_dedup(); }
     if (what & D2G_WARM_K3) d2g_warm_k3();
     if (what & D2G_WARM_KSET) d2g_warm_kset();
+    if (what & D2G_WARM_SCREEN) d2g_warm_screen();
     return D2G_OK;
 }
 int d2g_device_name(int device, char *buf, size_t cap) {
@@ -222,7 +232,7 @@ int d2g_device_name(int device, char *buf, size_t cap) {
 
 int d2g_set_timing(d2g_ctx *c, int enabled) {
     if (!c) return D2G_ERR_INVALID;
-    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET) : (enabled & ~1);
+    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN) : (enabled & ~1);
     return D2G_OK;
 }
 
@@ -238,6 +248,9 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     else if (!std::strcmp(which, "k3s")) e = &c->ev_k3s;
     else if (!std::strcmp(which, "kset")) e = &c->ev_kset;
     else if (!std::strcmp(which, "ksetprep")) e = &c->ev_ksetprep;
+    else if (!std::strcmp(which, "screen")) e = &c->ev_screen;
+    else if (!std::strcmp(which, "screenreduce")) e = &c->ev_screenreduce;
+    else if (!std::strcmp(which, "screenbuild")) e = &c->ev_screenbuild;
     else if (!std::strcmp(which, "k0")) e = &c->ev_k0;
     else if (!std::strcmp(which, "knn")) e = &c->ev_knn;
     else if (!std::strcmp(which, "dedup")) { e = &c->ev_dedup; e2 = &c->ev_dedup_resolve; }

@@ -114,7 +114,7 @@ struct Stats {
     }
 };
 inline Stats g_stats;
-constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET;
+constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN;
 
 // {"launches": n, "avg_ms": a, "total_ms": n a} of one timed kernel family on one context (synchronises on its events)
 inline std::string kernel_json(d2g_ctx *ctx, const char *which, bool reset = true) {

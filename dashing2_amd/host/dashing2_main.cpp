@@ -5,6 +5,7 @@
 //   sketch_main, sketch_core src/sketch_main.cpp:23-152 ...          sketch_cmd.cpp (host ingest: ingest_pipeline.h, bounded_queue.h)
 //   cmp_core, dense outputs  src/cmp_core.cpp:686-751, emitrect.cpp  cmp_dense.cpp (slot_queue.h)
 //   neighbours, clustering   src/emitnn.cpp, src/dedup_core.cpp      cmp_sparse.cpp
+//   contain_main             src/contain_main.cpp:133-299            contain_cmd.cpp (contain_files.h)
 #include "cli_common.h"
 #include "exact_files.h"
 #include "fmtfloat.h"
@@ -14,6 +15,7 @@
 namespace d2h {
 
 int wsketch_main(int argc, char **argv);                          // wsketch_main.cpp
+int contain_main(int argc, char **argv);                          // contain_cmd.cpp
 
 namespace {
 
@@ -163,7 +165,7 @@ int main_usage() {                                                // src/d2.cpp:
     std::fprintf(stderr, "\tsketch: converts FastX into k-mer sets/sketches; also contains functionality from cmp, for one-step sketch and comparisons\n");
     std::fprintf(stderr, "\tcmp: compares previously sketched/decomposed k-mer sets and emits results. alias: dist\n\n");
     std::fprintf(stderr, "\twsketch: Takes a tuple of [1-3] input binary files [(u32 or u64), (float or double), (u32 or u64)] and performs weighted minhash sketching.\n");
-    std::fprintf(stderr, "This MI355X build implements the sketch and cmp hot paths and wsketch's BagMinHash selections (contain/printmin are out of scope).\n");
+    std::fprintf(stderr, "This MI355X build implements the sketch and cmp hot paths and wsketch's BagMinHash selections and contain (printmin is out of scope).\n");
     return 1;
 }
 
@@ -206,7 +208,13 @@ int main(int argc, char **argv) {                                 // src/d2.cpp:
             return rc;
         }
         if (std::strcmp(argv[1], "wsketch") == 0) return wsketch_main(argc - 1, argv + 1);
-        if (std::strcmp(argv[1], "contain") == 0 || std::strcmp(argv[1], "printmin") == 0) {
+        if (std::strcmp(argv[1], "contain") == 0) {
+            const int rc = contain_main(argc - 1, argv + 1);
+            std::fflush(nullptr);                                  // the output is closed; leave as sketch and cmp do
+            if (!g_release_at_exit) _exit(rc);
+            return rc;
+        }
+        if (std::strcmp(argv[1], "printmin") == 0) {
             std::fprintf(stderr, "dashing2 (MI355X): subcommand %s is outside the hot-path scope of this build.\n", argv[1]);
             return 1;
         }

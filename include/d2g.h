@@ -74,6 +74,8 @@ int         d2g_ctx_tuning(const d2g_ctx *ctx, char *buf, size_t cap);
 int         d2g_sync(d2g_ctx *ctx, void *stream);
 int         d2g_malloc(d2g_ctx *ctx, size_t nbytes, void **dptr);
 int         d2g_free(d2g_ctx *ctx, void *dptr);
+/* device memory free now and in all, in bytes (a caller that sizes a resident object, e.g. the rows of a d2g_screen) */
+int         d2g_mem_info(d2g_ctx *ctx, size_t *free_bytes, size_t *total_bytes);
 /* page-locked host memory: D2H/H2D at PCIe rate, no per-batch page faults */
 int         d2g_malloc_host(d2g_ctx *ctx, size_t nbytes, void **hptr);
 int         d2g_free_host(d2g_ctx *ctx, void *hptr);
@@ -91,6 +93,7 @@ int         d2g_host_unregister(d2g_ctx *ctx, void *hptr);
 #define D2G_WARM_K2   8
 #define D2G_WARM_K3   16
 #define D2G_WARM_KSET 32
+#define D2G_WARM_SCREEN 64
 int         d2g_warmup(d2g_ctx *ctx, int what);
 /* "<marketing name> (<gcn arch>, <n> CUs)" of a device, for logs and --gpu-stats */
 int         d2g_device_name(int device, char *buf, size_t cap);
@@ -112,6 +115,8 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
 #define D2G_TIME_FILTER 256     /* "filter": the build of a k-mer filter's table (d2g_kmer_filter_create*) */
 #define D2G_TIME_KSET   512     /* "k3s": the sorted emission of d2g_kmer_sets* (behind the count chain, which is logged as "k3"); "kset": the exact
                                  * pair kernel of d2g_kset_isz_*_dev; "ksetprep": the slice table of a d2g_kset */
+#define D2G_TIME_SCREEN 1024    /* "screen": the count walk of d2g_screen_add_dev / d2g_sketcher_run_screen; "screenreduce": the per-reference
+                                 * sums of d2g_screen_result; "screenbuild": the table of d2g_screen_create */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -201,6 +206,8 @@ void d2g_seqpack_destroy(d2g_seqpack *sp);
 void d2g_seqpack_clear(d2g_seqpack *sp);
 /* appends one genome from a file "line" (gz transparently via zlib). */
 int  d2g_seqpack_add_path(d2g_seqpack *sp, const char *path_line);
+/* appends one genome from ONE file whose name is taken as it stands, spaces included (gz transparently) */
+int  d2g_seqpack_add_file(d2g_seqpack *sp, const char *path);
 /* appends one genome from an in-memory FASTA/FASTQ buffer */
 int  d2g_seqpack_add_fastx(d2g_seqpack *sp, const char *buf, size_t len);
 /* appends one genome consisting of a single raw sequence (no header) */
@@ -344,6 +351,61 @@ int  d2g_kmer_filter_contains(d2g_ctx *ctx, const d2g_kmer_filter *filter, const
  * (d2g_oph_sketch, d2g_bmh_sketch, d2g_kmer_count, ...) take no filter. */
 int  d2g_oph_plan_set_filter(d2g_oph_plan *plan, const d2g_kmer_filter *filter);
 int  d2g_sketcher_set_filter(d2g_sketcher *sk, const d2g_kmer_filter *filter);
+
+/* ---- K1s: `dashing2 contain`, reads screened against a database of sampled k-mers ----
+ * Replaces the reference's mash-screen loop (src/contain_main.cpp:34-59,188-244): kmer2ids.find(maskfn(kmer)) once per k-mer of
+ * every query, then per (query, reference) the number of the reference's S sampled keys that occur in the query and how often.
+ * A d2g_screen is resident on the device: the distinct keys of the database (keys[nrefs][S], MASKED: maskfn(kmer) =
+ * d2g_wang_hash(kmer ^ xormask), the payload of the <out>.kmer64 that `sketch -s` writes) in K1f's table of raw k-mers, a dense id
+ * per key, the id of every database position, and u32 counters cnt[nrows][ndistinct] -- one row per query the caller wants to keep
+ * apart.  Counters are zero at creation and after d2g_screen_reset, and ADDITIVE over calls: a query may be fed in pieces.
+ * Per (row q, reference r):  matches = #{ j : cnt[q][id(key[r][j])] > 0 },  matchsum = sum_j cnt[q][id(key[r][j])] mod 2^32
+ * (a key that stands in two registers of r counts twice, as in the reference: in practice the key of an empty register).
+ * The screen counts the k-mers fed to each row on the host; a call that would take a row to 2^32 k-mers or beyond returns
+ * D2G_ERR_UNSUPPORTED before it enqueues anything -- below that no counter can wrap.
+ * nrefs == 0 is legal.  Not enough device memory: D2G_ERR_NOMEM with the bytes needed and free in d2g_last_error, never a smaller
+ * table.  More than D2G_SCREEN_MAX_KEYS = 2^30 database keys (nrefs x S): D2G_ERR_UNSUPPORTED before anything is ranked -- the table
+ * would pass 2^31 slots, and the walker's probe names a slot in 32 bits with two values set aside (not found; the all-ones k-mer). */
+#define D2G_SCREEN_MAX_KEYS (1ull << 30)
+typedef struct d2g_screen d2g_screen;
+/* host, no GPU: the slots of the table of a screen with `ndistinct` distinct keys (the power of two >= 2 ndistinct, >= 16, <= 2^31);
+ * D2G_ERR_UNSUPPORTED and *slots = 0 beyond D2G_SCREEN_MAX_KEYS */
+int  d2g_screen_table_slots(uint64_t ndistinct, uint64_t *slots);
+int  d2g_screen_create(d2g_ctx *ctx, const uint64_t *keys /* host [nrefs][S] */, size_t nrefs, size_t sketchsize, int k, int canon,
+                       uint64_t xormask, size_t nrows, d2g_screen **out);
+void d2g_screen_destroy(d2g_screen *screen);
+/* every counter back to zero, every row's k-mer tally too; synchronises the device */
+int  d2g_screen_reset(d2g_ctx *ctx, d2g_screen *screen);
+/* distinct keys held, bytes of the device table (keys + ids), bytes of the counters */
+int  d2g_screen_info(d2g_ctx *ctx, const d2g_screen *screen, uint64_t *ndistinct, size_t *table_bytes, size_t *counter_bytes);
+/* the k-mers fed to a row since the last reset: what the 2^32 guard reads.  d2g_screen_set_fed overwrites the tally (the counters
+ * are not touched): a caller that restores a checkpoint, and the tests of the guard. */
+int  d2g_screen_fed(d2g_ctx *ctx, const d2g_screen *screen, size_t row, uint64_t *nkmers);
+int  d2g_screen_set_fed(d2g_ctx *ctx, d2g_screen *screen, size_t row, uint64_t nkmers);
+/* device-resident form: the k-mers of genome g of the plan count towards row genome_row[g] (host array [n]; several genomes may
+ * share a row, several rows a launch).  The k-mers are enumerated with the plan's k and the SCREEN's canonicalisation; a plan's
+ * filter plays no part.  Enqueues on `stream`, does not synchronise; calls on one screen go to one stream or are ordered by the
+ * caller.  A screen of another context or k: D2G_ERR_INVALID before anything is written. */
+int  d2g_screen_add_dev(d2g_ctx *ctx, d2g_screen *screen, const d2g_oph_plan *plan, const uint8_t *packed_dev,
+                        const uint32_t *genome_row /* host [n] */, void *stream);
+/* sketcher form: the packed-run arguments of d2g_sketcher_run (packed == NULL after d2g_sketcher_ingest_fasta works as there), so a
+ * d2g_seqpack and the K0 device parser feed it; synchronises.  A screen of another context, k or canon: D2G_ERR_INVALID before
+ * anything is written.  The sketcher's filter plays no part. */
+int  d2g_sketcher_run_screen(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
+                             const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                             const uint64_t *genome_run_off, size_t n, int k, int canon,
+                             d2g_screen *screen, const uint32_t *genome_row /* host [n] */);
+/* matches and matchsums of rows [row0, row0 + nrows) against every reference; synchronises the device */
+int  d2g_screen_result(d2g_ctx *ctx, const d2g_screen *screen, size_t row0, size_t nrows,
+                       uint32_t *matches_out /* host [nrows][nrefs] */, uint32_t *matchsums_out /* host [nrows][nrefs] */);
+/* the counters themselves: the distinct MASKED keys in ascending order and row `row`'s count of each (either may be NULL);
+ * synchronises the device */
+int  d2g_screen_key_counts(d2g_ctx *ctx, const d2g_screen *screen, size_t row, uint64_t *keys_out /* [ndistinct] */,
+                           uint32_t *counts_out /* [ndistinct] */);
+/* host, no GPU (reference src/contain_main.cpp:221,237-241): coverage = (float)((1.0 / S) * matches) -- the product in double --
+ * and depth = (float)(matchsum / matches), the INTEGER quotient of the two uint32; both 0 where matches == 0 */
+int  d2g_epilogue_contain(const uint32_t *matches, const uint32_t *matchsums, size_t n, size_t sketchsize,
+                          float *coverage_out /* [n] */, float *depth_out /* [n] */);
 
 /* ---- K0: FASTA bytes -> packed run stream on the GPU (host ingest pipelines) ------
  * Replaces, for plain FASTA inputs, the host parser + 2-bit packer (d2g_seqpack_*; reference call sites
