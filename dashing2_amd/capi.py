@@ -266,6 +266,29 @@ def _np_ptr(a):
     return a.ctypes.data if a is not None else None
 
 
+class _Runs:
+    """The nine leading arguments of every sketch entry point -- packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k,
+    canon -- as `args`, from a SeqPack (anything with arrays() and k), a tuple (packed, run_start, run_len, genome_run_off, k) of host
+    arrays, or (None, runs, k) for the stream a sketcher ingested last (packed == NULL).  Holds the arrays for the call."""
+
+    def __init__(self, src, canon):
+        if hasattr(src, "arrays"):
+            src = tuple(src.arrays()) + (src.k,)
+        elif src[0] is None:
+            src = (None,) + tuple(src[1][:3]) + (src[2],)
+        packed, rs, rl, go, self.k = src
+        self.packed = None if packed is None else np.ascontiguousarray(packed, np.uint8)
+        self.rs, self.rl, self.go = np.ascontiguousarray(rs, np.uint64), np.ascontiguousarray(rl, np.uint32), np.ascontiguousarray(go, np.uint64)
+        self.n = self.go.size - 1
+        self.args = (_np_ptr(self.packed), 0 if packed is None else self.packed.size, _np_ptr(self.rs), _np_ptr(self.rl), self.rs.size,
+                     _np_ptr(self.go), self.n, self.k, int(canon))
+
+    @property
+    def nkmers(self):
+        """k-mers of all runs: the most entries an exact count can return"""
+        return int(self.rl.astype(np.int64).sum()) - (self.k - 1) * self.rl.size if self.rl.size else 0
+
+
 # ---------------------------------------------------------------- host-side primitives
 def wang_hash(x):
     return int(lib().d2g_wang_hash(x & 0xFFFFFFFFFFFFFFFF))
@@ -708,50 +731,38 @@ class Context:
     # -- K1 ------------------------------------------------------------------
     def oph_sketch(self, packed, run_start, run_len, genome_run_off, k, S, canon=True, xormask=0):
         """host arrays -> regs u64 [n][m]"""
-        packed = np.ascontiguousarray(packed, np.uint8)
-        run_start = np.ascontiguousarray(run_start, np.uint64)
-        run_len = np.ascontiguousarray(run_len, np.uint32)
-        genome_run_off = np.ascontiguousarray(genome_run_off, np.uint64)
-        n = genome_run_off.size - 1
-        m = oph_m(S)
-        regs = np.empty((n, m), np.uint64)
-        self._check(lib().d2g_oph_sketch(self._h, _np_ptr(packed), packed.size, _np_ptr(run_start), _np_ptr(run_len),
-                                         run_start.size, _np_ptr(genome_run_off), n, k, int(canon), xormask, S,
-                                         _np_ptr(regs)))
+        return self._oph_sketch((packed, run_start, run_len, genome_run_off, k), S, canon, xormask)
+
+    def _oph_sketch(self, src, S, canon, xormask):
+        r = _Runs(src, canon)
+        regs = np.empty((r.n, oph_m(S)), np.uint64)
+        self._check(lib().d2g_oph_sketch(self._h, *r.args, xormask, S, _np_ptr(regs)))
         return regs
 
     def oph_sketch_seqpack(self, sp: SeqPack, S, canon=True, xormask=0):
-        packed, rs, rl, go = sp.arrays()
-        return self.oph_sketch(packed, rs, rl, go, sp.k, S, canon, xormask)
+        return self._oph_sketch(sp, S, canon, xormask)
 
     def oph_sketch_counts(self, packed, run_start, run_len, genome_run_off, k, S, canon=True, xormask=0):
         """host arrays -> (regs u64 [n][m], counts u32 [n][m]): K1, then how often the k-mer behind each register occurred"""
-        packed = np.ascontiguousarray(packed, np.uint8)
-        run_start = np.ascontiguousarray(run_start, np.uint64)
-        run_len = np.ascontiguousarray(run_len, np.uint32)
-        genome_run_off = np.ascontiguousarray(genome_run_off, np.uint64)
-        n = genome_run_off.size - 1
-        m = oph_m(S)
-        regs = np.empty((n, m), np.uint64)
-        counts = np.empty((n, m), np.uint32)
-        self._check(lib().d2g_oph_sketch_counts(self._h, _np_ptr(packed), packed.size, _np_ptr(run_start), _np_ptr(run_len),
-                                                run_start.size, _np_ptr(genome_run_off), n, k, int(canon), xormask, S,
-                                                _np_ptr(regs), _np_ptr(counts)))
+        return self._oph_sketch_counts((packed, run_start, run_len, genome_run_off, k), S, canon, xormask)
+
+    def _oph_sketch_counts(self, src, S, canon, xormask):
+        r = _Runs(src, canon)
+        regs = np.empty((r.n, oph_m(S)), np.uint64)
+        counts = np.empty((r.n, oph_m(S)), np.uint32)
+        self._check(lib().d2g_oph_sketch_counts(self._h, *r.args, xormask, S, _np_ptr(regs), _np_ptr(counts)))
         return regs, counts
 
     def oph_sketch_counts_seqpack(self, sp: SeqPack, S, canon=True, xormask=0):
-        packed, rs, rl, go = sp.arrays()
-        return self.oph_sketch_counts(packed, rs, rl, go, sp.k, S, canon, xormask)
+        return self._oph_sketch_counts(sp, S, canon, xormask)
 
     def oph_sketch_mincount_seqpack(self, sp: SeqPack, S, mincount, canon=True, xormask=0, counts=False):
         """One-Permutation registers over the k-mers seen at least `mincount` times (sketch -m; mincount < 2: the plain sketch)
         -> regs u64 [n][m], or (regs, counts u32 [n][m]) with counts=True"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        regs = np.empty((n, oph_m(S)), np.uint64)
-        cnts = np.empty((n, oph_m(S)), np.uint32) if counts else None
-        self._check(lib().d2g_oph_sketch_mincount(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
-                                                  sp.k, int(canon), xormask, S, mincount, _np_ptr(regs), _np_ptr(cnts) if counts else None))
+        r = _Runs(sp, canon)
+        regs = np.empty((r.n, oph_m(S)), np.uint64)
+        cnts = np.empty((r.n, oph_m(S)), np.uint32) if counts else None
+        self._check(lib().d2g_oph_sketch_mincount(self._h, *r.args, xormask, S, mincount, _np_ptr(regs), _np_ptr(cnts)))
         return (regs, cnts) if counts else regs
 
     def oph_sketch_mincount_dev(self, plan, packed_dev_ptr, S, mincount, regs_dev_ptr, canon=True, xormask=0, stream=None):
@@ -764,13 +775,10 @@ class Context:
     # -- K3 (--multiset: exact k-mer counts -> BagMinHash) ---------------------
     def bmh_sketch_seqpack(self, sp: "SeqPack", S, canon=True, xormask=0, count_threshold=0.0):
         """-> (sig float64[n][S], total_weight float64[n])"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        sig = np.empty((n, S), np.float64)
-        tw = np.empty(n, np.float64)
-        self._check(lib().d2g_bmh_sketch(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                         _np_ptr(go), n, sp.k, int(canon), xormask, S, count_threshold,
-                                         _np_ptr(sig), _np_ptr(tw)))
+        r = _Runs(sp, canon)
+        sig = np.empty((r.n, S), np.float64)
+        tw = np.empty(r.n, np.float64)
+        self._check(lib().d2g_bmh_sketch(self._h, *r.args, xormask, S, count_threshold, _np_ptr(sig), _np_ptr(tw)))
         return sig, tw
 
     def bmh_sketch_dev(self, plan, packed_dev_ptr, S, sig_dev_ptr, tw_dev_ptr, canon=True, xormask=0, count_threshold=0.0,
@@ -780,20 +788,17 @@ class Context:
 
     def kmer_count(self, packed, run_start, run_len, genome_run_off, k, canon=True, xormask=0, count_threshold=0.0):
         """host arrays (any run table over `packed`) -> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
-        packed = np.ascontiguousarray(packed, np.uint8)
-        rs = np.ascontiguousarray(run_start, np.uint64)
-        rl = np.ascontiguousarray(run_len, np.uint32)
-        go = np.ascontiguousarray(genome_run_off, np.uint64)
-        n = go.size - 1
-        cap = int(rl.astype(np.int64).sum()) - (k - 1) * rl.size if rl.size else 0
+        return self._kmer_count((packed, run_start, run_len, genome_run_off, k), canon, xormask, count_threshold)
+
+    def _kmer_count(self, src, canon, xormask, count_threshold):
+        r = _Runs(src, canon)
+        cap = r.nkmers
         keys = np.empty(max(cap, 1), np.uint64)
         counts = np.empty(max(cap, 1), np.uint32)
-        off = np.zeros(n + 1, np.uint64)
-        self._check(lib().d2g_kmer_count(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                         _np_ptr(go), n, k, int(canon), xormask, count_threshold,
-                                         _np_ptr(keys), _np_ptr(counts), cap, _np_ptr(off)))
+        off = np.zeros(r.n + 1, np.uint64)
+        self._check(lib().d2g_kmer_count(self._h, *r.args, xormask, count_threshold, _np_ptr(keys), _np_ptr(counts), cap, _np_ptr(off)))
         out = []
-        for g in range(n):
+        for g in range(r.n):
             k_, c_ = keys[int(off[g]):int(off[g + 1])], counts[int(off[g]):int(off[g + 1])]
             o = np.argsort(k_, kind="stable")
             out.append((k_[o].copy(), c_[o].copy()))
@@ -801,23 +806,12 @@ class Context:
 
     def kmer_count_seqpack(self, sp: "SeqPack", canon=True, xormask=0, count_threshold=0.0):
         """-> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
-        packed, rs, rl, go = sp.arrays()
-        return self.kmer_count(packed, rs, rl, go, sp.k, canon, xormask, count_threshold)
+        return self._kmer_count(sp, canon, xormask, count_threshold)
 
     def kmer_sets_seqpack(self, sp: "SeqPack", canon=True, xormask=0, count_threshold=0.0, counts=True):
         """the exact k-mer sets, sorted on the device -> (keys uint64[total], counts uint32[total] or None, set_off uint64[n+1],
         cards uint64[n][2] = (distinct keys, sum of the counts))"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        cap = sum(sp.nkmers(g) for g in range(n))
-        keys = np.empty(max(cap, 1), np.uint64)
-        cnts = np.empty(max(cap, 1), np.uint32) if counts else None
-        off = np.zeros(n + 1, np.uint64)
-        cards = np.zeros((n, 2), np.uint64)
-        self._check(lib().d2g_kmer_sets(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n, sp.k,
-                                        int(canon), xormask, count_threshold, _np_ptr(keys), _np_ptr(cnts), cap, _np_ptr(off), _np_ptr(cards)))
-        total = int(off[n])
-        return keys[:total], (cnts[:total] if counts else None), off, cards
+        return _kmer_sets(self, lib().d2g_kmer_sets, self._h, _Runs(sp, canon), xormask, count_threshold, counts)
 
     def kmer_sets_dev(self, plan, packed_dev_ptr, keys_dev_ptr, counts_dev_ptr, cap, set_off_dev_ptr, cards_dev_ptr, canon=True, xormask=0,
                       count_threshold=0.0, stream=None):
@@ -842,11 +836,9 @@ class Context:
 
     def kmer_distinct_seqpack(self, sp: "SeqPack", canon=True, xormask=0):
         """-> uint64[n]: exact number of distinct masked k-mers per genome"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        out = np.zeros(n, np.uint64)
-        self._check(lib().d2g_kmer_distinct(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                            _np_ptr(go), n, sp.k, int(canon), xormask, _np_ptr(out)))
+        r = _Runs(sp, canon)
+        out = np.zeros(r.n, np.uint64)
+        self._check(lib().d2g_kmer_distinct(self._h, *r.args, xormask, _np_ptr(out)))
         return out
 
     def bmh_from_weighted(self, ids, weights, set_off, S):
@@ -901,10 +893,9 @@ class Context:
     # -- K1f (--filterset: k-mers every sketch skips) ---------------------------
     def kmer_filter(self, sp: "SeqPack", canon=True):
         """the k-mers of ALL genomes of `sp` as one device-resident set (host-pointer form; synchronises)"""
-        packed, rs, rl, go = sp.arrays()
+        r = _Runs(sp, canon)
         h = _vp()
-        self._check(lib().d2g_kmer_filter_create(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, sp.k,
-                                                 int(canon), C.byref(h)))
+        self._check(lib().d2g_kmer_filter_create(self._h, *r.args[:5], *r.args[7:], C.byref(h)))      # no genomes: all runs feed one set
         return KmerFilter(self, h, sp.k, bool(canon))
 
     def kmer_filter_dev(self, plan, packed_dev_ptr, canon=True, stream=None):
@@ -1040,6 +1031,18 @@ def _knn_csr(ctx, nrows, K, call):
     return indptr, indices[:need.value].copy(), data[:need.value].copy()
 
 
+def _kmer_sets(ctx, fn, handle, r, xormask, count_threshold, counts):
+    """d2g_kmer_sets / d2g_sketcher_run_sets over the runs `r` -> (keys, counts or None, set_off, cards)"""
+    cap = r.nkmers
+    keys = np.empty(max(cap, 1), np.uint64)
+    cnts = np.empty(max(cap, 1), np.uint32) if counts else None
+    off = np.zeros(r.n + 1, np.uint64)
+    cards = np.zeros((r.n, 2), np.uint64)
+    ctx._check(fn(handle, *r.args, xormask, count_threshold, _np_ptr(keys), _np_ptr(cnts), cap, _np_ptr(off), _np_ptr(cards)))
+    total = int(off[r.n])
+    return keys[:total], (cnts[:total] if counts else None), off, cards
+
+
 class Sketcher:
     """persistent K1 front end (d2g_sketcher): reuses device buffers across calls"""
 
@@ -1055,89 +1058,71 @@ class Sketcher:
         self.ctx._check(lib().d2g_sketcher_set_filter(self._h, filt._h if filt is not None else None))
         self._filter = filt
 
+    def _ingested(self, runs, k):
+        """the source of a run table over the stream ingested last (k: default the k of the ingest)"""
+        return (None, runs, self.k if k is None else k)
+
+    def _run_screen(self, src, screen, genome_row, canon):
+        r = _Runs(src, canon)
+        rows = np.ascontiguousarray(genome_row, np.uint32)
+        assert rows.size == r.n
+        self.ctx._check(lib().d2g_sketcher_run_screen(self._h, *r.args, screen._h, _np_ptr(rows)))
+
     def run_screen(self, sp, screen, genome_row, canon=True):
         """the k-mers of genome g of the pack count towards row genome_row[g] of the Screen; synchronises"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        rows = np.ascontiguousarray(genome_row, np.uint32)
-        assert rows.size == n
-        self.ctx._check(lib().d2g_sketcher_run_screen(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
-                                                      sp.k, int(canon), screen._h, _np_ptr(rows)))
+        self._run_screen(sp, screen, genome_row, canon)
 
     def run_screen_ingested(self, runs, screen, genome_row, canon=True, k=None):
         """run_screen over the stream ingested last (packed == NULL)"""
-        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
-                      np.ascontiguousarray(runs[2], np.uint64))
-        rows = np.ascontiguousarray(genome_row, np.uint32)
-        self.ctx._check(lib().d2g_sketcher_run_screen(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), go.size - 1,
-                                                      self.k if k is None else k, int(canon), screen._h, _np_ptr(rows)))
+        self._run_screen(self._ingested(runs, k), screen, genome_row, canon)
 
     def run_distinct(self, sp, canon=True, xormask=0):
         """-> distinct k-mers per genome, u64 [n] (exact)"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        nd = np.zeros(n, np.uint64)
-        self.ctx._check(lib().d2g_sketcher_run_distinct(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                                        _np_ptr(go), n, sp.k, int(canon), xormask, _np_ptr(nd)))
+        r = _Runs(sp, canon)
+        nd = np.zeros(r.n, np.uint64)
+        self.ctx._check(lib().d2g_sketcher_run_distinct(self._h, *r.args, xormask, _np_ptr(nd)))
         return nd
 
+    def run_sets(self, sp, canon=True, xormask=0, count_threshold=0.0, counts=True):
+        """the exact k-mer sets, sorted on the device, through this sketcher's buffers -> as Context.kmer_sets_seqpack"""
+        return _kmer_sets(self.ctx, lib().d2g_sketcher_run_sets, self._h, _Runs(sp, canon), xormask, count_threshold, counts)
+
     def run(self, sp, S, canon=True, xormask=0):
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        regs = np.empty((n, oph_m(S)), np.uint64)
-        self.ctx._check(lib().d2g_sketcher_run(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                               _np_ptr(go), n, sp.k, int(canon), xormask, S, _np_ptr(regs)))
+        r = _Runs(sp, canon)
+        regs = np.empty((r.n, oph_m(S)), np.uint64)
+        self.ctx._check(lib().d2g_sketcher_run(self._h, *r.args, xormask, S, _np_ptr(regs)))
         return regs
 
     def run_counts(self, sp, S, canon=True, xormask=0):
         """-> (regs u64 [n][m], counts u32 [n][m])"""
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        regs = np.empty((n, oph_m(S)), np.uint64)
-        counts = np.empty((n, oph_m(S)), np.uint32)
-        self.ctx._check(lib().d2g_sketcher_run_counts(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                                      _np_ptr(go), n, sp.k, int(canon), xormask, S, _np_ptr(regs), _np_ptr(counts)))
+        r = _Runs(sp, canon)
+        regs = np.empty((r.n, oph_m(S)), np.uint64)
+        counts = np.empty((r.n, oph_m(S)), np.uint32)
+        self.ctx._check(lib().d2g_sketcher_run_counts(self._h, *r.args, xormask, S, _np_ptr(regs), _np_ptr(counts)))
         return regs, counts
 
     def run_counts_ingested(self, runs, S, canon=True, xormask=0, k=None):
         """run_counts over the stream ingested last (packed == NULL)"""
-        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
-                      np.ascontiguousarray(runs[2], np.uint64))
-        n = go.size - 1
-        regs = np.empty((n, oph_m(S)), np.uint64)
-        counts = np.empty((n, oph_m(S)), np.uint32)
-        self.ctx._check(lib().d2g_sketcher_run_counts(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
-                                                      self.k if k is None else k, int(canon), xormask, S, _np_ptr(regs), _np_ptr(counts)))
-        return regs, counts
-
-    def _run_mincount(self, packed, nbytes, rs, rl, go, k, S, mincount, canon, xormask, counts):
-        n = go.size - 1
-        regs = np.empty((n, oph_m(S)), np.uint64)
-        cnts = np.empty((n, oph_m(S)), np.uint32) if counts else None
-        self.ctx._check(lib().d2g_sketcher_run_mincount(self._h, packed, nbytes, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n, k,
-                                                        int(canon), xormask, S, mincount, _np_ptr(regs), _np_ptr(cnts) if counts else None))
-        return (regs, cnts) if counts else regs
+        return self.run_counts(self._ingested(runs, k), S, canon, xormask)
 
     def run_mincount(self, sp, S, mincount, canon=True, xormask=0, counts=False):
         """registers over the k-mers seen at least `mincount` times (mincount < 2: run / run_counts) -> regs u64 [n][m], or
         (regs, counts u32 [n][m]) with counts=True"""
-        packed, rs, rl, go = sp.arrays()
-        return self._run_mincount(_np_ptr(packed), packed.size, rs, rl, go, sp.k, S, mincount, canon, xormask, counts)
+        r = _Runs(sp, canon)
+        regs = np.empty((r.n, oph_m(S)), np.uint64)
+        cnts = np.empty((r.n, oph_m(S)), np.uint32) if counts else None
+        self.ctx._check(lib().d2g_sketcher_run_mincount(self._h, *r.args, xormask, S, mincount, _np_ptr(regs), _np_ptr(cnts)))
+        return (regs, cnts) if counts else regs
 
     def run_mincount_ingested(self, runs, S, mincount, canon=True, xormask=0, counts=False, k=None):
         """run_mincount over the stream ingested last (packed == NULL)"""
-        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
-                      np.ascontiguousarray(runs[2], np.uint64))
-        return self._run_mincount(None, 0, rs, rl, go, self.k if k is None else k, S, mincount, canon, xormask, counts)
+        return self.run_mincount(self._ingested(runs, k), S, mincount, canon, xormask, counts)
 
     def run_bmh(self, sp, S, canon=True, xormask=0, count_threshold=0.0):
-        packed, rs, rl, go = sp.arrays()
-        n = go.size - 1
-        sig = np.empty((n, S), np.float64)
-        tw = np.empty(n, np.float64)
-        self.ctx._check(lib().d2g_sketcher_run_bmh(self._h, _np_ptr(packed), packed.size, _np_ptr(rs), _np_ptr(rl), rs.size,
-                                                   _np_ptr(go), n, sp.k, int(canon), xormask, S, count_threshold,
-                                                   _np_ptr(sig), _np_ptr(tw)))
+        r = _Runs(sp, canon)
+        sig = np.empty((r.n, S), np.float64)
+        tw = np.empty(r.n, np.float64)
+        self.ctx._check(lib().d2g_sketcher_run_bmh(self._h, *r.args, xormask, S, count_threshold, _np_ptr(sig), _np_ptr(tw)))
         return sig, tw
 
     # -- K0: FASTA bytes -> packed run stream on the GPU ------------------------------------------
@@ -1186,23 +1171,10 @@ class Sketcher:
     def run_ingested(self, runs, S, canon=True, xormask=0, k=None):
         """K1 over the stream ingested last (packed == NULL): -> regs u64 [n][m].  `runs` may be any run table inside the stream's
         extent, and k any k its runs allow (default: the k of the ingest)"""
-        rs, rl, go = (np.ascontiguousarray(runs[0], np.uint64), np.ascontiguousarray(runs[1], np.uint32),
-                      np.ascontiguousarray(runs[2], np.uint64))
-        n = go.size - 1
-        regs = np.empty((n, oph_m(S)), np.uint64)
-        self.ctx._check(lib().d2g_sketcher_run(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n,
-                                               self.k if k is None else k, int(canon),
-                                               xormask, S, _np_ptr(regs)))
-        return regs
+        return self.run(self._ingested(runs, k), S, canon, xormask)
 
     def run_bmh_ingested(self, runs, S, canon=True, xormask=0, count_threshold=0.0):
-        rs, rl, go = runs[0], runs[1], runs[2]
-        n = go.size - 1
-        sig = np.empty((n, S), np.float64)
-        tw = np.empty(n, np.float64)
-        self.ctx._check(lib().d2g_sketcher_run_bmh(self._h, None, 0, _np_ptr(rs), _np_ptr(rl), rs.size, _np_ptr(go), n, self.k, int(canon),
-                                                   xormask, S, count_threshold, _np_ptr(sig), _np_ptr(tw)))
-        return sig, tw
+        return self.run_bmh(self._ingested(runs, None), S, canon, xormask, count_threshold)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -102,9 +102,12 @@ void d2g_warm_filter() {
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&filter_build_kernel));
 }
 
-// the table of the k-mers that the walk of `km` over nblk blocks enumerates (nkmers of them), built on `s`; whatever filter km
+// the table of the k-mers that the walk of the batch enumerates (nkmers of them), built on its stream; whatever filter the batch
 // carries plays no part in building one
-static int filter_build(d2g_ctx *ctx, KmerArgs km, size_t nblk, uint64_t nkmers, int k, int canon, hipStream_t s, d2g_kmer_filter **out) {
+static int filter_build(const KmerBatch &b, uint64_t nkmers, d2g_kmer_filter **out) {
+    d2g_ctx *ctx = b.ctx;
+    hipStream_t s = b.s;
+    const int k = b.runs.k, canon = b.runs.canon;
     if (nkmers > (1ull << 31)) {
         ctx->last_error = "k-mer filter of more than 2^31 k-mers (its table would pass 2^32 slots)";
         return D2G_ERR_UNSUPPORTED;
@@ -120,14 +123,14 @@ static int filter_build(d2g_ctx *ctx, KmerArgs km, size_t nblk, uint64_t nkmers,
     d2g_timer tm(ctx, &ctx->ev_filter, s);
     D2G_HIP(ctx, hipMemsetAsync(f->d_tab, 0xFF, f->slots * sizeof(uint64_t), s));
     D2G_HIP(ctx, hipMemsetAsync(f->d_tab + f->slots, 0, 2 * sizeof(uint64_t), s));
-    if (nblk) {
+    if (b.nblk) {
         FilterBuildArgs a;
         KmerArgs self;
         d2g_filter_args(f, &self);
-        a.km = km;
+        a.km = b.km;
         a.km.ftab = nullptr;
         a.tab = f->d_tab; a.mask = self.fmask; a.shift = self.fshift;
-        hipLaunchKernelGGL(filter_build_kernel, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a);
+        hipLaunchKernelGGL(filter_build_kernel, dim3((unsigned)b.nblk), dim3(K1_THREADS), 0, s, a);
     }
     tm.stop();
     D2G_HIP(ctx, hipGetLastError());
@@ -147,10 +150,9 @@ int d2g_kmer_filter_create_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uin
                                d2g_kmer_filter **out) {
     if (!ctx || !plan || !out) return D2G_ERR_INVALID;
     *out = nullptr;
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
-    return filter_build(ctx, d2g_plan_args(plan, packed_dev, canon), plan->nblk, plan->nkmers, plan->k, canon, as_stream(stream), out);
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    return filter_build(b, plan->nkmers, out);
 }
 
 int d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
@@ -160,12 +162,11 @@ int d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_by
     if (!ctx || !out) return D2G_ERR_INVALID;
     *out = nullptr;
     return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) -> int {
-        KmerArgs km;
-        size_t nblk = 0;
+        KmerBatch b;
         PlanHost ph;
-        if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, &ph)) return rc;
+        if (int rc = d2g_sketcher_stage(sk, in, &b, &ph)) return rc;
         d2g_kmer_filter *f = nullptr;
-        if (int rc = filter_build(ctx, km, nblk, ph.nkmers, k, canon, sk->stream, &f)) return rc;
+        if (int rc = filter_build(b, ph.nkmers, &f)) return rc;
         const hipError_t e = hipStreamSynchronize(sk->stream);    // the stream and the staged input are released on return
         if (e != hipSuccess) { d2g_kmer_filter_destroy(f); return d2g_hip_status(ctx, e, "k-mer filter build"); }
         *out = f;

@@ -52,12 +52,6 @@ inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &l
     a.k = k; a.canon = canon; a.blk0 = 0;
     return a;
 }
-inline KmerArgs d2g_plan_args(const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon) {
-    KmerArgs a = d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon);
-    d2g_filter_args(plan->filter, &a);
-    return a;
-}
-
 // Host ingest feeds K1 in groups of inputs; re-allocating device buffers and uploading eight
 // small tables per group costs ~20 ms, the kernel ~0.1 ms.  The sketcher keeps grow-only device
 // buffers and ships all launch tables in ONE copy from a pinned arena.
@@ -80,15 +74,28 @@ bool d2g_k0_ingested(const d2g_sketcher *sk, uint64_t *nbases);   // d_packed ho
 void d2g_k0_invalidate(d2g_sketcher *sk);
 
 
-// validate + upload one batch (launch tables in one pinned-arena copy, packed stream through the
-// pinned stage) on sk->stream; fills `out` with device pointers, `nblk` with the grid size, `ph_out` (if given) with the plan.
+// One batch of genomes ready for a walker: all that an operation behind a front door (K1, K1b, K3, the filter build, the screen)
+// takes.  A view; exactly two functions make one, and each refuses before it touches the device.
+struct KmerBatch {
+    d2g_ctx *ctx = nullptr;
+    hipStream_t s = nullptr;
+    KmerArgs km{};                             // launch tables and packed stream on the device, the attached filter applied
+    size_t nblk = 0;                           // workgroups of the walk
+    PackedRuns runs{};                         // the host run tables (packed == nullptr): K3's layout, the screen's accounting
+    d2g_k3_state **k3 = nullptr;               // where the K3 work state of this batch's owner lives: &sk->k3 or &ctx->k3
+};
+// a plan applied to a device stream on the caller's stream.  Refuses, in this order and before the first HIP call: a plan of
+// another context, a stream that is not 4-byte aligned, a null stream under a plan with blocks, a filter that does not fit
+// (d2g_filter_check).  The ONLY reader of a plan's launch tables.
+int d2g_plan_batch(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, void *stream, KmerBatch *out);
+// validate + upload one batch (launch tables in one pinned-arena copy, packed stream through the pinned stage) on sk->stream;
+// `ph_out` (if given) receives the plan.
 // in.packed == nullptr: the stream d2g_sketcher_ingest_fasta left in the device buffer is used as it is.
-int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &in, KmerArgs *out, size_t *nblk, PlanHost *ph_out);
+int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &in, KmerBatch *out, PlanHost *ph_out);
 
-// K3o (d2g_k3_bmh.hip) behind the min-count entry points of d2g_k1.hip: the batch is staged (or a plan applied) and `regs_dev` [n][m]
-// pre-set to ~0 on `s`; lowers the registers over the k-mers seen at least `mincount` (>= 2) times, waits for the status word
-int d2g_k3_ophmin(d2g_ctx *ctx, d2g_k3_state **st, const PackedRuns &in, const KmerArgs &km, size_t nblk, uint64_t xormask, size_t m,
-                  uint32_t mincount, uint64_t *regs_dev, hipStream_t s);
+// K3o (d2g_k3_bmh.hip) behind the min-count entry points of d2g_k1.hip: `regs_dev` [n][m] is pre-set to ~0 on the batch's stream;
+// lowers the registers over the k-mers seen at least `mincount` (>= 2) times, waits for the status word
+int d2g_k3_ophmin(const KmerBatch &b, uint64_t xormask, size_t m, uint32_t mincount, uint64_t *regs_dev);
 
 // A host-pointer one-shot is the sketcher form on a sketcher that lives for one call: f(sk), and the sketcher goes on every path.
 template <class F> int d2g_with_sketcher(d2g_ctx *ctx, F &&f) {

@@ -139,88 +139,59 @@ int launch_k1_any(d2g_ctx *ctx, void (*const kerns[8])(Args), const Args &a, siz
     return D2G_OK;
 }
 
-// K1 over a staged batch or an applied plan: empty registers for n genomes, then the walk (if there is a block to walk)
-int k1_fill_regs(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n, size_t m, uint64_t xormask, uint64_t *regs_dev, hipStream_t s) {
-    D2G_HIP(ctx, hipMemsetAsync(regs_dev, 0xFF, n * m * sizeof(uint64_t), s));       // registers_ initialise to T(-1): oph.h:147,233
-    if (nblk == 0) return D2G_OK;
-    const K1Args a{km, regs_dev, xormask, d2g_oph_xor_const(), (uint32_t)m};
-    return launch_k1_any(ctx, k1_kernels, a, nblk, sizeof(uint64_t), &ctx->ev_k1, s);
+// K1 over a batch: empty registers for its genomes, then the walk (if there is a block to walk)
+int k1_fill_regs(const KmerBatch &b, size_t m, uint64_t xormask, uint64_t *regs_dev) {
+    D2G_HIP(b.ctx, hipMemsetAsync(regs_dev, 0xFF, b.runs.n * m * sizeof(uint64_t), b.s));   // registers_ initialise to T(-1): oph.h:147,233
+    if (b.nblk == 0) return D2G_OK;
+    const K1Args a{b.km, regs_dev, xormask, d2g_oph_xor_const(), (uint32_t)m};
+    return launch_k1_any(b.ctx, k1_kernels, a, b.nblk, sizeof(uint64_t), &b.ctx->ev_k1, b.s);
 }
 
 // K1b over the same batch, behind K1 on the same stream: zero counters, then the second walk
-int k1_fill_counts(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n, size_t m, uint64_t xormask, const uint64_t *regs_dev,
-                   uint32_t *counts_dev, hipStream_t s) {
-    D2G_HIP(ctx, hipMemsetAsync(counts_dev, 0, n * m * sizeof(uint32_t), s));        // counts_ start at 0: oph.h:148,234
-    if (nblk == 0) return D2G_OK;
-    const K1CountArgs a{km, regs_dev, counts_dev, xormask, d2g_oph_xor_const(), (uint32_t)m};
-    return launch_k1_any(ctx, k1_count_kernels, a, nblk, sizeof(uint64_t) + sizeof(uint32_t), &ctx->ev_k1count, s);
+int k1_fill_counts(const KmerBatch &b, size_t m, uint64_t xormask, const uint64_t *regs_dev, uint32_t *counts_dev) {
+    D2G_HIP(b.ctx, hipMemsetAsync(counts_dev, 0, b.runs.n * m * sizeof(uint32_t), b.s));    // counts_ start at 0: oph.h:148,234
+    if (b.nblk == 0) return D2G_OK;
+    const K1CountArgs a{b.km, regs_dev, counts_dev, xormask, d2g_oph_xor_const(), (uint32_t)m};
+    return launch_k1_any(b.ctx, k1_count_kernels, a, b.nblk, sizeof(uint64_t) + sizeof(uint32_t), &b.ctx->ev_k1count, b.s);
 }
 
-// what the plan forms check alike, before the device is touched
-int check_dev_call(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, size_t sketchsize) {
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
+// the registers of a batch.  mincount < 2 is the plain sketch, K1 (set_mincount only takes effect above 1: oph.h:154-159); sketch -m c:
+// empty registers lowered over the k-mers seen at least `mincount` times (K3o, d2g_k3_bmh.hip), which waits for its status word
+int oph_regs(const KmerBatch &b, size_t m, uint64_t xormask, uint32_t mincount, uint64_t *regs_dev) {
+    if (mincount < 2) return k1_fill_regs(b, m, xormask, regs_dev);
+    D2G_HIP(b.ctx, hipMemsetAsync(regs_dev, 0xFF, b.runs.n * m * sizeof(uint64_t), b.s));
+    return b.nblk ? d2g_k3_ophmin(b, xormask, m, mincount, regs_dev) : D2G_OK;
+}
+
+// what every K1 form refuses alike
+int check_sketchsize(d2g_ctx *ctx, size_t sketchsize) {
     D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
-    return d2g_filter_check(ctx, plan->filter, plan->k, canon);
+    return D2G_OK;
 }
 
-// the sketcher forms: the batch staged on the sketcher's stream, K1 (and K1b) behind it, the results copied back, ONE wait
-int sketcher_run(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out,
-                 bool counts) {
+// the sketcher forms: the batch staged on the sketcher's stream, the registers (and, `counts`, K1b over them: LazyOnePermSetSketch's
+// counts_ under set_mincount, oph.h:188-205, is what K1b defines for any registers) behind it, the results copied back, ONE wait
+int sketcher_run(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out,
+                 uint32_t *counts_out, bool counts) {
     if (!sk) return D2G_ERR_INVALID;
     d2g_ctx *ctx = sk->ctx;
     const size_t n = in.n;
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
+    if (int rc = check_sketchsize(ctx, sketchsize)) return rc;
     D2G_CHECK(ctx, (regs_out != nullptr && (counts_out != nullptr || !counts)) || n == 0, counts ? "null regs_out or counts_out" : "null regs_out");
     if (counts) {                                                                     // before the stage touches the device stream
         std::string err;
         if (int rc = d2g_plan_err(ctx, d2g_plan_check_count_range(in, err), err)) return rc;
     }
-    KmerArgs km;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, nullptr)) return rc;
+    KmerBatch b;
+    if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
     const size_t m = d2g_oph_m(sketchsize), nm = std::max<size_t>(n * m, 1);
     if (int rc = sk->d_regs.grow(ctx, nm, 4096)) return rc;
     if (counts) if (int rc = sk->d_counts.grow(ctx, nm, 4096)) return rc;
-    hipStream_t s = sk->stream;
-    if (int rc = k1_fill_regs(ctx, km, nblk, n, m, xormask, sk->d_regs, s)) return rc;
-    if (counts) if (int rc = k1_fill_counts(ctx, km, nblk, n, m, xormask, sk->d_regs, sk->d_counts, s)) return rc;
-    if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (n && counts) D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    D2G_HIP(ctx, hipStreamSynchronize(s));
-    return D2G_OK;
-}
-
-// sketch -m c: registers over the k-mers seen at least `mincount` times (K3o, d2g_k3_bmh.hip), then -- counts_out given -- K1b over
-// those registers: LazyOnePermSetSketch's counts_ under set_mincount (oph.h:188-205) is what K1b defines for any registers.
-// mincount < 2 is the plain sketch (set_mincount only takes effect above 1: oph.h:154-159)
-int sketcher_run_mincount(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out,
-                          uint32_t *counts_out) {
-    if (!sk) return D2G_ERR_INVALID;
-    const bool counts = counts_out != nullptr;
-    if (mincount < 2) return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, counts);
-    d2g_ctx *ctx = sk->ctx;
-    const size_t n = in.n;
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 31), "sketchsize out of range");
-    D2G_CHECK(ctx, regs_out != nullptr || n == 0, "null regs_out");
-    if (counts) {
-        std::string err;
-        if (int rc = d2g_plan_err(ctx, d2g_plan_check_count_range(in, err), err)) return rc;
-    }
-    KmerArgs km;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, nullptr)) return rc;
-    const size_t m = d2g_oph_m(sketchsize), nm = std::max<size_t>(n * m, 1);
-    if (int rc = sk->d_regs.grow(ctx, nm, 4096)) return rc;
-    if (counts) if (int rc = sk->d_counts.grow(ctx, nm, 4096)) return rc;
-    hipStream_t s = sk->stream;
-    D2G_HIP(ctx, hipMemsetAsync(sk->d_regs, 0xFF, n * m * sizeof(uint64_t), s));
-    if (nblk) if (int rc = d2g_k3_ophmin(ctx, &sk->k3, in, km, nblk, xormask, m, mincount, sk->d_regs, s)) return rc;
-    if (counts) if (int rc = k1_fill_counts(ctx, km, nblk, n, m, xormask, sk->d_regs, sk->d_counts, s)) return rc;
-    if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    if (n && counts) D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    D2G_HIP(ctx, hipStreamSynchronize(s));
+    if (int rc = oph_regs(b, m, xormask, mincount, sk->d_regs)) return rc;
+    if (counts) if (int rc = k1_fill_counts(b, m, xormask, sk->d_regs, sk->d_counts)) return rc;
+    if (n) D2G_HIP(ctx, hipMemcpyAsync(regs_out, sk->d_regs, n * m * sizeof(uint64_t), hipMemcpyDeviceToHost, b.s));
+    if (n && counts) D2G_HIP(ctx, hipMemcpyAsync(counts_out, sk->d_counts, n * m * sizeof(uint32_t), hipMemcpyDeviceToHost, b.s));
+    D2G_HIP(ctx, hipStreamSynchronize(b.s));
     return D2G_OK;
 }
 
@@ -264,39 +235,32 @@ int d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t 
 int d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon,
                        uint64_t xormask, size_t sketchsize, uint64_t *regs_out_dev, void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    if (int rc = check_dev_call(ctx, plan, packed_dev, canon, sketchsize)) return rc;
+    if (int rc = check_sketchsize(ctx, sketchsize)) return rc;
     D2G_CHECK(ctx, regs_out_dev != nullptr, "null regs_out");
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    return k1_fill_regs(ctx, d2g_plan_args(plan, packed_dev, canon), plan->nblk, plan->n, d2g_oph_m(sketchsize), xormask, regs_out_dev,
-                        as_stream(stream));
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    return k1_fill_regs(b, d2g_oph_m(sketchsize), xormask, regs_out_dev);
 }
 
 int d2g_oph_count_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
                       size_t sketchsize, const uint64_t *regs_dev, uint32_t *counts_out_dev, void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    if (int rc = check_dev_call(ctx, plan, packed_dev, canon, sketchsize)) return rc;
+    if (int rc = check_sketchsize(ctx, sketchsize)) return rc;
     D2G_CHECK(ctx, regs_dev != nullptr && counts_out_dev != nullptr, "null regs or counts_out");
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    return k1_fill_counts(ctx, d2g_plan_args(plan, packed_dev, canon), plan->nblk, plan->n, d2g_oph_m(sketchsize), xormask, regs_dev,
-                          counts_out_dev, as_stream(stream));
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    return k1_fill_counts(b, d2g_oph_m(sketchsize), xormask, regs_dev, counts_out_dev);
 }
 
 int d2g_oph_sketch_mincount_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, uint64_t xormask,
                                 size_t sketchsize, uint32_t mincount, uint64_t *regs_out_dev, void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    if (int rc = check_dev_call(ctx, plan, packed_dev, canon, sketchsize)) return rc;
+    if (int rc = check_sketchsize(ctx, sketchsize)) return rc;
     D2G_CHECK(ctx, regs_out_dev != nullptr || plan->n == 0, "null regs_out");
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = as_stream(stream);
-    const size_t m = d2g_oph_m(sketchsize);
-    const KmerArgs km = d2g_plan_args(plan, packed_dev, canon);
-    if (mincount < 2) {
-        if (int rc = k1_fill_regs(ctx, km, plan->nblk, plan->n, m, xormask, regs_out_dev, s)) return rc;
-    } else {
-        D2G_HIP(ctx, hipMemsetAsync(regs_out_dev, 0xFF, plan->n * m * sizeof(uint64_t), s));
-        if (plan->nblk) return d2g_k3_ophmin(ctx, &ctx->k3, plan->runs(canon), km, plan->nblk, xormask, m, mincount, regs_out_dev, s);
-    }
-    D2G_HIP(ctx, hipStreamSynchronize(s));
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    if (int rc = oph_regs(b, d2g_oph_m(sketchsize), xormask, mincount, regs_out_dev)) return rc;
+    D2G_HIP(ctx, hipStreamSynchronize(b.s));
     return D2G_OK;
 }
 
@@ -326,35 +290,35 @@ int d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_byte
                      const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                      uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    return sketcher_run(sk, in, xormask, sketchsize, regs_out, nullptr, false);
+    return sketcher_run(sk, in, xormask, sketchsize, 0, regs_out, nullptr, false);
 }
 
 int d2g_sketcher_run_counts(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                             const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                             uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, true);
+    return sketcher_run(sk, in, xormask, sketchsize, 0, regs_out, counts_out, true);
 }
 
 int d2g_oph_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                    const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
                    int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, regs_out, nullptr, false); });
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, 0, regs_out, nullptr, false); });
 }
 
 int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                           const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k,
                           int canon, uint64_t xormask, size_t sketchsize, uint64_t *regs_out, uint32_t *counts_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, regs_out, counts_out, true); });
+    return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) { return sketcher_run(sk, in, xormask, sketchsize, 0, regs_out, counts_out, true); });
 }
 
 int d2g_sketcher_run_mincount(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                               const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                               uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out, uint32_t *counts_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    return sketcher_run_mincount(sk, in, xormask, sketchsize, mincount, regs_out, counts_out);
+    return sketcher_run(sk, in, xormask, sketchsize, mincount, regs_out, counts_out, counts_out != nullptr);
 }
 
 int d2g_oph_sketch_mincount(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
@@ -362,13 +326,25 @@ int d2g_oph_sketch_mincount(d2g_ctx *ctx, const uint8_t *packed, size_t packed_b
                             uint64_t xormask, size_t sketchsize, uint32_t mincount, uint64_t *regs_out, uint32_t *counts_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
     return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) {
-        return sketcher_run_mincount(sk, in, xormask, sketchsize, mincount, regs_out, counts_out);
+        return sketcher_run(sk, in, xormask, sketchsize, mincount, regs_out, counts_out, counts_out != nullptr);
     });
 }
 
 }  // extern "C"
 
-int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerArgs *out, size_t *nblk_out, PlanHost *ph_out) {
+int d2g_plan_batch(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon, void *stream, KmerBatch *out) {
+    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
+    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
+    D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
+    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
+    D2G_HIP(ctx, hipSetDevice(ctx->device));
+    *out = KmerBatch{ctx, as_stream(stream), d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon), plan->nblk, plan->runs(canon),
+                     &ctx->k3};
+    d2g_filter_args(plan->filter, &out->km);
+    return D2G_OK;
+}
+
+int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerBatch *out, PlanHost *ph_out) {
     d2g_ctx *ctx = sk->ctx;
     PackedRuns in = caller;
     if (int rc = d2g_filter_check(ctx, sk->filter, in.k, in.canon)) return rc;   // before the stream, the buffers or an output are touched
@@ -399,9 +375,9 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerArgs *out
         std::memcpy(sk->h_stage, in.packed, in.packed_bytes);
         D2G_HIP(ctx, hipMemcpyAsync(sk->d_packed, sk->h_stage, in.packed_bytes, hipMemcpyHostToDevice, s));
     }
-    *out = d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon);
-    d2g_filter_args(sk->filter, out);
-    *nblk_out = nblk;
+    *out = KmerBatch{ctx, s, d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon), nblk, caller, &sk->k3};
+    out->runs.packed = nullptr; out->runs.packed_bytes = 0;
+    d2g_filter_args(sk->filter, &out->km);
     return D2G_OK;
 }
 

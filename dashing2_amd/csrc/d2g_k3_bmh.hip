@@ -1719,31 +1719,43 @@ int k3_check_status(d2g_ctx *ctx, d2g_k3_state *st, hipStream_t s) {
     return k3_status_error(ctx, status);
 }
 
-// what the sketcher's three forms begin with: its work buffers, the batch staged on its stream, the bucket layout
-int k3_stage(d2g_sketcher *sk, const PackedRuns &in, K3Run &r) {
-    if (!sk->k3) sk->k3 = new (std::nothrow) d2g_k3_state();
-    if (!sk->k3) return D2G_ERR_NOMEM;
-    r.ctx = sk->ctx; r.st = sk->k3; r.s = sk->stream; r.n = in.n;
-    if (int rc = d2g_sketcher_stage(sk, in, &r.km, &r.nblk, nullptr)) return rc;
-    return k3_layout(r.ctx, in, r.kh);
+// what every K3 operation begins with: the work state of the batch's owner (made on first use), the run filled from the batch, the
+// bucket layout.  The only place that fills a K3Run's ctx / st / s / n / km / nblk.
+int k3_begin(const KmerBatch &b, K3Run &r) {
+    if (!*b.k3) *b.k3 = new (std::nothrow) d2g_k3_state();
+    if (!*b.k3) return D2G_ERR_NOMEM;
+    r.ctx = b.ctx; r.st = *b.k3; r.s = b.s; r.n = b.runs.n; r.km = b.km; r.nblk = b.nblk;
+    return k3_layout(b.ctx, b.runs, r.kh);
 }
 
-int sketcher_run_bmh(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, double count_threshold, double *sig_out,
-                     double *total_weight_out) {
-    if (!sk) return D2G_ERR_INVALID;
-    d2g_ctx *ctx = sk->ctx;
-    const size_t n = in.n;
+// BagMinHash.  The checks stand in front of the batch (a stage uploads; a refusal comes before it); the operation leaves registers
+// [n][sketchsize] and total weights [n] in the state and copies them out as `out` says: device to host or device to device
+int bmh_check(d2g_ctx *ctx, size_t n, size_t sketchsize, double count_threshold, const double *sig_out, const double *total_weight_out) {
     D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 24), "sketchsize out of range");
     D2G_CHECK(ctx, (sig_out && total_weight_out) || n == 0, "null output");
     D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
+    return D2G_OK;
+}
+int bmh_sketch(const KmerBatch &b, uint64_t xormask, size_t sketchsize, double count_threshold, double *sig_out, double *total_weight_out,
+               hipMemcpyKind out) {
+    d2g_ctx *ctx = b.ctx;
     K3Run r;
-    if (int rc = k3_stage(sk, in, r)) return rc;
+    if (int rc = k3_begin(b, r)) return rc;
+    const size_t n = r.n;
     if (n == 0) return D2G_OK;
     r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
     if (int rc = r.run(K3Mode::Sketch)) return rc;
-    D2G_HIP(ctx, hipMemcpyAsync(sig_out, r.st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToHost, r.s));
-    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out, r.st->d_tw, n * sizeof(double), hipMemcpyDeviceToHost, r.s));
+    D2G_HIP(ctx, hipMemcpyAsync(sig_out, r.st->d_h, n * sketchsize * sizeof(double), out, r.s));
+    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out, r.st->d_tw, n * sizeof(double), out, r.s));
     return k3_check_status(ctx, r.st, r.s);
+}
+int sketcher_run_bmh(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_t sketchsize, double count_threshold, double *sig_out,
+                     double *total_weight_out) {
+    if (!sk) return D2G_ERR_INVALID;
+    if (int rc = bmh_check(sk->ctx, in.n, sketchsize, count_threshold, sig_out, total_weight_out)) return rc;
+    KmerBatch b;
+    if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
+    return bmh_sketch(b, xormask, sketchsize, count_threshold, sig_out, total_weight_out, hipMemcpyDeviceToHost);
 }
 
 int sketcher_run_distinct(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, uint64_t *ndistinct_out) {
@@ -1751,8 +1763,10 @@ int sketcher_run_distinct(d2g_sketcher *sk, const PackedRuns &in, uint64_t xorma
     d2g_ctx *ctx = sk->ctx;
     const size_t n = in.n;
     D2G_CHECK(ctx, ndistinct_out != nullptr || n == 0, "null output");
+    KmerBatch b;
+    if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
     K3Run r;
-    if (int rc = k3_stage(sk, in, r)) return rc;
+    if (int rc = k3_begin(b, r)) return rc;
     if (n == 0) return D2G_OK;
     const K3Host &kh = r.kh;
     r.xormask = xormask;
@@ -1769,19 +1783,26 @@ int sketcher_run_distinct(d2g_sketcher *sk, const PackedRuns &in, uint64_t xorma
     return D2G_OK;
 }
 
+// the exact (key, count) of every bucket of a begun run (n > 0), left in the state: what the count and both set forms read
+int k3_exact_counts(K3Run &r, uint64_t xormask, double count_threshold) {
+    r.xormask = xormask; r.thr = count_threshold;
+    if (int rc = r.run(K3Mode::Count)) return rc;
+    return k3_check_status(r.ctx, r.st, r.s);
+}
+
 // the distinct (key, count) of every genome, compacted on the host (utility form, not the sketch path)
 int sketcher_kmer_count(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, double count_threshold, uint64_t *keys_out,
                         uint32_t *counts_out, size_t cap, uint64_t *genome_off_out) {
     d2g_ctx *ctx = sk->ctx;
     const size_t n = in.n;
+    KmerBatch b;
+    if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
     K3Run r;
-    if (int rc = k3_stage(sk, in, r)) return rc;
+    if (int rc = k3_begin(b, r)) return rc;
     const K3Host &kh = r.kh; d2g_k3_state *st = r.st;
     for (size_t g = 0; g <= n; ++g) genome_off_out[g] = 0;
     if (n == 0) return D2G_OK;
-    r.xormask = xormask; r.thr = count_threshold;
-    if (int rc = r.run(K3Mode::Count)) return rc;
-    if (int rc = k3_check_status(ctx, st, r.s)) return rc;
+    if (int rc = k3_exact_counts(r, xormask, count_threshold)) return rc;
     std::vector<uint32_t> nd(kh.TB);
     std::vector<uint64_t> boff((size_t)kh.TB + 1);
     std::vector<uint64_t> hk(std::max<uint64_t>(kh.total, 1));
@@ -2014,18 +2035,43 @@ int k3_sorted_sets(K3Run &r, const char *who, uint64_t *keys_dev, uint32_t *coun
     return k3_check_status(ctx, st, s);
 }
 
-// the host-pointer form: sorted on the device into the sketcher's own buffers, then copied out
+// the checks of both forms of the exact sets, in front of the batch; `sfx` names the form's outputs in the refusal ("out", "dev")
+int sets_check(d2g_ctx *ctx, size_t n, double count_threshold, const uint64_t *keys, size_t cap, const uint64_t *set_off, const uint64_t *cards,
+               const char *sfx) {
+    D2G_CHECK(ctx, set_off != nullptr, std::string("null set_off_") + sfx);
+    D2G_CHECK(ctx, cards != nullptr || n == 0, std::string("null cards_") + sfx);
+    D2G_CHECK(ctx, cap == 0 || keys, "null output");
+    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
+    return D2G_OK;
+}
+
+// the device form: k3_sorted_sets straight into the caller's arrays
+int kmer_sets_dev(const KmerBatch &b, uint64_t xormask, double count_threshold, uint64_t *keys_dev, uint32_t *counts_dev, size_t cap,
+                  uint64_t *set_off_dev, uint64_t *cards_dev) {
+    K3Run r;
+    if (int rc = k3_begin(b, r)) return rc;
+    if (r.n == 0) {
+        D2G_HIP(b.ctx, hipMemsetAsync(set_off_dev, 0, sizeof(uint64_t), r.s));
+        return D2G_OK;
+    }
+    if (int rc = k3_exact_counts(r, xormask, count_threshold)) return rc;
+    return k3_sorted_sets(r, "d2g_kmer_sets_dev", keys_dev, counts_dev, cap, set_off_dev, cards_dev, nullptr);
+}
+
+// the host-pointer form: that function on the sketcher's own buffers, then copied out
 int sketcher_kmer_sets(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, double count_threshold, uint64_t *keys_out,
                        uint32_t *counts_out, size_t cap, uint64_t *set_off_out, uint64_t *cards_out) {
+    if (!sk) return D2G_ERR_INVALID;
     d2g_ctx *ctx = sk->ctx;
     const size_t n = in.n;
+    if (int rc = sets_check(ctx, n, count_threshold, keys_out, cap, set_off_out, cards_out, "out")) return rc;
+    KmerBatch b;
+    if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
     K3Run r;
-    if (int rc = k3_stage(sk, in, r)) return rc;
+    if (int rc = k3_begin(b, r)) return rc;
     d2g_k3_state *st = r.st;
     if (n == 0) { set_off_out[0] = 0; return D2G_OK; }
-    r.xormask = xormask; r.thr = count_threshold;
-    if (int rc = r.run(K3Mode::Count)) return rc;
-    if (int rc = k3_check_status(ctx, st, r.s)) return rc;
+    if (int rc = k3_exact_counts(r, xormask, count_threshold)) return rc;
     const uint64_t room = std::max<uint64_t>(r.kh.total, 1);
     if (int rc = st->d_ks_keys.grow(ctx, room, 4096)) return rc;
     if (int rc = st->d_ks_counts.grow(ctx, room, 4096)) return rc;
@@ -2046,20 +2092,15 @@ int sketcher_kmer_sets(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask,
 
 }  // namespace
 
-// K3o behind the entry points of d2g_k1.hip: the batch is staged (or a plan applied) and `regs_dev` [n][m] pre-set to ~0 on `s`;
-// lowers the registers over the k-mers seen at least `mincount` (>= 2) times and waits for the status word.  `*st` is made on first use.
-int d2g_k3_ophmin(d2g_ctx *ctx, d2g_k3_state **st, const PackedRuns &in, const KmerArgs &km, size_t nblk, uint64_t xormask, size_t m,
-                  uint32_t mincount, uint64_t *regs_dev, hipStream_t s) {
-    if (!*st) *st = new (std::nothrow) d2g_k3_state();
-    if (!*st) return D2G_ERR_NOMEM;
+// K3o behind the entry points of d2g_k1.hip: `regs_dev` [n][m] is pre-set to ~0 on the batch's stream; lowers the registers over the
+// k-mers seen at least `mincount` (>= 2) times and waits for the status word
+int d2g_k3_ophmin(const KmerBatch &b, uint64_t xormask, size_t m, uint32_t mincount, uint64_t *regs_dev) {
     K3Run r;
-    r.ctx = ctx; r.st = *st; r.s = s; r.n = in.n;
-    if (int rc = k3_layout(ctx, in, r.kh)) return rc;
-    if (in.n == 0) return D2G_OK;
-    r.km = km; r.nblk = nblk;
+    if (int rc = k3_begin(b, r)) return rc;
+    if (r.n == 0) return D2G_OK;
     r.xormask = xormask; r.m = m; r.thr = (double)(mincount - 1); r.oph_regs = regs_dev;
     if (int rc = r.run(K3Mode::OphMin)) return rc;
-    return k3_check_status(ctx, r.st, r.s);
+    return k3_check_status(r.ctx, r.st, r.s);
 }
 
 extern "C" {
@@ -2076,26 +2117,10 @@ int d2g_bmh_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pa
                        size_t sketchsize, double count_threshold, double *sig_out_dev, double *total_weight_out_dev,
                        void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
-    D2G_CHECK(ctx, sketchsize >= 1 && sketchsize < (1ull << 24), "sketchsize out of range");
-    D2G_CHECK(ctx, (sig_out_dev && total_weight_out_dev) || plan->n == 0, "null output");
-    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->k3) ctx->k3 = new (std::nothrow) d2g_k3_state();
-    if (!ctx->k3) return D2G_ERR_NOMEM;
-    const size_t n = plan->n;
-    K3Run r;
-    r.ctx = ctx; r.st = ctx->k3; r.s = as_stream(stream); r.n = n;
-    if (int rc = k3_layout(ctx, plan->runs(canon), r.kh)) return rc;
-    if (n == 0) return D2G_OK;
-    r.km = d2g_plan_args(plan, packed_dev, canon); r.nblk = plan->nblk;
-    r.xormask = xormask; r.m = sketchsize; r.thr = count_threshold;
-    if (int rc = r.run(K3Mode::Sketch)) return rc;
-    D2G_HIP(ctx, hipMemcpyAsync(sig_out_dev, r.st->d_h, n * sketchsize * sizeof(double), hipMemcpyDeviceToDevice, r.s));
-    D2G_HIP(ctx, hipMemcpyAsync(total_weight_out_dev, r.st->d_tw, n * sizeof(double), hipMemcpyDeviceToDevice, r.s));
-    return k3_check_status(ctx, r.st, r.s);
+    if (int rc = bmh_check(ctx, plan->n, sketchsize, count_threshold, sig_out_dev, total_weight_out_dev)) return rc;
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    return bmh_sketch(b, xormask, sketchsize, count_threshold, sig_out_dev, total_weight_out_dev, hipMemcpyDeviceToDevice);
 }
 
 int d2g_bmh_sketch(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
@@ -2139,11 +2164,6 @@ int d2g_kmer_sets(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, cons
                   uint64_t xormask, double count_threshold, uint64_t *keys_out, uint32_t *counts_out, size_t cap,
                   uint64_t *set_off_out, uint64_t *cards_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    if (!ctx) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, set_off_out != nullptr, "null set_off_out");
-    D2G_CHECK(ctx, cards_out != nullptr || n == 0, "null cards_out");
-    D2G_CHECK(ctx, cap == 0 || keys_out, "null output");
-    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
     return d2g_with_sketcher(ctx, [&](d2g_sketcher *sk) {
         return sketcher_kmer_sets(sk, in, xormask, count_threshold, keys_out, counts_out, cap, set_off_out, cards_out);
     });
@@ -2153,12 +2173,6 @@ int d2g_sketcher_run_sets(d2g_sketcher *sk, const uint8_t *packed, size_t packed
                           size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask, double count_threshold,
                           uint64_t *keys_out, uint32_t *counts_out, size_t cap, uint64_t *set_off_out, uint64_t *cards_out) {
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
-    if (!sk) return D2G_ERR_INVALID;
-    d2g_ctx *ctx = sk->ctx;
-    D2G_CHECK(ctx, set_off_out != nullptr, "null set_off_out");
-    D2G_CHECK(ctx, cards_out != nullptr || n == 0, "null cards_out");
-    D2G_CHECK(ctx, cap == 0 || keys_out, "null output");
-    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
     return sketcher_kmer_sets(sk, in, xormask, count_threshold, keys_out, counts_out, cap, set_off_out, cards_out);
 }
 
@@ -2166,29 +2180,10 @@ int d2g_kmer_sets_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *pac
                       double count_threshold, uint64_t *keys_dev, uint32_t *counts_dev, size_t cap, uint64_t *set_off_dev,
                       uint64_t *cards_dev, void *stream) {
     if (!ctx || !plan) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
-    D2G_CHECK(ctx, set_off_dev != nullptr, "null set_off_dev");
-    D2G_CHECK(ctx, cards_dev != nullptr || plan->n == 0, "null cards_dev");
-    D2G_CHECK(ctx, cap == 0 || keys_dev, "null output");
-    D2G_CHECK(ctx, count_threshold == count_threshold, "count_threshold is NaN");
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->k3) ctx->k3 = new (std::nothrow) d2g_k3_state();
-    if (!ctx->k3) return D2G_ERR_NOMEM;
-    const size_t n = plan->n;
-    K3Run r;
-    r.ctx = ctx; r.st = ctx->k3; r.s = as_stream(stream); r.n = n;
-    if (int rc = k3_layout(ctx, plan->runs(canon), r.kh)) return rc;
-    if (n == 0) {
-        D2G_HIP(ctx, hipMemsetAsync(set_off_dev, 0, sizeof(uint64_t), r.s));
-        return D2G_OK;
-    }
-    r.km = d2g_plan_args(plan, packed_dev, canon); r.nblk = plan->nblk;
-    r.xormask = xormask; r.thr = count_threshold;
-    if (int rc = r.run(K3Mode::Count)) return rc;
-    if (int rc = k3_check_status(ctx, r.st, r.s)) return rc;
-    return k3_sorted_sets(r, "d2g_kmer_sets_dev", keys_dev, counts_dev, cap, set_off_dev, cards_dev, nullptr);
+    if (int rc = sets_check(ctx, plan->n, count_threshold, keys_dev, cap, set_off_dev, cards_dev, "dev")) return rc;
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    return kmer_sets_dev(b, xormask, count_threshold, keys_dev, counts_dev, cap, set_off_dev, cards_dev);
 }
 
 // Every host-side check of the weights of explicit sets, without a context.  The last one keeps the walk finite: a set's first guess of
@@ -2274,7 +2269,6 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
     d2g_dev<int> d_status;
     int rc = D2G_OK;
     const char *what = "weighted sets alloc";
-#define K3_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { ctx->last_error = hipGetErrorString(e_); return D2G_ERR_HIP; } } while (0)
     if ((rc = d_ids.alloc(ctx, std::max<uint64_t>(total, 1), what)) ||
         (rc = d_blo.alloc(ctx, std::max<size_t>(nb, 1), what)) ||
         (rc = d_bset.alloc(ctx, std::max<size_t>(nb, 1), what)) ||
@@ -2284,15 +2278,15 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
         (rc = d_redo.alloc(ctx, nsets, what)) ||
         (rc = d_tw.alloc(ctx, nsets, what)) ||
         (rc = d_status.alloc(ctx, 2, what))) return rc;
-    if (weights) { if ((rc = d_w.alloc(ctx, std::max<uint64_t>(total, 1), what))) return rc; K3_TRY(hipMemcpy(d_w, weights, total * 8, hipMemcpyHostToDevice)); }
-    if (total) K3_TRY(hipMemcpy(d_ids, ids, total * 8, hipMemcpyHostToDevice));
-    K3_TRY(hipMemcpy(d_guess, guess.data(), nsets * 8, hipMemcpyHostToDevice));
+    if (weights) { if ((rc = d_w.alloc(ctx, std::max<uint64_t>(total, 1), what))) return rc; D2G_HIP(ctx, hipMemcpy(d_w, weights, total * 8, hipMemcpyHostToDevice)); }
+    if (total) D2G_HIP(ctx, hipMemcpy(d_ids, ids, total * 8, hipMemcpyHostToDevice));
+    D2G_HIP(ctx, hipMemcpy(d_guess, guess.data(), nsets * 8, hipMemcpyHostToDevice));
     if (nb) {
-        K3_TRY(hipMemcpy(d_blo, blo.data(), nb * 8, hipMemcpyHostToDevice));
-        K3_TRY(hipMemcpy(d_bset, bset.data(), nb * 4, hipMemcpyHostToDevice));
-        K3_TRY(hipMemcpy(d_bcnt, bcnt.data(), nb * 4, hipMemcpyHostToDevice));
+        D2G_HIP(ctx, hipMemcpy(d_blo, blo.data(), nb * 8, hipMemcpyHostToDevice));
+        D2G_HIP(ctx, hipMemcpy(d_bset, bset.data(), nb * 4, hipMemcpyHostToDevice));
+        D2G_HIP(ctx, hipMemcpy(d_bcnt, bcnt.data(), nb * 4, hipMemcpyHostToDevice));
     }
-    K3_TRY(hipMemset(d_status, 0, 2 * sizeof(int)));
+    D2G_HIP(ctx, hipMemset(d_status, 0, 2 * sizeof(int)));
     WsArgs a;
     a.ids = d_ids; a.w = d_w; a.blk_set = d_bset; a.blk_lo = d_blo; a.blk_cnt = d_bcnt;
     a.m = (uint32_t)m; a.h = d_h; a.guess = d_guess; a.redo = d_redo; a.redo_mode = 0; a.status = d_status;
@@ -2302,34 +2296,33 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
         const size_t ninit = std::max<size_t>(nsets * m, nsets);
         hipLaunchKernelGGL(k3_bmh_init_kernel, dim3((unsigned)div_up<size_t>(ninit, K3_THREADS)), dim3(K3_THREADS), 0, nullptr,
                            d_h, nsets * m, d_tw, d_redo, nsets);
-        K3_TRY(hipMemcpy(d_tw, tw.data(), nsets * 8, hipMemcpyHostToDevice));
+        D2G_HIP(ctx, hipMemcpy(d_tw, tw.data(), nsets * 8, hipMemcpyHostToDevice));
         for (int pass = 0;; ++pass) {
             a.redo_mode = pass > 0;
             if (nb) hipLaunchKernelGGL(k3_bmh_sets_kernel, dim3((unsigned)nb), dim3(K3_THREADS), 0, nullptr, a);
             hipLaunchKernelGGL(k3_sets_verify_kernel, dim3((unsigned)nsets), dim3(K3_THREADS), 0, nullptr, d_h, (uint32_t)m, d_guess, d_redo,
                                d_tw, reinterpret_cast<uint32_t *>(d_status + 1), a.redo_mode);
             int st2[2] = {0, 0};
-            K3_TRY(hipMemcpy(st2, d_status, sizeof(st2), hipMemcpyDeviceToHost));
+            D2G_HIP(ctx, hipMemcpy(st2, d_status, sizeof(st2), hipMemcpyDeviceToHost));
             if (st2[0] || !st2[1]) break;
             if (pass >= 40) { ctx->last_error = "internal: BagMinHash bound did not converge"; return D2G_ERR_INTERNAL; }
-            K3_TRY(hipMemset(d_status + 1, 0, sizeof(int)));
+            D2G_HIP(ctx, hipMemset(d_status + 1, 0, sizeof(int)));
         }
         if (owner_out) {
             if ((rc = d_arg.alloc(ctx, nsets * m, what)) || (rc = d_setlo.alloc(ctx, nsets, what))) return rc;
-            K3_TRY(hipMemset(d_arg, 0xFF, nsets * m * 8));
-            K3_TRY(hipMemcpy(d_setlo, set_off, nsets * 8, hipMemcpyHostToDevice));
+            D2G_HIP(ctx, hipMemset(d_arg, 0xFF, nsets * m * 8));
+            D2G_HIP(ctx, hipMemcpy(d_setlo, set_off, nsets * 8, hipMemcpyHostToDevice));
             a.arg = d_arg; a.set_lo = d_setlo;
             if (nb) hipLaunchKernelGGL(k3_bmh_sets_argmin_kernel, dim3((unsigned)nb), dim3(K3_THREADS), 0, nullptr, a);
         }
         tm.stop();
     }
-    K3_TRY(hipGetLastError());
+    D2G_HIP(ctx, hipGetLastError());
     int status = 0;
-    K3_TRY(hipMemcpy(&status, d_status, sizeof(int), hipMemcpyDeviceToHost));
-    K3_TRY(hipMemcpy(sig_out, d_h, nsets * m * 8, hipMemcpyDeviceToHost));
-    if (owner_out) K3_TRY(hipMemcpy(owner_out, d_arg, nsets * m * 8, hipMemcpyDeviceToHost));
+    D2G_HIP(ctx, hipMemcpy(&status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    D2G_HIP(ctx, hipMemcpy(sig_out, d_h, nsets * m * 8, hipMemcpyDeviceToHost));
+    if (owner_out) D2G_HIP(ctx, hipMemcpy(owner_out, d_arg, nsets * m * 8, hipMemcpyDeviceToHost));
     std::memcpy(total_weight_out, tw.data(), nsets * sizeof(double));
-#undef K3_TRY
     return k3_status_error(ctx, status);
 }
 

@@ -105,8 +105,10 @@ int screen_check(d2g_ctx *ctx, const d2g_screen *sc, int k, int canon) {
 
 // the k-mers this call adds to every row, checked against the 2^32 guard; `add` [nrows] comes back filled, nothing is committed.
 // Tables that d2g_plan_build will reject (null, not monotone, a run shorter than k) pass: they are left to it.
-int screen_account(d2g_ctx *ctx, const d2g_screen *sc, const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n,
-                   const uint32_t *genome_row, std::vector<uint64_t> &add) {
+int screen_account(d2g_ctx *ctx, const d2g_screen *sc, const PackedRuns &in, const uint32_t *genome_row, std::vector<uint64_t> &add) {
+    const uint32_t *run_len = in.run_len;
+    const uint64_t *genome_run_off = in.genome_run_off;
+    const size_t nrun = in.nrun, n = in.n;
     add.assign(sc->nrows, 0);
     D2G_CHECK(ctx, n == 0 || genome_row != nullptr, "null genome_row");
     for (size_t g = 0; g < n; ++g) D2G_CHECK(ctx, genome_row[g] < sc->nrows, "genome_row names a row the screen does not have");
@@ -127,9 +129,13 @@ int screen_account(d2g_ctx *ctx, const d2g_screen *sc, const uint32_t *run_len, 
     return D2G_OK;
 }
 
-// the count walk of one staged batch or applied plan on `s`; commits `add` once the launch is enqueued
-int screen_launch(d2g_ctx *ctx, d2g_screen *sc, KmerArgs km, size_t nblk, size_t n, const uint32_t *genome_row, const std::vector<uint64_t> &add,
-                  hipStream_t s) {
+// the count walk of one batch on its stream (the table is the screen's: a filter the batch carries plays no part); commits `add`
+// once the launch is enqueued
+int screen_launch(d2g_screen *sc, const KmerBatch &b, const uint32_t *genome_row, const std::vector<uint64_t> &add) {
+    d2g_ctx *ctx = b.ctx;
+    hipStream_t s = b.s;
+    const size_t nblk = b.nblk, n = b.runs.n;
+    KmerArgs km = b.km;
     if (nblk && sc->D) {
         if (int rc = sc->d_grow.grow(ctx, n, 1024, "screen genome rows")) return rc;
         D2G_HIP(ctx, hipMemcpyAsync(sc->d_grow, genome_row, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
@@ -264,16 +270,13 @@ int d2g_screen_set_fed(d2g_ctx *ctx, d2g_screen *sc, size_t row, uint64_t nkmers
 
 int d2g_screen_add_dev(d2g_ctx *ctx, d2g_screen *sc, const d2g_oph_plan *plan, const uint8_t *packed_dev, const uint32_t *genome_row, void *stream) {
     if (!ctx || !sc || !plan) return D2G_ERR_INVALID;
-    D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
     const int canon = sc->canon;                                   // a plan carries k, not the canonicalisation: the screen's holds
     if (int rc = screen_check(ctx, sc, plan->k, canon)) return rc;
-    D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
-    D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
     std::vector<uint64_t> add;
-    if (int rc = screen_account(ctx, sc, plan->h_run_len.data(), plan->nrun, plan->h_genome_run_off.data(), plan->n, genome_row, add)) return rc;
-    D2G_HIP(ctx, hipSetDevice(ctx->device));
-    return screen_launch(ctx, sc, d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon), plan->nblk, plan->n, genome_row, add,
-                         as_stream(stream));
+    if (int rc = screen_account(ctx, sc, plan->runs(canon), genome_row, add)) return rc;
+    KmerBatch b;
+    if (int rc = d2g_plan_batch(ctx, plan, packed_dev, canon, stream, &b)) return rc;
+    return screen_launch(sc, b, genome_row, add);
 }
 
 int d2g_sketcher_run_screen(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
@@ -283,12 +286,11 @@ int d2g_sketcher_run_screen(d2g_sketcher *sk, const uint8_t *packed, size_t pack
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
     if (int rc = screen_check(ctx, sc, k, canon)) return rc;        // before the stage touches the stream or the buffers
     std::vector<uint64_t> add;
-    if (int rc = screen_account(ctx, sc, run_len, nrun, genome_run_off, n, genome_row, add)) return rc;
-    KmerArgs km;
-    size_t nblk = 0;
-    if (int rc = d2g_sketcher_stage(sk, in, &km, &nblk, nullptr)) return rc;
-    if (int rc = screen_launch(ctx, sc, km, nblk, n, genome_row, add, sk->stream)) return rc;
-    D2G_HIP(ctx, hipStreamSynchronize(sk->stream));
+    if (int rc = screen_account(ctx, sc, in, genome_row, add)) return rc;
+    KmerBatch b;
+    if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
+    if (int rc = screen_launch(sc, b, genome_row, add)) return rc;
+    D2G_HIP(ctx, hipStreamSynchronize(b.s));
     return D2G_OK;
 }
 

@@ -345,7 +345,7 @@ int  d2g_kmer_filter_contains(d2g_ctx *ctx, const d2g_kmer_filter *filter, const
 /* attach (NULL detaches).  The filter must outlive the plan / sketcher or be detached first.  A filter of another context, k or
  * canon makes the SKETCH call return D2G_ERR_INVALID, before it writes anything.  More than 2^31 k-mers: D2G_ERR_UNSUPPORTED at
  * creation; no memory for the table: D2G_ERR_NOMEM (never a smaller table).
- * A plan's filter is honoured by d2g_oph_sketch_dev, d2g_oph_count_dev, d2g_oph_sketch_mincount_dev and d2g_bmh_sketch_dev; a sketcher's by every
+ * A plan's filter is honoured by d2g_oph_sketch_dev, d2g_oph_count_dev, d2g_oph_sketch_mincount_dev, d2g_bmh_sketch_dev and d2g_kmer_sets_dev; a sketcher's by every
  * d2g_sketcher_run*, packed == NULL (K0-ingested) included.  --multiset calls with a filter walk the input once more, first, to count
  * the surviving k-mers per genome (their layout depends on it) and wait for that count.  The one-shot host-pointer entry points
  * (d2g_oph_sketch, d2g_bmh_sketch, d2g_kmer_count, ...) take no filter. */
@@ -384,7 +384,7 @@ int  d2g_screen_fed(d2g_ctx *ctx, const d2g_screen *screen, size_t row, uint64_t
 int  d2g_screen_set_fed(d2g_ctx *ctx, d2g_screen *screen, size_t row, uint64_t nkmers);
 /* device-resident form: the k-mers of genome g of the plan count towards row genome_row[g] (host array [n]; several genomes may
  * share a row, several rows a launch).  The k-mers are enumerated with the plan's k and the SCREEN's canonicalisation; a plan's
- * filter plays no part.  Enqueues on `stream`, does not synchronise; calls on one screen go to one stream or are ordered by the
+ * filter plays no part (one that does not fit the call is refused, as a sketcher's is).  Enqueues on `stream`, does not synchronise; calls on one screen go to one stream or are ordered by the
  * caller.  A screen of another context or k: D2G_ERR_INVALID before anything is written. */
 int  d2g_screen_add_dev(d2g_ctx *ctx, d2g_screen *screen, const d2g_oph_plan *plan, const uint8_t *packed_dev,
                         const uint32_t *genome_row /* host [n] */, void *stream);

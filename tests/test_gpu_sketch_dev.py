@@ -16,7 +16,9 @@ Every output has guard words behind it and starts as a pattern that no result co
 import numpy as np
 import pytest
 
+import exact_ref as X
 import oph_kmers_ref as R
+import oph_mincount_ref as Q
 import sketch_dev_cases as V
 from gpu_ballast import keep_busy
 
@@ -152,6 +154,63 @@ def assert_host_forms(gpu_ctx, lay, k, S, canon, xormask, exp, what):
             np.testing.assert_array_equal(cnts, exp[1], err_msg=f"{what}: {form}: counts")
 
 
+class AsBatch:
+    """a layout's distinct keys and counts where exact_ref wants a k3_seam_cases.Batch"""
+
+    def __init__(self, lay, k, canon, xormask):
+        self.kc = lay.key_counts(k, canon, xormask)
+
+    def counts(self):
+        return self.kc
+
+
+def mincount_expected(lay, k, canon, xormask, S, c):
+    """-> (registers [n][m], counts [n][m]) over the k-mers seen at least c times: oph_mincount_ref.closed_form per genome"""
+    m = R.oph_m(S)
+    regs, cnts = np.empty((lay.n, m), np.uint64), np.empty((lay.n, m), np.uint32)
+    for g, (keys, counts, _) in enumerate(lay.key_counts(k, canon, xormask)):
+        regs[g], cnts[g] = Q.closed_form(keys, counts, m, c)
+    return regs, cnts
+
+
+def run_mincount_dev(gpu_ctx, torch, plan, n, p, S, c, canon, xormask):
+    """plan + d2g_oph_sketch_mincount_dev, then d2g_oph_count_dev over its registers -> (registers [n][m], counts [n][m])"""
+    m = R.oph_m(S)
+    regs, cnts = Out(torch, n * m * 8, REG_FILL), Out(torch, n * m * 4, REG_FILL)
+    torch.cuda.synchronize()
+    gpu_ctx.oph_sketch_mincount_dev(plan, p, S, c, regs.ptr, canon=canon, xormask=xormask)
+    gpu_ctx.oph_count_dev(plan, p, S, regs.ptr, cnts.ptr, canon=canon, xormask=xormask)
+    torch.cuda.synchronize()
+    return regs.read(np.uint64, (n, m)), cnts.read(np.uint32, (n, m))
+
+
+def run_sets_dev(gpu_ctx, torch, plan, n, p, cap, canon, xormask, counts=True):
+    """plan + d2g_kmer_sets_dev into guarded device arrays of cap entries -> (keys, counts or None, set_off [n+1], cards [n][2])"""
+    room = (max(cap, 1) + 1) // 2 * 2
+    keys, cnts = Out(torch, room * 8, REG_FILL), Out(torch, room * 4, REG_FILL)
+    off, cards = Out(torch, (n + 1) * 8, REG_FILL), Out(torch, max(n, 1) * 16, REG_FILL)
+    torch.cuda.synchronize()
+    gpu_ctx.kmer_sets_dev(plan, p, keys.ptr, cnts.ptr if counts else None, cap, off.ptr, cards.ptr, canon=canon, xormask=xormask)
+    torch.cuda.synchronize()
+    o = off.read(np.uint64, (n + 1,))
+    total = int(o[n])
+    if not counts:
+        cnts.assert_untouched()
+    return (keys.read(np.uint64, (room,))[:total], cnts.read(np.uint32, (2 * (room // 2),))[:total] if counts else None, o,
+            cards.read(np.uint64, (max(n, 1), 2))[:n])
+
+
+def assert_sets(got, exp, counts, what):
+    keys, cnts, off, cards = got
+    np.testing.assert_array_equal(off, exp[2], err_msg=what + ": set_off")
+    np.testing.assert_array_equal(cards, exp[3], err_msg=what + ": cards")
+    np.testing.assert_array_equal(keys, exp[0], err_msg=what + ": keys")
+    if counts:
+        np.testing.assert_array_equal(cnts, exp[1], err_msg=what + ": counts")
+    else:
+        assert cnts is None, what
+
+
 # ---------------------------------------------------------------- a. K1 at the plan's seams
 @pytest.mark.parametrize("xormask", [0, V.SEEDED], ids=["mask0", "seeded"])
 @pytest.mark.parametrize("canon", [True, False], ids=["canon", "fwd"])
@@ -196,15 +255,37 @@ def test_every_front_door_gives_the_same(gpu_ctx, torch, case):
     """one layout through every way in.  K1: the one-shots, a sketcher and plan + *_dev give the layout's own expected registers and
     counts, so the same bits as each other, at S = 64 and S = 1000.  The filter: d2g_kmer_filter_create and plan +
     d2g_kmer_filter_create_dev over the same runs hold the same set -- the occurrences and distinct k-mers that the layout's bases
-    hold, every one of its k-mers and none of 64 that it does not hold"""
+    hold, every one of its k-mers and none of 64 that it does not hold.  At the same sizes the registers over the k-mers seen twice
+    (with and without counts) and BagMinHash; once per layout the distinct counts and the exact sets (with and without counts):
+    the one-shot, a sketcher and, where there is one, plan + *_dev, each against the restatement of oph_mincount_ref, Layout.bmh
+    and exact_ref, so bit for bit like each other"""
     make, k, xormask = case
     lay, canon = make(), True
     A = device_bytes(torch, lay.packed)
     plan = gpu_ctx.oph_plan(*lay.tables(), k)
+    sp, sk = AsSeqPack(lay, k), gpu_ctx.sketcher()
     for S in (64, 1000):
         exp = lay.oph(k, canon, xormask, S)
         assert_k1(run_k1(gpu_ctx, torch, None, plan, lay.n, A, None, S, canon, xormask), exp, f"{lay} S {S}: plan + dev")
         assert_host_forms(gpu_ctx, lay, k, S, canon, xormask, exp, f"{lay} S {S}")
+        exp = mincount_expected(lay, k, canon, xormask, S, 2)
+        assert_k1(run_mincount_dev(gpu_ctx, torch, plan, lay.n, A.data_ptr(), S, 2, canon, xormask), exp, f"{lay} S {S}: mincount, plan + dev")
+        for form, f in (("d2g_oph_sketch_mincount", gpu_ctx.oph_sketch_mincount_seqpack), ("d2g_sketcher_run_mincount", sk.run_mincount)):
+            assert_k1(f(sp, S, 2, canon, xormask, counts=True), exp, f"{lay} S {S}: {form}")
+            np.testing.assert_array_equal(f(sp, S, 2, canon, xormask), exp[0], err_msg=f"{lay} S {S}: {form} without counts")
+        exp = lay.bmh(k, canon, xormask, S, 0.0)
+        assert_k3(run_k3(gpu_ctx, torch, None, plan, lay.n, A, None, S, 0.0, canon=canon, xormask=xormask), exp, f"{lay} S {S}: bmh, plan + dev")
+        assert_k3(gpu_ctx.bmh_sketch_seqpack(sp, S, canon, xormask), exp, f"{lay} S {S}: d2g_bmh_sketch")
+        assert_k3(sk.run_bmh(sp, S, canon, xormask), exp, f"{lay} S {S}: d2g_sketcher_run_bmh")
+    exp = X.flat(X.exact_sets(AsBatch(lay, k, canon, xormask)))
+    for form, got in (("d2g_kmer_distinct", gpu_ctx.kmer_distinct_seqpack(sp, canon, xormask)), ("d2g_sketcher_run_distinct", sk.run_distinct(sp, canon, xormask))):
+        np.testing.assert_array_equal(got, exp[3][:, 0], err_msg=f"{lay}: {form}")
+    for counts in (True, False):
+        assert_sets(gpu_ctx.kmer_sets_seqpack(sp, canon, xormask, counts=counts), exp, counts, f"{lay}: d2g_kmer_sets")
+        assert_sets(sk.run_sets(sp, canon, xormask, counts=counts), exp, counts, f"{lay}: d2g_sketcher_run_sets")
+        assert_sets(run_sets_dev(gpu_ctx, torch, plan, lay.n, A.data_ptr(), sum(lay.nkmers(k)), canon, xormask, counts), exp, counts,
+                    f"{lay}: plan + d2g_kmer_sets_dev")
+    sk.close()
     kmers = np.concatenate([V.kmers_np(lay.run_codes(r), k, canon) for r in range(lay.nrun)] + [np.zeros(0, np.uint64)])
     held = np.unique(kmers)
     absent = np.random.default_rng(3800).integers(0, 1 << (2 * k), 80, dtype=np.uint64)
@@ -370,22 +451,37 @@ def refused(d2g, status, call, *args, **kw):
 
 
 def test_dev_calls_refuse_bad_arguments_and_write_nothing(gpu_ctx, d2g, torch):
-    k, S = 21, 64
+    """every plan form against a plan of another context, a packed pointer off by 1 or 2 and a null packed pointer under a plan with
+    blocks: D2G_ERR_INVALID and nothing written (the forms that always refused a null stream first); then the wrong sizes and null
+    outputs; then every form with the same arguments put right"""
+    k, S, canon = 21, 64, True
     lay = V.multiset_slots()
     packed = device_bytes(torch, lay.packed)
     p = packed.data_ptr()
     plan = gpu_ctx.oph_plan(*lay.head(4), k)
     m = R.oph_m(S)
+    kc = lay.key_counts(k, canon, 0)[:4]
+    cap = sum(lay.nkmers(k)[:4])
+    room = (cap + 1) // 2 * 2
     regs, cnts = Out(torch, 4 * m * 8, REG_FILL), Out(torch, 4 * m * 4, REG_FILL)
     sig, tw = Out(torch, 4 * S * 8, NAN_FILL), Out(torch, 4 * 8, NAN_FILL)
+    keys, kcnt = Out(torch, room * 8, REG_FILL), Out(torch, room * 4, REG_FILL)
+    off, cards = Out(torch, 5 * 8, REG_FILL), Out(torch, 4 * 16, REG_FILL)
+    db = kc[0][0][:S].reshape(1, S)                                    # a database of one reference: 64 masked k-mers of genome 0
+    screen = gpu_ctx.screen(db, k, canon=canon, xormask=0, nrows=1)
+    rows = [0, 0, 0, 0]
     torch.cuda.synchronize()
     other_ctx = d2g.Context(0)
     foreign = other_ctx.oph_plan(*lay.head(4), k)
+    forms = [                                                          # (call, arguments after (plan, packed)); K3's two last
+        (gpu_ctx.oph_sketch_dev, (S, regs.ptr)), (gpu_ctx.oph_count_dev, (S, regs.ptr, cnts.ptr)),
+        (gpu_ctx.oph_sketch_mincount_dev, (S, 2, regs.ptr)), (gpu_ctx.kmer_filter_dev, ()), (screen.add_dev, (rows,)),
+        (gpu_ctx.bmh_sketch_dev, (S, sig.ptr, tw.ptr)), (gpu_ctx.kmer_sets_dev, (keys.ptr, kcnt.ptr, cap, off.ptr, cards.ptr)),
+    ]
+    for i, (call, args) in enumerate(forms):
+        for wrong in ((foreign, p), (plan, p + 1 + i % 2), (plan, None)):
+            refused(d2g, INVALID, call, *wrong, *args)
     bad = [
-        (gpu_ctx.oph_sketch_dev, (foreign, p, S, regs.ptr)), (gpu_ctx.oph_count_dev, (foreign, p, S, regs.ptr, cnts.ptr)),
-        (gpu_ctx.bmh_sketch_dev, (foreign, p, S, sig.ptr, tw.ptr)),
-        (gpu_ctx.oph_sketch_dev, (plan, p + 1, S, regs.ptr)), (gpu_ctx.oph_count_dev, (plan, p + 1, S, regs.ptr, cnts.ptr)),
-        (gpu_ctx.bmh_sketch_dev, (plan, p + 2, S, sig.ptr, tw.ptr)),
         (gpu_ctx.oph_sketch_dev, (plan, p, 0, regs.ptr)), (gpu_ctx.oph_count_dev, (plan, p, 0, regs.ptr, cnts.ptr)),
         (gpu_ctx.bmh_sketch_dev, (plan, p, 0, sig.ptr, tw.ptr)), (gpu_ctx.bmh_sketch_dev, (plan, p, 1 << 24, sig.ptr, tw.ptr)),
         (gpu_ctx.oph_sketch_dev, (plan, p, 1 << 31, regs.ptr)),
@@ -397,12 +493,32 @@ def test_dev_calls_refuse_bad_arguments_and_write_nothing(gpu_ctx, d2g, torch):
         refused(d2g, INVALID, call, *args)
     refused(d2g, INVALID, gpu_ctx.bmh_sketch_dev, plan, p, S, sig.ptr, tw.ptr, count_threshold=float("nan"))
     torch.cuda.synchronize()
-    for o in (regs, cnts, sig, tw):
+    for o in (regs, cnts, sig, tw, keys, kcnt, off, cards):
         o.assert_untouched()
+    assert screen.fed(0) == 0 and not screen.key_counts(0)[1].any()
     # the same arguments, put right, are served: the refusals above were of what was wrong with them
     gpu_ctx.bmh_sketch_dev(plan, p, S, sig.ptr, tw.ptr)
     torch.cuda.synchronize()
     assert_k3((sig.read(np.float64, (4, S)), tw.read(np.float64, (4,))), tuple(a[:4] for a in lay.bmh(k, True, 0, S, 0.0)), "after the refusals")
+    gpu_ctx.oph_sketch_dev(plan, p, S, regs.ptr)
+    gpu_ctx.oph_count_dev(plan, p, S, regs.ptr, cnts.ptr)
+    torch.cuda.synchronize()
+    assert_k1((regs.read(np.uint64, (4, m)), cnts.read(np.uint32, (4, m))), tuple(a[:4] for a in lay.oph(k, canon, 0, S)), "after the refusals")
+    gpu_ctx.oph_sketch_mincount_dev(plan, p, S, 2, regs.ptr)
+    np.testing.assert_array_equal(regs.read(np.uint64, (4, m)), mincount_expected(lay, k, canon, 0, S, 2)[0][:4], err_msg="after the refusals")
+    gpu_ctx.kmer_sets_dev(plan, p, keys.ptr, kcnt.ptr, cap, off.ptr, cards.ptr)
+    torch.cuda.synchronize()
+    exp = X.flat([(ks, cs) for ks, cs, _ in kc])
+    total = int(exp[2][4])
+    assert_sets((keys.read(np.uint64, (room,))[:total], kcnt.read(np.uint32, (room,))[:total], off.read(np.uint64, (5,)),
+                 cards.read(np.uint64, (4, 2))), exp, True, "after the refusals")
+    f = gpu_ctx.kmer_filter_dev(plan, p, canon)
+    assert f.info()[:2] == (cap, np.unique(np.concatenate([V.kmers_np(lay.run_codes(g), k, canon) for g in range(4)])).size)
+    f.close()
+    screen.add_dev(plan, p, rows)
+    hits = sum(cs[np.isin(ks, db)].astype(np.int64).sum() for ks, cs, _ in kc)
+    assert screen.fed(0) == cap and int(screen.key_counts(0)[1].sum()) == hits > 0
+    screen.close()
     foreign.close()
     other_ctx.close()
     plan.close()
