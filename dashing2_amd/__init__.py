@@ -16,7 +16,7 @@ from .capi import (  # noqa: F401
     regs_truncate, epilogue_trunc_neq, epilogue_trunc_gtlt, host_epilogue_trunc_ut, host_epilogue_trunc_rect,
     knn_finish, KnnOverflow, TIME_KNN, dedup_clusters, TIME_DEDUP, bmh_check_weights, wang_hash_inverse, oph_kmer_ids,
     KmerFilter, TIME_FILTER,
-    Screen, TIME_SCREEN, epilogue_contain, screen_table_slots, SCREEN_MAX_KEYS,
+    Screen, TIME_SCREEN, epilogue_contain, screen_table_slots, SCREEN_MAX_KEYS, run_emissions,
     KSet, TIME_KSET, epilogue_exact, host_epilogue_exact_ut, host_epilogue_exact_rect, kset_check,
 )
 
@@ -30,6 +30,6 @@ __all__ = [
     "regs_truncate", "epilogue_trunc_neq", "epilogue_trunc_gtlt", "host_epilogue_trunc_ut", "host_epilogue_trunc_rect",
     "knn_finish", "KnnOverflow", "TIME_KNN", "dedup_clusters", "TIME_DEDUP", "bmh_check_weights", "wang_hash_inverse", "oph_kmer_ids",
     "KmerFilter", "TIME_FILTER",
-    "Screen", "TIME_SCREEN", "epilogue_contain", "screen_table_slots", "SCREEN_MAX_KEYS",
+    "Screen", "TIME_SCREEN", "epilogue_contain", "screen_table_slots", "SCREEN_MAX_KEYS", "run_emissions",
     "KSet", "TIME_KSET", "epilogue_exact", "host_epilogue_exact_ut", "host_epilogue_exact_rect", "kset_check",
 ]

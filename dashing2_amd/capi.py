@@ -101,6 +101,9 @@ SIGNATURES = {
     "d2g_seqpack_nbases": (_u64, [_vp]),
     "d2g_oph_sketch": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _vp]),
     "d2g_oph_plan_create": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _int, C.POINTER(_vp)]),
+    "d2g_oph_plan_create_windowed": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _int, _int, C.POINTER(_vp)]),
+    "d2g_run_emissions": (_u64, [_u64, _int, _int]),
+    "d2g_sketcher_set_window": (_int, [_vp, _int]),
     "d2g_oph_plan_destroy": (None, [_vp]),
     "d2g_oph_plan_nkmers": (_u64, [_vp]),
     "d2g_oph_plan_nbases": (_u64, [_vp]),
@@ -113,6 +116,7 @@ SIGNATURES = {
     "d2g_oph_sketch_mincount_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, C.c_uint32, _vp, _vp]),
     "d2g_kmer_filter_create_dev": (_int, [_vp, _vp, _vp, _int, _vp, C.POINTER(_vp)]),
     "d2g_kmer_filter_create": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _int, _int, C.POINTER(_vp)]),
+    "d2g_kmer_filter_create_windowed": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _int, _int, _int, C.POINTER(_vp)]),
     "d2g_kmer_filter_destroy": (None, [_vp]),
     "d2g_kmer_filter_info": (_int, [_vp, _vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_sz)]),
     "d2g_kmer_filter_contains": (_int, [_vp, _vp, _vp, _sz, _vp]),
@@ -299,6 +303,11 @@ def wang_hash_inverse(x):
 
 
 SCREEN_MAX_KEYS = 1 << 30                                               # include/d2g.h D2G_SCREEN_MAX_KEYS
+
+
+def run_emissions(length, k, w=0):
+    """k-mers a run of `length` valid bases emits under (k, w): its k-mers, or its window positions when w > k (host, no GPU)"""
+    return int(lib().d2g_run_emissions(int(length), int(k), int(w)))
 
 
 def screen_table_slots(ndistinct):
@@ -866,13 +875,14 @@ class Context:
                                                     ns, S, _np_ptr(sig), _np_ptr(tw), _np_ptr(own)))
         return sig, tw, own
 
-    def oph_plan(self, run_start, run_len, genome_run_off, k):
+    def oph_plan(self, run_start, run_len, genome_run_off, k, w=0):
+        """launch plan over a run table; w > k: a windowed one (K1w) -- every *_dev call over it walks minimizers"""
         run_start = np.ascontiguousarray(run_start, np.uint64)
         run_len = np.ascontiguousarray(run_len, np.uint32)
         genome_run_off = np.ascontiguousarray(genome_run_off, np.uint64)
         h = _vp()
-        self._check(lib().d2g_oph_plan_create(self._h, _np_ptr(run_start), _np_ptr(run_len), run_start.size,
-                                              _np_ptr(genome_run_off), genome_run_off.size - 1, k, C.byref(h)))
+        self._check(lib().d2g_oph_plan_create_windowed(self._h, _np_ptr(run_start), _np_ptr(run_len), run_start.size,
+                                                       _np_ptr(genome_run_off), genome_run_off.size - 1, k, w, C.byref(h)))
         return OphPlan(self, h, genome_run_off.size - 1)
 
     # -- K1s (contain: reads screened against a k-mer database) ----------------
@@ -891,11 +901,11 @@ class Context:
         return int(f.value), int(t.value)
 
     # -- K1f (--filterset: k-mers every sketch skips) ---------------------------
-    def kmer_filter(self, sp: "SeqPack", canon=True):
-        """the k-mers of ALL genomes of `sp` as one device-resident set (host-pointer form; synchronises)"""
+    def kmer_filter(self, sp: "SeqPack", canon=True, w=0):
+        """the k-mers of ALL genomes of `sp` as one device-resident set (host-pointer form; synchronises); w > k: its minimizers"""
         r = _Runs(sp, canon)
         h = _vp()
-        self._check(lib().d2g_kmer_filter_create(self._h, *r.args[:5], *r.args[7:], C.byref(h)))      # no genomes: all runs feed one set
+        self._check(lib().d2g_kmer_filter_create_windowed(self._h, *r.args[:5], *r.args[7:], w, C.byref(h)))      # no genomes: all runs feed one set
         return KmerFilter(self, h, sp.k, bool(canon))
 
     def kmer_filter_dev(self, plan, packed_dev_ptr, canon=True, stream=None):
@@ -1057,6 +1067,10 @@ class Sketcher:
         """attach a KmerFilter (None detaches): every run* of this sketcher skips its k-mers.  The sketcher keeps it alive."""
         self.ctx._check(lib().d2g_sketcher_set_filter(self._h, filt._h if filt is not None else None))
         self._filter = filt
+
+    def set_window(self, w):
+        """K1w: every later run* of this sketcher walks the minimizers of windows of w bases when w > its k; 0 or w <= k: off"""
+        self.ctx._check(lib().d2g_sketcher_set_window(self._h, int(w)))
 
     def _ingested(self, runs, k):
         """the source of a run table over the stream ingested last (k: default the k of the ingest)"""

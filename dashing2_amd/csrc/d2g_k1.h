@@ -14,12 +14,15 @@ inline int d2g_plan_err(d2g_ctx *ctx, int rc, const std::string &err) {
 struct d2g_kmer_filter {
     d2g_ctx *ctx = nullptr;
     int k = 0, canon = 0;
+    int w = 0;                                 // the window it was built under, 0 = none (never a value <= k)
     uint64_t noccurrences = 0;                 // k-mers put in, duplicates counted (the reference's data_.size())
     uint64_t slots = 0;                        // a power of two >= 2 * noccurrences (>= 16)
     d2g_dev<uint64_t> d_tab;                   // [slots] keys, then [0] the all-ones flag, [1] the distinct keys in the slots
 };
-// the filter a plan or sketcher carries must fit the call: same context, k and canon (nullptr fits everything)
-int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon);
+// the filter a plan or sketcher carries must fit the call: same context, k, canon and window (nullptr fits everything)
+int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon, int w);
+// a window as the library keeps it: w when w > k, else 0
+inline int d2g_window_norm(int k, int w) { return w > k ? w : 0; }
 // table pointer, mask and shift into the walker's arguments (nullptr: no filter); the caller has run d2g_filter_check
 void d2g_filter_args(const d2g_kmer_filter *f, KmerArgs *km);
 // K3 lays its key regions out from the k-mers per genome, which a filter makes data: one walk of the launch plan counts the
@@ -30,6 +33,7 @@ struct d2g_oph_plan {
     d2g_ctx *ctx = nullptr;
     const d2g_kmer_filter *filter = nullptr;   // VIEW (d2g_oph_plan_set_filter)
     int k = 0;
+    int w = 0;                                 // d2g_oph_plan_create_windowed: the chunks are window positions (0 = none)
     size_t n = 0, nrun = 0, nblk = 0;
     uint64_t nkmers = 0, nbases = 0;
     std::vector<uint32_t> h_run_len;           // host copies kept for K3's bucket layout
@@ -37,11 +41,11 @@ struct d2g_oph_plan {
     PlanLayout lay;                            // the eight launch tables: pieces of ONE device buffer, as the sketcher ships them
     d2g_dev<uint8_t> d_arena;
     // the tables K3 lays its buckets out from (host copies; no stream: a plan is applied to any)
-    PackedRuns runs(int canon) const { return {nullptr, 0, nullptr, h_run_len.data(), nrun, h_genome_run_off.data(), n, k, canon}; }
+    PackedRuns runs(int canon) const { return {nullptr, 0, nullptr, h_run_len.data(), nrun, h_genome_run_off.data(), n, k, canon, w}; }
 };
 
 // the ONLY place that points a walker's arguments at launch tables: `arena_dev` holds them as `lay` says (d2g_plan_fill)
-inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &lay, const uint8_t *packed_dev, int k, int canon) {
+inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &lay, const uint8_t *packed_dev, int k, int canon, int w) {
     KmerArgs a{};
     auto u64 = [&](size_t at) { return reinterpret_cast<const uint64_t *>(arena_dev + at); };
     auto u32 = [&](size_t at) { return reinterpret_cast<const uint32_t *>(arena_dev + at); };
@@ -49,7 +53,7 @@ inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &l
     a.run_start = u64(lay.run_start); a.run_len = u32(lay.run_len); a.run_chunk_off = u64(lay.run_chunk_off);
     a.blk_genome = u32(lay.blk_genome); a.blk_chunk0 = u64(lay.blk_chunk0); a.blk_nchunks = u32(lay.blk_nchunks);
     a.blk_run_lo = u32(lay.blk_run_lo); a.blk_run_hi = u32(lay.blk_run_hi);
-    a.k = k; a.canon = canon; a.blk0 = 0;
+    a.k = k; a.canon = canon; a.blk0 = 0; a.q = (uint32_t)d2g_window_q(k, w);
     return a;
 }
 // Host ingest feeds K1 in groups of inputs; re-allocating device buffers and uploading eight
@@ -60,6 +64,7 @@ struct d2g_k0_state;
 struct d2g_sketcher {
     d2g_ctx *ctx = nullptr;
     const d2g_kmer_filter *filter = nullptr;               // VIEW (d2g_sketcher_set_filter)
+    int w = 0;                                             // d2g_sketcher_set_window: every run walks minimizers when w > its k
     d2g_stream stream;
     d2g_dev<uint8_t> d_packed;                             // grow-only, like the buffers below
     d2g_dev<uint64_t> d_regs;
@@ -69,6 +74,8 @@ struct d2g_sketcher {
     d2g_k3_state *k3 = nullptr;                            // --multiset work buffers (d2g_k3_bmh.hip)
     d2g_k0_state *k0 = nullptr;                            // device FASTA ingest (d2g_k0.hip): raw bytes, tile tables, the last run table
 };
+// an entry point's view of its arguments carries no window: the sketcher's, as the plan unit and the accounting in front of a stage see it
+inline PackedRuns d2g_sketcher_view(const d2g_sketcher *sk, PackedRuns in) { in.w = d2g_window_norm(in.k, sk->w); return in; }
 void d2g_k0_state_destroy(d2g_k0_state *st);
 bool d2g_k0_ingested(const d2g_sketcher *sk, uint64_t *nbases);   // d_packed holds a stream ingested by K0 (and how many bases)
 void d2g_k0_invalidate(d2g_sketcher *sk);
@@ -81,7 +88,7 @@ struct KmerBatch {
     hipStream_t s = nullptr;
     KmerArgs km{};                             // launch tables and packed stream on the device, the attached filter applied
     size_t nblk = 0;                           // workgroups of the walk
-    PackedRuns runs{};                         // the host run tables (packed == nullptr): K3's layout, the screen's accounting
+    PackedRuns runs{};                         // the host run tables (packed == nullptr), the window in runs.w: K3's layout
     d2g_k3_state **k3 = nullptr;               // where the K3 work state of this batch's owner lives: &sk->k3 or &ctx->k3
 };
 // a plan applied to a device stream on the caller's stream.  Refuses, in this order and before the first HIP call: a plan of

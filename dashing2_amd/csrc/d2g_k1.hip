@@ -30,7 +30,7 @@ struct K1Args {
     uint32_t m;
 };
 
-template <bool POW2, bool USE_LDS, bool FILT>
+template <bool POW2, bool USE_LDS, bool FILT, bool WIN = false>
 __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
     const int tid = threadIdx.x;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
         __syncthreads();
     }
     const uint64_t xormask = a.xormask, ophxor = a.ophxor;
-    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
         const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
         // Schismatic<uint32_t>::mod(size_t): argument narrowed to 32 bits (oph.h:184)
         const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
@@ -79,7 +79,7 @@ struct K1CountArgs {
     uint32_t m;
 };
 
-template <bool POW2, bool USE_LDS, bool FILT>
+template <bool POW2, bool USE_LDS, bool FILT, bool WIN = false>
 __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
     const int tid = threadIdx.x;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a)
         __syncthreads();
     }
     const uint64_t xormask = a.xormask, ophxor = a.ophxor;
-    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
         const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
         const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
         if (USE_LDS) {
@@ -112,24 +112,32 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a)
     }
 }
 
-// the instantiations, indexed by POW2 * 4 + USE_LDS * 2 + FILT
-void (*const k1_kernels[8])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
+// the instantiations, indexed by POW2 * 4 + USE_LDS * 2 + FILT; the windowed ones (K1w) behind them, + 8
+void (*const k1_kernels[16])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
                                        k1_oph_kernel<false, true, true>,   k1_oph_kernel<true, false, false>, k1_oph_kernel<true, false, true>,
-                                       k1_oph_kernel<true, true, false>,   k1_oph_kernel<true, true, true>};
-void (*const k1_count_kernels[8])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
+                                       k1_oph_kernel<true, true, false>,   k1_oph_kernel<true, true, true>,
+                                       k1_oph_kernel<false, false, false, true>, k1_oph_kernel<false, false, true, true>,
+                                       k1_oph_kernel<false, true, false, true>,  k1_oph_kernel<false, true, true, true>,
+                                       k1_oph_kernel<true, false, false, true>,  k1_oph_kernel<true, false, true, true>,
+                                       k1_oph_kernel<true, true, false, true>,   k1_oph_kernel<true, true, true, true>};
+void (*const k1_count_kernels[16])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
                                                   k1_oph_count_kernel<false, true, false>,  k1_oph_count_kernel<false, true, true>,
                                                   k1_oph_count_kernel<true, false, false>,  k1_oph_count_kernel<true, false, true>,
-                                                  k1_oph_count_kernel<true, true, false>,   k1_oph_count_kernel<true, true, true>};
+                                                  k1_oph_count_kernel<true, true, false>,   k1_oph_count_kernel<true, true, true>,
+                                                  k1_oph_count_kernel<false, false, false, true>, k1_oph_count_kernel<false, false, true, true>,
+                                                  k1_oph_count_kernel<false, true, false, true>,  k1_oph_count_kernel<false, true, true, true>,
+                                                  k1_oph_count_kernel<true, false, false, true>,  k1_oph_count_kernel<true, false, true, true>,
+                                                  k1_oph_count_kernel<true, true, false, true>,   k1_oph_count_kernel<true, true, true, true>};
 
 // one workgroup per block of the plan; its genome's m registers (K1: 8 bytes each; the count pass: 8 + 4) in LDS while they
 // fit the 128 KB asked for at most (m <= 16 384; m <= 10 922), beyond against HBM/L2
 template <class Args>
-int launch_k1_any(d2g_ctx *ctx, void (*const kerns[8])(Args), const Args &a, size_t nblk, size_t lds_per_reg, d2g_evlog *ev, hipStream_t s) {
+int launch_k1_any(d2g_ctx *ctx, void (*const kerns[16])(Args), const Args &a, size_t nblk, size_t lds_per_reg, d2g_evlog *ev, hipStream_t s) {
     const size_t m = a.m;
     const bool pow2 = (m & (m - 1)) == 0;
     const size_t lds = m * lds_per_reg;
     const bool use_lds = lds <= 128 * 1024;
-    auto kern = kerns[pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
+    auto kern = kerns[(a.km.q > 1) * 8 + pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
     if (use_lds && lds > 48 * 1024)
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     d2g_timer tm(ctx, ev, s);
@@ -180,7 +188,7 @@ int sketcher_run(d2g_sketcher *sk, const PackedRuns &in, uint64_t xormask, size_
     D2G_CHECK(ctx, (regs_out != nullptr && (counts_out != nullptr || !counts)) || n == 0, counts ? "null regs_out or counts_out" : "null regs_out");
     if (counts) {                                                                     // before the stage touches the device stream
         std::string err;
-        if (int rc = d2g_plan_err(ctx, d2g_plan_check_count_range(in, err), err)) return rc;
+        if (int rc = d2g_plan_err(ctx, d2g_plan_check_count_range(d2g_sketcher_view(sk, in), err), err)) return rc;
     }
     KmerBatch b;
     if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
@@ -210,7 +218,12 @@ uint64_t d2g_oph_plan_nbases(const d2g_oph_plan *p) { return p ? p->nbases : 0; 
 
 int d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                         const uint64_t *genome_run_off, size_t n, int k, d2g_oph_plan **out) {
-    const PackedRuns in{nullptr, 0, run_start, run_len, nrun, genome_run_off, n, k, 0};      // a plan is made without a stream
+    return d2g_oph_plan_create_windowed(ctx, run_start, run_len, nrun, genome_run_off, n, k, 0, out);
+}
+
+int d2g_oph_plan_create_windowed(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                                 const uint64_t *genome_run_off, size_t n, int k, int w, d2g_oph_plan **out) {
+    const PackedRuns in{nullptr, 0, run_start, run_len, nrun, genome_run_off, n, k, 0, d2g_window_norm(k, w)};   // a plan is made without a stream
     if (!ctx || !out) return D2G_ERR_INVALID;
     *out = nullptr;
     PlanHost ph;
@@ -219,7 +232,7 @@ int d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t 
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> p(new (std::nothrow) d2g_oph_plan(), d2g_oph_plan_destroy);
     if (!p) return D2G_ERR_NOMEM;
-    p->ctx = ctx; p->k = k; p->n = n; p->nrun = nrun;
+    p->ctx = ctx; p->k = k; p->w = in.w; p->n = n; p->nrun = nrun;
     p->h_run_len.assign(run_len, run_len + nrun);
     p->h_genome_run_off.assign(genome_run_off, genome_run_off + n + 1);
     p->nkmers = ph.nkmers; p->nbases = ph.nbases; p->nblk = ph.bg.size();
@@ -286,6 +299,12 @@ int d2g_sketcher_create(d2g_ctx *ctx, d2g_sketcher **out) {
     return D2G_OK;
 }
 
+int d2g_sketcher_set_window(d2g_sketcher *sk, int w) {
+    if (!sk) return D2G_ERR_INVALID;
+    sk->w = w > 0 ? w : 0;                       // compared with k by every run: w <= k is no window
+    return D2G_OK;
+}
+
 int d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                      const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                      uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
@@ -336,9 +355,9 @@ int d2g_plan_batch(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed
     D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
     D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
-    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon)) return rc;
+    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon, plan->w)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    *out = KmerBatch{ctx, as_stream(stream), d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon), plan->nblk, plan->runs(canon),
+    *out = KmerBatch{ctx, as_stream(stream), d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon, plan->w), plan->nblk, plan->runs(canon),
                      &ctx->k3};
     d2g_filter_args(plan->filter, &out->km);
     return D2G_OK;
@@ -346,8 +365,8 @@ int d2g_plan_batch(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed
 
 int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerBatch *out, PlanHost *ph_out) {
     d2g_ctx *ctx = sk->ctx;
-    PackedRuns in = caller;
-    if (int rc = d2g_filter_check(ctx, sk->filter, in.k, in.canon)) return rc;   // before the stream, the buffers or an output are touched
+    PackedRuns in = d2g_sketcher_view(sk, caller);
+    if (int rc = d2g_filter_check(ctx, sk->filter, in.k, in.canon, in.w)) return rc;   // before the stream, the buffers or an output are touched
     uint64_t ingested_bases = 0;
     const bool use_ingested = in.packed == nullptr && d2g_k0_ingested(sk, &ingested_bases);
     D2G_CHECK(ctx, in.nrun == 0 || (in.run_start && (in.packed || use_ingested)), "null input");   // refused with an ingested stream left usable
@@ -375,8 +394,8 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerBatch *ou
         std::memcpy(sk->h_stage, in.packed, in.packed_bytes);
         D2G_HIP(ctx, hipMemcpyAsync(sk->d_packed, sk->h_stage, in.packed_bytes, hipMemcpyHostToDevice, s));
     }
-    *out = KmerBatch{ctx, s, d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon), nblk, caller, &sk->k3};
-    out->runs.packed = nullptr; out->runs.packed_bytes = 0;
+    *out = KmerBatch{ctx, s, d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon, in.w), nblk, caller, &sk->k3};
+    out->runs.packed = nullptr; out->runs.packed_bytes = 0; out->runs.w = in.w;
     d2g_filter_args(sk->filter, &out->km);
     return D2G_OK;
 }

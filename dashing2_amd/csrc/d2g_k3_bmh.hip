@@ -73,7 +73,7 @@ struct K3Args {
 
 __device__ __forceinline__ uint32_t bucket_of(uint64_t key, uint32_t bb) { return bb ? (uint32_t)(key >> (64 - bb)) : 0u; }
 
-template <bool FILT>
+template <bool FILT, bool WIN = false>
 __global__ __launch_bounds__(K1_THREADS) void k3_hist_kernel(K3Args a) {
     __shared__ uint32_t hist[K3_MAXB];
     const int tid = threadIdx.x;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_hist_kernel(K3Args a) {
     for (uint32_t i = tid; i < B; i += K1_THREADS) hist[i] = 0;
     __syncthreads();
     const uint64_t xormask = a.xormask;
-    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);              // maskfn: src/enums.h:136-140
         atomicAdd(&hist[bucket_of(key, bb)], 1u);
     });
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(K3_THREADS) void k3_scan_kernel(K3Args a) {
 // genomes with more than 2^l1bits buckets are split in two levels: here by the top l1bits of the bucket index -- the
 // coarse bucket's region is the union of its buckets' regions, reserved through the cursor of its first bucket -- and
 // then by the remaining bits, per coarse bucket, in k3_refine_kernel (<= 2^(12 - l1bits) fronts per workgroup there).
-template <bool FILT>
+template <bool FILT, bool WIN = false>
 __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     // ONE LDS array: first the workgroup's count per (coarse) bucket, then (after one 64-bit reservation
     // per bucket) the next write position relative to the genome's first key -- a genome holds < 2^32
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     }
     __syncthreads();
     uint64_t *keys = (sb ? a.coarse : a.keys) + koff;
-    d2g_for_each_kmer<FILT>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);
         const uint32_t slot = atomicAdd(&pos[bucket_of(key, b1)], 1u);
         keys[slot] = key;
@@ -236,7 +236,7 @@ struct K3cArgs {
     uint32_t TB;
 };
 
-template <bool FILT>
+template <bool FILT, bool WIN = false>
 __global__ __launch_bounds__(K1_THREADS) void k3c_hist_kernel(K3cArgs a) {
     __shared__ uint32_t cnt[K3C_MAXB];
     const int tid = threadIdx.x;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_hist_kernel(K3cArgs a) {
     for (int it = 0; it < K1_CPT; ++it) {
         for (uint32_t i = tid; i < B; i += K1_THREADS) cnt[i] = 0;
         __syncthreads();
-        d2g_for_each_kmer_its<FILT>(a.km, it, it + 1, [&](uint64_t x) { atomicAdd(&cnt[k3c_bucket(x, bb, hb)], 1u); });
+        d2g_for_each_kmer_its<FILT, false, WIN>(a.km, it, it + 1, [&](uint64_t x) { atomicAdd(&cnt[k3c_bucket(x, bb, hb)], 1u); });
         __syncthreads();
         // a tile holds at most 16384 k-mers: the counts fit u16
         uint16_t *dst = a.tile_cnt + ((size_t)blockIdx.x * K1_CPT + it) * K3C_MAXB;
@@ -303,7 +303,7 @@ struct K3cScatterLds {
     uint32_t wsum[K1_THREADS / 64];
 };
 
-template <bool FILT>
+template <bool FILT, bool WIN = false>
 __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char k3c_lds_raw[];
     K3cScatterLds &L = *reinterpret_cast<K3cScatterLds *>(k3c_lds_raw);
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
         if (tid == K1_THREADS - 1) L.lbase[K3C_MAXB] = run;
         __syncthreads();
         if (total == 0) continue;                                    // uniform: every thread computed the same total
-        d2g_for_each_kmer_its<FILT>(a.km, it, it + 1, [&](uint64_t x) {
+        d2g_for_each_kmer_its<FILT, false, WIN>(a.km, it, it + 1, [&](uint64_t x) {
             L.stage[atomicAdd(&L.lcur[k3c_bucket(x, bb, hb)], 1u)] = (uint32_t)x;
         });
         __syncthreads();
@@ -1300,7 +1300,7 @@ int k3_layout(d2g_ctx *ctx, const PackedRuns &in, K3Host &kh) {
     for (size_t g = 0; g < n; ++g) {
         uint64_t nk = 0, chunks = 0;
         for (uint64_t r = in.genome_run_off[g]; r < in.genome_run_off[g + 1]; ++r) {
-            const uint64_t rk = (uint64_t)in.run_len[r] - k + 1;
+            const uint64_t rk = d2g_run_emissions_of(in.run_len[r], k, in.w);
             nk += rk; chunks += div_up<uint64_t>(rk, K1_CHUNK);
         }
         D2G_CHECK(ctx, nk < (1ull << 32), "--multiset: more than 2^32 k-mers in one input");
@@ -1459,10 +1459,13 @@ int K3Run::bucket(size_t g_lo, size_t g_hi) {
     if (kh.compact) {
         const unsigned nb = (unsigned)nblk;
         const bool filt = km.ftab != nullptr;           // hist and scatter must drop the same k-mers: one switch for both
-        if (nb) hipLaunchKernelGGL(filt ? k3c_hist_kernel<true> : k3c_hist_kernel<false>, dim3(nb), dim3(K1_THREADS), 0, s, kc);
+        const bool win = km.q > 1;                      // ... and walk the same ones: k-mers or minimizers
+        const auto hist = win ? (filt ? k3c_hist_kernel<true, true> : k3c_hist_kernel<false, true>) : (filt ? k3c_hist_kernel<true> : k3c_hist_kernel<false>);
+        if (nb) hipLaunchKernelGGL(hist, dim3(nb), dim3(K1_THREADS), 0, s, kc);
         hipLaunchKernelGGL(k3c_scan_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, kc);
         if (nb) {
-            const auto scatter = filt ? k3c_scatter_kernel<true> : k3c_scatter_kernel<false>;
+            const auto scatter = win ? (filt ? k3c_scatter_kernel<true, true> : k3c_scatter_kernel<false, true>)
+                                     : (filt ? k3c_scatter_kernel<true> : k3c_scatter_kernel<false>);
             D2G_HIP(ctx, hipFuncSetAttribute((const void *)scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K3cScatterLds)));
             hipLaunchKernelGGL(scatter, dim3(nb), dim3(K1_THREADS), sizeof(K3cScatterLds), s, kc);
         }
@@ -1472,9 +1475,13 @@ int K3Run::bucket(size_t g_lo, size_t g_hi) {
     const unsigned blk_lo = kh.gblk[g_lo], nb = (g_lo == 0 && g_hi == n) ? (unsigned)nblk : kh.gblk[g_hi] - blk_lo;
     a.km.blk0 = blk_lo; a.g0 = (uint32_t)g_lo;
     const bool filt = km.ftab != nullptr;               // hist and scatter must drop the same k-mers: one switch for both
-    if (nb) hipLaunchKernelGGL(filt ? k3_hist_kernel<true> : k3_hist_kernel<false>, dim3(nb), dim3(K1_THREADS), 0, s, a);
+    const bool win = km.q > 1;                          // ... and walk the same ones: k-mers or minimizers
+    const auto hist = win ? (filt ? k3_hist_kernel<true, true> : k3_hist_kernel<false, true>) : (filt ? k3_hist_kernel<true> : k3_hist_kernel<false>);
+    const auto scatter = win ? (filt ? k3_scatter_kernel<true, true> : k3_scatter_kernel<false, true>)
+                             : (filt ? k3_scatter_kernel<true> : k3_scatter_kernel<false>);
+    if (nb) hipLaunchKernelGGL(hist, dim3(nb), dim3(K1_THREADS), 0, s, a);
     hipLaunchKernelGGL(k3_scan_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(K3_THREADS), 0, s, a);
-    if (nb) hipLaunchKernelGGL(filt ? k3_scatter_kernel<true> : k3_scatter_kernel<false>, dim3(nb), dim3(K1_THREADS), 0, s, a);
+    if (nb) hipLaunchKernelGGL(scatter, dim3(nb), dim3(K1_THREADS), 0, s, a);
     const unsigned l2_lo = kh.l2_start[g_lo], nl = kh.l2_start[g_hi] - l2_lo;
     if (nb && nl) {
         a.l2_tb0 += l2_lo; a.l2_bits += l2_lo;

@@ -3,6 +3,7 @@
 #pragma once
 #include "d2g_internal.h"
 #include "d2g_plan.h"                 // K1_THREADS, K1_CHUNK, K1_CPT, K1_BLOCK_CHUNKS: the geometry the plan is built for
+#include "d2g_minq.h"                 // the windowed walker's sliding minimum
 
 // Thomas Wang's 64-bit mix (sketch::hash::WangHash::hash; call sites src/enums.h:138, src/oph.h:49)
 __device__ __forceinline__ uint64_t wang64(uint64_t k) {
@@ -31,6 +32,9 @@ struct KmerArgs {
     int k;
     int canon;
     uint32_t blk0;                 // first launch-plan block of this launch (a launch may cover a sub-range of the plan)
+    // K1w, -w > k: k-mers per window, q = w - k + 1 (1 = no window).  Read only by the WIN instantiations of the walker below; it sits
+    // in what was padding in front of ftab, so every other field is where it was.
+    uint32_t q;
     // K1f, --filterset (d2g_filter.hip): open-addressing table of RAW (canonical when canon) k-mers; nullptr = no filter.
     // Read only by the FILT instantiations of the walker below.
     const uint64_t *ftab;          // [fmask + 1] keys, D2G_FILTER_EMPTY = free slot; [fmask + 1] != 0: the all-ones k-mer is in the set
@@ -64,6 +68,108 @@ __device__ __forceinline__ uint32_t fsr(uint32_t hi, uint32_t lo, uint32_t sh) {
     return __builtin_amdgcn_alignbit(hi, lo, sh);
 }
 
+// K1w: the windowed walker, -w > k (the reference's bns::Encoder with a Spacer(k, w) and score::Lex; restated from its published
+// form, parity unpinned).  A chunk is K1_CHUNK consecutive WINDOW POSITIONS of one run; position i emits the k-mer of x_i .. x_{i+q-1}
+// with the smallest score x ^ D2G_LEX_XOR, once per position.  The lane rolls q - 1 k-mers ahead of its first position and keeps the
+// window's minimum in a register queue (d2g_minq.h).  The emitted k-mer then meets the filter / the screen's table as any k-mer does.
+// Reads: only dwords that hold a base of the lane's own positions' windows, all inside the run -- nothing the tail pad has to cover.
+constexpr int D2G_MINQ_DEPTH = 8;
+
+struct D2gBaseStream {            // the packed bases from base index p on, one at a time; a dword is loaded when its first base is asked for
+    const uint32_t *w; uint32_t W; int have;
+    __device__ __forceinline__ D2gBaseStream(const uint32_t *packed, uint64_t p) : w(packed + (p >> 4)) {
+        const uint32_t o = (uint32_t)(p & 15);
+        W = *w >> (2 * o); have = 16 - (int)o;
+    }
+    __device__ __forceinline__ uint64_t next() {
+        if (have == 0) { W = *++w; have = 16; }
+        const uint64_t cb = W & 3u;
+        W >>= 2; --have;
+        return cb;
+    }
+};
+
+template <bool FILT, bool HITS, class F>
+__device__ __forceinline__ void d2g_for_each_minimizer_its(const KmerArgs &a, int it0, int it1, F &&f) {
+    const int tid = threadIdx.x;
+    const uint32_t b = blockIdx.x + a.blk0;
+    const uint64_t c0 = a.blk_chunk0[b];
+    const uint32_t nc = a.blk_nchunks[b];
+    const uint32_t rlo = a.blk_run_lo[b], rhi = a.blk_run_hi[b];
+    const int k = a.k, q = (int)a.q;
+    const uint64_t kmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1);
+    const int rcshift = 2 * (k - 1);
+    const bool canon = a.canon != 0;
+
+    for (int it = it0; it < it1; ++it) {
+        const uint32_t ci_blk = it * K1_THREADS + tid;
+        if (ci_blk >= nc) break;
+        const uint64_t c = c0 + ci_blk;
+        // run containing chunk c: the LAST run of the block that starts at or before it (a run shorter than w owns no chunk)
+        uint32_t lo = rlo, hi = rhi;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.run_chunk_off[mid] <= c) lo = mid; else hi = mid;
+        }
+        const uint64_t ci = c - a.run_chunk_off[lo];
+        const uint64_t np = (uint64_t)a.run_len[lo] - (uint32_t)(k + q - 1) + 1;    // window positions of the run (len >= w: it owns a chunk)
+        const uint64_t p = a.run_start[lo] + ci * K1_CHUNK;                         // first base of the lane's first window
+        const uint64_t left = np - ci * K1_CHUNK;
+        const int n = left < (uint64_t)K1_CHUNK ? (int)left : K1_CHUNK;
+
+        D2gBaseStream bs(a.packed, p);
+        uint64_t fwd = 0, rc = 0;
+        for (int j = 0; j < k - 1; ++j) {
+            const uint64_t cb = bs.next();
+            fwd = (fwd << 2) | cb;
+            rc = (rc >> 2) | ((3 - cb) << rcshift);
+        }
+        D2gMinQueue<D2G_MINQ_DEPTH> mq;
+        mq.clear();
+        const int steps = q - 1 + n;                                                // k-mers t = 0 .. q - 2 + n; position i closes at t = i + q - 1
+#pragma unroll 1
+        for (int t = 0; t < steps; ++t) {
+            const uint64_t cb = bs.next();
+            fwd = ((fwd << 2) | cb) & kmask;
+            rc = (rc >> 2) | ((3 - cb) << rcshift);
+            mq.push((canon ? (fwd < rc ? fwd : rc) : fwd) ^ D2G_LEX_XOR, t);
+            const int first = t - (q - 1);
+            if (first < 0) continue;
+            mq.expire(first);
+            if (mq.empty()) {
+                // every entry the queue kept has left and later ones were dropped: the window's q k-mers once more
+                D2gBaseStream rs(a.packed, p + (uint64_t)first);
+                uint64_t f2 = 0, r2 = 0;
+                for (int j = 0; j < k - 1; ++j) {
+                    const uint64_t c2 = rs.next();
+                    f2 = (f2 << 2) | c2;
+                    r2 = (r2 >> 2) | ((3 - c2) << rcshift);
+                }
+                mq.clear();
+#pragma unroll 1
+                for (int u = first; u <= t; ++u) {
+                    const uint64_t c2 = rs.next();
+                    f2 = ((f2 << 2) | c2) & kmask;
+                    r2 = (r2 >> 2) | ((3 - c2) << rcshift);
+                    mq.push((canon ? (f2 < r2 ? f2 : r2) : f2) ^ D2G_LEX_XOR, u);
+                }
+            }
+            const uint64_t x = mq.front() ^ D2G_LEX_XOR;
+            if constexpr (FILT) {
+                const uint64_t v = a.ftab[d2g_filter_slot(x, a.fshift)];
+                if constexpr (HITS) {
+                    const uint32_t slot = d2g_filter_find(a, x, v);
+                    if (slot != D2G_FILTER_NOSLOT) f(x, slot);
+                } else {
+                    if (!d2g_filter_hit(a, x, v)) f(x);
+                }
+            } else {
+                f(x);
+            }
+        }
+    }
+}
+
 // f(x) once per k-mer of the chunks this lane owns in workgroup blockIdx.x; x = canonical
 // (min(fwd, revcomp)) or forward 2-bit k-mer.  A lane owns chunk (it * K1_THREADS + tid).
 // IT0 <= it < IT1: the passes ("tiles" of K1_THREADS chunks = K1_THREADS * K1_CHUNK k-mers) of the workgroup to walk
@@ -71,8 +177,14 @@ __device__ __forceinline__ uint32_t fsr(uint32_t hi, uint32_t lo, uint32_t sh) {
 // a template flag, so that the unfiltered instantiations are the code they were (profiles/filter_resource_usage.txt)
 // HITS (with FILT): the third mode, K1s -- f(x, slot) for the k-mers that ARE in a.ftab, slot as d2g_filter_find gives it; a miss
 // does nothing.  The other instantiations stay the code they were (profiles/screen_resource_usage.txt)
-template <bool FILT = false, bool HITS = false, class F>
+// WIN: the fourth, K1w -- f sees the minimizer of every window position instead (d2g_for_each_minimizer_its above), under either of
+// the other two flags.  The unwindowed instantiations stay the code they were (profiles/window_resource_usage.txt)
+template <bool FILT = false, bool HITS = false, bool WIN = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0, int it1, F &&f) {
+    if constexpr (WIN) {
+        d2g_for_each_minimizer_its<FILT, HITS>(a, it0, it1, static_cast<F &&>(f));
+        return;
+    }
     const int tid = threadIdx.x;
     const uint32_t b = blockIdx.x + a.blk0;
     const uint64_t c0 = a.blk_chunk0[b];
@@ -165,8 +277,8 @@ __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0
     }
 }
 
-template <bool FILT = false, bool HITS = false, class F>
+template <bool FILT = false, bool HITS = false, bool WIN = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer(const KmerArgs &a, F &&f) {
     static_assert(FILT || !HITS, "the hit mode walks a table");
-    d2g_for_each_kmer_its<FILT, HITS>(a, 0, K1_CPT, static_cast<F &&>(f));
+    d2g_for_each_kmer_its<FILT, HITS, WIN>(a, 0, K1_CPT, static_cast<F &&>(f));
 }

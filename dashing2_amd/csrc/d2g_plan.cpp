@@ -13,12 +13,14 @@ int d2g_plan_build(const PackedRuns &in, PlanHost &p, std::string &err) {
     const int k = in.k;
     if (!in.genome_run_off || (nrun && !(in.run_len && in.run_start))) return refuse(err, "oph plan: null table");
     if (k < 1 || k > 32) return refuse(err, "k must be in [1,32] (exact 2-bit encoding path)", D2G_ERR_UNSUPPORTED);
+    if (d2g_window_q(k, in.w) > D2G_WINDOW_MAX_Q)
+        return refuse(err, "window too wide: -w may exceed k by at most 4095 (a window of 4096 k-mers)", D2G_ERR_UNSUPPORTED);
     if (in.genome_run_off[n] != nrun) return refuse(err, "oph plan: genome_run_off[n] != nrun");
     if (nrun >= (1ull << 32)) return refuse(err, "oph plan: too many runs");
     p.chunk_off.assign(nrun + 1, 0);
     for (size_t r = 0; r < nrun; ++r) {
         if (in.run_len[r] < (uint32_t)k) return refuse(err, "run shorter than k");
-        const uint64_t nk = (uint64_t)in.run_len[r] - k + 1;
+        const uint64_t nk = d2g_run_emissions_of(in.run_len[r], k, in.w);
         p.chunk_off[r + 1] = p.chunk_off[r] + (nk + K1_CHUNK - 1) / K1_CHUNK;
         p.nkmers += nk;
         p.nbases += in.run_len[r];
@@ -55,12 +57,14 @@ int d2g_plan_check_count_range(const PackedRuns &in, std::string &err) {
     for (size_t g = 0; g < in.n; ++g) {
         uint64_t nk = 0;
         for (uint64_t r = in.genome_run_off[g]; r < in.genome_run_off[g + 1] && r < in.nrun; ++r)
-            if (in.run_len[r] >= (uint32_t)in.k) nk += (uint64_t)in.run_len[r] - in.k + 1;
+            nk += d2g_run_emissions_of(in.run_len[r], in.k, in.w);
         if (nk >= (1ull << 32))
             return refuse(err, "k-mer counts of a genome with 2^32 k-mers or more (the reference's uint32 counts wrap there)", D2G_ERR_UNSUPPORTED);
     }
     return D2G_OK;
 }
+
+extern "C" uint64_t d2g_run_emissions(uint64_t len, int k, int w) { return k >= 1 ? d2g_run_emissions_of(len, k, w) : 0; }
 
 PlanLayout d2g_plan_layout(size_t nrun, size_t nblk) {
     PlanLayout l{};

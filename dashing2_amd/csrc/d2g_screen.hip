@@ -69,10 +69,11 @@ struct ScreenCountArgs {
     uint64_t D;
 };
 
+template <bool WIN>
 __global__ __launch_bounds__(K1_THREADS) void screen_count_kernel(ScreenCountArgs a) {
     uint32_t *const row = a.cnt + (size_t)a.genome_row[a.km.blk_genome[blockIdx.x]] * a.D;
     const uint32_t *const slot_id = a.slot_id;
-    d2g_for_each_kmer<true, true>(a.km, [&](uint64_t, uint32_t slot) {
+    d2g_for_each_kmer<true, true, WIN>(a.km, [&](uint64_t, uint32_t slot) {
         (void)atomicAdd(&row[slot_id[slot]], 1u);                // result unused: a non-returning global_atomic_add
     });
 }
@@ -117,7 +118,7 @@ int screen_account(d2g_ctx *ctx, const d2g_screen *sc, const PackedRuns &in, con
         if (genome_run_off[g] > genome_run_off[g + 1] || genome_run_off[g + 1] > nrun) return D2G_OK;
         for (uint64_t r = genome_run_off[g]; r < genome_run_off[g + 1]; ++r) {
             if (run_len[r] < (uint32_t)sc->k) return D2G_OK;
-            add[genome_row[g]] += (uint64_t)run_len[r] - sc->k + 1;
+            add[genome_row[g]] += d2g_run_emissions_of(run_len[r], sc->k, in.w);
         }
     }
     for (size_t q = 0; q < sc->nrows; ++q)
@@ -144,7 +145,7 @@ int screen_launch(d2g_screen *sc, const KmerBatch &b, const uint32_t *genome_row
         km.fshift = 64 - lg; km.blk0 = 0;
         const ScreenCountArgs a{km, sc->d_slot_id.get(), sc->d_grow.get(), sc->d_cnt.get(), sc->D};
         d2g_timer tm(ctx, &ctx->ev_screen, s);
-        hipLaunchKernelGGL(screen_count_kernel, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a);
+        hipLaunchKernelGGL(km.q > 1 ? screen_count_kernel<true> : screen_count_kernel<false>, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a);
         tm.stop();
         D2G_HIP(ctx, hipGetLastError());
     }
@@ -156,7 +157,7 @@ int screen_launch(d2g_screen *sc, const KmerBatch &b, const uint32_t *genome_row
 
 void d2g_warm_screen() {
     hipFuncAttributes a;
-    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&screen_count_kernel));
+    (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&screen_count_kernel<false>));
 }
 
 extern "C" {
@@ -286,7 +287,7 @@ int d2g_sketcher_run_screen(d2g_sketcher *sk, const uint8_t *packed, size_t pack
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
     if (int rc = screen_check(ctx, sc, k, canon)) return rc;        // before the stage touches the stream or the buffers
     std::vector<uint64_t> add;
-    if (int rc = screen_account(ctx, sc, in, genome_row, add)) return rc;
+    if (int rc = screen_account(ctx, sc, d2g_sketcher_view(sk, in), genome_row, add)) return rc;
     KmerBatch b;
     if (int rc = d2g_sketcher_stage(sk, in, &b, nullptr)) return rc;
     if (int rc = screen_launch(sc, b, genome_row, add)) return rc;

@@ -12,7 +12,7 @@ Launch:  python -m dashing2_amd.dist cmp --presketched stack.bin --cmpout dist.b
          python -m dashing2_amd.dist sketch -F files.txt -o stack.bin [...]
              (one process: `D2G_DEVICES=all dashing2 sketch`, a pair of device threads per GPU -- the product path since round 4)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
-             -m dashing2_amd.dist sketch -F files.txt -o stack.bin [-k 31 -S 1024 --multiset ...]
+             -m dashing2_amd.dist sketch -F files.txt -o stack.bin [-k 31 -w 50 -S 1024 --multiset ...]
 The torch.distributed classes below (sharded_allpairs, RowShardedAllPairs) are the same exchange written against
 torch collectives: bench.py's fallback when the C-ABI engine cannot be used, and what the gloo CPU tests exercise.
 SKETCH shards by input (rank r takes files r, r+world, ...; each rank runs the CLI on its own GPU;

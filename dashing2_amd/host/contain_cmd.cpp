@@ -74,7 +74,9 @@ int contain_main(int argc, char **argv) {
     if (db.dtype != 0) refuse_out_of_scope("contain over a database that is not DNA (data type " + std::to_string(db.dtype) + " in its header)");
     if (db.S == 0) refuse_out_of_scope("contain over a database of sketch size 0");
     if (db.k > 32 || db.k == 0) refuse_out_of_scope("contain with k = " + std::to_string(db.k) + " (k-mers of 1 .. 32 bases are exact 64-bit keys; longer ones are rolling hashes)");
-    if (db.w != db.k) refuse_out_of_scope("contain over windowed minimizers (window " + std::to_string(db.w) + ", k " + std::to_string(db.k) + ")");
+    // a header w <= k (0 included) is every k-mer.  A database of windowed minimizers (w > k, what `sketch -s -w` writes) stays refused
+    // here: the library screens minimizers (d2g_sketcher_set_window + d2g_sketcher_run_screen), this command does not ask it to yet
+    if (db.w > db.k) refuse_out_of_scope("contain over windowed minimizers (window " + std::to_string(db.w) + ", k " + std::to_string(db.k) + ")");
     if (db.nrefs > D2G_SCREEN_MAX_KEYS / db.S) refuse_out_of_scope("contain over a database of more than 2^30 keys (" + std::to_string(db.nrefs) + " references x " + std::to_string(db.S) + ")");
     Options o;
     if (const char *d = std::getenv("D2G_DEVICE")) o.device = std::atoi(d);

@@ -41,6 +41,9 @@ void sketch_usage() {
                          "MI355X build: One-Permutation SetSketch (default) or --multiset BagMinHash of k-mers (k <= 32),\n"
                          "optional all-pairs comparison.\n"
                          "  -k/--kmer-length k   -S/--sketchsize S   -L/--sketch-size-l2 l   -p/--threads n\n"
+                         "  -w/--window-size w     w > k: only the minimizer of every window of w bases (the k-mer x of its w - k + 1 with the smallest\n"
+                         "                         x ^ 0xe37e28c4271b5a2d, once per window position) is sketched, counted or filtered;         \n"
+                         "                         w <= k: every k-mer.  Cache and set file names carry .w<w>; at most w - k = 4095\n"
                          "  -F/--ffile paths.txt -Q/--qfile queries.txt  -o/--outfile stacked.bin\n"
                          "  --cmpout/--distout/--cmp-outfile out   --phylip   --binary-output   --asymmetric-all-pairs\n"
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
@@ -336,8 +339,9 @@ int parse_options(int argc, char **argv, Options &o) {
                              "(fastxsketch.cpp:420), which is outside this build's hot-path scope.\n", o.k);
         return 1 + 1;
     }
-    if (o.w > o.k) {
-        std::fprintf(stderr, "dashing2 (MI355X): windowed minimizers (-w > k) are outside this build's hot-path scope.\n");
+    if (o.w > o.k && o.w - o.k + 1 > D2G_WINDOW_MAX_Q) {      // K1w: said here, before a GPU is asked for; the library refuses it too
+        std::fprintf(stderr, "dashing2 (MI355X): -w %d with -k %d: a window of more than %d k-mers (w - k > %d) is outside this build's "
+                             "hot-path scope.\n", o.w, o.k, D2G_WINDOW_MAX_Q, D2G_WINDOW_MAX_Q - 1);
         return 1 + 1;
     }
     if (o.is_cmp && o.greedy) {

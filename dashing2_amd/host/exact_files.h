@@ -15,9 +15,9 @@
 
 namespace d2h {
 
-struct ExactNameOpts { int k; bool canon; uint64_t seedseed; unsigned count_threshold; std::string outprefix; };
+struct ExactNameOpts { int k; bool canon; uint64_t seedseed; unsigned count_threshold; std::string outprefix; int w = 0; };
 
-// <path>[.seed<s>][.rc_canon].k<k>[.ct_threshold<c>].FullMmerSet.DNA.kmerset64 -- no .sketchsize part (fastxmerge.cpp:85), and
+// <path>[.seed<s>][.rc_canon].k<k>[.w<w>][.ct_threshold<c>].FullMmerSet.DNA.kmerset64 (.w<w> when w > k, fastxmerge.cpp:87-90) -- no .sketchsize part (fastxmerge.cpp:85), and
 // FullMmerSet for BOTH modes (fastxsketch.cpp:313 passes iskmer for the count dictionary, fastxmerge.cpp:112-114)
 inline std::string exact_key_file(const ExactNameOpts &o, const std::string &path) {
     std::string ret = path.substr(0, path.find_first_of(' '));
@@ -28,6 +28,7 @@ inline std::string exact_key_file(const ExactNameOpts &o, const std::string &pat
     if (o.seedseed != 0) ret += ".seed" + std::to_string(o.seedseed);
     if (o.canon) ret += ".rc_canon";
     ret += ".k" + std::to_string(o.k);
+    if (o.w > o.k) ret += ".w" + std::to_string(o.w);
     if (o.count_threshold > 0) ret += ".ct_threshold" + std::to_string(int(o.count_threshold));
     return ret + ".FullMmerSet.DNA.kmerset64";
 }

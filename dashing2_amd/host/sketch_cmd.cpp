@@ -15,7 +15,7 @@ namespace d2h {
 
 namespace {
 
-// src/fastxmerge.cpp:70-120 for DNA, unspaced, w <= k: OPH set sketches and exact-counting multiset sketches
+// src/fastxmerge.cpp:70-120 for DNA, unspaced: OPH set sketches and exact-counting multiset sketches
 std::string makedest(const Options &o, const std::string &path) {
     std::string ret = path.substr(0, path.find_first_of(' '));
     if (!o.outprefix.empty()) ret = o.outprefix + '/' + trim_folder(path);
@@ -23,6 +23,7 @@ std::string makedest(const Options &o, const std::string &path) {
     if (o.canon) ret += ".rc_canon";
     ret += ".sketchsize" + std::to_string(o.sketchsize);
     ret += ".k" + std::to_string(o.k);
+    if (o.w > o.k) ret += ".w" + std::to_string(o.w);     // fastxmerge.cpp:87-90
     if (o.count_threshold > 0) {
         // fastxmerge.cpp:91-95 prints std::to_string(double) when fmod(threshold, 1) != 0 -- but Dashing2Options::count_threshold_ is a
         // uint32_t (d2.h:103) filled by std::atoi (options.h:352), so that branch cannot be reached from the reference's CLI
@@ -125,7 +126,9 @@ struct JobFilter {
         check(nullptr, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
         if (d2g_seqpack_add_path(sp, o.filterset.c_str()) != D2G_OK) die("Failed to open file " + o.filterset + " for reading");   // d2.cpp:63
         o.filterset_built = true;
-        o.filterset_size = d2g_seqpack_nkmers(sp, 0);     // occurrences: the reference sorts but never deduplicates (filterset.h:82)
+        o.filterset_size = 0;                             // occurrences: the reference sorts but never deduplicates (filterset.h:82);
+        const uint32_t *rl = d2g_seqpack_run_len(sp);     // with -w the filter file's minimizers, one per window position (options.h:556)
+        for (size_t r = 0, nr = d2g_seqpack_nruns(sp); r < nr; ++r) o.filterset_size += d2g_run_emissions(rl[r], o.k, o.w);
         if (o.cache) std::fprintf(stderr, "dashing2 (MI355X): warning: --cache with --filterset: cache file names do not carry the filter "
                                           "(fastxmerge.cpp:70-120); existing caches are loaded as they are, filtered or not.\n");
     }
@@ -134,8 +137,8 @@ struct JobFilter {
     d2g_kmer_filter *attach(d2g_ctx *ctx, d2g_sketcher *sk, const Options &o) {
         if (!sp) return nullptr;
         d2g_kmer_filter *f = nullptr;
-        check(ctx, d2g_kmer_filter_create(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp), d2g_seqpack_run_len(sp),
-                                          d2g_seqpack_nruns(sp), o.k, o.canon, &f), "d2g_kmer_filter_create");
+        check(ctx, d2g_kmer_filter_create_windowed(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp),
+                                                   d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp), o.k, o.canon, o.w, &f), "d2g_kmer_filter_create");
         check(ctx, d2g_sketcher_set_filter(sk, f), "d2g_sketcher_set_filter");
         std::lock_guard<std::mutex> lk(mu);
         if (g_stats.on && !reported) {
@@ -231,6 +234,7 @@ struct DeviceSide {
         }
         d2g_sketcher *sk = nullptr;
         check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+        check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
         d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);              // before the first group
         double gpu = 0; uint64_t bases = 0; size_t ndevg = 0, nhostg = 0;
         for (IngestGroup r; pipe.next(r);) {
@@ -420,6 +424,7 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     const uint32_t *run_len = d2g_seqpack_run_len(sp);
     d2g_sketcher *sk = nullptr;
     check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+    check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
     JobFilter filter(o);
     d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);                         // fastxsketchbyseq.cpp:327,370,383,420-423
     std::vector<uint64_t> regs, rs_rel, goff_rel, ndist;
@@ -483,7 +488,7 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
     const size_t N = o.paths.size();
     if (!N) die(o.presketched ? "No paths provided to --presketched" : "Can't sketch empty path set");
     const bool weighted = o.exact == 2;
-    const ExactNameOpts no{o.k, o.canon, o.seedseed, o.count_threshold, o.outprefix};
+    const ExactNameOpts no{o.k, o.canon, o.seedseed, o.count_threshold, o.outprefix, o.w};
     es.weighted = weighted;
     es.keys.assign(N, {}); es.counts.assign(N, {});
     res.destination_files.resize(N);
@@ -512,6 +517,7 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
         d2g_ctx *ctx = lctx.get();
         d2g_sketcher *sk = nullptr;
         check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+        check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
         d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);
         const uint64_t xormask = d2g_seed_mask(o.seedseed);
         size_t limit = size_t(32) << 20;

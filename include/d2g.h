@@ -254,7 +254,29 @@ typedef struct d2g_oph_plan d2g_oph_plan;
 int  d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                          const uint64_t *genome_run_off, size_t n, int k, d2g_oph_plan **out);
 void d2g_oph_plan_destroy(d2g_oph_plan *plan);
-uint64_t d2g_oph_plan_nkmers(const d2g_oph_plan *plan);   /* total k-mers the plan covers */
+uint64_t d2g_oph_plan_nkmers(const d2g_oph_plan *plan);   /* total k-mers the plan covers: emissions (window positions under a window) */
+
+/* ---- K1w: windowed minimizers, -w / --window-size -------------------------------
+ * Replaces bns::Encoder<bns::score::Lex> over a Spacer(k, w) (reference d2.h:136, contain_main.cpp:34,185; the enumerator itself lives
+ * in the absent bonsai and is restated from its published form: parity unpinned).  With w > k, q = w - k + 1: a run of valid bases
+ * with k-mers x_0 .. x_{nk-1} has nk - q + 1 = len - w + 1 window positions (none when len < w); position i emits the ONE k-mer of
+ * x_i .. x_{i+q-1} with the smallest score x ^ 0xe37e28c4271b5a2d (compared as uint64), once per position, duplicates included.
+ * Nothing spans two runs.  The emitted k-mer stands for "a k-mer of the input" for everything downstream -- the filter test, the
+ * OPH register, counts, the -m threshold, the exact counter, the distinct count, the screen's hit counters -- and every multiplicity
+ * is a number of window positions.  w <= k (0 included) is no window: every k-mer, bit for bit as without one.
+ * Cap: w - k <= 4095 (D2G_WINDOW_MAX_Q = 4096 k-mers per window); a wider window is D2G_ERR_UNSUPPORTED from the plan / the run.
+ * A window is an attribute of a plan or a sketcher, like a filter: every d2g_*_dev call over a windowed plan and every
+ * d2g_sketcher_run* (packed == NULL included), d2g_kmer_filter_create_dev and d2g_screen_add_dev / d2g_sketcher_run_screen honour it.
+ * The one-shot host-pointer entry points (d2g_oph_sketch, ...) take none.  Runs are still cut at k: a run with k <= len < w is legal
+ * and emits nothing.  A d2g_seqpack and the device parser know no window: their per-genome totals (d2g_seqpack_nkmers, genome_nkmers) stay
+ * k-mer counts; d2g_oph_plan_nkmers and d2g_run_emissions give emissions.  A run longer than 2^30 bases is split by the packer into
+ * pieces that overlap by k - 1 bases, so the windows across such a cut are not walked. */
+#define D2G_WINDOW_MAX_Q 4096
+/* host, no GPU: the k-mers a run of len valid bases emits under (k, w) -- the one count every layout and total follows from */
+uint64_t d2g_run_emissions(uint64_t len, int k, int w);
+/* d2g_oph_plan_create is the w = 0 form */
+int  d2g_oph_plan_create_windowed(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                                  const uint64_t *genome_run_off, size_t n, int k, int w, d2g_oph_plan **out);
 uint64_t d2g_oph_plan_nbases(const d2g_oph_plan *plan);   /* total bases in the runs */
 int  d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev,
                         int canon, uint64_t xormask, size_t sketchsize,
@@ -281,6 +303,9 @@ int d2g_oph_sketch_counts(d2g_ctx *ctx, const uint8_t *packed, size_t packed_byt
 typedef struct d2g_sketcher d2g_sketcher;
 int  d2g_sketcher_create(d2g_ctx *ctx, d2g_sketcher **out);
 void d2g_sketcher_destroy(d2g_sketcher *sk);
+/* K1w (above): every later d2g_sketcher_run* of this sketcher walks the minimizers of windows of w bases when w > its k; 0, or any
+ * w <= k, switches the window off.  A w beyond the cap is refused by the run (it is the run that knows k). */
+int  d2g_sketcher_set_window(d2g_sketcher *sk, int w);
 int  d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
                       const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                       const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
@@ -336,14 +361,17 @@ int  d2g_kmer_filter_create_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const ui
 /* host-pointer form: the packed-run-stream arguments of d2g_oph_sketch (so a d2g_seqpack feeds it); synchronises */
 int  d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
                             size_t nrun, int k, int canon, d2g_kmer_filter **out);
+/* the same under a window (K1w): the filter input is enumerated with it, noccurrences counts its emissions; w <= k: no window */
+int  d2g_kmer_filter_create_windowed(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                                     const uint32_t *run_len, size_t nrun, int k, int canon, int w, d2g_kmer_filter **out);
 void d2g_kmer_filter_destroy(d2g_kmer_filter *filter);
 /* k-mer occurrences put in (duplicates counted: the reference's data_.size()), distinct keys held, bytes of the device table;
  * synchronises the device */
 int  d2g_kmer_filter_info(d2g_ctx *ctx, const d2g_kmer_filter *filter, uint64_t *noccurrences, uint64_t *ndistinct, size_t *table_bytes);
 /* membership of n raw 2-bit k-mers (host arrays; canonical ones for a canon filter), through the SAME device probe the walker uses */
 int  d2g_kmer_filter_contains(d2g_ctx *ctx, const d2g_kmer_filter *filter, const uint64_t *kmers, size_t n, uint8_t *out);
-/* attach (NULL detaches).  The filter must outlive the plan / sketcher or be detached first.  A filter of another context, k or
- * canon makes the SKETCH call return D2G_ERR_INVALID, before it writes anything.  More than 2^31 k-mers: D2G_ERR_UNSUPPORTED at
+/* attach (NULL detaches).  The filter must outlive the plan / sketcher or be detached first.  A filter of another context, k,
+ * canon or window (a filter remembers the window it was built under, 0 = none) makes the SKETCH call return D2G_ERR_INVALID, before it writes anything.  More than 2^31 k-mers: D2G_ERR_UNSUPPORTED at
  * creation; no memory for the table: D2G_ERR_NOMEM (never a smaller table).
  * A plan's filter is honoured by d2g_oph_sketch_dev, d2g_oph_count_dev, d2g_oph_sketch_mincount_dev, d2g_bmh_sketch_dev and d2g_kmer_sets_dev; a sketcher's by every
  * d2g_sketcher_run*, packed == NULL (K0-ingested) included.  --multiset calls with a filter walk the input once more, first, to count
