@@ -224,6 +224,7 @@ SIGNATURES = {
     "d2g_cmp_set_create_codes_dev": (_int, [_vp, _vp, _sz, _sz, _int, _vp, C.POINTER(_vp)]),
     "d2g_cmp_set_create_codes": (_int, [_vp, _vp, _sz, _sz, _int, C.POINTER(_vp)]),
     "d2g_cmp_set_operand_bytes": (_sz, [_vp]),
+    "d2g_cmp_set_id_bits": (_int, [_vp]),
     "d2g_cmp_dist_trunc_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _int, _int, _vp]),
     "d2g_cmp_knn_dev": (_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "d2g_knn_finish": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _sz, _int, _vp, _vp, _vp, _sz, C.POINTER(_sz), C.POINTER(_sz)]),
@@ -259,7 +260,12 @@ def lib():
                           "(dashing2_amd has no CPU fallback)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
-            f = getattr(l, name)
+            try:
+                f = getattr(l, name)
+            except AttributeError:
+                if os.environ.get("D2G_LIB"):      # another build selected for an A/B measurement may predate a symbol: the call fails where it is made
+                    continue
+                raise
             f.restype = res
             f.argtypes = args
         _lib = l
@@ -1360,6 +1366,11 @@ class CmpSet:
     @property
     def operand_bytes(self):
         return int(lib().d2g_cmp_set_operand_bytes(self._h))
+
+    @property
+    def id_bits(self):
+        """width of the set's per-column id words: 16 or 32 (0: the set keeps no ids)"""
+        return int(lib().d2g_cmp_set_id_bits(self._h))
 
     def close(self):
         if getattr(self, "_h", None):

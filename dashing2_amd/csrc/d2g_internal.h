@@ -93,6 +93,7 @@ struct d2g_k2_tuning {
     size_t list_div = 8;                // D2G_SP_LIST_DIV: the pair list holds at most pairs / list_div entries (and at most 2^27)
     bool sort = true;                   // D2G_BS_SORT: 0 = keep the caller's column order (A/B measurements, tests)
     int tagbits_max = 31;               // D2G_BS_TAGBITS: 0 .. 30 (tests); unset or out of range: 31
+    int id16 = 1;                       // D2G_BS_ID16: 0 = 32-bit column ids in every set (1: 16-bit ids where the rank kernel is single-partition, N <= 21 845; A/B measurements, tests)
     int nsplit_req = 0;                 // D2G_BS_NSPLIT: 1, 2 or 4 rank workgroups per column where the hash space has that many partitions (tests / experiments); 0 = automatic
 };
 d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)

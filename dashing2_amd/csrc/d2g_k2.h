@@ -175,6 +175,8 @@ struct d2g_cmp_set {
     uint32_t *d_meta = nullptr;   // [tb] = max over the group's columns of (#values occurring >= 2 times) + 1 (device side; the kernels
                                   //       derive the live plane count from it, no host round trip)
     d2g_dev<uint32_t> d_ids;      // workspace: [S][Npad] dense ids (engine-managed gathered operands: allocated with d_colcnt for the sparse path, ids re-derived from the planes)
+    int id_bits = 32;             // width of a word of d_ids: 16 where the set's rank kernel is single-partition (N <= 21 845) and D2G_BS_ID16 is on -- 0 = padding,
+                                  // 0x8000 = unique, 1 .. 0x7FFF = rank -- 32 otherwise (MULTI / split ranks, ids unpacked from planes); d_ids then holds half as many words
     uint32_t T = 0; int logT = 0; // hash space of the rank kernel (power of two >= 1.5 N)
     bool borrowed = false;        // planes/meta are the caller's (d2g_cmp_set_from_planes_dev): never re-prepared, status from status_words
     bool want_exchange = false;   // d_planes is kept up to date by every prepare (set by the first export)

@@ -206,6 +206,8 @@ void d2g_cmp_set_destroy(d2g_cmp_set *set) {
 
 int d2g_cmp_set_algo(const d2g_cmp_set *set) { return set ? set->algo : D2G_ERR_INVALID; }
 
+int d2g_cmp_set_id_bits(const d2g_cmp_set *set) { return (set && set->algo == D2G_CMP_BITSLICE && set->d_ids) ? set->id_bits : 0; }
+
 size_t d2g_cmp_set_operand_bytes(const d2g_cmp_set *set) {
     if (!set) return 0;
     return (set->d_rows.cap() + set->d_cols.cap()) * sizeof(uint64_t) +

@@ -41,6 +41,16 @@ constexpr uint32_t BS_DUP = 0x80000000u;       // owner-table flag: the value ha
 constexpr uint32_t BS_UNIQ = 0x80000000u;      // id flag: value occurs once in its column (never equal)
 constexpr uint32_t BS_PENDING = 0x40000000u;   // multi-partition rank kernel: ids[] holds a table slot of the current pass
 constexpr int BS_LOG_TLDS_MAX = 15;            // LDS owner table: at most 32768 slots = 128 KiB
+// The width of an id word is a property of the SET (d2g_cmp_set::id_bits).  A set ranked by a single-partition kernel (N <= 21 845: FAST or general) holds, per
+// (column, sketch), 0 = padding, the unique flag, or a plain rank 1 .. D2 with D2 <= N / 2 <= 10 922: 16 bits carry that -- 0x8000 = unique, 1 .. 0x7FFF = rank --
+// and every pass over ids[] moves half the bytes (D2G_BS_ID16=0: 32-bit words everywhere).  BS_PENDING and the split tag of bits 28-29 exist in the MULTI
+// kernel only; MULTI, split and unpacked (sp_unpack_kernel) sets keep 32-bit words.  Every kernel that touches ids takes the word type as a template parameter.
+template <typename IdT> struct BsId;
+template <> struct BsId<uint32_t> { static constexpr uint32_t UNIQ = BS_UNIQ; static constexpr int UBIT = 31; };
+template <> struct BsId<uint16_t> { static constexpr uint32_t UNIQ = 0x8000u; static constexpr int UBIT = 15; };
+constexpr size_t BS_ID16_MAX_N = ((size_t(1) << BS_LOG_TLDS_MAX) * 2) / 3;      // = 21 845: the largest N whose hash space (>= 1.5 N slots) is one LDS table
+static_assert(BS_ID16_MAX_N / 2 < BsId<uint16_t>::UNIQ, "16-bit ids: the highest rank (N / 2) must stay below the unique flag");
+static_assert((size_t(1) << BS_LOG_TLDS_MAX) - 1 <= 0xFFFFu, "16-bit ids: the general single-partition kernel parks a table slot in ids[] between its two loops");
 
 __device__ __forceinline__ uint32_t bs_hash(uint64_t v, int logT) {
     // Fibonacci hashing: the top logT bits of the product (partition = top bits, slot = low bits of those)
@@ -87,9 +97,9 @@ __device__ unsigned long long g_rank_trace[8192 * 16];
 #else
 #define RK_STAMP(k) do { } while (0)
 #endif
-template <bool MULTI, bool FAST>
+template <bool MULTI, bool FAST, typename IdT = uint32_t>
 __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t *__restrict__ cols, size_t N, size_t Npad,
-                                                                  uint32_t T, int logT, uint32_t *ids_all, uint32_t *colcnt,
+                                                                  uint32_t T, int logT, void *ids_void, uint32_t *colcnt,
                                                                   uint32_t *status, int tagbits_max, uint32_t S, int nsplit,
                                                                   uint32_t *__restrict__ owner_all, size_t ostride) {
     extern __shared__ __attribute__((aligned(16))) uint32_t own[];        // Tl owner slots
@@ -97,7 +107,8 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
     const size_t t = MULTI ? blockIdx.x - split * S : blockIdx.x;
     const uint32_t htag = (MULTI && nsplit > 1) ? split << BS_SPLIT_SHIFT : 0u;
     const uint64_t *col = cols + t * Npad;
-    uint32_t *ids = ids_all + t * Npad;
+    static_assert(!MULTI || sizeof(IdT) == 4, "bs_rank_kernel: the pending words and split tags of the MULTI kernel need 32-bit ids");
+    IdT *ids = static_cast<IdT *>(ids_void) + t * Npad;
     const int tid = threadIdx.x;
     const int logTl = logT < BS_LOG_TLDS_MAX ? logT : BS_LOG_TLDS_MAX;
     const uint32_t Tl = 1u << logTl, mask = Tl - 1, nparts = MULTI ? (T >> logTl) : 1u;
@@ -141,7 +152,7 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
             const uint32_t cur = own[h];
             if (cur != BS_EMPTY) {
                 if ((cur & BS_DUP) && owner) owner[r - 1] = cur & ownmask;
-                own[h] = (cur & BS_DUP) ? (r++ | htag) : BS_UNIQ;
+                own[h] = (cur & BS_DUP) ? (r++ | htag) : BsId<IdT>::UNIQ;
             }
         }
         __syncthreads();
@@ -270,13 +281,13 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
 #pragma unroll
         for (int i = 0; i < PF; ++i) {
             const size_t j = (size_t)i * BS_RANK_THREADS + tid;
-            if (j < N && !(skip >> i & 1)) ids[j] = own[hs[i]];
+            if (j < N && !(skip >> i & 1)) ids[j] = (IdT)own[hs[i]];      // (16-bit ids: a wave still writes 64 consecutive words -- lane = sketch, packing two would cost a cross-lane move per value)
         }
 #ifdef D2G_RANK_TRACE
         __syncthreads();
         RK_STAMP(5);
 #endif
-        for (uint32_t k = tid; k < nfix && k < BS_MAXFIX; k += BS_RANK_THREADS) ids[fix_j[k]] = own[fix_h[k]];
+        for (uint32_t k = tid; k < nfix && k < BS_MAXFIX; k += BS_RANK_THREADS) ids[fix_j[k]] = (IdT)own[fix_h[k]];
         if (tid == 0) { colcnt[t * BS_CC_STRIDE] = running - 1; colcnt[t * BS_CC_STRIDE + 5] = running - 1; }   // #values shared by >= 2 sketches ([5]: a copy the column plan leaves alone -- sp_sample_fin_kernel reads it beside that kernel)
         return;
     }
@@ -352,7 +363,7 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
 #pragma unroll
             for (int i = 0; i < PG; ++i) {
                 const size_t j = j0 + (size_t)i * BS_RANK_THREADS + tid;
-                if ((mineb & ~redo) >> i & 1) ids[j] = hs[i] | (MULTI ? ptag : 0u);
+                if ((mineb & ~redo) >> i & 1) ids[j] = (IdT)(hs[i] | (MULTI ? ptag : 0u));
                 else if (MULTI && !tagged && part == 0 && j < N && !(redo >> i & 1)) ids[j] = 0;
             }
             while (redo) {                                                // tag collisions: the exact chain from the home slot
@@ -360,7 +371,7 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
                 redo &= redo - 1;
                 const size_t j = j0 + (size_t)i * BS_RANK_THREADS + tid;
                 const uint64_t vv = col[j];
-                ids[j] = insert(vv, (uint32_t)j, bs_hash(vv, logT) & mask) | (MULTI ? ptag : 0u);
+                ids[j] = (IdT)(insert(vv, (uint32_t)j, bs_hash(vv, logT) & mask) | (MULTI ? ptag : 0u));
             }
             if (batch < 8) mine_all |= (unsigned long long)mineb << (8 * batch);
             ++batch;
@@ -381,7 +392,7 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
             for (int i = 0; i < PG; ++i) {
                 const size_t j = j0 + (size_t)i * BS_RANK_THREADS + tid;
                 if (j < N && (mb >> i & 1) && (mine_known || !MULTI || (tagged ? (sl[i] & ~0x7FFFu) == ptag : (sl[i] & BS_PENDING) != 0)))
-                    ids[j] = own[sl[i] & (tagged ? 0x7FFFu : ~BS_PENDING)];
+                    ids[j] = (IdT)own[sl[i] & (tagged ? 0x7FFFu : ~BS_PENDING)];
             }
         }
         __syncthreads();
@@ -598,16 +609,23 @@ __global__ __launch_bounds__(BS_PLAN_THREADS) void bs_colplan_kernel(BsPlanArgs 
 constexpr int BS_FORM_STREAM = 1, BS_FORM_EXCHANGE = 2;
 constexpr size_t BS_SLACK = 64;          // words behind position Npad of every plane (Nstride = Npad + BS_SLACK)
 struct BsPlanesArgs {
-    const uint32_t *ids; size_t N, Npad; uint32_t *planes, *stream; size_t Nstride; int nbits_cap; const uint32_t *meta; int forms;
+    const void *ids; size_t N, Npad; uint32_t *planes, *stream; size_t Nstride; int nbits_cap; const uint32_t *meta; int forms;
     const uint32_t *perm, *colcnt, *sperm;
 };
 BsPlanesArgs planes_args_of(const d2g_cmp_set *set, uint32_t *planes, int forms) {
-    return BsPlanesArgs{set->d_ids, set->N, set->Npad, planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms, set->d_perm, set->d_colcnt, nullptr};
+    return BsPlanesArgs{set->d_ids.get(), set->N, set->Npad, planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms, set->d_perm, set->d_colcnt, nullptr};
 }
 // the body of workgroup (bx, tb) of the grid ceil(Nstride / 256) x ntb: 256 threads (bs_planes_kernel; the merged planes launch, bs_planes_flatten_kernel)
-template <bool SPLIT>
+// (16-bit ids: one 2-byte load per lane and column, a wave reads 128 consecutive bytes.  Measured and dropped: TWO adjacent positions per thread -- one 32-bit
+// load holds both ids, the bit transpose runs on the packed words (bit b and bit b + 16), the two words of a plane leave as one 8-byte store; half the
+// workgroups and half the load instructions -- the planes launch of the merged schedule took 19.6 us instead of 17.5 at config 3 (32-bit ids: 18.4):
+// the same VALU work in half as many waves hides the loads worse.  profiles/k2_id16.txt)
+template <bool SPLIT, typename IdT = uint32_t>
 __device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx, size_t tb) {
-    const uint32_t *__restrict__ ids = a.ids, *__restrict__ meta = a.meta, *__restrict__ perm = a.perm, *__restrict__ colcnt = a.colcnt, *__restrict__ sperm = a.sperm;
+    static_assert(!SPLIT || sizeof(IdT) == 4, "bs_planes_body: split ranks are 32-bit ids");
+    constexpr int UBIT = BsId<IdT>::UBIT;
+    const IdT *__restrict__ ids = static_cast<const IdT *>(a.ids);
+    const uint32_t *__restrict__ meta = a.meta, *__restrict__ perm = a.perm, *__restrict__ colcnt = a.colcnt, *__restrict__ sperm = a.sperm;
     uint32_t *__restrict__ planes = a.planes, *__restrict__ stream = a.stream;
     const size_t N = a.N, Npad = a.Npad, Nstride = a.Nstride;
     const int nbits_cap = a.nbits_cap, forms = a.forms;
@@ -632,7 +650,7 @@ __device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx,
     }
     uint32_t u = 0;                                    // the "unique" plane
 #pragma unroll
-    for (int x = 0; x < 32; ++x) u |= (id[x] >> 31) << x;
+    for (int x = 0; x < 32; ++x) u |= (id[x] >> UBIT) << x;
     // forms: BS_FORM_STREAM = what this GPU's pair kernel walks; BS_FORM_EXCHANGE = what ranks exchange -- written only
     // once somebody has asked for it (d2g_bitslice_export: 29 MB of stores per prepare at config 3 that a single GPU never reads)
     uint32_t *dst = planes + tb * (size_t)(nbits_cap + 1) * Nstride + jpos;
@@ -657,8 +675,8 @@ __device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx,
         dst[(size_t)nbits_cap * Nstride] = uw;
     }
 }
-template <bool SPLIT>
-__global__ __launch_bounds__(256) void bs_planes_kernel(BsPlanesArgs a) { bs_planes_body<SPLIT>(a, blockIdx.x, blockIdx.y); }
+template <bool SPLIT, typename IdT = uint32_t>
+__global__ __launch_bounds__(256) void bs_planes_kernel(BsPlanesArgs a) { bs_planes_body<SPLIT, IdT>(a, blockIdx.x, blockIdx.y); }
 
 // plane stream of an operand that arrived in the exchanged form (the gathered operand of the multi-GPU path,
 // d2g_cmp_set_from_planes_dev)
@@ -928,8 +946,12 @@ int alloc_prepare_workspace(d2g_ctx *ctx, d2g_cmp_set *set) {
     }
     const char *what = "bitslice alloc";
     int rc;
-    if ((rc = set->d_ids.alloc(ctx, S * Npad, what)) ||
-        (rc = d2g_hip_status(ctx, hipMemset(set->d_ids, 0, S * Npad * sizeof(uint32_t)), what)) ||     // split rank passes rely on "no stale pending word"
+    // the ids of a set whose rank kernel is single-partition are 16-bit words (BsId): decided HERE, once per set, and every kernel that touches them follows
+    set->id_bits = (ctx->k2.id16 && set->logT <= BS_LOG_TLDS_MAX) ? 16 : 32;
+    D2G_CHECK(ctx, set->id_bits == 32 || (N <= BS_ID16_MAX_N && set->nsplit == 1), "bitslice: 16-bit ids need a single-partition rank kernel");
+    const size_t id_words = set->id_bits == 16 ? (S * Npad + 1) / 2 : S * Npad;
+    if ((rc = set->d_ids.alloc(ctx, id_words, what)) ||
+        (rc = d2g_hip_status(ctx, hipMemset(set->d_ids, 0, id_words * sizeof(uint32_t)), what)) ||     // split rank passes rely on "no stale pending word"; the link passes and emit on "the padding holds id 0"
         (rc = set->d_colcnt.alloc(ctx, S * BS_CC_STRIDE, what)) ||
         (rc = set->d_perm.alloc(ctx, (size_t)set->ntb * 32, what)) ||
         (rc = set->own_meta.alloc(ctx, (size_t)(set->ntb + 4), what)) ||
@@ -941,7 +963,8 @@ int alloc_prepare_workspace(d2g_ctx *ctx, d2g_cmp_set *set) {
 int launch_planes(d2g_ctx *ctx, const d2g_cmp_set *set, uint32_t *planes, int forms, hipStream_t s) {
     const dim3 grid((unsigned)div_up<size_t>(set->Nstride, 256), (unsigned)set->ntb);
     const bool split = set->logT > BS_LOG_TLDS_MAX && set->nsplit > 1;
-    hipLaunchKernelGGL(split ? bs_planes_kernel<true> : bs_planes_kernel<false>, grid, dim3(256), 0, s, planes_args_of(set, planes, forms));
+    D2G_CHECK(ctx, !(split && set->id_bits == 16), "bitslice: a split set with 16-bit ids");
+    hipLaunchKernelGGL((set->id_bits == 16 ? bs_planes_kernel<false, uint16_t> : split ? bs_planes_kernel<true> : bs_planes_kernel<false>), grid, dim3(256), 0, s, planes_args_of(set, planes, forms));
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
 }
@@ -1008,9 +1031,12 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     {
         const int logTl = set->logT < BS_LOG_TLDS_MAX ? set->logT : BS_LOG_TLDS_MAX;
         const size_t lds = (size_t(1) << logTl) * sizeof(uint32_t);
-        void (*kern)(const uint64_t *, size_t, size_t, uint32_t, int, uint32_t *, uint32_t *, uint32_t *, int, uint32_t, int, uint32_t *, size_t) = bs_rank_kernel<false, false>;
+        const bool id16 = set->id_bits == 16;
+        D2G_CHECK(ctx, !(multi && id16), "bitslice: the multi-partition rank kernel with 16-bit ids");
+        void (*kern)(const uint64_t *, size_t, size_t, uint32_t, int, void *, uint32_t *, uint32_t *, int, uint32_t, int, uint32_t *, size_t) = bs_rank_kernel<false, false>;
         if (multi) kern = bs_rank_kernel<true, false>;
-        else if (N <= (size_t)12 * BS_RANK_THREADS) kern = bs_rank_kernel<false, true>;     // PF * BS_RANK_THREADS
+        else if (N <= (size_t)12 * BS_RANK_THREADS) kern = id16 ? bs_rank_kernel<false, true, uint16_t> : bs_rank_kernel<false, true>;     // PF * BS_RANK_THREADS
+        else if (id16) kern = bs_rank_kernel<false, false, uint16_t>;
         if (lds > 48 * 1024)
             D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         // split passes tell their pending words from final ids by a tag and trust that ids[] holds nothing else that looks pending.  A
@@ -1018,7 +1044,7 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         // after step: ids[] starts from zero in every split prepare -- a few MB for the narrow column slices that are split
         if (nsplit > 1) D2G_HIP(ctx, hipMemsetAsync(set->d_ids, 0, S * Npad * sizeof(uint32_t), s));
         hipLaunchKernelGGL(kern, dim3((unsigned)(S * nsplit)), dim3(BS_RANK_THREADS), lds, s, set->d_cols, N, Npad, set->T, set->logT,
-                           set->d_ids, set->d_colcnt, set->d_meta + set->ntb, ctx->k2.tagbits_max, (uint32_t)S, nsplit,
+                           (void *)set->d_ids.get(), set->d_colcnt, set->d_meta + set->ntb, ctx->k2.tagbits_max, (uint32_t)S, nsplit,
                            (sp && nsplit == 1) ? sp->d_owner.get() : (uint32_t *)nullptr, sp ? sp->owner_stride : 0);
         if (sp) sp->dec.kernels = 2 + (join.ev ? 1 : 0);               // the transpose in front of this prepare, the rank kernel (, the side fill)
         // a set's first prepare looks at its matrix before it orders it: the sample needs the ids only, so it stands HERE and the two kernels
@@ -1279,8 +1305,8 @@ std::string d2g_k2_tuning_json(const d2g_ctx *ctx) {
     const d2g_k2_tuning &t = ctx->k2;
     char b[640];
     std::snprintf(b, sizeof b, "{\"D2G_BS_SPARSE\": %d, \"D2G_BS_SPARSE_MIN_N\": %zu, \"D2G_BS_SORT\": %d, \"D2G_SP_LINK\": %d, \"D2G_SP_OLINK\": %d, \"D2G_SP_TILE_FRAC\": %.3f, "
-                  "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d, \"D2G_K2_MERGE\": %d}",
-                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big, t.merge);
+                  "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d, \"D2G_K2_MERGE\": %d, \"D2G_BS_ID16\": %d}",
+                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big, t.merge, t.id16);
     return b;
 }
 

@@ -40,9 +40,12 @@ constexpr unsigned long long SP_NULL_ENTRY = ~0ull;   // an empty slot of the pa
 #define D2G_SP_WPE 8
 #endif
 
+// (IdT: the set's id word, BsId -- a 16-bit id is a plain rank, never a split one)
+template <typename IdT = uint32_t>
 __device__ __forceinline__ uint32_t sp_rank(uint32_t w, const uint32_t *__restrict__ colcnt, size_t t, bool split) {
-    if ((w >> 31) || w == 0) return 0;          // unique (or padding): never equal to anything
-    return split ? (w & BS_RANK_MASK) + colcnt[t * BS_CC_STRIDE + (w >> BS_SPLIT_SHIFT)] : w;
+    if ((w >> BsId<IdT>::UBIT) || w == 0) return 0;          // unique (or padding): never equal to anything
+    if constexpr (sizeof(IdT) == 2) return w;
+    else return split ? (w & BS_RANK_MASK) + colcnt[t * BS_CC_STRIDE + (w >> BS_SPLIT_SHIFT)] : w;
 }
 
 __device__ __forceinline__ uint32_t sp_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -83,10 +86,11 @@ __device__ __forceinline__ bool sp_union(uint32_t *label, uint32_t a, uint32_t b
 //            roots (every matcher doing so cost 40 us; a quarter of the column pairs still sees every family dozens of times).
 // Values beyond the table (nv = min(D2, cap)) take no part: the partition is a heuristic, sp_emit_kernel keeps the result exact.
 constexpr uint32_t SP_UDONE = 0x40000000u, SP_R2MASK = 0x3FFFFFFFu;   // r2[]: bit 30 = one of the value's matchers has run the union (ranks stay below 2^29: N < 2^30)
-template <int MODE>
-__global__ __launch_bounds__(1024) void sp_link_kernel(const uint32_t *__restrict__ ids, size_t N, size_t Npad, uint32_t ncols, const uint32_t *__restrict__ colcnt,
+template <int MODE, typename IdT = uint32_t>
+__global__ __launch_bounds__(1024) void sp_link_kernel(const void *__restrict__ ids_void, size_t N, size_t Npad, uint32_t ncols, const uint32_t *__restrict__ colcnt,
                                                        int split, uint32_t cap, uint32_t stride, uint32_t *label, uint32_t *__restrict__ hint) {
     extern __shared__ uint32_t sp_l[];
+    const IdT *__restrict__ ids = static_cast<const IdT *>(ids_void);
     const size_t pair = (size_t)blockIdx.x * stride;
     const size_t t1 = 2 * pair, t2 = t1 + 1;
     if (t2 >= ncols) return;
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(1024) void sp_link_kernel(const uint32_t *__restric
 #pragma unroll
         for (int x = 0; x < U; ++x) {
             const uint32_t j = (uint32_t)(j0 + (size_t)x * T + threadIdx.x);
-            const uint32_t a = sp_rank(w1[x], colcnt, t1, split != 0), b = sp_rank(w2[x], colcnt, t2, split != 0);
+            const uint32_t a = sp_rank<IdT>(w1[x], colcnt, t1, split != 0), b = sp_rank<IdT>(w2[x], colcnt, t2, split != 0);
             if (!a || a > nv) continue;
             if (MODE == 0) any[a - 1] = j;                            // (a plain LDS store: the lanes of a wave that share the value write once; a minimum cost 13 us)
             if (!b) continue;
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(1024) void sp_link_kernel(const uint32_t *__restric
 #pragma unroll
         for (int x = 0; x < U; ++x) {
             const uint32_t j = (uint32_t)(j0 + (size_t)x * T + threadIdx.x);
-            const uint32_t a = sp_rank(w1[x], colcnt, t1, split != 0), b = sp_rank(w2[x], colcnt, t2, split != 0);
+            const uint32_t a = sp_rank<IdT>(w1[x], colcnt, t1, split != 0), b = sp_rank<IdT>(w2[x], colcnt, t2, split != 0);
             if (!a || a > nv) continue;
             const uint32_t rr = r2[a - 1];
             const bool match = b && rr != SP_NONE && (rr & SP_R2MASK) == b;
@@ -161,41 +165,48 @@ __global__ __launch_bounds__(1024) void sp_link_kernel(const uint32_t *__restric
 // that find no link take the owner as their hint and are attached afterwards.  MODE 1: the first matcher of a value whose label differs from the
 // owner's (bit 31 of the owner word, set with one atomic) unites the two trees.
 constexpr uint32_t SP_OWNER_MASK = 0x7FFFFFFFu;
-struct SpOlinkArgs { const uint32_t *ids; size_t N, Npad; uint32_t ncols; uint32_t *owner; size_t ostride; uint32_t stride; uint32_t *label, *hint; };
+struct SpOlinkArgs { const void *ids; size_t N, Npad; uint32_t ncols; uint32_t *owner; size_t ostride; uint32_t stride; uint32_t *label, *hint; };
+// Four sketches per thread at either id width: one 16-byte load per column of 32-bit ids, one 8-byte load of 16-bit ones.
+// (Measured and dropped: EIGHT sketches per thread from one 16-byte load of 16-bit ids -- half the waves, twice the gathers in flight per thread, 54 VGPRs instead
+// of 32: the merged link launch took 23.0 us instead of 20.3 at config 3 (32-bit ids: 21.4), the uniting pass 8.0 instead of 6.4 (7.5).  profiles/k2_id16.txt)
+constexpr int SP_OLINK_W = 4;
 // the body of workgroup (bx, by) of the grid ceil(N / 1024) x column pairs: 256 threads (sp_olink_kernel; MODE 0 also in the merged link launch, sp_link0_plan_kernel)
-template <int MODE>
+template <int MODE, typename IdT = uint32_t>
 __device__ __forceinline__ void sp_olink_body(const SpOlinkArgs &a, size_t bx, size_t by) {
-    const uint32_t *__restrict__ ids = a.ids;
+    constexpr int W = SP_OLINK_W, UBIT = BsId<IdT>::UBIT;
+    const IdT *__restrict__ ids = static_cast<const IdT *>(a.ids);
     uint32_t *__restrict__ owner = a.owner, *label = a.label, *__restrict__ hint = a.hint;
     const size_t N = a.N, Npad = a.Npad, ostride = a.ostride;
     const size_t pair = by * a.stride;
     const size_t t1 = 2 * pair, t2 = t1 + 1;
     if (t2 >= a.ncols) return;
-    const size_t j0 = (bx * 256 + threadIdx.x) * 4;
+    const size_t j0 = (bx * 256 + threadIdx.x) * W;
     if (j0 >= N) return;
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 w1 = *reinterpret_cast<const u32x4 *>(ids + t1 * Npad + j0);       // (Npad is a multiple of 256: aligned; the padding holds id 0)
-    const u32x4 w2 = *reinterpret_cast<const u32x4 *>(ids + t2 * Npad + j0);
-    const u32x4 lb = *reinterpret_cast<const u32x4 *>(label + j0);                  // plain loads: a stale label is still an earlier member of the family
+    // (Npad is a multiple of 256 and j0 of W: the W words lie inside the column, aligned to their own size; the padding holds id 0)
+    IdT w1[W], w2[W];
+    uint32_t lb[W];
+    __builtin_memcpy(w1, __builtin_assume_aligned(ids + t1 * Npad + j0, W * sizeof(IdT)), sizeof w1);
+    __builtin_memcpy(w2, __builtin_assume_aligned(ids + t2 * Npad + j0, W * sizeof(IdT)), sizeof w2);
+    __builtin_memcpy(lb, __builtin_assume_aligned(label + j0, 16), sizeof lb);                  // plain loads: a stale label is still an earlier member of the family
     uint32_t *myhint = hint + (size_t)(pair & 1u) * Npad;
-    uint32_t o[4], r2o[4], lo[4];
+    uint32_t o[W], r2o[W], lo[W];
 #pragma unroll
-    for (int x = 0; x < 4; ++x) {
+    for (int x = 0; x < W; ++x) {
         const uint32_t r1 = w1[x];
-        o[x] = (r1 && !(r1 >> 31) && j0 + x < N) ? owner[t1 * ostride + r1 - 1] & SP_OWNER_MASK : SP_NONE;
+        o[x] = (r1 && !(r1 >> UBIT) && j0 + x < N) ? owner[t1 * ostride + r1 - 1] & SP_OWNER_MASK : SP_NONE;
     }
 #pragma unroll
-    for (int x = 0; x < 4; ++x) {
+    for (int x = 0; x < W; ++x) {
         const bool live = o[x] != SP_NONE && o[x] != (uint32_t)(j0 + x);
-        r2o[x] = live ? ids[t2 * Npad + o[x]] : 0u;
+        r2o[x] = live ? (uint32_t)ids[t2 * Npad + o[x]] : 0u;
         lo[x] = live ? label[o[x]] : 0u;
         if (!live) o[x] = SP_NONE;
     }
 #pragma unroll
-    for (int x = 0; x < 4; ++x) {
+    for (int x = 0; x < W; ++x) {
         if (o[x] == SP_NONE) continue;
         const uint32_t j = (uint32_t)(j0 + x), r2 = w2[x];
-        const bool match = r2 && !(r2 >> 31) && r2 == r2o[x];
+        const bool match = r2 && !(r2 >> UBIT) && r2 == r2o[x];
         if (MODE == 0) {
             if (match) {
                 if (lo[x] < lb[x]) label[j] = lo[x]; else if (lb[x] < lo[x]) label[o[x]] = lb[x];
@@ -206,8 +217,8 @@ __device__ __forceinline__ void sp_olink_body(const SpOlinkArgs &a, size_t bx, s
         }
     }
 }
-template <int MODE>
-__global__ __launch_bounds__(256) void sp_olink_kernel(SpOlinkArgs a) { sp_olink_body<MODE>(a, blockIdx.x, blockIdx.y); }
+template <int MODE, typename IdT = uint32_t>
+__global__ __launch_bounds__(256) void sp_olink_kernel(SpOlinkArgs a) { sp_olink_body<MODE, IdT>(a, blockIdx.x, blockIdx.y); }
 
 // every label straight at its root (the walk halves the path behind it; plain loads and stores: a label is only ever replaced by an
 // ancestor, so racing with itself is harmless).  Between the two link passes: the uniting pass compares LABELS, and two members of a
@@ -245,18 +256,20 @@ __global__ __launch_bounds__(256) void sp_flatten_kernel(uint32_t *label, size_t
 // (Measured, profiles/k2_merged_prepare.txt: the planes workgroups beside link pass 1, beside the scan's one workgroup, and handed out in shares to flatten /
 // count / attach / place like the fill's riders -- the step takes the same time within 2 us: the planes body moves 60 MB itself and every host already
 // carries a share of the fill, so it costs ~13 us of chain time wherever it stands.  The plan and flatten, a few workgroups each, do disappear.)
+template <typename IdT = uint32_t>
 __global__ __launch_bounds__(256) void sp_link0_plan_kernel(BsPlanArgs pa, SpOlinkArgs la, uint32_t nx, SpRider rider) {
     SP_RIDE_OR_WORK(rider);
     extern __shared__ __attribute__((aligned(16))) uint32_t plan_lds[];
     if (blockIdx.x == 0) { bs_colplan_body<256>(pa, bs_plan_lds(plan_lds, (uint32_t)pa.ntb * 32u)); return; }
     const uint32_t b = blockIdx.x - 1u;                                 // (nx = 0: no link pass, the grid ends here)
-    sp_olink_body<0>(la, b % nx, b / nx);
+    sp_olink_body<0, IdT>(la, b % nx, b / nx);
 }
+template <typename IdT = uint32_t>
 __global__ __launch_bounds__(256) void bs_planes_flatten_kernel(BsPlanesArgs a, uint32_t gx, uint32_t nflat, uint32_t *label, SpRider rider) {
     SP_RIDE_OR_WORK(rider);
     if (blockIdx.x < nflat) { sp_flatten_body(label, a.N, blockIdx.x); return; }
     const uint32_t b = blockIdx.x - nflat;
-    bs_planes_body<false>(a, b % gx, b / gx);
+    bs_planes_body<false, IdT>(a, b % gx, b / gx);
 }
 
 // Behind the count kernel (the roots are final, root[] and cnt[] say who is alone): a sketch ALONE under its root joins the family its hints
@@ -497,7 +510,8 @@ __device__ unsigned long long g_emit_trace[4096 * 16];
 // 32 768 of them -- every column below 65 536 sketches is ONE step, pass A + pass B
 // (1024 threads and 2560 values per step -- every column of config 3 ONE step, two workgroups per CU -- was measured: 35 us against 24 clean, 108 against 78 at c = 10)
 constexpr uint32_t SP_EMIT_VCAP = 1536, SP_EMIT_ECAP = 32768, SP_EMIT_T = D2G_SP_EMIT_T;
-__global__ __launch_bounds__(SP_EMIT_T) __attribute__((amdgpu_waves_per_eu(8, 8))) void sp_emit_kernel(const uint32_t *__restrict__ ids, size_t N, size_t Npad, uint32_t ncols, const uint32_t *__restrict__ colcnt, int split,
+template <typename IdT = uint32_t>
+__global__ __launch_bounds__(SP_EMIT_T) __attribute__((amdgpu_waves_per_eu(8, 8))) void sp_emit_kernel(const void *__restrict__ ids_void, size_t N, size_t Npad, uint32_t ncols, const uint32_t *__restrict__ colcnt, int split,
                                                             const uint32_t *__restrict__ seg, uint32_t *__restrict__ order,
                                                             SpColWork cw, uint32_t *__restrict__ plctl, uint32_t plcap, uint32_t *__restrict__ gaveup, int big) {
     __shared__ uint32_t first[SP_EMIT_VCAP];
@@ -517,9 +531,34 @@ __global__ __launch_bounds__(SP_EMIT_T) __attribute__((amdgpu_waves_per_eu(8, 8)
     // fn(rank, segment, sketch) for every sketch of the column that holds a shared value
     // (keeping a thread's 20 (rank, segment) pairs packed in registers instead of re-reading the column in the second pass was measured at
     // N = 10 000: 89 VGPRs, two workgroups per CU instead of four, 37.9 vs 35.6 us)
-    const uint32_t *__restrict__ col = ids + t * Npad;                 // (uniform base + 32-bit lane offset: N < 2^30)
+    const IdT *__restrict__ col = static_cast<const IdT *>(ids_void) + t * Npad;                 // (uniform base + 32-bit lane offset: N < 2^30)
     const uint32_t n32 = (uint32_t)N;
     auto for_each_holder = [&](auto &&fn) {
+        if constexpr (sizeof(IdT) == 2) {
+            // 16-bit ids: a thread takes PAIRS of adjacent sketches -- one 32-bit load for the two ids, one 8-byte load for their segments; still eight sketches per
+            // thread and round.  (j even, j < N <= Npad even: both words lie inside the column / seg[]; the id of position N of an odd N is padding, 0: no holder)
+            // (one 2-byte id and one segment per lane, as for 32-bit ids, was measured: 20.0 us instead of 19.2 at config 3; 32-bit ids: 21.9.  profiles/k2_id16.txt)
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+#pragma unroll 1
+            for (uint32_t j0 = 0; j0 < n32; j0 += T * 8) {
+                uint32_t w[4];
+                u32x2 sg[4];
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    const uint32_t j = j0 + 2u * ((uint32_t)x * T + tid);
+                    w[x] = j < n32 ? *reinterpret_cast<const uint32_t *>(col + j) : 0u;
+                    sg[x] = j < n32 ? *reinterpret_cast<const u32x2 *>(seg + j) : u32x2{0u, 0u};
+                }
+#pragma unroll
+                for (int x = 0; x < 4; ++x) {
+                    const uint32_t j = j0 + 2u * ((uint32_t)x * T + tid);
+                    const uint32_t ra = sp_rank<IdT>(w[x] & 0xFFFFu, colcnt, t, false), rb = sp_rank<IdT>(w[x] >> 16, colcnt, t, false);
+                    if (ra) fn(ra, sg[x].x, j);
+                    if (rb) fn(rb, sg[x].y, j + 1u);
+                }
+            }
+            return;
+        }
 #pragma unroll 1
         for (uint32_t j0 = 0; j0 < n32; j0 += T * 8) {
             uint32_t w[8], sg[8];
@@ -530,7 +569,7 @@ __global__ __launch_bounds__(SP_EMIT_T) __attribute__((amdgpu_waves_per_eu(8, 8)
                 sg[x] = j < n32 ? seg[j] : 0u;
             }
 #pragma unroll
-            for (int x = 0; x < 8; ++x) { const uint32_t r = sp_rank(w[x], colcnt, t, split != 0); if (r) fn(r, sg[x], j0 + (uint32_t)x * T + tid); }
+            for (int x = 0; x < 8; ++x) { const uint32_t r = sp_rank<IdT>(w[x], colcnt, t, split != 0); if (r) fn(r, sg[x], j0 + (uint32_t)x * T + tid); }
         }
     };
     const uint32_t vcap = big ? SP_EMIT_VCAP / 2 : SP_EMIT_VCAP;
@@ -1501,16 +1540,17 @@ struct SpSampleRows { uint32_t r[SP_SAMPLE_ROWS]; };
 // a (sample, sketch) count is the sum over the 32-column groups of min(equal registers in the group, SP_SAMPLE_FAM): below 256 up to 63 groups
 // (S <= 2016), a byte per sample, four samples per word; more groups take 16-bit fields, two per word (2048 groups x 4 = 8192 at S = 65535)
 inline uint32_t sp_sample_field_bits(size_t ncols) { return div_up<size_t>(ncols, SP_SAMPLE_COLS) * SP_SAMPLE_FAM < 256 ? 8u : 16u; }
-template <uint32_t FB>
-__global__ __launch_bounds__(256) void sp_sample_kernel(const uint32_t *__restrict__ ids, size_t N, size_t Npad, uint32_t ncols, SpSampleRows rows, uint32_t *__restrict__ cntm) {
+template <uint32_t FB, typename IdT = uint32_t>
+__global__ __launch_bounds__(256) void sp_sample_kernel(const void *__restrict__ ids_void, size_t N, size_t Npad, uint32_t ncols, SpSampleRows rows, uint32_t *__restrict__ cntm) {
     constexpr uint32_t PW = 32 / FB;                                  // samples per count word
     __shared__ __attribute__((aligned(16))) uint32_t sm[SP_SAMPLE_COLS][SP_SAMPLE_ROWS];   // the sampled sketches' ids in this workgroup's columns
+    const IdT *__restrict__ ids = static_cast<const IdT *>(ids_void);
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t t0 = blockIdx.y * SP_SAMPLE_COLS, t1 = min(ncols, t0 + SP_SAMPLE_COLS);
     for (uint32_t x = threadIdx.x; x < SP_SAMPLE_COLS * SP_SAMPLE_ROWS; x += 256) {
         const uint32_t t = t0 + x / SP_SAMPLE_ROWS, k = x % SP_SAMPLE_ROWS;
         const uint32_t w = t < t1 ? ids[(size_t)t * Npad + rows.r[k]] : 0u;
-        sm[x / SP_SAMPLE_ROWS][k] = (w != 0 && !(w >> 31)) ? w : 0xFFFFFFFFu;      // (a value nobody else holds matches nothing: never equal to a shared id)
+        sm[x / SP_SAMPLE_ROWS][k] = (w != 0 && !(w >> BsId<IdT>::UBIT)) ? w : 0xFFFFFFFFu;      // (a value nobody else holds matches nothing: never equal to a shared id)
     }
     __syncthreads();
     uint32_t acc[SP_SAMPLE_ROWS];
@@ -1519,7 +1559,7 @@ __global__ __launch_bounds__(256) void sp_sample_kernel(const uint32_t *__restri
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll 4
     for (uint32_t x = 0; x < SP_SAMPLE_COLS; ++x) {
-        const uint32_t wx = (j < N && t0 + x < t1) ? ids[(size_t)(t0 + x) * Npad + j] : 0u;      // (0 or bit 31: equal to no staged id)
+        const uint32_t wx = (j < N && t0 + x < t1) ? ids[(size_t)(t0 + x) * Npad + j] : 0u;      // (0 or the unique flag: equal to no staged id)
 #pragma unroll
         for (uint32_t q = 0; q < SP_SAMPLE_ROWS / 4; ++q) {
             const u32x4 s4 = reinterpret_cast<const u32x4 *>(&sm[x][0])[q];
@@ -1640,7 +1680,8 @@ int sp_sample_enqueue(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
 #endif
     const bool wide = sp_sample_field_bits(set->ncols) == 16;           // (d_samp holds SP_SAMPLE_ROWS words per sketch: 16-bit fields fill all of them)
     const dim3 sgrid((unsigned)div_up<size_t>(N, 256), (unsigned)div_up<size_t>(set->ncols, SP_SAMPLE_COLS)), fgrid((unsigned)div_up<size_t>(std::max(N, set->ncols), 256));
-    hipLaunchKernelGGL(wide ? sp_sample_kernel<16> : sp_sample_kernel<8>, sgrid, dim3(256), 0, s, set->d_ids, N, Npad, (uint32_t)set->ncols, rows, sp.d_samp);
+    const bool id16 = set->id_bits == 16;
+    hipLaunchKernelGGL((wide ? (id16 ? sp_sample_kernel<16, uint16_t> : sp_sample_kernel<16>) : (id16 ? sp_sample_kernel<8, uint16_t> : sp_sample_kernel<8>)), sgrid, dim3(256), 0, s, (const void *)set->d_ids.get(), N, Npad, (uint32_t)set->ncols, rows, sp.d_samp);
     hipLaunchKernelGGL(wide ? sp_sample_fin_kernel<16> : sp_sample_fin_kernel<8>, fgrid, dim3(256), 0, s, sp.d_samp, N, Npad, rows, acc3, sp.d_gaveup + SP_MW_SUMS,
                        set->d_colcnt, (uint32_t)set->ncols, set->nsplit, ++sp.dec.sample_ticket);
     D2G_HIP(ctx, hipGetLastError());
@@ -1689,13 +1730,14 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
 int sp_launch_merged(d2g_ctx *ctx, d2g_cmp_set *set, const SpOlinkArgs *l0, unsigned nx, unsigned npair, unsigned nflat, hipStream_t s) {
     SpState &sp = *set->sp;
     const BsPlanArgs pa{set->d_colcnt, (uint32_t)set->S, set->ntb, 1, set->d_perm, set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, ctx->k2.sort ? 1 : 0};
+    const bool id16 = set->id_bits == 16;
     const size_t nlink = (size_t)nx * npair, gx = div_up<size_t>(set->Nstride, 256), nplanes = gx * (size_t)set->ntb;
     D2G_CHECK(ctx, 1 + nlink < 0x40000000u && nflat + nplanes < 0x40000000u, "bitslice sparse: a merged launch does not fit a grid");
     unsigned g;
     SpRider rd = sp.announced.take((unsigned)(1 + nlink), SP_RW_M_LINK0, false, 1, &g);
-    hipLaunchKernelGGL(sp_link0_plan_kernel, dim3(g), dim3(256), bs_plan_lds_words((uint32_t)set->ntb * 32u, pa.sort) * 4, s, pa, l0 ? *l0 : SpOlinkArgs{}, (uint32_t)nx, rd);
+    hipLaunchKernelGGL((id16 ? sp_link0_plan_kernel<uint16_t> : sp_link0_plan_kernel<uint32_t>), dim3(g), dim3(256), bs_plan_lds_words((uint32_t)set->ntb * 32u, pa.sort) * 4, s, pa, l0 ? *l0 : SpOlinkArgs{}, (uint32_t)nx, rd);
     rd = sp.announced.take((unsigned)(nflat + nplanes), SP_RW_M_PLANES, false, 2, &g);
-    hipLaunchKernelGGL(bs_planes_flatten_kernel, dim3(g), dim3(256), 0, s, planes_args_of(set, set->d_planes, BS_FORM_STREAM), (uint32_t)gx, (uint32_t)nflat, sp.d_label.get(), rd);
+    hipLaunchKernelGGL((id16 ? bs_planes_flatten_kernel<uint16_t> : bs_planes_flatten_kernel<uint32_t>), dim3(g), dim3(256), 0, s, planes_args_of(set, set->d_planes, BS_FORM_STREAM), (uint32_t)gx, (uint32_t)nflat, sp.d_label.get(), rd);
     sp.dec.kernels += 2;
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
@@ -1731,28 +1773,32 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
     const unsigned nb = (unsigned)div_up<size_t>(N, 256);
     uint32_t *la = sp.d_label, *lb = sp.d_label + Npad;
     const d2g_k2_tuning &tu = ctx->k2;
+    const bool id16 = set->id_bits == 16;
+    const void *const ids = set->d_ids.get();
+    D2G_CHECK(ctx, !(id16 && split), "bitslice sparse: split ranks in 16-bit ids");
     if (tu.link && S >= 2) {
         const uint32_t cap = (uint32_t)std::min<size_t>(N / 2 + 1, 12288);              // shared values of a column that take part: 3 words each, 144 KB of LDS at most
-        D2G_HIP(ctx, hipFuncSetAttribute((const void *)sp_link_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 12));
-        D2G_HIP(ctx, hipFuncSetAttribute((const void *)sp_link_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 8));
+        const auto link0 = id16 ? sp_link_kernel<0, uint16_t> : sp_link_kernel<0, uint32_t>, link1 = id16 ? sp_link_kernel<1, uint16_t> : sp_link_kernel<1, uint32_t>;
+        D2G_HIP(ctx, hipFuncSetAttribute((const void *)link0, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 12));
+        D2G_HIP(ctx, hipFuncSetAttribute((const void *)link1, hipFuncAttributeMaxDynamicSharedMemorySize, 12288 * 8));
         const unsigned npair = (unsigned)(S / 2);
         const uint32_t ustride = (uint32_t)std::max<size_t>(1, std::min<size_t>(SP_UNITE_STRIDE, npair / 32));   // at least 32 column pairs take part in the uniting pass
         if (sp.d_owner && !split && tu.olink) {                        // one holder per shared value at hand: the streaming form
-            const unsigned nx = (unsigned)div_up<size_t>(N, 1024);
-            const SpOlinkArgs l0{set->d_ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, 1u, la, sp.d_hint};
+            const unsigned nx = (unsigned)div_up<size_t>(N, 256 * (size_t)SP_OLINK_W);
+            const SpOlinkArgs l0{ids, N, Npad, (uint32_t)S, sp.d_owner, sp.owner_stride, 1u, la, sp.d_hint};
             SpOlinkArgs l1 = l0; l1.stride = ustride;
             if (!sp.dec.merged) {
-                hipLaunchKernelGGL(sp_olink_kernel<0>, dim3(nx, npair), dim3(256), 0, s, l0);
+                hipLaunchKernelGGL((id16 ? sp_olink_kernel<0, uint16_t> : sp_olink_kernel<0, uint32_t>), dim3(nx, npair), dim3(256), 0, s, l0);
                 { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
                 sp.dec.kernels += 2;
             } else if (int rc = sp_launch_merged(ctx, set, &l0, nx, npair, nb, s)) return rc;
-            hipLaunchKernelGGL(sp_olink_kernel<1>, dim3(nx, div_up<unsigned>(npair, ustride)), dim3(256), 0, s, l1);
+            hipLaunchKernelGGL((id16 ? sp_olink_kernel<1, uint16_t> : sp_olink_kernel<1, uint32_t>), dim3(nx, div_up<unsigned>(npair, ustride)), dim3(256), 0, s, l1);
             sp.dec.kernels += 1;
         } else {
-            hipLaunchKernelGGL(sp_link_kernel<0>, dim3(npair), dim3(1024), (size_t)cap * 12, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, 1u,
+            hipLaunchKernelGGL(link0, dim3(npair), dim3(1024), (size_t)cap * 12, s, ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, 1u,
                                la, sp.d_hint);
             { unsigned g; const SpRider rd = sp.announced.take(nb, SP_RW_FLATTEN, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, la, N, rd); }
-            hipLaunchKernelGGL(sp_link_kernel<1>, dim3(div_up<unsigned>(npair, ustride)), dim3(1024), (size_t)cap * 8, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, ustride,
+            hipLaunchKernelGGL(link1, dim3(div_up<unsigned>(npair, ustride)), dim3(1024), (size_t)cap * 8, s, ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, cap, ustride,
                                la, sp.d_hint);
             sp.dec.kernels += 3;
         }
@@ -1778,7 +1824,7 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
     // columns where nothing crosses a segment need no workgroup here -- was measured: 17 us for the pass, and the 17 stragglers a clean
     // collection of 10 000 leaves still put a mixed value into a hundred columns, whose workgroups take as long as before: 0.338 vs 0.329 ms)
     const SpColWork cw = sp_colwork_of(sp);
-    hipLaunchKernelGGL(sp_emit_kernel, dim3((unsigned)S), dim3(SP_EMIT_T), 0, s, set->d_ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, lb, sp.d_order,
+    hipLaunchKernelGGL((id16 ? sp_emit_kernel<uint16_t> : sp_emit_kernel<uint32_t>), dim3((unsigned)S), dim3(SP_EMIT_T), 0, s, ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, lb, sp.d_order,
                        cw, sp.d_plctl, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), sp.d_gaveup, (N >= 65536 || tu.emit_big) ? 1 : 0);
     // the pairs of the mixed values: a kernel of its own when the list is expected to be long (it must be complete before the workgroups that
     // count it per bin, which ride on the permute launch); otherwise extra workgroups of the permute launch itself (sp_permute)

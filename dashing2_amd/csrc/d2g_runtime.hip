@@ -8,7 +8,7 @@
 // the library's run-time switches (DESIGN.md section 4 lists what each one does).  Host-side switches that need no context
 // (D2G_MAX_RUN and D2G_NO_AVX512 in d2g_host.cpp, D2G_RCCL_LIB, D2G_COMM_LOOPBACK) are read where they apply.
 static const char *const kTuningNames[] = {
-    "D2G_BS_SORT", "D2G_BS_NSPLIT", "D2G_BS_TAGBITS", "D2G_K2_MERGE",
+    "D2G_BS_SORT", "D2G_BS_NSPLIT", "D2G_BS_TAGBITS", "D2G_BS_ID16", "D2G_K2_MERGE",
     "D2G_BS_SPARSE", "D2G_BS_SPARSE_MIN_N", "D2G_SP_LINK", "D2G_SP_TILE_FRAC", "D2G_SP_LIST_DIV", "D2G_SP_LONG_LIST", "D2G_SP_LIST_FORM", "D2G_SP_PREDICT", "D2G_SP_REMEMBER", "D2G_SP_EMIT_BIG", "D2G_SP_OLINK", "D2G_SP_RIDE",
     "D2G_MGPU_CHUNKS",
     "D2G_K3_COMPACT", "D2G_K3_L1BITS", "D2G_K3_BUCKET_KEYS", "D2G_K3_SUB_KEYS", "D2G_K3_SPLIT_MIN", "D2G_K3_SUBBATCH", "D2G_K3_ROUND_KEYS",
@@ -38,6 +38,7 @@ d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t) {
     if (const char *e = t.get("D2G_SP_LIST_DIV")) { const long d = std::atol(e); if (d >= 1 && d <= (1 << 20)) v.list_div = (size_t)d; }
     if (const char *e = t.get("D2G_BS_SORT")) v.sort = !(e[0] == '0');
     if (const char *e = t.get("D2G_BS_TAGBITS")) { const int d = std::atoi(e); if (d >= 0 && d < 31) v.tagbits_max = d; }
+    if (const char *e = t.get("D2G_BS_ID16")) v.id16 = std::atoi(e) != 0;
     if (const char *e = t.get("D2G_BS_NSPLIT")) { const int d = std::atoi(e); if (d == 1 || d == 2 || d == 4) v.nsplit_req = d; }
     return v;
 }

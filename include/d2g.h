@@ -562,6 +562,11 @@ int  d2g_cmp_set_status(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream);
  * Synchronises `stream` and returns d2g_cmp_set_status's error, if any; all 0 for a DIRECT set. */
 int  d2g_cmp_set_planes(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, unsigned *max_distinct, int *nbits,
                         float *mean_nbits);
+/* width of the words a bit-sliced set keeps its per-column ids in between the kernels of its prepare: 16 for a set of N <= 21 845 sketches (the
+ * rank kernel is single-partition: an id is 0, the unique flag 0x8000 or a rank 1 .. N / 2), 32 for larger sets, for sets whose ids are re-derived from
+ * exchanged planes and everywhere under D2G_BS_ID16=0 (A/B measurements, tests); 0 for a set that keeps no ids (DIRECT sets, sets of truncated codes,
+ * gathered operands without a sparse path).  Results do not depend on it. */
+int  d2g_cmp_set_id_bits(const d2g_cmp_set *set);
 /* Sparse tiles + pair list (bit-sliced sets of N >= 8192 sketches, owning sets and the multi-GPU engine's gathered operand;
  * D2G_BS_SPARSE=0 switches it off, D2G_BS_SPARSE_MIN_N moves the threshold): an equality count is 0 unless the two sketches share a
  * value in some register column.  The prepare finds the families (sketches that agree in MANY registers; a single chance collision

@@ -89,6 +89,7 @@ def main():
                 N = int(rng.integers(2, 700)) if rng.random() < 0.8 else int(rng.integers(700, 2600))
                 S = int(rng.choice([32, 64, 100, 128, 1000, 1024])); meas = int(rng.integers(0, 6))
                 os.environ["D2G_BS_SORT"] = str(int(rng.integers(0, 2)))                    # column plan on / off
+                os.environ["D2G_BS_ID16"] = str(int(rng.integers(0, 2)))                    # 16-bit column ids (these sets are all single-partition) or 32-bit ones
                 # sparse tiles + pair list (rounds 5-6): forced on for these small matrices half of the time -- families found or not
                 # (D2G_SP_LINK=0: the pair list alone), any tile budget, a short list (overflow -> dense walk), the list applied entry by
                 # entry or binned + composed, with or without the first look at the matrix; the other half takes the default (dense walk
@@ -212,6 +213,7 @@ def main():
             elif which == "mgpu":
                 W = int(rng.integers(1, 7)); N = int(rng.integers(2, 400)); S = int(rng.choice([32, 100, 256, 1000, 1024]))
                 os.environ["D2G_MGPU_CHUNKS"] = str(int(rng.integers(1, 5)))                # chunked exchange inside the step
+                os.environ["D2G_BS_ID16"] = str(int(rng.integers(0, 2)))                    # the exporter sets' column ids: 16-bit or 32-bit words
                 regs = synth.synthetic_registers(N, S, nclusters=int(rng.integers(1, 9)), seed=int(rng.integers(0, 1 << 30)))
                 exp = O.eqcounts_ut(regs.view(np.float64))
                 ctxs = [D.Context(0) for _ in range(W)]
