@@ -18,6 +18,8 @@ from .capi import (  # noqa: F401
     KmerFilter, TIME_FILTER,
     Screen, TIME_SCREEN, epilogue_contain, screen_table_slots, SCREEN_MAX_KEYS, run_emissions,
     KSet, TIME_KSET, epilogue_exact, host_epilogue_exact_ut, host_epilogue_exact_rect, kset_check,
+    ALPHABET_DNA, ALPHABET_PROTEIN20, ALPHABET_PROTEIN_3BIT, ALPHABET_PROTEIN_14, ALPHABET_PROTEIN_6,
+    alphabet_size, alphabet_max_k, alphabet_code, alphabet_name, key_bits,
 )
 
 __all__ = [
@@ -32,4 +34,6 @@ __all__ = [
     "KmerFilter", "TIME_FILTER",
     "Screen", "TIME_SCREEN", "epilogue_contain", "screen_table_slots", "SCREEN_MAX_KEYS", "run_emissions",
     "KSet", "TIME_KSET", "epilogue_exact", "host_epilogue_exact_ut", "host_epilogue_exact_rect", "kset_check",
+    "ALPHABET_DNA", "ALPHABET_PROTEIN20", "ALPHABET_PROTEIN_3BIT", "ALPHABET_PROTEIN_14", "ALPHABET_PROTEIN_6",
+    "alphabet_size", "alphabet_max_k", "alphabet_code", "alphabet_name", "key_bits",
 ]

@@ -85,6 +85,16 @@ SIGNATURES = {
     "d2g_epilogue_trunc_ut": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _int, _int, _int, _vp, _int, _vp]),
     "d2g_epilogue_trunc_rect": (_int, [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _sz, _sz, _int, _int, _int, _vp, _int, _vp]),
     "d2g_seqpack_create": (_int, [_int, C.POINTER(_vp)]),
+    "d2g_seqpack_create_alphabet": (_int, [_int, _int, C.POINTER(_vp)]),
+    "d2g_seqpack_alphabet": (_int, [_vp]),
+    "d2g_alphabet_size": (_int, [_int]),
+    "d2g_alphabet_max_k": (_int, [_int]),
+    "d2g_alphabet_code": (_int, [_int, _int]),
+    "d2g_alphabet_name": (C.c_char_p, [_int]),
+    "d2g_key_bits": (_int, [_int, _int]),
+    "d2g_oph_plan_create_alphabet": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _int, _int, C.POINTER(_vp)]),
+    "d2g_sketcher_set_alphabet": (_int, [_vp, _int]),
+    "d2g_kmer_filter_create_alphabet": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _int, _int, C.POINTER(_vp)]),
     "d2g_seqpack_destroy": (None, [_vp]),
     "d2g_seqpack_clear": (None, [_vp]),
     "d2g_seqpack_add_path": (_int, [_vp, _cp]),
@@ -606,15 +616,45 @@ def ut_partition(N, nparts):
     return [int(x) for x in b]
 
 
+# ---------------------------------------------------------------- alphabets (K1a)
+ALPHABET_DNA, ALPHABET_PROTEIN20, ALPHABET_PROTEIN_3BIT, ALPHABET_PROTEIN_14, ALPHABET_PROTEIN_6 = 0, 2, 3, 4, 5
+
+
+def alphabet_size(alphabet):
+    """symbols of the alphabet (4 for DNA; 0 for an unknown id)"""
+    return int(lib().d2g_alphabet_size(alphabet))
+
+
+def alphabet_max_k(alphabet):
+    """the largest k whose key fits 64 bits (32 for DNA; 0 for an unknown id)"""
+    return int(lib().d2g_alphabet_max_k(alphabet))
+
+
+def alphabet_code(alphabet, byte):
+    """code of a byte (an int, or a one-character str / bytes) under the alphabet, -1 for anything that ends a run"""
+    return int(lib().d2g_alphabet_code(alphabet, byte if isinstance(byte, int) else ord(byte)))
+
+
+def alphabet_name(alphabet):
+    return lib().d2g_alphabet_name(alphabet).decode()
+
+
+def key_bits(k, alphabet=ALPHABET_DNA):
+    """bits of the widest key of (k, alphabet): 2k for DNA, the bit length of A^k - 1 for a protein alphabet"""
+    return int(lib().d2g_key_bits(k, alphabet))
+
+
 # ---------------------------------------------------------------- ingest
 class SeqPack:
-    """FASTA/FASTQ -> packed run stream (d2g_seqpack_*)."""
+    """FASTA/FASTQ -> packed run stream (d2g_seqpack_*).  alphabet: ALPHABET_DNA (2 bits per base) or a protein alphabet (one byte per
+    residue, K1a) -- the stream then belongs to a Sketcher / a plan / a filter under the same alphabet."""
 
-    def __init__(self, k):
+    def __init__(self, k, alphabet=ALPHABET_DNA):
         self.k = k
+        self.alphabet = alphabet
         self._h = None
         h = _vp()
-        rc = lib().d2g_seqpack_create(k, C.byref(h))
+        rc = lib().d2g_seqpack_create_alphabet(k, alphabet, C.byref(h))
         if rc:
             raise D2GError(rc)
         self._h = h
@@ -881,12 +921,19 @@ class Context:
                                                     ns, S, _np_ptr(sig), _np_ptr(tw), _np_ptr(own)))
         return sig, tw, own
 
-    def oph_plan(self, run_start, run_len, genome_run_off, k, w=0):
-        """launch plan over a run table; w > k: a windowed one (K1w) -- every *_dev call over it walks minimizers"""
+    def oph_plan(self, run_start, run_len, genome_run_off, k, w=0, alphabet=ALPHABET_DNA):
+        """launch plan over a run table; w > k: a windowed one (K1w) -- every *_dev call over it walks minimizers; a protein alphabet
+        (K1a): every *_dev call over it reads a byte-per-residue stream (no window with it)"""
         run_start = np.ascontiguousarray(run_start, np.uint64)
         run_len = np.ascontiguousarray(run_len, np.uint32)
         genome_run_off = np.ascontiguousarray(genome_run_off, np.uint64)
         h = _vp()
+        if alphabet != ALPHABET_DNA:
+            if w > k:
+                raise ValueError("a window (w > k) with a protein alphabet: the windowed walker is DNA only")
+            self._check(lib().d2g_oph_plan_create_alphabet(self._h, _np_ptr(run_start), _np_ptr(run_len), run_start.size,
+                                                           _np_ptr(genome_run_off), genome_run_off.size - 1, k, alphabet, C.byref(h)))
+            return OphPlan(self, h, genome_run_off.size - 1)
         self._check(lib().d2g_oph_plan_create_windowed(self._h, _np_ptr(run_start), _np_ptr(run_len), run_start.size,
                                                        _np_ptr(genome_run_off), genome_run_off.size - 1, k, w, C.byref(h)))
         return OphPlan(self, h, genome_run_off.size - 1)
@@ -911,6 +958,11 @@ class Context:
         """the k-mers of ALL genomes of `sp` as one device-resident set (host-pointer form; synchronises); w > k: its minimizers"""
         r = _Runs(sp, canon)
         h = _vp()
+        if getattr(sp, "alphabet", ALPHABET_DNA) != ALPHABET_DNA:      # K1a: the pack's alphabet; there is no canonical form (canon is not looked at)
+            if w > sp.k:
+                raise ValueError("a window (w > k) with a protein alphabet: the windowed walker is DNA only")
+            self._check(lib().d2g_kmer_filter_create_alphabet(self._h, *r.args[:5], r.args[7], sp.alphabet, C.byref(h)))
+            return KmerFilter(self, h, sp.k, False)
         self._check(lib().d2g_kmer_filter_create_windowed(self._h, *r.args[:5], *r.args[7:], w, C.byref(h)))      # no genomes: all runs feed one set
         return KmerFilter(self, h, sp.k, bool(canon))
 
@@ -1077,6 +1129,11 @@ class Sketcher:
     def set_window(self, w):
         """K1w: every later run* of this sketcher walks the minimizers of windows of w bases when w > its k; 0 or w <= k: off"""
         self.ctx._check(lib().d2g_sketcher_set_window(self._h, int(w)))
+
+    def set_alphabet(self, alphabet):
+        """K1a: every later run* of this sketcher reads its stream as one byte per residue of this protein alphabet (a SeqPack made
+        with the same one); ALPHABET_DNA switches back"""
+        self.ctx._check(lib().d2g_sketcher_set_alphabet(self._h, int(alphabet)))
 
     def _ingested(self, runs, k):
         """the source of a run table over the stream ingested last (k: default the k of the ingest)"""

@@ -28,11 +28,11 @@ struct FilterBuildArgs {
     uint32_t mask, shift;
 };
 
-template <bool WIN>
+template <bool WIN, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void filter_build_kernel(FilterBuildArgs a) {
     uint32_t claimed = 0;
     bool ones = false;
-    d2g_for_each_kmer<false, false, WIN>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<false, false, WIN, AA>(a.km, [&](uint64_t x) {
         if (x == D2G_FILTER_EMPTY) { ones = true; return; }
         uint32_t s = d2g_filter_slot(x, a.shift);
         for (;;) {
@@ -52,10 +52,10 @@ __global__ __launch_bounds__(K1_THREADS) void filter_build_kernel(FilterBuildArg
 }
 
 // surviving k-mers per genome (K3's layout)
-template <bool WIN>
+template <bool WIN, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void filter_survivors_kernel(KmerArgs km, unsigned long long *per_genome) {
     uint32_t c = 0;
-    d2g_for_each_kmer<true, false, WIN>(km, [&](uint64_t) { ++c; });
+    d2g_for_each_kmer<true, false, WIN, AA>(km, [&](uint64_t) { ++c; });
     for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(&per_genome[km.blk_genome[blockIdx.x]], (unsigned long long)c);
 }
@@ -70,9 +70,10 @@ __global__ __launch_bounds__(256) void filter_contains_kernel(KmerArgs km, const
 
 }  // namespace
 
-int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon, int w) {
+int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon, int w, int alphabet) {
     if (!f) return D2G_OK;
     D2G_CHECK(ctx, f->ctx == ctx, "k-mer filter belongs to another context");
+    D2G_CHECK(ctx, f->alphabet == alphabet, "k-mer filter was built under another alphabet");
     D2G_CHECK(ctx, f->k == k, "k-mer filter was built for another k");
     D2G_CHECK(ctx, (f->canon != 0) == (canon != 0), "k-mer filter was built with another canonicalisation");
     D2G_CHECK(ctx, f->w == d2g_window_norm(k, w), "k-mer filter was built under another window (-w)");
@@ -93,7 +94,8 @@ int d2g_filter_survivors(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n
     if (int rc = d_cnt.alloc(ctx, n, "k-mer filter survivor counts")) return rc;
     D2G_HIP(ctx, hipMemsetAsync(d_cnt, 0, n * sizeof(unsigned long long), s));
     KmerArgs a = km; a.blk0 = 0;
-    hipLaunchKernelGGL(km.q > 1 ? filter_survivors_kernel<true> : filter_survivors_kernel<false>, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a, d_cnt.get());
+    const auto kern = d2g_km_protein(km) ? filter_survivors_kernel<false, true> : km.q > 1 ? filter_survivors_kernel<true> : filter_survivors_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a, d_cnt.get());
     D2G_HIP(ctx, hipGetLastError());
     D2G_HIP(ctx, hipMemcpyAsync(out, d_cnt, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
     D2G_HIP(ctx, hipStreamSynchronize(s));
@@ -119,7 +121,7 @@ static int filter_build(const KmerBatch &b, uint64_t nkmers, d2g_kmer_filter **o
     d2g_kmer_filter *f = new (std::nothrow) d2g_kmer_filter();
     if (!f) return D2G_ERR_NOMEM;
     std::unique_ptr<d2g_kmer_filter, void (*)(d2g_kmer_filter *)> owner(f, d2g_kmer_filter_destroy);
-    f->ctx = ctx; f->k = k; f->canon = canon != 0; f->w = b.runs.w; f->noccurrences = nkmers;
+    f->ctx = ctx; f->k = k; f->canon = canon != 0; f->w = b.runs.w; f->alphabet = b.runs.alphabet; f->noccurrences = nkmers;
     f->slots = 16;
     while (f->slots < 2 * f->noccurrences) f->slots <<= 1;
     if (int rc = f->d_tab.alloc(ctx, f->slots + 2, "k-mer filter table")) return rc;      // out of memory: D2G_ERR_NOMEM, no smaller table
@@ -133,7 +135,8 @@ static int filter_build(const KmerBatch &b, uint64_t nkmers, d2g_kmer_filter **o
         a.km = b.km;
         a.km.ftab = nullptr;
         a.tab = f->d_tab; a.mask = self.fmask; a.shift = self.fshift;
-        hipLaunchKernelGGL(a.km.q > 1 ? filter_build_kernel<true> : filter_build_kernel<false>, dim3((unsigned)b.nblk), dim3(K1_THREADS), 0, s, a);
+        const auto kern = d2g_km_protein(a.km) ? filter_build_kernel<false, true> : a.km.q > 1 ? filter_build_kernel<true> : filter_build_kernel<false>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)b.nblk), dim3(K1_THREADS), 0, s, a);
     }
     tm.stop();
     D2G_HIP(ctx, hipGetLastError());
@@ -163,8 +166,9 @@ int d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_by
     return d2g_kmer_filter_create_windowed(ctx, packed, packed_bytes, run_start, run_len, nrun, k, canon, 0, out);
 }
 
-int d2g_kmer_filter_create_windowed(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
-                                    const uint32_t *run_len, size_t nrun, int k, int canon, int w, d2g_kmer_filter **out) {
+// the host-pointer forms: a sketcher that lives for the call, under the window or the alphabet asked for
+static int filter_create_host(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start, const uint32_t *run_len,
+                              size_t nrun, int k, int canon, int w, int alphabet, d2g_kmer_filter **out) {
     const uint64_t gro[2] = {0, nrun};                            // all runs feed ONE set
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, gro, 1, k, canon};
     if (!ctx || !out) return D2G_ERR_INVALID;
@@ -173,6 +177,7 @@ int d2g_kmer_filter_create_windowed(d2g_ctx *ctx, const uint8_t *packed, size_t 
         KmerBatch b;
         PlanHost ph;
         if (int rc = d2g_sketcher_set_window(sk, w)) return rc;
+        if (int rc = d2g_sketcher_set_alphabet(sk, alphabet)) return rc;
         if (int rc = d2g_sketcher_stage(sk, in, &b, &ph)) return rc;
         d2g_kmer_filter *f = nullptr;
         if (int rc = filter_build(b, ph.nkmers, &f)) return rc;
@@ -181,6 +186,16 @@ int d2g_kmer_filter_create_windowed(d2g_ctx *ctx, const uint8_t *packed, size_t 
         *out = f;
         return D2G_OK;
     });
+}
+
+int d2g_kmer_filter_create_windowed(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                                    const uint32_t *run_len, size_t nrun, int k, int canon, int w, d2g_kmer_filter **out) {
+    return filter_create_host(ctx, packed, packed_bytes, run_start, run_len, nrun, k, canon, w, D2G_ALPHABET_DNA, out);
+}
+
+int d2g_kmer_filter_create_alphabet(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                                    const uint32_t *run_len, size_t nrun, int k, int alphabet, d2g_kmer_filter **out) {
+    return filter_create_host(ctx, packed, packed_bytes, run_start, run_len, nrun, k, 0, 0, alphabet, out);
 }
 
 int d2g_kmer_filter_info(d2g_ctx *ctx, const d2g_kmer_filter *f, uint64_t *noccurrences, uint64_t *ndistinct, size_t *table_bytes) {

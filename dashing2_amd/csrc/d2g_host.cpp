@@ -5,6 +5,7 @@
 //
 // Reference lines restated here are cited per function.
 #include "../../include/d2g.h"
+#include "d2g_alphabet.h"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -701,6 +702,8 @@ __attribute__((target("avx512f,avx512bw,avx512vl,avx512vbmi2"))) static inline i
 
 struct d2g_seqpack {
     int k;
+    int alphabet = D2G_ALPHABET_DNA;   // K1a: under a protein alphabet `packed` holds one byte per residue (its code) and "bases" are residues
+    int8_t aa_lut[256];                // ... and this is the code of every input byte, -1 = ends a run
     std::vector<uint8_t> packed;       // 4 bases / byte
     uint64_t nbases = 0;               // bases appended to the stream
     std::vector<uint64_t> run_start;
@@ -722,6 +725,7 @@ struct d2g_seqpack {
     // (packed.size() may exceed the stream: the logical length is nbases)
     inline void rewind_to(uint64_t nb) {
         nbases = nb;
+        if (alphabet) return;                              // whole bytes: nothing of the dropped residues shares one with the stream
         if (nb & 3) packed[nb >> 2] &= uint8_t((1u << ((nb & 3) * 2)) - 1);
     }
     void close_run_raw() {
@@ -741,7 +745,25 @@ struct d2g_seqpack {
         cur_len = 0;
     }
     void close_run() { close_run_raw(); }
+    // K1a: one byte per residue
+    void feed_aa(const char *s, size_t n) {
+        const size_t need = nbases + n + 1;
+        if (packed.size() < need) packed.resize(std::max(need, packed.size() + packed.size() / 2));
+        uint8_t *pk = packed.data();
+        uint64_t nb = nbases, clen = cur_len;
+        for (size_t i = 0; i < n; ++i) {
+            const int c = aa_lut[(unsigned char)s[i]];
+            if (c < 0) {
+                if (clen) { nbases = nb; cur_len = clen; close_run_raw(); nb = nbases; clen = 0; }
+                continue;
+            }
+            if (!clen) cur_start = nb;
+            pk[nb++] = uint8_t(c); ++clen;
+        }
+        nbases = nb; cur_len = clen;
+    }
     inline void feed(const char *s, size_t n) {
+        if (alphabet) { feed_aa(s, n); return; }
         static const int8_t *lut = code_lut();
         // worst case every byte is a base: make room once, then write through a raw pointer
         const size_t need = (nbases + n + 3) / 4 + 1;
@@ -888,7 +910,7 @@ struct d2g_seqpack {
                 const int c = (unsigned char)buf[pos];
                 // a record boundary is only looked for at the start of a line (the block path may stop inside one)
                 if (at_line_start && (c == '>' || c == '+' || c == '@')) { term = c; ++pos; break; }
-                if (have_vbmi2 && len - pos >= 64) {
+                if (have_vbmi2 && !alphabet && len - pos >= 64) {
                     const size_t took = feed_blocks(buf + pos, len - pos, &seqlen);
                     if (took) {
                         pos += took;
@@ -942,14 +964,14 @@ struct d2g_seqpack {
     }
     void finalize_pad() {
         // logical stream = ceil(nbases/4) bytes; everything after it must read as zero-initialised pad
-        const size_t nbytes = (nbases + 3) / 4;
+        const size_t nbytes = alphabet ? nbases : (nbases + 3) / 4;
         if (packed.size() < nbytes + 64) packed.resize(nbytes + 64, 0);
         std::memset(packed.data() + nbytes, 0, 64);
         padded_bytes = nbytes + 64;
     }
     void unpad() {}
     void reserve_bases(uint64_t more) {
-        const size_t need = (nbases + more + 3) / 4 + 65;
+        const size_t need = alphabet ? nbases + more + 65 : (nbases + more + 3) / 4 + 65;
         if (packed.size() < need) packed.resize(need);
     }
     size_t padded_bytes = 0;
@@ -1017,15 +1039,20 @@ static bool slurp(const char *path, std::vector<char> &out, size_t &len) {
 
 extern "C" {
 
-int d2g_seqpack_create(int k, d2g_seqpack **out) {
+int d2g_seqpack_create(int k, d2g_seqpack **out) { return d2g_seqpack_create_alphabet(k, D2G_ALPHABET_DNA, out); }
+int d2g_seqpack_create_alphabet(int k, int alphabet, d2g_seqpack **out) {
     if (!out) return D2G_ERR_INVALID;
-    if (k < 1 || k > 32) return D2G_ERR_UNSUPPORTED;   // k > 32 is the reference's rolling-hash path (fastxsketch.cpp:420)
+    // k > 32 is the reference's rolling-hash path (fastxsketch.cpp:420); so is k beyond what 64 bits hold of a protein alphabet
+    if (k < 1 || k > d2g_alphabet_max_k_of(alphabet)) return D2G_ERR_UNSUPPORTED;
     auto *sp = new (std::nothrow) d2g_seqpack();
     if (!sp) return D2G_ERR_NOMEM;
     sp->k = k;
+    sp->alphabet = alphabet;
+    for (int c = 0; c < 256; ++c) sp->aa_lut[c] = (int8_t)d2g_alphabet_code_of(alphabet, (unsigned char)c);
     *out = sp;
     return D2G_OK;
 }
+int d2g_seqpack_alphabet(const d2g_seqpack *sp) { return sp ? sp->alphabet : D2G_ALPHABET_DNA; }
 void d2g_seqpack_destroy(d2g_seqpack *sp) { delete sp; }
 void d2g_seqpack_clear(d2g_seqpack *sp) {          // keep every allocation, forget the content
     if (!sp) return;

@@ -358,6 +358,7 @@ int d2g_sketcher_ingest_fasta(d2g_sketcher *sk, const uint8_t *raw, size_t raw_b
                               size_t nfiles, const uint64_t *genome_file_off, size_t n, int k) {
     if (!sk) return D2G_ERR_INVALID;
     d2g_ctx *ctx = sk->ctx;
+    if (sk->alphabet != D2G_ALPHABET_DNA) { ctx->last_error = "ingest: the device parser reads DNA; a protein alphabet goes through the host parser"; return D2G_ERR_UNSUPPORTED; }
     D2G_CHECK(ctx, k >= 1 && k <= 32, "k out of range (1..32)");
     D2G_CHECK(ctx, nfiles < (1u << 30) && (nfiles == 0 || (raw && file_off && file_len)) && genome_file_off && genome_file_off[n] == nfiles, "ingest: bad file table");
     if (!sk->k0) { sk->k0 = new (std::nothrow) d2g_k0_state(); if (!sk->k0) return D2G_ERR_NOMEM; }

@@ -15,12 +15,13 @@ struct d2g_kmer_filter {
     d2g_ctx *ctx = nullptr;
     int k = 0, canon = 0;
     int w = 0;                                 // the window it was built under, 0 = none (never a value <= k)
+    int alphabet = 0;                          // the alphabet its keys were encoded under (D2G_ALPHABET_*)
     uint64_t noccurrences = 0;                 // k-mers put in, duplicates counted (the reference's data_.size())
     uint64_t slots = 0;                        // a power of two >= 2 * noccurrences (>= 16)
     d2g_dev<uint64_t> d_tab;                   // [slots] keys, then [0] the all-ones flag, [1] the distinct keys in the slots
 };
-// the filter a plan or sketcher carries must fit the call: same context, k, canon and window (nullptr fits everything)
-int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon, int w);
+// the filter a plan or sketcher carries must fit the call: same context, alphabet, k, canon and window (nullptr fits everything)
+int d2g_filter_check(d2g_ctx *ctx, const d2g_kmer_filter *f, int k, int canon, int w, int alphabet);
 // a window as the library keeps it: w when w > k, else 0
 inline int d2g_window_norm(int k, int w) { return w > k ? w : 0; }
 // table pointer, mask and shift into the walker's arguments (nullptr: no filter); the caller has run d2g_filter_check
@@ -34,6 +35,7 @@ struct d2g_oph_plan {
     const d2g_kmer_filter *filter = nullptr;   // VIEW (d2g_oph_plan_set_filter)
     int k = 0;
     int w = 0;                                 // d2g_oph_plan_create_windowed: the chunks are window positions (0 = none)
+    int alphabet = 0;                          // d2g_oph_plan_create_alphabet: the stream is one byte per residue (0 = DNA)
     size_t n = 0, nrun = 0, nblk = 0;
     uint64_t nkmers = 0, nbases = 0;
     std::vector<uint32_t> h_run_len;           // host copies kept for K3's bucket layout
@@ -41,11 +43,14 @@ struct d2g_oph_plan {
     PlanLayout lay;                            // the eight launch tables: pieces of ONE device buffer, as the sketcher ships them
     d2g_dev<uint8_t> d_arena;
     // the tables K3 lays its buckets out from (host copies; no stream: a plan is applied to any)
-    PackedRuns runs(int canon) const { return {nullptr, 0, nullptr, h_run_len.data(), nrun, h_genome_run_off.data(), n, k, canon, w}; }
+    PackedRuns runs(int canon) const { return {nullptr, 0, nullptr, h_run_len.data(), nrun, h_genome_run_off.data(), n, k, canon, w, alphabet}; }
 };
 
+// THE single constructor of the arguments a walker sees, and what d2g_km_protein() (d2g_kmers.h) rests on: a DNA batch stores canon
+// as 0 or 1 here -- whatever non-zero value the caller passed; the kernels only ever asked `canon != 0` -- and a protein batch stores
+// its alphabet's size (>= 6) in the same word.  Every KmerArgs that reaches a walking kernel is a copy of one made here.
 // the ONLY place that points a walker's arguments at launch tables: `arena_dev` holds them as `lay` says (d2g_plan_fill)
-inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &lay, const uint8_t *packed_dev, int k, int canon, int w) {
+inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &lay, const uint8_t *packed_dev, int k, int canon, int w, int alphabet) {
     KmerArgs a{};
     auto u64 = [&](size_t at) { return reinterpret_cast<const uint64_t *>(arena_dev + at); };
     auto u32 = [&](size_t at) { return reinterpret_cast<const uint32_t *>(arena_dev + at); };
@@ -53,7 +58,8 @@ inline KmerArgs d2g_plan_kmer_args(const uint8_t *arena_dev, const PlanLayout &l
     a.run_start = u64(lay.run_start); a.run_len = u32(lay.run_len); a.run_chunk_off = u64(lay.run_chunk_off);
     a.blk_genome = u32(lay.blk_genome); a.blk_chunk0 = u64(lay.blk_chunk0); a.blk_nchunks = u32(lay.blk_nchunks);
     a.blk_run_lo = u32(lay.blk_run_lo); a.blk_run_hi = u32(lay.blk_run_hi);
-    a.k = k; a.canon = canon; a.blk0 = 0; a.q = (uint32_t)d2g_window_q(k, w);
+    a.k = k; a.canon = canon != 0; a.blk0 = 0; a.q = (uint32_t)d2g_window_q(k, w);
+    if (alphabet != D2G_ALPHABET_DNA) a.canon = d2g_alphabet_size(alphabet);               // K1a: A (>= 6) where canon (0 here) stands; the kernels read it as asize
     return a;
 }
 // Host ingest feeds K1 in groups of inputs; re-allocating device buffers and uploading eight
@@ -65,6 +71,7 @@ struct d2g_sketcher {
     d2g_ctx *ctx = nullptr;
     const d2g_kmer_filter *filter = nullptr;               // VIEW (d2g_sketcher_set_filter)
     int w = 0;                                             // d2g_sketcher_set_window: every run walks minimizers when w > its k
+    int alphabet = 0;                                      // d2g_sketcher_set_alphabet: every run reads a byte-per-residue stream (0 = DNA)
     d2g_stream stream;
     d2g_dev<uint8_t> d_packed;                             // grow-only, like the buffers below
     d2g_dev<uint64_t> d_regs;
@@ -74,8 +81,9 @@ struct d2g_sketcher {
     d2g_k3_state *k3 = nullptr;                            // --multiset work buffers (d2g_k3_bmh.hip)
     d2g_k0_state *k0 = nullptr;                            // device FASTA ingest (d2g_k0.hip): raw bytes, tile tables, the last run table
 };
-// an entry point's view of its arguments carries no window: the sketcher's, as the plan unit and the accounting in front of a stage see it
-inline PackedRuns d2g_sketcher_view(const d2g_sketcher *sk, PackedRuns in) { in.w = d2g_window_norm(in.k, sk->w); return in; }
+// an entry point's view of its arguments carries no window and no alphabet: the sketcher's, as the plan unit and the accounting in
+// front of a stage see them
+inline PackedRuns d2g_sketcher_view(const d2g_sketcher *sk, PackedRuns in) { in.w = d2g_window_norm(in.k, sk->w); in.alphabet = sk->alphabet; return in; }
 void d2g_k0_state_destroy(d2g_k0_state *st);
 bool d2g_k0_ingested(const d2g_sketcher *sk, uint64_t *nbases);   // d_packed holds a stream ingested by K0 (and how many bases)
 void d2g_k0_invalidate(d2g_sketcher *sk);

@@ -30,7 +30,7 @@ struct K1Args {
     uint32_t m;
 };
 
-template <bool POW2, bool USE_LDS, bool FILT, bool WIN = false>
+template <bool POW2, bool USE_LDS, bool FILT, bool WIN = false, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
     const int tid = threadIdx.x;
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_kernel(K1Args a) {
         __syncthreads();
     }
     const uint64_t xormask = a.xormask, ophxor = a.ophxor;
-    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN, AA>(a.km, [&](uint64_t x) {
         const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
         // Schismatic<uint32_t>::mod(size_t): argument narrowed to 32 bits (oph.h:184)
         const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
@@ -79,7 +79,7 @@ struct K1CountArgs {
     uint32_t m;
 };
 
-template <bool POW2, bool USE_LDS, bool FILT, bool WIN = false>
+template <bool POW2, bool USE_LDS, bool FILT, bool WIN = false, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint64_t lreg[];
     const int tid = threadIdx.x;
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a)
         __syncthreads();
     }
     const uint64_t xormask = a.xormask, ophxor = a.ophxor;
-    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN, AA>(a.km, [&](uint64_t x) {
         const uint64_t id = wang64(wang64(x ^ xormask) ^ ophxor);
         const uint32_t idx = POW2 ? ((uint32_t)id & (m - 1)) : ((uint32_t)id % m);
         if (USE_LDS) {
@@ -112,32 +112,40 @@ __global__ __launch_bounds__(K1_THREADS) void k1_oph_count_kernel(K1CountArgs a)
     }
 }
 
-// the instantiations, indexed by POW2 * 4 + USE_LDS * 2 + FILT; the windowed ones (K1w) behind them, + 8
-void (*const k1_kernels[16])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
+// the instantiations, indexed by POW2 * 4 + USE_LDS * 2 + FILT; the windowed ones (K1w) behind them, + 8; the amino-acid ones (K1a), + 16
+void (*const k1_kernels[24])(K1Args) = {k1_oph_kernel<false, false, false>, k1_oph_kernel<false, false, true>, k1_oph_kernel<false, true, false>,
                                        k1_oph_kernel<false, true, true>,   k1_oph_kernel<true, false, false>, k1_oph_kernel<true, false, true>,
                                        k1_oph_kernel<true, true, false>,   k1_oph_kernel<true, true, true>,
                                        k1_oph_kernel<false, false, false, true>, k1_oph_kernel<false, false, true, true>,
                                        k1_oph_kernel<false, true, false, true>,  k1_oph_kernel<false, true, true, true>,
                                        k1_oph_kernel<true, false, false, true>,  k1_oph_kernel<true, false, true, true>,
-                                       k1_oph_kernel<true, true, false, true>,   k1_oph_kernel<true, true, true, true>};
-void (*const k1_count_kernels[16])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
+                                       k1_oph_kernel<true, true, false, true>,   k1_oph_kernel<true, true, true, true>,
+                                       k1_oph_kernel<false, false, false, false, true>, k1_oph_kernel<false, false, true, false, true>,
+                                       k1_oph_kernel<false, true, false, false, true>,  k1_oph_kernel<false, true, true, false, true>,
+                                       k1_oph_kernel<true, false, false, false, true>,  k1_oph_kernel<true, false, true, false, true>,
+                                       k1_oph_kernel<true, true, false, false, true>,   k1_oph_kernel<true, true, true, false, true>};
+void (*const k1_count_kernels[24])(K1CountArgs) = {k1_oph_count_kernel<false, false, false>, k1_oph_count_kernel<false, false, true>,
                                                   k1_oph_count_kernel<false, true, false>,  k1_oph_count_kernel<false, true, true>,
                                                   k1_oph_count_kernel<true, false, false>,  k1_oph_count_kernel<true, false, true>,
                                                   k1_oph_count_kernel<true, true, false>,   k1_oph_count_kernel<true, true, true>,
                                                   k1_oph_count_kernel<false, false, false, true>, k1_oph_count_kernel<false, false, true, true>,
                                                   k1_oph_count_kernel<false, true, false, true>,  k1_oph_count_kernel<false, true, true, true>,
                                                   k1_oph_count_kernel<true, false, false, true>,  k1_oph_count_kernel<true, false, true, true>,
-                                                  k1_oph_count_kernel<true, true, false, true>,   k1_oph_count_kernel<true, true, true, true>};
+                                                  k1_oph_count_kernel<true, true, false, true>,   k1_oph_count_kernel<true, true, true, true>,
+                                                  k1_oph_count_kernel<false, false, false, false, true>, k1_oph_count_kernel<false, false, true, false, true>,
+                                                  k1_oph_count_kernel<false, true, false, false, true>,  k1_oph_count_kernel<false, true, true, false, true>,
+                                                  k1_oph_count_kernel<true, false, false, false, true>,  k1_oph_count_kernel<true, false, true, false, true>,
+                                                  k1_oph_count_kernel<true, true, false, false, true>,   k1_oph_count_kernel<true, true, true, false, true>};
 
 // one workgroup per block of the plan; its genome's m registers (K1: 8 bytes each; the count pass: 8 + 4) in LDS while they
 // fit the 128 KB asked for at most (m <= 16 384; m <= 10 922), beyond against HBM/L2
 template <class Args>
-int launch_k1_any(d2g_ctx *ctx, void (*const kerns[16])(Args), const Args &a, size_t nblk, size_t lds_per_reg, d2g_evlog *ev, hipStream_t s) {
+int launch_k1_any(d2g_ctx *ctx, void (*const kerns[24])(Args), const Args &a, size_t nblk, size_t lds_per_reg, d2g_evlog *ev, hipStream_t s) {
     const size_t m = a.m;
     const bool pow2 = (m & (m - 1)) == 0;
     const size_t lds = m * lds_per_reg;
     const bool use_lds = lds <= 128 * 1024;
-    auto kern = kerns[(a.km.q > 1) * 8 + pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
+    auto kern = kerns[(d2g_km_protein(a.km) ? 16 : (a.km.q > 1) * 8) + pow2 * 4 + use_lds * 2 + (a.km.ftab != nullptr)];
     if (use_lds && lds > 48 * 1024)
         D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     d2g_timer tm(ctx, ev, s);
@@ -221,9 +229,27 @@ int d2g_oph_plan_create(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t 
     return d2g_oph_plan_create_windowed(ctx, run_start, run_len, nrun, genome_run_off, n, k, 0, out);
 }
 
+namespace {
+int oph_plan_create(d2g_ctx *ctx, const PackedRuns &in, d2g_oph_plan **out);
+}
+
 int d2g_oph_plan_create_windowed(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                                  const uint64_t *genome_run_off, size_t n, int k, int w, d2g_oph_plan **out) {
     const PackedRuns in{nullptr, 0, run_start, run_len, nrun, genome_run_off, n, k, 0, d2g_window_norm(k, w)};   // a plan is made without a stream
+    return oph_plan_create(ctx, in, out);
+}
+
+int d2g_oph_plan_create_alphabet(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                                 const uint64_t *genome_run_off, size_t n, int k, int alphabet, d2g_oph_plan **out) {
+    const PackedRuns in{nullptr, 0, run_start, run_len, nrun, genome_run_off, n, k, 0, 0, alphabet};
+    return oph_plan_create(ctx, in, out);
+}
+
+}  // extern "C"
+
+namespace {
+int oph_plan_create(d2g_ctx *ctx, const PackedRuns &in, d2g_oph_plan **out) {
+    const size_t nrun = in.nrun, n = in.n;
     if (!ctx || !out) return D2G_ERR_INVALID;
     *out = nullptr;
     PlanHost ph;
@@ -232,9 +258,9 @@ int d2g_oph_plan_create_windowed(d2g_ctx *ctx, const uint64_t *run_start, const 
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     std::unique_ptr<d2g_oph_plan, void (*)(d2g_oph_plan *)> p(new (std::nothrow) d2g_oph_plan(), d2g_oph_plan_destroy);
     if (!p) return D2G_ERR_NOMEM;
-    p->ctx = ctx; p->k = k; p->w = in.w; p->n = n; p->nrun = nrun;
-    p->h_run_len.assign(run_len, run_len + nrun);
-    p->h_genome_run_off.assign(genome_run_off, genome_run_off + n + 1);
+    p->ctx = ctx; p->k = in.k; p->w = in.w; p->alphabet = in.alphabet; p->n = n; p->nrun = nrun;
+    p->h_run_len.assign(in.run_len, in.run_len + nrun);
+    p->h_genome_run_off.assign(in.genome_run_off, in.genome_run_off + n + 1);
     p->nkmers = ph.nkmers; p->nbases = ph.nbases; p->nblk = ph.bg.size();
     p->lay = d2g_plan_layout(nrun, p->nblk);
     std::vector<uint8_t> h(p->lay.total);
@@ -244,6 +270,9 @@ int d2g_oph_plan_create_windowed(d2g_ctx *ctx, const uint64_t *run_start, const 
     *out = p.release();
     return D2G_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev, int canon,
                        uint64_t xormask, size_t sketchsize, uint64_t *regs_out_dev, void *stream) {
@@ -305,6 +334,13 @@ int d2g_sketcher_set_window(d2g_sketcher *sk, int w) {
     return D2G_OK;
 }
 
+int d2g_sketcher_set_alphabet(d2g_sketcher *sk, int alphabet) {
+    if (!sk) return D2G_ERR_INVALID;
+    D2G_CHECK(sk->ctx, alphabet == D2G_ALPHABET_DNA || d2g_alphabet_size(alphabet) > 0, "unknown alphabet");
+    sk->alphabet = alphabet;
+    return D2G_OK;
+}
+
 int d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                      const uint32_t *run_len, size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon,
                      uint64_t xormask, size_t sketchsize, uint64_t *regs_out) {
@@ -355,9 +391,10 @@ int d2g_plan_batch(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed
     D2G_CHECK(ctx, plan->ctx == ctx, "plan belongs to another context");
     D2G_CHECK(ctx, ((uintptr_t)packed_dev & 3) == 0, "packed stream must be 4-byte aligned");
     D2G_CHECK(ctx, plan->nblk == 0 || packed_dev != nullptr, "null packed stream");
-    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon, plan->w)) return rc;
+    D2G_CHECK(ctx, plan->alphabet == D2G_ALPHABET_DNA || canon == 0, "a protein alphabet has no canonical k-mers: canon must be 0");
+    if (int rc = d2g_filter_check(ctx, plan->filter, plan->k, canon, plan->w, plan->alphabet)) return rc;
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    *out = KmerBatch{ctx, as_stream(stream), d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon, plan->w), plan->nblk, plan->runs(canon),
+    *out = KmerBatch{ctx, as_stream(stream), d2g_plan_kmer_args(plan->d_arena, plan->lay, packed_dev, plan->k, canon, plan->w, plan->alphabet), plan->nblk, plan->runs(canon),
                      &ctx->k3};
     d2g_filter_args(plan->filter, &out->km);
     return D2G_OK;
@@ -366,9 +403,10 @@ int d2g_plan_batch(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed
 int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerBatch *out, PlanHost *ph_out) {
     d2g_ctx *ctx = sk->ctx;
     PackedRuns in = d2g_sketcher_view(sk, caller);
-    if (int rc = d2g_filter_check(ctx, sk->filter, in.k, in.canon, in.w)) return rc;   // before the stream, the buffers or an output are touched
+    if (int rc = d2g_filter_check(ctx, sk->filter, in.k, in.canon, in.w, in.alphabet)) return rc;   // before the stream, the buffers or an output are touched
     uint64_t ingested_bases = 0;
     const bool use_ingested = in.packed == nullptr && d2g_k0_ingested(sk, &ingested_bases);
+    D2G_CHECK(ctx, !(use_ingested && in.alphabet != D2G_ALPHABET_DNA), "the ingested stream is DNA: a protein alphabet needs a packed stream");
     D2G_CHECK(ctx, in.nrun == 0 || (in.run_start && (in.packed || use_ingested)), "null input");   // refused with an ingested stream left usable
     if (use_ingested) in.packed_bytes = (size_t)((ingested_bases + 3) / 4 + 64);      // the device stream's extent (zero-padded by the ingest)
     else d2g_k0_invalidate(sk);                                                       // the device buffer is about to be overwritten
@@ -394,8 +432,8 @@ int d2g_sketcher_stage(d2g_sketcher *sk, const PackedRuns &caller, KmerBatch *ou
         std::memcpy(sk->h_stage, in.packed, in.packed_bytes);
         D2G_HIP(ctx, hipMemcpyAsync(sk->d_packed, sk->h_stage, in.packed_bytes, hipMemcpyHostToDevice, s));
     }
-    *out = KmerBatch{ctx, s, d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon, in.w), nblk, caller, &sk->k3};
-    out->runs.packed = nullptr; out->runs.packed_bytes = 0; out->runs.w = in.w;
+    *out = KmerBatch{ctx, s, d2g_plan_kmer_args(sk->d_arena, lay, sk->d_packed, in.k, in.canon, in.w, in.alphabet), nblk, caller, &sk->k3};
+    out->runs.packed = nullptr; out->runs.packed_bytes = 0; out->runs.w = in.w; out->runs.alphabet = in.alphabet;
     d2g_filter_args(sk->filter, &out->km);
     return D2G_OK;
 }

@@ -73,7 +73,7 @@ struct K3Args {
 
 __device__ __forceinline__ uint32_t bucket_of(uint64_t key, uint32_t bb) { return bb ? (uint32_t)(key >> (64 - bb)) : 0u; }
 
-template <bool FILT, bool WIN = false>
+template <bool FILT, bool WIN = false, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void k3_hist_kernel(K3Args a) {
     __shared__ uint32_t hist[K3_MAXB];
     const int tid = threadIdx.x;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_hist_kernel(K3Args a) {
     for (uint32_t i = tid; i < B; i += K1_THREADS) hist[i] = 0;
     __syncthreads();
     const uint64_t xormask = a.xormask;
-    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN, AA>(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);              // maskfn: src/enums.h:136-140
         atomicAdd(&hist[bucket_of(key, bb)], 1u);
     });
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(K3_THREADS) void k3_scan_kernel(K3Args a) {
 // genomes with more than 2^l1bits buckets are split in two levels: here by the top l1bits of the bucket index -- the
 // coarse bucket's region is the union of its buckets' regions, reserved through the cursor of its first bucket -- and
 // then by the remaining bits, per coarse bucket, in k3_refine_kernel (<= 2^(12 - l1bits) fronts per workgroup there).
-template <bool FILT, bool WIN = false>
+template <bool FILT, bool WIN = false, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     // ONE LDS array: first the workgroup's count per (coarse) bucket, then (after one 64-bit reservation
     // per bucket) the next write position relative to the genome's first key -- a genome holds < 2^32
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3_scatter_kernel(K3Args a) {
     }
     __syncthreads();
     uint64_t *keys = (sb ? a.coarse : a.keys) + koff;
-    d2g_for_each_kmer<FILT, false, WIN>(a.km, [&](uint64_t x) {
+    d2g_for_each_kmer<FILT, false, WIN, AA>(a.km, [&](uint64_t x) {
         const uint64_t key = wang64(x ^ xormask);
         const uint32_t slot = atomicAdd(&pos[bucket_of(key, b1)], 1u);
         keys[slot] = key;
@@ -185,11 +185,11 @@ __global__ __launch_bounds__(K3_THREADS) void k3_refine_kernel(K3Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// COMPACT path (k <= 21, D2G_K3_COMPACT=1): the multi-split stores 4 bytes per k-mer and writes them coalesced.
+// COMPACT path (DNA k <= 21 -- key bits d2g_key_bits(k, alphabet) <= 42 --, D2G_K3_COMPACT=1): the multi-split stores 4 bytes per k-mer and writes them coalesced.
 //
 // Counting only needs a key that identifies the k-mer, so the split works on the 2k-bit k-mer x itself (the
 // masked key Wang(x ^ XORMASK) is a bijection of it and is computed once per DISTINCT k-mer in the main pass).
-// x = hi:lo with lo = 32 bits, hi = 2k - 32 <= 10 bits.  With m = lo * 0x9E3779B1 and t = the top bb bits of m,
+// x = hi:lo with lo = 32 bits, hi = key bits - 32 <= 10 bits (DNA: 2k - 32).  With m = lo * 0x9E3779B1 and t = the top bb bits of m,
 //     bucket = t ^ (hi << (bb - hb))                           (bb >= hb bucket bits per genome)
 // hi is recovered from (bucket, lo), so a bucket stores lo only; and within a bucket lo identifies the k-mer.
 // Lower bits of m select sub-ranges and table rounds.
@@ -232,11 +232,11 @@ struct K3cArgs {
     uint32_t *bucket_cnt;      // [TB]
     uint64_t *bucket_off;      // [TB+1]
     uint32_t *keys32;          // [total k-mers]
-    uint32_t hb;               // hi bits = max(0, 2k - 32)
+    uint32_t hb;               // hi bits = max(0, d2g_key_bits(k, alphabet) - 32): 2k - 32 for DNA
     uint32_t TB;
 };
 
-template <bool FILT, bool WIN = false>
+template <bool FILT, bool WIN = false, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void k3c_hist_kernel(K3cArgs a) {
     __shared__ uint32_t cnt[K3C_MAXB];
     const int tid = threadIdx.x;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_hist_kernel(K3cArgs a) {
     for (int it = 0; it < K1_CPT; ++it) {
         for (uint32_t i = tid; i < B; i += K1_THREADS) cnt[i] = 0;
         __syncthreads();
-        d2g_for_each_kmer_its<FILT, false, WIN>(a.km, it, it + 1, [&](uint64_t x) { atomicAdd(&cnt[k3c_bucket(x, bb, hb)], 1u); });
+        d2g_for_each_kmer_its<FILT, false, WIN, AA>(a.km, it, it + 1, [&](uint64_t x) { atomicAdd(&cnt[k3c_bucket(x, bb, hb)], 1u); });
         __syncthreads();
         // a tile holds at most 16384 k-mers: the counts fit u16
         uint16_t *dst = a.tile_cnt + ((size_t)blockIdx.x * K1_CPT + it) * K3C_MAXB;
@@ -303,7 +303,7 @@ struct K3cScatterLds {
     uint32_t wsum[K1_THREADS / 64];
 };
 
-template <bool FILT, bool WIN = false>
+template <bool FILT, bool WIN = false, bool AA = false>
 __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char k3c_lds_raw[];
     K3cScatterLds &L = *reinterpret_cast<K3cScatterLds *>(k3c_lds_raw);
@@ -330,7 +330,7 @@ __global__ __launch_bounds__(K1_THREADS) void k3c_scatter_kernel(K3cArgs a) {
         if (tid == K1_THREADS - 1) L.lbase[K3C_MAXB] = run;
         __syncthreads();
         if (total == 0) continue;                                    // uniform: every thread computed the same total
-        d2g_for_each_kmer_its<FILT, false, WIN>(a.km, it, it + 1, [&](uint64_t x) {
+        d2g_for_each_kmer_its<FILT, false, WIN, AA>(a.km, it, it + 1, [&](uint64_t x) {
             L.stage[atomicAdd(&L.lcur[k3c_bucket(x, bb, hb)], 1u)] = (uint32_t)x;
         });
         __syncthreads();
@@ -717,7 +717,7 @@ struct BmhArgs {
     const uint64_t *keys;        // generic path: bucketed 64-bit masked keys
     const uint32_t *keys32;      // compact path: bucketed 32-bit stored words (k3c_*)
     const uint32_t *g_bbits;     // compact path: [n] bucket bits of genome g
-    uint32_t hb;                 // compact path: hi bits = max(0, 2k - 32)
+    uint32_t hb;                 // compact path: hi bits = max(0, d2g_key_bits(k, alphabet) - 32): 2k - 32 for DNA
     uint64_t xormask;            // compact path: the masked key Wang(x ^ xormask) is formed per distinct k-mer here
     const uint64_t *bucket_off;
     const uint32_t *g_boff;
@@ -1276,7 +1276,7 @@ struct K3Host {
     std::vector<uint64_t> gsub;        // [n+1] first sub-range of genome g
     std::vector<uint32_t> gblk;        // [n+1] first launch-plan block of genome g (compact path)
     bool compact = false;              // k <= 21: 4-byte stored words + tile-sorted split (k3c_*)
-    uint32_t hb = 0;                   // compact path: hi bits = max(0, 2k - 32)
+    uint32_t hb = 0;                   // compact path: hi bits = max(0, d2g_key_bits(k, alphabet) - 32): 2k - 32 for DNA
     bool any_split = false;
     uint64_t total = 0;
     uint32_t TB = 0;
@@ -1293,7 +1293,8 @@ int k3_layout(d2g_ctx *ctx, const PackedRuns &in, K3Host &kh) {
     const int k = in.k;
     kh.gk.assign(n, 0);
     kh.gblk.assign(n + 1, 0);
-    kh.hb = k > 16 ? (uint32_t)(2 * k - 32) : 0u;
+    const int key_bits = d2g_key_bits(k, in.alphabet);             // DNA: 2k; a protein alphabet: the bit length of A^k - 1
+    kh.hb = key_bits > 32 ? (uint32_t)(key_bits - 32) : 0u;
     // the compact path (4-byte stored words, tile-sorted split) halves the chain's HBM traffic but is ~11 % slower end to
     // end (one Wang mix per distinct k-mer moves into the issue-bound main pass): opt-in with D2G_K3_COMPACT=1, k <= 21
     kh.compact = t.compact && kh.hb <= (uint32_t)K3C_MAXBBITS;
@@ -1460,11 +1461,14 @@ int K3Run::bucket(size_t g_lo, size_t g_hi) {
         const unsigned nb = (unsigned)nblk;
         const bool filt = km.ftab != nullptr;           // hist and scatter must drop the same k-mers: one switch for both
         const bool win = km.q > 1;                      // ... and walk the same ones: k-mers or minimizers
-        const auto hist = win ? (filt ? k3c_hist_kernel<true, true> : k3c_hist_kernel<false, true>) : (filt ? k3c_hist_kernel<true> : k3c_hist_kernel<false>);
+        const bool aa = d2g_km_protein(km);             // ... of the same alphabet (K1a: never with a window)
+        const auto hist = aa ? (filt ? k3c_hist_kernel<true, false, true> : k3c_hist_kernel<false, false, true>)
+                        : win ? (filt ? k3c_hist_kernel<true, true> : k3c_hist_kernel<false, true>) : (filt ? k3c_hist_kernel<true> : k3c_hist_kernel<false>);
         if (nb) hipLaunchKernelGGL(hist, dim3(nb), dim3(K1_THREADS), 0, s, kc);
         hipLaunchKernelGGL(k3c_scan_kernel, dim3((unsigned)n), dim3(K3_THREADS), 0, s, kc);
         if (nb) {
-            const auto scatter = win ? (filt ? k3c_scatter_kernel<true, true> : k3c_scatter_kernel<false, true>)
+            const auto scatter = aa ? (filt ? k3c_scatter_kernel<true, false, true> : k3c_scatter_kernel<false, false, true>)
+                               : win ? (filt ? k3c_scatter_kernel<true, true> : k3c_scatter_kernel<false, true>)
                                      : (filt ? k3c_scatter_kernel<true> : k3c_scatter_kernel<false>);
             D2G_HIP(ctx, hipFuncSetAttribute((const void *)scatter, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(K3cScatterLds)));
             hipLaunchKernelGGL(scatter, dim3(nb), dim3(K1_THREADS), sizeof(K3cScatterLds), s, kc);
@@ -1476,8 +1480,11 @@ int K3Run::bucket(size_t g_lo, size_t g_hi) {
     a.km.blk0 = blk_lo; a.g0 = (uint32_t)g_lo;
     const bool filt = km.ftab != nullptr;               // hist and scatter must drop the same k-mers: one switch for both
     const bool win = km.q > 1;                          // ... and walk the same ones: k-mers or minimizers
-    const auto hist = win ? (filt ? k3_hist_kernel<true, true> : k3_hist_kernel<false, true>) : (filt ? k3_hist_kernel<true> : k3_hist_kernel<false>);
-    const auto scatter = win ? (filt ? k3_scatter_kernel<true, true> : k3_scatter_kernel<false, true>)
+    const bool aa = d2g_km_protein(km);                 // ... of the same alphabet (K1a: never with a window)
+    const auto hist = aa ? (filt ? k3_hist_kernel<true, false, true> : k3_hist_kernel<false, false, true>)
+                    : win ? (filt ? k3_hist_kernel<true, true> : k3_hist_kernel<false, true>) : (filt ? k3_hist_kernel<true> : k3_hist_kernel<false>);
+    const auto scatter = aa ? (filt ? k3_scatter_kernel<true, false, true> : k3_scatter_kernel<false, false, true>)
+                       : win ? (filt ? k3_scatter_kernel<true, true> : k3_scatter_kernel<false, true>)
                              : (filt ? k3_scatter_kernel<true> : k3_scatter_kernel<false>);
     if (nb) hipLaunchKernelGGL(hist, dim3(nb), dim3(K1_THREADS), 0, s, a);
     hipLaunchKernelGGL(k3_scan_kernel, dim3((unsigned)(g_hi - g_lo)), dim3(K3_THREADS), 0, s, a);

@@ -30,7 +30,12 @@ struct KmerArgs {
     const uint32_t *blk_run_lo;
     const uint32_t *blk_run_hi;
     int k;
-    int canon;
+    // K1a, a protein alphabet: an amino-acid k-mer has no canonical form, so the alphabet's size A (6, 8, 14 or 20) stands where
+    // canon does -- read under this name only by the AA instantiations of the walker below; a DNA batch holds 0 or 1 here and every
+    // field is where it was.  The HOST only ever writes and reads `canon` (d2g_plan_kmer_args, d2g_k1.h, stores 0 / 1 for DNA and A for
+    // a protein alphabet; d2g_km_protein() below tells them apart by canon > 1); `asize` is read on the device alone, from the byte copy
+    // of the struct that a kernel launch makes -- no member is read on the side that wrote the other.
+    union { int canon; uint32_t asize; };
     uint32_t blk0;                 // first launch-plan block of this launch (a launch may cover a sub-range of the plan)
     // K1w, -w > k: k-mers per window, q = w - k + 1 (1 = no window).  Read only by the WIN instantiations of the walker below; it sits
     // in what was padding in front of ftab, so every other field is where it was.
@@ -41,6 +46,8 @@ struct KmerArgs {
     uint32_t fmask;                // slots - 1 (a power of two, >= twice the k-mers put in: the probe always ends)
     uint32_t fshift;               // 64 - log2(slots)
 };
+
+inline bool d2g_km_protein(const KmerArgs &a) { return a.canon > 1; }
 
 // the all-ones k-mer (T x 32, forward) is a legal key and the value of a free slot: its membership is a flag behind the table
 constexpr uint64_t D2G_FILTER_EMPTY = ~0ull;
@@ -170,6 +177,107 @@ __device__ __forceinline__ void d2g_for_each_minimizer_its(const KmerArgs &a, in
     }
 }
 
+// K1a: the amino-acid walker (spec D2G-AA; the reference's bns::Encoder over a protein alphabet, restated: parity
+// unpinned).  The stream holds ONE BYTE per residue, its code c < A; the key of residues c_0 .. c_{k-1} is sum c_j A^(k-1-j), below
+// A^k <= 2^64.  A chunk is K1_CHUNK consecutive k-mer starts of one run, as for DNA.  The lane keeps y = the value of the k - 1
+// residues in front of the next one; a step is
+//     x = y * A + in          the k-mer that ends at `in` (y < A^(k-1), so x < A^k: nothing wraps)
+//     y = x - out * A^(k-1)   its first residue `out` leaves
+// `in` (residue p + k - 1 + e) and `out` (residue p + e) come from two windows of sixteen bytes, each five dwords aligned to the run's
+// byte offset with alignbit; a run starts at any byte of a dword.  A and A^(k-1) are run-time values, uniform over the launch.
+// Reads: the bytes of the lane's own k-mers and at most 19 bytes behind the run's last one (the stream's 64-byte pad covers them).
+// FILT as for DNA: sixteen k-mers, then sixteen home-slot loads in flight.  There is no canonical form, no HITS and no WIN.
+template <bool FILT, class F>
+__device__ __forceinline__ void d2g_for_each_aa_kmer_its(const KmerArgs &a, int it0, int it1, F &&f) {
+    const int tid = threadIdx.x;
+    const uint32_t b = blockIdx.x + a.blk0;
+    const uint64_t c0 = a.blk_chunk0[b];
+    const uint32_t nc = a.blk_nchunks[b];
+    const uint32_t rlo = a.blk_run_lo[b], rhi = a.blk_run_hi[b];
+    const int k = a.k;
+    const uint64_t A = a.asize;
+    uint64_t apow = 1;
+    for (int j = 1; j < k; ++j) apow *= A;
+
+    for (int it = it0; it < it1; ++it) {
+        const uint32_t ci_blk = it * K1_THREADS + tid;
+        if (ci_blk >= nc) break;
+        const uint64_t c = c0 + ci_blk;
+        uint32_t lo = rlo, hi = rhi;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (a.run_chunk_off[mid] <= c) lo = mid; else hi = mid;
+        }
+        const uint64_t ci = c - a.run_chunk_off[lo];
+        const uint64_t nk = (uint64_t)a.run_len[lo] - k + 1;
+        const uint64_t p = a.run_start[lo] + ci * K1_CHUNK;       // first k-mer start (residue = byte index)
+        const uint64_t left = nk - ci * K1_CHUNK;
+        const int n = left < (uint64_t)K1_CHUNK ? (int)left : K1_CHUNK;
+
+        const uint32_t *wo = a.packed + (p >> 2);                 // the window that leaves: residues [p, p + 64)
+        const uint32_t sho = (uint32_t)(p & 3) * 8;
+        // warm-up: residues [p, p + k - 1), at most 23: whole dwords of four, then the one to three that are left.  Two short
+        // loops with uniform trip counts and not an unrolled, predicated ladder: that kept 24 conditions alive in SGPRs
+        uint64_t y = 0;
+        {
+            const int full = (k - 1) >> 2, rest = (k - 1) & 3;
+            uint32_t wprev = wo[0];
+#pragma unroll 1
+            for (int g = 0; g < full; ++g) {
+                const uint32_t wnext = wo[g + 1];
+                const uint32_t W = fsr(wnext, wprev, sho);
+                wprev = wnext;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y = y * A + ((W >> (8 * e)) & 0xffu);
+            }
+            if (rest) {
+                uint32_t W = fsr(wo[full + 1], wprev, sho);
+#pragma unroll 1
+                for (int e = 0; e < rest; ++e) { y = y * A + (W & 0xffu); W >>= 8; }
+            }
+        }
+        const uint64_t q = p + (uint64_t)(k - 1);                 // the window that enters: residues [q, q + 64)
+        const uint32_t *wn = a.packed + (q >> 2);
+        const uint32_t shn = (uint32_t)(q & 3) * 8;
+#pragma unroll 1
+        for (int wi = 0; wi < 4; ++wi) {
+            const int ebase = wi * 16;
+            if (ebase >= n) break;
+            uint32_t I[4], O[4];
+            {
+                const uint32_t *w = wn + 4 * wi;
+                const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+                I[0] = fsr(w1, w0, shn); I[1] = fsr(w2, w1, shn); I[2] = fsr(w3, w2, shn); I[3] = fsr(w4, w3, shn);
+            }
+            {
+                const uint32_t *w = wo + 4 * wi;
+                const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+                O[0] = fsr(w1, w0, sho); O[1] = fsr(w2, w1, sho); O[2] = fsr(w3, w2, sho); O[3] = fsr(w4, w3, sho);
+            }
+            if constexpr (FILT) {
+                uint64_t xs[16], vs[16];
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    const uint64_t x = y * A + ((I[e >> 2] >> (8 * (e & 3))) & 0xffu);
+                    y = x - (uint64_t)((O[e >> 2] >> (8 * (e & 3))) & 0xffu) * apow;
+                    xs[e] = x;
+                    vs[e] = ebase + e < n ? a.ftab[d2g_filter_slot(x, a.fshift)] : 0;
+                }
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    if (ebase + e < n && !d2g_filter_hit(a, xs[e], vs[e])) f(xs[e]);
+                continue;
+            }
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const uint64_t x = y * A + ((I[e >> 2] >> (8 * (e & 3))) & 0xffu);
+                y = x - (uint64_t)((O[e >> 2] >> (8 * (e & 3))) & 0xffu) * apow;
+                if (ebase + e < n) f(x);
+            }
+        }
+    }
+}
+
 // f(x) once per k-mer of the chunks this lane owns in workgroup blockIdx.x; x = canonical
 // (min(fwd, revcomp)) or forward 2-bit k-mer.  A lane owns chunk (it * K1_THREADS + tid).
 // IT0 <= it < IT1: the passes ("tiles" of K1_THREADS chunks = K1_THREADS * K1_CHUNK k-mers) of the workgroup to walk
@@ -179,8 +287,15 @@ __device__ __forceinline__ void d2g_for_each_minimizer_its(const KmerArgs &a, in
 // does nothing.  The other instantiations stay the code they were (profiles/screen_resource_usage.txt)
 // WIN: the fourth, K1w -- f sees the minimizer of every window position instead (d2g_for_each_minimizer_its above), under either of
 // the other two flags.  The unwindowed instantiations stay the code they were (profiles/window_resource_usage.txt)
-template <bool FILT = false, bool HITS = false, bool WIN = false, class F>
+// AA: the fifth, K1a -- f sees the amino-acid k-mers of a byte-per-residue stream (d2g_for_each_aa_kmer_its above), under FILT or
+// not.  The DNA instantiations stay the code they were (profiles/protein_resource_usage.txt)
+template <bool FILT = false, bool HITS = false, bool WIN = false, bool AA = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0, int it1, F &&f) {
+    if constexpr (AA) {
+        static_assert(!HITS && !WIN, "the amino-acid walker knows neither the hit mode nor a window");
+        d2g_for_each_aa_kmer_its<FILT>(a, it0, it1, static_cast<F &&>(f));
+        return;
+    }
     if constexpr (WIN) {
         d2g_for_each_minimizer_its<FILT, HITS>(a, it0, it1, static_cast<F &&>(f));
         return;
@@ -277,8 +392,8 @@ __device__ __forceinline__ void d2g_for_each_kmer_its(const KmerArgs &a, int it0
     }
 }
 
-template <bool FILT = false, bool HITS = false, bool WIN = false, class F>
+template <bool FILT = false, bool HITS = false, bool WIN = false, bool AA = false, class F>
 __device__ __forceinline__ void d2g_for_each_kmer(const KmerArgs &a, F &&f) {
     static_assert(FILT || !HITS, "the hit mode walks a table");
-    d2g_for_each_kmer_its<FILT, HITS, WIN>(a, 0, K1_CPT, static_cast<F &&>(f));
+    d2g_for_each_kmer_its<FILT, HITS, WIN, AA>(a, 0, K1_CPT, static_cast<F &&>(f));
 }

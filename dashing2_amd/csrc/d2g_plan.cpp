@@ -1,5 +1,6 @@
 // d2g_plan.cpp -- the checks of a packed run stream and the launch plan over it (d2g_plan.h): plain host arithmetic.
 #include "d2g_plan.h"
+#include "d2g_alphabet.h"
 #include "../../include/d2g.h"
 #include <algorithm>
 #include <cstring>
@@ -12,6 +13,14 @@ int d2g_plan_build(const PackedRuns &in, PlanHost &p, std::string &err) {
     const size_t nrun = in.nrun, n = in.n;
     const int k = in.k;
     if (!in.genome_run_off || (nrun && !(in.run_len && in.run_start))) return refuse(err, "oph plan: null table");
+    if (in.alphabet != D2G_ALPHABET_DNA) {
+        // K1a: what a protein alphabet refuses, before anything else is looked at
+        if (!d2g_is_protein(in.alphabet)) return refuse(err, "unknown alphabet");
+        if (in.canon != 0) return refuse(err, "a protein alphabet has no canonical k-mers: canon must be 0");
+        if (k >= 1 && k > d2g_alphabet_max_k_of(in.alphabet))
+            return refuse(err, "k exceeds the alphabet's largest exact k (20 letters: 14, 14: 16, 8: 21, 6: 24)", D2G_ERR_UNSUPPORTED);
+        if (in.w > k) return refuse(err, "a window (-w > k) with a protein alphabet: the windowed walker is DNA only", D2G_ERR_UNSUPPORTED);
+    }
     if (k < 1 || k > 32) return refuse(err, "k must be in [1,32] (exact 2-bit encoding path)", D2G_ERR_UNSUPPORTED);
     if (d2g_window_q(k, in.w) > D2G_WINDOW_MAX_Q)
         return refuse(err, "window too wide: -w may exceed k by at most 4095 (a window of 4096 k-mers)", D2G_ERR_UNSUPPORTED);
@@ -48,7 +57,8 @@ int d2g_plan_check_tail(const PackedRuns &in, std::string &err) {
     if (!in.run_start || !in.run_len) return refuse(err, "oph plan: null table");
     uint64_t maxend = 0;
     for (size_t r = 0; r < in.nrun; ++r) maxend = std::max<uint64_t>(maxend, in.run_start[r] + in.run_len[r]);
-    if (in.packed_bytes < (maxend + 3) / 4 + 64) return refuse(err, "packed stream lacks the 64-byte tail pad");
+    const uint64_t stream_bytes = in.alphabet != D2G_ALPHABET_DNA ? maxend : (maxend + 3) / 4;     // a byte per residue, four bases per byte
+    if (in.packed_bytes < stream_bytes + 64) return refuse(err, "packed stream lacks the 64-byte tail pad");
     return D2G_OK;
 }
 
@@ -65,6 +75,21 @@ int d2g_plan_check_count_range(const PackedRuns &in, std::string &err) {
 }
 
 extern "C" uint64_t d2g_run_emissions(uint64_t len, int k, int w) { return k >= 1 ? d2g_run_emissions_of(len, k, w) : 0; }
+
+extern "C" int d2g_alphabet_size(int alphabet) { return d2g_alphabet_size_of(alphabet); }
+extern "C" int d2g_alphabet_max_k(int alphabet) { return d2g_alphabet_max_k_of(alphabet); }
+extern "C" int d2g_alphabet_code(int alphabet, int byte) { return byte >= 0 && byte < 256 ? d2g_alphabet_code_of(alphabet, (unsigned char)byte) : -1; }
+extern "C" const char *d2g_alphabet_name(int alphabet) {
+    switch (alphabet) {
+    case D2G_ALPHABET_DNA: return "DNA";
+    case D2G_ALPHABET_PROTEIN20: return "PROTEIN20";
+    case D2G_ALPHABET_PROTEIN_3BIT: return "PROTEIN_3BIT";
+    case D2G_ALPHABET_PROTEIN_14: return "PROTEIN_14";
+    case D2G_ALPHABET_PROTEIN_6: return "PROTEIN_6";
+    default: return "";
+    }
+}
+extern "C" int d2g_key_bits(int k, int alphabet) { return d2g_key_bits_of(k, alphabet); }
 
 PlanLayout d2g_plan_layout(size_t nrun, size_t nblk) {
     PlanLayout l{};

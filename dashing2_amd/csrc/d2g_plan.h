@@ -23,6 +23,8 @@ struct PackedRuns {
     size_t n;
     int k, canon;
     int w = 0;                                      // -w: only the minimizer of every window of w bases is walked; <= k (0 included): every k-mer
+    int alphabet = 0;                               // K1a: a protein D2G_ALPHABET_* reads `packed` as ONE BYTE per residue (its code); starts and
+                                                    // lengths then count residues, canon must be 0 and there is no window
 };
 
 // K1w.  The widest window: q = w - k + 1 <= D2G_WINDOW_MAX_Q k-mers per window (include/d2g.h; a wider one is D2G_ERR_UNSUPPORTED)
@@ -45,8 +47,8 @@ struct PlanHost {
 // Each returns a D2G_* status and, with a refusal, its text in `err` (a caller with a context copies it to last_error).
 // The plan of `in` (its tables only: packed is not looked at).  The kernels index with what this writes and check nothing.
 int d2g_plan_build(const PackedRuns &in, PlanHost &p, std::string &err);
-// packed_bytes >= (max(run_start + run_len) + 3) / 4 + 64: all that keeps the walker's window reads (up to 20 bytes past a
-// chunk's first word) inside the buffer
+// packed_bytes >= (max(run_start + run_len) + 3) / 4 + 64 (a protein alphabet: max(run_start + run_len) + 64, a byte per symbol):
+// all that keeps the walker's window reads (up to 20 bytes past a chunk's first word) inside the buffer
 int d2g_plan_check_tail(const PackedRuns &in, std::string &err);
 // the counting forms with host outputs return uint32 counts without the reference's wrap (idcounts() copies doubles into
 // uint32, oph.h:272-277): a genome that could reach 2^32 emissions is refused.  Tables that d2g_plan_build will reject (null, not

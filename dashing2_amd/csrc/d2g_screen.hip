@@ -271,6 +271,7 @@ int d2g_screen_set_fed(d2g_ctx *ctx, d2g_screen *sc, size_t row, uint64_t nkmers
 
 int d2g_screen_add_dev(d2g_ctx *ctx, d2g_screen *sc, const d2g_oph_plan *plan, const uint8_t *packed_dev, const uint32_t *genome_row, void *stream) {
     if (!ctx || !sc || !plan) return D2G_ERR_INVALID;
+    if (plan->alphabet != D2G_ALPHABET_DNA) { ctx->last_error = "screen: a k-mer database is DNA; a plan under a protein alphabet cannot be screened"; return D2G_ERR_UNSUPPORTED; }
     const int canon = sc->canon;                                   // a plan carries k, not the canonicalisation: the screen's holds
     if (int rc = screen_check(ctx, sc, plan->k, canon)) return rc;
     std::vector<uint64_t> add;
@@ -284,6 +285,7 @@ int d2g_sketcher_run_screen(d2g_sketcher *sk, const uint8_t *packed, size_t pack
                             size_t nrun, const uint64_t *genome_run_off, size_t n, int k, int canon, d2g_screen *sc, const uint32_t *genome_row) {
     if (!sk || !sc) return D2G_ERR_INVALID;
     d2g_ctx *ctx = sk->ctx;
+    if (sk->alphabet != D2G_ALPHABET_DNA) { ctx->last_error = "screen: a k-mer database is DNA; a sketcher under a protein alphabet cannot screen"; return D2G_ERR_UNSUPPORTED; }
     const PackedRuns in{packed, packed_bytes, run_start, run_len, nrun, genome_run_off, n, k, canon};
     if (int rc = screen_check(ctx, sc, k, canon)) return rc;        // before the stage touches the stream or the buffers
     std::vector<uint64_t> add;

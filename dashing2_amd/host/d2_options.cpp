@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_PROTEIN, OPT_PROTEIN6, OPT_PROTEIN8, OPT_PROTEIN14, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -44,6 +44,10 @@ void sketch_usage() {
                          "  -w/--window-size w     w > k: only the minimizer of every window of w bases (the k-mer x of its w - k + 1 with the smallest\n"
                          "                         x ^ 0xe37e28c4271b5a2d, once per window position) is sketched, counted or filtered;         \n"
                          "                         w <= k: every k-mer.  Cache and set file names carry .w<w>; at most w - k = 4095\n"
+                         "  --protein/--protein20/--enable-protein   amino-acid k-mers over the 20 letters (k <= 14, the default k);\n"
+                         "  --protein14 / --protein8 / --protein6    ... over the reduced alphabets SE-B(14) (k <= 16), SE-B(8) (k <= 21), SE-B(6) (k <= 24).\n"
+                         "                         No canonical form (as -C); any other letter ends a run as N does; file names carry PROTEIN20 /\n"
+                         "                         PROTEIN_14 / PROTEIN_3BIT / PROTEIN_6 where DNA stands.  Not with -w > k, k above the limit, several GPUs\n"
                          "  -F/--ffile paths.txt -Q/--qfile queries.txt  -o/--outfile stacked.bin\n"
                          "  --cmpout/--distout/--cmp-outfile out   --phylip   --binary-output   --asymmetric-all-pairs\n"
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
@@ -163,6 +167,8 @@ int parse_options(int argc, char **argv, Options &o) {
         {"save-kmers", no_argument, 0, 's'}, {"save-kmercounts", no_argument, 0, 'N'},
         {"filterset", required_argument, 0, OPT_FILTERSET},
         {"set", no_argument, 0, OPT_SET}, {"countdict", no_argument, 0, 'J'},
+        {"protein", no_argument, 0, OPT_PROTEIN}, {"protein20", no_argument, 0, OPT_PROTEIN}, {"enable-protein", no_argument, 0, OPT_PROTEIN},
+        {"protein6", no_argument, 0, OPT_PROTEIN6}, {"protein8", no_argument, 0, OPT_PROTEIN8}, {"protein14", no_argument, 0, OPT_PROTEIN14},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
     std::vector<struct option> all(longopts, longopts + sizeof(longopts) / sizeof(longopts[0]) - 1);
@@ -247,6 +253,11 @@ int parse_options(int argc, char **argv, Options &o) {
             case OPT_SET: case 'H': gave_set = true; break;                          // options.h:348
             case 'J': gave_countdict = true; break;                                 // options.h:349
             case OPT_FILTERSET: o.filterset_arg = optarg; break;                    // options.h:509-511
+            // PROT_FIELD, options.h:328-331: the alphabet, canon = false, the reference's one stderr line
+            case OPT_PROTEIN: o.alphabet = D2G_ALPHABET_PROTEIN20; std::fprintf(stderr, "Parsing 20-character amino acid sequences\n"); break;
+            case OPT_PROTEIN6: o.alphabet = D2G_ALPHABET_PROTEIN_6; std::fprintf(stderr, "Parsing amino acid sequences with 6-letter compressed alphabet.\n"); break;
+            case OPT_PROTEIN14: o.alphabet = D2G_ALPHABET_PROTEIN_14; std::fprintf(stderr, "Parsing amino acid sequences with 14-letter compressed alphabet.\n"); break;
+            case OPT_PROTEIN8: o.alphabet = D2G_ALPHABET_PROTEIN_3BIT; std::fprintf(stderr, "Using 3-bit protein encoding\n"); break;
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
             case OPT_UNSUPPORTED:
@@ -258,7 +269,8 @@ int parse_options(int argc, char **argv, Options &o) {
                 return 1 + 1;
         }
     }
-    if (o.k < 0) o.k = 32;                                     // nregperitem(DNA): sketch_main.cpp:70, options.h:474
+    if (o.alphabet) o.canon = false;                           // whatever else was given (options.h:328-331; d2.cpp:100-102)
+    if (o.k < 0) o.k = o.alphabet ? d2g_alphabet_max_k(o.alphabet) : 32;   // nregperitem(rht): sketch_main.cpp:70, options.h:474
     if (o.nt < 0) {                                            // sketch_main.cpp:71-74
         if (const char *s = std::getenv("OMP_NUM_THREADS")) o.nt = std::max(std::atoi(s), 1);
     }
@@ -333,6 +345,26 @@ int parse_options(int argc, char **argv, Options &o) {
             return 1 + 1;
         }
         o.filterset = o.filterset_arg.substr(0, i);
+    }
+    if (o.alphabet && !o.presketched) {                        // K1a: said here, before a GPU is asked for; the library refuses the first two as well
+        const char *e = std::getenv("D2G_DEVICES");
+        if (o.k > d2g_alphabet_max_k(o.alphabet)) {
+            std::fprintf(stderr, "dashing2 (MI355X): k = %d > %d with %s uses the reference's rolling-hash encoder, as k > 32 does for DNA; "
+                                 "it is outside this build's hot-path scope.\n", o.k, d2g_alphabet_max_k(o.alphabet), d2g_alphabet_name(o.alphabet));
+            return 1 + 1;
+        }
+        if (o.w > o.k) {
+            std::fprintf(stderr, "dashing2 (MI355X): -w %d > -k %d with %s: windowed minimizers of amino-acid k-mers are outside this build's "
+                                 "hot-path scope (the windowed walker is DNA only).\n", o.w, o.k, d2g_alphabet_name(o.alphabet));
+            return 1 + 1;
+        }
+        if (e && *e && (std::strcmp(e, "all") == 0 || std::strchr(e, ','))) {
+            std::fprintf(stderr, "dashing2 (MI355X): %s together with D2G_DEVICES naming several GPUs is outside the hot-path scope of this build "
+                                 "(amino-acid inputs are sketched on one GPU).\n", d2g_alphabet_name(o.alphabet));
+            return 1 + 1;
+        }
+        if (std::getenv("D2G_DEVICE_PARSE") && !std::getenv("D2G_HOST_PARSE"))
+            std::fprintf(stderr, "[d2g] D2G_DEVICE_PARSE ignored with %s: the device parser reads DNA, the host parser runs\n", d2g_alphabet_name(o.alphabet));
     }
     if (o.k > 32) {
         std::fprintf(stderr, "dashing2 (MI355X): k = %d > 32 uses the reference's rolling-hash encoder "

@@ -49,6 +49,8 @@ struct Options {
     mutable uint64_t filterset_size = 0;  // ... of this many k-mer occurrences: FilterSet::data_.size(), printed by to_string()
     int exact = 0;                        // --set/-H = 1 (FULL_MMER_SET), --countdict/-J = 2 (FULL_MMER_COUNTDICT) (options.h:153,348-349): no sketch, the exact
                                           // k-mer set / count dictionary of every input; kept iff count > count_threshold; cmp gives exact values
+    int alphabet = 0;                     // --protein/--protein20/--enable-protein = 2, --protein8 = 3, --protein14 = 4, --protein6 = 5 (options.h:143-148,328-331;
+                                          // ids of python/parse.py:8-23 = D2G_ALPHABET_*): amino-acid k-mers (K1a), canon forced off, default k = the alphabet's largest
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -15,9 +15,10 @@
 
 namespace d2h {
 
-struct ExactNameOpts { int k; bool canon; uint64_t seedseed; unsigned count_threshold; std::string outprefix; int w = 0; };
+struct ExactNameOpts { int k; bool canon; uint64_t seedseed; unsigned count_threshold; std::string outprefix; int w = 0;
+                       std::string alphabet = "DNA"; };      // bns::to_string(rht_): the alphabet's name (d2g_alphabet_name), fastxmerge.cpp:117
 
-// <path>[.seed<s>][.rc_canon].k<k>[.w<w>][.ct_threshold<c>].FullMmerSet.DNA.kmerset64 (.w<w> when w > k, fastxmerge.cpp:87-90) -- no .sketchsize part (fastxmerge.cpp:85), and
+// <path>[.seed<s>][.rc_canon].k<k>[.w<w>][.ct_threshold<c>].FullMmerSet.<DNA | PROTEIN20 | ...>.kmerset64 (.w<w> when w > k, fastxmerge.cpp:87-90) -- no .sketchsize part (fastxmerge.cpp:85), and
 // FullMmerSet for BOTH modes (fastxsketch.cpp:313 passes iskmer for the count dictionary, fastxmerge.cpp:112-114)
 inline std::string exact_key_file(const ExactNameOpts &o, const std::string &path) {
     std::string ret = path.substr(0, path.find_first_of(' '));
@@ -30,7 +31,7 @@ inline std::string exact_key_file(const ExactNameOpts &o, const std::string &pat
     ret += ".k" + std::to_string(o.k);
     if (o.w > o.k) ret += ".w" + std::to_string(o.w);
     if (o.count_threshold > 0) ret += ".ct_threshold" + std::to_string(int(o.count_threshold));
-    return ret + ".FullMmerSet.DNA.kmerset64";
+    return ret + ".FullMmerSet." + o.alphabet + ".kmerset64";
 }
 // the key file's name up to its last '.' plus .kmercounts.f64
 inline std::string exact_count_file(const std::string &key_file) { return key_file.substr(0, key_file.find_last_of('.')) + ".kmercounts.f64"; }

@@ -55,13 +55,13 @@ inline GroupPlan plan_groups(const std::vector<std::string> &lines, size_t limit
     return p;
 }
 
-struct IngestConfig { int k; size_t readers, nbufs, buf_bytes, max_ready; };
+struct IngestConfig { int k; size_t readers, nbufs, buf_bytes, max_ready; int alphabet = 0; };    // alphabet: D2G_ALPHABET_* of the host packers
 // The sizes `dashing2 sketch` runs with.  (A byte-bounded queue deep enough to parse all of 1000 x 5 Mbp before the first launch,
 // with four device threads to drain it, was measured: the 112 freshly allocated packers fault in 1.3 GB and the pipeline went
 // 0.21 -> 0.34 s.  The recycled pool stays.)
-inline IngestConfig ingest_config(const GroupPlan &plan, int k, size_t workers, bool host_parser_only) {
+inline IngestConfig ingest_config(const GroupPlan &plan, int k, size_t workers, bool host_parser_only, int alphabet = 0) {
     IngestConfig c;
-    c.k = k;
+    c.k = k; c.alphabet = alphabet;
     c.readers = std::max<size_t>(1, std::min<size_t>({workers, plan.groups.size(), size_t(192)}));
     c.max_ready = 2 * c.readers + 2;
     size_t max_group = 16;
@@ -138,7 +138,7 @@ class IngestPipeline {
             std::lock_guard<std::mutex> lk(mu_);
             if (!pool_.empty()) { r.sp = pool_.back(); pool_.pop_back(); }
         }
-        int rc = r.sp ? int(D2G_OK) : d2g_seqpack_create(cfg_.k, &r.sp);
+        int rc = r.sp ? int(D2G_OK) : d2g_seqpack_create_alphabet(cfg_.k, cfg_.alphabet, &r.sp);
         for (size_t x = plan_.groups[r.g].first; rc == D2G_OK && x < plan_.groups[r.g].second; ++x) {
             rc = d2g_seqpack_add_path(r.sp, lines_[x].c_str());
             if (rc) bad = lines_[x];

@@ -32,7 +32,7 @@ std::string makedest(const Options &o, const std::string &path) {
     }
     if (o.sspace != SPACE_SET) ret += ".ExactCounting";   // to_string(ct()), src/enums.cpp:47; fastxmerge.cpp:96-100
     ret += o.sspace == SPACE_SET ? ".SetSpace" : ".MultisetSpace";   // to_string(sspace), src/enums.cpp:40-46
-    ret += ".DNA";                                        // bns::to_string(rht_) (absent bonsai; expected "DNA")
+    ret += std::string(".") + d2g_alphabet_name(o.alphabet);   // bns::to_string(rht_) (absent bonsai; "DNA", or the names of python/parse.py:8-23)
     // to_suffix, src/enums.cpp:28-38, gives ".bmh" for BagMinHash.  Multiset sketches of this build follow the repository's
     // BMH-D2G spec (the reference's sketch/bmh.h is absent): same layout, incomparable register values.  They get their own
     // suffix so that a --cache directory shared with a stock dashing2 can never mix the two silently.
@@ -63,7 +63,7 @@ void write_cached(const std::string &path, const double *sig, double card, size_
 // without one the reference keeps them in memory and drops them
 bool saves_kmers(const Options &o) { return o.save_kmers && !o.outfile.empty() && o.outfile != "-" && o.outfile != "/dev/stdout"; }
 
-// <out>.kmer64: [u32 dtype = DNA | canon << 8][u32 S][u32 k][u32 w][u64 seedseed], then N x S u64 (fastxsketch.cpp:245-259,619-620);
+// <out>.kmer64: [u32 dtype = alphabet id (DNA 0) | canon << 8][u32 S][u32 k][u32 w][u64 seedseed], then N x S u64 (fastxsketch.cpp:245-259,619-620);
 // <out>.kmer64.names.txt: the input lines (:260-263); <out>.kmercounts.f64: N x S float32 (sketch_core.cpp:162-171)
 void write_kmer_files(const Result &res, const Options &o) {
     if (res.kmers.empty() && res.kmercounts.empty()) return;
@@ -71,7 +71,7 @@ void write_kmer_files(const Result &res, const Options &o) {
     if (!res.kmers.empty()) {
         const std::string kf = o.outfile + ".kmer64", nf = kf + ".names.txt";
         if (!(fp = std::fopen(kf.c_str(), "wb"))) die("Failed to open " + kf + " for writing.");
-        const uint32_t hdr[4] = {uint32_t(0) | (uint32_t(o.canon) << 8), uint32_t(o.sketchsize), uint32_t(o.k), uint32_t(o.w < 0 ? o.k : o.w)};
+        const uint32_t hdr[4] = {uint32_t(o.alphabet) | (uint32_t(o.canon) << 8), uint32_t(o.sketchsize), uint32_t(o.k), uint32_t(o.w < 0 ? o.k : o.w)};
         const uint64_t seed = o.seedseed;
         if (std::fwrite(hdr, 4, 4, fp) != 4 || std::fwrite(&seed, 8, 1, fp) != 1 ||
             std::fwrite(res.kmers.data(), 8, res.kmers.size(), fp) != res.kmers.size()) die("Failed to write " + kf);
@@ -123,7 +123,7 @@ struct JobFilter {
     bool reported = false;                                // --gpu-stats "filter": the first table built speaks for all
     explicit JobFilter(const Options &o) {
         if (o.filterset.empty()) return;
-        check(nullptr, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
+        check(nullptr, d2g_seqpack_create_alphabet(o.k, o.alphabet, &sp), "d2g_seqpack_create");    // the filter file under the job's alphabet
         if (d2g_seqpack_add_path(sp, o.filterset.c_str()) != D2G_OK) die("Failed to open file " + o.filterset + " for reading");   // d2.cpp:63
         o.filterset_built = true;
         o.filterset_size = 0;                             // occurrences: the reference sorts but never deduplicates (filterset.h:82);
@@ -137,8 +137,12 @@ struct JobFilter {
     d2g_kmer_filter *attach(d2g_ctx *ctx, d2g_sketcher *sk, const Options &o) {
         if (!sp) return nullptr;
         d2g_kmer_filter *f = nullptr;
-        check(ctx, d2g_kmer_filter_create_windowed(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp),
-                                                   d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp), o.k, o.canon, o.w, &f), "d2g_kmer_filter_create");
+        if (o.alphabet)
+            check(ctx, d2g_kmer_filter_create_alphabet(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp),
+                                                       d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp), o.k, o.alphabet, &f), "d2g_kmer_filter_create");
+        else
+            check(ctx, d2g_kmer_filter_create_windowed(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp),
+                                                       d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp), o.k, o.canon, o.w, &f), "d2g_kmer_filter_create");
         check(ctx, d2g_sketcher_set_filter(sk, f), "d2g_sketcher_set_filter");
         std::lock_guard<std::mutex> lk(mu);
         if (g_stats.on && !reported) {
@@ -191,7 +195,7 @@ struct DeviceSide {
             if (rc == D2G_OK) check(ctx, d2g_sketcher_ingested_runs(sk, &run_start, &run_len, &nrun, &goff, nullptr, &nb), "d2g_sketcher_ingested_runs");
             pipe.release_buffer(r);
             if (rc == D2G_ERR_UNSUPPORTED) {                            // e.g. a '+' line further down: the host parser takes the group
-                check(ctx, d2g_seqpack_create(o.k, &r.sp), "d2g_seqpack_create");
+                check(ctx, d2g_seqpack_create_alphabet(o.k, o.alphabet, &r.sp), "d2g_seqpack_create");
                 for (size_t x = b; x < e; ++x)
                     if (d2g_seqpack_add_path(r.sp, o.paths[todo[x]].c_str()) != D2G_OK) die("Failed to open " + o.paths[todo[x]]);
             } else check(ctx, rc, "d2g_sketcher_ingest_fasta");
@@ -235,6 +239,7 @@ struct DeviceSide {
         d2g_sketcher *sk = nullptr;
         check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
         check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
+        check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");  // --protein...: amino-acid k-mers (K1a)
         d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);              // before the first group
         double gpu = 0; uint64_t bases = 0; size_t ndevg = 0, nhostg = 0;
         for (IngestGroup r; pipe.next(r);) {
@@ -311,8 +316,9 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
     const auto &groups = plan.groups;
     const double t_setup = now();
     const std::vector<int> devs = job_devices(o);
-    const bool force_host = std::getenv("D2G_DEVICE_PARSE") == nullptr || std::getenv("D2G_HOST_PARSE") != nullptr || devs.size() > 1;
-    const IngestConfig cfg = ingest_config(plan, o.k, size_t(o.workers()), force_host);
+    const bool force_host = std::getenv("D2G_DEVICE_PARSE") == nullptr || std::getenv("D2G_HOST_PARSE") != nullptr || devs.size() > 1 ||
+                            o.alphabet != 0;                            // K0 parses DNA: amino-acid inputs go through the host parser
+    const IngestConfig cfg = ingest_config(plan, o.k, size_t(o.workers()), force_host, o.alphabet);
     std::unique_ptr<IngestPipeline> pipe;
     try { pipe.reset(new IngestPipeline(lines, plan, cfg)); } catch (const std::bad_alloc &) { die("out of memory (ingest staging)"); }
     d2g_ctx *ctx = lctx.get();                                          // the readers are busy: now wait for the GPU context
@@ -409,7 +415,8 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     const size_t S = o.sketchsize, m = d2g_oph_m(S);
     const uint64_t xormask = d2g_seed_mask(o.seedseed);
     d2g_seqpack *sp = nullptr;
-    check(nullptr, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
+    check(nullptr, d2g_seqpack_create_alphabet(o.k, o.alphabet, &sp), "d2g_seqpack_create");
+    const uint64_t per_byte = o.alphabet ? 1 : 4;                                  // symbols per stream byte: a byte per residue, four bases
     if (d2g_seqpack_add_path_by_record(sp, o.paths[0].c_str()) != D2G_OK) die("Failed to read from " + o.paths[0]);
     d2g_ctx *ctx = lctx.get();
     const size_t N = d2g_seqpack_ngenomes(sp);
@@ -425,6 +432,7 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     d2g_sketcher *sk = nullptr;
     check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
     check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
+    check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");  // --protein...: amino-acid k-mers (K1a)
     JobFilter filter(o);
     d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);                         // fastxsketchbyseq.cpp:327,370,383,420-423
     std::vector<uint64_t> regs, rs_rel, goff_rel, ndist;
@@ -445,9 +453,9 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
         rs_rel.resize(nrun); goff_rel.resize(n + 1);
         for (size_t r = 0; r < nrun; ++r) rs_rel[r] = run_start[r0 + r] - base0;
         for (size_t g = 0; g <= n; ++g) goff_rel[g] = goff[g0 + g] - r0;
-        const uint8_t *pk = packed + base0 / 4;
+        const uint8_t *pk = packed + base0 / per_byte;                             // base0 is a multiple of 16 symbols: 4-byte aligned either way
         const uint64_t endb = nrun ? run_start[r1 - 1] + run_len[r1 - 1] : base0;
-        const size_t pk_bytes = std::min<size_t>(total_bytes - base0 / 4, (endb - base0 + 3) / 4 + 64);   // slice + its 64 readable pad bytes
+        const size_t pk_bytes = std::min<size_t>(total_bytes - base0 / per_byte, (endb - base0 + per_byte - 1) / per_byte + 64);   // slice + its 64 readable pad bytes
         sigs.resize(n * S); cards.resize(n);
         if (o.sspace == SPACE_MULTISET) {
             check(ctx, d2g_sketcher_run_bmh(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k, o.canon,
@@ -488,7 +496,7 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
     const size_t N = o.paths.size();
     if (!N) die(o.presketched ? "No paths provided to --presketched" : "Can't sketch empty path set");
     const bool weighted = o.exact == 2;
-    const ExactNameOpts no{o.k, o.canon, o.seedseed, o.count_threshold, o.outprefix, o.w};
+    const ExactNameOpts no{o.k, o.canon, o.seedseed, o.count_threshold, o.outprefix, o.w, d2g_alphabet_name(o.alphabet)};
     es.weighted = weighted;
     es.keys.assign(N, {}); es.counts.assign(N, {});
     res.destination_files.resize(N);
@@ -518,12 +526,13 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
         d2g_sketcher *sk = nullptr;
         check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
         check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
+        check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");  // --protein...: amino-acid k-mers (K1a)
         d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);
         const uint64_t xormask = d2g_seed_mask(o.seedseed);
         size_t limit = size_t(32) << 20;
         if (const char *e = std::getenv("D2G_GROUP_BYTES")) { const long long v = std::atoll(e); if (v >= 1) limit = size_t(v); }   // tests: many small batches
         d2g_seqpack *sp = nullptr;
-        check(ctx, d2g_seqpack_create(o.k, &sp), "d2g_seqpack_create");
+        check(ctx, d2g_seqpack_create_alphabet(o.k, o.alphabet, &sp), "d2g_seqpack_create");
         std::vector<uint64_t> keys, off, cards;
         std::vector<uint32_t> counts;
         for (size_t t0i = 0; t0i < todo.size();) {

@@ -201,6 +201,11 @@ int      d2g_epilogue_trunc_rect(const uint32_t *ca, const uint32_t *cb, const d
  * are dropped (they contain no k-mer). */
 typedef struct d2g_seqpack d2g_seqpack;
 int  d2g_seqpack_create(int k, d2g_seqpack **out);
+/* the same under an alphabet (K1a below): D2G_ALPHABET_DNA is d2g_seqpack_create; under a protein alphabet the stream holds ONE BYTE
+ * per residue (its code), the runs are the maximal runs of the alphabet's letters, and every add_* form works as it does for DNA.
+ * k above d2g_alphabet_max_k or an unknown alphabet is D2G_ERR_UNSUPPORTED. */
+int  d2g_seqpack_create_alphabet(int k, int alphabet, d2g_seqpack **out);
+int  d2g_seqpack_alphabet(const d2g_seqpack *sp);
 void d2g_seqpack_destroy(d2g_seqpack *sp);
 /* forget the content but keep the allocations (pooling packers avoids page-fault storms) */
 void d2g_seqpack_clear(d2g_seqpack *sp);
@@ -278,6 +283,41 @@ uint64_t d2g_run_emissions(uint64_t len, int k, int w);
 int  d2g_oph_plan_create_windowed(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                                   const uint64_t *genome_run_off, size_t n, int k, int w, d2g_oph_plan **out);
 uint64_t d2g_oph_plan_nbases(const d2g_oph_plan *plan);   /* total bases in the runs */
+
+/* ---- K1a: amino-acid k-mers, --protein / --protein14 / --protein8 / --protein6 -------------------------------
+ * Replaces bns::Encoder over a protein RollingHashingType (reference options.h:143-148,328-331; the encoder and the reduced
+ * alphabets live in the absent bonsai and are restated as this library's own spec "D2G-AA": parity unpinned).  Ids and names are
+ * those of the reference's python/parse.py:8-23.  A residue's code is the position of its group in the list:
+ *   D2G_ALPHABET_PROTEIN20     A = 20   A C D E F G H I K L M N P Q R S T V W Y      k <= 14
+ *   D2G_ALPHABET_PROTEIN_14    A = 14   A C D EQ FY G H IV KR LM N P ST W            k <= 16
+ *   D2G_ALPHABET_PROTEIN_3BIT  A =  8   AST C DHN EKQR FWY G ILMV P                  k <= 21
+ *   D2G_ALPHABET_PROTEIN_6     A =  6   AST CP DEHKNQR FWY G ILMV                    k <= 24
+ * Letters of either case; any other byte (X B Z J U O * - included) and a record boundary end a run; runs shorter than k are
+ * dropped.  The key of the k-mer with codes c_0 .. c_{k-1} is sum c_j A^(k-1-j) (first residue most significant), k at most the
+ * largest with A^k <= 2^64; every key is below 2^63.  There is no canonical form: canon != 0 is D2G_ERR_INVALID.  The key then
+ * takes the road of a DNA k-mer: Wang(x ^ xormask), OPH, counts, the filter table, the exact counter.
+ * Stream layout: one byte per residue holding its code, runs back to back, >= 64 readable bytes behind the last residue, 4-byte
+ * aligned; run_start / run_len count residues.
+ * An alphabet is an attribute of a plan or a sketcher, like a window: every d2g_*_dev call over such a plan and every
+ * d2g_sketcher_run* honour it; a k-mer filter records the alphabet it was built under and fits only calls under the same.  The
+ * one-shot host-pointer entry points take none.  D2G_ERR_UNSUPPORTED: k > d2g_alphabet_max_k; a window w > k together with a
+ * protein alphabet; d2g_sketcher_ingest_fasta (K0 parses DNA); d2g_sketcher_run_screen / d2g_screen_add_dev. */
+#define D2G_ALPHABET_DNA 0
+#define D2G_ALPHABET_PROTEIN20 2
+#define D2G_ALPHABET_PROTEIN_3BIT 3
+#define D2G_ALPHABET_PROTEIN_14 4
+#define D2G_ALPHABET_PROTEIN_6 5
+/* host, no GPU.  Symbols of the alphabet (4 for DNA; 0 for an unknown id), the largest k (32 for DNA; 0), the code of a byte or
+ * -1, the reference's name ("DNA", "PROTEIN20", "PROTEIN_3BIT", "PROTEIN_14", "PROTEIN_6"; "" for an unknown id) */
+int         d2g_alphabet_size(int alphabet);
+int         d2g_alphabet_max_k(int alphabet);
+int         d2g_alphabet_code(int alphabet, int byte);
+const char *d2g_alphabet_name(int alphabet);
+/* bits of the widest key of (k, alphabet): 2k for DNA, the bit length of A^k - 1 otherwise; 0 when k is outside [1, max k] */
+int         d2g_key_bits(int k, int alphabet);
+/* d2g_oph_plan_create is the alphabet-0 form; runs count residues */
+int  d2g_oph_plan_create_alphabet(d2g_ctx *ctx, const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                                  const uint64_t *genome_run_off, size_t n, int k, int alphabet, d2g_oph_plan **out);
 int  d2g_oph_sketch_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev,
                         int canon, uint64_t xormask, size_t sketchsize,
                         uint64_t *regs_out_dev /* [n][m] */, void *stream);
@@ -306,6 +346,9 @@ void d2g_sketcher_destroy(d2g_sketcher *sk);
 /* K1w (above): every later d2g_sketcher_run* of this sketcher walks the minimizers of windows of w bases when w > its k; 0, or any
  * w <= k, switches the window off.  A w beyond the cap is refused by the run (it is the run that knows k). */
 int  d2g_sketcher_set_window(d2g_sketcher *sk, int w);
+/* K1a (above): every later d2g_sketcher_run* of this sketcher reads its stream as one byte per residue of this alphabet;
+ * D2G_ALPHABET_DNA switches back.  An unknown id is D2G_ERR_INVALID. */
+int  d2g_sketcher_set_alphabet(d2g_sketcher *sk, int alphabet);
 int  d2g_sketcher_run(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
                       const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
                       const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
@@ -364,6 +407,10 @@ int  d2g_kmer_filter_create(d2g_ctx *ctx, const uint8_t *packed, size_t packed_b
 /* the same under a window (K1w): the filter input is enumerated with it, noccurrences counts its emissions; w <= k: no window */
 int  d2g_kmer_filter_create_windowed(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
                                      const uint32_t *run_len, size_t nrun, int k, int canon, int w, d2g_kmer_filter **out);
+/* the same under a protein alphabet (K1a): a byte-per-residue stream, no canonical form, no window.  A filter records its alphabet and
+ * fits only plans and sketchers under the same one */
+int  d2g_kmer_filter_create_alphabet(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes, const uint64_t *run_start,
+                                     const uint32_t *run_len, size_t nrun, int k, int alphabet, d2g_kmer_filter **out);
 void d2g_kmer_filter_destroy(d2g_kmer_filter *filter);
 /* k-mer occurrences put in (duplicates counted: the reference's data_.size()), distinct keys held, bytes of the device table;
  * synchronises the device */
