@@ -20,6 +20,7 @@ from .capi import (  # noqa: F401
     KSet, TIME_KSET, epilogue_exact, host_epilogue_exact_ut, host_epilogue_exact_rect, kset_check,
     ALPHABET_DNA, ALPHABET_PROTEIN20, ALPHABET_PROTEIN_3BIT, ALPHABET_PROTEIN_14, ALPHABET_PROTEIN_6,
     alphabet_size, alphabet_max_k, alphabet_code, alphabet_name, key_bits,
+    countsketch_lds_cells,
 )
 
 __all__ = [
@@ -36,4 +37,5 @@ __all__ = [
     "KSet", "TIME_KSET", "epilogue_exact", "host_epilogue_exact_ut", "host_epilogue_exact_rect", "kset_check",
     "ALPHABET_DNA", "ALPHABET_PROTEIN20", "ALPHABET_PROTEIN_3BIT", "ALPHABET_PROTEIN_14", "ALPHABET_PROTEIN_6",
     "alphabet_size", "alphabet_max_k", "alphabet_code", "alphabet_name", "key_bits",
+    "countsketch_lds_cells",
 ]

@@ -175,6 +175,13 @@ SIGNATURES = {
     "d2g_seqpack_add_path_by_record": (_int, [_vp, C.c_char_p]),
     "d2g_seqpack_add_fastx_by_record": (_int, [_vp, C.c_char_p, _sz]),
     "d2g_seqpack_name": (C.c_char_p, [_vp, _sz]),
+    "d2g_bmh_sketch_cs": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _u64, C.c_double, _vp, _vp]),
+    "d2g_bmh_sketch_cs_dev": (_int, [_vp, _vp, _vp, _int, _u64, _sz, _u64, C.c_double, _vp, _vp, _vp]),
+    "d2g_sketcher_run_bmh_cs": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _sz, _u64, C.c_double, _vp, _vp]),
+    "d2g_countsketch_table": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _u64, _vp]),
+    "d2g_countsketch_cells": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp, _sz, _int, _int, _u64, _u64, C.c_double, _vp, _vp, _sz, _vp, _vp]),
+    "d2g_countsketch_lds_cells": (_int, []),
+    "d2g_countsketch_stats": (_int, [_vp, _vp, _vp, _vp]),
     "d2g_bmh_check_weights": (_int, [_vp, _vp, _sz, _sz, _dbl, C.c_char_p, _sz]),
     "d2g_bmh_from_weighted": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     "d2g_bmh_from_weighted_ids": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
@@ -324,6 +331,11 @@ SCREEN_MAX_KEYS = 1 << 30                                               # includ
 def run_emissions(length, k, w=0):
     """k-mers a run of `length` valid bases emits under (k, w): its k-mers, or its window positions when w > k (host, no GPU)"""
     return int(lib().d2g_run_emissions(int(length), int(k), int(w)))
+
+
+def countsketch_lds_cells():
+    """L: count-sketch tables of up to this many cells are accumulated in LDS (host, no GPU)"""
+    return int(lib().d2g_countsketch_lds_cells())
 
 
 def screen_table_slots(ndistinct):
@@ -841,6 +853,44 @@ class Context:
         self._check(lib().d2g_bmh_sketch_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, count_threshold,
                                              sig_dev_ptr, tw_dev_ptr, stream))
 
+    # -- K3k (--multiset -c <cells>: count-sketch -> BagMinHash) --------------------
+    def bmh_sketch_cs_seqpack(self, sp: "SeqPack", S, cells, canon=True, xormask=0, count_threshold=0.0):
+        """-> (sig float64[n][S], total_weight float64[n]) over the cells with |count| >= count_threshold"""
+        r = _Runs(sp, canon)
+        sig = np.empty((r.n, S), np.float64)
+        tw = np.empty(r.n, np.float64)
+        self._check(lib().d2g_bmh_sketch_cs(self._h, *r.args, xormask, S, cells, count_threshold, _np_ptr(sig), _np_ptr(tw)))
+        return sig, tw
+
+    def bmh_sketch_cs_dev(self, plan, packed_dev_ptr, S, cells, sig_dev_ptr, tw_dev_ptr, canon=True, xormask=0, count_threshold=0.0,
+                          stream=None):
+        self._check(lib().d2g_bmh_sketch_cs_dev(self._h, plan._h, packed_dev_ptr, int(canon), xormask, S, cells, count_threshold,
+                                                sig_dev_ptr, tw_dev_ptr, stream))
+
+    def countsketch_table(self, sp: "SeqPack", cells, canon=True, xormask=0):
+        """-> int32[n][cells]: the signed tables (small tables only)"""
+        r = _Runs(sp, canon)
+        tab = np.empty((r.n, cells), np.int32)
+        self._check(lib().d2g_countsketch_table(self._h, *r.args, xormask, cells, _np_ptr(tab)))
+        return tab
+
+    def countsketch_cells(self, sp: "SeqPack", cells, canon=True, xormask=0, count_threshold=0.0, cap=None):
+        """-> (ids uint64[total], weights float64[total], set_off uint64[n+1], totals uint64[n]): the kept cells of every input, ascending"""
+        r = _Runs(sp, canon)
+        if cap is None:
+            cap = sum(min(cells, sp.nkmers(g)) for g in range(r.n)) if hasattr(sp, "nkmers") else r.nkmers
+        ids, w = np.empty(max(cap, 1), np.uint64), np.empty(max(cap, 1), np.float64)
+        off, tot = np.zeros(r.n + 1, np.uint64), np.zeros(r.n, np.uint64)
+        self._check(lib().d2g_countsketch_cells(self._h, *r.args, xormask, cells, count_threshold, _np_ptr(ids), _np_ptr(w), cap,
+                                                _np_ptr(off), _np_ptr(tot)))
+        return ids[:int(off[-1])].copy(), w[:int(off[-1])].copy(), off, tot
+
+    def countsketch_stats(self):
+        """-> (largest table in bytes, groups, batches) of the count-sketch calls on this context"""
+        b, g, n = _u64(), _u64(), _u64()
+        self._check(lib().d2g_countsketch_stats(self._h, C.byref(b), C.byref(g), C.byref(n)))
+        return int(b.value), int(g.value), int(n.value)
+
     def kmer_count(self, packed, run_start, run_len, genome_run_off, k, canon=True, xormask=0, count_threshold=0.0):
         """host arrays (any run table over `packed`) -> list over genomes of (keys uint64[nd], counts uint32[nd]), each sorted by key"""
         return self._kmer_count((packed, run_start, run_len, genome_run_off, k), canon, xormask, count_threshold)
@@ -1200,6 +1250,14 @@ class Sketcher:
         sig = np.empty((r.n, S), np.float64)
         tw = np.empty(r.n, np.float64)
         self.ctx._check(lib().d2g_sketcher_run_bmh(self._h, *r.args, xormask, S, count_threshold, _np_ptr(sig), _np_ptr(tw)))
+        return sig, tw
+
+    def run_bmh_cs(self, sp, S, cells, canon=True, xormask=0, count_threshold=0.0):
+        """K3k through this sketcher's buffers, filter, window and alphabet -> as Context.bmh_sketch_cs_seqpack"""
+        r = _Runs(sp, canon)
+        sig = np.empty((r.n, S), np.float64)
+        tw = np.empty(r.n, np.float64)
+        self.ctx._check(lib().d2g_sketcher_run_bmh_cs(self._h, *r.args, xormask, S, cells, count_threshold, _np_ptr(sig), _np_ptr(tw)))
         return sig, tw
 
     # -- K0: FASTA bytes -> packed run stream on the GPU ------------------------------------------

@@ -121,6 +121,8 @@ struct d2g_k3_tuning {
     double gq_scale = 2.0;              // ... a survivor region holds this multiple of the survivors expected in it ...
     uint64_t gq_slack = 256;            // ... plus this many entries: 1 when the scale was given, else 256 above 24 workgroups per CU and 1024 up to there
     uint64_t sort_keys = K3_TARGET;     // D2G_K3S_RANGE_KEYS: 1 .. K3_TARGET mean keys per sort range of the sorted emission, K3s (tests: small inputs with many ranges)
+    uint64_t cs_table_bytes = 0;        // D2G_CS_TABLE_BYTES: the count-sketch table (K3k) takes at most this many bytes, so a batch goes in more groups of genomes (debugging, tests); 0 = a sixth of the free device memory
+    int cs_lds_cells = -1;              // D2G_CS_LDS_CELLS: 0 .. 40960, the most cells K3k accumulates in LDS (0: every table in global memory; measurements); -1 = K3K_LDS_CELLS
 };
 // the exact-set compare (d2g_kset_cmp.hip)
 struct d2g_kset_tuning {
@@ -144,10 +146,12 @@ struct d2g_ctx {
     d2g_evlog ev_k1, ev_k2, ev_k2prep, ev_k3, ev_k0, ev_knn;
     d2g_evlog ev_k1count;                   // "k1count": the count pass after K1 (d2g_oph_count_dev), timed under D2G_TIME_K1
     d2g_evlog ev_filter;                    // "filter": the build of a k-mer filter's table (d2g_kmer_filter_create_dev), under D2G_TIME_FILTER
+    d2g_evlog ev_k3k, ev_k3kcompact, ev_k3kbmh;   // under D2G_TIME_K3, the count-sketch chain (K3k): "k3k" = zeroing and k3k_add_kernel, "k3kcompact" = table -> (cell, |count|) lists, "k3kbmh" = BagMinHash over them
     d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
     d2g_evlog ev_screen, ev_screenreduce, ev_screenbuild;   // under D2G_TIME_SCREEN (d2g_screen.hip): "screen" = the count walk, "screenreduce" = d2g_screen_result's kernel, "screenbuild" = a screen's table
     d2g_evlog ev_dedup, ev_dedup_resolve;   // "dedup" = both: the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the latter alone)
     struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3_bmh.hip)
+    uint64_t cs_table_bytes = 0, cs_groups = 0, cs_batches = 0;   // K3k (d2g_countsketch_stats): the largest table so far, the groups and the batches of all count-sketch calls
     d2g_dev<uint32_t> knn_band;             // [band rows][N] equality counts the selection kernel reads (d2g_knn.hip); grow-only
     d2g_dev<unsigned long long> dedup_keys; // one key per row of a band: its best representative of earlier bands (d2g_dedup.hip)
 };

@@ -14,6 +14,7 @@ static const char *const kTuningNames[] = {
     "D2G_K3_COMPACT", "D2G_K3_L1BITS", "D2G_K3_BUCKET_KEYS", "D2G_K3_SUB_KEYS", "D2G_K3_SPLIT_MIN", "D2G_K3_SUBBATCH", "D2G_K3_ROUND_KEYS",
     "D2G_K3_GUESS_SCALE", "D2G_K3_GRID_PER_CU", "D2G_K3_LIGHT", "D2G_K3_GQ_SCALE",
     "D2G_K3S_RANGE_KEYS", "D2G_KSET_SPLIT", "D2G_KSET_PBITS",
+    "D2G_CS_TABLE_BYTES", "D2G_CS_LDS_CELLS",
 };
 void d2g_tuning_load(d2g_tuning &t) {
     t.kv.clear();
@@ -58,6 +59,8 @@ d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t) {
     if (const char *e = t.get("D2G_K3_GQ_SCALE")) { v.gq_scale_set = true; v.gq_scale = std::max(0.0, std::atof(e)); }
     v.gq_slack = v.gq_scale_set ? 1 : v.grid_per_cu > 24 ? 256 : 1024;
     if (const char *e = t.get("D2G_K3S_RANGE_KEYS")) { const long d = std::atol(e); if (d >= 1 && d <= K3_TARGET) v.sort_keys = (uint64_t)d; }
+    if (const char *e = t.get("D2G_CS_TABLE_BYTES")) { const long long d = std::atoll(e); if (d >= 1) v.cs_table_bytes = (uint64_t)d; }
+    if (const char *e = t.get("D2G_CS_LDS_CELLS")) { const int d = std::atoi(e); if (d >= 0 && d <= 40960) v.cs_lds_cells = d; }
     return v;
 }
 
@@ -247,6 +250,9 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;
     else if (!std::strcmp(which, "k3")) e = &c->ev_k3;
     else if (!std::strcmp(which, "k3s")) e = &c->ev_k3s;
+    else if (!std::strcmp(which, "k3k")) e = &c->ev_k3k;
+    else if (!std::strcmp(which, "k3kcompact")) e = &c->ev_k3kcompact;
+    else if (!std::strcmp(which, "k3kbmh")) e = &c->ev_k3kbmh;
     else if (!std::strcmp(which, "kset")) e = &c->ev_kset;
     else if (!std::strcmp(which, "ksetprep")) e = &c->ev_ksetprep;
     else if (!std::strcmp(which, "screen")) e = &c->ev_screen;

@@ -52,6 +52,10 @@ void sketch_usage() {
                          "  --cmpout/--distout/--cmp-outfile out   --phylip   --binary-output   --asymmetric-all-pairs\n"
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
                          "  --multiset/--bagminhash/-B   --parse-by-seq (one sketch per record of ONE file)\n"
+                         "  -c/--countsketch-size/--countmin-size cells   with --multiset: count the k-mers in a single-row count-sketch of that many cells\n"
+                         "                         (weighted sketching with fixed memory usage at the expense of some approximation: 4 bytes per cell and input,\n"
+                         "                         whatever the input's length) instead of exactly; a cell is kept when |count| >= -m c; cache names carry\n"
+                         "                         .CountMinCounting<cells>; 0: exact counting.  Not with --set/--countdict, --parse-by-seq, several GPUs, cells > 2^31\n"
                          "  -m/--count-threshold c   set sketches (OPH) of whole inputs: only k-mers seen at least c times are sketched (c < 2: all);\n"
                          "                         with --multiset: only k-mers seen MORE than c times.  In set space not with --parse-by-seq or\n"
                          "                         --presketched, and only where the sketches are written (-o, --cache or --cmpout)\n"
@@ -129,6 +133,7 @@ std::string Options::to_string() const {    // src/d2.cpp:10-43 (fields that exi
                          : (sspace == SPACE_SET ? "fullsetsketch" : sspace == SPACE_MULTISET ? "bagminhash" : "probminhash"));
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";%s", "Fastx");
     if (!outprefix.empty()) pos += std::snprintf(buf + pos, sizeof buf - pos, ";outprefix:%s", outprefix.c_str());
+    if (cssize) pos += std::snprintf(buf + pos, sizeof buf - pos, ";counting=countsketch%zu\n", size_t(cssize));   // d2.cpp:33, with its line feed
     if (canon) pos += std::snprintf(buf + pos, sizeof buf - pos, ";canon");
     if (filterset_built) pos += std::snprintf(buf + pos, sizeof buf - pos, ";FilterSetSortedHashSet-size=%llu", (unsigned long long)filterset_size);   // d2.cpp:38-40, filterset.h:82
     return std::string(buf, pos);
@@ -144,6 +149,7 @@ int parse_options(int argc, char **argv, Options &o) {
         {"outprefix", required_argument, 0, OPT_OUTPREF}, {"prefix", required_argument, 0, OPT_OUTPREF},
         {"kmer-length", required_argument, 0, 'k'}, {"outfile", required_argument, 0, 'o'},
         {"window-size", required_argument, 0, 'w'},
+        {"countsketch-size", required_argument, 0, 'c'}, {"countmin-size", required_argument, 0, 'c'},
         {"binary-output", no_argument, 0, OPT_BINARY}, {"emit-binary", no_argument, 0, OPT_BINARY}, {"binary", no_argument, 0, OPT_BINARY},
         {"intersection", no_argument, 0, OPT_ISZ}, {"intersection-size", no_argument, 0, OPT_ISZ}, {"union-size", no_argument, 0, OPT_USZ},
         {"mash-distance", no_argument, 0, OPT_MASH}, {"distance", no_argument, 0, OPT_MASH}, {"poisson-distance", no_argument, 0, OPT_MASH},
@@ -197,6 +203,7 @@ int parse_options(int argc, char **argv, Options &o) {
             case 'S': o.sketchsize = size_t(std::atoi(optarg)); break;
             case 'k': o.k = std::atoi(optarg); break;
             case 'w': o.w = std::atoi(optarg); break;
+            case 'c': o.cssize = std::strtoull(optarg, nullptr, 10); break;          // options.h:357
             case 'o': o.outfile = optarg; break;
             case 'C': o.canon = false; break;
             case 'W': o.cache = true; break;
@@ -306,6 +313,21 @@ int parse_options(int argc, char **argv, Options &o) {
         else if (e && *e && (std::strcmp(e, "all") == 0 || std::strchr(e, ','))) why = "D2G_DEVICES naming several GPUs (exact sets are kept and compared on one GPU)";
         if (why) {
             std::fprintf(stderr, "dashing2 (MI355X): %s together with %s is outside the hot-path scope of this build.\n", mode, why);
+            return 1 + 1;
+        }
+    }
+    if (o.cssize && !o.presketched) {
+        // K3k: what the count-sketch does not combine with in this build, each named, before a GPU is asked for.  With --presketched
+        // nothing is counted: -c only shows in the options line.  In set space the reference never builds a Counter for whole inputs.
+        const char *why = nullptr;
+        const char *e = std::getenv("D2G_DEVICES");
+        if (o.exact) why = "--set/-H or --countdict/-J (the reference's finalize(vector&...) arm writes maskfn(cell) keys for a count-sketch; that arm is not built)";
+        else if (o.parse_by_seq) why = "--parse-by-seq (a count-sketch table per record)";
+        else if (o.cssize > (uint64_t(1) << 31)) why = "more than 2^31 cells (a cell number is a 32-bit index on the device)";
+        else if (o.sspace == SPACE_MULTISET && e && *e && (std::strcmp(e, "all") == 0 || std::strchr(e, ',')))
+            why = "D2G_DEVICES naming several GPUs (count-sketch multiset sketches are made on one GPU)";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): -c/--countsketch-size/--countmin-size together with %s is outside the hot-path scope of this build.\n", why);
             return 1 + 1;
         }
     }

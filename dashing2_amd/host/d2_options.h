@@ -51,6 +51,8 @@ struct Options {
                                           // k-mer set / count dictionary of every input; kept iff count > count_threshold; cmp gives exact values
     int alphabet = 0;                     // --protein/--protein20/--enable-protein = 2, --protein8 = 3, --protein14 = 4, --protein6 = 5 (options.h:143-148,328-331;
                                           // ids of python/parse.py:8-23 = D2G_ALPHABET_*): amino-acid k-mers (K1a), canon forced off, default k = the alphabet's largest
+    uint64_t cssize = 0;                  // -c/--countsketch-size/--countmin-size cells (options.h:78-79,357; d2.h:107): with --multiset the k-mers are counted in a
+                                          // single-row count-sketch of that many cells (K3k) instead of exactly; 0 = exact counting.  Elsewhere only to_string() shows it
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -30,7 +30,8 @@ std::string makedest(const Options &o, const std::string &path) {
         // either: `-m 2.7` is 2 there and here.  The integer branch: std::to_string(int(count_threshold_)).
         ret += ".ct_threshold" + std::to_string(int(o.count_threshold));
     }
-    if (o.sspace != SPACE_SET) ret += ".ExactCounting";   // to_string(ct()), src/enums.cpp:47; fastxmerge.cpp:96-100
+    // to_string(ct()), src/enums.cpp:47-48; fastxmerge.cpp:96-100.  opts.ct() is COUNTMIN_COUNTING whenever cssize > 0 (d2.h:207), whichever flag gave it
+    if (o.sspace != SPACE_SET) ret += o.cssize ? ".CountMinCounting" + std::to_string(o.cssize) : std::string(".ExactCounting");
     ret += o.sspace == SPACE_SET ? ".SetSpace" : ".MultisetSpace";   // to_string(sspace), src/enums.cpp:40-46
     ret += std::string(".") + d2g_alphabet_name(o.alphabet);   // bns::to_string(rht_) (absent bonsai; "DNA", or the names of python/parse.py:8-23)
     // to_suffix, src/enums.cpp:28-38, gives ".bmh" for BagMinHash.  Multiset sketches of this build follow the repository's
@@ -160,8 +161,9 @@ struct JobFilter {
 // x87 finalisation (getcard / data, src/oph.h:240-263) and cache files leave the device threads through a small queue
 struct Fin { size_t g; std::vector<uint64_t> regs; std::vector<double> sigs, cards; std::vector<uint32_t> counts; };   // counts: [n][m] with -N
 
-constexpr int NSK = 4;
-constexpr const char *SKETCH_KERNELS[NSK] = {"k0", "k1", "k3", "k1count"};   // k1count: reported only by jobs that count (-N with -o)
+constexpr int NSK = 7, NSK_ALWAYS = 3, NSK_CS = 4;
+// k1count: reported only by jobs that count (-N with -o); k3k, k3kcompact, k3kbmh: only by --multiset -c jobs (the count-sketch chain)
+constexpr const char *SKETCH_KERNELS[NSK] = {"k0", "k1", "k3", "k1count", "k3k", "k3kcompact", "k3kbmh"};
 struct KAcc { int launches = 0; double total_ms = 0; };
 
 // What the device threads of one sketch job share.  `const` members and what they point to are read-only while the threads run.
@@ -181,6 +183,7 @@ struct DeviceSide {
     size_t n_dev_groups = 0, n_host_groups = 0;
     std::vector<std::array<KAcc, NSK>> kacc;              // per device: k0, k1, k3, k1count
     std::vector<size_t> groups_of;                        // per device
+    uint64_t cs_table_bytes = 0, cs_groups = 0, cs_batches = 0;   // -c: the largest count-sketch table of any thread, the table groups and batches of all
 
     // sketches one group: the raw bytes parsed on the device, or the stream the host parser packed -> Fin; true: parsed on the device
     bool sketch_group(d2g_ctx *ctx, d2g_sketcher *sk, IngestGroup &r, Fin &f, uint64_t &nb) {
@@ -209,8 +212,12 @@ struct DeviceSide {
         if (o.sspace == SPACE_MULTISET) {
             // fastxsketch.cpp:425-445: Counter -> BagMinHash; cardinality = total weight, signature = data()[0..S)
             f.sigs.resize(n * S); f.cards.resize(n);
-            check(ctx, d2g_sketcher_run_bmh(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S,
-                                            double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh");
+            if (o.cssize)                                               // -c: Counter(cssize), counter.h:74-75,131-137 (K3k)
+                check(ctx, d2g_sketcher_run_bmh_cs(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, o.cssize,
+                                                   double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh_cs");
+            else
+                check(ctx, d2g_sketcher_run_bmh(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S,
+                                                double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh");
         } else {
             f.regs.resize(n * d2g_oph_m(S));
             if (o.count_threshold >= 2) {                               // fastxsketch.cpp:192: set_mincount(count_threshold_); with -N idcounts() too
@@ -258,8 +265,11 @@ struct DeviceSide {
                 int n = 0; float avg = 0, last = 0;
                 if (d2g_kernel_ms(ctx, SKETCH_KERNELS[x], 1, &n, &avg, &last) == D2G_OK) { mine[x].launches = n; mine[x].total_ms = double(avg) * n; }
             }
+        uint64_t cs_b = 0, cs_g = 0, cs_n = 0;
+        if (g_stats.on && o.cssize) (void)d2g_countsketch_stats(ctx, &cs_b, &cs_g, &cs_n);
         if (g_release_at_exit) { d2g_sketcher_destroy(sk); d2g_kmer_filter_destroy(kf); if (ctx != first_ctx) d2g_ctx_destroy(ctx); }
         std::lock_guard<std::mutex> lk(mu);
+        cs_table_bytes = std::max(cs_table_bytes, cs_b); cs_groups += cs_g; cs_batches += cs_n;
         t_gpu += gpu; total_bases += bases; n_dev_groups += ndevg; n_host_groups += nhostg;
         groups_of[di] += ndevg + nhostg;
         for (int x = 0; x < NSK; ++x) { kacc[di][x].launches += mine[x].launches; kacc[di][x].total_ms += mine[x].total_ms; }
@@ -385,18 +395,24 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
                                   ds.t_gpu, t_fin, cfg.nbufs, cfg.buf_bytes >> 20, t_pin);
     if (o.verbosity) std::fprintf(stderr, "[d2g] sketch wall: setup (stat, cache probe) %.3fs, ingest pipeline %.3fs\n", t_setup - t_enter, t_pipe - t_setup);
     if (g_stats.on) {
+        const bool multiset = o.sspace == SPACE_MULTISET, countsketch = multiset && o.cssize != 0;
         Json dj = Json::array();
         for (size_t d = 0; d < devs.size(); ++d) {
             Json e = device_json(devs[d]);
             e.integer("groups", ds.groups_of[d]);
-            for (int x = 0; x < (want_counts ? NSK : NSK - 1); ++x) e.nest(SKETCH_KERNELS[x], Json::object().integer("launches", ds.kacc[d][x].launches).num("total_ms", ds.kacc[d][x].total_ms));
+            for (int x = 0; x < NSK; ++x) {
+                if (x == NSK_ALWAYS ? !want_counts : x >= NSK_CS ? !countsketch : false) continue;
+                e.nest(SKETCH_KERNELS[x], Json::object().integer("launches", ds.kacc[d][x].launches).num("total_ms", ds.kacc[d][x].total_ms));
+            }
             dj.push(e);
         }
-        const bool multiset = o.sspace == SPACE_MULTISET;
+        if (countsketch)
+            g_stats.nest("countsketch", Json::object().integer("cells", o.cssize).integer("table_bytes", ds.cs_table_bytes).integer("table_groups", ds.cs_groups)
+                         .integer("batches", ds.cs_batches));
         // ceil(L/4) + 8 m per input (set sketches), + 8 for the total weight of a multiset sketch
         const double alg = double((ds.total_bases + 3) / 4) + double(todo.size()) * (8.0 * double(multiset ? S : m) + (multiset ? 8.0 : 0.0));
         g_stats.nest("sketch", Json::object().integer("inputs", N).integer("sketched", todo.size()).integer("from_cache", N - todo.size()).integer("k", o.k)
-                     .integer("sketchsize", S).str("space", multiset ? "multiset (K3: counts + BagMinHash)" : "set (K1: OPH)").integer("groups", groups.size())
+                     .integer("sketchsize", S).str("space", countsketch ? "multiset (K3k: count-sketch + BagMinHash)" : multiset ? "multiset (K3: counts + BagMinHash)" : "set (K1: OPH)").integer("groups", groups.size())
                      .integer("groups_parsed_on_device", ds.n_dev_groups).integer("bases", ds.total_bases).num("algorithmic_bytes", alg)
                      .integer("device_threads", nthreads_dev).integer("parser_threads", cfg.readers).nest("devices", dj)
                      .nest("wall_s", Json::object().num("setup", t_setup - t_enter).num("ingest_pipeline", t_pipe - t_setup).num("device_loops", t_dev2 - t_dev1)

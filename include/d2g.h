@@ -574,6 +574,49 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
                               double *sig_out /* host [nsets][S] */, double *total_weight_out /* host [nsets] */,
                               uint64_t *owner_out /* host [nsets][S] or NULL */);
 
+/* ---- K3k: --multiset -c/--countsketch-size/--countmin-size <cells>: approximate counts in a single-row count-sketch (R20) ----
+ * Replaces, per input, Counter(cssize)::add(maskfn(kmer)) and ::finalize(bmh, threshold) (src/counter.h:16-19,68-77,131-137):
+ *   hv = Wang(maskfn(x)) for every k-mer x the walker emits; table[hv % cells] += (hv >> 63) ? +1 : -1;
+ *   then every cell i with |table[i]| >= threshold (>=, where the exact mode keeps count > threshold) and > 0 is the element
+ *   (id = i, weight = |table[i]|) of BagMinHash (BMH-D2G, as d2g_bmh_from_weighted), total weight = the sum of those weights.
+ * The cells are int32 on the device and hold the exact sums; the reference's float cells stop counting at 2^24.
+ * Device memory: 4 * cells bytes per input whatever its length (K3 keeps 16 bytes per k-mer).  A batch whose tables do not fit a
+ * sixth of the free device memory -- or D2G_CS_TABLE_BYTES, a debugging switch -- goes in groups of inputs; the output is the same.
+ * Refused with D2G_ERR_INVALID before anything is staged or launched: cells outside [1, 2^31], an input of 2^31 k-mers or more;
+ * with D2G_ERR_NOMEM before anything is launched: one table larger than the free device memory (the message has both figures).
+ * The three forms of every K3 job; a sketcher's / plan's filter, window and alphabet are honoured as by d2g_sketcher_run_bmh /
+ * d2g_bmh_sketch_dev.  An input without k-mers, or with every cell below the threshold: +inf registers, total weight 0. */
+int d2g_bmh_sketch_cs(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
+                      const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                      const uint64_t *genome_run_off, size_t n,
+                      int k, int canon, uint64_t xormask, size_t sketchsize, uint64_t cells, double count_threshold,
+                      double *sig_out /* host [n][S] */, double *total_weight_out /* host [n] */);
+/* synchronises `stream` before returning, like d2g_bmh_sketch_dev (and once per group and BagMinHash pass in between) */
+int d2g_bmh_sketch_cs_dev(d2g_ctx *ctx, const d2g_oph_plan *plan, const uint8_t *packed_dev,
+                          int canon, uint64_t xormask, size_t sketchsize, uint64_t cells, double count_threshold,
+                          double *sig_out_dev /* [n][S] */, double *total_weight_out_dev /* [n] */, void *stream);
+int d2g_sketcher_run_bmh_cs(d2g_sketcher *sk, const uint8_t *packed, size_t packed_bytes,
+                            const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                            const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                            size_t sketchsize, uint64_t cells, double count_threshold,
+                            double *sig_out /* host [n][S] */, double *total_weight_out /* host [n] */);
+/* the first two stages on their own (tests, integrators).  The signed tables, dense: at most 2^28 cells in all */
+int d2g_countsketch_table(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
+                          const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                          const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                          uint64_t cells, int32_t *table_out /* host [n][cells] */);
+/* ... and the compacted lists, any table size: input g's kept cells, ascending, in ids_out / w_out[set_off_out[g] .. set_off_out[g+1]);
+ * total_out[g] = the sum of its weights.  cap = capacity of the two arrays (min(cells, k-mers) per input always suffices) */
+int d2g_countsketch_cells(d2g_ctx *ctx, const uint8_t *packed, size_t packed_bytes,
+                          const uint64_t *run_start, const uint32_t *run_len, size_t nrun,
+                          const uint64_t *genome_run_off, size_t n, int k, int canon, uint64_t xormask,
+                          uint64_t cells, double count_threshold, uint64_t *ids_out, double *w_out, size_t cap,
+                          uint64_t *set_off_out /* [n+1] */, uint64_t *total_out /* [n] */);
+/* L: tables of up to this many cells are accumulated in LDS per workgroup and flushed; larger ones take every add in global memory */
+int d2g_countsketch_lds_cells(void);
+/* since the context was made: the largest table allocated (bytes), the groups and the batches of all count-sketch calls */
+int d2g_countsketch_stats(d2g_ctx *ctx, uint64_t *table_bytes, uint64_t *groups, uint64_t *batches);
+
 /* ---- K2: dense all-pairs comparison -------------------------------------------
  * Replaces HOT LOOP B: emit_rectangular's row loops calling compare()
  * (reference src/emitrect.cpp:211-323 ; src/cmp_core.cpp:349-361,458-517).
