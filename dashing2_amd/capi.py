@@ -194,6 +194,7 @@ SIGNATURES = {
     "d2g_cmp_set_sparse_info": (_int, [_vp, _vp, _vp, _vp]),
     "d2g_cmp_set_debug_pairs": (_int, [_vp, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
     "d2g_cmp_set_sparse_detail": (_int, [_vp, _vp, _vp, _vp]),
+    "d2g_cmp_set_fill_detail": (_int, [_vp, _vp, _vp]),
     "d2g_sparse_bin_geometry": (_int, [_sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(_int)]),
     "d2g_warmup": (_int, [_vp, _int]),
     "d2g_device_name": (_int, [_int, C.c_char_p, _sz]),
@@ -1518,6 +1519,13 @@ class CmpSet:
         self.ctx._check(lib().d2g_cmp_set_sparse_detail(self.ctx._h, self._h, stream, a.ctypes.data))
         return {"looked": bool(a[0]), "looked_dense": bool(a[1]), "entries": int(a[2]), "family_pairs": int(a[3]), "shared_values": int(a[4]),
                 "planes": int(a[5]), "binned": bool(a[6]), "bin_cshift": int(a[7]), "schedule": "merged" if a[8] else "classic", "prepare_kernels": int(a[9])}
+
+    def fill_detail(self):
+        """-> dict of what became of the output announced to the last prepare, in 32 KB pieces: "announced", "rank" (written by the rank kernel's own
+        threads), "riders" (carried by the prepare's other kernels), "launch" (left to the launch); host bookkeeping, nothing is synchronised"""
+        a = np.zeros(4, np.uint64)
+        self.ctx._check(lib().d2g_cmp_set_fill_detail(self.ctx._h, self._h, a.ctypes.data))
+        return {"announced": int(a[0]), "rank": int(a[1]), "riders": int(a[2]), "launch": int(a[3])}
 
     def debug_pairs(self, cap=1 << 24, stream=None):
         """-> (pairs [n][2] uint32: the pair list of the last prepare (i < j), roots [N] uint32: the family root of every sketch)"""

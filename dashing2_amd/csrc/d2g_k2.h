@@ -24,6 +24,14 @@ inline size_t sp_fill_pieces(size_t cnt) { return div_up<size_t>(cnt / 4 + 1, (s
 #endif
 constexpr unsigned SP_RW_PLAN = 6, SP_RW_FLATTEN = 5, SP_RW_COUNT = 5, SP_RW_ATTACH = 5, SP_RW_SCAN = 8, SP_RW_ALL = 35;
 constexpr unsigned SP_RW_M_LINK0 = D2G_SP_RW_M_LINK0, SP_RW_M_PLANES = D2G_SP_RW_M_PLANES;
+// The FAST rank kernel (bs_rank_kernel<false, true>: N <= 12 288) is no host of rider workgroups -- every wave slot of the chip is taken for its 52 us at
+// config 3 -- but its HBM is almost idle, and a store needs no wave slot: its own threads write the FIRST pieces of the fill between their probe chains
+// (bit 64 of D2G_SP_RIDE).  Its share in parts of SP_RW_ALL is d2g_k2_tuning::rank_share (D2G_SP_RANK_SHARE; fitted: profiles/k2_rank_fill.txt);
+// SP_RANK_FILL_PER_WG = what one workgroup can hold: one 16-byte store per thread and iteration of its claim loop.  What is left goes to the six hosts by
+// the weights above.
+constexpr int BS_RANK_THREADS = 1024, BS_RANK_PF = 12;          // bs_rank_kernel: threads of a workgroup; values a FAST thread keeps in registers
+constexpr uint32_t SP_RANK_FILL_PER_WG = (uint32_t)(BS_RANK_PF * BS_RANK_THREADS * 16 / (SP_FILL_THREADS * SP_FILL_PER_THREAD * 16));   // = 6 pieces
+static_assert(SP_RANK_FILL_PER_WG * SP_FILL_THREADS * SP_FILL_PER_THREAD == BS_RANK_PF * BS_RANK_THREADS, "the rank kernel's stores of one workgroup are whole pieces");
 
 // start-of-prepare work of the sparse path's ordering, carried by a kernel that runs anyway (k2_transpose_kernel for a set that owns its operand,
 // sp_unpack_kernel for the multi-GPU engine's gathered one) instead of a launch and memsets of its own: label[j] = j, `owords` words at `ones` set to
@@ -59,6 +67,15 @@ struct SpAnnounced {
     }
     uint32_t riding() const { return total; }         // pieces this prepare carries
     SpRider take_all() { next = total; return SpRider{out, cnt, vsrc, vimm, 0u, 0u}; }   // a fill kernel of its own writes every piece: nothing left for the riders
+    // the FAST rank kernel's share (bit 64 of the mask), asked for BEFORE any host: the first pieces [0, *n), at most `cap` (what its grid holds).  What the
+    // riders and the launch see is the same prefix bookkeeping as without it
+    SpRider take_first(unsigned weight, uint64_t cap, uint32_t *n) {
+        *n = 0;
+        if (next != 0 || !total || !(mask & 64)) return SP_NO_RIDER;
+        *n = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(total, cap), ((uint64_t)total * weight + SP_RW_ALL - 1) / SP_RW_ALL);
+        next = *n;
+        return SpRider{out, cnt, vsrc, vimm, 0u, 0u};
+    }
     // the share of a hosting kernel with `own` workgroups of its own (bit `bit` of the mask): `grid` = what to launch
     SpRider take(unsigned own, unsigned weight, bool last, int bit, unsigned *grid) {
         *grid = own;
@@ -106,6 +123,7 @@ struct SpDecision {
     bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)
     bool big = true;                  // this prepare enqueued the binned form of the pair list (sp_expect_long_list)
     bool looked = false, looked_dense = false; uint32_t samp_sums[4] = {0, 0, 0, 0};   // the last prepare's first look: taken, its decision, its raw sums E, F, shared values, planes
+    uint64_t fill_announced = 0, fill_rank = 0, fill_carried = 0;   // the last prepare: 32 KB pieces of the output announced to it / written by its rank kernel / by its other kernels (riders, side fill) -- d2g_cmp_set_fill_detail
 };
 
 // everything the sparse path of a set owns (sp_alloc builds one; a set without it takes the dense walk)
@@ -225,6 +243,7 @@ int  d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set);
 int  d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s);
 int  d2g_bitslice_sparse_info(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint32_t *out4);
 int  d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *out10);
+void d2g_bitslice_fill_detail(const d2g_cmp_set *set, uint64_t *out4);   // host bookkeeping of the last prepare; no synchronisation
 SpInit d2g_bitslice_sp_init(const d2g_cmp_set *set);   // what the transpose in front of the set's prepare initialises for its ordering (nothing: a set without sparse state)
 int  d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s, uint64_t *pairs_out, size_t cap, size_t *npairs, uint32_t *root_out);
 int  d2g_bitslice_status(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s);   // synchronises; D2G_ERR_INTERNAL on overflow

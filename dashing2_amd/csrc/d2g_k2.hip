@@ -363,6 +363,15 @@ int d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream
     return d2g_bitslice_sparse_detail(ctx, set, as_stream(stream), out10);
 }
 
+int d2g_cmp_set_fill_detail(d2g_ctx *ctx, const d2g_cmp_set *set, uint64_t *out4) {
+    if (!ctx || !out4) return D2G_ERR_INVALID;
+    D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_fill_detail: set belongs to another context");
+    D2G_NO_CODE_SET(ctx, set, "cmp_set_fill_detail");
+    for (int x = 0; x < 4; ++x) out4[x] = 0;
+    if (set->algo == D2G_CMP_BITSLICE) d2g_bitslice_fill_detail(set, out4);
+    return D2G_OK;
+}
+
 int d2g_cmp_set_status(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream) {
     if (!ctx) return D2G_ERR_INVALID;
     D2G_CHECK(ctx, set && set->ctx == ctx, "cmp_set_status: set belongs to another context");

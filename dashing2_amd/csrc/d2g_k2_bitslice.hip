@@ -31,7 +31,6 @@ namespace {
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 typedef u32x16 __attribute__((aligned(4))) u32x16_u;
 constexpr uint32_t BS_EMPTY = 0xFFFFFFFFu;
-constexpr int BS_RANK_THREADS = 1024;
 
 // ------------------------------------------------------------------ 1. per-column dense ids
 // One workgroup per register index t.  owner[] (T slots, pre-set to EMPTY) records the first
@@ -88,6 +87,30 @@ __device__ __forceinline__ uint32_t bs_hash(uint64_t v, int logT) {
 // kernel stays; what it costs is ~84 dependent round trips per workgroup (three per batch of eight values and pass) with one 128 KiB-table
 // workgroup per CU to hide them.)
 constexpr uint32_t BS_SPLIT_SHIFT = 28, BS_RANK_MASK = (1u << BS_SPLIT_SHIFT) - 1u;
+// ---- where the pieces of an announced output's fill lie (the riders below, the side fill, the FAST rank kernel): ONE definition.  The output pointer is
+// only 4-byte aligned in general: `head` words (0 .. 3) in front of the 16-byte aligned body of `nb` vectors, at most three tail words behind it.  Piece p
+// is the vectors [2048 p, 2048 (p + 1)) of the body; whoever writes piece 0 writes the head and tail words too (sp_fill_ends).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+// s_waitcnt immediate of the gfx9 family (gfx950 among it): vmcnt = bits 3:0 and 15:14, expcnt = 6:4, lgkmcnt = 11:8 -- "every vector memory operation
+// has returned", the other two counters not waited for (their maxima)
+constexpr int BS_WAIT_VM0 = (0x7 << 4) | (0xF << 8);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(__GFX9__)
+#error "BS_WAIT_VM0 is the s_waitcnt encoding of the gfx9 family"
+#endif
+struct SpFillAddr { u32x4 *body; size_t nb; uint32_t head, v; };
+constexpr size_t SP_PIECE_VECS = (size_t)SP_FILL_THREADS * SP_FILL_PER_THREAD;
+__device__ __forceinline__ SpFillAddr sp_fill_addr(const SpRider &r) {
+    const size_t head = min(r.cnt, (size_t)((16 - ((uintptr_t)r.out & 15)) & 15) / 4);
+    return SpFillAddr{reinterpret_cast<u32x4 *>(r.out + head), (r.cnt - head) / 4, (uint32_t)head, r.vsrc ? r.vsrc[0] : r.vimm};
+}
+// non-temporal stores (as in sp_fill_kernel): 200 MB of output nobody reads again must not push the prepare's working set out of the MALL
+__device__ __forceinline__ void sp_fill_store(const SpFillAddr &a, size_t i) { __builtin_nontemporal_store(u32x4{a.v, a.v, a.v, a.v}, &a.body[i]); }
+__device__ __forceinline__ void sp_fill_ends(const SpRider &r, const SpFillAddr &a) {
+    if (threadIdx.x < a.head) r.out[threadIdx.x] = a.v;
+    const size_t tail0 = a.head + a.nb * 4;
+    if (tail0 + threadIdx.x < r.cnt) r.out[tail0 + threadIdx.x] = a.v;
+}
+
 #ifdef D2G_RANK_TRACE
 // variant builds only (tools/build_variant.sh ranktrace -DD2G_RANK_TRACE; tools/rank_trace.py): per-workgroup time stamps of the rank kernel --
 // FAST: 0 start, 1 values loaded + table cleared, 2 claims done, 3 confirms done, 4 compaction done, 5 ids stored;
@@ -101,7 +124,7 @@ template <bool MULTI, bool FAST, typename IdT = uint32_t>
 __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t *__restrict__ cols, size_t N, size_t Npad,
                                                                   uint32_t T, int logT, void *ids_void, uint32_t *colcnt,
                                                                   uint32_t *status, int tagbits_max, uint32_t S, int nsplit,
-                                                                  uint32_t *__restrict__ owner_all, size_t ostride) {
+                                                                  uint32_t *__restrict__ owner_all, size_t ostride, SpRider fill, uint32_t fill_n) {
     extern __shared__ __attribute__((aligned(16))) uint32_t own[];        // Tl owner slots
     const uint32_t split = MULTI ? blockIdx.x / S : 0u;
     const size_t t = MULTI ? blockIdx.x - split * S : blockIdx.x;
@@ -188,7 +211,7 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
         return h;                                                         // garbage id, flagged
     };
 
-    constexpr int PF = 12;      // values a thread keeps in registers (fast path: N <= 12288, one partition)
+    constexpr int PF = BS_RANK_PF;      // values a thread keeps in registers (fast path: N <= 12288, one partition)
     if constexpr (FAST) {
         // every value is fetched BEFORE the probe chains (a load inside the chain exposed a full HBM/L2 round
         // trip per value) and its slot stays in a register until the ids are written.
@@ -200,6 +223,23 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
         // same candidate (claimed slots never change owner or tag), so the outcome is the exact ranking.
         // (Probing a thread's values TOGETHER, round by round, was measured too: it needs > 64 VGPRs, i.e. one
         // workgroup per CU instead of two, and is slower -- profiles/r02_k2_experiments.txt.)
+        //
+        // The announced fill's first fill_n pieces (SpAnnounced::take_first), in equal runs of `per` <= SP_RANK_FILL_PER_WG pieces per workgroup: one
+        // 16-byte non-temporal store per thread in front of each probe chain of the claim loop.  THERE and nowhere later: loads and stores share the one
+        // VM counter, so the confirm phase's wait for its owner fetches also waits for every store issued before them -- in the claim phase, LDS round
+        // trips only, nothing waits for them by name (not free either: the trace in profiles/k2_rank_fill.txt section 6).  Set up HERE, in front of the value loads: the fill value is one scalar load, and
+        // workgroup 0's head and tail words are on their way with the values.  fa.body = this workgroup's run, fcnt its vectors (nothing rides: 0)
+        SpFillAddr fa{nullptr, 0, 0u, 0u};
+        uint32_t fcnt = 0;
+        if (fill_n) {
+            fa = sp_fill_addr(fill);
+            if (blockIdx.x == 0) sp_fill_ends(fill, fa);
+            const uint32_t per = (fill_n + gridDim.x - 1) / gridDim.x;
+            const size_t p0 = (size_t)blockIdx.x * per;
+            const size_t b0 = min(p0 * SP_PIECE_VECS, fa.nb), b1 = min(min(p0 + per, (size_t)fill_n) * SP_PIECE_VECS, fa.nb);
+            fa.body += b0;
+            fcnt = b1 > b0 ? (uint32_t)(b1 - b0) : 0u;                    // (<= SP_RANK_FILL_PER_WG pieces = PF x 1024 vectors: the host's bound)
+        }
         uint64_t v[PF];
         uint32_t hs[PF];
 #pragma unroll
@@ -209,6 +249,11 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
         }
         for (uint32_t h = tid; h < Tl; h += BS_RANK_THREADS) own[h] = BS_EMPTY;
         __syncthreads();
+        // every value has arrived (they were requested together, in front of the table clear) before the first probe chain -- said HERE, outside any branch:
+        // the claim loop below issues the fill's stores between its chains, and a wait for value i placed by the compiler behind store i - 1 (stores and
+        // loads share the one VM counter, and it cannot count across the loop's branches) would be a wait for that store's whole round trip to the HBM
+        // (Unconditional: under `if (fill_n)` the compiler no longer knows at the join that the loads are in, and puts the waits back behind every store.)
+        __builtin_amdgcn_s_waitcnt(BS_WAIT_VM0);
         RK_STAMP(1);
         uint32_t candidate = 0;                                           // bit i: value i stopped at a tag match
         // (round 6: per-workgroup time stamps -- tools/rank_trace.py, profiles/r06_rank_trace.txt -- put this claim phase at 10.7 of the workgroup's 21 us at
@@ -218,6 +263,7 @@ __global__ __launch_bounds__(BS_RANK_THREADS) void bs_rank_kernel(const uint64_t
         for (int i = 0; i < PF; ++i) {
             const size_t j = (size_t)i * BS_RANK_THREADS + tid;
             hs[i] = 0;
+            if ((uint32_t)(i * BS_RANK_THREADS + tid) < fcnt) sp_fill_store(fa, (uint32_t)(i * BS_RANK_THREADS + tid));
             if (j < N) {
                 const uint64_t prod = v[i] * 0x9E3779B97F4A7C15ull;
                 const uint32_t mine = slot_word(prod, (uint32_t)j);
@@ -437,20 +483,15 @@ __device__ __forceinline__ size_t stream_slot_wave(const uint32_t *meta, int tb)
 // output is announced ahead of the prepare (d2g_cmp_ut_announce_dev) those kernels are launched with extra workgroups BEHIND their own --
 // the dispatcher starts workgroups in index order, the kernel's own work is never queued behind a rider -- each writing one 32 KB piece.
 // (The same fill on a second stream was measured in rounds 4 and 5: the two cross-stream dependencies cost more than the fill.)
+// In front of the riders stands the FAST rank kernel (bit 64 of D2G_SP_RIDE, D2G_SP_RANK_SHARE): no rider workgroup fits beside it, every wave slot is
+// taken, but its own threads write the FIRST pieces [0, n) from inside their claim loop (bs_rank_kernel; n <= six pieces per column: all of config 3's
+// 6 104), and the riders here carry what is left, by their weights, from piece n on.  Where a piece lies is defined once, in sp_fill_addr / sp_fill_ends
+// above the rank kernel; SpFilled::pieces stays the prefix the launch skips (what it gives and takes: profiles/k2_rank_fill.txt).
 __device__ __forceinline__ void sp_ride_piece(const SpRider &r, size_t piece) {
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const uint32_t v = r.vsrc ? r.vsrc[0] : r.vimm;
-    const size_t head = min(r.cnt, (size_t)((16 - ((uintptr_t)r.out & 15)) & 15) / 4);   // the output pointer is only 4-byte aligned in general
-    u32x4 *body = reinterpret_cast<u32x4 *>(r.out + head);
-    const size_t nb = (r.cnt - head) / 4;
-    const size_t end = min((piece + 1) * (size_t)2048, nb);
-    // non-temporal stores (as in sp_fill_kernel): 200 MB of output nobody reads again must not push the prepare's working set out of the MALL
-    for (size_t i = piece * 2048 + threadIdx.x; i < end; i += blockDim.x) __builtin_nontemporal_store(u32x4{v, v, v, v}, &body[i]);
-    if (piece == 0) {
-        if (threadIdx.x < head) r.out[threadIdx.x] = v;
-        const size_t tail0 = head + nb * 4;
-        if (tail0 + threadIdx.x < r.cnt) r.out[tail0 + threadIdx.x] = v;
-    }
+    const SpFillAddr a = sp_fill_addr(r);
+    const size_t end = min((piece + 1) * SP_PIECE_VECS, a.nb);
+    for (size_t i = piece * SP_PIECE_VECS + threadIdx.x; i < end; i += blockDim.x) sp_fill_store(a, i);
+    if (piece == 0) sp_fill_ends(r, a);
 }
 __device__ __forceinline__ void sp_ride(const SpRider &r) { sp_ride_piece(r, (size_t)r.piece0 + (blockIdx.x - r.own)); }
 #define SP_RIDE_OR_WORK(r) do { if (blockIdx.x >= (r).own) { sp_ride(r); return; } } while (0)
@@ -1004,6 +1045,8 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         // (the remembered word is device-written host memory read without synchronisation: read ONCE per prepare -- ADVICE r5 -- and handed down)
         sp->dec.skip_cached = sparse_path ? (sp_will_skip(ctx, *sp) ? 1 : 0) : -1;
         sp->announced.begin(ctx->k2.ride, sparse_path && sp->dec.skip_cached != 1);
+        const size_t pieces = sp->announced.out ? sp_fill_pieces(sp->announced.cnt) : 0;
+        sp->dec.fill_announced = pieces; sp->dec.fill_rank = sp->dec.fill_carried = 0;   // (diagnostics: d2g_cmp_set_fill_detail)
     }
     if (sp && sp->announced.riding() >= SP_SIDE_FILL_PIECES) {
         if (!sp->fill_stream) {
@@ -1033,9 +1076,10 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         const size_t lds = (size_t(1) << logTl) * sizeof(uint32_t);
         const bool id16 = set->id_bits == 16;
         D2G_CHECK(ctx, !(multi && id16), "bitslice: the multi-partition rank kernel with 16-bit ids");
-        void (*kern)(const uint64_t *, size_t, size_t, uint32_t, int, void *, uint32_t *, uint32_t *, int, uint32_t, int, uint32_t *, size_t) = bs_rank_kernel<false, false>;
+        void (*kern)(const uint64_t *, size_t, size_t, uint32_t, int, void *, uint32_t *, uint32_t *, int, uint32_t, int, uint32_t *, size_t, SpRider, uint32_t) = bs_rank_kernel<false, false>;
+        const bool fast = !multi && N <= (size_t)BS_RANK_PF * BS_RANK_THREADS;
         if (multi) kern = bs_rank_kernel<true, false>;
-        else if (N <= (size_t)12 * BS_RANK_THREADS) kern = id16 ? bs_rank_kernel<false, true, uint16_t> : bs_rank_kernel<false, true>;     // PF * BS_RANK_THREADS
+        else if (fast) kern = id16 ? bs_rank_kernel<false, true, uint16_t> : bs_rank_kernel<false, true>;
         else if (id16) kern = bs_rank_kernel<false, false, uint16_t>;
         if (lds > 48 * 1024)
             D2G_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1043,13 +1087,23 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         // prepare that overflowed (status bit 0) may leave pending words behind, and the multi-GPU engine re-uses its exporter sets step
         // after step: ids[] starts from zero in every split prepare -- a few MB for the narrow column slices that are split
         if (nsplit > 1) D2G_HIP(ctx, hipMemsetAsync(set->d_ids, 0, S * Npad * sizeof(uint32_t), s));
+        // a set's first prepare looks at its matrix before it orders it (below); asked HERE, once, because the rank kernel's share of an announced fill
+        // depends on it too
+        const bool look = sparse_path && sp_sample_due(ctx, set);
+        // the FAST rank kernel writes the first pieces of an announced fill itself (D2G_SP_RANK_SHARE) -- when this prepare's path is known as it is enqueued: a
+        // first look may still decide for the dense walk, whose launch fills nothing (a remembered give-up carries nothing at all: announced.begin), and
+        // a large output has its side stream (taken above: nothing is left here)
+        SpRider rank_fill = SP_NO_RIDER; uint32_t rank_n = 0;
+        if (sparse_path && fast && !look && sp->announced.riding() < SP_SIDE_FILL_PIECES)
+            rank_fill = sp->announced.take_first((unsigned)ctx->k2.rank_share, (uint64_t)SP_RANK_FILL_PER_WG * S, &rank_n);
+        D2G_CHECK(ctx, rank_n <= (uint64_t)SP_RANK_FILL_PER_WG * S * nsplit, "bitslice: the rank kernel's share of the fill does not fit its grid");
+        if (sp) sp->dec.fill_rank = rank_n;
         hipLaunchKernelGGL(kern, dim3((unsigned)(S * nsplit)), dim3(BS_RANK_THREADS), lds, s, set->d_cols, N, Npad, set->T, set->logT,
                            (void *)set->d_ids.get(), set->d_colcnt, set->d_meta + set->ntb, ctx->k2.tagbits_max, (uint32_t)S, nsplit,
-                           (sp && nsplit == 1) ? sp->d_owner.get() : (uint32_t *)nullptr, sp ? sp->owner_stride : 0);
+                           (sp && nsplit == 1) ? sp->d_owner.get() : (uint32_t *)nullptr, sp ? sp->owner_stride : 0, rank_fill, rank_n);
         if (sp) sp->dec.kernels = 2 + (join.ev ? 1 : 0);               // the transpose in front of this prepare, the rank kernel (, the side fill)
-        // a set's first prepare looks at its matrix before it orders it: the sample needs the ids only, so it stands HERE and the two kernels
-        // below run while the host waits for its word (sp_sample_collect)
-        const bool look = sparse_path && sp_sample_due(ctx, set);
+        // the first look: the sample needs the ids only, so it stands HERE and the two kernels below run while the host waits for its word
+        // (sp_sample_collect)
         if (look) { if (int rc = sp_sample_enqueue(ctx, set, s)) return rc; if (sp->dec.sample_pending) sp->dec.kernels += 2; }
         // Two schedules from here on.  Behind the rank kernel the chain A = column plan -> planes (reads colcnt and ids; writes perm, meta, the caller's-order
         // stream) and the chain B = the ordering (link pass 0 -> flatten -> link pass 1 -> count -> attach -> scan -> place -> emit: reads ids, owner, labels;
@@ -1082,6 +1136,7 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         if (int rc = sp_prepare_order(ctx, set, nsplit > 1, s)) return rc;
         if (int rc = sp_permute(ctx, set, s)) return rc;
         set->srt_valid = true; set->nat_valid = true;
+        sp->dec.fill_carried = sp->announced.next - sp->dec.fill_rank;
         if (sp->announced.riding()) sp->filled.set_by_riders(sp->announced);
         else sp->filled.void_after_prepare();
         sp->announced.served();
@@ -1265,6 +1320,15 @@ int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t
     return D2G_OK;
 }
 
+// what became of the output announced to the last prepare, in 32 KB pieces: announced, written by the rank kernel, by the prepare's other kernels (the
+// riders; the side fill of a large output), left to the launch.  Host bookkeeping: nothing is synchronised
+void d2g_bitslice_fill_detail(const d2g_cmp_set *set, uint64_t *out4) {
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    if (!set->sp) return;
+    const SpDecision &d = set->sp->dec;
+    out4[0] = d.fill_announced; out4[1] = d.fill_rank; out4[2] = d.fill_carried; out4[3] = d.fill_announced - d.fill_rank - d.fill_carried;
+}
+
 int d2g_sparse_bin_geometry(size_t N, uint32_t *cshift, uint32_t *nch, uint32_t *nbins, int *binned_ok) {
     if (!N) return D2G_ERR_INVALID;
     const SpBinGeom g = sp_bin_geometry(N);
@@ -1295,7 +1359,7 @@ int d2g_bitslice_debug_read(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t s,
 uint64_t d2g_k2_tuning_hash(const d2g_ctx *ctx) {
     const d2g_k2_tuning &t = ctx->k2;
     const long long v[] = {t.sparse, (long long)t.min_n, t.link, (long long)(t.tile_frac * 1e6), t.olink, t.emit_big, t.ride, t.remember, (long long)t.list_div, (long long)t.long_list,
-                           t.list_form, t.predict, t.sort ? 1 : 0, t.tagbits_max, t.nsplit_req, t.merge};
+                           t.list_form, t.predict, t.sort ? 1 : 0, t.tagbits_max, t.nsplit_req, t.merge, t.rank_share};
     uint64_t h = 1469598103934665603ull;
     for (long long x : v) for (int b = 0; b < 8; ++b) { h ^= (uint64_t)(x >> (8 * b)) & 0xFF; h *= 1099511628211ull; }
     return h;
@@ -1305,8 +1369,8 @@ std::string d2g_k2_tuning_json(const d2g_ctx *ctx) {
     const d2g_k2_tuning &t = ctx->k2;
     char b[640];
     std::snprintf(b, sizeof b, "{\"D2G_BS_SPARSE\": %d, \"D2G_BS_SPARSE_MIN_N\": %zu, \"D2G_BS_SORT\": %d, \"D2G_SP_LINK\": %d, \"D2G_SP_OLINK\": %d, \"D2G_SP_TILE_FRAC\": %.3f, "
-                  "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d, \"D2G_K2_MERGE\": %d, \"D2G_BS_ID16\": %d}",
-                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big, t.merge, t.id16);
+                  "\"D2G_SP_LIST_DIV\": %zu, \"D2G_SP_LONG_LIST\": %zu, \"D2G_SP_LIST_FORM\": %d, \"D2G_SP_PREDICT\": %d, \"D2G_SP_REMEMBER\": %d, \"D2G_SP_RIDE\": %d, \"D2G_SP_EMIT_BIG\": %d, \"D2G_K2_MERGE\": %d, \"D2G_BS_ID16\": %d, \"D2G_SP_RANK_SHARE\": %d}",
+                  t.sparse ? 1 : 0, t.min_n, t.sort ? 1 : 0, t.link, t.olink, t.tile_frac, t.list_div, t.long_list, t.list_form, t.predict, t.remember, t.ride, t.emit_big, t.merge, t.id16, t.rank_share);
     return b;
 }
 

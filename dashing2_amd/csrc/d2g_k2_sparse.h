@@ -255,7 +255,9 @@ __global__ __launch_bounds__(256) void sp_flatten_kernel(uint32_t *label, size_t
 // NEXT launch waits for tends to start first; flatten's forty workgroups stand in front of the planes' for the same reason.  The 2-D grids are linearised.
 // (Measured, profiles/k2_merged_prepare.txt: the planes workgroups beside link pass 1, beside the scan's one workgroup, and handed out in shares to flatten /
 // count / attach / place like the fill's riders -- the step takes the same time within 2 us: the planes body moves 60 MB itself and every host already
-// carries a share of the fill, so it costs ~13 us of chain time wherever it stands.  The plan and flatten, a few workgroups each, do disappear.)
+// carries a share of the fill, so it costs ~13 us of chain time wherever it stands.  The plan and flatten, a few workgroups each, do disappear.
+// Measured AGAIN with the fill gone from the hosts (the rank kernel writes it; profiles/k2_rank_fill.txt section 7): thirds over count / attach / place take
+// 11 us off the flatten launch and put 11 us onto the three hosts; no split beats all-beside-flatten.  Dropped again.)
 template <typename IdT = uint32_t>
 __global__ __launch_bounds__(256) void sp_link0_plan_kernel(BsPlanArgs pa, SpOlinkArgs la, uint32_t nx, SpRider rider) {
     SP_RIDE_OR_WORK(rider);

@@ -683,6 +683,12 @@ int  d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream,
  * planes inside launches of the ordering), 0 = classic (kernel by kernel: D2G_K2_MERGE=0, a first look, a remembered give-up, the table form of the link
  * passes, split rank passes), [9] the kernels that prepare enqueued, the transpose included.  out10: TEN words.  Nothing in the product reads these back. */
 int  d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out10);
+/* what became of the output announced to the set's last prepare (d2g_cmp_ut_announce_dev), in pieces of 32 KB: [0] the pieces announced (0: nothing was
+ * announced, or it was cancelled), [1] those the rank kernel's own threads wrote (bit 64 of D2G_SP_RIDE; the single-partition register kernel, N <= 12 288,
+ * on a prepare whose path is known when it is enqueued), [2] those the prepare's other kernels carried (rider workgroups; the side stream of an output of
+ * 1 GB and more), [3] those left to the launch.  [1] + [2] + [3] = [0].  Host bookkeeping only: nothing is synchronised, no stream is touched; all 0 for a
+ * set without a sparse path.  out4: FOUR words.  Nothing in the product reads these back. */
+int  d2g_cmp_set_fill_detail(d2g_ctx *ctx, const d2g_cmp_set *set, uint64_t *out4);
 /* the output bins of the pair list of a set of N sketches (bands of 32 rows x chunks of 2^cshift columns): what a set's allocation computes.
  * binned_ok = 0: more bands than bins fit, the list is applied entry by entry (nbins = 0).  Host arithmetic, no context. */
 int  d2g_sparse_bin_geometry(size_t N, uint32_t *cshift, uint32_t *nch, uint32_t *nbins, int *binned_ok);
@@ -724,7 +730,8 @@ int  d2g_cmp_ut_prefill_dev(d2g_ctx *ctx, d2g_cmp_set *set, size_t r0, size_t r1
  *     d2g_cmp_ut_announce_dev(ctx, set, r0, r1, ...);  d2g_cmp_set_update_dev(ctx, set, sigs, stream);  d2g_cmp_lut_ut_dev(..., stream);
  * The announcement serves exactly one prepare; the launch must follow on the prepare's stream with the same rows and output (any other
  * launch simply fills for itself).  lut_dev must hold the table by the time the prepare runs on its stream.  Nothing is enqueued here.
- * A no-op for sets that would not fill; D2G_SP_RIDE=0 turns the riding off (the launch fills as before).
+ * A no-op for sets that would not fill; D2G_SP_RIDE=0 turns the riding off (the launch fills as before); d2g_cmp_set_fill_detail says which
+ * kernels of the prepare wrote how much of it.
  * The set keeps the announced pointer until its next prepare: a caller that frees the output before that prepare CANCELS the announcement
  * with neq_out_dev = out_dev = NULL.  A launch skips its own fill only where the announced (or pre-filled) output, rows AND fill value --
  * the count 0, or the table pointer -- are its own; a table whose first entry changes between the prepare and the launch is the caller's

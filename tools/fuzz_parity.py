@@ -94,7 +94,7 @@ def main():
                 # (D2G_SP_LINK=0: the pair list alone), any tile budget, a short list (overflow -> dense walk), the list applied entry by
                 # entry or binned + composed, with or without the first look at the matrix; the other half takes the default (dense walk
                 # below 8192 sketches)
-                for var in ("D2G_SP_RIDE", "D2G_BS_SPARSE_MIN_N", "D2G_SP_LINK", "D2G_SP_TILE_FRAC", "D2G_SP_LIST_DIV", "D2G_SP_OLINK", "D2G_SP_REMEMBER", "D2G_SP_EMIT_BIG",
+                for var in ("D2G_SP_RIDE", "D2G_SP_RANK_SHARE", "D2G_BS_SPARSE_MIN_N", "D2G_SP_LINK", "D2G_SP_TILE_FRAC", "D2G_SP_LIST_DIV", "D2G_SP_OLINK", "D2G_SP_REMEMBER", "D2G_SP_EMIT_BIG",
                             "D2G_SP_LIST_FORM", "D2G_SP_PREDICT", "D2G_K2_MERGE"):
                     os.environ.pop(var, None)
                 if rng.random() < 0.5:
@@ -146,7 +146,8 @@ def main():
                 if os.environ.get("D2G_BS_SPARSE_MIN_N") == "1" and N > 3 and rng.random() < 0.6:
                     # the announced output (d2g_cmp_ut_announce_dev): any subset of the prepare's small kernels carries the fill, the
                     # launch finishes it; a row range, a 4-byte aligned output, counts against the oracle; then a launch nobody announced
-                    os.environ["D2G_SP_RIDE"] = str(int(rng.integers(0, 64)))
+                    os.environ["D2G_SP_RIDE"] = str(int(rng.integers(0, 128)))           # (bit 64: the FAST rank kernel's own stores)
+                    os.environ["D2G_SP_RANK_SHARE"] = str(int(rng.integers(0, 36)))
                     ctx.reload_tuning()
                     bits = np.ascontiguousarray(sig.view(np.uint64))
                     neq = O.eqcounts_ut(sig)
@@ -172,6 +173,7 @@ def main():
                     finally:
                         ctx.free(d_sig); ctx.free(d_out)
                     os.environ.pop("D2G_SP_RIDE", None)
+                    os.environ.pop("D2G_SP_RANK_SHARE", None)
             elif which == "k3":
                 k = int(rng.integers(3, 33)); S = int(rng.choice([16, 100, 256, 2048])); canon = bool(rng.integers(0, 2))
                 thr = float(rng.choice([0, 0, 1, 3]))

@@ -22,8 +22,16 @@ regs = synth.unrelated_registers(N, S) if which == "unrelated" else synth.synthe
 t = torch.from_numpy(regs.view(np.int64)).to(dev)
 st = torch.cuda.current_stream().cuda_stream
 cs = ctx.cmp_set_dev(t.data_ptr(), N, S, algo=D.CMP_BITSLICE, stream=st)
+ANNOUNCE = os.environ.get("ANNOUNCE", "0") == "1"   # the next launch's output announced ahead of every prepare: the FAST kernel writes its share of the fill (D2G_SP_RIDE bit 64)
+if ANNOUNCE:
+    out = torch.empty(N * (N - 1) // 2, dtype=torch.float32, device=dev)
+    lut = torch.from_numpy(D.epilogue_lut(S, D.SIMILARITY, 31)).to(dev)
 for _ in range(4):
+    if ANNOUNCE:
+        cs.announce_ut_dev(out.data_ptr(), 0, N, lut_dev_ptr=lut.data_ptr())
     cs.update_dev(t.data_ptr(), st)
+if ANNOUNCE and hasattr(cs, "fill_detail") and "parent" not in os.environ.get("D2G_LIB", ""):
+    print("fill_detail of the traced prepare:", cs.fill_detail())
 torch.cuda.synchronize()
 buf = np.zeros(8192 * 16, dtype=np.uint64)
 f = lib().d2g_debug_rank_trace
