@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get("D2G_LIB") or os.path.join(_HERE, "libd2g.so")
 _lib = None
 
 SIMILARITY, CONTAINMENT, SYMMETRIC_CONTAINMENT, POISSON_LLR, INTERSECTION, UNION_SIZE = range(6)
+K2_SCHEDULES = ("classic", "merged", "planes-emit")     # D2G_K2_MERGE = 0, 1, 2: the bit-sliced prepare's schedule (CmpSet.sparse_detail)
 CMP_AUTO, CMP_DIRECT, CMP_BITSLICE, CMP_PLANES = 0, 1, 2, 3
 # bit-sliced pair kernel: VALU operations per pair and 32-register group = (id planes of the group) + this (one v_bcnt)
 BITSLICE_OPS_PER_GROUP_EXTRA = 1
@@ -1513,12 +1514,13 @@ class CmpSet:
         return sparse_info_dict(a)
 
     def sparse_detail(self, stream=None):
-        """-> dict of the last prepare's first look (its decision and raw sums), list form and schedule -- "merged" (column plan and planes inside
-        launches of the ordering) or "classic" -- with the kernels it enqueued, the transpose included (synchronises; zeros without a sparse path)"""
+        """-> dict of the last prepare's first look (its decision and raw sums), list form and schedule -- "classic", "merged" (column plan and planes
+        inside launches of the ordering: D2G_K2_MERGE=1) or "planes-emit" (the planes behind the pair-list kernel's workgroups: D2G_K2_MERGE=2); "merge" is
+        the same as the switch's number -- with the kernels it enqueued, the transpose included (synchronises; zeros without a sparse path)"""
         a = np.zeros(10, np.uint64)
         self.ctx._check(lib().d2g_cmp_set_sparse_detail(self.ctx._h, self._h, stream, a.ctypes.data))
         return {"looked": bool(a[0]), "looked_dense": bool(a[1]), "entries": int(a[2]), "family_pairs": int(a[3]), "shared_values": int(a[4]),
-                "planes": int(a[5]), "binned": bool(a[6]), "bin_cshift": int(a[7]), "schedule": "merged" if a[8] else "classic", "prepare_kernels": int(a[9])}
+                "planes": int(a[5]), "binned": bool(a[6]), "bin_cshift": int(a[7]), "schedule": K2_SCHEDULES[min(int(a[8]), 2)], "merge": int(a[8]), "prepare_kernels": int(a[9])}
 
     def fill_detail(self):
         """-> dict of what became of the output announced to the last prepare, in 32 KB pieces: "announced", "rank" (written by the rank kernel's own

@@ -86,7 +86,7 @@ struct d2g_k2_tuning {
     int emit_big = 0;                   // D2G_SP_EMIT_BIG: sp_emit_kernel counts with two words per value at every N (it does from N = 65 536 on; tests)
     int ride = 127;                     // D2G_SP_RIDE: which kernels of the prepare carry an announced output's fill (d2g_cmp_ut_announce_dev) -- 1 column plan (merged schedule: the launch that contains it), 2 flatten (likewise), 4 count, 8 attach, 16 scan, 32 place, 64 the FAST rank kernel's own threads (N <= 12 288; 63 = riders only, as before it); 0 = none, the launch fills (measurements)
     int rank_share = 35;                // D2G_SP_RANK_SHARE: 0 .. 35, the part of an announced fill (in 35ths, like the riders' weights: SP_RW_ALL) the FAST rank kernel writes where bit 64 of D2G_SP_RIDE lets it; at most what its grid holds, six pieces per column (measurements, tests)
-    int merge = 1;                      // D2G_K2_MERGE: 0 = the prepare's classic schedule, kernel by kernel (column plan and planes in front of the link passes) instead of the merged launches (A/B measurements, tests)
+    int merge = 2;                      // D2G_K2_MERGE: the prepare's schedule -- 0 = classic, kernel by kernel (column plan and planes in front of the link passes); 1 = merged launches, the planes beside flatten; 2 = merged launches, the planes behind the pair-list kernel's workgroups (d2g_bitslice_prepare; A/B measurements, tests)
     int remember = 1;                   // D2G_SP_REMEMBER: 0 = every prepare runs the ordering, whatever the last one decided
     size_t long_list = 786432;          // D2G_SP_LONG_LIST: a pair list of this many entries or more is binned and composed (the last prepare's length decides)
     int predict = 1;                    // D2G_SP_PREDICT: 0 = no sample before the ordering of a set's first prepare (the ordering finds out by itself, as in round 5)

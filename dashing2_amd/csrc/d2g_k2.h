@@ -16,6 +16,8 @@ inline size_t sp_fill_pieces(size_t cnt) { return div_up<size_t>(cnt / 4 + 1, (s
 // launches that CONTAIN the column plan (link pass 0) and flatten (the planes body); they last ~20 and ~17 us but stream the ids themselves, so their
 // shares are not their durations but what was fitted on the GPU (profiles/k2_merged_prepare.txt section 4): the step is flat between 3 and 8 parts for
 // either of them, and 2 us slower with 12 parts on the link launch or with fewer than ~8 on the two together (the rest lands on place).
+// Schedule 2 (the planes behind emit's workgroups): bit 2's host is flatten alone again, forty workgroups; it keeps SP_RW_M_PLANES -- NOT re-fitted
+// (profiles/k2_planes_emit.txt says so); emit, the planes' new host, carries no riders.
 #ifndef D2G_SP_RW_M_LINK0
 #define D2G_SP_RW_M_LINK0 8
 #endif
@@ -117,7 +119,7 @@ enum SpMappedWord : uint32_t { SP_MW_GAVEUP = 0, SP_MW_LIST_LEN = 1, SP_MW_SUMS 
 // which way a prepare goes: the first look at the matrix, the remembered give-up, the form of the pair list
 struct SpDecision {
     unsigned prepares = 0; bool skipped = false;   // prepares so far; the last one skipped the ordering
-    bool merged = false; unsigned kernels = 0;     // the last prepare: it ran the merged schedule (d2g_bitslice_prepare); the kernels it enqueued, the transpose included (diagnostics)
+    int merged = 0; unsigned kernels = 0;          // the last prepare: the schedule it ran -- 0 classic, 1 merged (planes beside flatten), 2 merged (planes behind emit) (d2g_bitslice_prepare); the kernels it enqueued, the transpose included (diagnostics)
     int skip_cached = -1;             // this prepare's reading of the remembered give-up (-1: not read yet)
     bool sample_pending = false; uint32_t sample_ticket = 0;   // the first look's kernels are enqueued; the value their last workgroup writes to the ticket word when the sums are in
     bool pred_valid = false, pred_dense = false; double pred_entries = 0, pred_family_pairs = 0;   // what the sample of THIS prepare says (valid until its ordering has been enqueued)

@@ -479,7 +479,8 @@ __device__ __forceinline__ size_t stream_slot_wave(const uint32_t *meta, int tb)
 // The fill of an upper-triangle launch (every output = "no register equal", 4 bytes per pair: 200 MB at config 3, 31 us of pure HBM
 // writes) depends on nothing the prepare computes, and six kernels of the prepare chain are one to forty workgroups waiting out
 // dependent round trips on an otherwise idle chip (column plan, flatten, count, attach, scan, place: 36 us together at config 3; in the merged schedule
-// the first two hosts are the launches that CONTAIN the column plan and flatten: sp_link0_plan_kernel, bs_planes_flatten_kernel).  When the
+// the first two hosts are the launches that CONTAIN the column plan and flatten: sp_link0_plan_kernel, bs_planes_flatten_kernel -- in schedule 2, where the
+// planes stand behind emit's workgroups, the second is sp_flatten_kernel itself again).  When the
 // output is announced ahead of the prepare (d2g_cmp_ut_announce_dev) those kernels are launched with extra workgroups BEHIND their own --
 // the dispatcher starts workgroups in index order, the kernel's own work is never queued behind a rider -- each writing one 32 KB piece.
 // (The same fill on a second stream was measured in rounds 4 and 5: the two cross-stream dependencies cost more than the fill.)
@@ -656,13 +657,14 @@ struct BsPlanesArgs {
 BsPlanesArgs planes_args_of(const d2g_cmp_set *set, uint32_t *planes, int forms) {
     return BsPlanesArgs{set->d_ids.get(), set->N, set->Npad, planes, set->d_stream, set->Nstride, set->nbits_cap, set->d_meta, forms, set->d_perm, set->d_colcnt, nullptr};
 }
-// the body of workgroup (bx, tb) of the grid ceil(Nstride / 256) x ntb: 256 threads (bs_planes_kernel; the merged planes launch, bs_planes_flatten_kernel)
+// the body of workgroup (bx, tb) of the grid ceil(Nstride / 256) x ntb: 256 threads (bs_planes_kernel; the merged planes launch, bs_planes_flatten_kernel;
+// `tid`: the thread's index among them where the block is larger -- sp_emit_kernel<IdT, true> runs two of these bodies in one block of 512, whole waves each)
 // (16-bit ids: one 2-byte load per lane and column, a wave reads 128 consecutive bytes.  Measured and dropped: TWO adjacent positions per thread -- one 32-bit
 // load holds both ids, the bit transpose runs on the packed words (bit b and bit b + 16), the two words of a plane leave as one 8-byte store; half the
 // workgroups and half the load instructions -- the planes launch of the merged schedule took 19.6 us instead of 17.5 at config 3 (32-bit ids: 18.4):
 // the same VALU work in half as many waves hides the loads worse.  profiles/k2_id16.txt)
 template <bool SPLIT, typename IdT = uint32_t>
-__device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx, size_t tb) {
+__device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx, size_t tb, uint32_t tid = threadIdx.x) {
     static_assert(!SPLIT || sizeof(IdT) == 4, "bs_planes_body: split ranks are 32-bit ids");
     constexpr int UBIT = BsId<IdT>::UBIT;
     const IdT *__restrict__ ids = static_cast<const IdT *>(a.ids);
@@ -670,7 +672,7 @@ __device__ __forceinline__ void bs_planes_body(const BsPlanesArgs &a, size_t bx,
     uint32_t *__restrict__ planes = a.planes, *__restrict__ stream = a.stream;
     const size_t N = a.N, Npad = a.Npad, Nstride = a.Nstride;
     const int nbits_cap = a.nbits_cap, forms = a.forms;
-    const size_t jpos = bx * 256 + threadIdx.x;   // position in the operand
+    const size_t jpos = bx * 256 + tid;           // position in the operand
     const size_t slot = (forms & BS_FORM_STREAM) ? stream_slot_wave(meta, (int)tb) : 0;     // (every lane still here)
     if (jpos >= Nstride) return;
     // sperm: the operand written in another order -- position p holds sketch sperm[p] (stream form only; unused: the sparse path permutes the finished stream)
@@ -1105,16 +1107,20 @@ int d2g_bitslice_prepare(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
         // the first look: the sample needs the ids only, so it stands HERE and the two kernels below run while the host waits for its word
         // (sp_sample_collect)
         if (look) { if (int rc = sp_sample_enqueue(ctx, set, s)) return rc; if (sp->dec.sample_pending) sp->dec.kernels += 2; }
-        // Two schedules from here on.  Behind the rank kernel the chain A = column plan -> planes (reads colcnt and ids; writes perm, meta, the caller's-order
+        // Three schedules from here on.  Behind the rank kernel the chain A = column plan -> planes (reads colcnt and ids; writes perm, meta, the caller's-order
         // stream) and the chain B = the ordering (link pass 0 -> flatten -> link pass 1 -> count -> attach -> scan -> place -> emit: reads ids, owner, labels;
         // writes labels, hints, counts, sperm / sinv, tile bitmap, list) meet only in sp_permute.
         //   classic   A in front of B, kernel by kernel: rank, plan, planes, link 0, flatten, link 1, count, attach, scan, place, emit, permute
         //   merged    A inside launches of B (sp_launch_merged):   rank, [plan + link 0], [flatten + planes], link 1, count, attach, scan, place, emit, permute
         //             (two launches and ~9 us fewer per step at config 3: profiles/k2_merged_prepare.txt)
-        // The merged one needs the streaming link form on unsplit columns, and a prepare whose path is known when it is enqueued: the first prepare of a set and
+        //   merged 2  the planes, which nobody reads before sp_permute, leave the ordering's critical path: they stand BEHIND the pair-list kernel's workgroups,
+        //             whose clean columns are done after half the launch (sp_emit_kernel<IdT, true>):
+        //                                                          rank, [plan + link 0], flatten, link 1, count, attach, scan, place, [emit + planes], permute
+        //             (profiles/k2_planes_emit.txt)
+        // The merged ones need the streaming link form on unsplit columns, and a prepare whose path is known when it is enqueued: the first prepare of a set and
         // the retry of a remembered give-up decide between dense and sparse on the host BEHIND the rank kernel (the first look) -- link pass 0 must not be
         // enqueued before that -- and a remembered give-up runs no ordering at all.  Exporter and exchange sets have no ordering.  D2G_K2_MERGE=0: classic.
-        const bool merged = sparse_path && !look && ctx->k2.merge && nsplit == 1 && sp->d_owner && ctx->k2.olink && ctx->k2.link && sp->dec.skip_cached != 1;
+        const int merged = (sparse_path && !look && ctx->k2.merge && nsplit == 1 && sp->d_owner && ctx->k2.olink && ctx->k2.link && sp->dec.skip_cached != 1) ? ctx->k2.merge : 0;
         if (sp) sp->dec.merged = merged;
         if (!merged) {
             unsigned g = 1; const SpRider rd = sp ? sp->announced.take(1, SP_RW_PLAN, false, 1, &g) : SP_NO_RIDER;
@@ -1271,7 +1277,7 @@ int d2g_bitslice_managed_sparse_alloc(d2g_ctx *ctx, d2g_cmp_set *set) {
 int d2g_bitslice_managed_ready(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
     if (!set->borrowed || !set->sparse_ok()) return D2G_OK;
     dim3 grid((unsigned)div_up<size_t>(set->Npad, 256), (unsigned)set->ntb);
-    set->sp->dec.merged = false; set->sp->dec.kernels = 1;            // (diagnostics: the unpack kernel, then the classic chain)
+    set->sp->dec.merged = 0; set->sp->dec.kernels = 1;            // (diagnostics: the unpack kernel, then the classic chain)
     hipLaunchKernelGGL(sp_unpack_kernel, grid, dim3(256), 0, s, set->d_planes, set->Nstride, set->nbits_cap, set->d_meta, set->N, set->Npad, set->d_ids, set->d_colcnt, sp_init_of(set));
     if (int rc = sp_prepare_order(ctx, set, false, s)) return rc;
     if (int rc = sp_permute(ctx, set, s)) return rc;
@@ -1316,7 +1322,7 @@ int d2g_bitslice_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, hipStream_t
     out8[0] = sp.dec.looked ? 1 : 0; out8[1] = sp.dec.looked_dense ? 1 : 0;
     if (sp.dec.looked) for (int x = 0; x < 4; ++x) out8[2 + x] = sp.dec.samp_sums[x];   // (a prepare that did not look reports no sums: those of an earlier look are not its own)
     out8[6] = binned ? 1 : 0; out8[7] = sp.bin_cshift;
-    out8[8] = sp.dec.merged ? 1 : 0; out8[9] = sp.dec.kernels;
+    out8[8] = (uint64_t)sp.dec.merged; out8[9] = sp.dec.kernels;
     return D2G_OK;
 }
 

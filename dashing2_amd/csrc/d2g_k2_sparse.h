@@ -25,7 +25,8 @@
 //          sp_flatten between the two link passes; sp_attach behind them: a sketch no column pair linked joins the family its hints -- some
 //                     holder of a value it shares, recorded by even and by odd column pairs -- point to (a weak member, families of two);
 //          sp_count / scan / place   counting sort by root -> sperm / sinv, the segments, keep-the-caller's-order decision;
-//          sp_emit    (b) above (the segments' tiles are set by the sort's place kernel);
+//          sp_emit    (b) above (the segments' tiles are set by the sort's place kernel); in schedule 2 of the prepare (D2G_K2_MERGE=2, the default) the
+//                     same launch carries, BEHIND emit's workgroups, the workgroups that write the caller's-order plane stream (sp_emit_kernel<IdT, true>);
 //          sp_permute the finished plane stream in sorted order.
 // launch   sp_list -> sp_fill -> k2_bitslice_sparse_kernel (listed tiles; stores the non-zero counts) -> sp_patch_add (list entries
 //          outside listed tiles: atomicAdd of 1 onto the filled word; the first adder of a position is its leader) -> sp_patch_lut (table
@@ -257,7 +258,10 @@ __global__ __launch_bounds__(256) void sp_flatten_kernel(uint32_t *label, size_t
 // count / attach / place like the fill's riders -- the step takes the same time within 2 us: the planes body moves 60 MB itself and every host already
 // carries a share of the fill, so it costs ~13 us of chain time wherever it stands.  The plan and flatten, a few workgroups each, do disappear.
 // Measured AGAIN with the fill gone from the hosts (the rank kernel writes it; profiles/k2_rank_fill.txt section 7): thirds over count / attach / place take
-// 11 us off the flatten launch and put 11 us onto the three hosts; no split beats all-beside-flatten.  Dropped again.)
+// 11 us off the flatten launch and put 11 us onto the three hosts; no split beats all-beside-flatten.  Dropped again.
+// A host that HAS room: sp_emit_kernel -- its workgroups on clean columns are done after ~7 of its 19 us, LDS-bound, the HBM idle, and it carries no riders.
+// Schedule 2 puts the planes workgroups behind emit's (sp_emit_kernel<IdT, true>, below): the planes launch here is then flatten alone (sp_flatten_kernel
+// with the same riders), 16 -> 5 us, and emit 19 -> 25: profiles/k2_planes_emit.txt.)
 template <typename IdT = uint32_t>
 __global__ __launch_bounds__(256) void sp_link0_plan_kernel(BsPlanArgs pa, SpOlinkArgs la, uint32_t nx, SpRider rider) {
     SP_RIDE_OR_WORK(rider);
@@ -512,10 +516,34 @@ __device__ unsigned long long g_emit_trace[4096 * 16];
 // 32 768 of them -- every column below 65 536 sketches is ONE step, pass A + pass B
 // (1024 threads and 2560 values per step -- every column of config 3 ONE step, two workgroups per CU -- was measured: 35 us against 24 clean, 108 against 78 at c = 10)
 constexpr uint32_t SP_EMIT_VCAP = 1536, SP_EMIT_ECAP = 32768, SP_EMIT_T = D2G_SP_EMIT_T;
-template <typename IdT = uint32_t>
+// PLANES -- schedule 2 of the prepare (d2g_bitslice_prepare): the caller's-order planes BEHIND emit's workgroups, in emit's block shape.  Emit's workgroups on
+// clean columns are done after half the launch and only the few with a mixed value run on (LDS-bound, the HBM idle); nobody reads the planes' stream before
+// sp_permute, which is enqueued behind this launch anyway, and neither body reads what the other writes (emit: ids, colcnt, segments, order -> entry stream,
+// records, list cursors; planes: ids, perm, meta -> the stream).  Blocks [0, ncols) are emit, unchanged; block ncols + b takes items 2 b and 2 b + 1 of the
+// linearised (bx, tb) grid of 256-thread planes work (gx = ceil(Nstride / 256) wide, nitems in all) -- four waves each; the second is missing where the item
+// count is odd.  The planes blocks leave for their body BEFORE emit's order[0] / d2 == 0 returns and before any barrier: when emit gives up, the dense walk
+// reads this stream.  No LDS of their own, no flag.  (One kernel with a flag, not a body shared by two kernels: as an inlined
+// function the emit body took a private segment in BOTH kernels -- 12 bytes of scratch, two VGPRs spilled.  profiles/k2_planes_emit.txt section 1)
+template <typename IdT = uint32_t, bool PLANES = false>
 __global__ __launch_bounds__(SP_EMIT_T) __attribute__((amdgpu_waves_per_eu(8, 8))) void sp_emit_kernel(const void *__restrict__ ids_void, size_t N, size_t Npad, uint32_t ncols, const uint32_t *__restrict__ colcnt, int split,
                                                             const uint32_t *__restrict__ seg, uint32_t *__restrict__ order,
-                                                            SpColWork cw, uint32_t *__restrict__ plctl, uint32_t plcap, uint32_t *__restrict__ gaveup, int big) {
+                                                            SpColWork cw, uint32_t *__restrict__ plctl, uint32_t plcap, uint32_t *__restrict__ gaveup, int big,
+                                                            BsPlanesArgs pl, uint32_t gx, uint32_t nitems) {
+    if constexpr (PLANES) {
+        if (blockIdx.x >= ncols) {
+            // (uniform per wave, and said so: the group's 32 column slots stay scalar loads and the item's coordinates scalar arithmetic, as in a kernel whose
+            // block index names the item -- as a per-lane value the slots took 32 VGPRs beside the 32 ids and the kernel a private segment)
+            const uint32_t item = (blockIdx.x - ncols) * 2u + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
+#ifdef D2G_SP_TRACE
+            if ((threadIdx.x & 255u) == 0 && blockIdx.x < 4096) g_emit_trace[blockIdx.x * 16 + (threadIdx.x >> 8)] = __builtin_amdgcn_s_memrealtime();
+#endif
+            if (item < nitems) bs_planes_body<false, IdT>(pl, item % gx, item / gx, threadIdx.x & 255u);
+#ifdef D2G_SP_TRACE
+            if ((threadIdx.x & 255u) == 0 && blockIdx.x < 4096) g_emit_trace[blockIdx.x * 16 + 2 + (threadIdx.x >> 8)] = __builtin_amdgcn_s_memrealtime();
+#endif
+            return;
+        }
+    }
     __shared__ uint32_t first[SP_EMIT_VCAP];
     __shared__ uint32_t cnt[SP_EMIT_VCAP];                // pass A: insiders | outsiders << 16 (big: [q] and [1024 + q]); in a round: the two cursors of a mixed value
     __shared__ uint32_t mrec[SP_EMIT_VCAP];               // the step's mixed values: first entry | q << 16
@@ -1729,6 +1757,8 @@ int sp_sample_collect(d2g_ctx *ctx, d2g_cmp_set *set, hipStream_t s) {
 
 // the merged schedule's two launches (sp_link0_plan_kernel, bs_planes_flatten_kernel): column plan + link pass 0 (`l0`; null: a single column, no link
 // pass), then flatten (`nflat` workgroups; none for a single column) + planes.  Bits 1 and 2 of D2G_SP_RIDE name these two launches.
+// Schedule 2: the second launch is flatten ALONE, with the riders and the weight (SP_RW_M_PLANES, not re-fitted) of schedule 1's -- the planes stand behind emit
+// (sp_emit_kernel<IdT, true>, launched by sp_prepare_order).  A single column has no flatten and so no second launch at all there: emit carries its planes too.
 int sp_launch_merged(d2g_ctx *ctx, d2g_cmp_set *set, const SpOlinkArgs *l0, unsigned nx, unsigned npair, unsigned nflat, hipStream_t s) {
     SpState &sp = *set->sp;
     const BsPlanArgs pa{set->d_colcnt, (uint32_t)set->S, set->ntb, 1, set->d_perm, set->d_meta, set->d_meta + set->ntb, set->ex_meta, set->ex_status, ctx->k2.sort ? 1 : 0};
@@ -1738,9 +1768,14 @@ int sp_launch_merged(d2g_ctx *ctx, d2g_cmp_set *set, const SpOlinkArgs *l0, unsi
     unsigned g;
     SpRider rd = sp.announced.take((unsigned)(1 + nlink), SP_RW_M_LINK0, false, 1, &g);
     hipLaunchKernelGGL((id16 ? sp_link0_plan_kernel<uint16_t> : sp_link0_plan_kernel<uint32_t>), dim3(g), dim3(256), bs_plan_lds_words((uint32_t)set->ntb * 32u, pa.sort) * 4, s, pa, l0 ? *l0 : SpOlinkArgs{}, (uint32_t)nx, rd);
-    rd = sp.announced.take((unsigned)(nflat + nplanes), SP_RW_M_PLANES, false, 2, &g);
-    hipLaunchKernelGGL((id16 ? bs_planes_flatten_kernel<uint16_t> : bs_planes_flatten_kernel<uint32_t>), dim3(g), dim3(256), 0, s, planes_args_of(set, set->d_planes, BS_FORM_STREAM), (uint32_t)gx, (uint32_t)nflat, sp.d_label.get(), rd);
-    sp.dec.kernels += 2;
+    if (sp.dec.merged == 2) {
+        if (nflat) { rd = sp.announced.take(nflat, SP_RW_M_PLANES, false, 2, &g); hipLaunchKernelGGL(sp_flatten_kernel, dim3(g), dim3(256), 0, s, sp.d_label.get(), set->N, rd); }
+        sp.dec.kernels += nflat ? 2 : 1;
+    } else {
+        rd = sp.announced.take((unsigned)(nflat + nplanes), SP_RW_M_PLANES, false, 2, &g);
+        hipLaunchKernelGGL((id16 ? bs_planes_flatten_kernel<uint16_t> : bs_planes_flatten_kernel<uint32_t>), dim3(g), dim3(256), 0, s, planes_args_of(set, set->d_planes, BS_FORM_STREAM), (uint32_t)gx, (uint32_t)nflat, sp.d_label.get(), rd);
+        sp.dec.kernels += 2;
+    }
     D2G_HIP(ctx, hipGetLastError());
     return D2G_OK;
 }
@@ -1826,8 +1861,17 @@ int sp_prepare_order(d2g_ctx *ctx, d2g_cmp_set *set, bool split, hipStream_t s) 
     // columns where nothing crosses a segment need no workgroup here -- was measured: 17 us for the pass, and the 17 stragglers a clean
     // collection of 10 000 leaves still put a mixed value into a hundred columns, whose workgroups take as long as before: 0.338 vs 0.329 ms)
     const SpColWork cw = sp_colwork_of(sp);
+    if (sp.dec.merged == 2) {
+        // schedule 2: the caller's-order planes behind emit's workgroups, two 256-thread items of their (bx, tb) grid per block of SP_EMIT_T
+        static_assert(SP_EMIT_T == 512, "sp_emit_kernel<IdT, true>: a block takes two 256-thread planes items");
+        const size_t gx = div_up<size_t>(set->Nstride, 256), nitems = gx * (size_t)set->ntb;
+        D2G_CHECK(ctx, !split && S + div_up<size_t>(nitems, 2) < 0x40000000u, "bitslice sparse: the emit + planes launch does not fit a grid");
+        hipLaunchKernelGGL((id16 ? sp_emit_kernel<uint16_t, true> : sp_emit_kernel<uint32_t, true>), dim3((unsigned)(S + div_up<size_t>(nitems, 2))), dim3(SP_EMIT_T), 0, s, ids, N, Npad, (uint32_t)S, set->d_colcnt, 0, lb, sp.d_order,
+                           cw, sp.d_plctl, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), sp.d_gaveup, (N >= 65536 || tu.emit_big) ? 1 : 0,
+                           planes_args_of(set, set->d_planes, BS_FORM_STREAM), (uint32_t)gx, (uint32_t)nitems);
+    } else
     hipLaunchKernelGGL((id16 ? sp_emit_kernel<uint16_t> : sp_emit_kernel<uint32_t>), dim3((unsigned)S), dim3(SP_EMIT_T), 0, s, ids, N, Npad, (uint32_t)S, set->d_colcnt, split ? 1 : 0, lb, sp.d_order,
-                       cw, sp.d_plctl, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), sp.d_gaveup, (N >= 65536 || tu.emit_big) ? 1 : 0);
+                       cw, sp.d_plctl, (uint32_t)std::min<size_t>(sp.plist_cap, 0xFFFFFFFFu), sp.d_gaveup, (N >= 65536 || tu.emit_big) ? 1 : 0, BsPlanesArgs{}, 0u, 0u);
     // the pairs of the mixed values: a kernel of its own when the list is expected to be long (it must be complete before the workgroups that
     // count it per bin, which ride on the permute launch); otherwise extra workgroups of the permute launch itself (sp_permute)
     if (sp.dec.big) hipLaunchKernelGGL(sp_pairs_kernel, dim3((unsigned)ctx->num_cus * 8), dim3(256), 0, s, sp_pairs_of(sp, cw, lb));

@@ -29,7 +29,7 @@ d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t) {
     if (const char *e = t.get("D2G_SP_LINK")) v.link = std::atoi(e) != 0;
     if (const char *e = t.get("D2G_SP_TILE_FRAC")) { const double f = std::atof(e); if (f > 0 && f <= 1) v.tile_frac = f; }
     if (const char *e = t.get("D2G_SP_OLINK")) v.olink = std::atoi(e) != 0;
-    if (const char *e = t.get("D2G_K2_MERGE")) v.merge = std::atoi(e) != 0;
+    if (const char *e = t.get("D2G_K2_MERGE")) { const int d = std::atoi(e); v.merge = d <= 0 ? 0 : d >= 2 ? 2 : 1; }
     if (const char *e = t.get("D2G_SP_EMIT_BIG")) v.emit_big = std::atoi(e) != 0;
     if (const char *e = t.get("D2G_SP_REMEMBER")) v.remember = std::atoi(e) != 0;
     if (const char *e = t.get("D2G_SP_RIDE")) v.ride = std::atoi(e) & 127;

@@ -680,7 +680,8 @@ int  d2g_cmp_set_debug_pairs(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream,
  * matrix (sixteen sampled sketches against all), [1] 1 = the first look decided for the dense walk, [2..5] that look's raw sums (0 without one): register
  * counts below 4 (E), pairs at 4 or more (F), shared values over all columns, id planes over all columns; [6] 1 = the pair list went through
  * the binned + composed form, [7] the set's bin width (log2 of the columns of a chunk), [8] the schedule of the last prepare: 1 = merged (column plan and
- * planes inside launches of the ordering), 0 = classic (kernel by kernel: D2G_K2_MERGE=0, a first look, a remembered give-up, the table form of the link
+ * planes inside launches of the ordering: the planes beside flatten), 2 = merged with the planes behind the pair-list kernel's workgroups (the default,
+ * D2G_K2_MERGE=2), 0 = classic (kernel by kernel: D2G_K2_MERGE=0, a first look, a remembered give-up, the table form of the link
  * passes, split rank passes), [9] the kernels that prepare enqueued, the transpose included.  out10: TEN words.  Nothing in the product reads these back. */
 int  d2g_cmp_set_sparse_detail(d2g_ctx *ctx, const d2g_cmp_set *set, void *stream, uint64_t *out10);
 /* what became of the output announced to the set's last prepare (d2g_cmp_ut_announce_dev), in pieces of 32 KB: [0] the pieces announced (0: nothing was

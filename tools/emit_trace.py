@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-workgroup timeline of sp_emit_kernel's first step (variant build: tools/build_variant.sh trace -DD2G_SP_TRACE; D2G_LIB=dashing2_amd/libd2g_trace.so).
 MATRIX / C / N as tools/k2_time.py.  Stamps (s_memrealtime, 100 MHz): 0 start, 1 LDS cleared, 2 pass A done, 3 counts read + mixed vote, 4 scan + places,
-5 stream places reserved, 6 pass B done, 7 slots scanned + list places reserved, 8 records written."""
+5 stream places reserved, 6 pass B done, 7 slots scanned + list places reserved, 8 records written.
+Schedule 2 of the prepare (D2G_K2_MERGE=2): the planes blocks behind emit's stamp rows [S, ...) -- 0 / 1 the start of the block's two 256-thread items,
+2 / 3 their ends (thread 0 of each; stores still in flight) -- and are reported after emit's own: when the window opens and when it is used."""
 import ctypes as C
 import os
 import sys
@@ -40,3 +42,18 @@ last = 8 if full.any() else 3
 for k in range(1, last + 1):
     print(f"{names[k]:48s}", stats(w[:, k] - w[:, k - 1]))
 print(f"{'end of the first step':48s}", stats(w[:, last]))
+# the window behind the clean columns: when the workgroups without a mixed value are done, when the last one is, and (schedule 2) where the planes blocks ran
+if (~full).any():
+    print(f"{'clean workgroups: end (stamp 3)':48s}", stats(us[~full][:, 3]), f" ({int((~full).sum())} workgroups)")
+print(f"{'last stamp of any emit workgroup':48s} {us[np.arange(S), np.where(full, 8, 3)].max():7.2f}")
+print("schedule of the traced prepare:", cs.sparse_detail(st)["schedule"])
+rid = buf.reshape(-1, 16).astype(np.int64)[S:]
+rid = rid[rid[:, 0] >= t0]
+if len(rid):
+    ru = (rid[:, :4] - t0) / 100.0
+    print(f"planes blocks behind emit's: {len(rid)}")
+    print(f"{'planes block: start':48s}", stats(ru[:, 0]))
+    print(f"{'planes block: end of its first item':48s}", stats(ru[:, 2]))
+    print(f"{'planes block: first item (0->2)':48s}", stats(ru[:, 2] - ru[:, 0]))
+else:
+    print("no planes blocks behind emit's in this launch")

@@ -111,8 +111,8 @@ def main():
                         os.environ["D2G_SP_OLINK"] = "0"                                      # the link passes in their table form
                     if rng.random() < 0.3:
                         os.environ["D2G_SP_EMIT_BIG"] = "1"                                   # the pair-list kernel's form for N >= 65 536
-                    if rng.random() < 0.3:
-                        os.environ["D2G_K2_MERGE"] = "0"                                      # the prepare's classic schedule (merged: needs D2G_SP_PREDICT=0 on a one-shot set)
+                    # the prepare's schedule: classic, merged, merged with the planes behind the pair-list kernel (merged: needs D2G_SP_PREDICT=0 on a one-shot set)
+                    os.environ["D2G_K2_MERGE"] = str(int(rng.integers(0, 3)))
                     os.environ["D2G_SP_REMEMBER"] = "0"                                       # one-shot sets: every prepare decides afresh
                 ctx.reload_tuning()
                 r = rng.random()

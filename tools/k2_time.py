@@ -54,5 +54,5 @@ for _ in range(STEPS):
 torch.cuda.synchronize()
 step_ms = (time.perf_counter() - t0) / STEPS * 1e3
 n, ms, _ = ctx.kernel_ms("k2")
-print(f"step (prepare + compare) {step_ms:.4f} ms announce={int(ANNOUNCE)} ride={os.environ.get('D2G_SP_RIDE','127')} fill={cs.fill_detail() if hasattr(cs, 'fill_detail') and not os.environ.get('D2G_LIB') else '-'}; sparse: {cs.sparse_info(st)}")
+print(f"step (prepare + compare) {step_ms:.4f} ms announce={int(ANNOUNCE)} ride={os.environ.get('D2G_SP_RIDE','127')} fill={cs.fill_detail() if hasattr(cs, 'fill_detail') and not os.environ.get('D2G_LIB') else '-'} schedule={cs.sparse_detail(st)['schedule']} (D2G_K2_MERGE={os.environ.get('D2G_K2_MERGE', '-')}); sparse: {cs.sparse_info(st)}")
 print(f"{which} C={os.environ.get('C','-')} N={N} D2G_BS_EXP={os.environ.get('D2G_BS_EXP','0')} planes={cs.planes(st)} pair kernel {ms:.4f} ms over {n} launches")
