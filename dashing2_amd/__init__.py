@@ -21,6 +21,7 @@ from .capi import (  # noqa: F401
     ALPHABET_DNA, ALPHABET_PROTEIN20, ALPHABET_PROTEIN_3BIT, ALPHABET_PROTEIN_14, ALPHABET_PROTEIN_6,
     alphabet_size, alphabet_max_k, alphabet_code, alphabet_name, key_bits,
     countsketch_lds_cells,
+    IntervalPlan, xxh3_64, bed_parse, XXH3_MAX_LEN,
 )
 
 __all__ = [
@@ -38,4 +39,5 @@ __all__ = [
     "ALPHABET_DNA", "ALPHABET_PROTEIN20", "ALPHABET_PROTEIN_3BIT", "ALPHABET_PROTEIN_14", "ALPHABET_PROTEIN_6",
     "alphabet_size", "alphabet_max_k", "alphabet_code", "alphabet_name", "key_bits",
     "countsketch_lds_cells",
+    "IntervalPlan", "xxh3_64", "bed_parse", "XXH3_MAX_LEN",
 ]

@@ -184,6 +184,15 @@ SIGNATURES = {
     "d2g_countsketch_lds_cells": (_int, []),
     "d2g_countsketch_stats": (_int, [_vp, _vp, _vp, _vp]),
     "d2g_bmh_check_weights": (_int, [_vp, _vp, _sz, _sz, _dbl, C.c_char_p, _sz]),
+    "d2g_xxh3_64": (_u64, [_vp, _sz]),
+    "d2g_bed_parse": (_int, [C.c_char_p, _sz, _int, _vp, _vp, _vp, _sz, _vp, C.c_char_p, _sz]),
+    "d2g_interval_plan_create": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "d2g_interval_plan_destroy": (None, [_vp]),
+    "d2g_interval_plan_npositions": (_u64, [_vp]),
+    "d2g_interval_oph_sketch": (_int, [_vp, _vp, _sz, _vp]),
+    "d2g_interval_oph_sketch_dev": (_int, [_vp, _vp, _sz, _vp, _vp]),
+    "d2g_interval_bmh_sketch": (_int, [_vp, _vp, _int, _sz, _vp, _vp]),
+    "d2g_interval_runs": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
     "d2g_bmh_from_weighted": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]),
     "d2g_bmh_from_weighted_ids": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
     "d2g_ut_count": (_sz, [_sz, _sz, _sz]),
@@ -526,6 +535,31 @@ def host_epilogue_exact_rect(isz, cards, N, a0, a1, b0, b1, measure=SIMILARITY, 
     if rc:
         raise D2GError(rc)
     return out
+
+
+XXH3_MAX_LEN = 240
+
+
+def xxh3_64(data):
+    """XXH3_64bits (seed 0) of at most XXH3_MAX_LEN bytes; host only"""
+    data = bytes(data)
+    if len(data) > XXH3_MAX_LEN:
+        raise ValueError("d2g_xxh3_64 covers inputs of at most 240 bytes")
+    return int(lib().d2g_xxh3_64(data, len(data)))
+
+
+def bed_parse(buf, trim_chr=True):
+    """the data lines of a BED buffer -> (chrhash, start, stop) uint64 arrays; host only.  Raises ValueError with the library's words
+    for a line without a tab, a gzip magic, a chromosome name of more than 240 bytes"""
+    buf = bytes(buf)
+    cap = buf.count(b"\n") + 1
+    h, a, b = (np.zeros(cap, np.uint64) for _ in range(3))
+    n = _sz()
+    err = C.create_string_buffer(512)
+    rc = lib().d2g_bed_parse(buf, len(buf), int(bool(trim_chr)), _np_ptr(h), _np_ptr(a), _np_ptr(b), cap, C.addressof(n), err, 512)
+    if rc != 0:
+        raise ValueError(err.value.decode(errors="replace"))
+    return h[:n.value].copy(), a[:n.value].copy(), b[:n.value].copy()
 
 
 def kset_check(keys, counts, set_off):
@@ -989,6 +1023,33 @@ class Context:
         self._check(lib().d2g_oph_plan_create_windowed(self._h, _np_ptr(run_start), _np_ptr(run_len), run_start.size,
                                                        _np_ptr(genome_run_off), genome_run_off.size - 1, k, w, C.byref(h)))
         return OphPlan(self, h, genome_run_off.size - 1)
+
+    # -- K1i (interval sets: sketch / cmp --bed) --------------------------------
+    def interval_plan(self, chrhash, start, stop, file_off):
+        """launch plan over the lines of n BED files: file f owns lines [file_off[f], file_off[f + 1])"""
+        chrhash, start, stop, file_off = (np.ascontiguousarray(x, np.uint64) for x in (chrhash, start, stop, file_off))
+        assert chrhash.size == start.size == stop.size
+        h = _vp()
+        self._check(lib().d2g_interval_plan_create(self._h, _np_ptr(chrhash), _np_ptr(start), _np_ptr(stop), chrhash.size, _np_ptr(file_off),
+                                                   file_off.size - 1, C.byref(h)))
+        return IntervalPlan(self, h, file_off.size - 1)
+
+    def interval_oph_sketch(self, plan, S):
+        """-> regs uint64[n][m]"""
+        regs = np.empty((plan.n, oph_m(S)), np.uint64)
+        self._check(lib().d2g_interval_oph_sketch(self._h, plan._h, S, _np_ptr(regs)))
+        return regs
+
+    def interval_oph_sketch_dev(self, plan, S, regs_dev_ptr, stream=None):
+        """the same into device memory [n][m] on `stream`; does not synchronise"""
+        self._check(lib().d2g_interval_oph_sketch_dev(self._h, plan._h, S, regs_dev_ptr, stream))
+
+    def interval_bmh_sketch(self, plan, S, normalize=False):
+        """--multiset -> (sig float64[n][S], total_weight float64[n])"""
+        sig = np.empty((plan.n, S), np.float64)
+        tw = np.empty(plan.n, np.float64)
+        self._check(lib().d2g_interval_bmh_sketch(self._h, plan._h, int(bool(normalize)), S, _np_ptr(sig), _np_ptr(tw)))
+        return sig, tw
 
     # -- K1s (contain: reads screened against a k-mer database) ----------------
     def screen(self, keys, k, canon=True, xormask=0, nrows=1):
@@ -1465,6 +1526,34 @@ class OphPlan:
     def close(self):
         if self._h:
             lib().d2g_oph_plan_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class IntervalPlan:
+    def __init__(self, ctx, h, n):
+        self.ctx, self._h, self.n = ctx, h, n
+
+    @property
+    def npositions(self):
+        return int(lib().d2g_interval_plan_npositions(self._h))
+
+    def runs(self, normalize=False):
+        """the sweep behind --multiset (host only) -> (hash, lo, hi uint64[nruns], weight float64[nruns], run_off uint64[n + 1])"""
+        off = np.zeros(self.n + 1, np.uint64)
+        nr = _sz()
+        self.ctx._check(lib().d2g_interval_runs(self._h, int(bool(normalize)), None, None, None, None, 0, _np_ptr(off), C.addressof(nr)))
+        n = max(int(nr.value), 1)
+        h, lo, hi, w = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.float64)
+        self.ctx._check(lib().d2g_interval_runs(self._h, int(bool(normalize)), _np_ptr(h), _np_ptr(lo), _np_ptr(hi), _np_ptr(w), n, _np_ptr(off),
+                                                C.addressof(nr)))
+        k = int(nr.value)
+        return h[:k], lo[:k], hi[:k], w[:k], off
+
+    def close(self):
+        if self._h:
+            lib().d2g_interval_plan_destroy(self._h)
             self._h = None
 
     __del__ = close

@@ -146,6 +146,7 @@ struct d2g_ctx {
     int timing = 0;                         // D2G_TIME_* mask (d2g_set_timing)
     d2g_evlog ev_k1, ev_k2, ev_k2prep, ev_k3, ev_k0, ev_knn;
     d2g_evlog ev_k1count;                   // "k1count": the count pass after K1 (d2g_oph_count_dev), timed under D2G_TIME_K1
+    d2g_evlog ev_k1i, ev_k1iexpand, ev_k1ibmh;   // interval inputs (d2g_k1i.hip): "k1i" = the OPH kernel, under D2G_TIME_K1; under D2G_TIME_K3 "k1iexpand" = runs -> (id, weight) lists, "k1ibmh" = BagMinHash over them
     d2g_evlog ev_filter;                    // "filter": the build of a k-mer filter's table (d2g_kmer_filter_create_dev), under D2G_TIME_FILTER
     d2g_evlog ev_k3k, ev_k3kcompact, ev_k3kbmh;   // under D2G_TIME_K3, the count-sketch chain (K3k): "k3k" = zeroing and k3k_add_kernel, "k3kcompact" = table -> (cell, |count|) lists, "k3kbmh" = BagMinHash over them
     d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
@@ -160,6 +161,11 @@ void d2g_k3_state_destroy(struct d2g_k3_state *st);
 // (d2g_host.cpp) the host ranking behind d2g_screen_create: distinct keys ascending, their raw k-mers, the rank of every position's key
 void d2g_screen_rank_keys(const uint64_t *keys, size_t n, uint64_t xormask, std::vector<uint64_t> &distinct, std::vector<uint64_t> &raw,
                           std::vector<uint32_t> &rank);
+// (d2g_k3_bmh.hip) BagMinHash (BMH-D2G) over (id, weight) lists that lie in device memory: set i = elements [set_off[i], set_off[i + 1])
+// of ids_dev / w_dev, set_off and the total weights tw host arrays [ng + 1] / [ng]; registers to the host array sig_out [ng][m].  Every
+// weight must be > 0 and <= 2^53.  Enqueues on `s` and waits for it; `ev` times the walk (under D2G_TIME_K3).
+int d2g_bmh_device_lists(d2g_ctx *ctx, hipStream_t s, const uint64_t *ids_dev, const double *w_dev, const uint64_t *set_off, const double *tw,
+                         size_t ng, size_t m, double *sig_out, d2g_evlog *ev);
 inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
     if (e == hipSuccess) return D2G_OK;
     ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
@@ -188,7 +194,7 @@ inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
 struct d2g_timer {
     d2g_evlog *ev; hipStream_t s; bool on;
     d2g_timer(d2g_ctx *c, d2g_evlog *e, hipStream_t st) : ev(e), s(st), on(false) {
-        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
+        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count || e == &c->ev_k1i) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
         on = (c->timing & bit) != 0;
         if (on) {
             d2g_event x, y;
@@ -202,7 +208,7 @@ struct d2g_timer {
 
 // one per translation unit with kernels: makes the runtime load that unit's code object now (hipFuncGetAttributes on one of
 // its kernels) instead of at its first launch
-void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup();
+void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k1i(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

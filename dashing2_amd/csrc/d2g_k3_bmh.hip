@@ -2367,6 +2367,61 @@ int d2g_bmh_from_weighted_ids(d2g_ctx *ctx, const uint64_t *ids, const double *w
 
 }  // extern "C"
 
+// BagMinHash over lists another unit left on the device (K1i's expanded interval runs, d2g_k1i.hip): d2g_bmh_from_weighted_ids without
+// the upload of the lists and without the owner pass; the totals and the checks that need them come from the caller's host arrays.
+int d2g_bmh_device_lists(d2g_ctx *ctx, hipStream_t s, const uint64_t *ids_dev, const double *w_dev, const uint64_t *set_off, const double *tw,
+                         size_t ng, size_t m, double *sig_out, d2g_evlog *ev) {
+    D2G_CHECK(ctx, m >= 1 && m < (1ull << 24), "sketchsize out of range");
+    D2G_CHECK(ctx, ng < (1ull << 31), "too many sets");
+    if (ng == 0) return D2G_OK;
+    {   // d2g_bmh_check_weights' last check, on the totals
+        const double lnm = std::log((double)m);
+        for (size_t i = 0; i < ng; ++i)
+            D2G_CHECK(ctx, !(tw[i] > 0.) || ctx->k3_tune.guess_scale * bmh_guess(tw[i], (double)m, lnm) < BMH_GUESS_LIMIT,
+                      "BagMinHash: total weight too small for the sketch size (the pruning bound would not stay finite)");
+    }
+    const std::vector<uint64_t> guess = ws_guesses(tw, ng, m, ctx->k3_tune.guess_scale);
+    d2g_ws_blocks wb;
+    d2g_ws_plan_blocks(set_off, ng, wb);
+    const size_t nb = wb.set.size();
+    D2G_CHECK(ctx, nb < (1ull << 31), "too many workgroups");
+    d2g_dev<uint64_t> d_blo, d_h, d_guess;
+    d2g_dev<double> d_tw;
+    d2g_dev<uint32_t> d_bset, d_redo;
+    d2g_dev<int> d_status;
+    int rc = D2G_OK;
+    const char *what = "weighted lists alloc";
+    if ((rc = d_blo.alloc(ctx, std::max<size_t>(nb, 1), what)) || (rc = d_bset.alloc(ctx, std::max<size_t>(2 * nb, 1), what)) ||
+        (rc = d_h.alloc(ctx, ng * m, what)) || (rc = d_guess.alloc(ctx, ng, what)) || (rc = d_redo.alloc(ctx, ng, what)) ||
+        (rc = d_tw.alloc(ctx, ng, what)) || (rc = d_status.alloc(ctx, 2, what))) return rc;
+    D2G_HIP(ctx, hipMemcpyAsync(d_guess, guess.data(), ng * 8, hipMemcpyHostToDevice, s));
+    if (nb) {
+        D2G_HIP(ctx, hipMemcpyAsync(d_blo, wb.lo.data(), nb * 8, hipMemcpyHostToDevice, s));
+        D2G_HIP(ctx, hipMemcpyAsync(d_bset, wb.set.data(), nb * 4, hipMemcpyHostToDevice, s));
+        D2G_HIP(ctx, hipMemcpyAsync(d_bset + nb, wb.cnt.data(), nb * 4, hipMemcpyHostToDevice, s));
+    }
+    D2G_HIP(ctx, hipMemsetAsync(d_status, 0, 2 * sizeof(int), s));
+    WsArgs a;
+    a.ids = ids_dev; a.w = w_dev; a.blk_set = d_bset; a.blk_lo = d_blo; a.blk_cnt = d_bset + nb;
+    a.m = (uint32_t)m; a.h = d_h; a.guess = d_guess; a.redo = d_redo; a.redo_mode = 0; a.status = d_status;
+    a.arg = nullptr; a.set_lo = nullptr;
+    {
+        d2g_timer tm(ctx, ev, s);
+        const size_t ninit = std::max<size_t>(ng * m, ng);
+        hipLaunchKernelGGL(k3_bmh_init_kernel, dim3((unsigned)div_up<size_t>(ninit, K3_THREADS)), dim3(K3_THREADS), 0, s, d_h, ng * m, d_tw, d_redo, ng);
+        D2G_HIP(ctx, hipMemcpyAsync(d_tw, tw, ng * 8, hipMemcpyHostToDevice, s));
+        rc = ws_walk(ctx, s, a, ng, nb, d_guess, d_redo, d_tw, d_status);
+        tm.stop();
+    }
+    if (rc) { (void)hipStreamSynchronize(s); return rc; }              // the host arrays above are read by copies that may still be in flight
+    D2G_HIP(ctx, hipGetLastError());
+    int status = 0;
+    D2G_HIP(ctx, hipMemcpyAsync(&status, d_status, sizeof(int), hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipMemcpyAsync(sig_out, d_h, ng * m * 8, hipMemcpyDeviceToHost, s));
+    D2G_HIP(ctx, hipStreamSynchronize(s));
+    return k3_status_error(ctx, status);
+}
+
 // =============================================================================================
 // K3k: --multiset -c/--countsketch-size/--countmin-size <cells> -- approximate counting in a single-row count-sketch
 //   reference src/counter.h:16-19 (the row of `cells` floats), 68-77 (Counter::add(uint64_t)), 131-137 (finalize into the sketch)

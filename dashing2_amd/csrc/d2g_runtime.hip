@@ -221,6 +221,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     }
     if (what & D2G_WARM_K0) d2g_warm_k0();
     if (what & D2G_WARM_K1) d2g_warm_k1();
+    if (what & D2G_WARM_K1I) d2g_warm_k1i();
     if (what & D2G_WARM_K2) { d2g_warm_k2(); d2g_warm_k2_bitslice(); d2g_warm_k2_planes(); d2g_warm_knn(); d2g_warm_dedup(); }
     if (what & D2G_WARM_K3) d2g_warm_k3();
     if (what & D2G_WARM_KSET) d2g_warm_kset();
@@ -246,6 +247,9 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     d2g_evlog *e = nullptr, *e2 = nullptr;                   // e2: a second log summed under the same name
     if (!std::strcmp(which, "k1")) e = &c->ev_k1;
     else if (!std::strcmp(which, "k1count")) e = &c->ev_k1count;
+    else if (!std::strcmp(which, "k1i")) e = &c->ev_k1i;
+    else if (!std::strcmp(which, "k1iexpand")) e = &c->ev_k1iexpand;
+    else if (!std::strcmp(which, "k1ibmh")) e = &c->ev_k1ibmh;
     else if (!std::strcmp(which, "filter")) e = &c->ev_filter;
     else if (!std::strcmp(which, "k2")) e = &c->ev_k2;
     else if (!std::strcmp(which, "k2prep")) e = &c->ev_k2prep;

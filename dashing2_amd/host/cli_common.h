@@ -199,6 +199,7 @@ struct HostBuf {
 // sketch_cmd.cpp
 void sketch_core(Result &res, const Options &o, LazyCtx &lctx);
 void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx);
+void sketch_core_bed(Result &res, const Options &o, LazyCtx &lctx);   // --bed: interval files (K1i)
 int sketch_main(int argc, char **argv);
 // --set / --countdict: per input, the key file (and count file) is loaded -- --presketched, or --cache and a complete file set -- or
 // the input's exact set is computed on the GPU and the files are written

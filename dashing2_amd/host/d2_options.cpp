@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_PROTEIN, OPT_PROTEIN6, OPT_PROTEIN8, OPT_PROTEIN14, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_PROTEIN, OPT_PROTEIN6, OPT_PROTEIN8, OPT_PROTEIN14, OPT_BED, OPT_NORMIV, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -48,6 +48,12 @@ void sketch_usage() {
                          "  --protein14 / --protein8 / --protein6    ... over the reduced alphabets SE-B(14) (k <= 16), SE-B(8) (k <= 21), SE-B(6) (k <= 24).\n"
                          "                         No canonical form (as -C); any other letter ends a run as N does; file names carry PROTEIN20 /\n"
                          "                         PROTEIN_14 / PROTEIN_3BIT / PROTEIN_6 where DNA stands.  Not with -w > k, k above the limit, several GPUs\n"
+                         "  --bed                  every input is an interval file (BED: chrom<TAB>start<TAB>stop...): the element of a sketch is a genomic\n"
+                         "                         position, XXH3_64bits(chrom, a leading chr/Chr dropped) ^ i for start <= i < stop, sketched on the GPU (K1i).\n"
+                         "                         With --multiset a position weighs the number of lines that cover it; --normalize-intervals: each line\n"
+                         "                         adds 1 / (stop - start) instead.  <input>.opss (.d2gbmh with --multiset) is always written, --cache loads it.\n"
+                         "                         -k, -w, -C and -m play no part.  Not with --parse-by-seq, -s/-N, --set/--countdict, --filterset, -c, the\n"
+                         "                         protein alphabets, several GPUs, gzip-compressed input; --bigwig, --leafcutter, --by-chrom: not built\n"
                          "  -F/--ffile paths.txt -Q/--qfile queries.txt  -o/--outfile stacked.bin\n"
                          "  --cmpout/--distout/--cmp-outfile out   --phylip   --binary-output   --asymmetric-all-pairs\n"
                          "  --no-canon/-C  --seed s  --cache/-W  --outprefix dir  --oph/-Z\n"
@@ -131,7 +137,7 @@ std::string Options::to_string() const {    // src/d2.cpp:10-43 (fields that exi
                          exact ? (exact == 2 ? "mmerset64,kmercountsf64" : "mmerset64")     // d2.cpp:24,26
                          : kmer_result == ONE_PERM ? "onepermsetsketch"
                          : (sspace == SPACE_SET ? "fullsetsketch" : sspace == SPACE_MULTISET ? "bagminhash" : "probminhash"));
-    pos += std::snprintf(buf + pos, sizeof buf - pos, ";%s", "Fastx");
+    pos += std::snprintf(buf + pos, sizeof buf - pos, ";%s", bed ? "BED" : "Fastx");                 // to_string(dtype_), d2.cpp:28
     if (!outprefix.empty()) pos += std::snprintf(buf + pos, sizeof buf - pos, ";outprefix:%s", outprefix.c_str());
     if (cssize) pos += std::snprintf(buf + pos, sizeof buf - pos, ";counting=countsketch%zu\n", size_t(cssize));   // d2.cpp:33, with its line feed
     if (canon) pos += std::snprintf(buf + pos, sizeof buf - pos, ";canon");
@@ -174,6 +180,7 @@ int parse_options(int argc, char **argv, Options &o) {
         {"filterset", required_argument, 0, OPT_FILTERSET},
         {"set", no_argument, 0, OPT_SET}, {"countdict", no_argument, 0, 'J'},
         {"protein", no_argument, 0, OPT_PROTEIN}, {"protein20", no_argument, 0, OPT_PROTEIN}, {"enable-protein", no_argument, 0, OPT_PROTEIN},
+        {"bed", no_argument, 0, OPT_BED}, {"normalize-intervals", no_argument, 0, OPT_NORMIV},
         {"protein6", no_argument, 0, OPT_PROTEIN6}, {"protein8", no_argument, 0, OPT_PROTEIN8}, {"protein14", no_argument, 0, OPT_PROTEIN14},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
@@ -265,6 +272,8 @@ int parse_options(int argc, char **argv, Options &o) {
             case OPT_PROTEIN6: o.alphabet = D2G_ALPHABET_PROTEIN_6; std::fprintf(stderr, "Parsing amino acid sequences with 6-letter compressed alphabet.\n"); break;
             case OPT_PROTEIN14: o.alphabet = D2G_ALPHABET_PROTEIN_14; std::fprintf(stderr, "Parsing amino acid sequences with 14-letter compressed alphabet.\n"); break;
             case OPT_PROTEIN8: o.alphabet = D2G_ALPHABET_PROTEIN_3BIT; std::fprintf(stderr, "Using 3-bit protein encoding\n"); break;
+            case OPT_BED: o.bed = true; break;                                      // options.h:149
+            case OPT_NORMIV: o.normalize_intervals = true; break;                   // options.h:150
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
             case OPT_HELP: case 'h': case '?': o.is_cmp ? cmp_usage() : sketch_usage(); return 1 + 1;
             case OPT_UNSUPPORTED:
@@ -295,6 +304,31 @@ int parse_options(int argc, char **argv, Options &o) {
         for (std::string l; std::getline(ifs, l);) o.paths.push_back(l);
     }
     o.nq = o.paths.size() - nref;
+    if (o.bed && !o.presketched) {
+        // K1i: what interval inputs do not combine with in this build, each named, before a GPU is asked for (with --presketched
+        // nothing is sketched: --bed only shows in the options line)
+        const char *why = nullptr;
+        const char *e = std::getenv("D2G_DEVICES");
+        if (o.parse_by_seq) why = "--parse-by-seq (an interval file has no records)";
+        else if (o.save_kmers) why = "-s/--save-kmers or -N/--save-kmercounts (the registers of an interval sketch hold positions, not k-mers)";
+        else if (gave_set || gave_countdict) why = "--set/-H or --countdict/-J (exact sets of positions)";
+        else if (!o.filterset_arg.empty()) why = "--filterset (a k-mer filter; an interval file has no k-mers)";
+        else if (o.cssize) why = "-c/--countsketch-size/--countmin-size (the reference's count-sketch arm for BED feeds signed cells to the sketch, bedsketch.cpp:77)";
+        else if (o.alphabet) why = "a protein alphabet (--protein, --protein14/8/6)";
+        else if (e && *e && (std::strcmp(e, "all") == 0 || std::strchr(e, ','))) why = "D2G_DEVICES naming several GPUs (interval files are sketched on one GPU)";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): --bed together with %s is outside the hot-path scope of this build.\n", why);
+            return 1 + 1;
+        }
+        if (o.normalize_intervals && o.sspace == SPACE_SET) {                       // bedsketch.cpp:7-8
+            std::fprintf(stderr, "Exception Can't normalize BED rows in set space. Use SPACE_MULTISET or SPACE_PSET\n");
+            return 1 + 1;
+        }
+        if (o.count_threshold > 0)
+            std::fprintf(stderr, "[d2g] -m/--count-threshold has no effect with --bed (bed2sketch never passes it to the sketch it fills)\n");
+        if (std::getenv("D2G_DEVICE_PARSE") && !std::getenv("D2G_HOST_PARSE"))
+            std::fprintf(stderr, "[d2g] D2G_DEVICE_PARSE ignored with --bed: the device parser reads FASTA, interval files are parsed on the host\n");
+    }
     if (gave_set || gave_countdict) {
         // exact k-mer sets / count dictionaries: what they do not combine with in this build, each named
         o.exact = gave_countdict ? 2 : 1;
@@ -332,7 +366,7 @@ int parse_options(int argc, char **argv, Options &o) {
         }
     }
     if (o.sspace != SPACE_SET && o.kmer_result == ONE_PERM) o.kmer_result = FULL_SETSKETCH;   // sketch_main.cpp:124-127
-    if (o.sspace == SPACE_SET && o.count_threshold > 0 && !o.exact) {
+    if (o.sspace == SPACE_SET && o.count_threshold > 0 && !o.exact && !o.bed) {
         // OPH min-count filtering (oph.h:186-205) is built for One-Permutation set sketches of whole inputs that are WRITTEN somewhere.
         // What the parent refused and this build still does not do stays refused as it was:
         const char *why = nullptr;

@@ -53,6 +53,8 @@ struct Options {
                                           // ids of python/parse.py:8-23 = D2G_ALPHABET_*): amino-acid k-mers (K1a), canon forced off, default k = the alphabet's largest
     uint64_t cssize = 0;                  // -c/--countsketch-size/--countmin-size cells (options.h:78-79,357; d2.h:107): with --multiset the k-mers are counted in a
                                           // single-row count-sketch of that many cells (K3k) instead of exactly; 0 = exact counting.  Elsewhere only to_string() shows it
+    bool bed = false;                     // --bed (options.h:149; DataType BED, sketch_core.cpp:48-62): every input is an interval file, a position of a line is an element (K1i)
+    bool normalize_intervals = false;     // --normalize-intervals (options.h:150): with --bed --multiset a line adds 1 / (stop - start) to each of its positions
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

@@ -133,7 +133,7 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
         }
     if (const char *sparse = sparse_job_name(o))                    // refused before a context exists
         if (const size_t S = o.presketched ? presketched_sketchsize(o) : o.sketchsize) refuse_sparse_job_out_of_scope(sparse, o, S);
-    LazyCtx lctx(o, D2G_WARM_COPY | (o.exact ? D2G_WARM_KSET : D2G_WARM_K2) | (o.presketched ? 0 : (o.sspace == SPACE_MULTISET || o.exact ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
+    LazyCtx lctx(o, D2G_WARM_COPY | (o.exact ? D2G_WARM_KSET : D2G_WARM_K2) | (o.presketched ? 0 : o.bed ? D2G_WARM_K1I | (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : 0) : (o.sspace == SPACE_MULTISET || o.exact ? D2G_WARM_K3 : D2G_WARM_K1)));   // under the reading of the sketch file(s)
     Result res;
     ExactSets es;
     if (o.exact) {
@@ -144,7 +144,8 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
         load_results(o, res);
     } else {
         if (o.paths.empty()) { std::fprintf(stderr, "No paths provided. See usage.\n"); cmp_usage(); return 1; }
-        if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
+        if (o.bed) sketch_core_bed(res, o, lctx);
+        else if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
         res.nq = o.nq;
     }
     const double t_wait = now();

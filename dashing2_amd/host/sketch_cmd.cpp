@@ -595,6 +595,105 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
                      .nest("k3s", Json::object().integer("launches", k3s.launches).num("total_ms", k3s.total_ms)).num("wall_s", now() - t0));
 }
 
+// --bed (sketch_core.cpp:48-62 -> bed2sketch, src/bedsketch.cpp:5-103): one sketch per interval file.  The files are a few MB of text
+// that stand for 10^7 - 10^9 positions each: they are read and parsed here, on this thread (d2g_bed_parse: the reference's line rules),
+// and every position is sketched on the GPU -- K1i registers finalised like K1's, or with --multiset the sweep's runs expanded and fed to
+// BagMinHash (d2g_interval_bmh_sketch).  Names and signatures are both in input order (the reference fills names_ in size-sorted order,
+// sketch_core.cpp:58-61: SURVEY F32).
+// Cache files: <input>.opss ([f64 card][f64 x S]; .d2gbmh in multiset space, as elsewhere in this build) next to the input or under
+// --outprefix, written ALWAYS (bedsketch.cpp:57 writes without --cache too) -- the name carries neither S nor the space's options.
+// --cache loads a file of exactly 8 (S + 1) bytes; any other size is sketched again and rewritten (the reference's loader appends to
+// an already sized vector and recomputes the cardinality, bedsketch.cpp:26-32: SURVEY F31).
+void sketch_core_bed(Result &res, const Options &o, LazyCtx &lctx) {
+    const double t_enter = now();
+    const size_t N = o.paths.size(), S = o.sketchsize, m = d2g_oph_m(S);
+    const bool multiset = o.sspace == SPACE_MULTISET;
+    if (!N) die("Can't sketch empty path set");
+    res.names = o.paths;
+    res.destination_files.resize(N);
+    res.cardinalities.assign(N, -1.);
+    res.signatures.assign(N * S, 0.);
+    std::vector<size_t> todo;
+    std::vector<uint64_t> chrhash, start, stop, file_off(1, 0);
+    uint64_t nlines = 0;
+    std::string buf;
+    for (size_t i = 0; i < N; ++i) {
+        const std::string &path = o.paths[i];
+        res.destination_files[i] = (o.outprefix.empty() ? path : o.outprefix + '/' + trim_folder(path)) + (multiset ? ".d2gbmh" : ".opss");
+        if (o.cache && isfile(res.destination_files[i])) {
+            if (filesize(res.destination_files[i]) == 8 + 8 * S && load_cached(res.destination_files[i], &res.signatures[i * S], &res.cardinalities[i], S)) continue;
+            std::fprintf(stderr, "[d2g] %s does not hold a sketch of size %zu: sketching %s again\n", res.destination_files[i].c_str(), S, path.c_str());
+        }
+        std::FILE *fp = std::fopen(path.c_str(), "rb");
+        if (!fp) die("Failed to open file " + path + " for reading");
+        buf.resize(filesize(path));
+        const size_t got = buf.empty() ? 0 : std::fread(&buf[0], 1, buf.size(), fp);
+        std::fclose(fp);
+        buf.resize(got);
+        size_t nl = 0;
+        char err[600] = "";
+        const size_t cap = size_t(std::count(buf.begin(), buf.end(), '\n')) + 1, at = chrhash.size();
+        chrhash.resize(at + cap); start.resize(at + cap); stop.resize(at + cap);
+        if (d2g_bed_parse(buf.data(), buf.size(), 1, &chrhash[at], &start[at], &stop[at], cap, &nl, err, sizeof err) != D2G_OK)
+            die(std::string(err) + " (" + path + ")");                   // "Malformed line: ...", bedsketch.cpp:40
+        chrhash.resize(at + nl); start.resize(at + nl); stop.resize(at + nl);
+        file_off.push_back(at + nl);
+        nlines += nl;
+        todo.push_back(i);
+    }
+    const double t_parse = now();
+    uint64_t npositions = 0, nruns = 0;
+    KAcc k1i, k1iexpand, k1ibmh;
+    if (!todo.empty()) {
+        d2g_ctx *ctx = lctx.get();
+        const size_t n = todo.size();
+        d2g_interval_plan *plan = nullptr;
+        check(ctx, d2g_interval_plan_create(ctx, chrhash.data(), start.data(), stop.data(), chrhash.size(), file_off.data(), n, &plan), "d2g_interval_plan_create");
+        npositions = d2g_interval_plan_npositions(plan);
+        std::vector<double> sigs(n * S), cards(n);
+        if (multiset) {
+            check(ctx, d2g_interval_bmh_sketch(ctx, plan, o.normalize_intervals, S, sigs.data(), cards.data()), "d2g_interval_bmh_sketch");
+            if (g_stats.on) {
+                std::vector<uint64_t> roff(n + 1);
+                size_t nr = 0;
+                (void)d2g_interval_runs(plan, o.normalize_intervals, nullptr, nullptr, nullptr, nullptr, 0, roff.data(), &nr);
+                nruns = nr;
+            }
+        } else {
+            std::vector<uint64_t> regs(n * m);
+            check(ctx, d2g_interval_oph_sketch(ctx, plan, S, regs.data()), "d2g_interval_oph_sketch");
+            check(ctx, d2g_oph_finalize(regs.data(), n, m, S, sigs.data(), cards.data(), int(o.workers())), "d2g_oph_finalize");
+        }
+        for (size_t t = 0; t < n; ++t) {
+            const size_t i = todo[t];
+            std::memcpy(&res.signatures[i * S], &sigs[t * S], S * sizeof(double));
+            res.cardinalities[i] = cards[t];
+            write_cached(res.destination_files[i], &sigs[t * S], cards[t], S);
+        }
+        if (g_stats.on) {
+            int c = 0; float avg = 0, last = 0;
+            if (d2g_kernel_ms(ctx, "k1i", 1, &c, &avg, &last) == D2G_OK) { k1i.launches = c; k1i.total_ms = double(avg) * c; }
+            if (d2g_kernel_ms(ctx, "k1iexpand", 1, &c, &avg, &last) == D2G_OK) { k1iexpand.launches = c; k1iexpand.total_ms = double(avg) * c; }
+            if (d2g_kernel_ms(ctx, "k1ibmh", 1, &c, &avg, &last) == D2G_OK) { k1ibmh.launches = c; k1ibmh.total_ms = double(avg) * c; }
+        }
+        if (g_release_at_exit) d2g_interval_plan_destroy(plan);
+    }
+    if (o.verbosity) std::fprintf(stderr, "[d2g] sketched %zu interval files (%" PRIu64 " lines, %" PRIu64 " positions; %zu from cache): read + parse %.3fs, device %.3fs\n",
+                                  todo.size(), nlines, npositions, N - todo.size(), t_parse - t_enter, now() - t_parse);
+    if (g_stats.on) {
+        Json dev = device_json(o.device);
+        dev.nest("k1i", Json::object().integer("launches", k1i.launches).num("total_ms", k1i.total_ms));
+        dev.nest("k1iexpand", Json::object().integer("launches", k1iexpand.launches).num("total_ms", k1iexpand.total_ms));
+        dev.nest("k1ibmh", Json::object().integer("launches", k1ibmh.launches).num("total_ms", k1ibmh.total_ms));
+        g_stats.nest("sketch", Json::object().integer("inputs", N).integer("sketched", todo.size()).integer("from_cache", N - todo.size()).integer("sketchsize", S)
+                     .str("space", multiset ? "multiset (K1i: interval runs + BagMinHash)" : "set (K1i: OPH over positions)")
+                     .nest("intervals", Json::object().integer("lines", nlines).integer("positions", npositions).integer("runs", nruns))
+                     .nest("devices", Json::array().push(dev))
+                     .nest("wall_s", Json::object().num("read_and_parse", t_parse - t_enter).num("device", now() - t_parse)));
+    }
+    write_stacked(res, o);
+}
+
 int sketch_main(int argc, char **argv) {                          // src/sketch_main.cpp:23-152
     Options o;
     if (int rc = parse_options(argc, argv, o)) return rc - 1;
@@ -603,10 +702,11 @@ int sketch_main(int argc, char **argv) {                          // src/sketch_
     o.device = job_devices(o)[0];
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "sketch");
-    LazyCtx lctx(o, D2G_WARM_COPY | (o.sspace == SPACE_MULTISET || o.count_threshold >= 2 || o.exact ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : o.exact ? D2G_WARM_KSET : D2G_WARM_K2));
+    LazyCtx lctx(o, D2G_WARM_COPY | (o.bed ? D2G_WARM_K1I | (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : 0) : o.sspace == SPACE_MULTISET || o.count_threshold >= 2 || o.exact ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : o.exact ? D2G_WARM_KSET : D2G_WARM_K2));
     Result res;
     ExactSets es;
     if (o.exact) exact_sets_job(res, o, lctx, es);
+    else if (o.bed) sketch_core_bed(res, o, lctx);
     else if (o.parse_by_seq) sketch_core_byseq(res, o, lctx); else sketch_core(res, o, lctx);
     if (o.verbosity) std::fprintf(stderr, "[d2g] GPU context %.3fs + warm-up %.3fs on a helper thread, under the host ingest\n", lctx.t_create, lctx.t_warm);
     res.nq = o.nq;

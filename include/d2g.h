@@ -94,13 +94,14 @@ int         d2g_host_unregister(d2g_ctx *ctx, void *hptr);
 #define D2G_WARM_K3   16
 #define D2G_WARM_KSET 32
 #define D2G_WARM_SCREEN 64
+#define D2G_WARM_K1I  128     /* the interval kernels (K1i, below) */
 int         d2g_warmup(d2g_ctx *ctx, int what);
 /* "<marketing name> (<gcn arch>, <n> CUs)" of a device, for logs and --gpu-stats */
 int         d2g_device_name(int device, char *buf, size_t cap);
 int         d2g_memcpy_h2d(d2g_ctx *ctx, void *dst_dev, const void *src_host, size_t nbytes, void *stream);
 int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, size_t nbytes, void *stream);
 /* Per-launch HIP-event timing of the dominant kernels.  With timing enabled every launch of
- * the K1 kernel ("k1"), its count pass ("k1count", also under D2G_TIME_K1), the K0 ingest chain ("k0"), the build of a k-mer filter ("filter"), the K3 chain ("k3"), the K2 pair kernel ("k2") and the K2 prepare chain ("k2prep") is
+ * the K1 kernel ("k1"), its count pass ("k1count", also under D2G_TIME_K1), the interval kernel ("k1i", likewise; "k1iexpand" and "k1ibmh" under D2G_TIME_K3), the K0 ingest chain ("k0"), the build of a k-mer filter ("filter"), the K3 chain ("k3"), the K2 pair kernel ("k2") and the K2 prepare chain ("k2prep") is
  * bracketed by events recorded on the launch stream; nothing synchronises until d2g_kernel_ms,
  * which reports the number of logged launches, their average and the last duration (ms) and
  * optionally clears the log. */
@@ -616,6 +617,56 @@ int d2g_countsketch_cells(d2g_ctx *ctx, const uint8_t *packed, size_t packed_byt
 int d2g_countsketch_lds_cells(void);
 /* since the context was made: the largest table allocated (bytes), the groups and the batches of all count-sketch calls */
 int d2g_countsketch_stats(d2g_ctx *ctx, uint64_t *table_bytes, uint64_t *groups, uint64_t *batches);
+
+/* ---- K1i: interval sets (BED), sketch / cmp --bed (R21) -------------------------
+ * Replaces bed2sketch (reference src/bedsketch.cpp:36-56): every position i of every line `chrom <TAB> start <TAB> stop`, start <= i <
+ * stop, is the element chrhash ^ i, chrhash = XXH3_64bits(chrom without a leading [cC]hr).
+ *   set space       OPSetSketch::update(chrhash ^ i): id = Wang((chrhash ^ i) ^ d2g_oph_xor_const()) -- ONE Wang hash, no maskfn, no seed --
+ *                   reg[id mod m] = min(.., id) with K1's index rule; finalised by d2g_oph_finalize like any K1 registers
+ *   --multiset      Counter::add(chrhash ^ i, inc), inc = 1 or 1 / (stop - start) (--normalize-intervals); the weight of a position is
+ *                   the sum, in line order, of the inc of every line that covers it; every (id, weight) goes to BagMinHash (BMH-D2G over
+ *                   the unhashed ids, as d2g_bmh_from_weighted).  Weights are summed per (chrhash, position): two chromosomes whose
+ *                   hashes alias under ^ i stay two elements here (they merge in the reference's map).
+ * Host half (no context): */
+#define D2G_XXH3_MAX_LEN 240
+/* XXH3_64bits (seed 0, default secret) of len <= D2G_XXH3_MAX_LEN bytes, restated from the published specification; a longer input
+ * is not hashed: the result is 0 and callers check the length first (d2g_bed_parse refuses such a chromosome name) */
+uint64_t d2g_xxh3_64(const void *data, size_t len);
+/* The data lines of a BED buffer, in order: empty lines and lines that begin with '#' are skipped; the chromosome is what stands before
+ * the first tab, less a leading chr / Chr when trim_chr; start and stop are two strtoul(p, &p, 10) calls on the rest of the line (a
+ * missing field reads 0, "+5" is 5, a trailing CR is ignored).  At most `cap` lines are written to chrhash / start / stop (NULL with
+ * cap 0: count only); *nlines is the number found (never more than the buffer's line feeds + 1).  D2G_ERR_INVALID with the text in err
+ * (may be NULL): "Malformed line: <line>" for a line without a tab (the reference's words), a gzip magic at the buffer's start, a
+ * chromosome name longer than D2G_XXH3_MAX_LEN bytes. */
+int d2g_bed_parse(const char *buf, size_t len, int trim_chr, uint64_t *chrhash, uint64_t *start, uint64_t *stop, size_t cap,
+                  size_t *nlines, char *err, size_t errcap);
+/* Device half.  A plan over n files: file f owns lines [file_off[f], file_off[f+1]) of the three tables (host arrays, copied).  A lane
+ * owns a chunk of at most 64 consecutive positions of ONE line, a workgroup chunks of ONE file; lines with start >= stop own nothing.
+ * D2G_ERR_INVALID with nothing allocated: null tables, file_off not monotone or file_off[n] != nint;
+ * D2G_ERR_UNSUPPORTED: a file with more than D2G_INTERVAL_MAX_POSITIONS positions (the message has the figure), 2^31 workgroups. */
+#define D2G_INTERVAL_MAX_POSITIONS (1ull << 44)
+typedef struct d2g_interval_plan d2g_interval_plan;
+int  d2g_interval_plan_create(d2g_ctx *ctx, const uint64_t *chrhash, const uint64_t *start, const uint64_t *stop, size_t nint,
+                              const uint64_t *file_off /* [n+1] */, size_t n, d2g_interval_plan **out);
+void d2g_interval_plan_destroy(d2g_interval_plan *plan);
+uint64_t d2g_interval_plan_npositions(const d2g_interval_plan *plan);   /* positions of all lines, overlaps counted */
+/* K1i: registers [n][m], m = d2g_oph_m(sketchsize), pre-set to ~0 by the call; a file without positions keeps ~0.  The host form
+ * synchronises; the _dev form enqueues on `stream` and returns (like d2g_oph_sketch_dev).  A plan of another context, a null output
+ * (n > 0) or a sketchsize out of range: D2G_ERR_INVALID before anything is written. */
+int  d2g_interval_oph_sketch(d2g_ctx *ctx, const d2g_interval_plan *plan, size_t sketchsize, uint64_t *regs_out /* host [n][m] */);
+int  d2g_interval_oph_sketch_dev(d2g_ctx *ctx, const d2g_interval_plan *plan, size_t sketchsize, uint64_t *regs_out_dev /* [n][m] */,
+                                 void *stream);
+/* --multiset: a host sweep per file gives the maximal runs (chrhash, lo, hi, weight) -- chromosome hashes ascending, positions
+ * ascending, the weight summed over the covering lines in line order; k1i_expand_kernel writes them out as (id, weight) lists on the
+ * device (16 bytes per covered position), BagMinHash runs over the lists where they lie.  total_weight_out[f] = the sum, in run order,
+ * of weight * positions.  Files go to the device in groups that fit a third of the free memory; one file that does not fit is
+ * D2G_ERR_NOMEM with the bytes needed and the bytes free.  normalize != 0: inc = 1.0 / (double)(stop - start).  Synchronises. */
+int  d2g_interval_bmh_sketch(d2g_ctx *ctx, const d2g_interval_plan *plan, int normalize, size_t sketchsize,
+                             double *sig_out /* host [n][S] */, double *total_weight_out /* host [n] */);
+/* the runs of the sweep on their own (host, no device work; tests): runs of file f in [run_off_out[f], run_off_out[f+1]); cap = capacity
+ * of the four arrays; *nruns = the runs found (nothing beyond cap is written) */
+int  d2g_interval_runs(const d2g_interval_plan *plan, int normalize, uint64_t *hash_out, uint64_t *lo_out, uint64_t *hi_out,
+                       double *w_out, size_t cap, uint64_t *run_off_out /* [n+1] */, size_t *nruns);
 
 /* ---- K2: dense all-pairs comparison -------------------------------------------
  * Replaces HOT LOOP B: emit_rectangular's row loops calling compare()
