@@ -1,4 +1,4 @@
-// d2g_countsketch.h -- the host arithmetic of K3k (--multiset -c <cells>, d2g_k3_bmh.hip): the exact remainder by a run-time divisor,
+// d2g_countsketch.h -- the host arithmetic of K3k (--multiset -c <cells>, d2g_k3_countsketch.hip) and of the list stage (d2g_k3_lists.hip): the exact remainder by a run-time divisor,
 // the groups of genomes whose table rows fit a byte budget, and the workgroup tables of BagMinHash over (id, weight) lists.  No HIP header
 // and no d2g_ctx in here, so that what the kernels trust runs under the host sanitizers (selftest/countsketch_selftest.cpp) as it runs
 // in libd2g.

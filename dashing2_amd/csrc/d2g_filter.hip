@@ -94,7 +94,7 @@ int d2g_filter_survivors(d2g_ctx *ctx, const KmerArgs &km, size_t nblk, size_t n
     if (int rc = d_cnt.alloc(ctx, n, "k-mer filter survivor counts")) return rc;
     D2G_HIP(ctx, hipMemsetAsync(d_cnt, 0, n * sizeof(unsigned long long), s));
     KmerArgs a = km; a.blk0 = 0;
-    const auto kern = d2g_km_protein(km) ? filter_survivors_kernel<false, true> : km.q > 1 ? filter_survivors_kernel<true> : filter_survivors_kernel<false>;
+    const auto kern = d2g_walker_variant(km, [](auto, auto w, auto aa) { return filter_survivors_kernel<w(), aa()>; });
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(K1_THREADS), 0, s, a, d_cnt.get());
     D2G_HIP(ctx, hipGetLastError());
     D2G_HIP(ctx, hipMemcpyAsync(out, d_cnt, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -135,7 +135,7 @@ static int filter_build(const KmerBatch &b, uint64_t nkmers, d2g_kmer_filter **o
         a.km = b.km;
         a.km.ftab = nullptr;
         a.tab = f->d_tab; a.mask = self.fmask; a.shift = self.fshift;
-        const auto kern = d2g_km_protein(a.km) ? filter_build_kernel<false, true> : a.km.q > 1 ? filter_build_kernel<true> : filter_build_kernel<false>;
+        const auto kern = d2g_walker_variant(a.km, [](auto, auto w, auto aa) { return filter_build_kernel<w(), aa()>; });
         hipLaunchKernelGGL(kern, dim3((unsigned)b.nblk), dim3(K1_THREADS), 0, s, a);
     }
     tm.stop();

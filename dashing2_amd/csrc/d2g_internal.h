@@ -101,7 +101,7 @@ d2g_k2_tuning d2g_k2_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
 std::string d2g_k2_tuning_json(const d2g_ctx *ctx);   // (d2g_k2_bitslice.hip) {"D2G_BS_SPARSE_MIN_N": 8192, ...}: the resolved values of the same switches
 uint64_t d2g_k2_tuning_hash(const d2g_ctx *ctx);   // (d2g_k2_bitslice.hip) FNV-1a over the RESOLVED values of the switches that select K2 kernels and thresholds: what the ranks of one job must agree on
 
-// K3's bucket geometry (d2g_k3_bmh.hip), here because the defaults and limits of its switches are these constants
+// K3's bucket geometry (d2g_k3_bucket.hip, d2g_k3_bmh.hip), here because the defaults and limits of its switches are these constants
 constexpr int K3_MAXBBITS = 12;             // log2 of the most buckets per genome (LDS histogram)
 constexpr int K3_ROUND_KEYS = 1400;         // keys one table round is sized for (load <= 0.69 of the 2048-slot LDS count table)
 constexpr int K3_TARGET = 1024;             // mean keys per bucket aimed for
@@ -152,7 +152,7 @@ struct d2g_ctx {
     d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
     d2g_evlog ev_screen, ev_screenreduce, ev_screenbuild;   // under D2G_TIME_SCREEN (d2g_screen.hip): "screen" = the count walk, "screenreduce" = d2g_screen_result's kernel, "screenbuild" = a screen's table
     d2g_evlog ev_dedup, ev_dedup_resolve;   // "dedup" = both: the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the latter alone)
-    struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3_bmh.hip)
+    struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3.h)
     uint64_t cs_table_bytes = 0, cs_groups = 0, cs_batches = 0;   // K3k (d2g_countsketch_stats): the largest table so far, the groups and the batches of all count-sketch calls
     d2g_dev<uint32_t> knn_band;             // [band rows][N] equality counts the selection kernel reads (d2g_knn.hip); grow-only
     d2g_dev<unsigned long long> dedup_keys; // one key per row of a band: its best representative of earlier bands (d2g_dedup.hip)
@@ -161,7 +161,7 @@ void d2g_k3_state_destroy(struct d2g_k3_state *st);
 // (d2g_host.cpp) the host ranking behind d2g_screen_create: distinct keys ascending, their raw k-mers, the rank of every position's key
 void d2g_screen_rank_keys(const uint64_t *keys, size_t n, uint64_t xormask, std::vector<uint64_t> &distinct, std::vector<uint64_t> &raw,
                           std::vector<uint32_t> &rank);
-// (d2g_k3_bmh.hip) BagMinHash (BMH-D2G) over (id, weight) lists that lie in device memory: set i = elements [set_off[i], set_off[i + 1])
+// (d2g_k3_lists.hip) BagMinHash (BMH-D2G) over (id, weight) lists that lie in device memory: set i = elements [set_off[i], set_off[i + 1])
 // of ids_dev / w_dev, set_off and the total weights tw host arrays [ng + 1] / [ng]; registers to the host array sig_out [ng][m].  Every
 // weight must be > 0 and <= 2^53.  Enqueues on `s` and waits for it; `ev` times the walk (under D2G_TIME_K3).
 int d2g_bmh_device_lists(d2g_ctx *ctx, hipStream_t s, const uint64_t *ids_dev, const double *w_dev, const uint64_t *set_off, const double *tw,

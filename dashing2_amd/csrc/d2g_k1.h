@@ -78,7 +78,7 @@ struct d2g_sketcher {
     d2g_dev<uint32_t> d_counts;                            // d2g_sketcher_run_counts: one u32 per register
     d2g_dev<uint8_t> d_arena; d2g_pinned<uint8_t> h_arena; // the launch tables: device copy and its pinned source
     d2g_pinned<uint8_t> h_stage;                           // pinned staging of the packed stream
-    d2g_k3_state *k3 = nullptr;                            // --multiset work buffers (d2g_k3_bmh.hip)
+    d2g_k3_state *k3 = nullptr;                            // --multiset work buffers (d2g_k3.h)
     d2g_k0_state *k0 = nullptr;                            // device FASTA ingest (d2g_k0.hip): raw bytes, tile tables, the last run table
 };
 // an entry point's view of its arguments carries no window and no alphabet: the sketcher's, as the plan unit and the accounting in

@@ -4,6 +4,7 @@
 #include "d2g_internal.h"
 #include "d2g_plan.h"                 // K1_THREADS, K1_CHUNK, K1_CPT, K1_BLOCK_CHUNKS: the geometry the plan is built for
 #include "d2g_minq.h"                 // the windowed walker's sliding minimum
+#include <type_traits>
 
 // Thomas Wang's 64-bit mix (sketch::hash::WangHash::hash; call sites src/enums.h:138, src/oph.h:49)
 __device__ __forceinline__ uint64_t wang64(uint64_t k) {
@@ -48,6 +49,16 @@ struct KmerArgs {
 };
 
 inline bool d2g_km_protein(const KmerArgs &a) { return a.canon > 1; }
+// The walker instantiation a batch takes: f(FILT, WIN, AA) with three std::bool_constants -- a filter attached, minimizers of a
+// window, a protein alphabet -- over exactly the six combinations that exist (K1a: never a window with a protein alphabet).  Every
+// pass over one batch chooses through this, so all of them drop and walk the same k-mers.
+template <class F> auto d2g_walker_variant(const KmerArgs &a, F &&f) {
+    constexpr std::true_type Y{}; constexpr std::false_type N{};
+    const bool filt = a.ftab != nullptr;
+    if (d2g_km_protein(a)) return filt ? f(Y, N, Y) : f(N, N, Y);
+    if (a.q > 1) return filt ? f(Y, Y, N) : f(N, Y, N);
+    return filt ? f(Y, N, N) : f(N, N, N);
+}
 
 // the all-ones k-mer (T x 32, forward) is a legal key and the value of a free slot: its membership is a flag behind the table
 constexpr uint64_t D2G_FILTER_EMPTY = ~0ull;

@@ -168,6 +168,32 @@ def test_multiset_sketches_match_bagminhash_over_the_reference_lists(oracle, gpu
         assert set(lists["depths"][1].tolist()) == {1.0, 2.0, 3.0, 4.0, 5.0}
 
 
+def test_multiset_redo_passes_leave_the_registers_unchanged(gpu_ctx, monkeypatch):
+    """D2G_K3_GUESS_SCALE=0.001 makes the first guess of every file's bound a thousand times too small, so the walk over the expanded
+    interval lists has to repeat its files under raised guesses.  Two files of very different weight -- overlapping and single-position
+    lines on two chromosomes; one line of one position -- must give the registers of the default scale bit for bit, which are those
+    of BagMinHash over the sweep's runs as explicit weighted sets."""
+    S = 64
+    h1, h2 = b"chr1", b"chr2"
+    h, a, b, off = R.tables([_bed([(h1, 0, 1000), (h1, 500, 1500), (h2, 10, 11)]), _bed([(h1, 0, 1)])])
+    p = gpu_ctx.interval_plan(h, a, b, off)
+    try:
+        sig, tw = gpu_ctx.interval_bmh_sketch(p, S)
+        monkeypatch.setenv("D2G_K3_GUESS_SCALE", "0.001")
+        rsig, rtw = gpu_ctx.interval_bmh_sketch(p, S)
+        monkeypatch.delenv("D2G_K3_GUESS_SCALE")
+        rh, rlo, rhi, rw, roff = p.runs()
+    finally:
+        p.close()
+    assert np.array_equal(rsig.view(np.uint64), sig.view(np.uint64)) and np.array_equal(rtw.view(np.uint64), tw.view(np.uint64))
+    assert tw.tolist() == [2001.0, 1.0] and np.isfinite(sig).all()
+    ids = [np.uint64(rh[r]) ^ np.arange(int(rlo[r]), int(rhi[r]), dtype=np.uint64) for r in range(int(roff[2]))]
+    ws = [np.full(int(rhi[r] - rlo[r]), rw[r]) for r in range(int(roff[2]))]
+    eoff = np.cumsum([0] + [sum(x.size for x in ids[int(roff[f]):int(roff[f + 1])]) for f in range(2)]).astype(np.uint64)
+    esig, etw = gpu_ctx.bmh_from_weighted(np.concatenate(ids), np.concatenate(ws), eoff, S)
+    assert np.array_equal(sig.view(np.uint64), esig.view(np.uint64)) and np.array_equal(tw, etw)
+
+
 def test_interval_kernels_are_timed_under_their_names(gpu_ctx, plan):
     h = np.array([R.chrom_hash(b"1")], np.uint64)
     gpu_ctx.set_timing(True)

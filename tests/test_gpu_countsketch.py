@@ -126,6 +126,28 @@ def test_chain_equals_bagminhash_of_the_models_lists(d2g, gpu_ctx, S):
         assert CS.batch_lists(kms, cells, XORMASK, 1.0)[3][4] == 40
 
 
+def test_chain_redo_passes_in_groups_leave_the_registers_unchanged(d2g, gpu_ctx, monkeypatch):
+    """D2G_K3_GUESS_SCALE=0.001 makes the first guess of every list's bound a thousand times too small, so BagMinHash over the lists has
+    to walk them again under raised guesses; D2G_CS_TABLE_BYTES = two rows sends the three inputs with k-mers in two table groups (the
+    empty one, placed second, takes no row), each walked into its own slice of the registers.  Registers and total weights must be
+    those of the default scale bit for bit, which are those of BagMinHash over the lists the chain itself hands out."""
+    k, S, cells = 21, 64, 4096
+    fastas = [_fa(_seq(21, 20000), "a"), b">none\nNNNN\n", _fa(_seq(22, 20000), "b"), _fa(_seq(23, 20000), "c")]
+    sp = _pack(d2g, fastas, k)
+    monkeypatch.setenv("D2G_CS_TABLE_BYTES", str(2 * cells * 4))
+    groups0 = gpu_ctx.countsketch_stats()[1]
+    sig, tw = gpu_ctx.bmh_sketch_cs_seqpack(sp, S, cells, xormask=XORMASK)
+    assert gpu_ctx.countsketch_stats()[1] - groups0 >= 2
+    monkeypatch.setenv("D2G_K3_GUESS_SCALE", "0.001")
+    rsig, rtw = gpu_ctx.bmh_sketch_cs_seqpack(sp, S, cells, xormask=XORMASK)
+    monkeypatch.delenv("D2G_K3_GUESS_SCALE")
+    assert np.array_equal(rsig.view(np.uint64), sig.view(np.uint64)) and np.array_equal(rtw.view(np.uint64), tw.view(np.uint64))
+    ids, w, off, tot = gpu_ctx.countsketch_cells(sp, cells, xormask=XORMASK)
+    esig, etw = gpu_ctx.bmh_from_weighted(ids, w, off, S)
+    assert np.array_equal(sig.view(np.uint64), esig.view(np.uint64)) and np.array_equal(tw, etw) and np.array_equal(tw, tot.astype(np.float64))
+    assert tw[1] == 0 and np.isinf(sig[1]).all() and np.isfinite(sig[[0, 2, 3]]).all() and (tw[[0, 2, 3]] > 0).all()
+
+
 def test_walker_modes(d2g, gpu_ctx):
     """one case each with a filter attached, with w > k and with a protein alphabet: the lists of the model fed by the matching enumerator"""
     S, cells = 64, 5000

@@ -9,7 +9,7 @@ calls after warm-up calls (5 for tables of 2^24 cells and more: a call zeroes an
                     compact ("k3kcompact") and BagMinHash ("k3kbmh"); the groups of genomes of each, and "table_bytes": the largest table
                     the context has allocated SO FAR (d2g_countsketch_stats; the switch sweep before it reached 4 * 40960 * 1000)
   (b) the switch    the add alone in BOTH forms at every table size that fits LDS: D2G_CS_LDS_CELLS=40960 (LDS) and =0 (global).
-                    L (K3K_LDS_CELLS, d2g_k3_bmh.hip) is set where the LDS form stops winning here
+                    L (K3K_LDS_CELLS, d2g_k3_countsketch.hip) is set where the LDS form stops winning here
   (c) beside it     the exact --multiset chain ("k3") and plain K1 ("k1"), same run, with the bytes both chains keep on the device
   (d) the parent    "k3" and "k1" of this tree against the parent commit: DIR is a checkout of the parent commit with its library built.
                     One fresh process per measurement, the two taking turns"""
