@@ -24,6 +24,8 @@ TIME_DEDUP = 128
 TIME_FILTER = 256
 TIME_KSET = 512
 TIME_SCREEN = 1024
+TIME_EDIT = 2048
+EDIT_MAX_LEN = 65535                                                     # include/d2g.h D2G_EDIT_MAX_LEN
 
 
 class D2GError(RuntimeError):
@@ -167,6 +169,26 @@ SIGNATURES = {
     "d2g_kset_slice_bits": (_int, [_vp]),
     "d2g_kset_isz_ut_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
     "d2g_kset_isz_rect_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "d2g_seqrecs_create": (_int, [C.POINTER(_vp)]),
+    "d2g_seqrecs_destroy": (None, [_vp]),
+    "d2g_seqrecs_add_path": (_int, [_vp, _cp]),
+    "d2g_seqrecs_add_fastx": (_int, [_vp, _cp, _sz]),
+    "d2g_seqrecs_nrecords": (_sz, [_vp]),
+    "d2g_seqrecs_name": (C.c_char_p, [_vp, _sz]),
+    "d2g_seqrecs_bytes": (_pu8, [_vp]),
+    "d2g_seqrecs_off": (_pu64, [_vp]),
+    "d2g_seqset_check": (_int, [_vp, _vp, _sz, _u64, C.c_char_p, _sz]),
+    "d2g_seqset_recode_map": (_int, [_vp, _u64, _vp]),
+    "d2g_seqset_create": (_int, [_vp, _vp, _vp, _sz, _u64, C.POINTER(_vp)]),
+    "d2g_seqset_destroy": (None, [_vp]),
+    "d2g_seqset_nrecords": (_sz, [_vp]),
+    "d2g_seqset_device_bytes": (_sz, [_vp]),
+    "d2g_seqset_alphabet_size": (_int, [_vp]),
+    "d2g_seqset_strip_blocks": (_int, [_vp, _vp]),
+    "d2g_edit_ut_dev": (_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
+    "d2g_edit_rect_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
+    "d2g_edit_ut": (_int, [_vp, _vp, _sz, _sz, _vp]),
+    "d2g_edit_rect": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp]),
     "d2g_epilogue_exact": (_f32, [_u64, _dbl, _dbl, _int, _int]),
     "d2g_epilogue_exact_ut": (_int, [_vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp]),
     "d2g_epilogue_exact_rect": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _int, _int, _int, _vp]),
@@ -575,6 +597,31 @@ def kset_check(keys, counts, set_off):
         raise D2GError(rc, err.value.decode())
 
 
+def _seq_arrays(records):
+    """a list of byte strings -> (bytes u8, off u64[n + 1])"""
+    off = np.zeros(len(records) + 1, np.uint64)
+    off[1:] = np.cumsum([len(r) for r in records], dtype=np.uint64)
+    return np.frombuffer(b"".join(bytes(r) for r in records), np.uint8).copy(), off
+
+
+def seqset_check(data, off):
+    """the host-side check of Context.seqset without a device: raises D2GError (INVALID) for an off that does not begin at 0, decreases
+    or does not end at the byte count, and (UNSUPPORTED) for a record of more than EDIT_MAX_LEN symbols"""
+    data = np.ascontiguousarray(data, np.uint8)
+    off = np.ascontiguousarray(off, np.uint64)
+    err = C.create_string_buffer(256)
+    rc = lib().d2g_seqset_check(_np_ptr(data), _np_ptr(off), off.size - 1, data.size, err, 256)
+    if rc:
+        raise D2GError(rc, err.value.decode())
+
+
+def seqset_recode_map(data):
+    """-> (map u8[256], sigma): the dense code of every byte value that occurs in `data`, in order of byte value"""
+    data = np.ascontiguousarray(data, np.uint8)
+    m = np.zeros(256, np.uint8)
+    return m, int(lib().d2g_seqset_recode_map(_np_ptr(data), data.size, _np_ptr(m)))
+
+
 def bmh_check_weights(weights, set_off, S, scale=1.0):
     """the host-side checks of Context.bmh_from_weighted / _ids without a device: raises D2GError for a NaN weight, a weight above
     2^53, a set_off that is not monotone, and a non-empty set whose total weight is too small for S (its bound would not stay finite)"""
@@ -974,6 +1021,16 @@ class Context:
         h = _vp()
         self._check(lib().d2g_kset_create_dev(self._h, keys_dev_ptr, counts_dev_ptr, set_off_dev_ptr, nsets, stream, C.byref(h)))
         return KSet(self, h)
+
+    def seqset(self, records=None, data=None, off=None):
+        """a list of byte strings (or their concatenation and off[n + 1]) -> SeqSet, resident and recoded on the device"""
+        if records is not None:
+            data, off = _seq_arrays(records)
+        data = np.ascontiguousarray(data, np.uint8)
+        off = np.ascontiguousarray(off, np.uint64)
+        h = _vp()
+        self._check(lib().d2g_seqset_create(self._h, _np_ptr(data), _np_ptr(off), off.size - 1, data.size, C.byref(h)))
+        return SeqSet(self, h)
 
     def kmer_distinct_seqpack(self, sp: "SeqPack", canon=True, xormask=0):
         """-> uint64[n]: exact number of distinct masked k-mers per genome"""
@@ -1504,6 +1561,99 @@ class KSet:
             self._h = None
 
     __del__ = close
+
+
+class SeqSet:
+    """Device-resident records, recoded to dense symbol codes, for exact edit distances (d2g_seqset, K2h)."""
+
+    def __init__(self, ctx, h):
+        self.ctx, self._h = ctx, h
+        self.N = int(lib().d2g_seqset_nrecords(h))
+
+    @property
+    def device_bytes(self):
+        return int(lib().d2g_seqset_device_bytes(self._h))
+
+    @property
+    def alphabet_size(self):
+        return int(lib().d2g_seqset_alphabet_size(self._h))
+
+    @property
+    def strip_blocks(self):
+        return int(lib().d2g_seqset_strip_blocks(self.ctx._h, self._h))
+
+    def edit_ut_dev(self, r0, r1, out_dev_ptr, stream=None):
+        self.ctx._check(lib().d2g_edit_ut_dev(self.ctx._h, self._h, r0, r1, out_dev_ptr, stream))
+
+    def edit_rect_dev(self, a0, a1, b0, b1, out_dev_ptr, stream=None):
+        self.ctx._check(lib().d2g_edit_rect_dev(self.ctx._h, self._h, a0, a1, b0, b1, out_dev_ptr, stream))
+
+    def edit_ut(self, r0=0, r1=None):
+        """-> uint32[d2g_ut_count(N, r0, r1)] (host-pointer form; synchronises)"""
+        r1 = self.N if r1 is None else r1
+        out = np.zeros(ut_count(self.N, r0, r1), np.uint32)
+        self.ctx._check(lib().d2g_edit_ut(self.ctx._h, self._h, r0, r1, _np_ptr(out)))
+        return out
+
+    def edit_rect(self, a0, a1, b0, b1):
+        out = np.zeros((a1 - a0, b1 - b0), np.uint32)
+        self.ctx._check(lib().d2g_edit_rect(self.ctx._h, self._h, a0, a1, b0, b1, _np_ptr(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().d2g_seqset_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class SeqRecs:
+    """FASTA/FASTQ -> raw records (d2g_seqrecs_*): the record walk of SeqPack.add_*_by_record, the sequence bytes kept as they are."""
+
+    def __init__(self):
+        self._h = None
+        h = _vp()
+        rc = lib().d2g_seqrecs_create(C.byref(h))
+        if rc:
+            raise D2GError(rc)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().d2g_seqrecs_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def add_path(self, path):
+        rc = lib().d2g_seqrecs_add_path(self._h, os.fsencode(path))
+        if rc:
+            raise D2GError(rc, str(path))
+
+    def add_fastx(self, buf):
+        rc = lib().d2g_seqrecs_add_fastx(self._h, buf, len(buf))
+        if rc:
+            raise D2GError(rc, "add_fastx")
+
+    @property
+    def nrecords(self):
+        return int(lib().d2g_seqrecs_nrecords(self._h))
+
+    def name(self, g):
+        return lib().d2g_seqrecs_name(self._h, g).decode()
+
+    def arrays(self):
+        """-> (bytes u8, off u64[n + 1]) as numpy copies"""
+        n = self.nrecords
+        off = np.ctypeslib.as_array(lib().d2g_seqrecs_off(self._h), shape=(n + 1,)).copy()
+        nb = int(off[n])
+        data = np.ctypeslib.as_array(lib().d2g_seqrecs_bytes(self._h), shape=(nb,)).copy() if nb else np.empty(0, np.uint8)
+        return data, off
+
+    def records(self):
+        data, off = self.arrays()
+        return [data[int(off[i]):int(off[i + 1])].tobytes() for i in range(self.nrecords)]
 
 
 class OphPlan:

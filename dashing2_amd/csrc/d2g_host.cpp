@@ -712,6 +712,9 @@ struct d2g_seqpack {
     std::vector<uint64_t> genome_nkmers;
     bool by_record = false;            // --parse-by-seq: every FASTX record is its own genome ...
     std::vector<std::string> names;    // ... named by its header up to the first whitespace (kseq name)
+    bool raw_mode = false;             // d2g_seqrecs: the same record walk, but the sequence bytes are KEPT as they are, not packed ...
+    std::vector<uint8_t> raw;          // ... here, record g at [raw_off[g], raw_off[g + 1])
+    std::vector<uint64_t> raw_off{0};
     // open run state
     uint64_t cur_start = 0, cur_len = 0;
     uint64_t cur_kmers = 0;
@@ -763,6 +766,7 @@ struct d2g_seqpack {
         nbases = nb; cur_len = clen;
     }
     inline void feed(const char *s, size_t n) {
+        if (raw_mode) { raw.insert(raw.end(), s, s + n); return; }
         if (alphabet) { feed_aa(s, n); return; }
         static const int8_t *lut = code_lut();
         // worst case every byte is a base: make room once, then write through a raw pointer
@@ -898,6 +902,7 @@ struct d2g_seqpack {
             if (pos >= len) break;                         // a header character at the very end: kseq returns -1, no record
             // state to return to if this record turns out to be an error
             const uint64_t snap_bases = nbases, snap_kmers = cur_kmers;
+            const size_t snap_raw = raw.size();
             const size_t snap_runs = run_start.size();
             size_t name_end = pos;
             while (name_end < len && !std::isspace((unsigned char)buf[name_end])) ++name_end;
@@ -910,7 +915,7 @@ struct d2g_seqpack {
                 const int c = (unsigned char)buf[pos];
                 // a record boundary is only looked for at the start of a line (the block path may stop inside one)
                 if (at_line_start && (c == '>' || c == '+' || c == '@')) { term = c; ++pos; break; }
-                if (have_vbmi2 && !alphabet && len - pos >= 64) {
+                if (have_vbmi2 && !alphabet && !raw_mode && len - pos >= 64) {
                     const size_t took = feed_blocks(buf + pos, len - pos, &seqlen);
                     if (took) {
                         pos += took;
@@ -953,10 +958,12 @@ struct d2g_seqpack {
                 run_start.resize(snap_runs); run_len.resize(snap_runs);
                 cur_kmers = snap_kmers;
                 rewind_to(snap_bases);
+                raw.resize(snap_raw);
                 break;
             }
             if (by_record) {                               // fastxsketchbyseq.cpp:243-244: names_ = kseq name
                 names.emplace_back(buf + name_pos, name_end - name_pos);
+                if (raw_mode) raw_off.push_back(raw.size());
                 end_genome();
             } else end_record();
             if (term == -1) break;
@@ -971,6 +978,7 @@ struct d2g_seqpack {
     }
     void unpad() {}
     void reserve_bases(uint64_t more) {
+        if (raw_mode) { raw.reserve(raw.size() + more); return; }
         const size_t need = alphabet ? nbases + more + 65 : (nbases + more + 3) / 4 + 65;
         if (packed.size() < need) packed.resize(need);
     }
@@ -1125,6 +1133,54 @@ int d2g_seqpack_add_fastx_by_record(d2g_seqpack *sp, const char *buf, size_t len
     sp->by_record = false;
     return D2G_OK;
 }
+
+// ---- K2h: the raw record reader and the host half of d2g_seqset (see d2g.h) ----
+}  // extern "C"
+struct d2g_seqrecs { d2g_seqpack sp; };
+extern "C" {
+int d2g_seqrecs_create(d2g_seqrecs **out) {
+    if (!out) return D2G_ERR_INVALID;
+    auto *sr = new (std::nothrow) d2g_seqrecs();
+    if (!sr) return D2G_ERR_NOMEM;
+    sr->sp.k = 1;
+    sr->sp.raw_mode = true;
+    std::memset(sr->sp.aa_lut, -1, sizeof sr->sp.aa_lut);
+    *out = sr;
+    return D2G_OK;
+}
+void d2g_seqrecs_destroy(d2g_seqrecs *sr) { delete sr; }
+int d2g_seqrecs_add_path(d2g_seqrecs *sr, const char *line) { return sr ? d2g_seqpack_add_path_by_record(&sr->sp, line) : D2G_ERR_INVALID; }
+int d2g_seqrecs_add_fastx(d2g_seqrecs *sr, const char *buf, size_t len) { return sr ? d2g_seqpack_add_fastx_by_record(&sr->sp, buf, len) : D2G_ERR_INVALID; }
+size_t d2g_seqrecs_nrecords(const d2g_seqrecs *sr) { return sr ? sr->sp.names.size() : 0; }
+const char *d2g_seqrecs_name(const d2g_seqrecs *sr, size_t g) { return sr && g < sr->sp.names.size() ? sr->sp.names[g].c_str() : ""; }
+const uint8_t *d2g_seqrecs_bytes(const d2g_seqrecs *sr) { return sr ? sr->sp.raw.data() : nullptr; }
+const uint64_t *d2g_seqrecs_off(const d2g_seqrecs *sr) { return sr ? sr->sp.raw_off.data() : nullptr; }
+
+// what d2g_seqset_create asks of host arrays before anything reaches a device: the pair kernel indexes by these offsets without checks
+int d2g_seqset_check(const uint8_t *bytes, const uint64_t *off, size_t nrec, uint64_t nbytes, char *err, size_t errcap) {
+    auto fail = [&](int rc, const char *fmt, unsigned long long a, unsigned long long b) {
+        if (err && errcap) std::snprintf(err, errcap, fmt, a, b);
+        return rc;
+    };
+    if (!off) return fail(D2G_ERR_INVALID, "d2g_seqset: null off", 0, 0);
+    if (nbytes && !bytes) return fail(D2G_ERR_INVALID, "d2g_seqset: null bytes", 0, 0);
+    if (off[0] != 0) return fail(D2G_ERR_INVALID, "d2g_seqset: off must begin at 0 (it begins at %llu)", off[0], 0);
+    for (size_t i = 0; i < nrec; ++i)
+        if (off[i + 1] < off[i]) return fail(D2G_ERR_INVALID, "d2g_seqset: off decreases at record %llu (to %llu)", i, off[i + 1]);
+    if (off[nrec] != nbytes) return fail(D2G_ERR_INVALID, "d2g_seqset: off ends at %llu, the records have %llu bytes", off[nrec], nbytes);
+    for (size_t i = 0; i < nrec; ++i)
+        if (off[i + 1] - off[i] > D2G_EDIT_MAX_LEN)
+            return fail(D2G_ERR_UNSUPPORTED, "d2g_seqset: record %llu has %llu symbols, more than D2G_EDIT_MAX_LEN = 65535", i, off[i + 1] - off[i]);
+    return D2G_OK;
+}
+int d2g_seqset_recode_map(const uint8_t *bytes, uint64_t nbytes, uint8_t map[256]) {
+    bool seen[256] = {};
+    for (uint64_t e = 0; e < nbytes; ++e) seen[bytes[e]] = true;
+    int sigma = 0;
+    for (int b = 0; b < 256; ++b) map[b] = seen[b] ? uint8_t(sigma++) : uint8_t(0);
+    return std::max(sigma, 1);
+}
+
 const char *d2g_seqpack_name(const d2g_seqpack *sp, size_t g) { return sp && g < sp->names.size() ? sp->names[g].c_str() : ""; }
 int d2g_seqpack_add_fastx(d2g_seqpack *sp, const char *buf, size_t len) {
     if (!sp || (!buf && len)) return D2G_ERR_INVALID;

@@ -114,7 +114,7 @@ struct Stats {
     }
 };
 inline Stats g_stats;
-constexpr int TIME_ALL = D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN;
+constexpr int TIME_ALL = D2G_TIME_EDIT | D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN;
 
 // {"launches": n, "avg_ms": a, "total_ms": n a} of one timed kernel family on one context (synchronises on its events)
 inline std::string kernel_json(d2g_ctx *ctx, const char *which, bool reset = true) {
@@ -204,6 +204,10 @@ int sketch_main(int argc, char **argv);
 // --set / --countdict: per input, the key file (and count file) is loaded -- --presketched, or --cache and a complete file set -- or
 // the input's exact set is computed on the GPU and the files are written
 void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es);
+// --parse-by-seq --edit-distance --compute-edit-distance (K2h): the records of the one input file, read and checked on the host (no GPU
+// is asked for before every refusal has had its say), then the context, the resident set and the dense outputs of their edit distances
+int edit_distance_job(const Options &o);
+void cmp_core_edit(const Options &o, Result &res, d2g_ctx *ctx, const d2g_seqrecs *sr, double t_read);   // cmp_dense.cpp
 void apply_fmt_compat(Options &o);                                 // dashing2_main.cpp
 // cmp_dense.cpp: every cmp output of an Options / Result pair; hands nearest neighbours and clustering on to cmp_sparse.cpp
 void cmp_core(const Options &o, Result &res, d2g_ctx *ctx);

@@ -465,6 +465,58 @@ void cmp_core_exact(const Options &o, Result &res, d2g_ctx *ctx, const ExactSets
     if (g_release_at_exit) d2g_kset_destroy(ks);
 }
 
+// --edit-distance --compute-edit-distance: the same dense outputs from exact edit distances.  Replaces one edlibAlign per pair
+// (cmp_core.cpp:331-347,450-457): the records go to the device once (d2g_seqset), row batches of u32 distances come back
+// (d2g_edit_*_dev) and become the float32 the writers take -- exactly: a distance is at most 65 535 < 2^24.  --square takes the rect form,
+// as the reference's asymmetric route calls compare(i, j) for every cell: the diagonal comes out of the kernel as 0 and no batch has
+// to wait for rows of the triangle that lie in another one.
+void cmp_core_edit(const Options &o, Result &res, d2g_ctx *ctx, const d2g_seqrecs *sr, double t_read) {
+    const CmpShape sh(o, res);
+    const size_t ns = sh.ns;
+    const uint64_t *off = d2g_seqrecs_off(sr);
+    const double t0 = now();
+    d2g_seqset *ss = nullptr;
+    check(ctx, d2g_seqset_create(ctx, d2g_seqrecs_bytes(sr), off, ns, off[ns], &ss), "d2g_seqset_create");
+    const double t_set = now();
+    Emitter em(o, res);
+    em.header();
+    const size_t cap = std::max<size_t>(1, std::min(std::max(cmp_slot_values(sh.total_vals), sh.widest), std::max<size_t>(sh.total_vals, 1)));
+    DevBuf d(ctx, cap * 4);
+    std::vector<uint32_t> dist(cap);
+    std::vector<float> out(cap);
+    size_t nbatches = 0;
+    long double cells = 0;
+    std::vector<uint64_t> suffix(ns + 1, 0);                        // symbols of records [i, ns)
+    for (size_t i = ns; i-- > 0;) suffix[i] = suffix[i + 1] + (off[i + 1] - off[i]);
+    for (size_t r0 = 0; r0 < sh.nrows; ++nbatches) {
+        const auto b = sh.batch(r0, cap);
+        const size_t r1 = b.first, cnt = b.second;
+        if (cnt) {
+            if (sh.symmetric) check(ctx, d2g_edit_ut_dev(ctx, ss, r0, r1, (uint32_t *)d.p, nullptr), "d2g_edit_ut_dev");
+            else check(ctx, d2g_edit_rect_dev(ctx, ss, r0, r1, sh.c0, sh.c1, (uint32_t *)d.p, nullptr), "d2g_edit_rect_dev");
+            check(ctx, d2g_memcpy_d2h(ctx, dist.data(), d.p, cnt * 4, nullptr), "d2h");
+            for (size_t e = 0; e < cnt; ++e) out[e] = float(dist[e]);
+        }
+        for (size_t i = r0; i < r1; ++i) cells += (long double)(off[i + 1] - off[i]) * (long double)(sh.symmetric ? suffix[i + 1] : suffix[sh.c0] - suffix[sh.c1]);
+        if (sh.symmetric) em.rows(r0, r1, out.data(), [ns](size_t i) { return ns - 1 - i; });
+        else { const size_t ncol = sh.ncol; em.rows(r0, r1, out.data(), [ncol](size_t) { return ncol; }); }
+        r0 = r1;
+    }
+    if (o.verbosity) std::fprintf(stderr, "[d2g] edit distances: %zu records, %llu symbols over %d letters (%zu bytes resident): read %.3fs, upload + recoding %.3fs, %zu batches %.3fs\n",
+                                  ns, (unsigned long long)off[ns], d2g_seqset_alphabet_size(ss), d2g_seqset_device_bytes(ss), t_read, t_set - t0, nbatches, now() - t_set);
+    if (g_stats.on) {
+        Json dj = Json::array();
+        Json e = device_json(o.device);
+        e.raw("edit", kernel_json(ctx, "edit")).raw("editprep", kernel_json(ctx, "editprep"));
+        g_stats.nest("cmp", Json::object().integer("values", sh.total_vals).str("shape", sh.name(o)).str("algo", "exact edit distances (bit-parallel, K2h)")
+                     .nest("edit", Json::object().integer("records", ns).integer("symbols", off[ns]).integer("alphabet", d2g_seqset_alphabet_size(ss))
+                           .integer("cells", (unsigned long long)cells).integer("batches", nbatches).integer("resident_bytes", d2g_seqset_device_bytes(ss)))
+                     .integer("slot_values", cap).nest("devices", dj.push(e))
+                     .nest("wall_s", Json::object().num("read", t_read).num("upload_recode", t_set - t0).num("batches", now() - t_set)));
+    }
+    if (g_release_at_exit) d2g_seqset_destroy(ss);
+}
+
 void cmp_core(const Options &o, Result &res, d2g_ctx *ctx) {      // src/cmp_core.cpp:615-751
     const size_t ns = res.names.size(), S = o.sketchsize;
     if (res.nsigs() != ns * S) die("Empty signatures; trying to compare but don't have any");

@@ -33,7 +33,7 @@ static const char *const VALID_LONG[] = {
 
 enum {
     OPT_CMPOUT = 1000, OPT_OUTPREF, OPT_BINARY, OPT_PHYLIP, OPT_ASYM, OPT_ISZ, OPT_USZ, OPT_MASH, OPT_SYMCONTAIN,
-    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_PROTEIN, OPT_PROTEIN6, OPT_PROTEIN8, OPT_PROTEIN14, OPT_BED, OPT_NORMIV, OPT_UNSUPPORTED
+    OPT_CONTAIN, OPT_SEED, OPT_HELP, OPT_BATCH, OPT_PRESKETCHED, OPT_MULTISET, OPT_PARSEBYSEQ, OPT_FMTCOMPAT, OPT_GPUSTATS, OPT_FASTCMP, OPT_BBITSIGS, OPT_TOPK, OPT_SIMTHRESH, OPT_GREEDY, OPT_FILTERSET, OPT_SET, OPT_PROTEIN, OPT_PROTEIN6, OPT_PROTEIN8, OPT_PROTEIN14, OPT_BED, OPT_NORMIV, OPT_EDITDIST, OPT_COMPUTEEDIT, OPT_UNSUPPORTED
 };
 
 void sketch_usage() {
@@ -77,6 +77,13 @@ void sketch_usage() {
                          "  --countdict/-J         the same with every k-mer's count (<...>.kmercounts.f64): exact weighted Jaccard, sum of min counts.\n"
                          "                         -m c keeps the k-mers seen MORE than c times.  Not with -o, --multiset, --parse-by-seq, -s/-N, --fastcmp <8,\n"
                          "                         --topk, --similarity-threshold, --greedy, several GPUs; cmp --presketched *.kmerset64 is --set\n"
+                         "  --edit-distance --compute-edit-distance   with --parse-by-seq: the EXACT edit distance (unit-cost Levenshtein over the raw bytes:\n"
+                         "                         no case folding, N a symbol like any other, qualities ignored) between every two records of ONE\n"
+                         "                         FASTA/FASTQ(.gz) file, computed on the GPU (K2h); --cmpout / cmp give the triangle, --square, --phylip or\n"
+                         "                         --binary-output.  Both flags are needed: --edit-distance alone is the OrderMinHash LSH similarity, which is\n"
+                         "                         not built.  Records of at most 65535 symbols.  -k, -w, -S, -C and the protein flags play no part.  Not with\n"
+                         "                         -o, --cache, --presketched, -Q, --topk, --similarity-threshold, --greedy, --multiset, --set/--countdict,\n"
+                         "                         -s/-N, -m, -c, --filterset, --bed, --fastcmp <8, another measure, several GPUs\n"
                          "  --distance/--mash-distance --containment --symmetric-containment --intersection --union-size\n"
                          "  --fastcmp/--regsize/--regbytes <8|4|2|1>   compare registers truncated to that many bytes (8: as sketched); logarithmic\n"
                          "                         (setsketch) truncation unless --bbit-sigs selects b-bit signatures\n"
@@ -135,6 +142,7 @@ std::string Options::to_string() const {    // src/d2.cpp:10-43 (fields that exi
     if (count_threshold > 0) pos += std::snprintf(buf + pos, sizeof buf - pos, ";%u", count_threshold);
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";sketchtype:%s",
                          exact ? (exact == 2 ? "mmerset64,kmercountsf64" : "mmerset64")     // d2.cpp:24,26
+                         : edit ? "orderminhash"                                             // d2.cpp:22, SPACE_EDIT_DISTANCE
                          : kmer_result == ONE_PERM ? "onepermsetsketch"
                          : (sspace == SPACE_SET ? "fullsetsketch" : sspace == SPACE_MULTISET ? "bagminhash" : "probminhash"));
     pos += std::snprintf(buf + pos, sizeof buf - pos, ";%s", bed ? "BED" : "Fastx");                 // to_string(dtype_), d2.cpp:28
@@ -181,6 +189,7 @@ int parse_options(int argc, char **argv, Options &o) {
         {"set", no_argument, 0, OPT_SET}, {"countdict", no_argument, 0, 'J'},
         {"protein", no_argument, 0, OPT_PROTEIN}, {"protein20", no_argument, 0, OPT_PROTEIN}, {"enable-protein", no_argument, 0, OPT_PROTEIN},
         {"bed", no_argument, 0, OPT_BED}, {"normalize-intervals", no_argument, 0, OPT_NORMIV},
+        {"edit-distance", no_argument, 0, OPT_EDITDIST}, {"compute-edit-distance", no_argument, 0, OPT_COMPUTEEDIT},
         {"protein6", no_argument, 0, OPT_PROTEIN6}, {"protein8", no_argument, 0, OPT_PROTEIN8}, {"protein14", no_argument, 0, OPT_PROTEIN14},
         {0, 0, 0, 0}};
     // every other valid reference flag is recognised but outside the hot-path scope
@@ -191,6 +200,7 @@ int parse_options(int argc, char **argv, Options &o) {
         all.push_back({"similarity-threshold", required_argument, 0, OPT_SIMTHRESH});
         all.push_back({"greedy", required_argument, 0, OPT_GREEDY});
     }
+    int nmeasure = 0;                                         // measure flags other than --compute-edit-distance
     bool saw_square = false, saw_phylip = false, gave_topk = false, gave_thresh = false, greedy_fasta = false, gave_set = false, gave_countdict = false;
     std::set<std::string> have;
     for (auto &x : all) have.insert(x.name);
@@ -229,11 +239,11 @@ int parse_options(int argc, char **argv, Options &o) {
             case OPT_BINARY: o.of = MACHINE_READABLE; break;
             case OPT_PHYLIP: o.ok = PHYLIP; saw_phylip = true; break;
             case OPT_ASYM: o.ok = ASYMMETRIC_ALL_PAIRS; saw_square = true; break;
-            case OPT_ISZ: o.measure = D2G_INTERSECTION; break;
-            case OPT_USZ: o.measure = D2G_UNION_SIZE; break;
-            case OPT_MASH: o.measure = D2G_POISSON_LLR; break;
-            case OPT_SYMCONTAIN: o.measure = D2G_SYMMETRIC_CONTAINMENT; break;
-            case OPT_CONTAIN: o.measure = D2G_CONTAINMENT; break;
+            case OPT_ISZ: ++nmeasure; o.measure = D2G_INTERSECTION; break;
+            case OPT_USZ: ++nmeasure; o.measure = D2G_UNION_SIZE; break;
+            case OPT_MASH: ++nmeasure; o.measure = D2G_POISSON_LLR; break;
+            case OPT_SYMCONTAIN: ++nmeasure; o.measure = D2G_SYMMETRIC_CONTAINMENT; break;
+            case OPT_CONTAIN: ++nmeasure; o.measure = D2G_CONTAINMENT; break;
             case OPT_SEED: o.seedseed = std::strtoull(optarg, 0, 10); break;
             case OPT_BATCH: o.batch_size = std::strtoull(optarg, 0, 10); break;
             case OPT_PRESKETCHED: o.presketched = true; break;
@@ -272,6 +282,8 @@ int parse_options(int argc, char **argv, Options &o) {
             case OPT_PROTEIN6: o.alphabet = D2G_ALPHABET_PROTEIN_6; std::fprintf(stderr, "Parsing amino acid sequences with 6-letter compressed alphabet.\n"); break;
             case OPT_PROTEIN14: o.alphabet = D2G_ALPHABET_PROTEIN_14; std::fprintf(stderr, "Parsing amino acid sequences with 14-letter compressed alphabet.\n"); break;
             case OPT_PROTEIN8: o.alphabet = D2G_ALPHABET_PROTEIN_3BIT; std::fprintf(stderr, "Using 3-bit protein encoding\n"); break;
+            case OPT_EDITDIST: o.edit_space = true; break;                          // options.h:134,337: sketch space SPACE_EDIT_DISTANCE
+            case OPT_COMPUTEEDIT: o.compute_edit = true; break;                     // options.h:110: measure M_EDIT_DISTANCE
             case OPT_BED: o.bed = true; break;                                      // options.h:149
             case OPT_NORMIV: o.normalize_intervals = true; break;                   // options.h:150
             case OPT_BBITSIGS: o.bbit_sigs = true; break;                           // options.h:101
@@ -304,6 +316,40 @@ int parse_options(int argc, char **argv, Options &o) {
         for (std::string l; std::getline(ifs, l);) o.paths.push_back(l);
     }
     o.nq = o.paths.size() - nref;
+    if (o.edit_space || o.compute_edit) {
+        // K2h: the one edit-distance job this build runs is --parse-by-seq --edit-distance --compute-edit-distance with a matrix as its
+        // output; everything else that names these flags is refused here, each by name, before a GPU is asked for
+        const char *why = nullptr;
+        const char *e = std::getenv("D2G_DEVICES");
+        const char *const mode = o.edit_space ? "--edit-distance" : "--compute-edit-distance";
+        if (!o.edit_space) why = "no --edit-distance (the measure is defined in the edit-distance space only)";
+        else if (!o.parse_by_seq) why = "no --parse-by-seq (the reference throws there, fastxsketch.cpp:215-220,273: an edit distance is between records)";
+        else if (!o.compute_edit) why = "no --compute-edit-distance (that is the OrderMinHash LSH similarity; the OrderMinHash sketch is absent from the reference's tree)";
+        else if (!o.outfile.empty()) why = "-o/--outfile (the stacked file would hold OrderMinHash registers, which are not built)";
+        else if (o.cache) why = "--cache (there are no sketches to cache)";
+        else if (o.presketched) why = "--presketched (a sketch file holds no records)";
+        else if (!o.is_cmp && o.cmpout.empty()) why = "a sketch job without --cmpout (nothing would be written: there are no OrderMinHash sketches)";
+        else if (!o.qfile.empty()) why = "-Q/--qfile (a query panel)";
+        else if (gave_topk || gave_thresh) why = "--topk / --similarity-threshold (nearest neighbours by edit distance)";
+        else if (o.greedy) why = "--greedy (greedy clustering by edit distance)";
+        else if (o.sspace != SPACE_SET) why = "--multiset (another sketch space)";
+        else if (gave_set || gave_countdict) why = "--set/-H or --countdict/-J (exact k-mer sets; an edit distance has no k-mers)";
+        else if (o.save_kmers) why = "-s/--save-kmers or -N/--save-kmercounts (there are no k-mers behind an edit distance)";
+        else if (o.count_threshold > 0) why = "-m/--count-threshold (there are no k-mers to count)";
+        else if (o.cssize) why = "-c/--countsketch-size/--countmin-size (there are no k-mers to count)";
+        else if (!o.filterset_arg.empty()) why = "--filterset (a k-mer filter; an edit distance has no k-mers)";
+        else if (o.bed) why = "--bed (an interval file has no records)";
+        else if (o.regbytes < 8) why = "--fastcmp/--regsize/--regbytes below 8 (there are no registers to truncate)";
+        else if (nmeasure) why = "a second measure flag (--compute-edit-distance is the measure)";
+        else if (e && *e && (std::strcmp(e, "all") == 0 || std::strchr(e, ','))) why = "D2G_DEVICES naming several GPUs (edit distances are computed on one GPU)";
+        if (why) {
+            std::fprintf(stderr, "dashing2 (MI355X): %s together with %s is outside the hot-path scope of this build.\n", mode, why);
+            return 1 + 1;
+        }
+        o.edit = true;
+        o.kmer_result = FULL_SETSKETCH;                          // sketch_main.cpp:124-127
+        if (o.alphabet) std::fprintf(stderr, "[d2g] the protein alphabet plays no part in an edit distance (bytes are bytes); it only shows in the options line\n");
+    }
     if (o.bed && !o.presketched) {
         // K1i: what interval inputs do not combine with in this build, each named, before a GPU is asked for (with --presketched
         // nothing is sketched: --bed only shows in the options line)
@@ -402,7 +448,7 @@ int parse_options(int argc, char **argv, Options &o) {
         }
         o.filterset = o.filterset_arg.substr(0, i);
     }
-    if (o.alphabet && !o.presketched) {                        // K1a: said here, before a GPU is asked for; the library refuses the first two as well
+    if (o.alphabet && !o.presketched && !o.edit) {             // K1a: said here, before a GPU is asked for; the library refuses the first two as well
         const char *e = std::getenv("D2G_DEVICES");
         if (o.k > d2g_alphabet_max_k(o.alphabet)) {
             std::fprintf(stderr, "dashing2 (MI355X): k = %d > %d with %s uses the reference's rolling-hash encoder, as k > 32 does for DNA; "
@@ -422,12 +468,12 @@ int parse_options(int argc, char **argv, Options &o) {
         if (std::getenv("D2G_DEVICE_PARSE") && !std::getenv("D2G_HOST_PARSE"))
             std::fprintf(stderr, "[d2g] D2G_DEVICE_PARSE ignored with %s: the device parser reads DNA, the host parser runs\n", d2g_alphabet_name(o.alphabet));
     }
-    if (o.k > 32) {
+    if (o.k > 32 && !o.edit) {
         std::fprintf(stderr, "dashing2 (MI355X): k = %d > 32 uses the reference's rolling-hash encoder "
                              "(fastxsketch.cpp:420), which is outside this build's hot-path scope.\n", o.k);
         return 1 + 1;
     }
-    if (o.w > o.k && o.w - o.k + 1 > D2G_WINDOW_MAX_Q) {      // K1w: said here, before a GPU is asked for; the library refuses it too
+    if (!o.edit && o.w > o.k && o.w - o.k + 1 > D2G_WINDOW_MAX_Q) {      // K1w: said here, before a GPU is asked for; the library refuses it too
         std::fprintf(stderr, "dashing2 (MI355X): -w %d with -k %d: a window of more than %d k-mers (w - k > %d) is outside this build's "
                              "hot-path scope.\n", o.w, o.k, D2G_WINDOW_MAX_Q, D2G_WINDOW_MAX_Q - 1);
         return 1 + 1;

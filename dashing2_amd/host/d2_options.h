@@ -55,6 +55,10 @@ struct Options {
                                           // single-row count-sketch of that many cells (K3k) instead of exactly; 0 = exact counting.  Elsewhere only to_string() shows it
     bool bed = false;                     // --bed (options.h:149; DataType BED, sketch_core.cpp:48-62): every input is an interval file, a position of a line is an element (K1i)
     bool normalize_intervals = false;     // --normalize-intervals (options.h:150): with --bed --multiset a line adds 1 / (stop - start) to each of its positions
+    bool edit_space = false;              // --edit-distance (options.h:134,337): sketch space SPACE_EDIT_DISTANCE
+    bool compute_edit = false;            // --compute-edit-distance (options.h:110): measure M_EDIT_DISTANCE
+    bool edit = false;                    // both, with --parse-by-seq and a matrix output: exact edit distances between the records of one file (K2h);
+                                          // every other use of the two flags is refused by parse_options
     int fmt_compat = 0;                   // --fmt-compat {10,11} (not a reference flag): float text layout of fmt < 11 / >= 11; 0 = not given (10)
 
     unsigned nthreads() const { return nt < 1 ? 1u : unsigned(nt); }      // as requested (-p / OMP_NUM_THREADS): what is printed

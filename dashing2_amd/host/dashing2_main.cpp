@@ -123,6 +123,10 @@ int cmp_main(int argc, char **argv) {                             // src/cmp_mai
     o.device = job_devices(o)[0];
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "cmp");
+    if (o.edit) {
+        if (o.paths.empty()) { std::fprintf(stderr, "No paths provided. See usage.\n"); cmp_usage(); return 1; }
+        return edit_distance_job(o);
+    }
     if (o.presketched) sniff_presketched_suffix(o);
     if (o.exact && sparse_job_name(o)) refuse_out_of_scope(std::string(sparse_job_name(o)) + " of exact k-mer sets (*.kmerset64)");
     if (o.exact && o.presketched)                                   // a missing file is named before a context is asked for

@@ -503,6 +503,42 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     write_stacked(res, o);
 }
 
+// --parse-by-seq --edit-distance --compute-edit-distance: the reference keeps every record's bytes (sequences_, fastxsketchbyseq.cpp:243-246),
+// OrderMinHash-sketches them (:296-312; not built) and compare() calls edlib on the bytes (cmp_core.cpp:450-457).  Here the
+// records are read by the walker of sketch_core_byseq in its raw form (d2g_seqrecs: the same names and boundaries) and go to the device
+// as they are; nothing is sketched.  Every refusal that depends on the file comes before a GPU context is asked for.
+int edit_distance_job(const Options &o) {
+    if (o.paths.size() != 1)
+        die("parse-by-seq currently only handles one file at a time. To process multiple files, simply concatenate them into one file, and run dashing2 on that.");
+    const double t0 = now();
+    d2g_seqrecs *sr = nullptr;
+    check(nullptr, d2g_seqrecs_create(&sr), "d2g_seqrecs_create");
+    if (d2g_seqrecs_add_path(sr, o.paths[0].c_str()) != D2G_OK) die("Failed to read from " + o.paths[0]);
+    const size_t N = d2g_seqrecs_nrecords(sr);
+    const uint64_t *off = d2g_seqrecs_off(sr);
+    Result res;
+    res.names.resize(N);
+    for (size_t i = 0; i < N; ++i) res.names[i] = d2g_seqrecs_name(sr, i);
+    for (size_t i = 0; i < N; ++i)
+        if (off[i + 1] == off[i]) {                                                  // fastxsketchbyseq.cpp:302-305
+            std::fprintf(stderr, "EMPTY SEQ at idx %zu for %s in path %s\n", i, res.names[i].c_str(), o.paths[0].c_str());
+            std::exit(1);
+        }
+    for (size_t i = 0; i < N; ++i)
+        if (off[i + 1] - off[i] > D2G_EDIT_MAX_LEN)
+            refuse_out_of_scope("record " + res.names[i] + " of " + std::to_string(off[i + 1] - off[i]) + " symbols (an edit distance between records of more than " +
+                                std::to_string(D2G_EDIT_MAX_LEN) + " symbols, D2G_EDIT_MAX_LEN)");
+    char err[200] = "";
+    if (d2g_seqset_check(d2g_seqrecs_bytes(sr), off, N, off[N], err, sizeof err) != D2G_OK) die(err);
+    const double t_read = now() - t0;
+    LazyCtx lctx(o, D2G_WARM_COPY | D2G_WARM_EDIT);
+    d2g_ctx *ctx = lctx.get();
+    g_stats.nest("context", Json::object().num("create_s", lctx.t_create).num("warmup_s", lctx.t_warm).num("inputs_loaded_s", t_read).raw("switches", context_switches_json(ctx)));
+    cmp_core_edit(o, res, ctx, sr, t_read);
+    d2g_seqrecs_destroy(sr);
+    return 0;
+}
+
 // --set / --countdict (fastxsketch.cpp:425-441,462-524): Counter::finalize(vector&, vector&, threshold) per input, on the GPU
 // (d2g_sketcher_run_sets: K3's exact counts, sorted on the device), the key file and the count file per input -- always written, with
 // or without --cache (:462).  Inputs are parsed by the host parser and go to the device in batches of about 32 MB of packed bases.
@@ -702,6 +738,7 @@ int sketch_main(int argc, char **argv) {                          // src/sketch_
     o.device = job_devices(o)[0];
     g_stats.on = !o.gpu_stats.empty(); g_stats.path = o.gpu_stats;
     g_stats.str("command", "sketch");
+    if (o.edit) return edit_distance_job(o);
     LazyCtx lctx(o, D2G_WARM_COPY | (o.bed ? D2G_WARM_K1I | (o.sspace == SPACE_MULTISET ? D2G_WARM_K3 : 0) : o.sspace == SPACE_MULTISET || o.count_threshold >= 2 || o.exact ? D2G_WARM_K3 : D2G_WARM_K1) | (o.cmpout.empty() ? 0 : o.exact ? D2G_WARM_KSET : D2G_WARM_K2));
     Result res;
     ExactSets es;

@@ -95,6 +95,7 @@ int         d2g_host_unregister(d2g_ctx *ctx, void *hptr);
 #define D2G_WARM_KSET 32
 #define D2G_WARM_SCREEN 64
 #define D2G_WARM_K1I  128     /* the interval kernels (K1i, below) */
+#define D2G_WARM_EDIT 256     /* the edit-distance kernels (K2h, below) */
 int         d2g_warmup(d2g_ctx *ctx, int what);
 /* "<marketing name> (<gcn arch>, <n> CUs)" of a device, for logs and --gpu-stats */
 int         d2g_device_name(int device, char *buf, size_t cap);
@@ -118,6 +119,8 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
                                  * pair kernel of d2g_kset_isz_*_dev; "ksetprep": the slice table of a d2g_kset */
 #define D2G_TIME_SCREEN 1024    /* "screen": the count walk of d2g_screen_add_dev / d2g_sketcher_run_screen; "screenreduce": the per-reference
                                  * sums of d2g_screen_result; "screenbuild": the table of d2g_screen_create */
+#define D2G_TIME_EDIT   2048    /* "edit": the pair kernel of d2g_edit_*_dev (the launches of one call under one bracket); "editprep": the upload and
+                                 * recoding of d2g_seqset_create */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -1059,6 +1062,55 @@ int    d2g_epilogue_exact_ut(const uint64_t *isz, const double *cards, size_t N,
                              float *out);
 int    d2g_epilogue_exact_rect(const uint64_t *isz, const double *cards, size_t N, size_t a0, size_t a1, size_t b0, size_t b1,
                                int measure, int k, int nthreads, float *out);
+
+/* ---- K2h: exact edit distances between records, --parse-by-seq --edit-distance --compute-edit-distance (reference
+ * src/cmp_core.cpp:331-347,450-457: edlibAlign in global distance mode on the two records' raw bytes) ---------------------
+ * d(i, j) = the unit-cost Levenshtein distance between the BYTES of records i and j: no case folding, every byte value its own
+ * symbol.  An integer, returned exactly as u32.  There is no floating point on the device path.
+ *
+ * d2g_seqrecs: the host record reader.  The kseq record walk of d2g_seqpack_add_path_by_record / _add_fastx_by_record (the same
+ * walker: names and record boundaries cannot differ), keeping the raw sequence bytes instead of packing them: names, one
+ * concatenated byte array, off[n + 1].  An empty record is kept with length 0.  A record that the walk drops as an error (a FASTQ
+ * record whose quality length differs) is dropped here too, and ends the input. */
+typedef struct d2g_seqrecs d2g_seqrecs;
+int             d2g_seqrecs_create(d2g_seqrecs **out);
+void            d2g_seqrecs_destroy(d2g_seqrecs *sr);
+int             d2g_seqrecs_add_path(d2g_seqrecs *sr, const char *path_line);   /* FASTA/FASTQ(.gz), space-separated sub-paths */
+int             d2g_seqrecs_add_fastx(d2g_seqrecs *sr, const char *buf, size_t len);
+size_t          d2g_seqrecs_nrecords(const d2g_seqrecs *sr);
+const char     *d2g_seqrecs_name(const d2g_seqrecs *sr, size_t record);
+const uint8_t  *d2g_seqrecs_bytes(const d2g_seqrecs *sr);
+const uint64_t *d2g_seqrecs_off(const d2g_seqrecs *sr);              /* [nrecords + 1] */
+/* A d2g_seqset owns N records in device memory, recoded to dense codes 0 .. sigma - 1 in order of byte value (sigma = the number of
+ * distinct byte values of the set, 1 <= sigma <= 256; a set without a byte has sigma = 1), each record padded to 16 codes, with
+ * their lengths and an order of the records by length.
+ * d2g_seqset_check: the host-side check of d2g_seqset_create on its own (no context, no device): D2G_ERR_INVALID with a message in
+ * err (may be NULL) for null tables, an off that does not begin at 0 or decreases, off[nrec] != nbytes; D2G_ERR_UNSUPPORTED for a
+ * record of more than D2G_EDIT_MAX_LEN symbols (the message has the record and its length).
+ * d2g_seqset_recode_map: map[b] = the code of byte value b (0 for a value that does not occur); returns sigma.
+ * d2g_seqset_create copies the records once and recodes them on the device; D2G_ERR_NOMEM with the bytes needed and the bytes free
+ * when they do not fit, never a smaller object. */
+#define D2G_EDIT_MAX_LEN 65535
+typedef struct d2g_seqset d2g_seqset;
+int    d2g_seqset_check(const uint8_t *bytes, const uint64_t *off /* [nrec+1] */, size_t nrec, uint64_t nbytes, char *err, size_t errcap);
+int    d2g_seqset_recode_map(const uint8_t *bytes, uint64_t nbytes, uint8_t map[256]);
+int    d2g_seqset_create(d2g_ctx *ctx, const uint8_t *bytes, const uint64_t *off /* [nrec+1] */, size_t nrec, uint64_t nbytes, d2g_seqset **out);
+void   d2g_seqset_destroy(d2g_seqset *ss);
+size_t d2g_seqset_nrecords(const d2g_seqset *ss);
+size_t d2g_seqset_device_bytes(const d2g_seqset *ss);        /* resident bytes: codes, offsets, lengths, order */
+int    d2g_seqset_alphabet_size(const d2g_seqset *ss);       /* sigma */
+/* the 32-row blocks of a query that one strip of the pair kernel holds for this set under this context's switches (D2G_EDIT_STRIP):
+ * a longer query runs strip by strip */
+int    d2g_seqset_strip_blocks(const d2g_ctx *ctx, const d2g_seqset *ss);
+/* rows [r0, r1) of the condensed upper triangle, in the order of d2g_kset_isz_ut_dev: d2g_ut_count(N, r0, r1) u32.  A pair with an
+ * empty record yields the other's length.  An empty range is D2G_OK and writes nothing; a set of another context is D2G_ERR_INVALID
+ * before anything is written. */
+int    d2g_edit_ut_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, uint32_t *out_dev, void *stream);
+/* the row-major block rows [a0, a1) x columns [b0, b1), d(row, column); (r, r) is 0 (--square) */
+int    d2g_edit_rect_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t a0, size_t a1, size_t b0, size_t b1, uint32_t *out_dev, void *stream);
+/* host-pointer forms; synchronise */
+int    d2g_edit_ut(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, uint32_t *out);
+int    d2g_edit_rect(d2g_ctx *ctx, const d2g_seqset *ss, size_t a0, size_t a1, size_t b0, size_t b1, uint32_t *out);
 
 /* ---- multi-GPU row partition (host arithmetic; emitrect.cpp:290-323 row order) ----
  * Splits rows [0,N) into `nparts` contiguous ranges with (near-)equal pair counts.
