@@ -4,14 +4,17 @@
 //   ingest: host/ingest_pipeline.h + host/bounded_queue.h as `dashing2 sketch` runs them (sketch_cmd.cpp sketch_core): reader
 //           threads -> raw staging buffers or d2g_seqpack -> ready queue -> several consumers -> finisher queue -> one finisher.
 //           Fake device threads stand in for the GPU: they check the bytes or the base count of every group they get.
-//   emit:   producer filling slots -> SlotQueue -> consumer formatting floats (cmp_dense.cpp / host/slot_queue.h)
+//   emit:   host/row_batches.h + host/slot_queue.h as every dense `dashing2 cmp` job runs them (cmp_dense.cpp): run_row_batches over
+//           triangles, rectangles and panels with 1 - 3 fake lanes that fill their slots from (row, column), and a consumer that
+//           checks and formats every row.
 // The group planner is checked here too, against sizes written out by hand.
 // Exit code 0 and no ThreadSanitizer report = pass.
 #include "../../../include/d2g.h"
 #include "../../host/bounded_queue.h"
 #include "../../host/fmtfloat.h"
 #include "../../host/ingest_pipeline.h"
-#include "../../host/slot_queue.h"
+#include "../../host/row_batches.h"
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <cstring>
@@ -213,31 +216,95 @@ static int ingest_checks() {
     return 0;
 }
 
-int main() {
-    if (planner_checks() || ingest_checks()) return 1;
-    // ---------------------------------------------------------------- emit pipeline
-    struct Job { const float *data; size_t n; };
-    constexpr int NSLOT = 3;
-    std::vector<std::vector<float>> slots(NSLOT, std::vector<float>(4096));
+// ---------------------------------------------------------------- row batches: the loop of every dense `cmp` job
+// the value a fake lane computes for (row, column); exact in float
+static float cell(size_t row, size_t col) { return float((row * 131 + col * 7) % 100003) / 8.f; }
+
+// One run of the real run_row_batches with W fake lanes.  launch notes the batch its lane was given; finish checks it, fills its slot from (row, column)
+// and raises the slot's flag; the consumer checks rows, order and values, formats them, and lowers the flag.  -> values consumed
+static int row_batch_run(const CmpShape &sh, int W, size_t cap, size_t &nformatted) {
+    const int nslots = 2 * W + 1;
+    std::vector<std::vector<float>> slots(nslots, std::vector<float>(std::max<size_t>({cap, sh.widest, 1})));
+    std::vector<std::atomic<int>> full(nslots);                          // set by finish, cleared by the consumer
+    for (auto &f : full) f = 0;
+    std::atomic<int> errors{0}, outstanding{0}, most{0};
+    struct Seen { int lane; Batch bt; };
+    std::vector<Seen> finished;                                          // producer side only, like inflight
+    std::vector<Batch> inflight(W, Batch{0, 0, 0});                      // what launch gave a lane; cnt == 0: nothing
+    size_t next_row = 0, sum_cnt = 0;                                    // consumer side only; read after the run
     std::string text;
-    size_t nvals = 0;
-    {
-        d2h::SlotQueue<Job> q(NSLOT, [&](const Job &j) {
-            char buf[d2h::FMT_MAX_FLOAT_CHARS + 1];
-            for (size_t i = 0; i < j.n; ++i) { const size_t l = d2h::format_float(j.data[i], buf); text.append(buf, l); text += '\t'; }
-            nvals += j.n;
+    const RowBatchRun run = run_row_batches(sh, cap, W, nslots,
+        [&](int lane, const Batch &bt) {
+            if (lane < 0 || lane >= W || inflight[lane].cnt || !bt.cnt) { ++errors; return; }   // one batch per lane; never one without values
+            inflight[lane] = bt;
+        },
+        [&](int lane, const Batch &bt, int slot) -> const float * {
+            if (slot < 0 || slot >= nslots) { ++errors; return nullptr; }
+            if (bt.r1 <= bt.r0 || (bt.cnt > cap && bt.r1 - bt.r0 != 1)) ++errors;
+            if (bt.cnt && (inflight[lane].r0 != bt.r0 || inflight[lane].r1 != bt.r1 || inflight[lane].cnt != bt.cnt)) ++errors;   // the batch this lane was given
+            if (!bt.cnt && inflight[lane].cnt) ++errors;
+            inflight[lane].cnt = 0;
+            finished.push_back({lane, bt});
+            if (full[slot].exchange(1) != 0) ++errors;                   // handed out while its job is unconsumed
+            const int out = ++outstanding;
+            if (out > most) most = out;
+            float *p = slots[slot].data();
+            for (size_t i = bt.r0; i < bt.r1; ++i)
+                for (size_t j = 0; j < sh.nvals(i); ++j) *p++ = cell(i, sh.symmetric ? i + 1 + j : sh.c0 + j);
+            if (size_t(p - slots[slot].data()) != bt.cnt) ++errors;
+            return slots[slot].data();
+        },
+        [&](const Batch &bt, const float *data) {
+            int slot = -1;
+            for (int s = 0; s < nslots; ++s) if (data == slots[s].data()) slot = s;
+            if (slot < 0 || bt.r0 != next_row) { ++errors; return; }      // every row once, in ascending order
+            char buf[FMT_MAX_FLOAT_CHARS + 1];
+            const float *p = data;
+            for (size_t i = bt.r0; i < bt.r1; ++i)
+                for (size_t j = 0; j < sh.nvals(i); ++j, ++p) {
+                    if (*p != cell(i, sh.symmetric ? i + 1 + j : sh.c0 + j)) ++errors;
+                    text.append(buf, format_float(*p, buf));
+                }
+            next_row = bt.r1; sum_cnt += bt.cnt;
+            --outstanding;
+            if (full[slot].exchange(0) != 1) ++errors;
         });
-        std::mt19937 rng(5);
-        for (int b = 0; b < 200; ++b) {
-            const int s = q.acquire();
-            const size_t n = 1 + rng() % slots[s].size();
-            for (size_t i = 0; i < n; ++i) slots[s][i] = float(rng() % 100000) / float(1 + rng() % 1000);   // producer writes the slot ...
-            q.submit(s, Job{slots[s].data(), n});                                                           // ... the consumer reads it
-        }
-        q.finish();
-        REQUIRE(q.t_busy >= 0);
-    }
-    REQUIRE(nvals > 0 && !text.empty());
-    std::printf("host threads selftest OK (planner, ingest pipeline, %zu values formatted)\n", nvals);
+    nformatted += sum_cnt;
+    REQUIRE(errors == 0);
+    REQUIRE(next_row == sh.nrows && sum_cnt == sh.total_vals && run.nbatches == finished.size() && outstanding == 0 && most <= nslots);
+    for (size_t b = 0; b < finished.size(); ++b)                         // consecutive batches, dealt to the lanes in turn
+        REQUIRE(finished[b].bt.r0 == (b ? finished[b - 1].bt.r1 : 0) && finished[b].lane == int(b % size_t(W)));
+    if (cap >= sh.total_vals && (sh.symmetric || sh.ncol)) REQUIRE(run.nbatches == (sh.nrows ? 1 : 0));   // rows without columns go `cap` at a time
+    REQUIRE(run.t_dev_busy >= 0 && run.t_emit_busy >= 0 && run.t_wall >= 0 && text.size() >= sum_cnt);
+    return 0;
+}
+
+static int row_batch_checks(size_t &nformatted) {
+    const CmpShape tri(true, false, 7, 0), sq(false, false, 9, 0), panel(false, true, 12, 5);
+    REQUIRE(tri.nrows == 7 && tri.total_vals == 21 && tri.widest == 6 && tri.nvals(0) == 6 && tri.nvals(6) == 0 && std::string(tri.name()) == "upper triangle");
+    REQUIRE(sq.nrows == 9 && sq.ncol == 9 && sq.c0 == 0 && sq.total_vals == 81 && sq.nvals(3) == 9 && std::string(sq.name()) == "square");
+    REQUIRE(panel.nrows == 7 && panel.c0 == 7 && panel.c1 == 12 && panel.ncol == 5 && panel.total_vals == 35 && panel.nvals(6) == 5 && std::string(panel.name()) == "panel");
+    REQUIRE(tri.slot_cap(1) == 6 && tri.slot_cap(10) == 10 && tri.slot_cap(100) == 21 && CmpShape(true, false, 0, 0).slot_cap(5) == 1 && CmpShape(true, false, 1, 0).slot_cap(5) == 1);
+    const Batch b = tri.batch(1, 9);                                     // rows 1 and 2 hold 5 + 4 values, row 3 would make 12
+    REQUIRE(b.r0 == 1 && b.r1 == 3 && b.cnt == 9 && panel.batch(2, 12).r1 == 4 && panel.batch(2, 12).cnt == 10 && panel.batch(6, 100).r1 == 7);
+    std::vector<CmpShape> shapes;
+    for (size_t ns : {0, 1, 2, 7, 200}) shapes.emplace_back(true, false, ns, 0);
+    for (auto rc : {std::pair<size_t, size_t>{0, 5}, {3, 0}, {7, 5}, {64, 33}}) shapes.emplace_back(false, true, rc.first + rc.second, rc.second);   // nrows x ncol, c0 = nrows
+    shapes.push_back(sq);
+    for (const CmpShape &sh : shapes)
+        for (int W : {1, 2, 3})
+            for (size_t cap : {size_t(1), sh.widest, sh.widest + 1, sh.total_vals, sh.total_vals + 1})
+                if (row_batch_run(sh, W, cap, nformatted)) {
+                    std::fprintf(stderr, "row batches: %s, ns %zu, %zu rows x %zu columns from %zu, W %d, cap %zu\n", sh.name(), sh.ns, sh.nrows, sh.ncol, sh.c0, W, cap);
+                    return 1;
+                }
+    return 0;
+}
+
+int main() {
+    size_t nvals = 0;
+    if (planner_checks() || ingest_checks() || row_batch_checks(nvals)) return 1;
+    REQUIRE(nvals > 0);
+    std::printf("host threads selftest OK (planner, ingest pipeline, row batches: %zu values formatted)\n", nvals);
     return 0;
 }

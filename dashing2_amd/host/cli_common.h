@@ -116,11 +116,28 @@ struct Stats {
 inline Stats g_stats;
 constexpr int TIME_ALL = D2G_TIME_EDIT | D2G_TIME_K0 | D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN;
 
-// {"launches": n, "avg_ms": a, "total_ms": n a} of one timed kernel family on one context (synchronises on its events)
+// One timed kernel family on one context: launches and HIP-event milliseconds; ok == false: the library does not know the family
+struct KAcc {
+    bool ok = false; int launches = 0; float avg_ms = 0, last_ms = 0; double total_ms = 0;
+    KAcc &operator+=(const KAcc &k) { launches += k.launches; total_ms += k.total_ms; return *this; }
+    Json json() const { return Json::object().integer("launches", launches).num("total_ms", total_ms); }   // {"launches": n, "total_ms": t}
+};
+// reads (and by default resets) the family's log; synchronises on its events
+inline KAcc kernel_acc(d2g_ctx *ctx, const char *which, bool reset = true) {
+    KAcc k;
+    if (d2g_kernel_ms(ctx, which, reset, &k.launches, &k.avg_ms, &k.last_ms) != D2G_OK) return KAcc();
+    k.ok = true; k.total_ms = double(k.avg_ms) * k.launches;
+    return k;
+}
+// {"launches": n, "avg_ms": a, "total_ms": n a}; null for an unknown family
 inline std::string kernel_json(d2g_ctx *ctx, const char *which, bool reset = true) {
-    int n = 0; float avg = 0, last = 0;
-    if (d2g_kernel_ms(ctx, which, reset, &n, &avg, &last) != D2G_OK) return "null";
-    return Json::object().integer("launches", n).num("avg_ms", avg).num("total_ms", double(avg) * n).text();
+    const KAcc k = kernel_acc(ctx, which, reset);
+    return k.ok ? Json::object().integer("launches", k.launches).num("avg_ms", k.avg_ms).num("total_ms", k.total_ms).text() : "null";
+}
+// D2G_GROUP_BYTES: the packed bytes after which `sketch` closes a group of inputs (tests: many small groups); else the job's default
+inline size_t group_bytes_limit(size_t default_bytes) {
+    if (const char *e = std::getenv("D2G_GROUP_BYTES")) { const long long v = std::atoll(e); if (v >= 1) return size_t(v); }
+    return default_bytes;
 }
 
 // D2G_DEVICES = "all" | "0,1,2": the GPUs a job may spread over -- `sketch` deals its input groups to them (no collectives),

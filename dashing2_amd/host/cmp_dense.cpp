@@ -1,12 +1,12 @@
 // cmp_dense.cpp -- the dense outputs of `dashing2 cmp` / `sketch --cmpout`: condensed triangle, square matrix, panel.  Mirrors
 //   cmp_core (densify)       src/cmp_core.cpp:686-718,746-751
 //   emit_rectangular         src/emitrect.cpp:108-403
-// on one GPU or, rows dealt round-robin, on several (D2G_DEVICES).
+// on one GPU or, rows dealt round-robin, on several (D2G_DEVICES).  Four jobs -- registers on one GPU, on several, exact sets, edit
+// distances -- each: set-up, the two callbacks it hands to the one row-batch loop (row_batches.h), a report.
 #include "cli_common.h"
 #include "fmtfloat.h"
-#include "slot_queue.h"
-#include <functional>
-#include <memory>
+#include "row_batches.h"
+#include <deque>
 
 namespace d2h {
 
@@ -45,17 +45,16 @@ struct Emitter {
         for (size_t i = 0; i < ns; ++i) { std::fputc('\t', fp); std::fwrite(res.names[i].data(), 1, res.names[i].size(), fp); }
         std::fputc('\n', fp);
     }
-    // rows [r0, r1); row i has nvals(i) values starting at data + off(i)
-    template <class NV> void rows(size_t r0, size_t r1, const float *data, NV nvals) {
+    // the rows of one batch; row i has sh.nvals(i) values, one row after the other in `data`
+    void rows(const Batch &bt, const float *data, const CmpShape &sh) {
+        const size_t r0 = bt.r0, r1 = bt.r1;
         if (o.of == MACHINE_READABLE) {                                  // emitrect.cpp:189-192
-            size_t tot = 0;
-            for (size_t i = r0; i < r1; ++i) tot += nvals(i);
-            if (std::fwrite(data, sizeof(float), tot, fp) != tot) die("Failed to write rows " + std::to_string(r0) + "-" + std::to_string(r1) + " to disk");
+            if (std::fwrite(data, sizeof(float), bt.cnt, fp) != bt.cnt) die("Failed to write rows " + std::to_string(r0) + "-" + std::to_string(r1) + " to disk");
             return;
         }
         const size_t n = r1 - r0;
         std::vector<size_t> off(n + 1, 0);
-        for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + nvals(r0 + i);
+        for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + sh.nvals(r0 + i);
         std::vector<std::string> text(n);
 #ifdef _OPENMP
         #pragma omp parallel for schedule(dynamic, 8) num_threads(o.workers())
@@ -83,16 +82,8 @@ struct Emitter {
     }
 };
 
-// Row batches flow device -> host slot -> emitter thread: the kernel + D2H (+ host x87 epilogue) of batch i+1 run while
-// batch i is formatted / written (the CLI ran kernel -> D2H -> emit strictly in series per 512 MiB batch).
-// The queue itself is slot_queue.h (exercised under ThreadSanitizer by `make tsan`).
-struct EmitJob { size_t r0, r1; const float *data; std::function<size_t(size_t)> nvals; };
-struct EmitQueue : SlotQueue<EmitJob> {
-    EmitQueue(Emitter &em, int nslots) : SlotQueue<EmitJob>(nslots, [&em](const EmitJob &j) { em.rows(j.r0, j.r1, j.data, j.nvals); }) {}
-};
-
-// values per row batch: a slot is one batch's staging; three slots cycle device -> host epilogue -> emitter.  Small jobs take small
-// slots (more batches cost little: the pair kernel is launched per row range), big jobs 64 MiB ones.
+// values per row batch: a slot is one batch's staging; the slots cycle device -> host epilogue -> emitter (row_batches.h).  Small jobs
+// take small slots (more batches cost little: the pair kernel is launched per row range), big jobs 64 MiB ones.
 size_t cmp_slot_values(size_t total_vals) {
     size_t v = std::min<size_t>(size_t(1) << 24, std::max<size_t>(size_t(1) << 22, total_vals / 12));
     if (const char *e = std::getenv("D2G_CMP_SLOT_VALUES")) { const long long x = std::atoll(e); if (x >= 1) v = size_t(x); }   // tests: tiny slots
@@ -100,27 +91,17 @@ size_t cmp_slot_values(size_t total_vals) {
 }
 
 // ------------------------------------------------------------------------------------ the job
-// the shape of a dense comparison job (src/emitrect.cpp:211-323): which rows are emitted, how many values each has
-struct CmpShape {
-    bool symmetric; size_t ns, nrows, c0, c1, ncol, total_vals, widest;
-    CmpShape(const Options &o, const Result &res) {
-        ns = res.names.size();
-        symmetric = o.ok == SYMMETRIC_ALL_PAIRS || o.ok == PHYLIP;
-        const size_t nq = res.nq, nf = o.ok == PANEL ? ns - nq : ns;
-        c0 = o.ok == PANEL ? nf : 0; c1 = ns; ncol = symmetric ? 0 : c1 - c0;
-        nrows = symmetric ? ns : nf;
-        total_vals = symmetric ? ns * (ns - 1) / 2 : nf * ncol;
-        widest = symmetric ? (ns ? ns - 1 : 0) : ncol;
-    }
-    // the batch of rows starting at r0 that fits `cap` values -> (r1, values)
-    std::pair<size_t, size_t> batch(size_t r0, size_t cap) const {
-        size_t r1 = r0, cnt = 0;
-        if (symmetric) while (r1 < ns && (cnt == 0 || cnt + (ns - 1 - r1) <= cap)) { cnt += ns - 1 - r1; ++r1; }
-        else { r1 = std::min(nrows, r0 + std::max<size_t>(1, cap / std::max<size_t>(ncol, 1))); cnt = (r1 - r0) * ncol; }
-        return {r1, cnt};
-    }
-    const char *name(const Options &o) const { return symmetric ? "upper triangle" : o.ok == PANEL ? "panel" : "square"; }
+// the shape of the dense job that an Options / Result pair asks for, and the values per row batch it runs with
+struct JobShape : CmpShape {
+    const size_t cap;
+    JobShape(const Options &o, const Result &res)
+        : CmpShape(o.ok == SYMMETRIC_ALL_PAIRS || o.ok == PHYLIP, o.ok == PANEL, res.names.size(), res.nq), cap(slot_cap(cmp_slot_values(total_vals))) {}
 };
+// the one loop of every dense job: the rows of a finished batch go to the emitter on the queue's thread
+template <class Launch, class Finish>
+RowBatchRun emit_row_batches(const JobShape &sh, Emitter &em, int W, size_t nslots, Launch launch, Finish finish) {
+    return run_row_batches(sh, sh.cap, W, int(nslots), launch, finish, [&](const Batch &bt, const float *data) { em.rows(bt, data, sh); });
+}
 
 // One dense job: what is counted on the device and how a count becomes the float that is written.
 //   have_lut   the value is a table of the equality count alone (a triangle then comes back from the device as floats: `fused`)
@@ -128,33 +109,34 @@ struct CmpShape {
 //   trunc      --fastcmp: the registers were truncated to o.regbytes; trunc_b: the setsketch base (null for b-bit codes)
 struct DenseJob {
     const Options &o;
-    const CmpShape sh;
+    const JobShape sh;
     const size_t S;
     const double *cards;
     const bool have_lut, need_gtlt, trunc, multiset;
     const std::vector<float> &lut;
     const long double *trunc_b;
-    const size_t cap;                                                   // values per row batch
     DenseJob(const Options &oo, const Result &res, bool lutv, bool gtlt, bool tr, bool ms, const std::vector<float> &l, const long double *tb)
-        : o(oo), sh(oo, res), S(oo.sketchsize), cards(res.cardinalities.data()), have_lut(lutv), need_gtlt(gtlt), trunc(tr), multiset(ms), lut(l), trunc_b(tb),
-          cap(std::max<size_t>(1, std::min(std::max(cmp_slot_values(sh.total_vals), sh.widest), std::max<size_t>(sh.total_vals, 1)))) {}
+        : o(oo), sh(oo, res), S(oo.sketchsize), cards(res.cardinalities.data()), have_lut(lutv), need_gtlt(gtlt), trunc(tr), multiset(ms), lut(l), trunc_b(tb) {}
     bool fused() const { return have_lut && sh.symmetric; }
 };
-struct Batch { size_t r0, r1, cnt; };
 // where one GPU computes its batches: the operand, the table, the counts of the batch in flight
 struct DenseDevice {
     d2g_ctx *ctx; const d2g_cmp_set *set;
-    DevBuf dlut, da;
-    std::unique_ptr<DevBuf> db;
-    DenseDevice(const DenseJob &j, d2g_ctx *c, const d2g_cmp_set *s) : ctx(c), set(s), dlut(c, (j.S + 1) * sizeof(float)), da(c, j.cap * 4) {
+    DevBuf dlut, da, db;                                                // db: the lt counts of a (gt, lt) job
+    DenseDevice(const DenseJob &j, d2g_ctx *c, const d2g_cmp_set *s)
+        : ctx(c), set(s), dlut(c, (j.S + 1) * sizeof(float)), da(c, j.sh.cap * 4), db(c, j.need_gtlt ? j.sh.cap * 4 : 0) {
         if (j.have_lut) check(ctx, d2g_memcpy_h2d(ctx, dlut.p, j.lut.data(), (j.S + 1) * sizeof(float), nullptr), "h2d lut");
-        if (j.need_gtlt) db.reset(new DevBuf(c, j.cap * 4));
     }
 };
-// plain memory: nothing to page-lock, nothing for a helper thread to do
+// One slot's staging: what comes back from the device (`raw`: counts, intersection sizes, distances; `raw2`: the lt counts of a
+// (gt, lt) job) and the floats made of it.  Plain memory: nothing to page-lock, nothing for a helper thread to do
 struct HostSlot {
-    HostBuf out, ca, cb;
-    explicit HostSlot(const DenseJob &j) : out(j.cap * 4), ca(j.fused() ? 4 : j.cap * 4), cb(j.need_gtlt ? j.cap * 4 : 4) {}
+    HostBuf out, raw, raw2;
+    HostSlot(size_t out_bytes, size_t raw_bytes, size_t raw2_bytes) : out(out_bytes), raw(raw_bytes), raw2(raw2_bytes) {}
+};
+struct HostSlots : std::deque<HostSlot> {                               // the 2 W + 1 slots of a job on W lanes
+    HostSlots(int W, size_t out_bytes, size_t raw_bytes, size_t raw2_bytes = 0) { for (int i = 0; i < 2 * W + 1; ++i) emplace_back(out_bytes, raw_bytes, raw2_bytes); }
+    HostSlots(int W, const DenseJob &j) : HostSlots(W, j.sh.cap * 4, j.fused() ? 0 : j.sh.cap * 4, j.need_gtlt ? j.sh.cap * 4 : 0) {}
 };
 
 // counts of a rectangular batch -> floats (emitrect.cpp:211-268 call compare(i, j) per cell: cmp_core.cpp:458-517)
@@ -177,8 +159,7 @@ void rect_epilogue(const DenseJob &j, const Batch &bt, const uint32_t *ca, const
 
 // starts the pair kernel of one batch on a device (asynchronous): triangle rows emitrect.cpp:290-323, rectangle rows :211-268
 void launch_batch(const DenseJob &j, DenseDevice &d, const Batch &bt) {
-    if (!bt.cnt) return;
-    uint32_t *a = (uint32_t *)d.da.p, *b = d.db ? (uint32_t *)d.db->p : nullptr;
+    uint32_t *a = (uint32_t *)d.da.p, *b = (uint32_t *)d.db.p;
     if (j.sh.symmetric) {
         if (j.have_lut) check(d.ctx, d2g_cmp_lut_ut_dev(d.ctx, d.set, bt.r0, bt.r1, (const float *)d.dlut.p, (float *)d.da.p, nullptr), "d2g_cmp_lut_ut_dev");
         else if (j.need_gtlt) check(d.ctx, d2g_cmp_gtlt_ut_dev(d.ctx, d.set, bt.r0, bt.r1, a, b, nullptr), "d2g_cmp_gtlt_ut_dev");
@@ -190,16 +171,16 @@ void launch_batch(const DenseJob &j, DenseDevice &d, const Batch &bt) {
 }
 
 // copies the batch back into a host slot and finishes it there (x87 epilogue on the host: cmp_core.cpp:458-517; truncated
-// registers: 406-448), then hands its rows to the emitter thread
-void finish_batch(const DenseJob &j, DenseDevice &d, const Batch &bt, EmitQueue &eq, int si, HostSlot &sl) {
+// registers: 406-448) -> the floats of its rows
+const float *finish_batch(const DenseJob &j, DenseDevice &d, const Batch &bt, HostSlot &sl) {
     const Options &o = j.o;
     const CmpShape &sh = j.sh;
     const size_t ns = sh.ns, S = j.S;
     float *out = sl.out.as<float>();
-    uint32_t *ca = sl.ca.as<uint32_t>(), *cb = j.need_gtlt ? sl.cb.as<uint32_t>() : nullptr;
+    uint32_t *ca = sl.raw.as<uint32_t>(), *cb = j.need_gtlt ? sl.raw2.as<uint32_t>() : nullptr;
     if (bt.cnt && j.fused()) check(d.ctx, d2g_memcpy_d2h(d.ctx, out, d.da.p, bt.cnt * 4, nullptr), "d2h");
     else if (bt.cnt) {
-        if (cb) check(d.ctx, d2g_memcpy_d2h(d.ctx, cb, d.db->p, bt.cnt * 4, nullptr), "d2h");
+        if (cb) check(d.ctx, d2g_memcpy_d2h(d.ctx, cb, d.db.p, bt.cnt * 4, nullptr), "d2h");
         check(d.ctx, d2g_memcpy_d2h(d.ctx, ca, d.da.p, bt.cnt * 4, nullptr), "d2h");
         const int nt = int(o.workers());
         if (sh.symmetric && j.trunc) check(d.ctx, d2g_epilogue_trunc_ut(ca, cb, j.cards, ns, S, bt.r0, bt.r1, o.measure, o.k, o.regbytes, j.trunc_b, nt, out), "d2g_epilogue_trunc_ut");
@@ -207,8 +188,7 @@ void finish_batch(const DenseJob &j, DenseDevice &d, const Batch &bt, EmitQueue 
         else if (j.trunc) check(d.ctx, d2g_epilogue_trunc_rect(ca, cb, j.cards, ns, S, bt.r0, bt.r1, sh.c0, sh.c1, o.measure, o.k, o.regbytes, j.trunc_b, nt, out), "d2g_epilogue_trunc_rect");
         else rect_epilogue(j, bt, ca, cb, out);
     }
-    if (sh.symmetric) eq.submit(si, EmitJob{bt.r0, bt.r1, out, [ns](size_t i) { return ns - 1 - i; }});
-    else { const size_t ncol = sh.ncol; eq.submit(si, EmitJob{bt.r0, bt.r1, out, [ncol](size_t) { return ncol; }}); }
+    return out;
 }
 
 // ------------------------------------------------------------------------------------ --gpu-stats
@@ -284,7 +264,7 @@ struct MultiGpu {
 
 bool cmp_core_multi(const DenseJob &job, Result &res, const std::vector<int> &devs) {
     const Options &o = job.o;
-    const CmpShape &sh = job.sh;
+    const JobShape &sh = job.sh;
     const size_t ns = sh.ns, S = job.S;
     const double t0 = now();
     MultiGpu mg(devs);
@@ -296,46 +276,21 @@ bool cmp_core_multi(const DenseJob &job, Result &res, const std::vector<int> &de
     const double t_prep = now() - t0;
     Emitter em(o, res);
     em.header();
-    std::vector<std::unique_ptr<DenseDevice>> dd(W);
-    for (int r = 0; r < W; ++r) dd[r].reset(new DenseDevice(job, mg.ctxs[r], d2g_allpairs_operand(mg.engs[r])));
-    const int NSLOT = 2 * W + 1;
-    std::vector<std::unique_ptr<HostSlot>> slots(NSLOT);
-    for (auto &sl : slots) sl.reset(new HostSlot(job));
-    double t_dev = 0, emit_busy = 0;
-    const double t_loop = now();
-    size_t nbatches = 0;
-    {
-        EmitQueue eq(em, NSLOT);
-        for (size_t next = 0; next < sh.nrows;) {
-            // one round: up to W consecutive row batches, one per GPU, launched back to back (asynchronous) ...
-            std::vector<Batch> round;
-            const double ta = now();
-            for (int r = 0; r < W && next < sh.nrows; ++r) {
-                const auto b = sh.batch(next, job.cap);
-                round.push_back({next, b.first, b.second});
-                launch_batch(job, *dd[r], round.back());
-                next = b.first;
-            }
-            // ... drained in row order into free slots; the emitter thread writes slot i while the next ones are copied / finished
-            for (size_t b = 0; b < round.size(); ++b) {
-                const int si = eq.acquire();
-                finish_batch(job, *dd[b], round[b], eq, si, *slots[si]);
-                ++nbatches;
-            }
-            t_dev += now() - ta;
-        }
-        eq.finish();
-        emit_busy = eq.t_busy;
-    }
+    std::deque<DenseDevice> dd;
+    for (int r = 0; r < W; ++r) dd.emplace_back(job, mg.ctxs[r], d2g_allpairs_operand(mg.engs[r]));
+    HostSlots slots(W, job);
+    const RowBatchRun run = emit_row_batches(sh, em, W, slots.size(),
+                                             [&](int r, const Batch &bt) { launch_batch(job, dd[r], bt); },
+                                             [&](int r, const Batch &bt, int si) { return finish_batch(job, dd[r], bt, slots[si]); });
     if (o.verbosity) std::fprintf(stderr, "[d2g] cmp on %d GPUs (%s): %zu sketches x S=%zu: upload+exchange+prepare %.3fs, %zu batches %.3fs wall (device+D2H+epilogue %.3fs busy, emit %.3fs busy, overlapped)\n",
-                                  W, mg.transport(), ns, S, t_prep, nbatches, now() - t_loop, t_dev, emit_busy);
+                                  W, mg.transport(), ns, S, t_prep, run.nbatches, run.t_wall, run.t_dev_busy, run.t_emit_busy);
     if (g_stats.on) {
         Json dj = Json::array();
         for (int r = 0; r < W; ++r) dj.push(k2_device_json(devs[r], mg.ctxs[r]));
-        g_stats.nest("cmp", Json::object().integer("sketches", ns).integer("sketchsize", S).integer("values", sh.total_vals).str("shape", sh.name(o)).str("algo", "bitslice")
+        g_stats.nest("cmp", Json::object().integer("sketches", ns).integer("sketchsize", S).integer("values", sh.total_vals).str("shape", sh.name()).str("algo", "bitslice")
                      .str("transport", mg.transport()).integer("exchange_chunks", d2g_allpairs_chunks(mg.engs[0])).raw("bit_planes", planes_json(mg.ctxs[0], d2g_allpairs_operand(mg.engs[0])))
-                     .num("algorithmic_bytes", 8.0 * double(S) * double(ns) + 4.0 * double(sh.total_vals)).integer("batches", nbatches).integer("slot_values", job.cap).nest("devices", dj)
-                     .nest("wall_s", Json::object().num("upload_exchange_prepare", t_prep).num("batches", now() - t_loop).num("device_d2h_epilogue_busy", t_dev).num("emit_busy", emit_busy)));
+                     .num("algorithmic_bytes", 8.0 * double(S) * double(ns) + 4.0 * double(sh.total_vals)).integer("batches", run.nbatches).integer("slot_values", sh.cap).nest("devices", dj)
+                     .nest("wall_s", Json::object().num("upload_exchange_prepare", t_prep).num("batches", run.t_wall).num("device_d2h_epilogue_busy", run.t_dev_busy).num("emit_busy", run.t_emit_busy)));
     }
     return true;
 }
@@ -344,13 +299,11 @@ bool cmp_core_multi(const DenseJob &job, Result &res, const std::vector<int> &de
 // `codes`: the truncated registers of a --fastcmp job (consumed), else empty
 void cmp_core_single(const DenseJob &job, Result &res, d2g_ctx *ctx, std::vector<uint8_t> &codes, const long double *trunc_ab, double t_densify) {
     const Options &o = job.o;
-    const CmpShape &sh = job.sh;
+    const JobShape &sh = job.sh;
     const size_t ns = sh.ns, S = job.S;
     d2g_cmp_set *set = nullptr;
     const double t0 = now();
-    constexpr int NSLOT = 3;
-    std::unique_ptr<HostSlot> slots[NSLOT];
-    for (auto &sl : slots) sl.reset(new HostSlot(job));
+    HostSlots slots(1, job);
     Emitter em(o, res);
     em.header();
     if (job.trunc) check(ctx, d2g_cmp_set_create_codes(ctx, codes.data(), ns, S, o.regbytes, &set), "d2g_cmp_set_create_codes");
@@ -360,40 +313,24 @@ void cmp_core_single(const DenseJob &job, Result &res, d2g_ctx *ctx, std::vector
     DenseDevice dev(job, ctx, set);
     const double t_bufs = now();
     if (o.verbosity) std::fprintf(stderr, "[d2g] cmp set-up: host slots + header + operand upload + prepare %.3fs, device buffers %.3fs (slots of %zu values)\n",
-                                  t_set - t0, t_bufs - t_set, job.cap);
-    double t_dev = 0, emit_busy = 0;
-    size_t nbatches = 0;
-    const double t_loop = now();
-    {
-        EmitQueue eq(em, NSLOT);
-        for (size_t r0 = 0; r0 < sh.nrows;) {
-            const auto b = sh.batch(r0, job.cap);
-            const Batch bt{r0, b.first, b.second};
-            const int si = eq.acquire();
-            const double ta = now();
-            launch_batch(job, dev, bt);
-            finish_batch(job, dev, bt, eq, si, *slots[si]);
-            t_dev += now() - ta;
-            r0 = bt.r1;
-            ++nbatches;
-        }
-        eq.finish();
-        emit_busy = eq.t_busy;
-        if (o.verbosity) std::fprintf(stderr, "[d2g] cmp: %zu sketches x S=%zu: upload+prepare+buffers %.3fs, %zu batches %.3fs wall (device+D2H+epilogue %.3fs busy, emit %.3fs busy, "
-                                              "overlapped) (algo %s)\n", ns, S, t_loop - t0, nbatches, now() - t_loop, t_dev, emit_busy,
-                                      d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE ? "bitslice" : d2g_cmp_set_algo(set) == D2G_CMP_PLANES ? "planes" : "direct");
-    }
+                                  t_set - t0, t_bufs - t_set, sh.cap);
+    const RowBatchRun run = emit_row_batches(sh, em, 1, slots.size(),
+                                             [&](int, const Batch &bt) { launch_batch(job, dev, bt); },
+                                             [&](int, const Batch &bt, int si) { return finish_batch(job, dev, bt, slots[si]); });
+    if (o.verbosity) std::fprintf(stderr, "[d2g] cmp: %zu sketches x S=%zu: upload+prepare+buffers %.3fs, %zu batches %.3fs wall (device+D2H+epilogue %.3fs busy, emit %.3fs busy, "
+                                          "overlapped) (algo %s)\n", ns, S, t_bufs - t0, run.nbatches, run.t_wall, run.t_dev_busy, run.t_emit_busy,
+                                  d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE ? "bitslice" : d2g_cmp_set_algo(set) == D2G_CMP_PLANES ? "planes" : "direct");
     if (g_stats.on) {
         const bool bs = d2g_cmp_set_algo(set) == D2G_CMP_BITSLICE, ab = job.trunc && job.need_gtlt;
         Json dj = Json::array();
-        g_stats.nest("cmp", Json::object().integer("sketches", ns).integer("sketchsize", S).integer("values", sh.total_vals).str("shape", sh.name(o))
+        g_stats.nest("cmp", Json::object().integer("sketches", ns).integer("sketchsize", S).integer("values", sh.total_vals).str("shape", sh.name())
                      .str("algo", bs ? "bitslice" : job.trunc ? "planes" : "direct").integer("regbytes", o.regbytes)
                      .raw("truncation", !job.trunc ? "null" : ab ? "\"setsketch\"" : "\"bbit\"").raw("a", ab ? ldstr(trunc_ab[0]) : "null").raw("b", ab ? ldstr(trunc_ab[1]) : "null")
                      .raw("bit_planes", bs ? planes_json(ctx, set) : "null").raw("sparse_tiles", bs ? sparse_json(ctx, set) : "null")
-                     .num("algorithmic_bytes", double(o.regbytes) * double(S) * double(ns) + 4.0 * double(sh.total_vals)).integer("batches", nbatches).integer("slot_values", job.cap)
+                     .num("algorithmic_bytes", double(o.regbytes) * double(S) * double(ns) + 4.0 * double(sh.total_vals)).integer("batches", run.nbatches).integer("slot_values", sh.cap)
                      .nest("devices", dj.push(k2_device_json(o.device, ctx)))
-                     .nest("wall_s", Json::object().num("densify_scan", t_densify).num("slots_header_upload_prepare", t_set - t0).num("batches", now() - t_loop)
-                           .num("device_d2h_epilogue_busy", t_dev).num("emit_busy", emit_busy)));
+                     .nest("wall_s", Json::object().num("densify_scan", t_densify).num("slots_header_upload_prepare", t_set - t0).num("batches", run.t_wall)
+                           .num("device_d2h_epilogue_busy", run.t_dev_busy).num("emit_busy", run.t_emit_busy)));
     }
     if (g_release_at_exit) d2g_cmp_set_destroy(set);
 }
@@ -414,7 +351,7 @@ std::string context_switches_json(d2g_ctx *ctx) {
 // per pair, both files opened and merged with one fread per element) -- the sets go to the device once (d2g_kset), row batches of
 // u64 intersection sizes come back (d2g_kset_isz_*_dev), d2g_epilogue_exact_* turns them into the measure in double, as CORRECT_RES does.
 void cmp_core_exact(const Options &o, Result &res, d2g_ctx *ctx, const ExactSets &es) {
-    const CmpShape sh(o, res);
+    const JobShape sh(o, res);
     const size_t ns = sh.ns;
     const double t0 = now();
     std::vector<uint64_t> off(ns + 1, 0);
@@ -431,35 +368,32 @@ void cmp_core_exact(const Options &o, Result &res, d2g_ctx *ctx, const ExactSets
     const double t_set = now();
     Emitter em(o, res);
     em.header();
-    const size_t cap = std::max<size_t>(1, std::min(std::max(cmp_slot_values(sh.total_vals), sh.widest), std::max<size_t>(sh.total_vals, 1)));
-    DevBuf d(ctx, cap * 8);
-    std::vector<uint64_t> isz(cap);
-    std::vector<float> out(cap);
+    DevBuf d(ctx, sh.cap * 8);
+    HostSlots slots(1, sh.cap * 4, sh.cap * 8);
     const int nt = int(o.workers());
-    size_t nbatches = 0;
-    for (size_t r0 = 0; r0 < sh.nrows; ++nbatches) {
-        const auto b = sh.batch(r0, cap);
-        const size_t r1 = b.first, cnt = b.second;
-        if (cnt) {
-            if (sh.symmetric) check(ctx, d2g_kset_isz_ut_dev(ctx, ks, r0, r1, (uint64_t *)d.p, nullptr), "d2g_kset_isz_ut_dev");
-            else check(ctx, d2g_kset_isz_rect_dev(ctx, ks, r0, r1, sh.c0, sh.c1, (uint64_t *)d.p, nullptr), "d2g_kset_isz_rect_dev");
-            check(ctx, d2g_memcpy_d2h(ctx, isz.data(), d.p, cnt * 8, nullptr), "d2h");
-            if (sh.symmetric) check(ctx, d2g_epilogue_exact_ut(isz.data(), res.cardinalities.data(), ns, r0, r1, o.measure, o.k, nt, out.data()), "d2g_epilogue_exact_ut");
-            else check(ctx, d2g_epilogue_exact_rect(isz.data(), res.cardinalities.data(), ns, r0, r1, sh.c0, sh.c1, o.measure, o.k, nt, out.data()), "d2g_epilogue_exact_rect");
-        }
-        if (sh.symmetric) em.rows(r0, r1, out.data(), [ns](size_t i) { return ns - 1 - i; });
-        else { const size_t ncol = sh.ncol; em.rows(r0, r1, out.data(), [ncol](size_t) { return ncol; }); }
-        r0 = r1;
-    }
+    const RowBatchRun run = emit_row_batches(sh, em, 1, slots.size(),
+        [&](int, const Batch &bt) {
+            if (sh.symmetric) check(ctx, d2g_kset_isz_ut_dev(ctx, ks, bt.r0, bt.r1, (uint64_t *)d.p, nullptr), "d2g_kset_isz_ut_dev");
+            else check(ctx, d2g_kset_isz_rect_dev(ctx, ks, bt.r0, bt.r1, sh.c0, sh.c1, (uint64_t *)d.p, nullptr), "d2g_kset_isz_rect_dev");
+        },
+        [&](int, const Batch &bt, int si) -> const float * {
+            uint64_t *isz = slots[si].raw.as<uint64_t>();
+            float *out = slots[si].out.as<float>();
+            if (!bt.cnt) return out;
+            check(ctx, d2g_memcpy_d2h(ctx, isz, d.p, bt.cnt * 8, nullptr), "d2h");
+            if (sh.symmetric) check(ctx, d2g_epilogue_exact_ut(isz, res.cardinalities.data(), ns, bt.r0, bt.r1, o.measure, o.k, nt, out), "d2g_epilogue_exact_ut");
+            else check(ctx, d2g_epilogue_exact_rect(isz, res.cardinalities.data(), ns, bt.r0, bt.r1, sh.c0, sh.c1, o.measure, o.k, nt, out), "d2g_epilogue_exact_rect");
+            return out;
+        });
     if (o.verbosity) std::fprintf(stderr, "[d2g] exact cmp: %zu sets, %llu keys (%zu bytes resident, 2^%d slices): upload + slice table %.3fs, %zu batches %.3fs\n", ns,
-                                  (unsigned long long)off[ns], d2g_kset_device_bytes(ks), d2g_kset_slice_bits(ks), t_set - t0, nbatches, now() - t_set);
+                                  (unsigned long long)off[ns], d2g_kset_device_bytes(ks), d2g_kset_slice_bits(ks), t_set - t0, run.nbatches, now() - t_set);
     if (g_stats.on) {
         Json dj = Json::array();
         Json e = device_json(o.device);
         e.raw("kset", kernel_json(ctx, "kset")).raw("ksetprep", kernel_json(ctx, "ksetprep"));
-        g_stats.nest("cmp", Json::object().integer("sets", ns).integer("keys", off[ns]).integer("values", sh.total_vals).str("shape", sh.name(o))
+        g_stats.nest("cmp", Json::object().integer("sets", ns).integer("keys", off[ns]).integer("values", sh.total_vals).str("shape", sh.name())
                      .str("algo", es.weighted ? "exact count dictionaries" : "exact k-mer sets").integer("resident_bytes", d2g_kset_device_bytes(ks))
-                     .integer("slice_bits", d2g_kset_slice_bits(ks)).integer("batches", nbatches).integer("slot_values", cap).nest("devices", dj.push(e))
+                     .integer("slice_bits", d2g_kset_slice_bits(ks)).integer("batches", run.nbatches).integer("slot_values", sh.cap).nest("devices", dj.push(e))
                      .nest("wall_s", Json::object().num("upload_slice_table", t_set - t0).num("batches", now() - t_set)));
     }
     if (g_release_at_exit) d2g_kset_destroy(ks);
@@ -471,7 +405,7 @@ void cmp_core_exact(const Options &o, Result &res, d2g_ctx *ctx, const ExactSets
 // as the reference's asymmetric route calls compare(i, j) for every cell: the diagonal comes out of the kernel as 0 and no batch has
 // to wait for rows of the triangle that lie in another one.
 void cmp_core_edit(const Options &o, Result &res, d2g_ctx *ctx, const d2g_seqrecs *sr, double t_read) {
-    const CmpShape sh(o, res);
+    const JobShape sh(o, res);
     const size_t ns = sh.ns;
     const uint64_t *off = d2g_seqrecs_off(sr);
     const double t0 = now();
@@ -480,38 +414,34 @@ void cmp_core_edit(const Options &o, Result &res, d2g_ctx *ctx, const d2g_seqrec
     const double t_set = now();
     Emitter em(o, res);
     em.header();
-    const size_t cap = std::max<size_t>(1, std::min(std::max(cmp_slot_values(sh.total_vals), sh.widest), std::max<size_t>(sh.total_vals, 1)));
-    DevBuf d(ctx, cap * 4);
-    std::vector<uint32_t> dist(cap);
-    std::vector<float> out(cap);
-    size_t nbatches = 0;
+    DevBuf d(ctx, sh.cap * 4);
+    HostSlots slots(1, sh.cap * 4, sh.cap * 4);
     long double cells = 0;
     std::vector<uint64_t> suffix(ns + 1, 0);                        // symbols of records [i, ns)
     for (size_t i = ns; i-- > 0;) suffix[i] = suffix[i + 1] + (off[i + 1] - off[i]);
-    for (size_t r0 = 0; r0 < sh.nrows; ++nbatches) {
-        const auto b = sh.batch(r0, cap);
-        const size_t r1 = b.first, cnt = b.second;
-        if (cnt) {
-            if (sh.symmetric) check(ctx, d2g_edit_ut_dev(ctx, ss, r0, r1, (uint32_t *)d.p, nullptr), "d2g_edit_ut_dev");
-            else check(ctx, d2g_edit_rect_dev(ctx, ss, r0, r1, sh.c0, sh.c1, (uint32_t *)d.p, nullptr), "d2g_edit_rect_dev");
-            check(ctx, d2g_memcpy_d2h(ctx, dist.data(), d.p, cnt * 4, nullptr), "d2h");
-            for (size_t e = 0; e < cnt; ++e) out[e] = float(dist[e]);
-        }
-        for (size_t i = r0; i < r1; ++i) cells += (long double)(off[i + 1] - off[i]) * (long double)(sh.symmetric ? suffix[i + 1] : suffix[sh.c0] - suffix[sh.c1]);
-        if (sh.symmetric) em.rows(r0, r1, out.data(), [ns](size_t i) { return ns - 1 - i; });
-        else { const size_t ncol = sh.ncol; em.rows(r0, r1, out.data(), [ncol](size_t) { return ncol; }); }
-        r0 = r1;
-    }
+    const RowBatchRun run = emit_row_batches(sh, em, 1, slots.size(),
+        [&](int, const Batch &bt) {
+            if (sh.symmetric) check(ctx, d2g_edit_ut_dev(ctx, ss, bt.r0, bt.r1, (uint32_t *)d.p, nullptr), "d2g_edit_ut_dev");
+            else check(ctx, d2g_edit_rect_dev(ctx, ss, bt.r0, bt.r1, sh.c0, sh.c1, (uint32_t *)d.p, nullptr), "d2g_edit_rect_dev");
+        },
+        [&](int, const Batch &bt, int si) -> const float * {
+            uint32_t *dist = slots[si].raw.as<uint32_t>();
+            float *out = slots[si].out.as<float>();
+            if (bt.cnt) check(ctx, d2g_memcpy_d2h(ctx, dist, d.p, bt.cnt * 4, nullptr), "d2h");
+            for (size_t e = 0; e < bt.cnt; ++e) out[e] = float(dist[e]);
+            for (size_t i = bt.r0; i < bt.r1; ++i) cells += (long double)(off[i + 1] - off[i]) * (long double)(sh.symmetric ? suffix[i + 1] : suffix[sh.c0] - suffix[sh.c1]);
+            return out;
+        });
     if (o.verbosity) std::fprintf(stderr, "[d2g] edit distances: %zu records, %llu symbols over %d letters (%zu bytes resident): read %.3fs, upload + recoding %.3fs, %zu batches %.3fs\n",
-                                  ns, (unsigned long long)off[ns], d2g_seqset_alphabet_size(ss), d2g_seqset_device_bytes(ss), t_read, t_set - t0, nbatches, now() - t_set);
+                                  ns, (unsigned long long)off[ns], d2g_seqset_alphabet_size(ss), d2g_seqset_device_bytes(ss), t_read, t_set - t0, run.nbatches, now() - t_set);
     if (g_stats.on) {
         Json dj = Json::array();
         Json e = device_json(o.device);
         e.raw("edit", kernel_json(ctx, "edit")).raw("editprep", kernel_json(ctx, "editprep"));
-        g_stats.nest("cmp", Json::object().integer("values", sh.total_vals).str("shape", sh.name(o)).str("algo", "exact edit distances (bit-parallel, K2h)")
+        g_stats.nest("cmp", Json::object().integer("values", sh.total_vals).str("shape", sh.name()).str("algo", "exact edit distances (bit-parallel, K2h)")
                      .nest("edit", Json::object().integer("records", ns).integer("symbols", off[ns]).integer("alphabet", d2g_seqset_alphabet_size(ss))
-                           .integer("cells", (unsigned long long)cells).integer("batches", nbatches).integer("resident_bytes", d2g_seqset_device_bytes(ss)))
-                     .integer("slot_values", cap).nest("devices", dj.push(e))
+                           .integer("cells", (unsigned long long)cells).integer("batches", run.nbatches).integer("resident_bytes", d2g_seqset_device_bytes(ss)))
+                     .integer("slot_values", sh.cap).nest("devices", dj.push(e))
                      .nest("wall_s", Json::object().num("read", t_read).num("upload_recode", t_set - t0).num("batches", now() - t_set)));
     }
     if (g_release_at_exit) d2g_seqset_destroy(ss);

@@ -3,7 +3,7 @@
 //   main / dispatch          src/d2.cpp:133-151                      this file
 //   cmp_main / load_results  src/cmp_main.cpp:24-198,200-366         this file
 //   sketch_main, sketch_core src/sketch_main.cpp:23-152 ...          sketch_cmd.cpp (host ingest: ingest_pipeline.h, bounded_queue.h)
-//   cmp_core, dense outputs  src/cmp_core.cpp:686-751, emitrect.cpp  cmp_dense.cpp (slot_queue.h)
+//   cmp_core, dense outputs  src/cmp_core.cpp:686-751, emitrect.cpp  cmp_dense.cpp (row_batches.h, slot_queue.h)
 //   neighbours, clustering   src/emitnn.cpp, src/dedup_core.cpp      cmp_sparse.cpp
 //   contain_main             src/contain_main.cpp:133-299            contain_cmd.cpp (contain_files.h)
 #include "cli_common.h"

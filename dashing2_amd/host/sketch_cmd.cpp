@@ -115,6 +115,18 @@ void write_stacked(const Result &res, const Options &o) {
     write_kmer_files(res, o);
 }
 
+// A packed run stream as the d2g_sketcher_run_* / d2g_kmer_filter_create_* calls take it: the symbols, the runs of valid ones, the runs
+// of each of the n genomes (goff[0 .. n]).  packed == NULL: the stream the sketcher ingested on the device (d2g_sketcher_ingest_fasta).
+struct RunStream {
+    const uint8_t *packed = nullptr; size_t packed_bytes = 0;
+    const uint64_t *run_start = nullptr; const uint32_t *run_len = nullptr; size_t nrun = 0;
+    const uint64_t *goff = nullptr; size_t n = 0; uint64_t nbases = 0;
+    static RunStream of(d2g_seqpack *sp) {
+        return {d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp), d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp),
+                d2g_seqpack_genome_run_off(sp), d2g_seqpack_ngenomes(sp), d2g_seqpack_nbases(sp)};
+    }
+};
+
 // --filterset (Dashing2Options::filterset, src/d2.cpp:45-98; asked per k-mer at src/fastxsketch.cpp:387): the filter file(s) are
 // parsed and 2-bit-packed ONCE per job, as one sketch input line is; every GPU context of the job builds its own table from that
 // stream (a table lives in one context's device memory) and attaches it to its sketcher before the first batch.
@@ -134,27 +146,44 @@ struct JobFilter {
                                           "(fastxmerge.cpp:70-120); existing caches are loaded as they are, filtered or not.\n");
     }
     ~JobFilter() { if (sp) d2g_seqpack_destroy(sp); }
-    // the table of one context, attached to its sketcher; the filter lives until the process ends (or D2G_FULL_TEARDOWN's caller frees it)
+    // the table of one context, attached to its sketcher (JobSketcher, which also releases it)
     d2g_kmer_filter *attach(d2g_ctx *ctx, d2g_sketcher *sk, const Options &o) {
         if (!sp) return nullptr;
         d2g_kmer_filter *f = nullptr;
-        if (o.alphabet)
-            check(ctx, d2g_kmer_filter_create_alphabet(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp),
-                                                       d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp), o.k, o.alphabet, &f), "d2g_kmer_filter_create");
-        else
-            check(ctx, d2g_kmer_filter_create_windowed(ctx, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp),
-                                                       d2g_seqpack_run_len(sp), d2g_seqpack_nruns(sp), o.k, o.canon, o.w, &f), "d2g_kmer_filter_create");
+        const RunStream s = RunStream::of(sp);
+        if (o.alphabet) check(ctx, d2g_kmer_filter_create_alphabet(ctx, s.packed, s.packed_bytes, s.run_start, s.run_len, s.nrun, o.k, o.alphabet, &f), "d2g_kmer_filter_create");
+        else check(ctx, d2g_kmer_filter_create_windowed(ctx, s.packed, s.packed_bytes, s.run_start, s.run_len, s.nrun, o.k, o.canon, o.w, &f), "d2g_kmer_filter_create");
         check(ctx, d2g_sketcher_set_filter(sk, f), "d2g_sketcher_set_filter");
         std::lock_guard<std::mutex> lk(mu);
         if (g_stats.on && !reported) {
             reported = true;
             uint64_t nocc = 0, ndist = 0; size_t bytes = 0;
             check(ctx, d2g_kmer_filter_info(ctx, f, &nocc, &ndist, &bytes), "d2g_kmer_filter_info");
-            int n = 0; float avg = 0, last = 0;
-            (void)d2g_kernel_ms(ctx, "filter", 1, &n, &avg, &last);
-            g_stats.nest("filter", Json::object().integer("kmers", nocc).integer("distinct", ndist).integer("table_bytes", bytes).num("build_ms", last));
+            g_stats.nest("filter", Json::object().integer("kmers", nocc).integer("distinct", ndist).integer("table_bytes", bytes).num("build_ms", kernel_acc(ctx, "filter").last_ms));
         }
         return f;
+    }
+};
+
+// The sketcher of one job on one context, set up as every sketching job wants it: the window (-w > k: minimizers, K1w), the alphabet
+// (--protein...: amino-acid k-mers, K1a) and the job's --filterset table, attached before the first batch.  Sketcher and table are
+// released only on request, like everything else the process holds when it leaves (g_release_at_exit).
+struct JobSketcher {
+    d2g_ctx *const ctx; const Options &o;
+    d2g_sketcher *sk = nullptr; d2g_kmer_filter *kf = nullptr;
+    JobSketcher(d2g_ctx *c, const Options &oo, JobFilter &filter) : ctx(c), o(oo) {
+        check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
+        check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");
+        check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");
+        kf = filter.attach(ctx, sk, o);
+    }
+    ~JobSketcher() { if (g_release_at_exit) { d2g_sketcher_destroy(sk); d2g_kmer_filter_destroy(kf); } }
+    JobSketcher(const JobSketcher &) = delete;
+    JobSketcher &operator=(const JobSketcher &) = delete;
+    operator d2g_sketcher *() const { return sk; }
+    // one of the d2g_sketcher_run_* entry points over a stream: they all begin (sketcher, stream, k, canon, seed mask: d2.h:224 -> enums.cpp:131-140)
+    template <class Fn, class... Tail> void run(Fn fn, const char *what, const RunStream &s, Tail... tail) const {
+        check(ctx, fn(sk, s.packed, s.packed_bytes, s.run_start, s.run_len, s.nrun, s.goff, s.n, o.k, o.canon, d2g_seed_mask(o.seedseed), tail...), what);
     }
 };
 
@@ -164,7 +193,6 @@ struct Fin { size_t g; std::vector<uint64_t> regs; std::vector<double> sigs, car
 constexpr int NSK = 7, NSK_ALWAYS = 3, NSK_CS = 4;
 // k1count: reported only by jobs that count (-N with -o); k3k, k3kcompact, k3kbmh: only by --multiset -c jobs (the count-sketch chain)
 constexpr const char *SKETCH_KERNELS[NSK] = {"k0", "k1", "k3", "k1count", "k3k", "k3kcompact", "k3kbmh"};
-struct KAcc { int launches = 0; double total_ms = 0; };
 
 // What the device threads of one sketch job share.  `const` members and what they point to are read-only while the threads run.
 struct DeviceSide {
@@ -186,16 +214,14 @@ struct DeviceSide {
     uint64_t cs_table_bytes = 0, cs_groups = 0, cs_batches = 0;   // -c: the largest count-sketch table of any thread, the table groups and batches of all
 
     // sketches one group: the raw bytes parsed on the device, or the stream the host parser packed -> Fin; true: parsed on the device
-    bool sketch_group(d2g_ctx *ctx, d2g_sketcher *sk, IngestGroup &r, Fin &f, uint64_t &nb) {
+    bool sketch_group(d2g_ctx *ctx, const JobSketcher &sk, IngestGroup &r, Fin &f, uint64_t &nb) {
         const size_t S = o.sketchsize, b = plan.groups[r.g].first, e = plan.groups[r.g].second, n = e - b;
-        const uint64_t xormask = d2g_seed_mask(o.seedseed);                 // d2.h:224 -> enums.cpp:131-140
         // the packed run stream of the group: parsed on the device (packed == NULL below), or by the host parser
-        const uint8_t *packed = nullptr; size_t packed_bytes = 0, nrun = 0;
-        const uint64_t *run_start = nullptr, *goff = nullptr; const uint32_t *run_len = nullptr;
+        RunStream s;
         bool on_device = false;
         if (r.buf >= 0) {
             const int rc = d2g_sketcher_ingest_fasta(sk, r.raw, r.raw_bytes, r.foff.data(), r.flen.data(), r.foff.size(), r.gfo.data(), n, o.k);
-            if (rc == D2G_OK) check(ctx, d2g_sketcher_ingested_runs(sk, &run_start, &run_len, &nrun, &goff, nullptr, &nb), "d2g_sketcher_ingested_runs");
+            if (rc == D2G_OK) check(ctx, d2g_sketcher_ingested_runs(sk, &s.run_start, &s.run_len, &s.nrun, &s.goff, nullptr, &s.nbases), "d2g_sketcher_ingested_runs");
             pipe.release_buffer(r);
             if (rc == D2G_ERR_UNSUPPORTED) {                            // e.g. a '+' line further down: the host parser takes the group
                 check(ctx, d2g_seqpack_create_alphabet(o.k, o.alphabet, &r.sp), "d2g_seqpack_create");
@@ -204,34 +230,23 @@ struct DeviceSide {
             } else check(ctx, rc, "d2g_sketcher_ingest_fasta");
             on_device = rc == D2G_OK;
         }
-        if (r.sp) {
-            packed = d2g_seqpack_packed(r.sp); packed_bytes = d2g_seqpack_packed_bytes(r.sp);
-            run_start = d2g_seqpack_run_start(r.sp); run_len = d2g_seqpack_run_len(r.sp); nrun = d2g_seqpack_nruns(r.sp);
-            goff = d2g_seqpack_genome_run_off(r.sp); nb = d2g_seqpack_nbases(r.sp);
-        }
+        if (r.sp) s = RunStream::of(r.sp);
+        s.n = n;
+        nb = s.nbases;
         if (o.sspace == SPACE_MULTISET) {
             // fastxsketch.cpp:425-445: Counter -> BagMinHash; cardinality = total weight, signature = data()[0..S)
             f.sigs.resize(n * S); f.cards.resize(n);
             if (o.cssize)                                               // -c: Counter(cssize), counter.h:74-75,131-137 (K3k)
-                check(ctx, d2g_sketcher_run_bmh_cs(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, o.cssize,
-                                                   double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh_cs");
-            else
-                check(ctx, d2g_sketcher_run_bmh(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S,
-                                                double(o.count_threshold), f.sigs.data(), f.cards.data()), "d2g_sketcher_run_bmh");
+                sk.run(d2g_sketcher_run_bmh_cs, "d2g_sketcher_run_bmh_cs", s, S, o.cssize, double(o.count_threshold), f.sigs.data(), f.cards.data());
+            else sk.run(d2g_sketcher_run_bmh, "d2g_sketcher_run_bmh", s, S, double(o.count_threshold), f.sigs.data(), f.cards.data());
         } else {
             f.regs.resize(n * d2g_oph_m(S));
-            if (o.count_threshold >= 2) {                               // fastxsketch.cpp:192: set_mincount(count_threshold_); with -N idcounts() too
-                if (count_kmers) f.counts.resize(n * d2g_oph_m(S));
-                check(ctx, d2g_sketcher_run_mincount(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S,
-                                                     o.count_threshold, f.regs.data(), count_kmers ? f.counts.data() : nullptr), "d2g_sketcher_run_mincount");
-            } else if (count_kmers) {                                          // fastxsketch.cpp:590-591: idcounts()
-                f.counts.resize(n * d2g_oph_m(S));
-                check(ctx, d2g_sketcher_run_counts(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data(),
-                                                   f.counts.data()), "d2g_sketcher_run_counts");
-            } else {
-                check(ctx, d2g_sketcher_run(sk, packed, packed_bytes, run_start, run_len, nrun, goff, n, o.k, o.canon, xormask, S, f.regs.data()),
-                      "d2g_sketcher_run");
-            }
+            if (count_kmers) f.counts.resize(n * d2g_oph_m(S));         // -N with -o: idcounts(), fastxsketch.cpp:590-591
+            uint32_t *const counts = count_kmers ? f.counts.data() : nullptr;
+            if (o.count_threshold >= 2)                                 // fastxsketch.cpp:192: set_mincount(count_threshold_); with -N idcounts() too
+                sk.run(d2g_sketcher_run_mincount, "d2g_sketcher_run_mincount", s, S, o.count_threshold, f.regs.data(), counts);
+            else if (count_kmers) sk.run(d2g_sketcher_run_counts, "d2g_sketcher_run_counts", s, S, f.regs.data(), counts);
+            else sk.run(d2g_sketcher_run, "d2g_sketcher_run", s, S, f.regs.data());
         }
         return on_device;
     }
@@ -243,36 +258,30 @@ struct DeviceSide {
             if (rc != D2G_OK) die(std::string("d2g_ctx_create (device thread, GPU ") + std::to_string(devs[di]) + "): " + d2g_strerror(rc));
             if (g_stats.on) (void)d2g_set_timing(ctx, TIME_ALL);
         }
-        d2g_sketcher *sk = nullptr;
-        check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
-        check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
-        check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");  // --protein...: amino-acid k-mers (K1a)
-        d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);              // before the first group
         double gpu = 0; uint64_t bases = 0; size_t ndevg = 0, nhostg = 0;
-        for (IngestGroup r; pipe.next(r);) {
-            if (r.failed()) continue;                                       // error recorded by the pipeline; drain the queue
-            const double t1 = now();
-            Fin f{r.g, {}, {}, {}, {}};
-            uint64_t nb = 0;
-            ++(sketch_group(ctx, sk, r, f, nb) ? ndevg : nhostg);
-            gpu += now() - t1; bases += nb;
-            finq.push(std::move(f));
-            pipe.release(r);
-        }
         std::array<KAcc, NSK> mine;
-        if (g_stats.on)
-            for (int x = 0; x < NSK; ++x) {
-                int n = 0; float avg = 0, last = 0;
-                if (d2g_kernel_ms(ctx, SKETCH_KERNELS[x], 1, &n, &avg, &last) == D2G_OK) { mine[x].launches = n; mine[x].total_ms = double(avg) * n; }
-            }
         uint64_t cs_b = 0, cs_g = 0, cs_n = 0;
-        if (g_stats.on && o.cssize) (void)d2g_countsketch_stats(ctx, &cs_b, &cs_g, &cs_n);
-        if (g_release_at_exit) { d2g_sketcher_destroy(sk); d2g_kmer_filter_destroy(kf); if (ctx != first_ctx) d2g_ctx_destroy(ctx); }
+        {
+            JobSketcher sk(ctx, o, filter);                                 // the filter table is attached before the first group
+            for (IngestGroup r; pipe.next(r);) {
+                if (r.failed()) continue;                                   // error recorded by the pipeline; drain the queue
+                const double t1 = now();
+                Fin f{r.g, {}, {}, {}, {}};
+                uint64_t nb = 0;
+                ++(sketch_group(ctx, sk, r, f, nb) ? ndevg : nhostg);
+                gpu += now() - t1; bases += nb;
+                finq.push(std::move(f));
+                pipe.release(r);
+            }
+            if (g_stats.on) for (int x = 0; x < NSK; ++x) mine[x] = kernel_acc(ctx, SKETCH_KERNELS[x]);
+            if (g_stats.on && o.cssize) (void)d2g_countsketch_stats(ctx, &cs_b, &cs_g, &cs_n);
+        }                                                                   // the sketcher goes before its context
+        if (g_release_at_exit && ctx != first_ctx) d2g_ctx_destroy(ctx);
         std::lock_guard<std::mutex> lk(mu);
         cs_table_bytes = std::max(cs_table_bytes, cs_b); cs_groups += cs_g; cs_batches += cs_n;
         t_gpu += gpu; total_bases += bases; n_dev_groups += ndevg; n_host_groups += nhostg;
         groups_of[di] += ndevg + nhostg;
-        for (int x = 0; x < NSK; ++x) { kacc[di][x].launches += mine[x].launches; kacc[di][x].total_ms += mine[x].total_ms; }
+        for (int x = 0; x < NSK; ++x) kacc[di][x] += mine[x];
     }
 };
 
@@ -320,9 +329,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
         todo.push_back(i);
         lines.push_back(o.paths[i]);
     }
-    size_t limit = size_t(48) << 20;
-    if (const char *e = std::getenv("D2G_GROUP_BYTES")) { const long long v = std::atoll(e); if (v >= 1) limit = size_t(v); }   // tests: many small groups
-    const GroupPlan plan = plan_groups(lines, limit);
+    const GroupPlan plan = plan_groups(lines, group_bytes_limit(size_t(48) << 20));
     const auto &groups = plan.groups;
     const double t_setup = now();
     const std::vector<int> devs = job_devices(o);
@@ -402,7 +409,7 @@ void sketch_core(Result &res, const Options &o, LazyCtx &lctx) {
             e.integer("groups", ds.groups_of[d]);
             for (int x = 0; x < NSK; ++x) {
                 if (x == NSK_ALWAYS ? !want_counts : x >= NSK_CS ? !countsketch : false) continue;
-                e.nest(SKETCH_KERNELS[x], Json::object().integer("launches", ds.kacc[d][x].launches).num("total_ms", ds.kacc[d][x].total_ms));
+                e.nest(SKETCH_KERNELS[x], ds.kacc[d][x].json());
             }
             dj.push(e);
         }
@@ -429,7 +436,6 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     if (o.paths.size() != 1)
         die("parse-by-seq currently only handles one file at a time. To process multiple files, simply concatenate them into one file, and run dashing2 on that.");
     const size_t S = o.sketchsize, m = d2g_oph_m(S);
-    const uint64_t xormask = d2g_seed_mask(o.seedseed);
     d2g_seqpack *sp = nullptr;
     check(nullptr, d2g_seqpack_create_alphabet(o.k, o.alphabet, &sp), "d2g_seqpack_create");
     const uint64_t per_byte = o.alphabet ? 1 : 4;                                  // symbols per stream byte: a byte per residue, four bases
@@ -441,45 +447,37 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
     res.destination_files.assign(N, std::string());
     res.cardinalities.assign(N, 0.);
     res.signatures.assign(N * S, 0.);
-    const size_t total_bytes = d2g_seqpack_packed_bytes(sp);
-    const uint8_t *packed = d2g_seqpack_packed(sp);
-    const uint64_t *run_start = d2g_seqpack_run_start(sp), *goff = d2g_seqpack_genome_run_off(sp);
-    const uint32_t *run_len = d2g_seqpack_run_len(sp);
-    d2g_sketcher *sk = nullptr;
-    check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
-    check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
-    check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");  // --protein...: amino-acid k-mers (K1a)
+    const RunStream all = RunStream::of(sp);
     JobFilter filter(o);
-    d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);                         // fastxsketchbyseq.cpp:327,370,383,420-423
+    JobSketcher sk(ctx, o, filter);                                                // fastxsketchbyseq.cpp:327,370,383,420-423
     std::vector<uint64_t> regs, rs_rel, goff_rel, ndist;
     std::vector<double> sigs, cards;
     const size_t max_rec = std::max<size_t>(1, (size_t(64) << 20) / m);            // <= 512 MiB of registers per launch
     for (size_t g0 = 0; g0 < N;) {
         // batch [g0, g1): bounded by records and by packed bytes (the slice is re-based so that only it is uploaded)
         size_t g1 = g0;
-        const uint64_t r0 = goff[g0];
-        const uint64_t base0 = r0 < goff[N] ? (run_start[r0] & ~uint64_t(15)) : 0;
+        const uint64_t r0 = all.goff[g0];
+        const uint64_t base0 = r0 < all.goff[N] ? (all.run_start[r0] & ~uint64_t(15)) : 0;
         while (g1 < N && g1 - g0 < max_rec) {
-            const uint64_t r1 = goff[g1 + 1];
-            const uint64_t endb = r1 > r0 ? run_start[r1 - 1] + run_len[r1 - 1] : base0;
+            const uint64_t r1 = all.goff[g1 + 1];
+            const uint64_t endb = r1 > r0 ? all.run_start[r1 - 1] + all.run_len[r1 - 1] : base0;
             if (g1 > g0 && endb - base0 > (uint64_t(192) << 20)) break;            // ~48 MB of packed bases
             ++g1;
         }
-        const size_t n = g1 - g0, r1 = goff[g1], nrun = r1 - r0;
+        const size_t n = g1 - g0, r1 = all.goff[g1], nrun = r1 - r0;
         rs_rel.resize(nrun); goff_rel.resize(n + 1);
-        for (size_t r = 0; r < nrun; ++r) rs_rel[r] = run_start[r0 + r] - base0;
-        for (size_t g = 0; g <= n; ++g) goff_rel[g] = goff[g0 + g] - r0;
-        const uint8_t *pk = packed + base0 / per_byte;                             // base0 is a multiple of 16 symbols: 4-byte aligned either way
-        const uint64_t endb = nrun ? run_start[r1 - 1] + run_len[r1 - 1] : base0;
-        const size_t pk_bytes = std::min<size_t>(total_bytes - base0 / per_byte, (endb - base0 + per_byte - 1) / per_byte + 64);   // slice + its 64 readable pad bytes
+        for (size_t r = 0; r < nrun; ++r) rs_rel[r] = all.run_start[r0 + r] - base0;
+        for (size_t g = 0; g <= n; ++g) goff_rel[g] = all.goff[g0 + g] - r0;
+        const uint64_t endb = nrun ? all.run_start[r1 - 1] + all.run_len[r1 - 1] : base0;
+        // the slice + its 64 readable pad bytes; base0 is a multiple of 16 symbols: 4-byte aligned either way
+        const RunStream b{all.packed + base0 / per_byte, std::min<size_t>(all.packed_bytes - base0 / per_byte, (endb - base0 + per_byte - 1) / per_byte + 64),
+                          rs_rel.data(), all.run_len + r0, nrun, goff_rel.data(), n, 0};
         sigs.resize(n * S); cards.resize(n);
         if (o.sspace == SPACE_MULTISET) {
-            check(ctx, d2g_sketcher_run_bmh(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k, o.canon,
-                                            xormask, S, double(o.count_threshold), sigs.data(), cards.data()), "d2g_sketcher_run_bmh");
+            sk.run(d2g_sketcher_run_bmh, "d2g_sketcher_run_bmh", b, S, double(o.count_threshold), sigs.data(), cards.data());
         } else {
             regs.resize(n * m);
-            check(ctx, d2g_sketcher_run(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k, o.canon,
-                                        xormask, S, regs.data()), "d2g_sketcher_run");
+            sk.run(d2g_sketcher_run, "d2g_sketcher_run", b, S, regs.data());
             check(ctx, d2g_oph_finalize(regs.data(), n, m, S, sigs.data(), cards.data(), int(o.workers())), "d2g_oph_finalize");
             bool need = false;
             for (size_t i = 0; i < n; ++i) {
@@ -488,8 +486,7 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
             }
             if (need) {                                                               // lines 415-430: exact distinct count
                 ndist.resize(n);
-                check(ctx, d2g_sketcher_run_distinct(sk, pk, pk_bytes, rs_rel.data(), run_len + r0, nrun, goff_rel.data(), n, o.k,
-                                                     o.canon, xormask, ndist.data()), "d2g_sketcher_run_distinct");
+                sk.run(d2g_sketcher_run_distinct, "d2g_sketcher_run_distinct", b, ndist.data());
                 for (size_t i = 0; i < n; ++i) if (cards[i] < 10. * double(S)) cards[i] = double(ndist[i]);
             }
         }
@@ -497,8 +494,6 @@ void sketch_core_byseq(Result &res, const Options &o, LazyCtx &lctx) {
         std::memcpy(&res.cardinalities[g0], cards.data(), n * sizeof(double));
         g0 = g1;
     }
-    d2g_sketcher_destroy(sk);
-    d2g_kmer_filter_destroy(kf);
     d2g_seqpack_destroy(sp);
     write_stacked(res, o);
 }
@@ -570,19 +565,12 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
     res.names.clear();
     for (size_t i = 0; i < N; ++i) res.names.push_back(o.presketched ? "E" + std::to_string(i) : o.paths[i]);
     size_t nbatches = 0; uint64_t nkeys = 0;
-    KAcc k3, k3s;
     const double t0 = now();
     if (!todo.empty()) {
         JobFilter filter(o);
         d2g_ctx *ctx = lctx.get();
-        d2g_sketcher *sk = nullptr;
-        check(ctx, d2g_sketcher_create(ctx, &sk), "d2g_sketcher_create");
-        check(ctx, d2g_sketcher_set_window(sk, o.w), "d2g_sketcher_set_window");          // -w > k: minimizers (K1w)
-        check(ctx, d2g_sketcher_set_alphabet(sk, o.alphabet), "d2g_sketcher_set_alphabet");  // --protein...: amino-acid k-mers (K1a)
-        d2g_kmer_filter *const kf = filter.attach(ctx, sk, o);
-        const uint64_t xormask = d2g_seed_mask(o.seedseed);
-        size_t limit = size_t(32) << 20;
-        if (const char *e = std::getenv("D2G_GROUP_BYTES")) { const long long v = std::atoll(e); if (v >= 1) limit = size_t(v); }   // tests: many small batches
+        JobSketcher sk(ctx, o, filter);
+        const size_t limit = group_bytes_limit(size_t(32) << 20);
         d2g_seqpack *sp = nullptr;
         check(ctx, d2g_seqpack_create_alphabet(o.k, o.alphabet, &sp), "d2g_seqpack_create");
         std::vector<uint64_t> keys, off, cards;
@@ -599,9 +587,8 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
             for (size_t g = 0; g < n; ++g) cap += d2g_seqpack_nkmers(sp, g);
             keys.resize(std::max<uint64_t>(cap, 1)); off.resize(n + 1); cards.resize(2 * n);
             if (weighted) counts.resize(std::max<uint64_t>(cap, 1));
-            check(ctx, d2g_sketcher_run_sets(sk, d2g_seqpack_packed(sp), d2g_seqpack_packed_bytes(sp), d2g_seqpack_run_start(sp), d2g_seqpack_run_len(sp),
-                                             d2g_seqpack_nruns(sp), d2g_seqpack_genome_run_off(sp), n, o.k, o.canon, xormask, double(o.count_threshold),
-                                             keys.data(), weighted ? counts.data() : nullptr, cap, off.data(), cards.data()), "d2g_sketcher_run_sets");
+            sk.run(d2g_sketcher_run_sets, "d2g_sketcher_run_sets", RunStream::of(sp), double(o.count_threshold), keys.data(), weighted ? counts.data() : nullptr,
+                   cap, off.data(), cards.data());
             for (size_t g = 0; g < n; ++g) {
                 const size_t i = todo[t0i + g], ne = size_t(off[g + 1] - off[g]);
                 es.keys[i].assign(keys.begin() + off[g], keys.begin() + off[g + 1]);
@@ -614,21 +601,14 @@ void exact_sets_job(Result &res, const Options &o, LazyCtx &lctx, ExactSets &es)
             ++nbatches;
             t0i = t1;
         }
-        if (g_stats.on) {
-            int n = 0; float avg = 0, last = 0;
-            if (d2g_kernel_ms(ctx, "k3", 1, &n, &avg, &last) == D2G_OK) { k3.launches = n; k3.total_ms = double(avg) * n; }
-            if (d2g_kernel_ms(ctx, "k3s", 1, &n, &avg, &last) == D2G_OK) { k3s.launches = n; k3s.total_ms = double(avg) * n; }
-        }
         d2g_seqpack_destroy(sp);
-        if (g_release_at_exit) { d2g_sketcher_destroy(sk); d2g_kmer_filter_destroy(kf); }
     }
     if (o.verbosity) std::fprintf(stderr, "[d2g] exact k-mer sets: %zu inputs, %zu loaded, %zu computed in %zu batches (%" PRIu64 " keys) in %.3fs\n", N, N - todo.size(), todo.size(),
                                   nbatches, nkeys, now() - t0);
     if (g_stats.on)
         g_stats.nest("sketch", Json::object().integer("inputs", N).integer("sketched", todo.size()).integer("from_cache", N - todo.size()).integer("k", o.k)
                      .str("space", weighted ? "exact count dictionaries (K3 counts + K3s sort)" : "exact k-mer sets (K3 counts + K3s sort)").integer("batches", nbatches)
-                     .integer("keys", nkeys).nest("k3", Json::object().integer("launches", k3.launches).num("total_ms", k3.total_ms))
-                     .nest("k3s", Json::object().integer("launches", k3s.launches).num("total_ms", k3s.total_ms)).num("wall_s", now() - t0));
+                     .integer("keys", nkeys).nest("k3", kernel_acc(lctx.get(), "k3").json()).nest("k3s", kernel_acc(lctx.get(), "k3s").json()).num("wall_s", now() - t0));
 }
 
 // --bed (sketch_core.cpp:48-62 -> bed2sketch, src/bedsketch.cpp:5-103): one sketch per interval file.  The files are a few MB of text
@@ -679,7 +659,6 @@ void sketch_core_bed(Result &res, const Options &o, LazyCtx &lctx) {
     }
     const double t_parse = now();
     uint64_t npositions = 0, nruns = 0;
-    KAcc k1i, k1iexpand, k1ibmh;
     if (!todo.empty()) {
         d2g_ctx *ctx = lctx.get();
         const size_t n = todo.size();
@@ -706,21 +685,13 @@ void sketch_core_bed(Result &res, const Options &o, LazyCtx &lctx) {
             res.cardinalities[i] = cards[t];
             write_cached(res.destination_files[i], &sigs[t * S], cards[t], S);
         }
-        if (g_stats.on) {
-            int c = 0; float avg = 0, last = 0;
-            if (d2g_kernel_ms(ctx, "k1i", 1, &c, &avg, &last) == D2G_OK) { k1i.launches = c; k1i.total_ms = double(avg) * c; }
-            if (d2g_kernel_ms(ctx, "k1iexpand", 1, &c, &avg, &last) == D2G_OK) { k1iexpand.launches = c; k1iexpand.total_ms = double(avg) * c; }
-            if (d2g_kernel_ms(ctx, "k1ibmh", 1, &c, &avg, &last) == D2G_OK) { k1ibmh.launches = c; k1ibmh.total_ms = double(avg) * c; }
-        }
         if (g_release_at_exit) d2g_interval_plan_destroy(plan);
     }
     if (o.verbosity) std::fprintf(stderr, "[d2g] sketched %zu interval files (%" PRIu64 " lines, %" PRIu64 " positions; %zu from cache): read + parse %.3fs, device %.3fs\n",
                                   todo.size(), nlines, npositions, N - todo.size(), t_parse - t_enter, now() - t_parse);
     if (g_stats.on) {
         Json dev = device_json(o.device);
-        dev.nest("k1i", Json::object().integer("launches", k1i.launches).num("total_ms", k1i.total_ms));
-        dev.nest("k1iexpand", Json::object().integer("launches", k1iexpand.launches).num("total_ms", k1iexpand.total_ms));
-        dev.nest("k1ibmh", Json::object().integer("launches", k1ibmh.launches).num("total_ms", k1ibmh.total_ms));
+        for (const char *kernel : {"k1i", "k1iexpand", "k1ibmh"}) dev.nest(kernel, kernel_acc(lctx.get(), kernel).json());
         g_stats.nest("sketch", Json::object().integer("inputs", N).integer("sketched", todo.size()).integer("from_cache", N - todo.size()).integer("sketchsize", S)
                      .str("space", multiset ? "multiset (K1i: interval runs + BagMinHash)" : "set (K1i: OPH over positions)")
                      .nest("intervals", Json::object().integer("lines", nlines).integer("positions", npositions).integer("runs", nruns))
