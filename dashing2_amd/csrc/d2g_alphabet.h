@@ -1,6 +1,6 @@
 // d2g_alphabet.h -- the amino-acid alphabets of --protein / --protein14 / --protein8 / --protein6 (spec "D2G-AA", DESIGN section 3
 // K1a) on the host alone: the residue groups, their sizes and the largest k whose key fits 64 bits.  The reference keeps these in
-// the absent bonsai; ids and names are those of its python/parse.py:8-23.  Header-only, so that the packer (d2g_host.cpp) and the
+// the absent bonsai; ids and names are those of its python/parse.py:8-23.  Header-only, so that the packer (d2g_seqpack.cpp) and the
 // plan (d2g_plan.cpp) each build without the other, as the sanitizer programs do.
 #pragma once
 #include "../../include/d2g.h"

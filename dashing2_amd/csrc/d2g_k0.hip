@@ -1,7 +1,7 @@
 // d2g_k0.hip -- K0: FASTA bytes -> packed run stream ON THE GPU.
 //
 // Replaces, for plain FASTA inputs, the host half of the ingest: kseq's record walk + bns::Encoder's window resets
-// (reference call sites src/fastxsketch.cpp:383-424, src/d2.h:273-305) as restated by d2g_seqpack (d2g_host.cpp).  The
+// (reference call sites src/fastxsketch.cpp:383-424, src/d2.h:273-305) as restated by d2g_seqpack (d2g_seqpack.cpp).  The
 // host only read()s the files into page-locked memory; the raw bytes cross PCIe once (1 byte per base instead of the
 // host packer's 2 CPU-seconds per 5 GB) and three streaming passes turn them into exactly what K1/K3 consume:
 //   packed stream   every ACGT/acgt byte of a sequence line, 2 bits each, in file order, line feeds squeezed out

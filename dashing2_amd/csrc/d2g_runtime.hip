@@ -6,7 +6,7 @@
 #include <new>
 
 // the library's run-time switches (DESIGN.md section 4 lists what each one does).  Host-side switches that need no context
-// (D2G_MAX_RUN and D2G_NO_AVX512 in d2g_host.cpp, D2G_RCCL_LIB, D2G_COMM_LOOPBACK) are read where they apply.
+// (D2G_MAX_RUN and D2G_NO_AVX512 in d2g_seqpack.cpp, D2G_RCCL_LIB, D2G_COMM_LOOPBACK) are read where they apply.
 static const char *const kTuningNames[] = {
     "D2G_BS_SORT", "D2G_BS_NSPLIT", "D2G_BS_TAGBITS", "D2G_BS_ID16", "D2G_K2_MERGE",
     "D2G_BS_SPARSE", "D2G_BS_SPARSE_MIN_N", "D2G_SP_LINK", "D2G_SP_TILE_FRAC", "D2G_SP_LIST_DIV", "D2G_SP_LONG_LIST", "D2G_SP_LIST_FORM", "D2G_SP_PREDICT", "D2G_SP_REMEMBER", "D2G_SP_EMIT_BIG", "D2G_SP_OLINK", "D2G_SP_RIDE", "D2G_SP_RANK_SHARE",

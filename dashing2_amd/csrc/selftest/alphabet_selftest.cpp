@@ -1,7 +1,7 @@
 // alphabet_selftest.cpp -- the host side of the amino-acid walker (K1a) under AddressSanitizer + UndefinedBehaviorSanitizer
 // (`make sanitize` in dashing2_amd/csrc).  No GPU, no HIP.  Exit code 0 = no finding.
 //   1. the alphabet tables (d2g_alphabet.h): sizes, largest k, every byte's code, names, d2g_key_bits (DNA: 2k bit for bit)
-//   2. the byte-per-residue packer (d2g_host.cpp) against a direct restatement: streams, runs, per-genome k-mer totals -- lower case,
+//   2. the byte-per-residue packer (d2g_seqpack.cpp) against a direct restatement: streams, runs, per-genome k-mer totals -- lower case,
 //      every invalid letter, records shorter than k, by-record mode, the 64-byte pad, the run split with its k - 1 overlap, clear()
 //   3. d2g_plan_check_tail counting a byte per symbol, and what d2g_plan_build refuses under a protein alphabet
 #include "../../../include/d2g.h"

@@ -1,4 +1,4 @@
-// edit_selftest.cpp -- the host side of edit distances (K2h; d2g_host.cpp) under ASan + UBSan, no GPU:
+// edit_selftest.cpp -- the host side of edit distances (K2h; the reader in d2g_seqpack.cpp, the checks in d2g_host.cpp) under ASan + UBSan, no GPU:
 //   1. d2g_seqrecs against the seqpack reader (d2g_seqpack_add_fastx_by_record): the same number of records and the same names on FASTA,
 //      FASTQ, CRLF line ends, a last record without a line feed, an empty record, a FASTQ record that the walk drops; the bytes kept are
 //      the sequence lines as they stand (case, N, anything), qualities ignored; the path form on a file

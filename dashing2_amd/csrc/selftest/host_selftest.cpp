@@ -1,5 +1,5 @@
-// host_selftest.cpp -- exercises the x86 host half of libd2g (d2g_host.cpp: seqpack ingest, x87 finalisation,
-// densify, epilogues, partition) under AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize` in
+// host_selftest.cpp -- exercises the x86 host half of libd2g (d2g_seqpack.cpp: seqpack ingest; d2g_host.cpp: x87 finalisation,
+// densify, partition; d2g_epilogue.cpp: epilogues) under AddressSanitizer + UndefinedBehaviorSanitizer (`make sanitize` in
 // dashing2_amd/csrc; the reference has the same kind of target: Makefile:102-103).  No GPU, no HIP: only the
 // functions that never touch a device.  Exit code 0 = no finding (the sanitizers abort on any).
 // Also the sketch side's input checks and launch plan (d2g_plan.cpp): the grid arithmetic whose indices the kernels trust.

@@ -4,7 +4,7 @@ codes, a and b of make_compressed() for three small matrices, and values of both
 
     python tests/golden/make_trunc_golden.py          (run in the build container; the .npz is committed)
 
-The product (dashing2_amd/csrc/d2g_host.cpp) must reproduce every value bit for bit (tests/test_trunc_host.py).  long double
+The product (dashing2_amd/csrc/d2g_epilogue.cpp) must reproduce every value bit for bit (tests/test_trunc_host.py).  long double
 logl/expl/powl come from the machine's libm: the file pins what the build container's libm gives."""
 import os
 import sys

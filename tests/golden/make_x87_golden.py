@@ -5,7 +5,7 @@ nothing else in this repository -- and the fixture it freezes: tests/golden/x87_
 
     python tests/golden/make_x87_golden.py          (run in the build container; the .npz is committed)
 
-Both the product's host half (dashing2_amd/csrc/d2g_host.cpp) and the oracle (oracle/d2_oracle.c) must
+Both the product's host half (dashing2_amd/csrc/d2g_host.cpp, d2g_epilogue.cpp) and the oracle (oracle/d2_oracle.c) must
 reproduce every value bit for bit (tests/test_x87_fixtures.py).  Rows covered:
   R5  LazyOnePermSetSketch::getcard()   /root/reference/src/oph.h:240-247   (omul: oph.h:213-218)
   R6  LazyOnePermSetSketch::data()      /root/reference/src/oph.h:248-257

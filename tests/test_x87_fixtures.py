@@ -1,6 +1,6 @@
 """The x87 `long double` host rows (R5 getcard, R6 data(), R9 both compare() branches) checked against a THIRD,
 independent restatement: tests/golden/x87_kat.npz, frozen from NumPy np.longdouble arithmetic by
-tests/golden/make_x87_golden.py.  The product's host half (libd2g.so, d2g_host.cpp) and the oracle
+tests/golden/make_x87_golden.py.  The product's host half (libd2g.so: d2g_host.cpp, d2g_epilogue.cpp) and the oracle
 (oracle/d2_oracle.c) are two C restatements by the same hand; a shared misreading of the reference would pass
 a twin-vs-twin test, so both must reproduce these values bit for bit."""
 import os
