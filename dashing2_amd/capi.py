@@ -25,7 +25,9 @@ TIME_FILTER = 256
 TIME_KSET = 512
 TIME_SCREEN = 1024
 TIME_EDIT = 2048
+TIME_EDIT_NEAR = 4096
 EDIT_MAX_LEN = 65535                                                     # include/d2g.h D2G_EDIT_MAX_LEN
+EDIT_BAND_MAX = 31                                                       # include/d2g.h D2G_EDIT_BAND_MAX
 
 
 class D2GError(RuntimeError):
@@ -189,6 +191,10 @@ SIGNATURES = {
     "d2g_edit_rect_dev": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp]),
     "d2g_edit_ut": (_int, [_vp, _vp, _sz, _sz, _vp]),
     "d2g_edit_rect": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _vp]),
+    "d2g_edit_band_max": (_int, []),
+    "d2g_edit_near_dev": (_int, [_vp, _vp, _sz, _sz, C.c_uint32, _vp, _vp]),
+    "d2g_edit_within_dev": (_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "d2g_edit_knn": (_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "d2g_epilogue_exact": (_f32, [_u64, _dbl, _dbl, _int, _int]),
     "d2g_epilogue_exact_ut": (_int, [_vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp]),
     "d2g_epilogue_exact_rect": (_int, [_vp, _vp, _sz, _sz, _sz, _sz, _sz, _int, _int, _int, _vp]),
@@ -1599,6 +1605,24 @@ class SeqSet:
         out = np.zeros((a1 - a0, b1 - b0), np.uint32)
         self.ctx._check(lib().d2g_edit_rect(self.ctx._h, self._h, a0, a1, b0, b1, _np_ptr(out)))
         return out
+
+    def near_dev(self, T, close_dev_ptr, r0=0, r1=None, stream=None):
+        """d2g_edit_near_dev: closeness T + 1 - min(d, T + 1) of rows [r0, r1) x all N columns, u32 row-major in device memory"""
+        r1 = self.N if r1 is None else r1
+        self.ctx._check(lib().d2g_edit_near_dev(self.ctx._h, self._h, r0, r1, T, close_dev_ptr, stream))
+
+    def within_dev(self, rowcnt_dev_ptr, ids_dev_ptr, close_dev_ptr, cap, K=0, T=0, r0=0, r1=None, band_rows=0, stream=None):
+        """d2g_edit_within_dev: per-row selection on the device over closeness (K == 0: every j with d <= T)"""
+        r1 = self.N if r1 is None else r1
+        self.ctx._check(lib().d2g_edit_within_dev(self.ctx._h, self._h, r0, r1, K, T, cap, rowcnt_dev_ptr, ids_dev_ptr, close_dev_ptr,
+                                                  band_rows, stream))
+
+    def knn(self, K=0, T=0, r0=0, r1=None, cap=0, band_rows=0):
+        """d2g_edit_knn: CSR (indptr, indices, data) of rows [r0, r1), data = the distances as float32.  K == 0: every record within T
+        edits; K >= 1: the K nearest of all records with every tie of the K-th (T is only the bound the search starts from)"""
+        r1 = self.N if r1 is None else r1
+        return _knn_csr(self.ctx, r1 - r0, K, lambda ip, ix, dt, oc, need: lib().d2g_edit_knn(
+            self.ctx._h, self._h, r0, r1, K, T, cap, band_rows, ip, ix, dt, oc, need))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -24,8 +24,9 @@
 //     wave run to nearly the same column count; outputs are written by index, so the order is invisible.
 // Rows are launched in three classes by their block count (up to 8 blocks; one strip; several strips) so that a short query never
 // carries the LDS of a long one; a workgroup whose row is of another class leaves at once.
-// Not built: banding, an early exit at a threshold, the alignment path, a register-resident Peq for small alphabets.
-#include "d2g_internal.h"
+// Not built: the alignment path, a register-resident Peq for small alphabets.  Banding and the early exit at a threshold are not this
+// kernel's either (a block outside a band would be an idle lane here, not a saved step): they are d2g_edit_near.hip's (K2i).
+#include "d2g_edit.h"
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -35,9 +36,7 @@
 
 namespace {
 
-constexpr int EDIT_PAD = 16;               // a record's codes begin at a multiple of this and may be read to the next one
-constexpr int EDIT_SMALL_BLOCKS = 8;       // rows of up to this many blocks form the first launch class
-constexpr uint32_t EDIT_LDS_WORDS = 16384; // 64 KiB: one strip's table and, for queries of several strips, the two planes
+constexpr int EDIT_SMALL_BLOCKS = 8;       // rows of up to this many blocks form the first launch class (EDIT_PAD, EDIT_LDS_WORDS: d2g_edit.h)
 
 struct EditArgs {
     const uint8_t *codes;              // recoded symbols, record i at codes + doff[i]
@@ -200,18 +199,6 @@ __global__ __launch_bounds__(256) void edit_recode_kernel(const uint8_t *raw, co
 
 }  // namespace
 
-struct d2g_seqset {
-    d2g_ctx *ctx = nullptr;
-    size_t N = 0;
-    uint64_t nsym = 0, padded = 0;
-    uint32_t sigma = 1, maxlen = 0;
-    std::vector<uint32_t> len;         // host copy: which launch classes a row range has
-    d2g_dev<uint8_t> codes;
-    d2g_dev<uint64_t> doff;
-    d2g_dev<uint32_t> dlen, order;
-    size_t bytes = 0;
-};
-
 void d2g_warm_edit() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&edit_pair_kernel));
@@ -229,7 +216,8 @@ uint32_t edit_strip_blocks(const d2g_ctx *ctx, const d2g_seqset *ss, uint32_t *p
     return std::max<uint32_t>(strip, 1);
 }
 
-int edit_launch(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, int ut, uint32_t *out, hipStream_t s) {
+// columns: those of [b0, b1) (ut: every j > i) among the records at positions [p0, p1) of the order by length
+int edit_launch(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1, int ut, uint32_t *out, hipStream_t s, uint32_t p0, uint32_t p1) {
     uint32_t pw = 0;
     const uint32_t strip = edit_strip_blocks(ctx, ss, &pw);
     uint32_t cmax[3] = {0, 0, 0};                                // the most blocks of a row of each class; 0: no such row
@@ -243,8 +231,9 @@ int edit_launch(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t a0, uint32_t a1, ui
     for (uint32_t c = 0; c < 3; ++c) {
         if (!have[c]) continue;
         EditArgs a{ss->codes, ss->doff, ss->dlen, ss->order, (uint32_t)ss->N, ss->sigma, a0, a1, b0, b1, a0, 0, 0, c, strip, pw, ut, out};
+        if (p0 != 0 || p1 != ss->N) { a.order = ss->order.get() + p0; a.N = p1 - p0; }   // (rect only: the triangle's index needs the true N)
         a.tile = ctx->edit.tile > 0 ? (uint32_t)ctx->edit.tile : kTile[c];
-        a.ntiles = div_up<uint32_t>((uint32_t)ss->N, a.tile);
+        a.ntiles = div_up<uint32_t>(a.N, a.tile);
         uint32_t P = 1;                                              // the lanes of the class's widest pair: its table's stride
         while (P < cmax[c]) P <<= 1;
         const size_t lds = sizeof(uint32_t) * (c == 2 ? (size_t)ss->sigma * strip + 2 * (size_t)pw : (size_t)ss->sigma * P);
@@ -262,6 +251,11 @@ int edit_launch(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t a0, uint32_t a1, ui
 }
 
 }  // namespace
+
+int d2g_edit_rect_window(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t a0, uint32_t a1, uint32_t p0, uint32_t p1, uint32_t *out, hipStream_t s) {
+    if (a0 >= a1 || p0 >= p1) return D2G_OK;
+    return edit_launch(ctx, ss, a0, a1, 0, (uint32_t)ss->N, 0, out, s, p0, p1);
+}
 
 extern "C" {
 
@@ -288,6 +282,8 @@ int d2g_seqset_create(d2g_ctx *ctx, const uint8_t *bytes, const uint64_t *off, s
     std::vector<uint32_t> order(nrec);
     std::iota(order.begin(), order.end(), 0u);
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return ss->len[x] < ss->len[y]; });
+    ss->sorted_len.resize(nrec);
+    for (size_t p = 0; p < nrec; ++p) ss->sorted_len[p] = ss->len[order[p]];
     ss->bytes = ss->padded + (nrec + 1) * sizeof(uint64_t) + 2 * std::max<size_t>(nrec, 1) * sizeof(uint32_t);
     const size_t staging = std::max<uint64_t>(nbytes, 1) + (nrec + 1) * sizeof(uint64_t) + 256;
     size_t free_b = 0, total_b = 0;
@@ -346,7 +342,7 @@ int d2g_edit_ut_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, ui
     D2G_CHECK(ctx, out_dev != nullptr, "null output");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     const size_t rl = std::min(r1, ss->N - 1);                 // the last row has no pair
-    return edit_launch(ctx, ss, (uint32_t)r0, (uint32_t)rl, (uint32_t)r0 + 1, (uint32_t)ss->N, 1, out_dev, as_stream(stream));
+    return edit_launch(ctx, ss, (uint32_t)r0, (uint32_t)rl, (uint32_t)r0 + 1, (uint32_t)ss->N, 1, out_dev, as_stream(stream), 0, (uint32_t)ss->N);
 }
 
 int d2g_edit_rect_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t a0, size_t a1, size_t b0, size_t b1, uint32_t *out_dev, void *stream) {
@@ -356,7 +352,7 @@ int d2g_edit_rect_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t a0, size_t a1, 
     if (a0 == a1 || b0 == b1) return D2G_OK;
     D2G_CHECK(ctx, out_dev != nullptr, "null output");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
-    return edit_launch(ctx, ss, (uint32_t)a0, (uint32_t)a1, (uint32_t)b0, (uint32_t)b1, 0, out_dev, as_stream(stream));
+    return edit_launch(ctx, ss, (uint32_t)a0, (uint32_t)a1, (uint32_t)b0, (uint32_t)b1, 0, out_dev, as_stream(stream), 0, (uint32_t)ss->N);
 }
 
 // host-pointer forms: the distances of the range to `out`; synchronise

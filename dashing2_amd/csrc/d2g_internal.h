@@ -134,6 +134,7 @@ struct d2g_kset_tuning {
 struct d2g_edit_tuning {
     int strip = 0;                      // D2G_EDIT_STRIP: 1 .. 64, at most this many 32-row blocks of a query per strip (tests: the several-strip route on short records); 0 = what LDS holds
     int tile = 0;                       // D2G_EDIT_TILE: 1 .. 65536 column records per workgroup (tests, measurements); 0 = by launch class (512, 64, 8)
+    int near_route = 0;                 // D2G_EDIT_NEAR_ROUTE: 1 = the band route wherever it exists, 2 = the full route everywhere (measurements: the crossover of d2g_edit_near.hip); 0 = the dispatcher's choice
 };
 d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
 constexpr int MG_MAX_CHUNKS = 4;            // most chunks a rank's column slice is cut into inside one multi-GPU step (d2g_mgpu.hip)
@@ -157,6 +158,7 @@ struct d2g_ctx {
     d2g_evlog ev_k3k, ev_k3kcompact, ev_k3kbmh;   // under D2G_TIME_K3, the count-sketch chain (K3k): "k3k" = zeroing and k3k_add_kernel, "k3kcompact" = table -> (cell, |count|) lists, "k3kbmh" = BagMinHash over them
     d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
     d2g_evlog ev_edit, ev_editprep;         // under D2G_TIME_EDIT (d2g_edit.hip): "edit" = the pair kernel's launches of one call, "editprep" = a d2g_seqset's upload and recoding
+    d2g_evlog ev_editnear;                  // under D2G_TIME_EDIT_NEAR (d2g_edit_near.hip): "editnear" = the band kernel's and the clamp kernel's launches of one call (the full route's pair kernel is logged as "edit")
     d2g_evlog ev_screen, ev_screenreduce, ev_screenbuild;   // under D2G_TIME_SCREEN (d2g_screen.hip): "screen" = the count walk, "screenreduce" = d2g_screen_result's kernel, "screenbuild" = a screen's table
     d2g_evlog ev_dedup, ev_dedup_resolve;   // "dedup" = both: the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the latter alone)
     struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3.h)
@@ -165,6 +167,9 @@ struct d2g_ctx {
     d2g_dev<unsigned long long> dedup_keys; // one key per row of a band: its best representative of earlier bands (d2g_dedup.hip)
 };
 void d2g_k3_state_destroy(struct d2g_k3_state *st);
+// (d2g_knn.hip) the selection kernel of K2e over rows [row0, row0 + nrows) of a band [nrows][N] of values in [0, S] that the caller filled
+int d2g_knn_select_band(d2g_ctx *ctx, const uint32_t *band, size_t N, size_t S, size_t K, uint32_t min_count, size_t row0, size_t nrows, size_t out0,
+                        size_t cap, uint32_t *rowcnt_dev, uint32_t *ids_dev, uint32_t *counts_dev, hipStream_t s);
 // (d2g_host.cpp) the host ranking behind d2g_screen_create: distinct keys ascending, their raw k-mers, the rank of every position's key
 void d2g_screen_rank_keys(const uint64_t *keys, size_t n, uint64_t xormask, std::vector<uint64_t> &distinct, std::vector<uint64_t> &raw,
                           std::vector<uint32_t> &rank);
@@ -201,7 +206,7 @@ inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
 struct d2g_timer {
     d2g_evlog *ev; hipStream_t s; bool on;
     d2g_timer(d2g_ctx *c, d2g_evlog *e, hipStream_t st) : ev(e), s(st), on(false) {
-        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count || e == &c->ev_k1i) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_edit || e == &c->ev_editprep) ? D2G_TIME_EDIT : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
+        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count || e == &c->ev_k1i) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_edit || e == &c->ev_editprep) ? D2G_TIME_EDIT : e == &c->ev_editnear ? D2G_TIME_EDIT_NEAR : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
         on = (c->timing & bit) != 0;
         if (on) {
             d2g_event x, y;
@@ -215,7 +220,7 @@ struct d2g_timer {
 
 // one per translation unit with kernels: makes the runtime load that unit's code object now (hipFuncGetAttributes on one of
 // its kernels) instead of at its first launch
-void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k1i(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup(); void d2g_warm_edit();
+void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k1i(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup(); void d2g_warm_edit(); void d2g_warm_edit_near();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -173,6 +173,24 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_select_kernel(KnnArgs a) {
 
 }  // namespace
 
+// knn_select_kernel over a band that somebody else filled (d2g_edit_near.hip: closeness by edit distance): rows [row0, row0 + nrows)
+// of `band`, [nrows][N] values in [0, S]; outputs from row out0 on.  The contract of d2g_cmp_knn_dev's selection, logged as "knn".
+int d2g_knn_select_band(d2g_ctx *ctx, const uint32_t *band, size_t N, size_t S, size_t K, uint32_t min_count, size_t row0, size_t nrows, size_t out0,
+                        size_t cap, uint32_t *rowcnt_dev, uint32_t *ids_dev, uint32_t *counts_dev, hipStream_t s) {
+    D2G_CHECK(ctx, N < (1ull << 31) && S < (1ull << 31), "knn: shape too large");
+    if (!nrows) return D2G_OK;
+    KnnArgs a;
+    a.band = band; a.N = (uint32_t)N; a.S = (uint32_t)S;
+    a.K = (uint32_t)std::min<size_t>(K, 0xFFFFFFFFu); a.min_count = min_count;
+    a.row0 = row0; a.out0 = out0; a.cls = nullptr; a.cap = cap;
+    a.rowcnt = rowcnt_dev; a.ids = ids_dev; a.counts = counts_dev;
+    d2g_timer tm(ctx, &ctx->ev_knn, s);
+    hipLaunchKernelGGL(knn_select_kernel, dim3((unsigned)nrows), dim3(KNN_THREADS), 0, s, a);
+    tm.stop();
+    D2G_HIP(ctx, hipGetLastError());
+    return D2G_OK;
+}
+
 extern "C" {
 
 int d2g_cmp_knn_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, size_t K, uint32_t min_count, const uint32_t *cls_dev,

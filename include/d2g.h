@@ -121,6 +121,9 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
                                  * sums of d2g_screen_result; "screenbuild": the table of d2g_screen_create */
 #define D2G_TIME_EDIT   2048    /* "edit": the pair kernel of d2g_edit_*_dev (the launches of one call under one bracket); "editprep": the upload and
                                  * recoding of d2g_seqset_create */
+#define D2G_TIME_EDIT_NEAR 4096 /* "editnear": the band kernel and the clamp kernel of d2g_edit_near_dev (K2i), one bracket per run of consecutive
+                                 * rows that take one route (a call whose rows all take one route: one bracket; sum count x avg for a mixed
+                                 * call); the pair kernel of its full route is logged as "edit", the selection of d2g_edit_within_dev as "knn" */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -1111,6 +1114,51 @@ int    d2g_edit_rect_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t a0, size_t a
 /* host-pointer forms; synchronise */
 int    d2g_edit_ut(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, uint32_t *out);
 int    d2g_edit_rect(d2g_ctx *ctx, const d2g_seqset *ss, size_t a0, size_t a1, size_t b0, size_t b1, uint32_t *out);
+
+/* ---- K2i: neighbours within a bound on the edit distance (reference src/index_build.cpp:166-228, build_exact_graph with
+ * M_EDIT_DISTANCE as the distance) -----------------------------------------------------------------------------------------
+ * For a bound T >= 0 the CLOSENESS of records i and j is c(i, j) = T + 1 - d(i, j) if d(i, j) <= T, else 0, with d the distance of
+ * K2h above: c = T + 1 - min(d, T + 1), an exact integer in [0, T + 1]; c(i, i) = T + 1.  Larger is nearer and 0 is never a
+ * neighbour, so closeness is to K2e's selection what the equality count is (S = T + 1).  No floating point on the device.
+ *
+ * d2g_edit_near_dev writes c(i, j) for every row i in [r0, r1) and EVERY column j in [0, N), row-major; nothing is left unwritten.
+ * T < 2^31.  Per pair: |len_i - len_j| > T gives 0 without a table (the columns that can pass are one window of the set's order by
+ * length; the rest is a fill); for T <= D2G_EDIT_BAND_MAX a kernel that gives every LANE one column record and slides the band of
+ * 2T + 1 diagonals down the query in one 64-bit word, leaving a pair as soon as its score proves d > T; above that bound (and for a
+ * row whose match table would not fit in 64 KiB of LDS: (ceil(len / 32) + 4 | 1) * sigma > 16384; and for a row of 9 to 32 symbols
+ * with 5T >= its length, where that kernel was measured to be ahead) the pair kernel of K2h over the
+ * window, into close_dev itself, then a clamp in place.  The route is chosen per row and [r0, r1) is cut into runs of CONSECUTIVE rows of
+ * one route, a launch (or two) each: rows that alternate between the routes cost a launch per row (not measured; a set of one kind of
+ * record, or one sorted by length, has at most three runs).  Enqueues on `stream`, does not synchronise, allocates nothing.  An empty
+ * row range is D2G_OK and writes nothing; a set of another context or a null output is D2G_ERR_INVALID before anything is written. */
+#define D2G_EDIT_BAND_MAX 31
+int    d2g_edit_band_max(void);                              /* D2G_EDIT_BAND_MAX of the library that was loaded */
+int    d2g_edit_near_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, uint32_t T, uint32_t *close_dev /* [r1-r0][N] */,
+                         void *stream);
+/* The selection of d2g_cmp_knn_dev (K2e, the same kernel) over closeness, with min_count = 1 and cls = NULL: per row of [r0, r1) the
+ * columns j != i (self excluded by INDEX: duplicates list each other) in ASCENDING j with their closeness in the row's own cap slots,
+ * rowcnt_dev the TRUE number even beyond cap, nothing written past a row's slots; cap == 0 counts only (ids_dev / close_dev may be
+ * NULL).  K == 0: every j with d <= T.  K >= 1: the K nearest among those with d <= T with all ties of the K-th; a row with fewer
+ * than K inside the bound lists what it has.  Bands of band_rows rows (0 = a default) go through the context's ONE scratch band, the
+ * one d2g_cmp_knn_dev and d2g_cmp_dedup_dev use: the calls of one context that use it must be issued on ONE stream.  Enqueues, does
+ * not synchronise. */
+int    d2g_edit_within_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, size_t K, uint32_t T, size_t cap,
+                           uint32_t *rowcnt_dev /* [r1-r0] */, uint32_t *ids_dev /* [r1-r0][cap] */, uint32_t *close_dev /* [r1-r0][cap] */,
+                           size_t band_rows, void *stream);
+/* Host-pointer form, in the manner of d2g_cmp_set_knn: rows in chunks with `cap` slots each (0 = a default), only the rows that
+ * overflowed cap run again, d2g_knn_finish with lut[c] = (float)(T + 1 - c), isdist = 1; synchronises.  The values are the distances
+ * as float32, ascending, equal distances by ascending id (std::sort of (value, id)).  Outputs and errors as d2g_cmp_set_knn:
+ * indptr_out [r1 - r0 + 1] is always written, D2G_ERR_NOMEM with *nnz_needed when out_cap is short, D2G_ERR_INVALID for a bad range.
+ * As there, the whole result is computed before out_cap is looked at: a caller that retries after D2G_ERR_NOMEM pays the device work
+ * twice (pass an out_cap that is large enough where a bound on nnz is known).
+ *   K == 0, threshold mode: every j != i with d(i, j) <= T (the NN_GRAPH_THRESHOLD arm for a distance; a caller with a non-integer
+ *           threshold passes its floor).
+ *   K >= 1, top-K mode: the K smallest distances over ALL other records with every tie of the K-th, no zero-skipping.
+ *           T is only the STARTING bound: the rows that end with fewer than min(K, N - 1) entries, and only those, run again with
+ *           the bound 2T + 1, until they are full or the bound reaches the set's longest record, from where every record
+ *           qualifies.  The result does not depend on T. */
+int    d2g_edit_knn(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, size_t K, uint32_t T, size_t cap, size_t band_rows,
+                    uint64_t *indptr_out /* [r1-r0+1] */, uint32_t *indices_out, float *data_out, size_t out_cap, size_t *nnz_needed);
 
 /* ---- multi-GPU row partition (host arithmetic; emitrect.cpp:290-323 row order) ----
  * Splits rows [0,N) into `nparts` contiguous ranges with (near-)equal pair counts.
