@@ -22,7 +22,7 @@ from .capi import (  # noqa: F401
     alphabet_size, alphabet_max_k, alphabet_code, alphabet_name, key_bits,
     countsketch_lds_cells,
     IntervalPlan, xxh3_64, bed_parse, XXH3_MAX_LEN,
-    SeqSet, SeqRecs, TIME_EDIT, TIME_EDIT_NEAR, EDIT_MAX_LEN, EDIT_BAND_MAX, seqset_check, seqset_recode_map,
+    SeqSet, SeqRecs, TIME_EDIT, TIME_EDIT_NEAR, TIME_EDIT_DEDUP, EDIT_MAX_LEN, EDIT_BAND_MAX, seqset_check, seqset_recode_map,
 )
 
 __all__ = [
@@ -41,5 +41,5 @@ __all__ = [
     "alphabet_size", "alphabet_max_k", "alphabet_code", "alphabet_name", "key_bits",
     "countsketch_lds_cells",
     "IntervalPlan", "xxh3_64", "bed_parse", "XXH3_MAX_LEN",
-    "SeqSet", "SeqRecs", "TIME_EDIT", "TIME_EDIT_NEAR", "EDIT_MAX_LEN", "EDIT_BAND_MAX", "seqset_check", "seqset_recode_map",
+    "SeqSet", "SeqRecs", "TIME_EDIT", "TIME_EDIT_NEAR", "TIME_EDIT_DEDUP", "EDIT_MAX_LEN", "EDIT_BAND_MAX", "seqset_check", "seqset_recode_map",
 ]

@@ -26,6 +26,7 @@ TIME_KSET = 512
 TIME_SCREEN = 1024
 TIME_EDIT = 2048
 TIME_EDIT_NEAR = 4096
+TIME_EDIT_DEDUP = 8192
 EDIT_MAX_LEN = 65535                                                     # include/d2g.h D2G_EDIT_MAX_LEN
 EDIT_BAND_MAX = 31                                                       # include/d2g.h D2G_EDIT_BAND_MAX
 
@@ -194,6 +195,8 @@ SIGNATURES = {
     "d2g_edit_band_max": (_int, []),
     "d2g_edit_near_dev": (_int, [_vp, _vp, _sz, _sz, C.c_uint32, _vp, _vp]),
     "d2g_edit_within_dev": (_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "d2g_edit_dedup_dev": (_int, [_vp, _vp, C.c_uint32, _vp, _sz, _vp]),
+    "d2g_edit_dedup": (_int, [_vp, _vp, C.c_uint32, _sz, _vp]),
     "d2g_edit_knn": (_int, [_vp, _vp, _sz, _sz, _sz, C.c_uint32, _sz, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
     "d2g_epilogue_exact": (_f32, [_u64, _dbl, _dbl, _int, _int]),
     "d2g_epilogue_exact_ut": (_int, [_vp, _vp, _sz, _sz, _sz, _int, _int, _int, _vp]),
@@ -1623,6 +1626,16 @@ class SeqSet:
         r1 = self.N if r1 is None else r1
         return _knn_csr(self.ctx, r1 - r0, K, lambda ip, ix, dt, oc, need: lib().d2g_edit_knn(
             self.ctx._h, self._h, r0, r1, K, T, cap, band_rows, ip, ix, dt, oc, need))
+
+    def dedup_dev(self, assign_dev_ptr, T, band_rows=0, stream=None):
+        """d2g_edit_dedup_dev: greedy clustering by edit distance; assign[i] = the representative of record i, u32 [N] in device memory"""
+        self.ctx._check(lib().d2g_edit_dedup_dev(self.ctx._h, self._h, T, assign_dev_ptr, band_rows, stream))
+
+    def dedup(self, T, band_rows=0):
+        """d2g_edit_dedup -> uint32[N] (host-pointer form; synchronises)"""
+        out = np.zeros(self.N, np.uint32)
+        self.ctx._check(lib().d2g_edit_dedup(self.ctx._h, self._h, T, band_rows, _np_ptr(out)))
+        return out
 
     def close(self):
         if getattr(self, "_h", None):

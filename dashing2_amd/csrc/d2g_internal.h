@@ -134,6 +134,8 @@ struct d2g_kset_tuning {
 struct d2g_edit_tuning {
     int strip = 0;                      // D2G_EDIT_STRIP: 1 .. 64, at most this many 32-row blocks of a query per strip (tests: the several-strip route on short records); 0 = what LDS holds
     int tile = 0;                       // D2G_EDIT_TILE: 1 .. 65536 column records per workgroup (tests, measurements); 0 = by launch class (512, 64, 8)
+    int dedup_route = 0;                // D2G_EDIT_DEDUP_ROUTE: 1 = the list kernel wherever it exists, 2 = the all-columns route for every row (measurements, tests: d2g_edit_dedup.hip); 0 = the dispatcher's choice
+    int dedup_reverse = 0;              // D2G_EDIT_DEDUP_REVERSE: 1 = the representative list is written backwards (tests: the result does not depend on its order)
     int near_route = 0;                 // D2G_EDIT_NEAR_ROUTE: 1 = the band route wherever it exists, 2 = the full route everywhere (measurements: the crossover of d2g_edit_near.hip); 0 = the dispatcher's choice
 };
 d2g_k3_tuning d2g_k3_tuning_resolve(const d2g_tuning &t);   // (d2g_runtime.hip)
@@ -159,12 +161,14 @@ struct d2g_ctx {
     d2g_evlog ev_k3s, ev_kset, ev_ksetprep; // under D2G_TIME_KSET: "k3s" = the sorted emission after K3's count (d2g_kmer_sets*), "kset" = the exact pair kernel, "ksetprep" = a d2g_kset's slice table
     d2g_evlog ev_edit, ev_editprep;         // under D2G_TIME_EDIT (d2g_edit.hip): "edit" = the pair kernel's launches of one call, "editprep" = a d2g_seqset's upload and recoding
     d2g_evlog ev_editnear;                  // under D2G_TIME_EDIT_NEAR (d2g_edit_near.hip): "editnear" = the band kernel's and the clamp kernel's launches of one call (the full route's pair kernel is logged as "edit")
+    d2g_evlog ev_editdedup, ev_editdedup_list, ev_editdedup_resolve;   // under D2G_TIME_EDIT_DEDUP (d2g_edit_dedup.hip): "editdedup" = every kernel of one band of d2g_edit_dedup_dev; inside it "editdedup_list" = the two kernels that compact the representative list, "editdedup_resolve" = the in-order step
     d2g_evlog ev_screen, ev_screenreduce, ev_screenbuild;   // under D2G_TIME_SCREEN (d2g_screen.hip): "screen" = the count walk, "screenreduce" = d2g_screen_result's kernel, "screenbuild" = a screen's table
     d2g_evlog ev_dedup, ev_dedup_resolve;   // "dedup" = both: the per-row kernel and the in-order step of d2g_cmp_dedup_dev ("dedup_resolve": the latter alone)
     struct d2g_k3_state *k3 = nullptr;      // work buffers of d2g_bmh_sketch_dev (d2g_k3.h)
     uint64_t cs_table_bytes = 0, cs_groups = 0, cs_batches = 0;   // K3k (d2g_countsketch_stats): the largest table so far, the groups and the batches of all count-sketch calls
     d2g_dev<uint32_t> knn_band;             // [band rows][N] equality counts the selection kernel reads (d2g_knn.hip); grow-only
-    d2g_dev<unsigned long long> dedup_keys; // one key per row of a band: its best representative of earlier bands (d2g_dedup.hip)
+    d2g_dev<unsigned long long> dedup_keys; // one key per row of a band: its best representative of earlier bands (d2g_dedup.hip, d2g_edit_dedup.hip)
+    d2g_dev<uint32_t> edit_dedup_ws;        // d2g_edit_dedup.hip: the representative list [N], its length, the compaction's counts, the band's own block; grow-only
 };
 void d2g_k3_state_destroy(struct d2g_k3_state *st);
 // (d2g_knn.hip) the selection kernel of K2e over rows [row0, row0 + nrows) of a band [nrows][N] of values in [0, S] that the caller filled
@@ -206,7 +210,7 @@ inline int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what) {
 struct d2g_timer {
     d2g_evlog *ev; hipStream_t s; bool on;
     d2g_timer(d2g_ctx *c, d2g_evlog *e, hipStream_t st) : ev(e), s(st), on(false) {
-        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count || e == &c->ev_k1i) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_edit || e == &c->ev_editprep) ? D2G_TIME_EDIT : e == &c->ev_editnear ? D2G_TIME_EDIT_NEAR : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
+        const int bit = (e == &c->ev_k1 || e == &c->ev_k1count || e == &c->ev_k1i) ? D2G_TIME_K1 : e == &c->ev_k2 ? D2G_TIME_K2 : e == &c->ev_k2prep ? D2G_TIME_K2PREP : e == &c->ev_k0 ? D2G_TIME_K0 : e == &c->ev_knn ? D2G_TIME_KNN : e == &c->ev_filter ? D2G_TIME_FILTER : (e == &c->ev_k3s || e == &c->ev_kset || e == &c->ev_ksetprep) ? D2G_TIME_KSET : (e == &c->ev_dedup || e == &c->ev_dedup_resolve) ? D2G_TIME_DEDUP : (e == &c->ev_edit || e == &c->ev_editprep) ? D2G_TIME_EDIT : e == &c->ev_editnear ? D2G_TIME_EDIT_NEAR : (e == &c->ev_editdedup || e == &c->ev_editdedup_list || e == &c->ev_editdedup_resolve) ? D2G_TIME_EDIT_DEDUP : (e == &c->ev_screen || e == &c->ev_screenreduce || e == &c->ev_screenbuild) ? D2G_TIME_SCREEN : D2G_TIME_K3;
         on = (c->timing & bit) != 0;
         if (on) {
             d2g_event x, y;
@@ -220,7 +224,7 @@ struct d2g_timer {
 
 // one per translation unit with kernels: makes the runtime load that unit's code object now (hipFuncGetAttributes on one of
 // its kernels) instead of at its first launch
-void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k1i(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup(); void d2g_warm_edit(); void d2g_warm_edit_near();
+void d2g_warm_filter(); void d2g_warm_k0(); void d2g_warm_k1(); void d2g_warm_k1i(); void d2g_warm_k2(); void d2g_warm_k2_bitslice(); void d2g_warm_k2_planes(); void d2g_warm_k3(); void d2g_warm_kset(); void d2g_warm_screen(); void d2g_warm_knn(); void d2g_warm_dedup(); void d2g_warm_edit(); void d2g_warm_edit_near(); void d2g_warm_edit_dedup();
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 

@@ -15,7 +15,7 @@ static const char *const kTuningNames[] = {
     "D2G_K3_GUESS_SCALE", "D2G_K3_GRID_PER_CU", "D2G_K3_LIGHT", "D2G_K3_GQ_SCALE",
     "D2G_K3S_RANGE_KEYS", "D2G_KSET_SPLIT", "D2G_KSET_PBITS",
     "D2G_CS_TABLE_BYTES", "D2G_CS_LDS_CELLS",
-    "D2G_EDIT_STRIP", "D2G_EDIT_TILE", "D2G_EDIT_NEAR_ROUTE",
+    "D2G_EDIT_STRIP", "D2G_EDIT_TILE", "D2G_EDIT_NEAR_ROUTE", "D2G_EDIT_DEDUP_ROUTE", "D2G_EDIT_DEDUP_REVERSE",
 };
 void d2g_tuning_load(d2g_tuning &t) {
     t.kv.clear();
@@ -77,6 +77,8 @@ void d2g_tuning_resolve(d2g_ctx *c) {
     if (const char *e = c->tune.get("D2G_EDIT_STRIP")) { const int v = std::atoi(e); if (v >= 1 && v <= 64) c->edit.strip = v; }
     if (const char *e = c->tune.get("D2G_EDIT_TILE")) { const int v = std::atoi(e); if (v >= 1 && v <= 65536) c->edit.tile = v; }
     if (const char *e = c->tune.get("D2G_EDIT_NEAR_ROUTE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) c->edit.near_route = v; }
+    if (const char *e = c->tune.get("D2G_EDIT_DEDUP_ROUTE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) c->edit.dedup_route = v; }
+    if (const char *e = c->tune.get("D2G_EDIT_DEDUP_REVERSE")) c->edit.dedup_reverse = std::atoi(e) != 0;
     c->mgpu_chunks = 0;
     if (const char *e = c->tune.get("D2G_MGPU_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= MG_MAX_CHUNKS) c->mgpu_chunks = v; }
 }
@@ -231,7 +233,7 @@ int d2g_warmup(d2g_ctx *c, int what) {
     if (what & D2G_WARM_K3) d2g_warm_k3();
     if (what & D2G_WARM_KSET) d2g_warm_kset();
     if (what & D2G_WARM_SCREEN) d2g_warm_screen();
-    if (what & D2G_WARM_EDIT) { d2g_warm_edit(); d2g_warm_edit_near(); }
+    if (what & D2G_WARM_EDIT) { d2g_warm_edit(); d2g_warm_edit_near(); d2g_warm_edit_dedup(); }
     return D2G_OK;
 }
 int d2g_device_name(int device, char *buf, size_t cap) {
@@ -244,7 +246,7 @@ int d2g_device_name(int device, char *buf, size_t cap) {
 
 int d2g_set_timing(d2g_ctx *c, int enabled) {
     if (!c) return D2G_ERR_INVALID;
-    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN | D2G_TIME_EDIT | D2G_TIME_EDIT_NEAR) : (enabled & ~1);
+    c->timing = enabled == 1 ? (D2G_TIME_K1 | D2G_TIME_K2 | D2G_TIME_K2PREP | D2G_TIME_K3 | D2G_TIME_KNN | D2G_TIME_DEDUP | D2G_TIME_FILTER | D2G_TIME_KSET | D2G_TIME_SCREEN | D2G_TIME_EDIT | D2G_TIME_EDIT_NEAR | D2G_TIME_EDIT_DEDUP) : (enabled & ~1);
     return D2G_OK;
 }
 
@@ -269,6 +271,9 @@ int d2g_kernel_ms(d2g_ctx *c, const char *which, int reset, int *count, float *a
     else if (!std::strcmp(which, "edit")) e = &c->ev_edit;
     else if (!std::strcmp(which, "editprep")) e = &c->ev_editprep;
     else if (!std::strcmp(which, "editnear")) e = &c->ev_editnear;
+    else if (!std::strcmp(which, "editdedup")) e = &c->ev_editdedup;
+    else if (!std::strcmp(which, "editdedup_list")) e = &c->ev_editdedup_list;
+    else if (!std::strcmp(which, "editdedup_resolve")) e = &c->ev_editdedup_resolve;
     else if (!std::strcmp(which, "screen")) e = &c->ev_screen;
     else if (!std::strcmp(which, "screenreduce")) e = &c->ev_screenreduce;
     else if (!std::strcmp(which, "screenbuild")) e = &c->ev_screenbuild;

@@ -124,6 +124,9 @@ int         d2g_memcpy_d2h(d2g_ctx *ctx, void *dst_host, const void *src_dev, si
 #define D2G_TIME_EDIT_NEAR 4096 /* "editnear": the band kernel and the clamp kernel of d2g_edit_near_dev (K2i), one bracket per run of consecutive
                                  * rows that take one route (a call whose rows all take one route: one bracket; sum count x avg for a mixed
                                  * call); the pair kernel of its full route is logged as "edit", the selection of d2g_edit_within_dev as "knn" */
+#define D2G_TIME_EDIT_DEDUP 8192 /* "editdedup": the kernels of d2g_edit_dedup_dev (K2j) under one bracket per band; inside it "editdedup_list" = the
+                                 * two kernels that compact the representative list, "editdedup_resolve" = the in-order step; the kernels of
+                                 * d2g_edit_near_dev for rows on the all-columns route are also logged under their own names */
 /* enabled: 0 = off, 1 = every kernel above, or an OR of D2G_TIME_* (an event pair in the stream costs a few microseconds of
  * device time per launch: time only what is being reported) */
 int         d2g_set_timing(d2g_ctx *ctx, int enabled);
@@ -1159,6 +1162,27 @@ int    d2g_edit_within_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t
  *           qualifies.  The result does not depend on T. */
 int    d2g_edit_knn(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, size_t K, uint32_t T, size_t cap, size_t band_rows,
                     uint64_t *indptr_out /* [r1-r0+1] */, uint32_t *indices_out, float *data_out, size_t out_cap, size_t *nnz_needed);
+
+/* ---- K2j: greedy clustering by edit distance (the repository's own rule; the reference's exhaustive dedup_core is
+ * inverted for a distance, SURVEY F13, and is not reproduced) ---------------------------------------------------------------
+ * Records are taken in input order i = 0 .. N - 1; d is the distance of K2h above (unit costs, bytes as they are, d(x, "") = |x|).
+ * Among the representatives r < i the one with the smallest d(i, r) is picked, among equal distances the smallest r; if that
+ * distance is <= T, assign[i] = r, otherwise i is a representative and assign[i] = i.  A record is compared with representatives
+ * only: A ~ B, B ~ C, A !~ C gives {A, B}, {C}.  In the closeness c = T + 1 - min(d, T + 1) of K2i this is the rule of
+ * d2g_cmp_dedup_dev with the identity class table and min_count = 1, and d2g_dedup_clusters turns assign into clusters unchanged.
+ *
+ * d2g_edit_dedup_dev writes every word of assign_dev[0, N) and nothing else of the caller's.  It enqueues on `stream` and never
+ * synchronises with the host (the length of the representative list stays in a device word).  Bands of band_rows rows (0 = the
+ * default, 256; larger requests are cut to 256, as in d2g_cmp_dedup_dev).  For T <= D2G_EDIT_BAND_MAX a row whose match table fits in
+ * 64 KiB of LDS ((ceil(len / 32) + 4 | 1) * sigma <= 16384) runs the band kernel of K2i over the list of representatives in front of
+ * its band and keeps only the best key per row; every other row runs d2g_edit_near_dev over all N columns into the context's scratch
+ * band.  It may GROW scratch of the context (the band of d2g_edit_within_dev / d2g_cmp_knn_dev / d2g_cmp_dedup_dev, K2f's keys, and a
+ * list of N + 66 561 words of its own): the calls of one context that use that scratch must be issued on ONE stream.  T < 2^31 - 1.
+ * N = 0 does nothing and is D2G_OK.  A set of another context, or a null output, is D2G_ERR_INVALID before anything is written; a
+ * null context or set returns D2G_ERR_INVALID (-1) without a message.
+ * d2g_edit_dedup runs the set, copies the 4 N bytes of assign to assign_out and synchronises. */
+int    d2g_edit_dedup_dev(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t T, uint32_t *assign_dev /* [N] */, size_t band_rows, void *stream);
+int    d2g_edit_dedup(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t T, size_t band_rows, uint32_t *assign_out /* host [N] */);
 
 /* ---- multi-GPU row partition (host arithmetic; emitrect.cpp:290-323 row order) ----
  * Splits rows [0,N) into `nparts` contiguous ranges with (near-)equal pair counts.
