@@ -861,7 +861,9 @@ int  d2g_cmp_dist_trunc_ut(d2g_ctx *ctx, const double *sigs, const double *cards
  * ids_dev / counts_dev: its qualifying columns in ASCENDING j with their counts -- bit-reproducible -- and rowcnt_dev[i - r0] is the
  * TRUE number even beyond cap; nothing is written past a row's slots (cap == 0: counting only, ids_dev / counts_dev may be NULL).
  * band_rows == 0: the default (a band of at most 64 MB).  Enqueues on `stream`, does not synchronise.  The band lives in the context:
- * the selection launches of ONE context must be issued on ONE stream. */
+ * the selection launches of ONE context must be issued on ONE stream.  The band only grows: a call that has to grow it (this one,
+ * d2g_cmp_dedup_dev, d2g_edit_within_dev, d2g_edit_dedup_dev) waits for the device before it releases the old block (hipFree), so
+ * calls queued earlier that still read that block finish first; such a call does synchronise, and it allocates. */
 int  d2g_cmp_knn_dev(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, size_t K, uint32_t min_count,
                      const uint32_t *cls_dev, size_t cap, uint32_t *rowcnt_dev /* [r1-r0] */, uint32_t *ids_dev /* [r1-r0][cap] */,
                      uint32_t *counts_dev /* [r1-r0][cap] */, size_t band_rows, void *stream);
