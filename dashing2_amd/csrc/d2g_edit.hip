@@ -238,7 +238,7 @@ int edit_launch(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t a0, uint32_t a1, ui
         while (P < cmax[c]) P <<= 1;
         const size_t lds = sizeof(uint32_t) * (c == 2 ? (size_t)ss->sigma * strip + 2 * (size_t)pw : (size_t)ss->sigma * P);
         if (lds > sizeof(uint32_t) * EDIT_LDS_WORDS) { ctx->last_error = "d2g_edit: the match table does not fit in LDS"; return D2G_ERR_INTERNAL; }
-        const uint32_t rows_per = std::max<uint32_t>(1, 0x7fffffffu / a.ntiles);
+        const uint32_t rows_per = std::max<uint32_t>(1, ctx->limits.edit_grid_max / a.ntiles);
         for (uint32_t r = a0; r < a1; r += rows_per) {
             a.row0 = r;
             const uint32_t nr = std::min(rows_per, a1 - r);

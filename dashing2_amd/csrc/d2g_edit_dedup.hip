@@ -41,7 +41,7 @@ constexpr int EDD_THREADS = 256, EDD_WAVES = EDD_THREADS / 64;
 constexpr size_t EDD_MAX_BAND = EDD_THREADS;              // the in-order step: one band column per thread
 constexpr uint32_t EDD_TILE_MIN = 64, EDD_TILE_MAX = 512; // positions of a list per work item: between these by the list's length (edd_tile; D2G_EDIT_TILE overrides)
 constexpr uint32_t EDD_WAVES_PER_CU = 20;                 // the list kernel's grid: one-wave workgroups, five resident per SIMD (86 VGPRs)
-constexpr uint32_t EDD_CHUNK = 1024, EDD_MAX_CHUNKS = 1024;   // the compaction: positions of the order per workgroup, at most so many workgroups
+static_assert(EDD_THREADS == (int)EDD_THREADS_HOST, "d2g_limits.h rounds a compaction chunk to the workgroup size");   // EDD_CHUNK, EDD_MAX_CHUNKS: d2g_limits.h
 constexpr int EDD_UNROLL = 4, EDD_AHEAD = 4;              // as DEDUP_UNROLL, DEDUP_AHEAD of d2g_dedup.hip
 
 __device__ __forceinline__ uint32_t edd_wave_max32(uint32_t v) {
@@ -341,7 +341,7 @@ int d2g_edit_dedup_dev(d2g_ctx *ctx, const d2g_seqset *ss, uint32_t T, uint32_t 
     bool any_all = false;
     for (uint32_t i = 0; i < N; ++i) { list_row[i] = edd_list_row(ctx, ss, i, T); any_all |= !list_row[i]; }
     // scratch of the context (grow-only, K2e's one-stream rule): the list [N], its length [1], the chunk counts, the band's own block
-    const uint32_t chunk = std::max<uint32_t>(EDD_CHUNK, div_up<uint32_t>(div_up<uint32_t>(N, EDD_MAX_CHUNKS), EDD_THREADS) * EDD_THREADS);
+    const uint32_t chunk = d2g_edit_dedup_chunk(N, ctx->limits);   // EDD_CHUNK, or what EDD_MAX_CHUNKS workgroups need to cover N
     const uint32_t nchunks = div_up<uint32_t>(N, chunk);
     if (int rc = ctx->edit_dedup_ws.grow(ctx, (size_t)N + 1 + EDD_MAX_CHUNKS + EDD_MAX_BAND * EDD_MAX_BAND, 0, "edit dedup scratch alloc")) return rc;
     if (int rc = ctx->dedup_keys.grow(ctx, EDD_MAX_BAND, 0, "dedup keys alloc")) return rc;

@@ -50,7 +50,6 @@ constexpr uint32_t EDIT_NEAR_SHORT_T_FACTOR = 5;
 constexpr uint32_t EDIT_NEAR_TINY_LEN = 8;
 constexpr uint32_t EDIT_NEAR_TILE = 512;                    // positions of the order per workgroup (D2G_EDIT_TILE overrides)
 constexpr size_t NEAR_BAND_BYTES = (size_t)64 << 20;        // d2g_edit_within_dev's default band, as K2e's
-constexpr size_t NEAR_CHUNK_SLOTS = (size_t)1 << 24;        // d2g_edit_knn: candidate slots per chunk of rows
 
 struct NearArgs {
     const uint8_t *codes;
@@ -195,7 +194,7 @@ int d2g_edit_near_dev(d2g_ctx *ctx, const d2g_seqset *ss, size_t r0, size_t r1, 
             a.ntiles = div_up<uint32_t>(N, a.tile);
             const size_t lds = sizeof(uint32_t) * (size_t)ss->sigma * a.stride;
             if (lds > sizeof(uint32_t) * EDIT_LDS_WORDS) { ctx->last_error = "d2g_edit_near: the match table does not fit in LDS"; return D2G_ERR_INTERNAL; }
-            const uint32_t rows_per = std::max<uint32_t>(1, 0x7fffffffu / a.ntiles);
+            const uint32_t rows_per = std::max<uint32_t>(1, ctx->limits.edit_grid_max / a.ntiles);
             d2g_timer tm(ctx, &ctx->ev_editnear, s);
             for (uint32_t r = a0; r < a1; r += rows_per) {
                 a.row0 = r;
@@ -294,7 +293,8 @@ struct EditKnn {
     // rows [c0, c1) under `bound`, in chunks; top-K: the rows that are short of min(K, N - 1) entries go on with 2 bound + 1
     int run(size_t c0, size_t c1, uint32_t bound) {
         const size_t want = std::min(K, ss->N - 1);
-        const size_t chunk = std::max<size_t>(1, NEAR_CHUNK_SLOTS / cap);
+        const size_t slots = ctx->limits.edit_knn_chunk_slots;   // NEAR_CHUNK_SLOTS (d2g_limits.h) unless D2G_EDIT_KNN_CHUNK_SLOTS shrinks it
+        const size_t chunk = std::max<size_t>(1, slots / cap);
         std::vector<uint32_t> cnt, ids, cls, cnt2, ids2, cls2;
         for (size_t b0 = c0; b0 < c1; b0 += chunk) {
             const size_t b1 = std::min(b0 + chunk, c1), n = b1 - b0;
@@ -306,7 +306,7 @@ struct EditKnn {
                 size_t e = i + 1;
                 if (k == 1) {                                    // only the rows that overflowed run again: a run of them whose widest list fits the slot budget
                     size_t cap2 = cnt[i];
-                    while (e < n && kind(e) == 1 && (e - i + 1) * std::max<size_t>(cap2, cnt[e]) <= std::max<size_t>(NEAR_CHUNK_SLOTS, cnt[i])) { cap2 = std::max<size_t>(cap2, cnt[e]); ++e; }
+                    while (e < n && kind(e) == 1 && (e - i + 1) * std::max<size_t>(cap2, cnt[e]) <= std::max<size_t>(slots, cnt[i])) { cap2 = std::max<size_t>(cap2, cnt[e]); ++e; }
                     if ((rc = fetch(b0 + i, b0 + e, bound, cap2, cnt2, ids2, cls2))) return rc;
                     if ((rc = append(cnt2.data(), ids2.data(), cls2.data(), e - i, cap2, bound))) return rc;
                 } else {

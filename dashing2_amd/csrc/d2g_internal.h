@@ -8,6 +8,7 @@
 #include <utility>
 
 #include <vector>
+#include "d2g_limits.h"
 struct d2g_ctx;
 int d2g_hip_status(d2g_ctx *ctx, hipError_t e, const char *what);   // (below) sets last_error to what + ": " + HIP's text; out of memory -> D2G_ERR_NOMEM
 
@@ -63,20 +64,11 @@ struct d2g_evlog {
     std::vector<d2g_event> a, b;
 };
 
-// Every D2G_* switch that selects a kernel, a threshold or a test hook inside the library is read from the environment ONCE per context
-// (d2g_ctx_create; again only on d2g_ctx_reload_tuning) and used from this snapshot: a run's timing does not depend on who changed
-// the environment in between, d2g_ctx_tuning reports the resolved set, and the multi-GPU engine compares it across ranks.
-struct d2g_tuning {
-    std::vector<std::pair<std::string, std::string>> kv;      // the switches that were set, in the order of d2g_tuning_names()
-    const char *get(const char *name) const {                 // nullptr = not set
-        for (const auto &p : kv) if (p.first == name) return p.second.c_str();
-        return nullptr;
-    }
-};
+// the snapshot of the D2G_* switches (d2g_tuning) and the limits that cut a large call into pieces (d2g_limits_tuning): d2g_limits.h
 void d2g_tuning_load(d2g_tuning &t);
-// what the switches RESOLVE to (unset or invalid: the default).  The three records below are filled once per snapshot of the switches
+// what the switches RESOLVE to (unset or invalid: the default).  The records below are filled once per snapshot of the switches
 // (d2g_tuning_resolve, right after d2g_tuning_load) and read as ctx->k2 (K2 kernels and thresholds), ctx->k3_tune (the --multiset
-// chain) and ctx->mgpu_chunks (the multi-GPU engine): nobody parses a switch where it is used.
+// chain), ctx->limits (d2g_limits.h) and ctx->mgpu_chunks (the multi-GPU engine): nobody parses a switch where it is used.
 struct d2g_k2_tuning {
     bool sparse = true;                 // D2G_BS_SPARSE: 0 = every launch walks every tile
     size_t min_n = 8192;                // D2G_BS_SPARSE_MIN_N: below ~6000 sketches the extra launches cost more than the tiles they skip
@@ -149,6 +141,7 @@ struct d2g_ctx {
     d2g_k3_tuning k3_tune;                  // its K3 switches,
     d2g_kset_tuning kset;                   // the exact-set compare's,
     d2g_edit_tuning edit;                   // the edit-distance kernel's,
+    d2g_limits_tuning limits;               // the limits that cut a large call into pieces (tests shrink them: d2g_limits.h),
     int mgpu_chunks = 0;                    // and D2G_MGPU_CHUNKS: 1 .. MG_MAX_CHUNKS; 0 = the engine's default (a function of the shape)
     int num_cus = 0;
     std::string last_error;

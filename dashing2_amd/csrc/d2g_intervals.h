@@ -28,3 +28,19 @@ int d2g_interval_plan_build(const IntervalTables &in, IntervalPlanHost &p, std::
 // holds after `+= inc` line by line.  Adjacent pieces of bit-equal weight are one run.  Appends to the four vectors.
 void d2g_interval_sweep(const IntervalTables &in, size_t j0, size_t j1, bool normalize, std::vector<uint64_t> &hash,
                         std::vector<uint64_t> &lo, std::vector<uint64_t> &hi, std::vector<double> &w);
+
+// --multiset on the device (d2g_interval_bmh_sketch): the files' (id, weight) lists go in groups of consecutive files whose covered
+// positions fit `budget`.  The greedy cut of one group that starts at file f0 < n: `covered(f)` is asked for f0, f0 + 1, ... in order,
+// once each (the caller sweeps the file there), and the first file that would pass the budget ends the group and starts the next one;
+// a file that covers nothing always rides along.  -> f1, the group is [f0, f1): the last file asked was f1 where f1 < n, and its runs
+// are the caller's to drop.  f1 == f0: file f0 alone is over the budget, which no group can hold.
+template <class Covered> size_t d2g_interval_group(size_t f0, size_t n, uint64_t budget, Covered &&covered) {
+    uint64_t used = 0;                                      // <= budget; a file covers <= 2^44 positions
+    size_t f1 = f0;
+    for (; f1 < n; ++f1) {
+        const uint64_t c = covered(f1);
+        if (c > budget || used > budget - c) break;
+        used += c;
+    }
+    return f1;
+}

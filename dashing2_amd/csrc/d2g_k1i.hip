@@ -270,39 +270,48 @@ int d2g_interval_bmh_sketch(d2g_ctx *ctx, const d2g_interval_plan *plan, int nor
     d2g_dev<double> d_w;
     std::vector<uint64_t> h, lo, hi, run_off, set_off, tab;
     std::vector<double> w, tw;
+    std::vector<size_t> file_r0;
     for (size_t f0 = 0; f0 < n;) {
-        // a group of files: their lists (16 bytes per covered position) in a third of the free device memory
+        // a group of files: their lists (16 bytes per covered position) in a third of the free device memory (or D2G_INTERVAL_LIST_POSITIONS)
         size_t free_b = 0, total_b = 0;
         D2G_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
-        const uint64_t budget = free_b / 3 / 16;
+        const uint64_t list_positions = ctx->limits.interval_list_positions, budget = list_positions ? list_positions : free_b / 3 / 16;
         h.clear(); lo.clear(); hi.clear(); w.clear();
-        set_off.assign(1, 0); tw.clear(); run_off.assign(1, 0);
-        size_t f1 = f0;
-        for (; f1 < n; ++f1) {
+        set_off.assign(1, 0); tw.clear(); run_off.assign(1, 0); file_r0.clear();
+        uint64_t covered = 0;                                                      // of the last file swept
+        const size_t f1 = d2g_interval_group(f0, n, budget, [&](size_t f) {
             const size_t r0 = h.size();
-            d2g_interval_sweep(in, in.file_off[f1], in.file_off[f1 + 1], normalize != 0, h, lo, hi, w);
-            uint64_t covered = 0;
+            file_r0.push_back(r0);
+            d2g_interval_sweep(in, in.file_off[f], in.file_off[f + 1], normalize != 0, h, lo, hi, w);
+            covered = 0;
             for (size_t r = r0; r < h.size(); ++r) covered += hi[r] - lo[r];       // <= the file's positions <= 2^44
-            if (set_off.back() + covered > budget) {
-                if (f1 == f0) {
-                    char msg[256];
-                    std::snprintf(msg, sizeof msg, "--multiset interval lists of one file need %llu bytes of device memory (16 per covered position), %llu are free",
-                                  (unsigned long long)(covered * 16), (unsigned long long)free_b);
-                    ctx->last_error = msg;
-                    return D2G_ERR_NOMEM;
-                }
-                h.resize(r0); lo.resize(r0); hi.resize(r0); w.resize(r0);          // the next group takes it
-                break;
-            }
+            return covered;
+        });
+        if (f1 == f0) {
+            char msg[256];
+            if (list_positions)
+                std::snprintf(msg, sizeof msg, "--multiset interval lists of one file need %llu bytes of device memory (16 per covered position), D2G_INTERVAL_LIST_POSITIONS allows %llu",
+                              (unsigned long long)(covered * 16), (unsigned long long)(budget * 16));
+            else
+                std::snprintf(msg, sizeof msg, "--multiset interval lists of one file need %llu bytes of device memory (16 per covered position), %llu are free",
+                              (unsigned long long)(covered * 16), (unsigned long long)free_b);
+            ctx->last_error = msg;
+            return D2G_ERR_NOMEM;
+        }
+        const size_t ng = f1 - f0;
+        if (file_r0.size() > ng) { const size_t r0 = file_r0[ng]; h.resize(r0); lo.resize(r0); hi.resize(r0); w.resize(r0); }   // the next group takes it
+        file_r0.resize(ng);
+        file_r0.push_back(h.size());                                               // file g of the group owns runs [file_r0[g], file_r0[g + 1])
+        for (size_t g = 0; g < ng; ++g) {
             double t = 0.;
-            for (size_t r = r0; r < h.size(); ++r) {
+            for (size_t r = file_r0[g]; r < file_r0[g + 1]; ++r) {
                 run_off.push_back(run_off.back() + (hi[r] - lo[r]));
                 t += w[r] * (double)(hi[r] - lo[r]);
             }
             tw.push_back(t);
-            set_off.push_back(set_off.back() + covered);
+            set_off.push_back(run_off.back());
         }
-        const size_t ng = f1 - f0, nruns = h.size();
+        const size_t nruns = h.size();
         const uint64_t total = set_off.back();
         D2G_CHECK(ctx, nruns < (1ull << 32), "too many runs in one group of files");
         if (total) {

@@ -31,7 +31,6 @@ constexpr int KNN_THREADS = 256, KNN_WAVES = KNN_THREADS / 64;
 constexpr int KNN_UNROLL = 4;                               // loads of a row in flight per lane: one workgroup per row and a few hundred rows per band leave the latency to the lane
 constexpr uint32_t KNN_HIST_S = 4096;                       // sketch sizes up to this take the LDS histogram (16 KB), larger ones the bisection
 constexpr size_t KNN_BAND_BYTES = (size_t)64 << 20;         // default band: well inside the 256 MB memory-side cache
-constexpr size_t KNN_CHUNK_SLOTS = (size_t)1 << 24;         // d2g_cmp_set_knn: candidate slots per chunk of rows (2 x 64 MB on the device)
 
 struct KnnArgs {
     const uint32_t *band;       // [rows of this launch][N] equality counts
@@ -248,7 +247,8 @@ int d2g_cmp_set_knn(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, 
     const size_t widest = std::max<size_t>(N - 1, 1);
     if (!cap) cap = K ? std::max(2 * K, K + 32) : 64;
     cap = std::min(cap, widest);
-    const size_t chunk = std::min(rows, std::max<size_t>(1, KNN_CHUNK_SLOTS / cap));
+    const size_t slots = ctx->limits.knn_chunk_slots;          // KNN_CHUNK_SLOTS (d2g_limits.h) unless D2G_KNN_CHUNK_SLOTS shrinks it
+    const size_t chunk = std::min(rows, std::max<size_t>(1, slots / cap));
     d2g_dev<uint32_t> d_cls, d_cnt, d_ids, d_cts, d_ids2, d_cts2;
     int rc;
     if ((rc = d_cls.alloc(ctx, S + 1, "knn class table alloc")) || (rc = d_cnt.alloc(ctx, chunk, "knn row counts alloc")) ||
@@ -283,7 +283,7 @@ int d2g_cmp_set_knn(d2g_ctx *ctx, const d2g_cmp_set *set, size_t r0, size_t r1, 
                 if ((rc = append(h_cnt.data() + i, h_ids.data() + i * cap, h_cts.data() + i * cap, e - i, cap))) return rc;
             } else {                                         // a run of rows that did not: once more, with a cap that fits them
                 size_t cap2 = 0;
-                while (e < n && h_cnt[e] > cap && (e - i + 1) * std::max<size_t>(cap2, h_cnt[e]) <= std::max<size_t>(KNN_CHUNK_SLOTS, h_cnt[i])) { cap2 = std::max<size_t>(cap2, h_cnt[e]); ++e; }
+                while (e < n && h_cnt[e] > cap && (e - i + 1) * std::max<size_t>(cap2, h_cnt[e]) <= std::max<size_t>(slots, h_cnt[i])) { cap2 = std::max<size_t>(cap2, h_cnt[e]); ++e; }
                 const size_t m = e - i;
                 if ((rc = d_ids2.grow(ctx, m * cap2, 0, "knn candidates alloc")) || (rc = d_cts2.grow(ctx, m * cap2, 0, "knn candidates alloc"))) return rc;
                 if ((rc = d2g_cmp_knn_dev(ctx, set, c0 + i, c0 + e, K, min_count, K ? d_cls.get() : nullptr, cap2, d_cnt, d_ids2, d_cts2, band_rows, nullptr))) return rc;

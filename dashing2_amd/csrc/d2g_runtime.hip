@@ -16,6 +16,7 @@ static const char *const kTuningNames[] = {
     "D2G_K3S_RANGE_KEYS", "D2G_KSET_SPLIT", "D2G_KSET_PBITS",
     "D2G_CS_TABLE_BYTES", "D2G_CS_LDS_CELLS",
     "D2G_EDIT_STRIP", "D2G_EDIT_TILE", "D2G_EDIT_NEAR_ROUTE", "D2G_EDIT_DEDUP_ROUTE", "D2G_EDIT_DEDUP_REVERSE",
+    "D2G_KNN_CHUNK_SLOTS", "D2G_EDIT_KNN_CHUNK_SLOTS", "D2G_INTERVAL_LIST_POSITIONS", "D2G_SCREEN_RESULT_PAIRS", "D2G_EDIT_GRID_MAX", "D2G_EDIT_DEDUP_CHUNK", "D2G_EDIT_DEDUP_MAX_CHUNKS",
 };
 void d2g_tuning_load(d2g_tuning &t) {
     t.kv.clear();
@@ -79,6 +80,7 @@ void d2g_tuning_resolve(d2g_ctx *c) {
     if (const char *e = c->tune.get("D2G_EDIT_NEAR_ROUTE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) c->edit.near_route = v; }
     if (const char *e = c->tune.get("D2G_EDIT_DEDUP_ROUTE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) c->edit.dedup_route = v; }
     if (const char *e = c->tune.get("D2G_EDIT_DEDUP_REVERSE")) c->edit.dedup_reverse = std::atoi(e) != 0;
+    c->limits = d2g_limits_tuning_resolve(c->tune);
     c->mgpu_chunks = 0;
     if (const char *e = c->tune.get("D2G_MGPU_CHUNKS")) { const int v = std::atoi(e); if (v >= 1 && v <= MG_MAX_CHUNKS) c->mgpu_chunks = v; }
 }
@@ -102,7 +104,16 @@ int d2g_ctx_tuning(const d2g_ctx *c, char *buf, size_t cap) {
         j += "\"";
     }
     // ... and what the switches that select K2's kernels and thresholds RESOLVED to, set or not (the bench line's `tuning` names the defaults)
-    j += std::string(c->tune.kv.empty() ? "" : ", ") + "\"resolved\": " + d2g_k2_tuning_json(c);
+    // ... and to the limits of d2g_limits.h (tests compute a loop's piece count from them)
+    std::string res = d2g_k2_tuning_json(c);
+    const d2g_limits_tuning &l = c->limits;
+    char lb[512];
+    std::snprintf(lb, sizeof lb, ", \"D2G_KNN_CHUNK_SLOTS\": %zu, \"D2G_EDIT_KNN_CHUNK_SLOTS\": %zu, \"D2G_INTERVAL_LIST_POSITIONS\": %llu, \"D2G_SCREEN_RESULT_PAIRS\": %llu, "
+                  "\"D2G_EDIT_GRID_MAX\": %u, \"D2G_EDIT_DEDUP_CHUNK\": %u, \"D2G_EDIT_DEDUP_MAX_CHUNKS\": %u}",
+                  l.knn_chunk_slots, l.edit_knn_chunk_slots, (unsigned long long)l.interval_list_positions, (unsigned long long)l.screen_result_pairs,
+                  l.edit_grid_max, l.edit_dedup_chunk, l.edit_dedup_max_chunks);
+    res.replace(res.rfind('}'), 1, lb);
+    j += std::string(c->tune.kv.empty() ? "" : ", ") + "\"resolved\": " + res;
     j += "}";
     if (buf && cap) { std::snprintf(buf, cap, "%s", j.c_str()); }
     return (int)j.size();

@@ -306,8 +306,8 @@ int d2g_screen_result(d2g_ctx *ctx, const d2g_screen *sc, size_t row0, size_t nr
     D2G_CHECK(ctx, matches_out && matchsums_out, "null output");
     D2G_HIP(ctx, hipSetDevice(ctx->device));
     D2G_HIP(ctx, hipDeviceSynchronize());                           // a count walk may be in flight on any stream
-    // whole rows per launch, at most 2^30 waves each
-    const uint64_t rows_per = std::max<uint64_t>(1, std::min<uint64_t>(nrows, (1ull << 30) / sc->nrefs));
+    // whole rows per launch, at most 2^30 waves each (SCREEN_RESULT_PAIRS unless D2G_SCREEN_RESULT_PAIRS shrinks it)
+    const uint64_t rows_per = std::max<uint64_t>(1, std::min<uint64_t>(nrows, ctx->limits.screen_result_pairs / sc->nrefs));
     d2g_dev<uint32_t> d_res;
     if (int rc = d_res.alloc(ctx, 2 * rows_per * sc->nrefs, "screen result")) return rc;
     for (uint64_t r = 0; r < nrows; r += rows_per) {

@@ -3,7 +3,10 @@
 //   2. d2g_bed_parse on hand-made lines: the reference's rules (bedsketch.cpp:36-46) case by case, and its three refusals
 //   3. d2g_interval_plan_build: every position of every line in exactly one chunk of one workgroup of its file; the refusals
 //   4. d2g_interval_sweep against a map filled line by line, bit for bit, with and without --normalize-intervals
+//   5. d2g_interval_group, the cut of --multiset's files into groups under a budget of covered positions: budgets around one file,
+//      files that cover nothing at every place of a group, the file no group can hold
 #include "../d2g_intervals.h"
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -216,9 +219,75 @@ static int check_sweep() {
     return 0;
 }
 
+// the groups of files that cover `cov` positions each under `budget`, cut as d2g_interval_bmh_sketch cuts them: -> 0, and the
+// boundaries [0, ..., n] in `cut`; -> 1 + f where file f alone is over the budget (cut: the groups before it).  Every file must be
+// asked about once per group that looks at it, in order, and the last one asked is the one that ends the group.
+static size_t groups(const std::vector<uint64_t> &cov, uint64_t budget, std::vector<size_t> &cut, bool *order_ok) {
+    cut.assign(1, 0);
+    *order_ok = true;
+    for (size_t f0 = 0; f0 < cov.size();) {
+        size_t next = f0;
+        const size_t f1 = d2g_interval_group(f0, cov.size(), budget, [&](size_t f) { *order_ok = *order_ok && f == next; ++next; return cov[f]; });
+        *order_ok = *order_ok && f1 <= cov.size() && next == std::min(f1 + 1, cov.size());
+        if (f1 == f0) return 1 + f0;
+        cut.push_back(f1);
+        f0 = f1;
+    }
+    return 0;
+}
+
+static int check_groups() {
+    using V = std::vector<size_t>;
+    std::vector<size_t> cut;
+    bool ok = false;
+    const std::vector<uint64_t> three{5, 7, 5};
+    REQUIRE(groups(three, 17, cut, &ok) == 0 && ok && cut == V({0, 3}));                   // everything fits: one group
+    REQUIRE(groups(three, 16, cut, &ok) == 0 && ok && cut == V({0, 2, 3}));
+    REQUIRE(groups(three, 12, cut, &ok) == 0 && ok && cut == V({0, 2, 3}));                // exactly two files
+    REQUIRE(groups(three, 11, cut, &ok) == 0 && ok && cut == V({0, 1, 2, 3}));             // one position short of two
+    REQUIRE(groups(three, 7, cut, &ok) == 0 && ok && cut == V({0, 1, 2, 3}));              // exactly the largest file: it passes, alone
+    REQUIRE(groups(three, 6, cut, &ok) == 2 && ok && cut == V({0, 1}));                    // one position short of it: file 1 fits no group
+    REQUIRE(groups(three, 4, cut, &ok) == 1 && ok && cut == V({0}));                       // below every file
+    REQUIRE(groups(three, 0, cut, &ok) == 1 && ok);
+    REQUIRE(groups({}, 5, cut, &ok) == 0 && ok && cut == V({0}));
+    // files that cover nothing: first, last, on both sides of a border; they never open a group of their own behind a full one
+    const std::vector<uint64_t> holes{0, 4, 0, 0, 4, 0};
+    REQUIRE(groups(holes, 8, cut, &ok) == 0 && ok && cut == V({0, 6}));
+    REQUIRE(groups(holes, 4, cut, &ok) == 0 && ok && cut == V({0, 4, 6}));                 // the empty files at the border ride with the group in front
+    REQUIRE(groups(holes, 7, cut, &ok) == 0 && ok && cut == V({0, 4, 6}));
+    REQUIRE(groups(holes, 3, cut, &ok) == 2 && ok && cut == V({0, 1}));                    // the empty first file is a group; the next file fits none
+    REQUIRE(groups({0, 0, 0}, 0, cut, &ok) == 0 && ok && cut == V({0, 3}));                // nothing to hold: any budget does
+    REQUIRE(groups({0, 9}, 8, cut, &ok) == 2 && ok && cut == V({0, 1}));
+    // positions near the top of the range: no wrap-around lets a file in
+    const uint64_t big = 1ull << 63;
+    REQUIRE(groups({big, big, 1}, ~0ull, cut, &ok) == 0 && ok && cut == V({0, 1, 3}));
+    REQUIRE(groups({big, big}, big - 1, cut, &ok) == 1 && ok);
+    // random files against the rule stated from the groups' side: a group holds at most the budget, and the file behind it would not fit
+    std::mt19937_64 rng(11);
+    for (int it = 0; it < 2000; ++it) {
+        std::vector<uint64_t> cov(rng() % 12);
+        uint64_t most = 0;
+        for (auto &c : cov) { c = rng() % 4 ? rng() % 20 : 0; most = std::max(most, c); }
+        const uint64_t budget = most + rng() % 25;
+        REQUIRE(groups(cov, budget, cut, &ok) == 0 && ok && cut.back() == cov.size());
+        for (size_t g = 0; g + 1 < cut.size(); ++g) {
+            REQUIRE(cut[g] < cut[g + 1]);
+            uint64_t sum = 0;
+            for (size_t f = cut[g]; f < cut[g + 1]; ++f) sum += cov[f];
+            REQUIRE(sum <= budget && (cut[g + 1] == cov.size() || sum + cov[cut[g + 1]] > budget));
+        }
+        if (most) {
+            const size_t first = std::find(cov.begin(), cov.end(), most) - cov.begin();
+            const size_t bad = groups(cov, most - 1, cut, &ok);
+            REQUIRE(ok && bad == 1 + first);
+        }
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { std::fprintf(stderr, "usage: bed_selftest <tests/golden/xxh3_names.json>\n"); return 2; }
-    if (check_golden(argv[1]) || check_parse() || check_plan() || check_sweep()) return 1;
+    if (check_golden(argv[1]) || check_parse() || check_plan() || check_sweep() || check_groups()) return 1;
     std::printf("bed selftest OK\n");
     return 0;
 }

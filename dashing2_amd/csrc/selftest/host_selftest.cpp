@@ -5,6 +5,7 @@
 // Also the sketch side's input checks and launch plan (d2g_plan.cpp): the grid arithmetic whose indices the kernels trust.
 #include "../../../include/d2g.h"
 #include "../d2g_plan.h"
+#include "../d2g_limits.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -164,8 +165,77 @@ static int plan_selftest() {
     return 0;
 }
 
+// the limits that cut a large call into pieces (d2g_limits.h): unset, every one is the production constant; a switch takes a whole
+// number of its range and nothing else
+static int limits_selftest() {
+    auto with = [](std::initializer_list<std::pair<const char *, const char *>> kv) {
+        d2g_tuning t;
+        for (const auto &p : kv) t.kv.emplace_back(p.first, p.second);
+        return d2g_limits_tuning_resolve(t);
+    };
+    auto same = [](const d2g_limits_tuning &a, const d2g_limits_tuning &b) {
+        return a.knn_chunk_slots == b.knn_chunk_slots && a.edit_knn_chunk_slots == b.edit_knn_chunk_slots &&
+               a.interval_list_positions == b.interval_list_positions && a.screen_result_pairs == b.screen_result_pairs &&
+               a.edit_grid_max == b.edit_grid_max && a.edit_dedup_chunk == b.edit_dedup_chunk && a.edit_dedup_max_chunks == b.edit_dedup_max_chunks;
+    };
+    const d2g_limits_tuning def = with({});
+    REQUIRE(def.knn_chunk_slots == ((size_t)1 << 24) && def.knn_chunk_slots == KNN_CHUNK_SLOTS);
+    REQUIRE(def.edit_knn_chunk_slots == ((size_t)1 << 24) && def.edit_knn_chunk_slots == NEAR_CHUNK_SLOTS);
+    REQUIRE(def.interval_list_positions == 0);                      // 0: a third of the free device memory, asked per group
+    REQUIRE(def.screen_result_pairs == (1ull << 30));
+    REQUIRE(def.edit_grid_max == 0x7fffffffu);
+    REQUIRE(def.edit_dedup_chunk == 1024 && def.edit_dedup_chunk == EDD_CHUNK && def.edit_dedup_max_chunks == 1024 && EDD_MAX_CHUNKS == 1024);
+    REQUIRE(same(def, d2g_limits_tuning()));
+    static const char *const names[] = {"D2G_KNN_CHUNK_SLOTS", "D2G_EDIT_KNN_CHUNK_SLOTS", "D2G_INTERVAL_LIST_POSITIONS", "D2G_SCREEN_RESULT_PAIRS",
+                                        "D2G_EDIT_GRID_MAX", "D2G_EDIT_DEDUP_CHUNK", "D2G_EDIT_DEDUP_MAX_CHUNKS"};
+    // not a whole number, below the range, beyond 64 bits: the default, whichever switch
+    for (const char *n : names)
+        for (const char *bad : {"", "0", "-1", "-256", "+4", " 4", "4 ", "1e3", "0x100", "12x", "x", "1.5", "18446744073709551616", "99999999999999999999999"})
+            REQUIRE(same(def, with({{n, bad}})));
+    // each switch moves its own limit and no other
+    d2g_limits_tuning v = with({{"D2G_KNN_CHUNK_SLOTS", "1"}}), w = def;
+    w.knn_chunk_slots = 1; REQUIRE(same(v, w));
+    v = with({{"D2G_EDIT_KNN_CHUNK_SLOTS", "500"}}); w = def; w.edit_knn_chunk_slots = 500; REQUIRE(same(v, w));
+    v = with({{"D2G_INTERVAL_LIST_POSITIONS", "1"}}); w = def; w.interval_list_positions = 1; REQUIRE(same(v, w));
+    v = with({{"D2G_SCREEN_RESULT_PAIRS", "7"}}); w = def; w.screen_result_pairs = 7; REQUIRE(same(v, w));
+    v = with({{"D2G_EDIT_GRID_MAX", "5"}}); w = def; w.edit_grid_max = 5; REQUIRE(same(v, w));
+    v = with({{"D2G_EDIT_DEDUP_CHUNK", "256"}}); w = def; w.edit_dedup_chunk = 256; REQUIRE(same(v, w));
+    v = with({{"D2G_EDIT_DEDUP_MAX_CHUNKS", "2"}}); w = def; w.edit_dedup_max_chunks = 2; REQUIRE(same(v, w));
+    // the ends of the ranges
+    REQUIRE(with({{"D2G_KNN_CHUNK_SLOTS", "18446744073709551615"}}).knn_chunk_slots == ~(size_t)0);
+    REQUIRE(with({{"D2G_INTERVAL_LIST_POSITIONS", "1152921504606846975"}}).interval_list_positions == (~0ull) / 16);   // 16 bytes each still fit 64 bits
+    REQUIRE(same(def, with({{"D2G_INTERVAL_LIST_POSITIONS", "1152921504606846976"}})));
+    REQUIRE(with({{"D2G_SCREEN_RESULT_PAIRS", "1073741824"}}).screen_result_pairs == (1ull << 30));
+    REQUIRE(same(def, with({{"D2G_SCREEN_RESULT_PAIRS", "1073741825"}})));                 // never more waves per launch than today
+    REQUIRE(with({{"D2G_EDIT_GRID_MAX", "2147483647"}}).edit_grid_max == 0x7fffffffu);
+    REQUIRE(same(def, with({{"D2G_EDIT_GRID_MAX", "2147483648"}})));
+    REQUIRE(same(def, with({{"D2G_EDIT_GRID_MAX", "4294967297"}})));                       // (not 1 after a narrowing)
+    for (const char *bad : {"255", "257", "1000", "128", "1048832", "4294967552"}) REQUIRE(same(def, with({{"D2G_EDIT_DEDUP_CHUNK", bad}})));
+    REQUIRE(with({{"D2G_EDIT_DEDUP_CHUNK", "1048576"}}).edit_dedup_chunk == (1u << 20));
+    REQUIRE(with({{"D2G_EDIT_DEDUP_MAX_CHUNKS", "1024"}}).edit_dedup_max_chunks == 1024);
+    REQUIRE(same(def, with({{"D2G_EDIT_DEDUP_MAX_CHUNKS", "1025"}})));                     // the scratch holds EDD_MAX_CHUNKS counts
+    // a valid switch beside an invalid one
+    v = with({{"D2G_EDIT_DEDUP_CHUNK", "256"}, {"D2G_EDIT_DEDUP_MAX_CHUNKS", "0"}, {"D2G_EDIT_GRID_MAX", "7"}});
+    w = def; w.edit_dedup_chunk = 256; w.edit_grid_max = 7; REQUIRE(same(v, w));
+    // the compaction's chunk: today's formula without a switch, at most max_chunks workgroups with one, always whole workgroup rounds
+    for (uint32_t N : {1u, 255u, 513u, 1024u, 1025u, 2500u, 1u << 20, (1u << 20) + 1, 3000000u, 0x7fffffffu}) {
+        const uint32_t per = (uint32_t)(((uint64_t)N + 1023) / 1024), today = std::max<uint32_t>(1024, (per + 255) / 256 * 256);
+        REQUIRE(d2g_edit_dedup_chunk(N, def) == today);
+        for (const d2g_limits_tuning &t : {with({{"D2G_EDIT_DEDUP_CHUNK", "256"}}), with({{"D2G_EDIT_DEDUP_CHUNK", "256"}, {"D2G_EDIT_DEDUP_MAX_CHUNKS", "2"}}),
+                                           with({{"D2G_EDIT_DEDUP_CHUNK", "256"}, {"D2G_EDIT_DEDUP_MAX_CHUNKS", "1"}}), with({{"D2G_EDIT_DEDUP_MAX_CHUNKS", "3"}})}) {
+            const uint32_t c = d2g_edit_dedup_chunk(N, t);
+            REQUIRE(c % 256 == 0 && c >= t.edit_dedup_chunk && ((uint64_t)N + c - 1) / c <= t.edit_dedup_max_chunks);
+            REQUIRE(c == t.edit_dedup_chunk || (uint64_t)(c - 256) * t.edit_dedup_max_chunks < N);   // no larger than the cover needs
+        }
+    }
+    REQUIRE(d2g_edit_dedup_chunk(513, with({{"D2G_EDIT_DEDUP_CHUNK", "256"}})) == 256);
+    REQUIRE(d2g_edit_dedup_chunk(513, with({{"D2G_EDIT_DEDUP_CHUNK", "256"}, {"D2G_EDIT_DEDUP_MAX_CHUNKS", "2"}})) == 512);
+    REQUIRE(d2g_edit_dedup_chunk(513, with({{"D2G_EDIT_DEDUP_CHUNK", "256"}, {"D2G_EDIT_DEDUP_MAX_CHUNKS", "1"}})) == 768);
+    return 0;
+}
+
 int main() {
-    if (plan_selftest()) return 1;
+    if (plan_selftest() || limits_selftest()) return 1;
     std::mt19937_64 rng(7);
     // ---- seqpack: messy FASTA / FASTQ, lower case, N runs, short records, CRLF, no trailing newline, every k
     std::string fa;
